@@ -5,7 +5,11 @@ One "step" = the reference's postProcessing hot path on one synthetic 37.0 s int
 in HBM: AcquisitionResult.acquire (32 PRNs, 2 x 1 ms coherent blocks, 29 Doppler bins, fine search)
 -> preRun -> TrackingResult.track (8 channels x 37 000 ms).  BASELINE.json configs[1] + configs[2].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (plus the last step's outputs under DIR
+with --dump-outputs).  The side measurements - CPU baseline, the config-4 search, the rooflines, the many-channel,
+other-sample-type, from-file and concurrent-records legs - run with --full only.
 
 N > 1 runs one process per GPU.  Either the driver starts the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the
@@ -46,15 +50,21 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--ms", type=int, default=37000, help="code periods tracked (default: full config)")
     ap.add_argument("--channels", type=int, default=8, help="tracking channels per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (search results, channel table, tracking series) "
+                         "as DIR/<name>.npy in float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements below (CPU baseline, acq_config4, rooflines, extra legs); "
+                         "a plain run times the headline step only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--many-channels", type=int, default=3072,
-                    help="extra leg at N=1: channels of the many-channel (bandwidth-regime) tracking run, 0 = skip")
+                    help="(--full) extra leg at N=1: channels of the many-channel (bandwidth-regime) tracking run, 0 = skip")
     ap.add_argument("--many-ms", type=int, default=500)
     ap.add_argument("--concurrent", type=int, default=3,
-                    help="extra leg at N=1: this many independent records processed at once on one GPU (0 = skip)")
+                    help="(--full) extra leg at N=1: this many independent records processed at once on one GPU (0 = skip)")
     ap.add_argument("--cpu-trk-ms", type=int, default=1000, help="ms of oracle tracking timed per channel (BASELINE.md 3)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the acq_config4 leg")
-    ap.add_argument("--no-from-file", action="store_true", help="skip the from_file leg (the step from a record file)")
+    ap.add_argument("--no-config4", action="store_true", help="(--full) skip the acq_config4 leg")
+    ap.add_argument("--no-from-file", action="store_true", help="(--full) skip the from_file leg (the step from a record file)")
     ap.add_argument("--eager", action="store_true",
                     help="the host looks at every stage's result before it queues the next (the reference's call sequence "
                          "as written); default at one rank: the three stages queued, one wait")
@@ -323,6 +333,31 @@ def trace_avg_ms(kernel_prefix):
     return best
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, acq, series, names, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed step receives, as float64 .npy files - the search's results
+    (acq_<field>: 32 PRNs), the channel table preRun made (channels_<field>) and the tracking series
+    (trk_<name>: active channels x ms, one file per name in `names`).  The inputs are the seeded default scene, so two builds
+    compare output for output.  When the series would pass `limit`, a fixed seeded sample of the milliseconds is
+    written instead, its indices in trk_ms_index."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"acq_" + f: acq.results[f] for f in ("carrFreq", "codePhase", "peakMetric")}
+    arrays.update({"channels_" + f: acq.channels[f] for f in ("PRN", "acquiredFreq", "codePhase")})
+    n_act, n_series, ms = series.shape
+    assert n_series == len(names), (series.shape, names)
+    room = (limit - sum(np.asarray(a).size for a in arrays.values()) * 8) // (8 * max(1, n_act * n_series + 1))
+    if ms > room:
+        keep = np.sort(np.random.default_rng(20261016).choice(ms, size=int(room), replace=False))
+        series = series[:, :, keep]
+        arrays["trk_ms_index"] = keep
+    for k, name in enumerate(names):
+        arrays["trk_" + name] = series[:, k, :]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -348,7 +383,7 @@ def main():
 
     # The CPU baseline forks worker processes: it runs first, while this process has not loaded the GPU runtime.
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = leg("cpu_baseline", cpu_baseline, pkg, scene, n_code, args, float(rec_len), args.channels, args.ms)
 
     group = rendezvous.HostGroup(rank, world)
@@ -427,10 +462,12 @@ def main():
     per_rank = group.gather({"rank": rank, "device": local, "step_ms": elapsed_own / args.steps * 1e3,
                              "track_kernel_ms": float(np.mean(trk_kernel_ms)), "acquire_ms": float(np.mean(acq_ms)),
                              "peak_gather": gather.name})
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["acq"], last["series"], pkg._native.SERIES)
 
     # ---- BASELINE.json config 4: 32 PRNs x 10 ms non-coherent, PRNs sharded, RCCL gather included ----------
     cfg4 = None
-    if not args.no_config4:
+    if args.full and not args.no_config4:
         sig4 = pkg.DeviceSignal(rec, 0, 20 * n_code)
         reps = 5
 
@@ -513,21 +550,11 @@ def main():
     series = last["series"]
     n_act = series.shape[0]
     acq = last["acq"]
-    start_pos = np.array([acq.channels.codePhase[i] for i in range(n_act)])
-    streamed = float(np.sum(series[:, 0, -1] - start_pos))              # sum over channels of sum blksize
-    b_trk = streamed + n_act * args.ms * 13 * 8.0                       # SURVEY.md section 8(d) B_trk
     k_ms = float(np.mean(trk_kernel_ms))
-    achieved = b_trk / (k_ms * 1e-3) / 1e9
     samples_per_step = float(rec_len)                                   # IF samples of the record one rank consumes
     value = world * samples_per_step * args.steps / elapsed / 1e6
 
     if rank == 0:
-        traffic = pmc_file("_pmc_trk_kernel.json", {"channels": args.channels, "ms": args.ms})
-        chain = pmc_file("_trk_chain.json", {"channels": args.channels, "ms": args.ms})
-        tk = ctx.timing()
-        trk_name = {2: "trk2_kernel", 3: "trk_kernel_tp", 4: "trk_kernel_multi", 5: "trk3_kernel"}.get(tk.get("track_kernel"), "trk2_kernel")
-        prof_avg = trace_avg_ms(trk_name) if (args.channels, args.ms) == (8, 37000) else None
-        read_gbs, copy_gbs = ctx.stream_rates(1 << 30, 5)
         out = {
             "metric": "IF Msamples/s through acquisition + tracking (x real-time = value / 38.192)",
             "value": value, "unit": "Msamples/s", "x_realtime": value / REALTIME_MSPS,
@@ -549,52 +576,63 @@ def main():
             "per_rank": {k: {"min": min(r[k] for r in per_rank), "max": max(r[k] for r in per_rank)}
                          for k in ("step_ms", "track_kernel_ms", "acquire_ms")},
             "per_rank_peak_gather": sorted(set(r["peak_gather"] for r in per_rank)),
-            "roofline": {"kernel": trk_name, "bound": "latency", "bound_note": "frac is still the HBM fraction north_star asks "
-                         "for; the kernel is bound by the latency of its per-block chain (limited_by)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic[0]["hbm_bytes_per_launch"] if traffic else None,
-                         "traffic_source": (traffic[1] + " (rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE passes of this "
-                                            "command; FETCH_SIZE x2, gfx950 correction)") if traffic else None,
-                         "algorithmic_bytes_per_launch": b_trk,
-                         "kernel_avg_ms": k_ms, "kernel_avg_ms_profile": prof_avg[0] if prof_avg else None,
-                         "kernel_avg_ms_profile_source": prof_avg[1] if prof_avg else None,
-                         "measured_stream_read_gbs": read_gbs, "measured_stream_copy_gbs": copy_gbs,
-                         "frac_of_measured_read": achieved / read_gbs,
-                         "workgroups_per_channel": tk.get("track_members"),
-                         # WHY the fraction is what it is: the per-block dependency chain in shader cycles (SGX_TRK_PROFILE
-                         # phase times of the committed run) and how busy the occupied CUs' vector ALUs are (PMC passes)
-                         "limited_by": "latency of the per-block chain, not bandwidth",
-                         "chain_cycles": ({k: chain[0][k] for k in ("final_pass", "exchange", "loop_filter", "block") if k in chain[0]}
-                                          if chain else None),
-                         "chain_cycles_source": chain[1] if chain else None,
-                         "valu_busy_frac_on_the_occupied_cus": traffic[0].get("valu_busy_frac_on_the_occupied_cus") if traffic else None,
-                         "occupied_cus": traffic[0].get("occupied_cus") if traffic else None,
-                         "valu_insts_per_sample": traffic[0].get("valu_insts_per_sample") if traffic else None,
-                         "note": "37 000 dependent steps per channel; %d channels x %d workgroups on as many of the 256 CUs, "
-                                 "each on a latency-bound chain (final pass -> exchange -> loop filter): not bandwidth-bound "
-                                 "(DESIGN.md section 4.1)" % (args.channels, tk.get("track_members", 0))},
         }
-        if cfg4 is not None:
-            out["acq_config4"] = cfg4
-        out["roofline_acq"] = leg("roofline_acq", acq_roofline, pkg, ctx, s, signal, local, n_code)
-        if world == 1 and args.many_channels > 0:
-            out["roofline_many_channels"] = leg("roofline_many_channels", many_channels_leg, pkg, ctx, rec, acq, args,
-                                                read_gbs, n_code)
-        if world == 1 and args.many_channels > 0:
-            out["many_channels_other_types"] = leg("many_channels_other_types", many_typed_leg, pkg, ctx, rec, acq, n_code,
-                                                   1024, min(300, max(20, args.ms - 20)))
-        if world == 1 and args.many_channels > 0:
-            out["float_records"] = leg("float_records", float_records_leg, pkg, ctx, rec, acq, n_code,
-                                       min(2000, max(20, args.ms - 20)))
-        if world == 1 and not args.no_from_file:
-            out["from_file"] = leg("from_file", from_file_leg, pkg, ctx, s, rec, rec_len, n_code, local, args, series,
-                                   elapsed / args.steps * 1e3)
-        if world == 1 and args.concurrent > 1:
-            out["concurrent_records"] = leg("concurrent_records", concurrent_records, pkg, s, scene, rec_len, n_code,
-                                            local, args)
-        if cpu is not None:
-            out["cpu_baseline"] = cpu
+        if args.full:
+            start_pos = np.array([acq.channels.codePhase[i] for i in range(n_act)])
+            streamed = float(np.sum(series[:, 0, -1] - start_pos))              # sum over channels of sum blksize
+            b_trk = streamed + n_act * args.ms * 13 * 8.0                       # SURVEY.md section 8(d) B_trk
+            achieved = b_trk / (k_ms * 1e-3) / 1e9
+            traffic = pmc_file("_pmc_trk_kernel.json", {"channels": args.channels, "ms": args.ms})
+            chain = pmc_file("_trk_chain.json", {"channels": args.channels, "ms": args.ms})
+            tk = ctx.timing()
+            trk_name = {2: "trk2_kernel", 3: "trk_kernel_tp", 4: "trk_kernel_multi", 5: "trk3_kernel"}.get(tk.get("track_kernel"), "trk2_kernel")
+            prof_avg = trace_avg_ms(trk_name) if (args.channels, args.ms) == (8, 37000) else None
+            read_gbs, copy_gbs = ctx.stream_rates(1 << 30, 5)
+            out["roofline"] = {"kernel": trk_name, "bound": "latency", "bound_note": "frac is still the HBM fraction north_star asks "
+                               "for; the kernel is bound by the latency of its per-block chain (limited_by)",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic[0]["hbm_bytes_per_launch"] if traffic else None,
+                               "traffic_source": (traffic[1] + " (rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE passes of this "
+                                                  "command; FETCH_SIZE x2, gfx950 correction)") if traffic else None,
+                               "algorithmic_bytes_per_launch": b_trk,
+                               "kernel_avg_ms": k_ms, "kernel_avg_ms_profile": prof_avg[0] if prof_avg else None,
+                               "kernel_avg_ms_profile_source": prof_avg[1] if prof_avg else None,
+                               "measured_stream_read_gbs": read_gbs, "measured_stream_copy_gbs": copy_gbs,
+                               "frac_of_measured_read": achieved / read_gbs,
+                               "workgroups_per_channel": tk.get("track_members"),
+                               # WHY the fraction is what it is: the per-block dependency chain in shader cycles (SGX_TRK_PROFILE
+                               # phase times of the committed run) and how busy the occupied CUs' vector ALUs are (PMC passes)
+                               "limited_by": "latency of the per-block chain, not bandwidth",
+                               "chain_cycles": ({k: chain[0][k] for k in ("final_pass", "exchange", "loop_filter", "block") if k in chain[0]}
+                                                if chain else None),
+                               "chain_cycles_source": chain[1] if chain else None,
+                               "valu_busy_frac_on_the_occupied_cus": traffic[0].get("valu_busy_frac_on_the_occupied_cus") if traffic else None,
+                               "occupied_cus": traffic[0].get("occupied_cus") if traffic else None,
+                               "valu_insts_per_sample": traffic[0].get("valu_insts_per_sample") if traffic else None,
+                               "note": "37 000 dependent steps per channel; %d channels x %d workgroups on as many of the 256 CUs, "
+                                       "each on a latency-bound chain (final pass -> exchange -> loop filter): not bandwidth-bound "
+                                       "(DESIGN.md section 4.1)" % (args.channels, tk.get("track_members", 0))}
+            if cfg4 is not None:
+                out["acq_config4"] = cfg4
+            out["roofline_acq"] = leg("roofline_acq", acq_roofline, pkg, ctx, s, signal, local, n_code)
+            if world == 1 and args.many_channels > 0:
+                out["roofline_many_channels"] = leg("roofline_many_channels", many_channels_leg, pkg, ctx, rec, acq, args,
+                                                    read_gbs, n_code)
+            if world == 1 and args.many_channels > 0:
+                out["many_channels_other_types"] = leg("many_channels_other_types", many_typed_leg, pkg, ctx, rec, acq, n_code,
+                                                       1024, min(300, max(20, args.ms - 20)))
+            if world == 1 and args.many_channels > 0:
+                out["float_records"] = leg("float_records", float_records_leg, pkg, ctx, rec, acq, n_code,
+                                           min(2000, max(20, args.ms - 20)))
+            if world == 1 and not args.no_from_file:
+                out["from_file"] = leg("from_file", from_file_leg, pkg, ctx, s, rec, rec_len, n_code, local, args, series,
+                                       elapsed / args.steps * 1e3)
+            if world == 1 and args.concurrent > 1:
+                out["concurrent_records"] = leg("concurrent_records", concurrent_records, pkg, s, scene, rec_len, n_code,
+                                                local, args)
+            if cpu is not None:
+                out["cpu_baseline"] = cpu
         print(json.dumps(out))
         sys.stdout.flush()
     group.barrier()

@@ -122,4 +122,6 @@ class _NoRccl(object):
 
 
 _native = types.SimpleNamespace(device_count=lambda: int(os.environ.get("SGX_STUB_DEVICES", "2")),
-                                pinned_empty=lambda shape, dtype=np.float64: np.empty(shape, dtype=dtype), Comm=_NoRccl)
+                                pinned_empty=lambda shape, dtype=np.float64: np.empty(shape, dtype=dtype), Comm=_NoRccl,
+                                SERIES=("absoluteSample", "codeFreq", "carrFreq", "I_P", "I_E", "I_L", "Q_E", "Q_P", "Q_L",
+                                        "dllDiscr", "dllDiscrFilt", "pllDiscr", "pllDiscrFilt"))

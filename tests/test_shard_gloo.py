@@ -92,7 +92,9 @@ def _worker(rank, world, port, q):
 
 
 def test_peak_gather_world_size_2_gloo():
-    import torch.multiprocessing as mp
+    # torch is imported in the spawned ranks only: torch loads its own copies of the HIP and HSA runtimes, and a test
+    # process that has libsgx's runtime up on a GPU must not hold two of them
+    import multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -258,7 +260,7 @@ def test_bench_two_ranks_end_to_end_against_a_stand_in_package():
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--ms", "50", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--ms", "50", "--no-cpu-baseline", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        env=_stub_env(), timeout=300)
     assert r.returncode == 0, r.stderr.decode()
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -279,6 +281,55 @@ def test_bench_two_ranks_end_to_end_against_a_stand_in_package():
                         timeout=300)
     assert r1.returncode == 0, r1.stderr.decode()
     assert json.loads([ln for ln in r1.stdout.decode().splitlines() if ln.startswith("{")][0])["n_gpus"] == 1
+
+
+def test_bench_plain_run_times_the_step_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` (no --full) with tests/bench_stub.py answering for the GPU package: the JSON line holds the
+    headline figures and none of the side measurements, --steps sets the timed steps, and --dump-outputs writes the
+    last step's search results, channel table and tracking series as float64 .npy files, the same on every run.  A
+    series larger than the limit is written as a fixed sample of its milliseconds."""
+    import importlib.util
+    import json
+    import subprocess
+    import types
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ms", "50",
+                            "--dump-outputs", str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=_stub_env(),
+                           timeout=300)
+        assert r.returncode == 0, r.stderr.decode()
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["n_gpus"] == 1 and line["ms_per_step"] > 0
+        assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["value"] == pytest.approx(line["config"]["record_samples"] / (line["ms_per_step"] * 1e-3) / 1e6)
+        assert not set(line) & {"roofline", "acq_config4", "roofline_acq", "roofline_many_channels", "from_file",
+                                "concurrent_records", "cpu_baseline", "float_records", "many_channels_other_types"}
+        dumps.append({f.name: np.load(str(f)) for f in d.iterdir()})
+    got = dumps[0]
+    assert sum(a.nbytes for a in got.values()) <= 64 * 10 ** 6
+    assert all(f.endswith(".npy") for f in got) and all(a.dtype == np.float64 for a in got.values())
+    assert got["acq_codePhase.npy"].shape == (32,) and got["channels_PRN.npy"].shape == (8,)
+    assert got["trk_absoluteSample.npy"].shape == (int(np.sum(got["channels_PRN.npy"] != 0)), 50)
+    assert len([f for f in got if f.startswith("trk_")]) == 13
+    assert set(dumps[1]) == set(got) and all(np.array_equal(dumps[1][f], got[f]) for f in got)
+    # the limit: a seeded sample of the milliseconds, the same every time, its indices written beside it
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    acq = types.SimpleNamespace(results=np.rec.fromarrays([np.arange(32.0)] * 3, names="carrFreq,codePhase,peakMetric"),
+                                channels=np.rec.fromarrays([np.arange(1, 9), np.ones(8), np.zeros(8)],
+                                                           names="PRN,acquiredFreq,codePhase"))
+    series = np.arange(8 * 3 * 1000, dtype=np.float64).reshape(8, 3, 1000)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / ("small%d" % k)), acq, series, ("a", "b", "c"), limit=64 * 1024)
+    a, b = (np.load(str(tmp_path / ("small%d" % k) / "trk_b.npy")) for k in range(2))
+    idx = np.load(str(tmp_path / "small0" / "trk_ms_index.npy"))
+    total = sum(os.path.getsize(str(f)) for f in (tmp_path / "small0").iterdir())
+    assert 0 < a.shape[1] == idx.size < 1000 and np.array_equal(a, b) and np.array_equal(a, series[:, 1, idx.astype(int)])
+    assert total <= 64 * 1024 + 128 * len(list((tmp_path / "small0").iterdir()))   # (.npy headers on top)
 
 
 def test_bench_launcher_stops_the_other_ranks_when_one_dies():

@@ -1,6 +1,7 @@
 #!/bin/bash
 # (diagnosis) the headline step, the many-channel leg and the from-file leg of bench.py, key figures only.  GPU box.
 cd "$(dirname "$0")/.."
+set -- --full "$@"   # (the many-channel and from-file legs run with --full only)
 mkdir -p gpurun_out/legs
 python bench.py --no-cpu-baseline --concurrent 0 --no-config4 "$@" > gpurun_out/legs/bench.json 2> gpurun_out/legs/bench.err
 python - <<'PY'

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Instruction-mix counters of the two tracking kernels (separate --pmc passes, kernel trace only).
-# Usage (GPU box): bash tools/pmc_valu.sh   -> gpurun_out/pmc_valu.txt
+# Usage (GPU box): bash tools/pmc_valu.sh OUT_DIR   -> OUT_DIR/pmc_valu.txt
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/pmc_valu_*
+out=${1:?usage: bash tools/pmc_valu.sh OUT_DIR}
+mkdir -p "$out" && rm -rf "$out"/pmc_valu_*
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES" \
            "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_CVT" \
@@ -10,11 +11,11 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES" \
            "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_FLAT SQ_INSTS_VALU_FLOPS_FP64" \
            "GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES"; do
     i=$((i+1))
-    rocprofv3 --pmc $set --kernel-trace -d gpurun_out/pmc_valu_$i -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --concurrent 0 --many-channels 2048 --many-ms 200 > /dev/null 2> gpurun_out/pmc_valu_$i.err || echo "pass $i failed"
+    rocprofv3 --pmc $set --kernel-trace -d "$out/pmc_valu_$i" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --concurrent 0 --many-channels 2048 --many-ms 200 > /dev/null 2> "$out/pmc_valu_$i.err" || echo "pass $i failed"
 done
-python3 - <<'PY' | tee gpurun_out/pmc_valu.txt
-import glob, sqlite3
-for db in sorted(glob.glob("gpurun_out/pmc_valu_*/*/*_results.db")):
+python3 - "$out" <<'PY' | tee "$out/pmc_valu.txt"
+import glob, os, sqlite3, sys
+for db in sorted(glob.glob(os.path.join(sys.argv[1], "pmc_valu_*", "*", "*_results.db"))):
     c = sqlite3.connect(db)
     try:
         rows = list(c.execute("select kernel_name, counter_name, sum(value), count(*) from counters_collection "

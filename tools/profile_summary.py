@@ -41,7 +41,7 @@ def main():
     # ---- kernel trace ----
     rows = top_kernels(db_of(os.path.join(out, "trace")))
     with open(os.path.join(dst, "%s_kernel_trace_stats.csv" % tag), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --concurrent 0 "
+        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --concurrent 0 "
                 "--many-channels 0 (the headline command alone; the CPU leg forks and is left out under the profiler)\n")
         f.write("kernel,calls,total_us,average_us,percent\n")
         for n, calls, tot, avg, pct in rows:
@@ -51,7 +51,7 @@ def main():
     write = by_kernel(per_dispatch(db_of(os.path.join(out, "write")), "WRITE_SIZE"))
     with open(os.path.join(dst, "%s_pmc_hbm.csv" % tag), "w") as f:
         f.write("# separate passes: rocprofv3 --pmc FETCH_SIZE --kernel-trace / --pmc WRITE_SIZE --kernel-trace -- python3 bench.py "
-                "--steps 1 --warmup 0 --no-cpu-baseline --concurrent 0 --no-config4; raw counter unit = KiB, per kernel: dispatches, sum, largest dispatch\n")
+                "--full --steps 1 --warmup 0 --no-cpu-baseline --concurrent 0 --no-config4; raw counter unit = KiB, per kernel: dispatches, sum, largest dispatch\n")
         f.write("counter,kernel,dispatches,raw_sum_KiB,raw_max_KiB\n")
         for name, d in (("FETCH_SIZE", fetch), ("WRITE_SIZE", write)):
             for k, v in sorted(d.items(), key=lambda t: -sum(t[1])):
