@@ -304,6 +304,31 @@ int sgx_find_preambles(sgx_ctx* c, const double* I_P, int32_t n_ch, int32_t ms, 
  * flips d1..d24 in place when D30* != 1 like the reference; status +1 / -1 (parity ok) or 0. */
 int sgx_nav_parity_check(double* ndat32, int32_t* status);
 
+/* ---- C/N0 estimate and lock detector on the tracking output (the reference's hook at tracking.py:276-278) ----------
+ * Channel c's prompt series are I_P[c*row_stride + k], Q_P[c*row_stride + k] for k < ms_done[c] (ms_done NULL: ms).
+ * Over non-overlapping windows of W = p->window ms (window j covers k = jW .. jW+W-1, j < n_c = ms_done[c] / W; a
+ * trailing partial window is dropped), in fp64:
+ *   R = sum(I^2 - Q^2), X = sum(2 I Q), P = sum(I^2 + Q^2), phi = atan2(X, R) / 2, A = sum |I cos phi + Q sin phi|
+ *   cno[c][j] = 10 log10(Psig / ((Ptot - Psig) T)) dB-Hz with Psig = (A/W)^2, Ptot = P/W   (NaN for P = 0, -inf for
+ *               Psig = 0 < P, +inf for Ptot - Psig <= 0 < Psig)
+ *   carr_lock[c][j] = R / sqrt(R^2 + X^2) = cos 2 phi   (NaN for R = X = 0)
+ *   pass[c][j] = cno >= cno_min and carr_lock >= carr_lock_min (a NaN fails)
+ * lost[c] = the first j at which the counter f (0; fail: f + 1, pass: max(f - 1, 0)) reaches max_fail, else -1.
+ * Windows j >= n_c hold NaN, NaN, 0 and are not counted.  cno, carr_lock, pass are [n_ch][ms / W]; the inputs are any
+ * host memory (the [n][13][ms] series of sgx_track_ex: row_stride = 13 ms, pointers to rows 3 and 7).
+ * SGX_E_ARG for window < 2 or > ms, max_fail < 1, T not finite or <= 0, row_stride < ms, an ms_done entry outside
+ * [0, ms] or a NULL pointer; nothing is launched then.  tests/lock_spec.py restates all of it in numpy. */
+typedef struct sgx_lock_params {
+    double T;               /* s per ms-rate sample: codeLength / codeFreqBasis */
+    double cno_min;         /* dB-Hz */
+    double carr_lock_min;
+    int32_t window;         /* W, ms */
+    int32_t max_fail;
+} sgx_lock_params;          /* 32 bytes */
+int sgx_track_quality(sgx_ctx* c, const double* I_P, const double* Q_P, int64_t row_stride, int32_t n_ch, int32_t ms,
+                      const int32_t* ms_done, const sgx_lock_params* p, double* cno, double* carr_lock, uint8_t* pass,
+                      int32_t* lost);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -59,6 +59,12 @@ class Timing(C.Structure):
                 ("track_members", C.c_float), ("track_streamed", C.c_float)]
 
 
+class LockParams(C.Structure):
+    """sgx_lock_params: the C/N0 and lock-detector parameters of sgx_track_quality (32 bytes)."""
+    _fields_ = [("T", C.c_double), ("cno_min", C.c_double), ("carr_lock_min", C.c_double), ("window", C.c_int32),
+                ("max_fail", C.c_int32)]
+
+
 # every symbol include/sgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PROTOS = {
@@ -102,6 +108,8 @@ _PROTOS = {
     "sgx_probe_stats": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, _P, _P, _P, C.POINTER(C.c_int32)]),
     "sgx_find_preambles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sgx_nav_parity_check": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "sgx_track_quality": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(LockParams), _P, _P, _P,
+                                    _P]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -268,6 +276,23 @@ def pinned_empty(shape, dtype=np.float64):
     buf._owner = own                       # ctypes object keeps the owner, numpy keeps the ctypes object
     weakref.finalize(buf, _pinned_release, own)   # every view of the array holds `buf` through .base
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
+
+
+def lock_params(settings):
+    """LockParams from Settings' lock-detector attributes (cnoInterval, cnoThreshold, carrLockThreshold, maxLockFail)."""
+    return LockParams(float(settings.codeLength) / float(settings.codeFreqBasis), float(settings.cnoThreshold),
+                      float(settings.carrLockThreshold), int(round(float(settings.cnoInterval))),
+                      int(settings.maxLockFail))
+
+
+def _rows(a):
+    """(array, row stride in elements) of a 2-D float64 array whose rows are contiguous; copies anything else."""
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("expected a [channels, ms] array, got shape %r" % (a.shape,))
+    if a.dtype != np.float64 or a.strides[1] != 8 or a.strides[0] % 8 or a.strides[0] < 8 * a.shape[1]:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+    return a, (a.strides[0] // 8 if a.shape[0] > 1 else a.shape[1])
 
 
 def device_count():
@@ -469,6 +494,31 @@ class Context(object):
             raise (IndexError if msg.startswith("IndexError") else ValueError)(msg)
         check(rc)
         return out.astype(int)
+
+    def track_quality(self, i_p, q_p, params, ms_done=None):
+        """C/N0 and lock detector of sgx_track_quality.  i_p, q_p: float64[n_ch, ms] - views with contiguous rows such as
+        series[:, 3] and series[:, 7] of track() are passed as they lie; params: LockParams; ms_done: int[n_ch] or None.
+        Returns (cno[n_ch, ms // W], carr_lock[n_ch, ms // W], pass bool[n_ch, ms // W], lost window int32[n_ch])."""
+        a, sa = _rows(i_p)
+        b, sb = _rows(q_p)
+        if a.shape != b.shape:
+            raise ValueError("I_P %r and Q_P %r differ in shape" % (a.shape, b.shape))
+        if sa != sb:
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+            sa = a.shape[1]
+        n, ms = a.shape
+        nw = ms // max(int(params.window), 1)
+        cno = np.empty((n, nw))
+        cl = np.empty((n, nw))
+        ok = np.empty((n, nw), dtype=np.uint8)
+        lost = np.empty(n, dtype=np.int32)
+        done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
+        if done is not None and done.shape != (n,):
+            raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+        check(lib().sgx_track_quality(self._h, _ptr(a), _ptr(b), int(sa), int(n), int(ms),
+                                      None if done is None else _ptr(done), C.byref(params), _ptr(cno), _ptr(cl),
+                                      _ptr(ok), _ptr(lost)))
+        return cno, cl, ok.astype(bool), lost
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

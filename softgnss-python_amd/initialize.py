@@ -79,6 +79,16 @@ _DEFAULTS = (
     ("navSolPeriod", 500.0), ("elevationMask", 10.0), ("useTropCorr", True), ("plotTracking", True),
 )
 
+# the lock detector the reference leaves as a hook (tracking.py:276-278): TrackingResult.quality and, with lockDetector,
+# status '-' for every channel it declares lost ("C/N0 and lock detector")
+_LOCK_DEFAULTS = (
+    ("lockDetector", False),        # run it inside track() and mark lost channels '-'
+    ("cnoInterval", 20.0),          # ms per C/N0 window
+    ("cnoThreshold", 25.0),         # dB-Hz a window must reach to pass
+    ("carrLockThreshold", 0.85),    # cos(2 phi) a window must reach to pass
+    ("maxLockFail", 25),            # the fail counter (fail +1, pass -1, not below 0) at which a channel is lost
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -87,7 +97,7 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -218,6 +228,8 @@ class Settings(object):
             trackResults.track(fid)
             self.lastTrackingSeconds = (datetime.datetime.now() - start).total_seconds()
             print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
+            if self.lockDetector and trackResults.has_results():
+                trackResults.showTrackingQuality()
         if not trackResults.has_results():   # (the reference's short-read exit: results were not set, tracking.py:159-163)
             return acqResults, trackResults, None
         print('   Calculating navigation solutions...')

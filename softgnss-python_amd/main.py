@@ -1,8 +1,10 @@
 """The reference's main.py (banner, probeData, postProcessing) for this engine:
 
     python -m softgnss-python_amd.main record.bin [--fs 38192000 --IF 9548000 --ms 37000 --channels 8 --skip 0]
+                                                  [--lock-detector]
 
-Prints the channel table, the tracking time and, when the record is long enough (36 s, four satellites with
+Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
+was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
 ephemerides), the mean position fix."""
 from __future__ import print_function
 
@@ -22,12 +24,14 @@ def main(argv=None):
     ap.add_argument("--channels", type=int, default=None, help="numberOfChannels")
     ap.add_argument("--skip", type=int, default=None, help="skipNumberOfBytes")
     ap.add_argument("--no-probe", action="store_true", help="skip the raw-data statistics")
+    ap.add_argument("--lock-detector", action="store_true",
+                    help="estimate C/N0 per channel, print it after tracking and drop the channels lost on the way")
     a = ap.parse_args(argv)
     print('\nWelcome to:  softGNSS on MI355X\n')
     settings = initialize.Settings()
     settings.fileName = a.fileName
     for name, val in (("samplingFreq", a.fs), ("IF", a.IF), ("msToProcess", a.ms), ("numberOfChannels", a.channels),
-                      ("skipNumberOfBytes", a.skip)):
+                      ("skipNumberOfBytes", a.skip), ("lockDetector", True if a.lock_detector else None)):
         if val is not None:
             setattr(settings, name, val)
     if not a.no_probe:

@@ -19,6 +19,8 @@ RESULT_DTYPE = [('status', 'S1'), ('absoluteSample', 'object'), ('codeFreq', 'ob
                 ('Q_E', 'object'), ('Q_P', 'object'), ('Q_L', 'object'), ('dllDiscr', 'object'),
                 ('dllDiscrFilt', 'object'), ('pllDiscr', 'object'), ('pllDiscrFilt', 'object'),
                 ('PRN', 'int64')]   # reference tracking.py:285-293
+QUALITY_DTYPE = [('PRN', 'int64'), ('CNo', 'object'), ('carrLock', 'object'), ('lockPass', 'object'),
+                 ('lostAtMs', 'int64'), ('medianCNo', 'float64')]
 
 
 class TrackingResult(Result):
@@ -36,6 +38,10 @@ class TrackingResult(Result):
         self.chained = False        # the last track() ran preRun on the device behind a deferred acquisition
         self.series = None          # float64[n_active, 13, ms] in _native.SERIES order
         self.kernel_ms = None       # HIP-event duration of the tracking kernel
+        self._quality = None        # .quality, computed on first access (sgx_track_quality)
+        self._lost_rows = ()        # rows of .results the lock detector declared lost inside track() (status '-')
+        self._active = []           # channel numbers of the rows of .series
+        self._assigned = False      # .results was assigned (the reference's cache path): .quality reads it, not .series
 
     def has_results(self):
         """False after the reference's short-read exit (tracking.py:159-163 leaves the results unset) and before track()."""
@@ -55,7 +61,79 @@ class TrackingResult(Result):
                 res[j].PRN = int(channel[i].PRN)
                 for k, name in enumerate(_native.SERIES):
                     res[j][name] = series[j, k]
+            for j in self._lost_rows:
+                res[j].status = '-'
             self._results = res
+
+    @property
+    def results(self):
+        return Result.results.fget(self)
+
+    @results.setter
+    def results(self, records):
+        Result.results.fset(self, records)
+        self._quality = None
+        self._assigned = True
+
+    @property
+    def quality(self):
+        """C/N0 and lock detector per tracked channel (sgx_track_quality on I_P / Q_P; formulas in INTEGRATION.md):
+        a recarray with one row per record of .results - PRN, CNo and carrLock (float64 per cnoInterval window),
+        lockPass (bool per window), lostAtMs ((lost window + 1) x cnoInterval, or -1) and medianCNo (median of the
+        finite CNo before the loss).  Computed on first access; a new track() starts afresh."""
+        if self._quality is None:
+            self._quality = self._compute_quality()
+        return self._quality
+
+    def _compute_quality(self):
+        settings = self._settings
+        params = _native.lock_params(settings)
+        if self.series is not None and not self._assigned:
+            i_p, q_p = self.series[:, 3], self.series[:, 7]      # rows of the [n, 13, ms] array, passed as they lie
+            prn = [int(self._channels[i].PRN) for i in self._active]
+        else:
+            res = self.results
+            i_p = np.stack([np.asarray(r, dtype=np.float64) for r in res.I_P]) if len(res) else np.empty((0, 0))
+            q_p = np.stack([np.asarray(r, dtype=np.float64) for r in res.Q_P]) if len(res) else np.empty((0, 0))
+            prn = [int(p) for p in res.PRN]
+        q = np.recarray((len(prn),), dtype=QUALITY_DTYPE)
+        if not len(prn):
+            return q
+        ctx = engine.get_context(settings, self._device)
+        cno, carr, ok, lost = ctx.track_quality(i_p, q_p, params)
+        W = params.window
+        for j in range(len(prn)):
+            q[j].PRN = prn[j]
+            q[j].CNo = cno[j]
+            q[j].carrLock = carr[j]
+            q[j].lockPass = ok[j]
+            q[j].lostAtMs = (int(lost[j]) + 1) * W if lost[j] >= 0 else -1
+            before = cno[j, :lost[j]] if lost[j] >= 0 else cno[j]
+            before = before[np.isfinite(before)]
+            q[j].medianCNo = float(np.median(before)) if before.size else np.nan
+        return q
+
+    def showTrackingQuality(self):
+        """ASCII table of .quality, in the manner of AcquisitionResult.showChannelStatus."""
+        q = self.quality
+        bar = '*=========*=====*=============*===============*============*'
+        print('\n' + bar)
+        print('| Channel | PRN | C/N0 dB-Hz  | carrier lock  |  Lost at   |')
+        print(bar)
+        for j, r in enumerate(q):
+            lock = np.asarray(r.carrLock, dtype=np.float64)
+            if r.lostAtMs >= 0:                                   # the windows before the loss, as for medianCNo
+                lock = lock[:r.lostAtMs // int(round(float(self._settings.cnoInterval))) - 1]
+            lock = lock[np.isfinite(lock)]
+            print('|      %2d | %3d |   %7.2f   |    %6.3f     | %s |' % (
+                j, int(r.PRN), r.medianCNo, float(np.median(lock)) if lock.size else np.nan,
+                ('%7d ms' % r.lostAtMs) if r.lostAtMs >= 0 else '      --  '))
+        print(bar + '\n')
+
+    def _detect_locks(self):
+        """lockDetector: the quality right after tracking, and status '-' for every channel it declares lost."""
+        if getattr(self._settings, "lockDetector", False) and self.has_results():
+            self._lost_rows = tuple(int(j) for j in np.flatnonzero(self.quality.lostAtMs >= 0))
 
     def _data_type(self):
         """Settings.dataType -> (sgx_track_ex data_type, bytes per sample).  The reference reads np.fromfile(fid,
@@ -109,7 +187,12 @@ class TrackingResult(Result):
         self._results = None
         self.series = None
         self.chained = False
+        self._quality = None
+        self._lost_rows = ()
+        self._assigned = False
+        self._active = []
         if self._channels is None and self._try_chained(fid, ctx, nch, ms):
+            self._detect_locks()
             return
         if self._channels is None:
             self._channels = self._acq.channels   # (the queued sequence did not apply: the search is looked at, preRun runs here)
@@ -155,6 +238,8 @@ class TrackingResult(Result):
         fid.seek(int(series[-1, 0, ms - 1]), 0)    # where the reference's last read left the file
         self.series = series
         self._lazy = (series, active)              # the record array of object fields is packed on first access of .results
+        self._active = active
+        self._detect_locks()
         return
 
     def _try_chained(self, fid, ctx, nch, ms):
@@ -190,6 +275,7 @@ class TrackingResult(Result):
         fid.seek(int(series[-1, 0, ms - 1]), 0)
         self.series = series
         self._lazy = (series, list(range(n_act)))
+        self._active = list(range(n_act))
         return True
 
     def plot(self):
