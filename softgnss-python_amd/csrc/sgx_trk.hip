@@ -83,7 +83,7 @@ __global__ __launch_bounds__(SGX_TRK_LOOK_CH) void trk_finish_kernel(const int* 
     if (t == 0) __hip_atomic_store(&look->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// THE SPECULATIVE KERNEL'S SCALE GUARD for resident int8 records (sgx_trk3.hip: a unit's total must stay below 2^17, and no
+// THE SPECULATIVE KERNEL'S SCALE GUARD for int8 records read resident (sgx_trk3.hip: a unit's total must stay below 2^17, and no
 // arm's total can exceed the sum of the unit's magnitudes).  One pass over the record, once per record (cached in the
 // handle): the largest sum of |x| over 17 consecutive 128-byte blocks - any 2 048-byte window of the kernel lies inside
 // such a run - by workgroups of 256 blocks with a halo of 16.  1.4 GB in ~0.4 ms; a streaming record that is not resident
@@ -121,10 +121,11 @@ __global__ __launch_bounds__(256) void if_mag_kernel(const int8_t* __restrict__ 
 }
 
 // -> the bound (cached in the handle), or -1 when the record is not fully resident yet / on an error
+// (resident: every copy has completed - host_mark reaches the end a moment before the loader thread sets load_done)
 static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
     long long known = r->mag_max.load();
     if (known >= 0) return known;
-    if (r->loader && !r->load_done.load()) return -1;
+    if (r->loader && !r->load_done.load() && r->host_mark.load() < r->n) return -1;
     int* d_max = (int*)((char*)c->d_small + 730000);
     if (hipMemsetAsync(d_max, 0, sizeof(int), c->stream) != hipSuccess) return -1;
     const long long n_blocks128 = ((long long)r->n + 127) / 128;
@@ -432,15 +433,6 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     // straight to the caller's pinned buffer and the channels fit the page
     const bool fast_look = direct && n_ch <= SGX_TRK_LOOK_CH && !want_prof;
     const TrkLook* h_look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
-    if (use_v3 && kind == SGX_DT_INT8 && !(r->loader && !r->load_done.load())) {
-        // (resident int8 record: the scale guard is a bound computed once per record; sgx_trk3.hip says why 2^17)
-        const long long mag = if_mag_bound(c, r);
-        if (mag >= 131072) {
-            fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add up "
-                            "to 131 072 or more in magnitude); the round-3 kernel tracks this record\n");
-            v3_off = true;
-        }
-    }
     int used_members = 0;
     hipError_t e = hipSuccess;
     int h_err = 0;
@@ -451,6 +443,29 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     // speculative kernel's fixed point is repeated with the round-3 kernel: at most four launches, each repeat said on stderr.
     if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
     for (int launches = 0; launches < 4; ++launches) {
+        // a record that is still streaming in is followed by the latency-mode kernel (its record wave watches the
+        // device watermark); the other kernels, and a launch repeated on the resident record, first wait for all of it
+        const char* se2 = getenv("SGX_TRK_STREAM");
+        const bool v2 = use_v2;
+        const bool want_stream = r->loader && !r->load_done.load() && launches == 0 && !(se2 && se2[0] == '0') && v2;
+        if (use_v3 && kind == SGX_DT_INT8 && !fallback_one && !v3_off && !want_stream) {
+            // THE SCALE GUARD of every speculative launch that does not stream (sgx_trk3.hip says why 2^17; a streaming
+            // launch has its record wave's): the whole record, then a bound computed once per record.  Before the kernel
+            // is chosen - and its CUs reserved -, and whatever the record was when this call began: still loading
+            // (SGX_TRK_STREAM=0, a repeat after a stalled stream) or resident
+            const int rq = sgx_if_require(r, r->n);
+            if (rq != SGX_OK) return rq;
+            const long long mag = if_mag_bound(c, r);
+            if (mag < 0) {
+                sgx_set_error("tracking: the magnitude scan of the record failed");
+                return SGX_E_HIP;
+            }
+            if (mag >= 131072) {
+                fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add "
+                                "up to 131 072 or more in magnitude); the round-3 kernel tracks this record\n");
+                v3_off = true;
+            }
+        }
         if (!chained) {
             SGX_HIP(hipMemcpyAsync(d_ch, hc.data(), sizeof(TrkChan) * (size_t)n_ch, hipMemcpyHostToDevice, st));
         } else if (launches == 0) {
@@ -462,11 +477,6 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         SGX_HIP(hipMemsetAsync(aux + sz_ch, 0, sz_done + sz_xch + 256, st));   // done, every polled word, err
         stamp("memset queued");
         if (!direct) trk_fill_kernel<<<(unsigned)((elems + 255) / 256), 256, 0, st>>>(d_out, ms, (long long)elems);
-        // a record that is still streaming in is followed by the latency-mode kernel (its record wave watches the
-        // device watermark); the other kernels, and a launch repeated on the resident record, first wait for all of it
-        const char* se2 = getenv("SGX_TRK_STREAM");
-        const bool v2 = use_v2;
-        const bool want_stream = r->loader && !r->load_done.load() && launches == 0 && !(se2 && se2[0] == '0') && v2;
         K.split = fallback_one ? 1 : split0;                     // a member timed out: no co-residency needed with one
         K.n_units = n_units2;
         bool v3 = use_v3 && !fallback_one && !v3_off;

@@ -83,9 +83,9 @@
 // looked at the units' prompt payloads only, which have already WRAPPED when a total passes 1.5 x 2^17): any arm's sum over
 // samples is at most the sum of their magnitudes - every sample enters once, with a chip of +-1 and a phasor of modulus 1 -
 // so while the 2 048 bytes of a unit's window add up to less than 2^17 in magnitude (a mean of 64 of the 127 an int8 sample
-// can reach: a record that clips all the time), no arm of the unit can reach 2^17.  A resident record is scanned ONCE by the
-// host side (sgx_trk.hip: if_mag_bound, cached in the record's handle; a record beyond the bound goes to sgx_trk2.hip, said
-// on stderr); a record that is still streaming in is watched by the RECORD wave, block by block (v_sad_u8 on two 16-byte
+// can reach: a record that clips all the time), no arm of the unit can reach 2^17.  A launch that does not stream reads a
+// record the host side has scanned ONCE (sgx_trk.hip: if_mag_bound, cached in the record's handle; a record beyond the bound
+// goes to sgx_trk2.hip, said on stderr); a launch that follows a record still streaming in has it watched by the RECORD wave, block by block (v_sad_u8 on two 16-byte
 // loads per lane, a DPP reduction: it has the time; the map waves have none), and flags TRK_ERR_SCALE: the host repeats the
 // launch with sgx_trk2.hip and says so.  Offset-binary records (uint8, read as they lie: a DC of 128 that the correlation
 // cancels but a magnitude bound cannot) keep the round-5 guard: the units' prompt payloads beyond HALF the room, seen by the
@@ -1700,7 +1700,10 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
             // sgx_trk.hip: if_mag_bound): the magnitudes of the unit's 2 048 bytes of THIS block (its aligned window: an
             // L2 hit, the map waves read them two blocks ago) - signed bytes as |(b ^ 0x80) - 0x80| by v_sad_u8, a DPP
             // reduction into lane 63.  On this wave because it has the time: the speculative pass has none to spare (15
-            // instructions more in its part B: 42.8 -> 44.9 ms; here, for every record: + 0.17 ms).
+            // instructions more in its part B: 42.8 -> 44.9 ms; here, for every record: + 0.17 ms).  The window is EXACTLY
+            // the bytes the unit's map lanes load (t3_map_role: group g = lane + 128 unit reads (pos & ~15) + 16 g), and
+            // every sample the unit adds lies in it; the up to 15 bytes in front of pos (and any behind the block's end)
+            // are loaded but masked, so here they only make the bound larger, never smaller.
             long long a = (C.pos & ~15ll) + (long long)unit * T3_UNIT + 32ll * lane;
             const long long top = limit - 16;
             a = a < 0 ? 0 : (a > top ? top : a);

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, pkg, scene_from_json
+from full_scale import clean_record as _clean_record
 from oracle import softgnss_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -2027,17 +2028,6 @@ def test_deferred_search_raises_the_references_index_error_at_the_first_look():
     with pytest.raises(IndexError):
         t.track(m.DeviceFile(rec))                                 # the device found no channel table to make: the look raises
     rec.free()
-
-
-def _clean_record(m, s, amp, n_ms, prn=5, doppler=1250.0, start=7000):
-    """A NOISELESS one-satellite record: round(amp * chip * cos(carrier)) - every sample lines up with the replica."""
-    n = s.samplesPerCode
-    N = (n_ms + 2) * (n + 2)
-    t = np.arange(N, dtype=np.float64)
-    code = np.asarray(s.generateCAcode(prn - 1))
-    chip = code[(np.floor((t - start) * (s.codeFreqBasis / s.samplingFreq)).astype(np.int64)) % 1023]
-    x = np.rint(amp * chip * np.cos(2 * np.pi * ((s.IF + doppler) / s.samplingFreq) * t + 0.3))
-    return x.astype(np.int64)
 
 
 def test_a_record_too_strong_for_the_speculative_kernel_is_tracked_by_the_round_3_kernel(capfd):
