@@ -73,6 +73,14 @@ struct sgx_if {
 };
 // Block until samples [0, end) of a (possibly still streaming) record are resident; returns the loader's status.
 int sgx_if_require(const sgx_if* r, size_t end);
+// Tracking (sgx_trk.hip).  kind: SGX_DT_*.  int8 / uint8 / int16 run the typed kernels (sgx_trk2 / sgx_trk3 / sgx_trk_tp);
+// every other type - and int16 / uint8 at sampling rates below 16 x the chip rate - the per-sample kernel of sgx_trk_any.hip.
+// skip_bytes: Settings.skipNumberOfBytes, or what stands in for it (sgx_trk_f32.hip tracks a narrowed copy of a window).
+// fscale > 0 (float32 / float64 only): every sample the channels can reach is finite and at most 128 / fscale in magnitude
+// (sgx_trk_f32.hip has scanned the window; fscale is a power of two) - the record then runs the latency-mode kernel, which
+// scales the samples by it on conversion; the correlator series are scaled back.  0: the per-sample kernel.
+int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
+                   int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale);
 // float32 records by exact narrowing to int8 / int16 (sgx_trk_f32.hip)
 int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
                       double* out, int32_t* ms_done);

@@ -4,56 +4,13 @@
 // previous block's six correlator sums.  Channels are independent.  Every kernel is persistent: one launch walks all
 // code periods of all channels.  A block (~38 192 samples) is cut into UNITS of 256 groups x 16 samples (4 KiB of IF).
 //
-// Three kernels, chosen here:
-//   trk2_kernel     (sgx_trk2.hip) - the latency-mode kernel, every cooperative case and its own fallback: P members per
-//                   channel, member m owns units m, m + P, ...  P = units (one workgroup per unit - or, when three times
-//                   as many CUs are free, one per unit and correlator arm) while the CUs last, fewer members with
-//                   several units each for more channels, P = 1 (no co-residency needed) when a cooperative launch
-//                   timed out or the CUs are taken.  int8 and int16 records, resident or still streaming in.
-//   trk_kernel_tp   (sgx_trk_tp.hip) - throughput mode: more than 128 int8 channels, one workgroup per channel.
-//   trk_kernel_multi (sgx_trk_multi.hip) - sampling rates below ~15.4 samples per chip, where a 16-sample group can hold
-//                   several chip switches of one ramp (per-sample replica lookup; the round-1 cooperative body).
+// Which kernel runs, with how many workgroups per channel: the table in front of trk_plan below; what a repeated launch
+// runs: trk_launch_step.  The launchers and the layout the host sizes are declared in sgx_trk_common.h.
 // fp64 everywhere: 1e-7 errors in the sums move the code NCO enough to flip a chip-boundary sample somewhere in a 37 s
 // run, which is a 1e-3 relative blip.
+#include <algorithm>
 #include <chrono>
 #include "sgx_trk_common.h"
-
-// sgx_trk_tp.hip: throughput-mode kernel (one lane per prompt chip, two workgroups per CU) for split == 1, > 128 channels
-void sgx_trk_tp_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const void* chans,
-                       double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
-
-// sgx_trk2.hip: the latency-mode kernel (one unit per member - or, arms = 1, one unit and one correlator arm per
-// member -, tagged-granule exchange, dedicated filter waves)
-void sgx_trk2_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
-                     double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
-                     int sample_bytes, int arms, int lds_pad);
-#define T2_MAXP 16
-#ifndef T2_XLINE
-#define T2_XLINE 16
-#endif
-#define T2_XCH_STRIDE (((12 * T2_XLINE + 8 + 48) + 255) / 256 * 256)   // (as in sgx_trk2.hip)
-#define T2_PROF_STRIDE 192
-
-// sgx_trk3.hip: the speculative latency-mode kernel (round 4): one workgroup per unit of 128 groups serves all three
-// correlator arms, the map runs one block ahead of the loop filter and only corrections are on the per-block chain
-void sgx_trk3_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
-                     double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
-                     int lds_pad);
-#define T3_LANES 128
-#define T3_MAXP 32
-#ifndef T3_XCH_STRIDE
-#define T3_XCH_STRIDE 512   // (as in sgx_trk3.hip)
-#endif
-
-// sgx_trk_multi.hip: the cooperative kernel with a per-sample replica lookup, for low sampling rates
-void sgx_trk_multi_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
-                          double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch,
-                          int* err);
-
-// sgx_trk_any.hip: the same body with every sample fetched where it lies, for any sample type (K.kind)
-void sgx_trk_any_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
-                        double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch,
-                        int* err);
 
 // tracking.py:65-94: series start as zeros (absoluteSample, I/Q) or +Inf (the others)
 __global__ __launch_bounds__(256) void trk_fill_kernel(double* __restrict__ out, long long ms, long long total) {
@@ -138,6 +95,37 @@ static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
     return (long long)h;
 }
 
+// The environment a tracking call reads, once at its entry: diagnosis switches and test hooks (sgx_track_plan ignores them)
+struct TrkEnv {
+    bool trace, float_typed, v3_off, fast_xcd, profile, stream, withhold, stall;
+    int split, arms, lds_pad;
+    char timeout;
+};
+
+static TrkEnv trk_env() {
+    auto first = [](const char* name) -> char {   // (0 when unset)
+        const char* v = getenv(name);
+        return v ? v[0] : 0;
+    };
+    const char* split = getenv("SGX_TRK_SPLIT");
+    const char* arms = getenv("SGX_TRK_ARMS");
+    const char* lds = getenv("SGX_TRK_LDSPAD");
+    TrkEnv E;
+    E.trace = first("SGX_STEP_TRACE") == '1';              // host-side time stamps of the call on stderr, us since its entry
+    E.float_typed = first("SGX_TRK_FLOAT_TYPED") != '0';   // '0': float records always on the per-sample kernel
+    E.split = (split && atoi(split) >= 1) ? atoi(split) : 0;
+    E.arms = arms ? (arms[0] == '3' ? 3 : 1) : 0;
+    E.v3_off = first("SGX_TRK_V3") == '0';
+    E.fast_xcd = first("SGX_TRK_FASTX") != '0';            // '0': no same-XCD exchange path
+    E.profile = first("SGX_TRK_PROFILE") == '1';           // the kernels' phase cycles on stderr
+    E.lds_pad = lds ? atoi(lds) : 90112;                   // dynamic LDS per cooperative workgroup; default: one per CU
+    E.stream = first("SGX_TRK_STREAM") != '0';             // '0': never follow a record that is still streaming in
+    E.withhold = first("SGX_TRK_TEST_WITHHOLD") == '1';    // test hooks: launch without each channel's last member; ...
+    E.timeout = first("SGX_TRK_TEST_TIMEOUT");             // ... '1' the first launch times out, '2' the one after a stall;
+    E.stall = first("SGX_TRK_TEST_STALL") == '1';          // ... the first launch's stream stalls
+    return E;
+}
+
 // ---- WHICH KERNEL, HOW MANY MEMBERS: the one rule (include/sgx.h: sgx_track_plan; tests/test_cabi_and_host.py holds the table)
 //
 //   sample type                      channels   samples / chip      spacing   -> kernel                        members per channel
@@ -151,33 +139,35 @@ static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
 //   everything else                                                              2 trk2_kernel                 3 x units (one per unit and arm)
 //                                                                                                              while 3 ch8 units <= CUs and not float,
 //                                                                                                              else min(units, CUs / ch8)
-//   (ch8 = channels rounded up to 8; units = ceil((samplesPerCode + 94) / 16 / 256); a cooperative launch that cannot be
-//   resident, or whose member timed out, is repeated with ONE member per channel by sgx_track_kind)
+//   (ch8 = channels rounded up to 8; units = ceil((samplesPerCode + 94) / 16 / 256); the members are trk_launch_step's for
+//   the first launch with every CU free - a launch whose CUs are taken, or a repeated one, may run fewer)
 struct TrkPlan {
-    int kernel, members;
-    int multi, use_any, use_tp, use_v2, use_v3, arm_split, split, n_units, n_units3;
+    int kernel;          // of the first launch: 2, 3, 4, 5 or 6 (sgx_timing.track_kernel)
+    int ch8, multi, arm_split, split, n_units, n_units3;
 };
 
 // (split_env: SGX_TRK_SPLIT or 0; arms_env: 0 unset, 3 SGX_TRK_ARMS=3, 1 any other value; v3_off: SGX_TRK_V3=0 - diagnostics)
 static TrkPlan trk_plan(const sgx_settings& S, int kind, int n_ch, long long n_code, int cus_total, bool floaty,
                         int split_env = 0, int arms_env = 0, bool v3_off = false) {
     TrkPlan P;
-    const int sample_bytes = sgx_dt_bytes(kind);
     P.multi = (15.0 * 1.001 * S.codeFreqBasis / S.samplingFreq >= 1.0) ? 1 : 0;
     if (P.multi) floaty = false;
     const bool typed = kind == SGX_DT_INT8 || kind == SGX_DT_UINT8 || kind == SGX_DT_INT16 || floaty;
-    P.use_any = (!typed || (P.multi && kind != SGX_DT_INT8)) ? 1 : 0;
-    const int ch8 = ((n_ch + 7) / 8) * 8;
+    const bool use_any = !typed || (P.multi && kind != SGX_DT_INT8);
+    const int ch8 = P.ch8 = ((n_ch + 7) / 8) * 8;
+    // units needed by the longest possible block, worst alignment.  A block is samplesPerCode +- 1 samples long while the
+    // code NCO stays near its basis; the allowance of 64 samples corresponds to a code-rate error of 0.17 % (1.7 kHz at
+    // 1.023 MHz), three orders of magnitude beyond what the DLL's filter can command.
     P.n_units = (int)((n_code + 64 + 15 + 15) / 16 + TRK_THREADS - 1) / TRK_THREADS;
     int split = cus_total / ch8;
     if (split > P.n_units) split = P.n_units;
-    if ((P.multi || P.use_any) && split > TRK_MAX_SPLIT) split = TRK_MAX_SPLIT;
+    if ((P.multi || use_any) && split > TRK_MAX_SPLIT) split = TRK_MAX_SPLIT;
     if (split < 1) split = 1;
     if (split_env >= 1 && split_env <= split) split = split_env;
     P.split = split;
-    P.use_tp = (!P.use_any && !floaty && !P.multi && split == 1 && n_ch > 128) ? 1 : 0;
-    P.use_v2 = (!P.use_any && !P.multi && !P.use_tp) ? 1 : 0;
-    P.arm_split = (P.use_v2 && !floaty && split == P.n_units && P.n_units >= 2 && 3 * ch8 * P.n_units <= cus_total &&
+    const bool use_tp = !use_any && !floaty && !P.multi && split == 1 && n_ch > 128;
+    const bool use_v2 = !use_any && !P.multi && !use_tp;
+    P.arm_split = (use_v2 && !floaty && split == P.n_units && P.n_units >= 2 && 3 * ch8 * P.n_units <= cus_total &&
                    split_env == 0 && arms_env != 3) ? 1 : 0;
     // The speculative kernel (sgx_trk3.hip) serves all three arms from one lane, which rests on a 16-sample group (and one
     // sample on either side of it) meeting at most ONE chip boundary of ANY arm: the arms' boundaries lie at code phases
@@ -186,24 +176,54 @@ static TrkPlan trk_plan(const sgx_settings& S, int kind, int n_ch, long long n_c
     // on the ODD half chips: spacing 1/2 exactly.  int8 / uint8 records, one workgroup per unit of 128 groups, while
     // 8-padded channels x units fit the CUs.
     P.n_units3 = 2 * P.n_units;
-    {
-        const double d = S.dllCorrelatorSpacing, e = 1.0 - d;
-        double pts[3] = {0.0, d < e ? d : e, d < e ? e : d};
-        double gap = 2.0;
-        for (int i = 0; i < 3; ++i) {
-            const double g = (i < 2 ? pts[i + 1] : pts[0] + 1.0) - pts[i];
-            if (g > 1e-9 && g < gap) gap = g;
-        }
-        const double stepn = S.codeFreqBasis / S.samplingFreq;
-        P.use_v3 = (P.use_v2 && sample_bytes == 1 && P.n_units3 >= 2 && P.n_units3 <= T3_MAXP && ch8 * P.n_units3 <= cus_total &&
-                    fabs(d - 0.5) < 1e-12 && 18.0 * stepn * 1.01 <= gap && split_env == 0 && arms_env == 0 && !v3_off) ? 1 : 0;
+    const double d = S.dllCorrelatorSpacing, e = 1.0 - d;
+    double pts[3] = {0.0, d < e ? d : e, d < e ? e : d};
+    double gap = 2.0;
+    for (int i = 0; i < 3; ++i) {
+        const double g = (i < 2 ? pts[i + 1] : pts[0] + 1.0) - pts[i];
+        if (g > 1e-9 && g < gap) gap = g;
     }
-    if (P.use_any) { P.kernel = 6; P.members = split; }
-    else if (P.use_tp) { P.kernel = 3; P.members = 1; }
-    else if (P.use_v3) { P.kernel = 5; P.members = P.n_units3; }
-    else if (P.use_v2) { P.kernel = 2; P.members = (P.arm_split && split > 1) ? 3 * split : split; }
-    else { P.kernel = 4; P.members = split; }
+    const double stepn = S.codeFreqBasis / S.samplingFreq;
+    const bool use_v3 = use_v2 && sgx_dt_bytes(kind) == 1 && P.n_units3 >= 2 && P.n_units3 <= T3_MAXP && ch8 * P.n_units3 <= cus_total &&
+                        fabs(d - 0.5) < 1e-12 && 18.0 * stepn * 1.01 <= gap && split_env == 0 && arms_env == 0 && !v3_off;
+    P.kernel = use_any ? 6 : use_tp ? 3 : use_v3 ? 5 : use_v2 ? 2 : 4;
     return P;
+}
+
+// What the launches of a call have established: each cause of a repeated launch (at most four launches in all)
+struct TrkRepeat {
+    bool stream_stalled = false;   // a streaming record's watermark stalled: the launch was repeated on the resident record
+    bool one_member = false;       // a member of a cooperative layout timed out: one workgroup per channel from then on
+    bool v3_off = false;           // too strong for the speculative kernel's fixed point: the round-3 kernel from then on
+};
+
+// One launch: the kernel that runs (2, 3, 4, 5 or 6), its layout, and the CUs reserved for it
+struct TrkLaunch {
+    int kernel, split, n_units, arms, members, n_blocks, cus;   // (arms, trk2_kernel: 1 a workgroup per unit and arm, 3 per unit)
+};
+
+// THE PER-LAUNCH STEP: the plan's kernel under the repeats so far and the CUs that `reserve(want)` grants (want, or 0).
+// Cooperating workgroups wait for each other, so all of a launch must be resident at once, one workgroup per CU (of a budget
+// all contexts share): trk3 whose CUs are taken runs trk2; one per unit and arm tries one per unit, then one per channel.
+template <class Reserve>
+static TrkLaunch trk_launch_step(const TrkPlan& P, const TrkRepeat& R, Reserve reserve) {
+    TrkLaunch L{P.kernel, R.one_member ? 1 : P.split, P.n_units, 3, 0, 0, 0};
+    if (L.kernel == 5) {
+        if (!R.one_member && !R.v3_off) L.cus = reserve(P.ch8 * P.n_units3);
+        if (L.cus) L.split = L.n_units = P.n_units3;   // (units of half the size: the same room for a code NCO that left its basis)
+        else L.kernel = 2;
+    }
+    if (L.kernel != 5 && L.split > 1) {
+        if (L.kernel == 2 && P.arm_split) {
+            L.cus = reserve(P.ch8 * L.split * 3);
+            L.arms = L.cus ? 1 : 3;
+        }
+        if (!L.cus) L.cus = reserve(P.ch8 * L.split);
+        if (!L.cus) L.split = 1;
+    }
+    L.members = L.arms == 1 ? 3 * L.split : L.split;
+    L.n_blocks = P.ch8 * L.members;
+    return L;
 }
 
 extern "C" int sgx_track_plan(const sgx_settings* s, int32_t data_type, int32_t n_ch, int32_t n_cus, int32_t float_in_range,
@@ -218,49 +238,52 @@ extern "C" int sgx_track_plan(const sgx_settings* s, int32_t data_type, int32_t 
     if (rc != SGX_OK) return rc;
     const bool fl = (data_type == SGX_DT_FLOAT32 || data_type == SGX_DT_FLOAT64) && float_in_range != 0;
     const TrkPlan P = trk_plan(*s, data_type, n_ch, (long long)n_code, n_cus, fl);
-    *kernel = P.kernel;
-    *members = P.members;
+    const TrkLaunch L = trk_launch_step(P, TrkRepeat{}, [&](int want) { return want <= n_cus ? want : 0; });
+    *kernel = L.kernel;
+    *members = L.members;
     return SGX_OK;
 }
 
-// sample_bytes: 1 (int8 record) or 2 (little-endian int16 record; the record handle holds the file's BYTES).  The
-// reference seeks skipNumberOfBytes + codePhase BYTES whatever the sample type and reports fid.tell(), also bytes
-// (tracking.py:107, 255); so a two-byte channel may start on an odd byte - its samples then straddle the file's - and
-// the kernel follows it there (per-channel byte shift of the record pointer, unaligned 16-byte loads).
-// kind: SGX_DT_*.  int8 / uint8 / int16 run the typed kernels (sgx_trk2 / sgx_trk3 / sgx_trk_tp); every other type - and
-// int16 / uint8 at sampling rates below 16 x the chip rate - the per-sample kernel of sgx_trk_any.hip.
-// skip_bytes: Settings.skipNumberOfBytes, or what stands in for it (sgx_trk_f32.hip tracks a narrowed copy of a window).
-// fscale > 0 (float32 / float64 only): every sample the channels can reach is finite and at most 128 / fscale in magnitude
-// (sgx_trk_f32.hip has scanned the window; fscale is a power of two) - the record then runs the latency-mode kernel, which
-// scales the samples by it on conversion; the correlator series are scaled back here.  0: the per-sample kernel.
-// chained (round 6, sgx_track_chained): `ch` is null - the channel table is made ON THE DEVICE by the preRun kernel queued
-// in front of the first launch (sgx_prerun_enqueue, sgx_acq.hip) from the acquisition that is pending on this context.
-static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                           int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale,
-                           bool chained) {
-    SGX_CHECK_ARG(c && r && (ch || chained) && out && ms_done);
-    const int sample_bytes = sgx_dt_bytes(kind);
-    SGX_CHECK_ARG(sample_bytes >= 1);
-    const bool sample_uns = kind == SGX_DT_UINT8;
-    SGX_CHECK_ARG(n_ch >= 1 && n_ch <= 65535 && ms >= 1);
-    if (!(c->s.dllCorrelatorSpacing > 0.0 && c->s.dllCorrelatorSpacing < 1.0)) {
-        // beyond one chip the reference's replica index ceil(t) leaves its 1025-entry code table (or wraps)
-        sgx_set_error("dllCorrelatorSpacing %g outside (0, 1) chips", c->s.dllCorrelatorSpacing);
-        return SGX_E_ARG;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const sgx_settings& S = c->s;
-    // (diagnosis) SGX_STEP_TRACE=1: host-side time stamps of this call on stderr, microseconds since its entry
-    const char* tre = getenv("SGX_STEP_TRACE");
-    const bool trace = tre && tre[0] == '1';
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto stamp = [&](const char* what) {
-        if (trace) fprintf(stderr, "[sgx step trace] %-28s %8.1f us\n", what,
-                           std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count());
-    };
-
+// One tracking call: its arguments, and what the stages below make of them
+struct TrkCall {
+    sgx_ctx* c;
+    const sgx_if* r;
+    const sgx_chan_init* ch;     // null when chained
+    int n_ch, ms, kind, sample_bytes;
+    long long skip_bytes, rec_file_offset;
+    double* out;
+    int32_t* ms_done;
+    bool chained;
+    TrkEnv E;
+    std::chrono::steady_clock::time_point t0;
+    int cus_total;
+    TrkPlan P;
     TrkConst K;
+    std::vector<TrkChan> hc;     // the channel table (not when chained)
+    size_t elems;                // n_ch x SGX_NUM_SERIES x ms
+    double* d_out;               // the series: the caller's pinned buffer itself (direct), or the context's staging buffer
+    bool direct;
+    TrkChan* d_ch;               // the rest is one cached allocation: [channels | done | exchange | err | profile]
+    int* d_done;
+    unsigned long long* d_xch;
+    int* d_err;
+    long long* d_prof;           // SGX_TRK_PROFILE=1 only
+    size_t sz_clear, sz_prof;    // bytes from d_done to the profile (cleared in front of every launch); of the profile
+    bool fast_look;              // error words and ms_done through the pinned page: direct, and the channels fit the page
+    TrkRepeat rep;
+    TrkLaunch L;                 // the last launch ...
+    hipError_t e;                // ... its status (hipSuccess before the first) ...
+    int h_err;                   // ... and its error word: 0, or 1 + the channel that timed out
+    void stamp(const char* what) const {
+        if (E.trace) fprintf(stderr, "[sgx step trace] %-28s %8.1f us\n", what,
+                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    }
+};
+
+// tracking.py:13-64: the constants every kernel reads (each launch sets split, n_units and mark)
+static void trk_const(TrkCall& T) {
+    const sgx_settings& S = T.c->s;
+    TrkConst& K = T.K;
     K.fs = S.samplingFreq;
     K.code_basis = S.codeFreqBasis;
     K.code_len = (double)S.codeLength;
@@ -272,120 +295,80 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     K.k_code_b = 0.001 / t1c;
     K.k_carr_a = t2p / t1p;
     K.k_carr_b = 0.001 / t1p;
-    {
-        const long double two_pi = 2.0L * (long double)M_PI;   // the reference's 2*np.pi (a double)
-        const long double inv = 1.0L / (two_pi * (long double)S.samplingFreq);
-        K.inv_2pifs_hi = (double)inv;
-        K.inv_2pifs_lo = (double)(inv - (long double)K.inv_2pifs_hi);
-        K.inv_2pi = (double)(1.0L / two_pi);
-    }
-    K.rec_len = (long long)r->n;                         // bytes; two-byte samples: the kernel divides (per-channel shift)
-    K.rec_alloc = (long long)r->n + SGX_IF_PAD - (sample_bytes - 1);   // bytes, less the largest per-channel shift
-    K.mark = nullptr;
-    // (a float record the typed kernel can take: in range, no channel starting inside a sample, not switched off)
-    bool floaty = (kind == SGX_DT_FLOAT32 || kind == SGX_DT_FLOAT64) && fscale > 0.0;
-    for (int i = 0; i < n_ch && floaty && !chained; ++i) {
-        // (a channel that starts inside a sample reads other values than the ones that were scanned)
-        const long long p0 = skip_bytes + (long long)ch[i].codePhase - rec_file_offset;
-        if (ch[i].prn != 0 && p0 >= 0 && p0 % sample_bytes != 0) floaty = false;
-    }
-    {
-        const char* fe = getenv("SGX_TRK_FLOAT_TYPED");   // '0': float records always on the per-sample kernel
-        if (fe && fe[0] == '0') floaty = false;
-    }
-    int cus_total = 0;
-    SGX_HIP(hipDeviceGetAttribute(&cus_total, hipDeviceAttributeMultiprocessorCount, c->device));
-    // THE RULE (trk_plan above), with the diagnostic overrides of this process's environment
-    const char* se = getenv("SGX_TRK_SPLIT");
-    const char* ae = getenv("SGX_TRK_ARMS");
-    const char* v3e = getenv("SGX_TRK_V3");
-    const TrkPlan P0 = trk_plan(S, kind, n_ch, (long long)c->n_code, cus_total, floaty, (se && atoi(se) >= 1) ? atoi(se) : 0,
-                                ae ? (ae[0] == '3' ? 3 : 1) : 0, v3e && v3e[0] == '0');
-    K.multi = P0.multi;
-    if (K.multi) floaty = false;
-    K.uns = sample_uns ? 1 : 0;
-    K.kind = kind;
-    K.fscale = floaty ? fscale : 1.0;
-    const bool use_any = P0.use_any != 0;
-    K.file_off = rec_file_offset;
-    K.ms = ms;
-    K.n_ch = n_ch;
-    const int ch8 = ((n_ch + 7) / 8) * 8;
-    {
-        // units needed by the longest possible block, worst alignment.  A block is samplesPerCode +- 1 samples long
-        // while the code NCO stays near its basis; the allowance of 64 samples corresponds to a code-rate error of
-        // 0.17 % (1.7 kHz at 1.023 MHz), three orders of magnitude beyond what the DLL's filter can command.
-        K.n_units = P0.n_units;
-        if (K.n_units > 16) {
-            sgx_set_error("samplesPerCode %lld needs %d units, the tracking kernel holds 16", (long long)c->n_code,
-                          K.n_units);
-            return SGX_E_ARG;
-        }
-        // members (cooperating workgroups) per channel: one workgroup per CU, all of a cooperative launch must be
-        // resident at once (they wait for each other), so members * channels <= CU count
-        K.split = P0.split;
-        const char* fe = getenv("SGX_TRK_FASTX");
-        K.fast_xcd = (fe && fe[0] == '0') ? 0 : 1;
-        K.nb_base = (int)c->n_code - 3;
-        for (int k = 0; k < 8; ++k) K.inv_nb[k] = 1.0 / (double)(K.nb_base + k);
-        K.inv_fs = 1.0 / S.samplingFreq;
-        K.inv_pi = 1.0 / M_PI;
-    }
+    const long double two_pi = 2.0L * (long double)M_PI;   // the reference's 2*np.pi (a double)
+    const long double inv = 1.0L / (two_pi * (long double)S.samplingFreq);
+    K.inv_2pifs_hi = (double)inv;
+    K.inv_2pifs_lo = (double)(inv - (long double)K.inv_2pifs_hi);
+    K.inv_2pi = (double)(1.0L / two_pi);
+    K.rec_len = (long long)T.r->n;                       // bytes; two-byte samples: the kernel divides (per-channel shift)
+    K.rec_alloc = (long long)T.r->n + SGX_IF_PAD - (T.sample_bytes - 1);   // bytes, less the largest per-channel shift
+    K.multi = T.P.multi;
+    K.uns = T.kind == SGX_DT_UINT8 ? 1 : 0;
+    K.kind = T.kind;
+    K.file_off = T.rec_file_offset;
+    K.ms = T.ms;
+    K.n_ch = T.n_ch;
+    K.fast_xcd = T.E.fast_xcd ? 1 : 0;
+    K.nb_base = (int)T.c->n_code - 3;
+    for (int k = 0; k < 8; ++k) K.inv_nb[k] = 1.0 / (double)(K.nb_base + k);
+    K.inv_fs = 1.0 / S.samplingFreq;
+    K.inv_pi = 1.0 / M_PI;
+}
 
-    std::vector<TrkChan> hc((size_t)n_ch);
-    for (int i = 0; i < n_ch && !chained; ++i) {
-        hc[(size_t)i].acquiredFreq = ch[i].acquiredFreq;
-        hc[(size_t)i].prn = ch[i].prn;
-        hc[(size_t)i].pad = 0;
+// The channel table the kernels read (chained: made on the device by preRun instead)
+static int trk_channels(TrkCall& T) {
+    const sgx_chan_init* ch = T.ch;
+    T.hc.resize((size_t)T.n_ch);
+    for (int i = 0; i < T.n_ch && !T.chained; ++i) {
+        TrkChan& h = T.hc[(size_t)i];
+        h.acquiredFreq = ch[i].acquiredFreq;
+        h.prn = ch[i].prn;
         SGX_CHECK_ARG(ch[i].prn >= 0 && ch[i].prn <= 32);
-        const long long p0 = skip_bytes + (long long)ch[i].codePhase - rec_file_offset;
+        const long long p0 = T.skip_bytes + (long long)ch[i].codePhase - T.rec_file_offset;
         if (ch[i].prn != 0 && p0 < 0) {
             sgx_set_error("channel %d starts at file byte %lld, before the record (offset %lld)", i,
-                          skip_bytes + (long long)ch[i].codePhase, (long long)rec_file_offset);
+                          T.skip_bytes + (long long)ch[i].codePhase, (long long)T.rec_file_offset);
             return SGX_E_RANGE;
         }
         // two-byte samples: the channel's own sample grid starts at byte (p0 & 1) of the record
-        hc[(size_t)i].pos0 = p0 / sample_bytes;
-        hc[(size_t)i].pad = (int)(p0 % sample_bytes);
+        h.pos0 = p0 / T.sample_bytes;
+        h.pad = (int)(p0 % T.sample_bytes);
     }
-    const size_t elems = (size_t)n_ch * SGX_NUM_SERIES * (size_t)ms;
-    // If the caller's result buffer is pinned host memory (sgx_host_alloc; the Python binding's is), the kernel's
-    // record stores - 104 bytes per channel per millisecond, issued by an otherwise idle wave - go straight to it
-    // over PCIe: no device staging buffer, no D2H copy and no prefill pass after the kernel.
-    double* d_out = nullptr;
-    bool direct = false;
-    {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer) {
-            d_out = (double*)pa.devicePointer;
-            direct = true;
-        } else {
-            (void)hipGetLastError();   // a pageable pointer is not an error
-        }
-    }
-    if (!direct) {
-        if (c->trk_out_elems < elems) {
+    return SGX_OK;
+}
+
+// If the caller's result buffer is pinned host memory (sgx_host_alloc; the Python binding's is), the kernel's record
+// stores - 104 bytes per channel per millisecond, issued by an otherwise idle wave - go straight to it over PCIe: no device
+// staging buffer, no D2H copy and no prefill pass after the kernel.  The call state is one cached device allocation.
+static int trk_buffers(TrkCall& T) {
+    sgx_ctx* c = T.c;
+    T.elems = (size_t)T.n_ch * SGX_NUM_SERIES * (size_t)T.ms;
+    hipPointerAttribute_t pa;
+    T.direct = hipPointerGetAttributes(&pa, T.out) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer;
+    if (T.direct) {
+        T.d_out = (double*)pa.devicePointer;
+    } else {
+        (void)hipGetLastError();   // a pageable pointer is not an error
+        if (c->trk_out_elems < T.elems) {
             if (c->d_trk_out) hipFree(c->d_trk_out);
             c->d_trk_out = nullptr;
             c->trk_out_elems = 0;
-            hipError_t e = hipMalloc((void**)&c->d_trk_out, elems * sizeof(double));
-            if (e != hipSuccess) {
-                sgx_set_error("hipMalloc of %zu tracking output bytes failed", elems * sizeof(double));
+            if (hipMalloc((void**)&c->d_trk_out, T.elems * sizeof(double)) != hipSuccess) {
+                sgx_set_error("hipMalloc of %zu tracking output bytes failed", T.elems * sizeof(double));
                 return SGX_E_NOMEM;
             }
-            c->trk_out_elems = elems;
+            c->trk_out_elems = T.elems;
         }
-        d_out = c->d_trk_out;
+        T.d_out = c->d_trk_out;
     }
-    // device-side call state lives in one cached allocation: [channels | done | exchange | err | profile]
-    const size_t sz_ch = ((sizeof(TrkChan) * (size_t)n_ch + 255) / 256) * 256;
-    const size_t sz_done = ((sizeof(int) * (size_t)n_ch + 255) / 256) * 256;
-    size_t xch_words = (2 * TRK_MAX_SPLIT * 12 + 16) > T2_XCH_STRIDE ? (2 * TRK_MAX_SPLIT * 12 + 16) : T2_XCH_STRIDE;
-    if (xch_words < T3_XCH_STRIDE) xch_words = T3_XCH_STRIDE;
-    const size_t xch_bytes = sizeof(unsigned long long) * (size_t)n_ch * xch_words;
+    const size_t sz_ch = ((sizeof(TrkChan) * (size_t)T.n_ch + 255) / 256) * 256;
+    const size_t sz_done = ((sizeof(int) * (size_t)T.n_ch + 255) / 256) * 256;
+    const size_t xch_words = std::max({2 * TRK_MAX_SPLIT * 12 + 16, T2_XCH_STRIDE, T3_XCH_STRIDE});
+    const size_t xch_bytes = sizeof(unsigned long long) * (size_t)T.n_ch * xch_words;
     const size_t sz_xch = ((xch_bytes + 255) / 256) * 256;
-    const size_t sz_prof = sizeof(long long) * T2_PROF_STRIDE * (size_t)n_ch;
-    const size_t need = sz_ch + sz_done + sz_xch + 256 + sz_prof;
+    T.sz_clear = sz_done + sz_xch + 256;
+    T.sz_prof = sizeof(long long) * T2_PROF_STRIDE * (size_t)T.n_ch;
+    const size_t need = sz_ch + T.sz_clear + T.sz_prof;
     if (c->trk_aux_cap < need) {
         if (c->d_trk_aux) hipFree(c->d_trk_aux);
         c->d_trk_aux = nullptr;
@@ -397,246 +380,213 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         c->trk_aux_cap = need;
     }
     char* aux = (char*)c->d_trk_aux;
-    TrkChan* d_ch = (TrkChan*)aux;
-    int* d_done = (int*)(aux + sz_ch);
-    unsigned long long* d_xch = (unsigned long long*)(aux + sz_ch + sz_done);
-    int* d_err = (int*)(aux + sz_ch + sz_done + sz_xch);
-    const char* pe = getenv("SGX_TRK_PROFILE");
-    const bool want_prof = pe && pe[0] == '1';
-    long long* d_prof = want_prof ? (long long*)(aux + sz_ch + sz_done + sz_xch + 256) : nullptr;
-    // Which kernel: the low-rate variant when a group can hold several switches of a ramp; throughput mode for more
-    // than 128 int8 channels (one workgroup per channel anyway); the latency-mode kernel otherwise - with one workgroup
-    // per (unit, correlator arm) when three times the CUs of one-per-unit are free (SGX_TRK_ARMS=3 keeps one per unit).
-    const bool use_tp = P0.use_tp != 0;
-    const bool use_v2 = P0.use_v2 != 0;
-    const bool arm_split = P0.arm_split != 0;
-    const bool use_v3 = P0.use_v3 != 0;
-    const int n_units2 = K.n_units;
-    const int n_units3 = P0.n_units3;   // (units of half the size: the same room for a code NCO that left its basis)
-    const char* le = getenv("SGX_TRK_LDSPAD");   // dynamic LDS per workgroup (bytes); default: one workgroup per CU
-    const int lds_pad_coop = le ? atoi(le) : 90112;
-    const int split0 = K.split;
-    // CUs claimed by a cooperative launch; given back on EVERY way out of this function
-    struct CuGuard {
-        int device, n;
-        ~CuGuard() { drop(); }
-        void drop() {
-            if (n) sgx_cu_release(device, n);
-            n = 0;
+    T.d_ch = (TrkChan*)aux;
+    T.d_done = (int*)(aux + sz_ch);
+    T.d_xch = (unsigned long long*)(aux + sz_ch + sz_done);
+    T.d_err = (int*)(aux + sz_ch + sz_done + sz_xch);
+    T.d_prof = T.E.profile ? (long long*)(aux + sz_ch + T.sz_clear) : nullptr;
+    T.fast_look = T.direct && T.n_ch <= SGX_TRK_LOOK_CH && !T.E.profile;
+    return SGX_OK;
+}
+
+// The launch's error words ([0] flags | 1 + channel of a timeout; [1] 1 + channel of a block beyond the units): from the
+// pinned page trk_finish_kernel fills (the host spins, then sleeps in the stream synchronisation), or copied and synchronised
+static int trk_collect(TrkCall& T, int words[2]) {
+    sgx_ctx* c = T.c;
+    hipStream_t st = c->stream;
+    hipError_t& e = T.e;
+    if (!T.fast_look) {
+        if (e == hipSuccess) e = hipMemcpyAsync(words, T.d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+        T.stamp("error word copy queued");
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        T.stamp("stream synchronised");
+        return SGX_OK;
+    }
+    const unsigned long long seq = ++c->trk_seq;
+    if (e == hipSuccess) {
+        trk_finish_kernel<<<1, SGX_TRK_LOOK_CH, 0, st>>>(T.d_err, T.d_done, T.n_ch, (TrkLook*)((char*)c->d_look + SGX_TRK_LOOK_OFFSET), seq);
+        e = hipGetLastError();
+    }
+    T.stamp("finish kernel queued");
+    if (e == hipSuccess) {
+        const TrkLook* look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
+        const auto t0 = std::chrono::steady_clock::now();
+        bool seen = false;
+        for (unsigned sp = 0; !seen; ++sp) {
+            if (__atomic_load_n(&look->seq, __ATOMIC_ACQUIRE) == seq) seen = true;
+            else if ((sp & 4095u) == 4095u &&
+                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.25) break;
         }
-    } reserved{c->device, 0};
-    bool used_v2 = false;
-    // what the launches so far have established: the record's streaming has been tried (and stalled), a member of a
-    // cooperative layout timed out (the next launch runs with one workgroup per channel)
-    bool stream_tried = false, fallback_one = false, v3_off = false;
-    // the launch's error words and ms_done through the pinned page (one small kernel, the host spins) when the series go
-    // straight to the caller's pinned buffer and the channels fit the page
-    const bool fast_look = direct && n_ch <= SGX_TRK_LOOK_CH && !want_prof;
-    const TrkLook* h_look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
-    int used_members = 0;
-    hipError_t e = hipSuccess;
-    int h_err = 0;
-    // The cooperating workgroups of a channel wait for each other, so all of them must be resident at once.  If
-    // something else occupies the CUs a member times out (bounded spins) and flags the channel: the launch is
-    // then repeated once with one workgroup per channel, which needs no co-residency.  A streaming record whose
-    // watermark stalls is repeated on the resident record first, with the same decomposition; a record too strong for the
-    // speculative kernel's fixed point is repeated with the round-3 kernel: at most four launches, each repeat said on stderr.
-    if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
-    for (int launches = 0; launches < 4; ++launches) {
-        // a record that is still streaming in is followed by the latency-mode kernel (its record wave watches the
-        // device watermark); the other kernels, and a launch repeated on the resident record, first wait for all of it
-        const char* se2 = getenv("SGX_TRK_STREAM");
-        const bool v2 = use_v2;
-        const bool want_stream = r->loader && !r->load_done.load() && launches == 0 && !(se2 && se2[0] == '0') && v2;
-        if (use_v3 && kind == SGX_DT_INT8 && !fallback_one && !v3_off && !want_stream) {
-            // THE SCALE GUARD of every speculative launch that does not stream (sgx_trk3.hip says why 2^17; a streaming
-            // launch has its record wave's): the whole record, then a bound computed once per record.  Before the kernel
-            // is chosen - and its CUs reserved -, and whatever the record was when this call began: still loading
-            // (SGX_TRK_STREAM=0, a repeat after a stalled stream) or resident
-            const int rq = sgx_if_require(r, r->n);
-            if (rq != SGX_OK) return rq;
-            const long long mag = if_mag_bound(c, r);
-            if (mag < 0) {
-                sgx_set_error("tracking: the magnitude scan of the record failed");
+        if (!seen) {
+            e = hipStreamSynchronize(st);
+            if (e == hipSuccess && __atomic_load_n(&look->seq, __ATOMIC_ACQUIRE) != seq) {
+                sgx_set_error("tracking: the launch's result words were not written");
                 return SGX_E_HIP;
             }
-            if (mag >= 131072) {
-                fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add "
-                                "up to 131 072 or more in magnitude); the round-3 kernel tracks this record\n");
-                v3_off = true;
-            }
         }
-        if (!chained) {
-            SGX_HIP(hipMemcpyAsync(d_ch, hc.data(), sizeof(TrkChan) * (size_t)n_ch, hipMemcpyHostToDevice, st));
-        } else if (launches == 0) {
-            // preRun on the device: the table lands in d_ch (a repeated launch finds it there)
-            const int rp = sgx_prerun_enqueue(c, d_ch, n_ch, skip_bytes, rec_file_offset, sample_bytes);
-            if (rp != SGX_OK) return rp;
-        }
-        stamp("channel table queued");
-        SGX_HIP(hipMemsetAsync(aux + sz_ch, 0, sz_done + sz_xch + 256, st));   // done, every polled word, err
-        stamp("memset queued");
-        if (!direct) trk_fill_kernel<<<(unsigned)((elems + 255) / 256), 256, 0, st>>>(d_out, ms, (long long)elems);
-        K.split = fallback_one ? 1 : split0;                     // a member timed out: no co-residency needed with one
-        K.n_units = n_units2;
-        bool v3 = use_v3 && !fallback_one && !v3_off;
-        if (v3) {
-            reserved.n = sgx_cu_reserve(c->device, cus_total, ch8 * n_units3);
-            if (reserved.n == 0) v3 = false;                     // (the CUs are taken: the layouts below need fewer)
-            else {
-                K.split = n_units3;
-                K.n_units = n_units3;
-            }
-        }
-        int arms_now = (v2 && arm_split && K.split > 1) ? 1 : 3;
-        // Cooperating workgroups wait for each other, so all of a launch must be resident at once: one workgroup per CU
-        // out of a per-device budget shared by every context of this process (a launch that does not fit the CUs left
-        // by the others runs with one workgroup per channel, which needs no co-residency).
-        if (K.split > 1 && !v3) {
-            reserved.n = sgx_cu_reserve(c->device, cus_total, ch8 * K.split * (arms_now == 1 ? 3 : 1));
-            if (reserved.n == 0 && arms_now == 1) {
-                arms_now = 3;                                    // the CUs left may still hold one workgroup per unit
-                reserved.n = sgx_cu_reserve(c->device, cus_total, ch8 * K.split);
-            }
-            if (reserved.n == 0) K.split = 1;
-        }
-        const int members_now = v3 ? K.split : K.split * ((v2 && K.split > 1 && arms_now == 1) ? 3 : 1);
-        const int n_blocks = ch8 * members_now;
-        const bool streaming = want_stream;
-        if (!streaming) {
-            const int rq = sgx_if_require(r, r->n);
-            if (rq != SGX_OK) return rq;
-        }
-        K.mark = streaming ? r->d_mark : nullptr;
-        if (want_prof) SGX_HIP(hipMemsetAsync(d_prof, 0, sz_prof, st));
-        hipEventRecord(c->ev[3], st);
-        if (v3) {
-            const char* wh = getenv("SGX_TRK_TEST_WITHHOLD");   // test hook: launch without each channel's last member
-            const int nb3 = (wh && wh[0] == '1') ? n_blocks - 8 : n_blocks;
-            sgx_trk3_launch(nb3, st, r->d, c->d_codes, d_ch, d_out, d_done, K, d_prof, d_xch, d_err, lds_pad_coop);
-            used_v2 = true;
-            used_members = members_now;
-            c->timing.track_kernel = 5.f;
-        } else if (v2) {
-            const char* wh = getenv("SGX_TRK_TEST_WITHHOLD");   // test hook: launch without each channel's last member
-            const int nb2 = (wh && wh[0] == '1' && K.split > 1) ? n_blocks - 8 : n_blocks;
-            // (one workgroup per CU only matters while members wait for each other)
-            sgx_trk2_launch(nb2, st, r->d, c->d_codes, d_ch, d_out, d_done, K, d_prof, d_xch, d_err, sample_bytes, arms_now,
-                            K.split > 1 ? lds_pad_coop : 0);
-            used_v2 = true;
-            used_members = members_now;
-            c->timing.track_kernel = 2.f;
-        }
-        else if (use_any) {  // (any sample type, sample by sample)
-            const char* wh = getenv("SGX_TRK_TEST_WITHHOLD");
-            const int nba = (wh && wh[0] == '1' && K.split > 1) ? n_blocks - 8 : n_blocks;
-            sgx_trk_any_launch(nba, st, r->d, c->d_codes, d_ch, d_out, d_done, K, d_prof, d_xch, d_err);
-            c->timing.track_kernel = 6.f;
-        }
-        else if (use_tp) {   // (one lane per prompt chip)
-            sgx_trk_tp_launch(n_blocks, st, r->d, c->d_codes, d_ch, d_out, d_done, K, d_prof, d_xch, d_err);
-            c->timing.track_kernel = 3.f;
-        } else {
-            const char* wh = getenv("SGX_TRK_TEST_WITHHOLD");   // (the same test hook for the low-rate cooperative kernel)
-            const int nb1 = (wh && wh[0] == '1' && K.split > 1) ? n_blocks - 8 : n_blocks;
-            sgx_trk_multi_launch(nb1, st, r->d, c->d_codes, d_ch, d_out, d_done, K, d_prof, d_xch, d_err);
-            c->timing.track_kernel = 4.f;
-        }
-        hipEventRecord(c->ev[4], st);
-        stamp("kernel queued");
-        c->timing.track_members = (float)members_now;
-        c->timing.track_streamed = streaming ? 1.f : 0.f;
-        e = hipGetLastError();
-        int h_err2[2] = {0, 0};   // [0] flags | 1 + channel of a timeout; [1] 1 + channel of a block beyond the units
-        if (fast_look) {
-            const unsigned long long seq = ++c->trk_seq;
-            if (e == hipSuccess) {
-                trk_finish_kernel<<<1, SGX_TRK_LOOK_CH, 0, st>>>(d_err, d_done, n_ch, (TrkLook*)((char*)c->d_look + SGX_TRK_LOOK_OFFSET), seq);
-                e = hipGetLastError();
-            }
-            stamp("finish kernel queued");
-            if (e == hipSuccess) {
-                // spin (the kernel takes tens of milliseconds), then sleep in the stream synchronisation
-                const auto t0 = std::chrono::steady_clock::now();
-                bool seen = false;
-                for (unsigned sp = 0; !seen; ++sp) {
-                    if (__atomic_load_n(&h_look->seq, __ATOMIC_ACQUIRE) == seq) seen = true;
-                    else if ((sp & 4095u) == 4095u &&
-                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.25) break;
-                }
-                if (!seen) {
-                    e = hipStreamSynchronize(st);
-                    if (e == hipSuccess && __atomic_load_n(&h_look->seq, __ATOMIC_ACQUIRE) != seq) {
-                        sgx_set_error("tracking: the launch's result words were not written");
-                        return SGX_E_HIP;
-                    }
-                }
-                h_err2[0] = h_look->err[0];
-                h_err2[1] = h_look->err[1];
-            }
-            stamp("result words seen");
-        } else {
-            if (e == hipSuccess) e = hipMemcpyAsync(h_err2, d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-            stamp("error word copy queued");
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            stamp("stream synchronised");
-        }
-        h_err = h_err2[0];
-        reserved.drop();
-        // test hooks: treat the first launch as timed out ('1'), or the one that follows a stalled stream ('2'); treat
-        // the first launch as a stalled stream (SGX_TRK_TEST_STALL=1)
-        const char* th = getenv("SGX_TRK_TEST_TIMEOUT");
-        const char* tst = getenv("SGX_TRK_TEST_STALL");
-        if (e == hipSuccess && th && K.split > 1 && !fallback_one &&
-            ((th[0] == '1' && launches == 0) || (th[0] == '2' && stream_tried)))
-            h_err = 1;
-        if (e == hipSuccess && tst && tst[0] == '1' && launches == 0) h_err = TRK_ERR_STREAM;
-        if (e == hipSuccess && (h_err & TRK_ERR_STREAM) && !stream_tried && !fallback_one) {
-            // the streaming record's watermark stalled (the copy stream could not run beside the kernel): repeat
-            // with the same decomposition once the whole record is resident
-            fprintf(stderr, "[sgx] tracking: the record did not stream in beside the kernel; repeating the launch "
-                            "on the resident record\n");
-            stream_tried = true;
-            continue;
-        }
-        h_err &= ~TRK_ERR_STREAM;
-        if (e == hipSuccess && (h_err & TRK_ERR_SCALE) && !v3_off) {
-            // samples beyond what the speculative kernel's 2^30 fixed point holds in 48 bits (a record that clips all the
-            // time): the round-3 kernel, whose 2^28 holds full-scale samples that all line up, tracks it
-            fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add up "
-                            "to 131 072 or more in magnitude); repeating the launch with the round-3 kernel\n");
-            v3_off = true;
-            continue;
-        }
-        h_err &= ~TRK_ERR_SCALE;
-        if (e == hipSuccess && (h_err & TRK_ERR_RANGE) == 0) h_err &= 0xFFFF;
-        if (e == hipSuccess && (h_err & TRK_ERR_RANGE)) {
-            sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
-                          "provides (the code NCO left its plausible range; dllNoiseBandwidth %g)",
-                          (h_err2[1] ? h_err2[1] : (h_err & 0xFFFF)) - 1, K.n_units, TRK_UNIT, S.dllNoiseBandwidth);
-            return SGX_E_RANGE;
-        }
-        if (e != hipSuccess || h_err == 0 || K.split == 1) break;
-        fprintf(stderr, "[sgx] tracking: channel %d timed out waiting for a cooperating workgroup (%d workgroups per "
-                        "channel, are the CUs shared?); repeating the launch with one workgroup per channel\n", h_err - 1,
-                members_now);
-        fallback_one = true;
+        words[0] = look->err[0];
+        words[1] = look->err[1];
     }
-    if (fast_look && e == hipSuccess) {
-        for (int i = 0; i < n_ch; ++i) ms_done[i] = h_look->done[i];
+    T.stamp("result words seen");
+    return SGX_OK;
+}
+
+// What follows a launch whose error words are in: `again` when it is repeated (the cause recorded in T.rep, said on
+// stderr), or the error.  Test hooks first: a timed-out launch (SGX_TRK_TEST_TIMEOUT), a stalled stream (..._STALL).
+static int trk_repeat(TrkCall& T, int launch, const int words[2], bool& again) {
+    const TrkLaunch& L = T.L;
+    TrkRepeat& R = T.rep;
+    int& h_err = T.h_err;
+    again = false;
+    h_err = words[0];
+    if (T.e != hipSuccess) return SGX_OK;   // (trk_finish reports it)
+    if (T.E.timeout && L.split > 1 && !R.one_member &&
+        ((T.E.timeout == '1' && launch == 0) || (T.E.timeout == '2' && R.stream_stalled)))
+        h_err = 1;
+    if (T.E.stall && launch == 0) h_err = TRK_ERR_STREAM;
+    if ((h_err & TRK_ERR_STREAM) && !R.stream_stalled && !R.one_member) {
+        // the streaming record's watermark stalled (the copy stream could not run beside the kernel): repeat
+        // with the same decomposition once the whole record is resident
+        fprintf(stderr, "[sgx] tracking: the record did not stream in beside the kernel; repeating the launch "
+                        "on the resident record\n");
+        R.stream_stalled = again = true;
+        return SGX_OK;
+    }
+    h_err &= ~TRK_ERR_STREAM;
+    if ((h_err & TRK_ERR_SCALE) && !R.v3_off) {
+        // samples beyond what the speculative kernel's 2^30 fixed point holds in 48 bits (a record that clips all the
+        // time): the round-3 kernel, whose 2^28 holds full-scale samples that all line up, tracks it
+        fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add up "
+                        "to 131 072 or more in magnitude); repeating the launch with the round-3 kernel\n");
+        R.v3_off = again = true;
+        return SGX_OK;
+    }
+    h_err &= ~TRK_ERR_SCALE;
+    if ((h_err & TRK_ERR_RANGE) == 0) h_err &= 0xFFFF;
+    if (h_err & TRK_ERR_RANGE) {
+        sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
+                      "provides (the code NCO left its plausible range; dllNoiseBandwidth %g)",
+                      (words[1] ? words[1] : (h_err & 0xFFFF)) - 1, L.n_units, TRK_UNIT, T.c->s.dllNoiseBandwidth);
+        return SGX_E_RANGE;
+    }
+    if (h_err == 0 || L.split == 1) return SGX_OK;
+    // a member timed out (bounded spins) waiting for the others - something else occupies the CUs: one workgroup per channel
+    fprintf(stderr, "[sgx] tracking: channel %d timed out waiting for a cooperating workgroup (%d workgroups per "
+                    "channel, are the CUs shared?); repeating the launch with one workgroup per channel\n", h_err - 1,
+            L.members);
+    R.one_member = again = true;
+    return SGX_OK;
+}
+
+// CUs claimed by a cooperative launch; given back on EVERY way out of the call
+struct CuGuard {
+    int device, n;
+    ~CuGuard() { drop(); }
+    void drop() {
+        if (n) sgx_cu_release(device, n);
+        n = 0;
+    }
+};
+
+// One launch, in stream order: the scale scan, the channel table, the cleared state, the fill kernel, the CUs, the record,
+// the profile, the kernel between ev[3] and ev[4], its result words; -> what trk_repeat makes of them
+static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& again) {
+    sgx_ctx* c = T.c;
+    const sgx_if* r = T.r;
+    hipStream_t st = c->stream;
+    // a record that is still streaming in is followed by the latency-mode kernel (its record wave watches the
+    // device watermark); the other kernels, and a launch repeated on the resident record, first wait for all of it
+    const bool streaming = r->loader && !r->load_done.load() && launch == 0 && T.E.stream && (T.P.kernel == 2 || T.P.kernel == 5);
+    if (T.P.kernel == 5 && T.kind == SGX_DT_INT8 && !T.rep.one_member && !T.rep.v3_off && !streaming) {
+        // THE SCALE GUARD of every speculative launch that does not stream (sgx_trk3.hip says why 2^17; a streaming launch
+        // has its record wave's): a bound computed once per record, before the kernel is chosen and its CUs reserved,
+        // whatever the record was when the call began - still loading (SGX_TRK_STREAM=0, a stalled stream) or resident
+        const int rq = sgx_if_require(r, r->n);
+        if (rq != SGX_OK) return rq;
+        const long long mag = if_mag_bound(c, r);
+        if (mag < 0) {
+            sgx_set_error("tracking: the magnitude scan of the record failed");
+            return SGX_E_HIP;
+        }
+        if (mag >= 131072) {
+            fprintf(stderr, "[sgx] tracking: samples too strong for the speculative kernel's fixed point (2 048 samples add "
+                            "up to 131 072 or more in magnitude); the round-3 kernel tracks this record\n");
+            T.rep.v3_off = true;
+        }
+    }
+    if (!T.chained) {
+        SGX_HIP(hipMemcpyAsync(T.d_ch, T.hc.data(), sizeof(TrkChan) * (size_t)T.n_ch, hipMemcpyHostToDevice, st));
+    } else if (launch == 0) {
+        // preRun on the device: the table lands in d_ch (a repeated launch finds it there)
+        const int rp = sgx_prerun_enqueue(c, T.d_ch, T.n_ch, T.skip_bytes, T.rec_file_offset, T.sample_bytes);
+        if (rp != SGX_OK) return rp;
+    }
+    T.stamp("channel table queued");
+    SGX_HIP(hipMemsetAsync(T.d_done, 0, T.sz_clear, st));   // done, every polled word, err
+    T.stamp("memset queued");
+    if (!T.direct) trk_fill_kernel<<<(unsigned)((T.elems + 255) / 256), 256, 0, st>>>(T.d_out, T.ms, (long long)T.elems);
+    const TrkLaunch& L = T.L = trk_launch_step(T.P, T.rep, [&](int want) { return sgx_cu_reserve(c->device, T.cus_total, want); });
+    reserved.n = L.cus;
+    T.K.split = L.split;
+    T.K.n_units = L.n_units;
+    if (!streaming) {
+        const int rq = sgx_if_require(r, r->n);
+        if (rq != SGX_OK) return rq;
+    }
+    T.K.mark = streaming ? r->d_mark : nullptr;
+    if (T.d_prof) SGX_HIP(hipMemsetAsync(T.d_prof, 0, T.sz_prof, st));
+    hipEventRecord(c->ev[3], st);
+    // THE LAUNCH.  Test hook (SGX_TRK_TEST_WITHHOLD=1): launch without each channel's last member - the speculative kernel
+    // always, the other cooperative kernels while their members wait for each other, trk_kernel_tp never
+    const bool withhold = T.E.withhold && (L.kernel == 5 || (L.kernel != 3 && L.split > 1));
+    const int nb = withhold ? L.n_blocks - 8 : L.n_blocks;
+    const int8_t* codes = c->d_codes;
+    switch (L.kernel) {
+    case 2:   // (one workgroup per CU only matters while members wait for each other)
+        sgx_trk2_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.sample_bytes,
+                        L.arms, L.split > 1 ? T.E.lds_pad : 0);
+        break;
+    case 3: sgx_trk_tp_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    case 4: sgx_trk_multi_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    case 5: sgx_trk3_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.E.lds_pad); break;
+    case 6: sgx_trk_any_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    }
+    hipEventRecord(c->ev[4], st);
+    T.stamp("kernel queued");
+    c->timing.track_kernel = (float)L.kernel;
+    c->timing.track_members = (float)L.members;
+    c->timing.track_streamed = streaming ? 1.f : 0.f;
+    T.e = hipGetLastError();
+    int words[2] = {0, 0};
+    const int rc = trk_collect(T, words);
+    if (rc != SGX_OK) return rc;
+    reserved.drop();
+    return trk_repeat(T, launch, words, again);
+}
+
+// After the last launch: ms_done (and the series out of the staging buffer), the profile, the entries no channel reached,
+// the errors, the kernel time, the float scale undone
+static int trk_finish(TrkCall& T) {
+    sgx_ctx* c = T.c;
+    const int n_ch = T.n_ch, ms = T.ms;
+    hipError_t e = T.e;
+    if (T.fast_look && e == hipSuccess) {
+        const TrkLook* look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
+        for (int i = 0; i < n_ch; ++i) T.ms_done[i] = look->done[i];
         e = hipEventSynchronize(c->ev[4]);   // (the word is stored a moment before the kernels retire: the times need the event)
     } else {
-        if (e == hipSuccess && !direct) e = hipMemcpyAsync(out, d_out, elems * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ms_done, d_done, sizeof(int) * (size_t)n_ch, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && !T.direct) e = hipMemcpyAsync(T.out, T.d_out, T.elems * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(T.ms_done, T.d_done, sizeof(int) * (size_t)n_ch, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    stamp("ms_done copied");
-    if (want_prof && e == hipSuccess) {
+    T.stamp("ms_done copied");
+    if (T.d_prof && e == hipSuccess) {
+        // SGX_TRK_PROFILE=1: cycles per block of the kernel's phases (tools/r5_harvest.py and r6_harvest.py read these lines)
         std::vector<long long> hp(T2_PROF_STRIDE * (size_t)n_ch);
-        hipMemcpy(hp.data(), d_prof, sizeof(long long) * hp.size(), hipMemcpyDeviceToHost);
-        if (used_v2) {
+        hipMemcpy(hp.data(), T.d_prof, sizeof(long long) * hp.size(), hipMemcpyDeviceToHost);
+        if (T.L.kernel == 2 || T.L.kernel == 5) {
             for (int i = 0; i < n_ch && i < 8; ++i)
-                for (int mm = 0; mm < used_members; mm += (i == 0 ? 1 : used_members - 1))
+                for (int mm = 0; mm < T.L.members; mm += (i == 0 ? 1 : T.L.members - 1))
                     fprintf(stderr, "[sgx trk2 profile] ch %d member %2d cycles/block: release->publish %.0f  publish->sums %.0f  "
                                     "sums->release %.0f\n", i, mm, (double)hp[T2_PROF_STRIDE * i + mm] / ms,
                             (double)hp[T2_PROF_STRIDE * i + 64 + mm] / ms, (double)hp[T2_PROF_STRIDE * i + 128 + mm] / ms);
@@ -650,43 +600,92 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         sgx_set_error("tracking kernel failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;
     }
-    if (direct) {
+    if (T.direct) {
         // entries never reached keep the reference's initial values (tracking.py:65-94): zeros or +Inf
         const StepLook* slook = (const StepLook*)((const char*)c->h_look + SGX_STEP_LOOK_OFFSET);   // (chained: preRun's table)
         for (int i = 0; i < n_ch; ++i) {
-            if (chained && slook->prn[i] == 0) continue;      // (a channel that is off: the caller gets the first n_active rows)
-            const int dn = chained ? ms_done[i] : ((ch[i].prn == 0) ? 0 : ms_done[i]);
+            if (T.chained && slook->prn[i] == 0) continue;      // (a channel that is off: the caller gets the first n_active rows)
+            const int dn = T.chained ? T.ms_done[i] : ((T.ch[i].prn == 0) ? 0 : T.ms_done[i]);
             if (dn >= ms) continue;
             for (int sidx = 0; sidx < SGX_NUM_SERIES; ++sidx) {
                 const bool zero = (sidx == 0) || (sidx >= 3 && sidx <= 8);
-                double* row = out + ((size_t)i * SGX_NUM_SERIES + (size_t)sidx) * (size_t)ms;
+                double* row = T.out + ((size_t)i * SGX_NUM_SERIES + (size_t)sidx) * (size_t)ms;
                 for (int t = dn; t < ms; ++t) row[t] = zero ? 0.0 : INFINITY;
             }
         }
     }
-    if (h_err != 0) {
-        sgx_set_error("tracking kernel: channel %d reported a timeout with split %d", h_err - 1, K.split);
+    if (T.h_err != 0) {
+        sgx_set_error("tracking kernel: channel %d reported a timeout with split %d", T.h_err - 1, T.K.split);
         return SGX_E_HIP;
     }
-    {
-        const int rq = r->loader ? r->load_rc.load() : SGX_OK;   // the loader failed while the kernel ran
-        if (rq != SGX_OK) return sgx_if_require(r, r->n);
-    }
+    if (T.r->loader && T.r->load_rc.load() != SGX_OK) return sgx_if_require(T.r, T.r->n);   // the loader failed while the kernel ran
     hipEventElapsedTime(&c->timing.track_ms, c->ev[3], c->ev[4]);
-    stamp("done");
-    if (floaty && K.fscale != 1.0) {
+    T.stamp("done");
+    if (T.K.fscale != 1.0) {
         // the kernel tracked fscale x the record: the six correlator series carry the factor (a power of two: exact),
         // everything the discriminators made of them (ratios) does not
-        const double un = 1.0 / K.fscale;
-        for (int i = 0; i < n_ch && !chained; ++i) {
-            if (ch[i].prn == 0) continue;
-            double* o = out + (size_t)i * SGX_NUM_SERIES * (size_t)ms;
-            const int dn = ms_done[i] < ms ? ms_done[i] : ms;
+        const double un = 1.0 / T.K.fscale;
+        for (int i = 0; i < n_ch && !T.chained; ++i) {
+            if (T.ch[i].prn == 0) continue;
+            double* o = T.out + (size_t)i * SGX_NUM_SERIES * (size_t)ms;
+            const int dn = T.ms_done[i] < ms ? T.ms_done[i] : ms;
             for (int sidx = 3; sidx <= 8; ++sidx)
                 for (int t = 0; t < dn; ++t) o[(size_t)sidx * ms + t] *= un;
         }
     }
     return SGX_OK;
+}
+
+// sample_bytes: 1 (int8 record) or 2 (little-endian int16 record; the record handle holds the file's BYTES).  The
+// reference seeks skipNumberOfBytes + codePhase BYTES whatever the sample type and reports fid.tell(), also bytes
+// (tracking.py:107, 255); so a two-byte channel may start on an odd byte - its samples then straddle the file's - and
+// the kernel follows it there (per-channel byte shift of the record pointer, unaligned 16-byte loads).
+// kind, skip_bytes, fscale: sgx_internal.h (sgx_track_kind).
+// chained (round 6, sgx_track_chained): `ch` is null - the channel table is made ON THE DEVICE by the preRun kernel queued
+// in front of the first launch (sgx_prerun_enqueue, sgx_acq.hip) from the acquisition that is pending on this context.
+static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
+                           int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale,
+                           bool chained) {
+    SGX_CHECK_ARG(c && r && (ch || chained) && out && ms_done);
+    const int sample_bytes = sgx_dt_bytes(kind);
+    SGX_CHECK_ARG(sample_bytes >= 1);
+    SGX_CHECK_ARG(n_ch >= 1 && n_ch <= 65535 && ms >= 1);
+    if (!(c->s.dllCorrelatorSpacing > 0.0 && c->s.dllCorrelatorSpacing < 1.0)) {
+        // beyond one chip the reference's replica index ceil(t) leaves its 1025-entry code table (or wraps)
+        sgx_set_error("dllCorrelatorSpacing %g outside (0, 1) chips", c->s.dllCorrelatorSpacing);
+        return SGX_E_ARG;
+    }
+    SGX_HIP(hipSetDevice(c->device));
+    TrkCall T{c, r, ch, n_ch, ms, kind, sample_bytes, skip_bytes, (long long)rec_file_offset, out, ms_done, chained,
+              trk_env(), std::chrono::steady_clock::now()};
+    // (a float record the typed kernel can take: in range, no channel starting inside a sample, not switched off)
+    bool floaty = (kind == SGX_DT_FLOAT32 || kind == SGX_DT_FLOAT64) && fscale > 0.0 && T.E.float_typed;
+    for (int i = 0; i < n_ch && floaty && !chained; ++i) {
+        // (a channel that starts inside a sample reads other values than the ones that were scanned)
+        const long long p0 = skip_bytes + (long long)ch[i].codePhase - rec_file_offset;
+        if (ch[i].prn != 0 && p0 >= 0 && p0 % sample_bytes != 0) floaty = false;
+    }
+    SGX_HIP(hipDeviceGetAttribute(&T.cus_total, hipDeviceAttributeMultiprocessorCount, c->device));
+    // THE RULE (trk_plan above), with the diagnostic overrides of this process's environment
+    T.P = trk_plan(c->s, kind, n_ch, (long long)c->n_code, T.cus_total, floaty, T.E.split, T.E.arms, T.E.v3_off);
+    trk_const(T);
+    T.K.fscale = (floaty && !T.P.multi) ? fscale : 1.0;   // (a float record on the typed kernel: scaled back at the end)
+    if (T.P.n_units > 16) {
+        sgx_set_error("samplesPerCode %lld needs %d units, the tracking kernel holds 16", (long long)c->n_code, T.P.n_units);
+        return SGX_E_ARG;
+    }
+    int rc = trk_channels(T);
+    if (rc == SGX_OK) rc = trk_buffers(T);
+    if (rc != SGX_OK) return rc;
+    if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
+    CuGuard reserved{c->device, 0};
+    bool again = true;
+    // at most four launches: a repeat has a cause in T.rep (trk_repeat), said on stderr
+    for (int launch = 0; launch < 4 && again; ++launch) {
+        rc = trk_launch_once(T, launch, reserved, again);
+        if (rc != SGX_OK) return rc;
+    }
+    return trk_finish(T);
 }
 
 int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,

@@ -9,16 +9,10 @@
 #define T2_THREADS 448             // 4 map waves + PLL wave (4) + DLL wave (5) + record wave (6)
 #define T2_MAXP 16                 // units per channel
 #define T2_MAXM 48                 // members per channel (3 arms x 16 units)
-// The exchange area of a channel, in 64-bit words: 12 granule lines [2 parities][6 sums] of 16 units each, T2_XLINE words
-// apart, then the abort word and 48 placement granules.  (sgx_trk.hip sizes the allocation with the same T2_XCH_STRIDE.)
-#ifndef T2_XLINE
-#define T2_XLINE 16                // 128 bytes: the lines are adjacent
-#endif
+// The exchange area of a channel (T2_XLINE, T2_XCH_STRIDE: sgx_trk_common.h): granule lines, abort word, placement granules
 #define T2_XG 0
 #define T2_XABORT (12 * T2_XLINE)
 #define T2_XPLACE (12 * T2_XLINE + 8)
-#define T2_XCH_STRIDE (((12 * T2_XLINE + 8 + 48) + 255) / 256 * 256)
-#define T2_PROF_STRIDE 192         // profile words per channel: [3 phases][64 members]
 #define T2_FIX 268435456.0         // 2^28: fixed-point scale of a granule's 48-bit payload (member sums are < 2^19)
 #define T2_FIX16 524288.0          // 2^19: the same for two-byte samples (member sums are < 2^28)
 // SB = bytes per IF sample (1: int8 / uint8, 2: int16, 4: float32, 8: float64).  Positions are counted in samples

@@ -61,6 +61,38 @@ struct TrkConst {
 
 // (struct TrkChan: sgx_internal.h - the device-side preRun of sgx_acq.hip fills it too)
 
+// ---- What the host (sgx_trk.hip) and the kernels' files share: the layout the host allocates, and the launchers.
+// The exchange area of a trk2_kernel channel, in 64-bit words: 12 granule lines [2 parities][6 sums] of 16 units each,
+// T2_XLINE words apart, then the abort word and 48 placement granules (sgx_trk2_parts.h).  trk3_kernel's: T3_XCH_STRIDE
+// words (sgx_trk3.hip).  Profile words per channel: [3 phases][64 members].
+#ifndef T2_XLINE
+#define T2_XLINE 16                // 128 bytes: the lines are adjacent
+#endif
+#define T2_XCH_STRIDE (((12 * T2_XLINE + 8 + 48) + 255) / 256 * 256)
+#define T2_PROF_STRIDE 192
+#define T3_MAXP 32                 // trk3_kernel: units per channel
+#ifndef T3_XCH_STRIDE
+#define T3_XCH_STRIDE 512
+#endif
+
+// sgx_trk2.hip: the latency-mode kernel; arms = 1: one workgroup per unit and correlator arm, 3: one per unit
+void sgx_trk2_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
+                     double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
+                     int sample_bytes, int arms, int lds_pad);
+// sgx_trk3.hip: the speculative latency-mode kernel, one workgroup per unit of 128 groups for all three arms
+void sgx_trk3_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
+                     double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
+                     int lds_pad);
+// sgx_trk_tp.hip: the throughput-mode kernel, one workgroup per channel
+void sgx_trk_tp_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
+                       double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
+// sgx_trk_multi.hip: the cooperative kernel with a per-sample replica lookup, for low sampling rates
+void sgx_trk_multi_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
+                          double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
+// sgx_trk_any.hip: the same body with every sample fetched where it lies, for any sample type (K.kind)
+void sgx_trk_any_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
+                        double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
+
 // Per-block parameters: code part written by wave 1, carrier part by wave 0, read by everybody.
 struct TrkBlock {
     long long pos;

@@ -12,10 +12,6 @@
 #include <cstring>
 #include <vector>
 
-// sgx_trk.hip
-int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                   int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale);
-
 // the power of two that brings a record whose largest |sample| is mx to at most 128 (what the typed kernels' fixed point
 // is cut for); 1 for an all-zero record
 // The typed kernel's granules are a fixed point cut for samples of comparable size (2^-28 of the largest): a record whose

@@ -699,14 +699,14 @@ __global__ __launch_bounds__(TP_THREADS, TP_OCC_MODE(MODE)) void trk_kernel_tp(c
     if (tid == 0) ms_done[ch] = done;
 }
 
-void sgx_trk_tp_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const void* chans,
+void sgx_trk_tp_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                        double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch,
                        int* err) {
     (void)prof;
     (void)xch;
     (void)err;
-    if (K.kind == SGX_DT_INT16) trk_kernel_tp<2><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, (const TrkChan*)chans, out, done, K);
-    else if (K.kind == SGX_DT_UINT8) trk_kernel_tp<1><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, (const TrkChan*)chans, out, done, K);
-    else trk_kernel_tp<0><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, (const TrkChan*)chans, out, done, K);
+    if (K.kind == SGX_DT_INT16) trk_kernel_tp<2><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, chans, out, done, K);
+    else if (K.kind == SGX_DT_UINT8) trk_kernel_tp<1><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, chans, out, done, K);
+    else trk_kernel_tp<0><<<K.n_ch, TP_THREADS, 0, st>>>(rec, codes, chans, out, done, K);
     (void)n_blocks;
 }

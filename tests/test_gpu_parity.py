@@ -414,14 +414,16 @@ def test_timeout_after_a_stalled_stream_still_falls_back(full_run, capfd):
     assert _trk_err(s2, series[:, :, :500]) < 1e-9
 
 
-def test_many_channels_throughput_mode(full_run):
-    """256 channels (32 replicas of the 8 inits) on one GPU: one CU per channel, replicas bit-identical."""
+@pytest.mark.parametrize("n_ch", [256, 264])
+def test_many_channels_throughput_mode(full_run, n_ch):
+    """256 and 264 channels (replicas of the 8 inits) on one GPU: one CU per channel, replicas bit-identical.  Into the
+    pinned result buffer, up to 256 channels return their result words through the pinned page, more by a copy."""
     m, s, ctx, sc, rec, a, chans, series, done = full_run
-    many = [chans[i % 8] for i in range(256)]
+    many = [chans[i % 8] for i in range(n_ch)]
     ms = 300
     s2, d2 = ctx.track(rec, many, ms)
     assert np.all(d2 == ms)
-    for i in range(8, 256):
+    for i in range(8, n_ch):
         assert np.array_equal(s2[i], s2[i % 8])
     assert np.array_equal(s2[:8, 0], series[:, 0, :ms])
     assert _trk_err(s2[:8], series[:, :, :ms]) < 1e-9
