@@ -187,6 +187,44 @@ int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_samples, const in
                     int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
                     int32_t* freqBin, int32_t* fineIdx);
 
+/* ---- coherent multi-millisecond acquisition (extends acquisition.py:62-133) --------------------
+ * The reference correlates 1-ms blocks on a 500 Hz grid, which leaves signals below about 40 dB-Hz under acqThreshold.
+ * Here window w of coherent_ms = T_c blocks (1..20) is folded with a carrier that runs on across the window and restarts
+ * at each window start, as the reference restarts it at each block (acquisition.py:103-105):
+ *   F[w][k][n] = sum_{m < T_c} x[(w T_c + m) N + n] (sin + j cos)(f_k (((n + m N) 2) pi ts)),   n < N = samplesPerCode
+ * on the grid f_k = IF - acqSearchBand/2 * 1000 + bin_step_hz * k, k < round(acqSearchBand * 1000 / bin_step_hz) + 1
+ * (<= 1024 bins; bin_step_hz > 0, the Python layer's default is 500 / T_c).  Each folded window then goes through the
+ * reference's correlation (acquisition.py:120-126) and the n_windows = M windows (1..64, T_c M <= 400) take the place of
+ * the 1-ms blocks: noncoh = 0 keeps the window with the larger maximum (acquisition.py:129-133), noncoh = 1 sums them.
+ * Peak, second peak, peakMetric, codePhase and freqBin follow acquisition.py:135-166 on this grid.  The fine search is
+ * the reference's (acquisition.py:167-193); for T_c > 1 each detection's arg-max is limited to the spectrum indices i
+ * (frequency i fs / npts) within bin_step_hz of its coarse bin's frequency.  carrFreq / fineIdx keep the reference's
+ * slice index (acquisition.py:187-191).
+ * tests/coherent_acq_spec.py states the contract in numpy.  T_c = 1 with bin_step_hz = 500 is sgx_acquire itself.
+ * Errors, before anything is launched: SGX_E_ARG for parameters out of range, SGX_E_RANGE for a window shorter than
+ * T_c M N samples (and, as sgx_acquire, for a detection whose fine window leaves it), SGX_E_INDEX as sgx_acquire. */
+typedef struct sgx_acq_params {
+    int32_t coherent_ms;          /* T_c, 1..20 */
+    int32_t n_windows;            /* M, 1..64 */
+    int32_t noncoh;               /* 0 reference rule, 1 non-coherent sum over the windows */
+    int32_t reserved;             /* 0 */
+    double bin_step_hz;           /* Doppler step in Hz, > 0 (SGX_E_ARG otherwise) */
+} sgx_acq_params;
+int sgx_acquire_coherent(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                         const sgx_acq_params* p, double* carrFreq, double* codePhase, double* peakMetric,
+                         int32_t* freqBin, int32_t* fineIdx);
+int sgx_acquire_coherent_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                             const sgx_acq_params* p, double* carrFreq, double* codePhase, double* peakMetric,
+                             int32_t* freqBin, int32_t* fineIdx);
+/* The search sgx_acquire_coherent runs for these settings, for 32 PRNs; needs no GPU.  n_bins Doppler bins; n_phi distinct
+ * fractions phi of f_k N / fs = shift + phi; path 1: the shift path (the forward transforms are n_windows x n_phi folded
+ * rows, each bin reads its phi's spectrum with a circular shift; needs the four-step transform's length and n_phi <= 64),
+ * 0: the direct path (every (window, bin) row folded and transformed; n_windows x n_bins <= 2048).  prn_chunk PRNs per
+ * correlation batch; bin_runs > 1: one PRN per batch, cut into that many runs (of bins for noncoh = 1, of windows for
+ * noncoh = 0). */
+int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, int32_t* n_bins, int32_t* n_phi,
+                              int32_t* path, int32_t* prn_chunk, int32_t* bin_runs);
+
 /* ---- the same path without host round trips between its stages (round 6) --------------------
  * The reference's caller looks at every stage's result before it starts the next (initialize.py:484-506: acquire, preRun,
  * TrackingResult.track).  A caller that wants the tracking results can queue all three and wait once:

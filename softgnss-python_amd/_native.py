@@ -59,6 +59,18 @@ class Timing(C.Structure):
                 ("track_members", C.c_float), ("track_streamed", C.c_float)]
 
 
+class AcqParams(C.Structure):
+    """sgx_acq_params: a coherent multi-millisecond search (sgx_acquire_coherent, 24 bytes)."""
+    _fields_ = [("coherent_ms", C.c_int32), ("n_windows", C.c_int32), ("noncoh", C.c_int32), ("reserved", C.c_int32),
+                ("bin_step_hz", C.c_double)]
+
+
+def acq_params(coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
+    """AcqParams with the default step 500 / coherent_ms Hz where bin_step_hz is None."""
+    step = 500.0 / int(coherent_ms) if bin_step_hz is None and int(coherent_ms) > 0 else bin_step_hz
+    return AcqParams(int(coherent_ms), int(n_windows), 1 if noncoh else 0, 0, float(step if step is not None else 0.0))
+
+
 class LockParams(C.Structure):
     """sgx_lock_params: the C/N0 and lock-detector parameters of sgx_track_quality (32 bytes)."""
     _fields_ = [("T", C.c_double), ("cno_min", C.c_double), ("carr_lock_min", C.c_double), ("window", C.c_int32),
@@ -95,6 +107,10 @@ _PROTOS = {
     "sgx_acquire": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_int32, C.c_int32, C.c_int32,
                               _P, _P, _P, _P, _P]),
     "sgx_acquire_f64": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "sgx_acquire_coherent": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_int32, C.POINTER(AcqParams),
+                                       _P, _P, _P, _P, _P]),
+    "sgx_acquire_coherent_f64": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.POINTER(AcqParams), _P, _P, _P, _P, _P]),
+    "sgx_acquire_coherent_plan": (C.c_int, [C.POINTER(Settings), C.POINTER(AcqParams)] + [C.POINTER(C.c_int32)] * 5),
     "sgx_acquire_begin": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_int32, C.c_int32, C.c_int32]),
     "sgx_acquire_end": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "sgx_track_chained": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
@@ -194,6 +210,17 @@ def acquire_plan(n_prn=32, n_bins=29, n_blocks=2, noncoh=False, chunk_rows=0, ma
     check(lib().sgx_acquire_plan(int(n_prn), int(n_bins), int(n_blocks), 1 if noncoh else 0, int(chunk_rows), int(max_queues),
                                  *[C.byref(x) for x in v]))
     return tuple(x.value for x in v)
+
+
+def acquire_coherent_plan(settings, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
+    """The coherent search sgx_acquire_coherent runs for these settings, for 32 PRNs (include/sgx.h); needs no GPU.
+    Returns dict(n_bins, n_phi, path ('shift' or 'direct'), prn_chunk, bin_runs)."""
+    st = settings_struct(settings)
+    pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
+    v = [C.c_int32(0) for _ in range(5)]
+    check(lib().sgx_acquire_coherent_plan(C.byref(st), C.byref(pa), *[C.byref(x) for x in v]))
+    return dict(n_bins=v[0].value, n_phi=v[1].value, path="shift" if v[2].value == 1 else "direct",
+                prn_chunk=v[3].value, bin_runs=v[4].value)
 
 
 def acquire_plan_limits():
@@ -406,6 +433,38 @@ class Context(object):
         check(lib().sgx_acquire(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), n, int(n_blocks),
                                 1 if noncoh else 0, _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
         return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+
+    def acquire_coherent(self, rec, offset, n_samples, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
+        """acquire() with coherent_ms-ms windows (n_windows of them) on a bin_step_hz grid (None: 500 / coherent_ms)."""
+        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
+        prn = np.ascontiguousarray(prn0, dtype=np.int32)
+        n = prn.size
+        carr, cph, met = np.zeros(n), np.zeros(n), np.zeros(n)
+        fb = np.zeros(n, dtype=np.int32)
+        fi = np.zeros(n, dtype=np.int32)
+        check(lib().sgx_acquire_coherent(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), n, C.byref(pa),
+                                         _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
+        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+
+    def acquire_coherent_f64(self, signal, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
+        """acquire_coherent() on a host signal of any real dtype (copied to HBM as fp64)."""
+        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
+        sig = np.ascontiguousarray(signal, dtype=np.float64)
+        prn = np.ascontiguousarray(prn0, dtype=np.int32)
+        n = prn.size
+        carr, cph, met = np.zeros(n), np.zeros(n), np.zeros(n)
+        fb = np.zeros(n, dtype=np.int32)
+        fi = np.zeros(n, dtype=np.int32)
+        check(lib().sgx_acquire_coherent_f64(self._h, _ptr(sig), sig.size, _ptr(prn), n, C.byref(pa),
+                                             _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
+        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+
+    @staticmethod
+    def acquire_coherent_plan(settings, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
+        """The module-level acquire_coherent_plan (needs no device)."""
+        return acquire_coherent_plan(settings, coherent_ms, n_windows, noncoh, bin_step_hz)
 
     # ---- the same without host round trips between the stages (include/sgx.h, "round 6") ----
     def acquire_begin(self, rec, offset, n_samples, prn0, n_blocks=2, noncoh=False):

@@ -70,7 +70,7 @@ class AcquisitionResult(Result):
     def codePhase(self):
         return self.results.codePhase
 
-    def acquire(self, longSignal, n_blocks=2, noncoh=False, prn_indices=None):
+    def acquire(self, longSignal, n_blocks=2, noncoh=False, prn_indices=None, coherent_ms=1, bin_step_hz=None):
         """Cold-start acquisition (reference acquisition.py:27-204).
 
         longSignal  1-D int8 samples (11 ms: the fine search needs codePhase + 10 ms), or a
@@ -78,8 +78,13 @@ class AcquisitionResult(Result):
         The reference searches PRN indices range(len(acqSatelliteList)) - the list's VALUES
         are ignored - and so does this method unless prn_indices is given.
         n_blocks / noncoh are extensions (reference behaviour: 2, False).
+        coherent_ms / bin_step_hz (extension, include/sgx.h sgx_acquire_coherent): n_blocks windows of coherent_ms ms
+        each, on a Doppler grid of bin_step_hz (None: 500 / coherent_ms); longSignal must hold coherent_ms x n_blocks ms.
+        A deferred search with coherent_ms > 1 or another step runs eagerly.
         Raises IndexError exactly where the reference does (coarse code phase == 37 samples, Q5).
         """
+        coherent_ms = int(coherent_ms)
+        coherent = not (coherent_ms == 1 and (bin_step_hz is None or float(bin_step_hz) == 500.0))
         settings = self._settings
         ctx = engine.get_context(settings, self._device)
         if prn_indices is None:
@@ -103,7 +108,7 @@ class AcquisitionResult(Result):
                 f64 = arr.astype(np.float64)
         self._prerun_pending = False
         self._merged = None
-        if self._deferred and f64 is None and own is None and not self._verbose:
+        if self._deferred and f64 is None and own is None and not self._verbose and not coherent:
             token = ctx.acquire_begin(rec, off, n, prn_indices, n_blocks=n_blocks, noncoh=noncoh)
             self._pending = (ctx, prn_indices, token)
             self._results = None
@@ -113,7 +118,13 @@ class AcquisitionResult(Result):
         if self._verbose:
             print('(')
         try:
-            if f64 is not None:
+            if coherent:
+                kw = dict(coherent_ms=coherent_ms, n_windows=n_blocks, noncoh=noncoh, bin_step_hz=bin_step_hz)
+                if f64 is not None:
+                    r = ctx.acquire_coherent_f64(f64, prn_indices, **kw)
+                else:
+                    r = ctx.acquire_coherent(rec, off, n, prn_indices, **kw)
+            elif f64 is not None:
                 r = ctx.acquire_f64(f64, prn_indices, n_blocks=n_blocks, noncoh=noncoh)
             else:
                 r = ctx.acquire(rec, off, n, prn_indices, n_blocks=n_blocks, noncoh=noncoh)

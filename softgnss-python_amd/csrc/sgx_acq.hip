@@ -295,10 +295,16 @@ __global__ __launch_bounds__(256) void acq_fine_prep_kernel(SgxSig x,
 // acquisition.py:182-187: argmax of |X_d[4 : uniq-5]| (first occurrence) for detection d, where the row holds
 // Z = FFT(x_a + i x_b):  X_a[k] = (Z[k] + conj(Z[M-k]))/2,  X_b[k] = (Z[k] - conj(Z[M-k]))/(2i).
 // Only the argmax is observable, so the common factor 1/4 of |.|^2 is dropped.
+// win (coherent search, else null): detection d's own range [win[2 d], win[2 d + 1]) instead of [lo, hi)
 __global__ __launch_bounds__(256) void acq_fine_argmax_kernel(const cplx* __restrict__ X, long long row_stride,
                                                               long long lo, long long hi,
-                                                              double* __restrict__ pv, long long* __restrict__ pi) {
+                                                              double* __restrict__ pv, long long* __restrict__ pi,
+                                                              const long long* __restrict__ win = nullptr) {
     const int d = blockIdx.y;
+    if (win) {
+        lo = win[2 * d];
+        hi = win[2 * d + 1];
+    }
     const cplx* __restrict__ row = X + (long long)(d >> 1) * row_stride;
     const double sgn = (d & 1) ? -1.0 : 1.0;
     double best = -1.0;
@@ -445,12 +451,91 @@ static int ensure_buf(void** p, size_t* cap_bytes, size_t need) {
 static int acquire_four_step(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0,
                              int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
                              double* peakMetric, int32_t* freqBin, int32_t* fineIdx, bool* handled, bool defer = false);
+// The grid of a coherent multi-millisecond search (sgx_acquire_coherent; coh_grid fills it)
+#define ACQ_COH_MAX_MS 20
+#define ACQ_COH_MAX_WINDOWS 64
+#define ACQ_COH_MAX_SPAN_MS 400
+#define ACQ_COH_MAX_BINS 1024
+#define ACQ_COH_MAX_PHI 64
+struct CohGrid {
+    int T = 1, M = 1, noncoh = 0;       // coherent_ms, n_windows, rule
+    double step = 500.0, f0 = 0.0;      // f_k = f0 + step k
+    int n_bins = 0, n_phi = 0, path = 0;
+    std::vector<int2> bin_map;          // shift path: (phi index, circular shift) per bin
+    std::vector<double> phi;
+    int prn_chunk = 1, runs = 1, per_run = 1;   // correlation batches (coh_plan): per_run bins (noncoh) or windows
+};
+static std::vector<long long> coh_fine_windows(const CohGrid& g, const sgx_settings& S, long long N,
+                                               const std::vector<int>& det_bin);
+
+// Direct path of the coherent search: window w of bin k folded as the contract states it (include/sgx.h), every
+// (window, bin) row on its own - the same IEEE operations as acq_mix_kernel, which is the case T = 1:
+//   out[w][k][n] = sum_{m < T} x[(w T + m) n_code + n] (sin + j cos)(frq[k] (((n + m n_code) 2) pi ts))
+__global__ __launch_bounds__(256) void acq_fold_direct_kernel(SgxSig x, cplx* __restrict__ out, long long n, double ts,
+                                                              const double* __restrict__ frq, int n_bins, int T) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int k = blockIdx.y % n_bins;
+    const int w = blockIdx.y / n_bins;
+    const double f = frq[k];
+    double re = 0.0, im = 0.0;
+    for (int m = 0; m < T; ++m) {
+        const double pp = ((double)((i + (long long)m * n) * 2) * M_PI) * ts;
+        double sn, cs;
+        sincos(f * pp, &sn, &cs);
+        const double xv = x.at(((long long)w * T + m) * n + i);
+        re += sn * xv;
+        im += cs * xv;
+    }
+    out[(long long)blockIdx.y * n + i] = make_double2(re, im);
+}
+
+// Shift path of the coherent search.  With f_k n_code ts = shift_k + phi_k the window's carrier is
+// j e^(-j 2 pi shift_k n / n_code) e^(-j 2 pi phi_k (n / n_code + m)) (e^(-j 2 pi shift_k m) = 1): bins that share phi share
+// ONE folded row, whose spectrum they read with a circular shift (acq_mixphi_kernel's trick, across the window).  One
+// workgroup reads its 256 samples of each of the window's T blocks once and writes all n_phi folded rows of them:
+//   out[w][j][n] = e^(-j 2 pi phi_j n / n_code) sum_{m < T} x[(w T + m) n_code + n] e^(-j 2 pi phi_j m)
+struct FoldArgs {
+    double phi[ACQ_COH_MAX_PHI];
+    int n_phi, T;
+};
+__global__ __launch_bounds__(256) void acq_fold_phi_kernel(SgxSig x, cplx* __restrict__ out, long long n, FoldArgs a) {
+    __shared__ cplx s_rot[ACQ_COH_MAX_PHI * ACQ_COH_MAX_MS];   // e^(-j 2 pi phi_j m)
+    for (int t = threadIdx.x; t < a.n_phi * a.T; t += 256) {
+        const int j = t / a.T, m = t % a.T;
+        double sn = 0.0, cs = 1.0;
+        if (a.phi[j] != 0.0 && m != 0) sincospi(2.0 * a.phi[j] * (double)m, &sn, &cs);
+        s_rot[t] = make_double2(cs, -sn);
+    }
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int w = blockIdx.y;
+    double xv[ACQ_COH_MAX_MS];
+#pragma unroll
+    for (int m = 0; m < ACQ_COH_MAX_MS; ++m) xv[m] = m < a.T ? x.at(((long long)w * a.T + m) * n + i) : 0.0;
+    for (int j = 0; j < a.n_phi; ++j) {
+        const cplx* __restrict__ rot = s_rot + j * a.T;
+        double re = 0.0, im = 0.0;
+#pragma unroll
+        for (int m = 0; m < ACQ_COH_MAX_MS; ++m) {
+            if (m < a.T) {
+                re = __builtin_fma(xv[m], rot[m].x, re);
+                im = __builtin_fma(xv[m], rot[m].y, im);
+            }
+        }
+        double sn = 0.0, cs = 1.0;
+        if (a.phi[j] != 0.0) sincospi((2.0 * a.phi[j]) * ((double)i / (double)n), &sn, &cs);
+        // (re + j im) (cs - j sn)
+        out[((long long)w * a.n_phi + j) * n + i] = make_double2(__builtin_fma(re, cs, im * sn), __builtin_fma(im, cs, -(re * sn)));
+    }
+}
 static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
                           int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                          int32_t* fineIdx);
+                          int32_t* fineIdx, const CohGrid* g = nullptr);
 static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vector<int>& det_prn,
                         const std::vector<int>& det_phase, const std::vector<int>& det_slot, long long* d_sum,
-                        double* carrFreq, double* codePhase, int32_t* fineIdx);
+                        double* carrFreq, double* codePhase, int32_t* fineIdx, const std::vector<long long>* win = nullptr);
 
 static int acquire_any(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
                        int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
@@ -521,20 +606,22 @@ extern "C" int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_sample
 }
 
 // The round-1 path: one launch per radix pass, every Doppler bin mixed separately (any factorable samplesPerCode).
+// g (coherent search, direct path; else null): n_blocks = the windows, each folded from g->T blocks per Doppler bin of g's
+// grid (acq_fold_direct_kernel) in place of the 1-ms mix
 static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
                           int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                          int32_t* fineIdx) {
+                          int32_t* fineIdx, const CohGrid* g) {
     const long long N = c->n_code;
     const sgx_settings& S = c->s;
     hipStream_t st = c->stream;
 
     // A4 frequency grid (acquisition.py:68,99-101)
-    const int n_bins = (int)(nearbyint(S.acqSearchBand * 2) + 1);
-    SGX_CHECK_ARG(n_bins >= 1 && n_bins <= ACQ_MAX_BINS);
+    const int n_bins = g ? g->n_bins : (int)(nearbyint(S.acqSearchBand * 2) + 1);
+    SGX_CHECK_ARG(n_bins >= 1 && n_bins <= (g ? ACQ_COH_MAX_BINS : ACQ_MAX_BINS));
     MixArgs ma;
     ma.n_bins = n_bins;
     ma.n_blocks = n_blocks;
-    for (int k = 0; k < n_bins; ++k) ma.frq[k] = S.IF - S.acqSearchBand / 2 * 1000 + 500.0 * k;
+    for (int k = 0; k < n_bins && !g; ++k) ma.frq[k] = S.IF - S.acqSearchBand / 2 * 1000 + 500.0 * k;
     const double ts = 1.0 / S.samplingFreq;
     const double tc = 1.0 / S.codeFreqBasis;
     const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
@@ -587,7 +674,16 @@ static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t*
     // ---- PRN-independent part: mix + forward FFTs ------------------------------------------------
     {
         dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows_fwd);
-        acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, ma);
+        if (g) {
+            double* h_frq = (double*)(hsm + 800000);
+            double* d_frq = (double*)(dsm + 800000);
+            static_assert(800000 + ACQ_COH_MAX_BINS * sizeof(double) <= (1 << 20), "inside the small buffers");
+            for (int k = 0; k < n_bins; ++k) h_frq[k] = g->f0 + g->step * k;
+            SGX_HIP(hipMemcpyAsync(d_frq, h_frq, sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, st));
+            acq_fold_direct_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, d_frq, n_bins, g->T);
+        } else {
+            acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, ma);
+        }
         cplx* res = nullptr;
         rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows_fwd, st, &res, N);
         if (rc != SGX_OK) return rc;
@@ -762,7 +858,14 @@ static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t*
 
     // ---- fine frequency search (acquisition.py:167-193) -----------------------------------------------
     {
-        const int rcf = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx);
+        std::vector<long long> win;
+        if (g && g->T > 1) {
+            std::vector<int> det_bin;
+            for (int o : det_slot) det_bin.push_back(freqBin[o]);
+            win = coh_fine_windows(*g, S, N, det_bin);
+        }
+        const int rcf = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx,
+                                     win.empty() ? nullptr : &win);
         if (rcf != SGX_OK) return rcf;
     }
     hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
@@ -772,9 +875,10 @@ static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t*
 }
 
 // Fine frequency search (acquisition.py:167-193) for the detected PRNs; records event ev[2] and synchronises.
+// win (coherent search, else null): [2 d], [2 d + 1] = detection d's own arg-max range in place of [4, uniq - 5)
 static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vector<int>& det_prn,
                         const std::vector<int>& det_phase, const std::vector<int>& det_slot, long long* d_sum,
-                        double* carrFreq, double* codePhase, int32_t* fineIdx) {
+                        double* carrFreq, double* codePhase, int32_t* fineIdx, const std::vector<long long>* win) {
     hipStream_t st = c->stream;
     const sgx_settings& S = c->s;
     const long long N = c->n_code;
@@ -822,12 +926,29 @@ static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vecto
         double* h_pv = (double*)(hsm + 65536);
         long long* h_pi = (long long*)(hsm + 400000);   // (behind the row-map area at 200000)
         d_pi = (long long*)(dsm + 400000);
+        // per-detection ranges (coherent search): to device memory, and their union as the common range
+        long long* d_win = nullptr;
+        long long win_lo = 4, win_hi = uniq - 5;
+        if (win) {
+            long long* h_win = (long long*)(hsm + 810000);
+            d_win = (long long*)(dsm + 810000);
+            static_assert(810000 + 64 * sizeof(long long) <= (1 << 20), "inside the small buffers");
+            memcpy(h_win, win->data(), sizeof(long long) * 2 * (size_t)n_det);
+            SGX_HIP(hipMemcpyAsync(d_win, h_win, sizeof(long long) * 2 * (size_t)n_det, hipMemcpyHostToDevice, st));
+            win_lo = (*win)[0];
+            win_hi = (*win)[1];
+            for (int d = 1; d < n_det; ++d) {
+                win_lo = (*win)[2 * (size_t)d] < win_lo ? (*win)[2 * (size_t)d] : win_lo;
+                win_hi = (*win)[2 * (size_t)d + 1] > win_hi ? (*win)[2 * (size_t)d + 1] : win_hi;
+            }
+        }
         if (fine2) {
             // two kernels with LDS-resident sub-transforms, input built on the fly (the mean comes from the device-side
             // sum: no host look), arg-max fused (sgx_fft.hip)
             nblk = sgx_fft_fine_partials();
-            rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, det_prn.data(), det_phase.data(), n_det, len, d_sum, (double)n_samples, ts,
-                                     tc1, c->d_fine[0], 4, uniq - 5, d_pv, d_pi, st);
+            rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, det_prn.data(), det_phase.data(), n_det, len, d_sum,
+                                     (double)n_samples, ts, tc1, c->d_fine[0], win_lo, win_hi, d_pv, d_pi, st, nullptr,
+                                     nullptr, nullptr, 0, nullptr, nullptr, 0, d_win);
             if (rc != SGX_OK) return rc;
         } else {
             SGX_HIP(hipMemcpyAsync(d_detprn, det_prn.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
@@ -839,7 +960,7 @@ static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vecto
             rc = sgx_fft_forward(&c->plan_fine, c->d_fine[0], c->d_fine[1], n_rows, st, &res, len);
             if (rc != SGX_OK) return rc;
             dim3 g2((unsigned)nblk, (unsigned)n_det);
-            acq_fine_argmax_kernel<<<g2, 256, 0, st>>>(res, npts, 4, uniq - 5, d_pv, d_pi);
+            acq_fine_argmax_kernel<<<g2, 256, 0, st>>>(res, npts, 4, uniq - 5, d_pv, d_pi, d_win);
         }
         SGX_HIP(hipMemcpyAsync(h_pv, d_pv, sizeof(double) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
         SGX_HIP(hipMemcpyAsync(h_pi, d_pi, sizeof(long long) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
@@ -2038,5 +2159,387 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
         freqBin[q.prn0] = q.freqBin;
         fineIdx[q.prn0] = q.fineIdx;
     }
+    return SGX_OK;
+}
+
+// ================================ coherent multi-millisecond acquisition ================================
+// (include/sgx.h, sgx_acquire_coherent; tests/coherent_acq_spec.py is the contract in numpy.)  The search of the reference
+// (acquisition.py:62-166) with T-ms windows in place of its 1-ms blocks, on a finer Doppler grid.
+
+// How the correlation batch is cut: whole PRNs while one PRN's rows fit a chunk (ACQ_DEFAULT_CHUNK_ROWS), else one PRN
+// per batch in runs - of bins for non-coherent sums (rows (bin, window): a run's output rows are whole bins), of windows
+// for the reference rule (rows (window, bin): a run's output rows are whole windows).
+static void coh_plan(CohGrid* g, int n_prn) {
+    const int chunk = ACQ_DEFAULT_CHUNK_ROWS;
+    const int rows_per_prn = g->M * g->n_bins;
+    if (g->path == 0) {   // (acquire_passes: its own chunks of whole PRNs, ACQ_MAX_ROWS rows)
+        g->prn_chunk = ACQ_MAX_ROWS / rows_per_prn;
+        g->runs = 1;
+        g->per_run = g->noncoh ? g->n_bins : g->M;
+    } else if (rows_per_prn <= chunk) {
+        g->prn_chunk = chunk / rows_per_prn;
+        g->runs = 1;
+        g->per_run = g->noncoh ? g->n_bins : g->M;
+    } else {
+        g->prn_chunk = 1;
+        const int total = g->noncoh ? g->n_bins : g->M;
+        const int other = g->noncoh ? g->M : g->n_bins;
+        g->per_run = chunk / other < 1 ? 1 : chunk / other;
+        g->runs = (total + g->per_run - 1) / g->per_run;
+    }
+    if (g->prn_chunk < 1) g->prn_chunk = 1;
+    if (g->prn_chunk > n_prn) g->prn_chunk = n_prn;
+}
+
+// Parameters -> grid, phi decomposition, path and batches.  SGX_E_ARG (with the reason) for anything out of range.
+static int coh_grid(const sgx_settings& S, long long N, const sgx_acq_params* p, int n_prn, CohGrid* g) {
+    if (!p) {
+        sgx_set_error("bad argument: no sgx_acq_params");
+        return SGX_E_ARG;
+    }
+    const int T = p->coherent_ms, M = p->n_windows;
+    const double step = p->bin_step_hz;
+    if (T < 1 || T > ACQ_COH_MAX_MS || M < 1 || M > ACQ_COH_MAX_WINDOWS || (long long)T * M > ACQ_COH_MAX_SPAN_MS) {
+        sgx_set_error("bad argument: coherent_ms %d x n_windows %d (coherent_ms 1..%d, n_windows 1..%d, product <= %d ms)",
+                      T, M, ACQ_COH_MAX_MS, ACQ_COH_MAX_WINDOWS, ACQ_COH_MAX_SPAN_MS);
+        return SGX_E_ARG;
+    }
+    if ((p->noncoh != 0 && p->noncoh != 1) || p->reserved != 0) {
+        sgx_set_error("bad argument: noncoh %d (0 or 1), reserved %d (0)", p->noncoh, p->reserved);
+        return SGX_E_ARG;
+    }
+    if (!(step > 0.0) || !std::isfinite(step)) {
+        sgx_set_error("bad argument: bin_step_hz %g (must be > 0)", step);
+        return SGX_E_ARG;
+    }
+    const double nb = nearbyint(S.acqSearchBand * 1000.0 / step) + 1;
+    if (!(nb >= 1.0 && nb <= (double)ACQ_COH_MAX_BINS)) {
+        sgx_set_error("bad argument: a %g kHz band at %g Hz steps is %.0f Doppler bins (at most %d)", S.acqSearchBand, step,
+                      nb, ACQ_COH_MAX_BINS);
+        return SGX_E_ARG;
+    }
+    if (N < 2) {
+        sgx_set_error("bad argument: %lld samples per code", N);
+        return SGX_E_ARG;
+    }
+    g->T = T;
+    g->M = M;
+    g->noncoh = p->noncoh;
+    g->step = step;
+    g->f0 = S.IF - S.acqSearchBand / 2 * 1000;
+    g->n_bins = (int)nb;
+    g->bin_map.assign((size_t)g->n_bins, make_int2(0, 0));
+    g->phi.clear();
+    for (int k = 0; k < g->n_bins; ++k) {
+        const double f = g->f0 + step * k;
+        const double ratio = f * (double)N / S.samplingFreq;   // f N ts = shift + phi (acquire_four_step's rule)
+        const double sh = floor(ratio + 1e-9);
+        double phi = ratio - sh;
+        if (phi < 1e-9) phi = 0.0;
+        int j = -1;
+        for (size_t q = 0; q < g->phi.size() && j < 0; ++q)
+            if (fabs(g->phi[q] - phi) < 1e-9) j = (int)q;
+        if (j < 0) {
+            j = (int)g->phi.size();
+            g->phi.push_back(phi);
+        }
+        long long shm = (long long)sh % N;
+        if (shm < 0) shm += N;
+        g->bin_map[(size_t)k] = make_int2(j, (int)shm);
+    }
+    g->n_phi = (int)g->phi.size();
+    g->path = (sgx_fft4_supported(N) && g->n_phi <= ACQ_COH_MAX_PHI) ? 1 : 0;
+    if (g->path == 0 && (long long)M * g->n_bins > ACQ_MAX_ROWS) {
+        sgx_set_error("bad argument: the direct path (%d distinct Doppler fractions, %lld samples per code) takes at most "
+                      "%d windows x bins, asked for %d x %d", g->n_phi, N, ACQ_MAX_ROWS, M, g->n_bins);
+        return SGX_E_ARG;
+    }
+    coh_plan(g, n_prn);
+    return SGX_OK;
+}
+
+// Detection d's fine-search range for T > 1: the spectrum indices i of the 2^k-point transform (frequency i fs / npts)
+// within one bin step of its coarse bin, inside the reference's [4, uniq - 5).
+static std::vector<long long> coh_fine_windows(const CohGrid& g, const sgx_settings& S, long long N,
+                                               const std::vector<int>& det_bin) {
+    const long long len = 10 * N;
+    const long long npts = 8ll << (long long)ceil(log2((double)len));
+    const long long uniq = (long long)ceil((double)(npts + 1) / 2.0);
+    std::vector<long long> win;
+    for (int k : det_bin) {
+        const double fk = g.f0 + g.step * k;
+        long long lo = (long long)ceil(((fk - g.step) * (double)npts) / S.samplingFreq);
+        long long hi = (long long)floor(((fk + g.step) * (double)npts) / S.samplingFreq) + 1;
+        if (lo < 4) lo = 4;
+        if (hi > uniq - 5) hi = uniq - 5;
+        if (hi <= lo) hi = lo + 1;
+        win.push_back(lo);
+        win.push_back(hi);
+    }
+    return win;
+}
+
+// The shift path: folded rows per (window, phi), their forward spectra once, the correlation batches of acquire_four_step
+// (Fft4Fuse reads each bin's row with its circular shift), the same peak kernels, then one host look and the fine search.
+static int acquire_coherent_shift(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                                  const CohGrid& g, double* carrFreq, double* codePhase, double* peakMetric,
+                                  int32_t* freqBin, int32_t* fineIdx) {
+    const long long N = c->n_code;
+    const sgx_settings& S = c->s;
+    hipStream_t st = c->stream;
+    const double ts = 1.0 / S.samplingFreq;
+    const double tc = 1.0 / S.codeFreqBasis;
+    const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
+    const int n_bins = g.n_bins, n_phi = g.n_phi, M = g.M, noncoh = g.noncoh;
+    int rc = sgx_fft_plan_create(&c->plan_code, N);
+    if (rc != SGX_OK) return rc;
+
+    // ---- scratch ------------------------------------------------------------------------------
+    const int rows_fwd = M * n_phi;
+    const int rows_per_prn = M * n_bins;
+    const int run_rows = g.runs == 1 ? g.prn_chunk * rows_per_prn : g.per_run * (noncoh ? M : n_bins);
+    const size_t row_bytes = sizeof(cplx) * (size_t)N;
+    size_t work_rows = (size_t)run_rows;
+    if (work_rows < (size_t)(rows_fwd + n_prn)) work_rows = (size_t)(rows_fwd + n_prn);
+    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
+    const int nres = sgx_fft4_residues();
+    const int out_per_prn = noncoh ? n_bins : rows_per_prn;
+    const int rows_out_all = n_prn * out_per_prn;
+    // peak and second peak from one pass (acq_rowtop2_peak_kernel): the four-step length has 217 residues, so any exclusion
+    // list (2 spc + 1 = 75 indices at that length's rate) fits
+    if (2 * spc + 1 > nres) {
+        sgx_set_error("coherent acquisition: %d samples per chip exceed the one-pass second-peak search", spc);
+        return SGX_E_ARG;
+    }
+    const size_t part_bytes = (((size_t)rows_out_all * (size_t)nres * 20) + 255) / 256 * 256;
+    const size_t red_bytes = (part_bytes + (size_t)rows_out_all * 12 + 1023) / 256 * 256;
+    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, red_bytes)) != SGX_OK) return rc;
+    char* red = (char*)c->d_pow;
+    double* d_t2b1 = (double*)red;
+    double* d_t2b2 = d_t2b1 + (size_t)rows_out_all * nres;
+    int* d_t2i1 = (int*)(d_t2b2 + (size_t)rows_out_all * nres);
+    double* d_rowmax = (double*)(red + part_bytes);
+    int* d_rowarg = (int*)(red + part_bytes + (size_t)rows_out_all * 8);
+
+    char* dsm = (char*)c->d_small;
+    char* hsm = (char*)c->h_small;
+    long long* d_sum = (long long*)dsm;
+    int* d_prn = (int*)(dsm + 64);
+    int2* d_binmap = (int2*)(dsm + 1024);              // [n_bins <= ACQ_COH_MAX_BINS]
+    double* d_second = (double*)(dsm + 1024 + 12 * 4096);
+    int* d_arrived = (int*)(dsm + 51200);
+    PeakOut* d_po = (PeakOut*)(dsm + 620000);
+    static_assert(1024 + ACQ_COH_MAX_BINS * sizeof(int2) <= 1024 + 12 * 4096, "bin map in front of the second peaks");
+    // (host staging in the pinned small buffer: the copies are queued, the buffer is not touched again before the look)
+    int* h_prn = (int*)(hsm + 800000);
+    int2* h_binmap = (int2*)(hsm + 800000 + 256);
+    for (int i = 0; i < n_prn; ++i) h_prn[i] = prn0[i];
+    for (int k = 0; k < n_bins; ++k) h_binmap[k] = g.bin_map[(size_t)k];
+
+    hipEventRecord(c->ev[0], st);
+    cplx* const d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
+    {
+        SGX_HIP(hipMemcpyAsync(d_prn, h_prn, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemcpyAsync(d_binmap, h_binmap, sizeof(int2) * (size_t)n_bins, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemsetAsync(d_sum, 0, 8, st));
+        SGX_HIP(hipMemsetAsync(d_second, 0, sizeof(double) * 32, st));
+        SGX_HIP(hipMemsetAsync(d_arrived, 0, sizeof(int) * 64, st));
+        if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)n_samples, d_sum);
+        else acq_sum_kernel<<<64, 256, 0, st>>>(x.i8, (long long)n_samples, d_sum);
+        FoldArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.n_phi = n_phi;
+        fa.T = g.T;
+        for (int j = 0; j < n_phi; ++j) fa.phi[j] = g.phi[(size_t)j];
+        const unsigned gx = (unsigned)((N + 255) / 256);
+        acq_fold_phi_kernel<<<dim3(gx, (unsigned)M), 256, 0, st>>>(x, c->d_work[1], N, fa);
+        acq_code_kernel<<<dim3(gx, (unsigned)n_prn), 256, 0, st>>>(c->d_codes, d_prn, c->d_work[1] + (size_t)rows_fwd * (size_t)N,
+                                                                   N, ts, tc);
+        rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
+        if (rc != SGX_OK) return rc;
+    }
+    for (int i = 0; i < n_prn; ++i) {
+        carrFreq[i] = 0.0;
+        codePhase[i] = 0.0;
+        peakMetric[i] = 0.0;
+        freqBin[i] = -1;
+        fineIdx[i] = -1;
+    }
+    // ---- correlation: batches of whole PRNs, or one PRN in runs of bins (noncoh) / windows (reference rule) ----------
+    const double inv_n = 1.0 / (double)N;
+    const int total = noncoh ? n_bins : M;
+    for (int p0 = 0; p0 < n_prn; p0 += g.prn_chunk)
+        for (int r0 = 0; r0 < total; r0 += (g.runs == 1 ? total : g.per_run)) {
+            const int np = (p0 + g.prn_chunk <= n_prn) ? g.prn_chunk : (n_prn - p0);
+            const int nr = g.runs == 1 ? total : (r0 + g.per_run <= total ? g.per_run : total - r0);
+            Fft4Fuse fu;
+            fu.mul_f = d_codefd;
+            fu.n_phi = n_phi;
+            fu.prn_base = p0;
+            size_t out0;
+            if (noncoh) {
+                fu.mul_x = c->d_fwd;
+                fu.bin_map = d_binmap + r0;
+                fu.n_bins = nr;
+                fu.n_blocks = M;
+                fu.rows_per_prn = nr * M;
+                fu.blocks_fast = 1;
+                fu.sum_blocks = M;
+                out0 = (size_t)p0 * out_per_prn + (size_t)r0;
+            } else {
+                fu.mul_x = c->d_fwd + (size_t)r0 * n_phi * (size_t)N;   // (a run of windows reads its windows' rows)
+                fu.bin_map = d_binmap;
+                fu.n_bins = n_bins;
+                fu.n_blocks = nr;
+                fu.rows_per_prn = nr * n_bins;
+                fu.blocks_fast = 0;
+                fu.sum_blocks = 1;
+                out0 = (size_t)p0 * out_per_prn + (size_t)r0 * n_bins;
+            }
+            fu.t2_b1 = d_t2b1 + out0 * nres;
+            fu.t2_b2 = d_t2b2 + out0 * nres;
+            fu.t2_i1 = d_t2i1 + out0 * nres;
+            fu.inv_n = inv_n;
+            rc = sgx_fft4_forward(&c->plan_code, nullptr, c->d_work[0], nullptr, (int64_t)np * fu.rows_per_prn, st, &fu);
+            if (rc != SGX_OK) return rc;
+        }
+    // ---- row maxima, block (window) choice, global peak, exclusion list, second peak: acquire_four_step's kernels -------
+    const unsigned long long seq = ++c->look_seq;
+    const long long fine_len = 10 * N;
+    {
+        PublishArgs pub;
+        memset(&pub, 0, sizeof(pub));   // (no stage: the publish kernel below writes the page)
+        acq_rowtop2_peak_kernel<<<rows_out_all, 64, 0, st>>>(d_t2b1, d_t2b2, d_t2i1, nres, d_rowmax, d_rowarg, d_arrived, n_prn,
+                                                             out_per_prn, n_bins, M, noncoh, N, spc, d_po, d_second, pub);
+    }
+    acq_publish_kernel<<<1, 64, 0, st>>>(d_po, d_second, n_prn, (CoarseLook*)c->d_look, seq, d_prn, S.acqThreshold, fine_len,
+                                         (long long)n_samples, nullptr);
+    hipEventRecord(c->ev[1], st);
+    SGX_HIP(hipGetLastError());
+    rc = coarse_look_wait(c, seq);
+    if (rc != SGX_OK) return rc;
+    const CoarseLook* look = (const CoarseLook*)c->h_look;
+    const PeakOut* h_po = &look->po;
+    for (int pi = 0; pi < n_prn; ++pi) {
+        if (h_po->index_error[pi]) {
+            sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
+                          "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
+                          N, N, prn0[pi], h_po->cph[pi]);
+            return SGX_E_INDEX;
+        }
+    }
+    std::vector<int> det_prn, det_phase, det_slot, det_bin;
+    for (int pi = 0; pi < n_prn; ++pi) {
+        const double ratio = h_po->peak[pi] / look->second[pi];
+        peakMetric[pi] = ratio;
+        freqBin[pi] = h_po->fbi[pi];
+        if (ratio > S.acqThreshold) {
+            det_prn.push_back(prn0[pi]);
+            det_phase.push_back(h_po->cph[pi]);
+            det_slot.push_back(pi);
+            det_bin.push_back(h_po->fbi[pi]);
+        }
+    }
+    std::vector<long long> win;
+    if (g.T > 1) win = coh_fine_windows(g, S, N, det_bin);
+    rc = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx,
+                      win.empty() ? nullptr : &win);
+    if (rc != SGX_OK) return rc;
+    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
+    hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
+    hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
+    return SGX_OK;
+}
+
+static int acquire_coherent_any(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, const CohGrid& g,
+                                double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    if (g.path == 1)
+        return acquire_coherent_shift(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+    return acquire_passes(c, x, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx, &g);
+}
+
+// Everything an entry point checks before it touches the device: arguments, grid, record length.
+static int coherent_checks(sgx_ctx* c, size_t n_samples, const int32_t* prn0, int32_t n_prn, const sgx_acq_params* p,
+                           CohGrid* g, bool* legacy) {
+    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32);
+    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
+    const int rc = coh_grid(c->s, c->n_code, p, n_prn, g);
+    if (rc != SGX_OK) return rc;
+    const long long need = (long long)g->T * g->M * c->n_code;
+    if ((long long)n_samples < need) {
+        sgx_set_error("record window too short: %zu samples, coherent_ms %d x n_windows %d need %lld (%lld short)",
+                      n_samples, g->T, g->M, need, need - (long long)n_samples);
+        return SGX_E_RANGE;
+    }
+    *legacy = g->T == 1 && g->step == 500.0;   // the reference's grid: sgx_acquire itself
+    return SGX_OK;
+}
+
+extern "C" int sgx_acquire_coherent(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
+                                    int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,
+                                    double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    SGX_CHECK_ARG(c && r && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    SGX_CHECK_ARG(offset <= r->n && n_samples <= r->n - offset);
+    CohGrid g;
+    bool legacy = false;
+    int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
+    if (rc != SGX_OK) return rc;
+    if (legacy)
+        return sgx_acquire(c, r, offset, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
+                           fineIdx);
+    rc = sgx_if_require(r, offset + n_samples);   // a record that is still streaming in
+    if (rc != SGX_OK) return rc;
+    SGX_HIP(hipSetDevice(c->device));
+    SgxSig x;
+    x.i8 = r->d + offset;
+    x.f64 = nullptr;
+    return acquire_coherent_any(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+}
+
+extern "C" int sgx_acquire_coherent_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0,
+                                        int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,
+                                        double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    SGX_CHECK_ARG(c && signal && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    CohGrid g;
+    bool legacy = false;
+    int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
+    if (rc != SGX_OK) return rc;
+    if (legacy)
+        return sgx_acquire_f64(c, signal, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
+                               fineIdx);
+    SGX_HIP(hipSetDevice(c->device));
+    const size_t need = sizeof(double) * (n_samples + 64);
+    if (c->cap_sig64 < need) {
+        if (c->d_sig64) hipFree(c->d_sig64);
+        c->d_sig64 = nullptr;
+        c->cap_sig64 = 0;
+        if (hipMalloc((void**)&c->d_sig64, need) != hipSuccess) {
+            sgx_set_error("hipMalloc of %zu signal bytes failed", need);
+            return SGX_E_NOMEM;
+        }
+        c->cap_sig64 = need;
+    }
+    SGX_HIP(hipMemcpyAsync(c->d_sig64, signal, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
+    SGX_HIP(hipStreamSynchronize(c->stream));   // the caller may free `signal` on return
+    SgxSig x;
+    x.i8 = nullptr;
+    x.f64 = c->d_sig64;
+    return acquire_coherent_any(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+}
+
+extern "C" int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, int32_t* n_bins, int32_t* n_phi,
+                                         int32_t* path, int32_t* prn_chunk, int32_t* bin_runs) {
+    SGX_CHECK_ARG(s && p && n_bins && n_phi && path && prn_chunk && bin_runs);
+    SGX_CHECK_ARG(s->codeLength > 0 && s->codeFreqBasis > 0 && s->samplingFreq > 0);
+    CohGrid g;
+    const int rc = coh_grid(*s, sgx_host_samples_per_code(s), p, 32, &g);
+    if (rc != SGX_OK) return rc;
+    *n_bins = g.n_bins;
+    *n_phi = g.n_phi;
+    *path = g.path;
+    *prn_chunk = g.prn_chunk;
+    *bin_runs = g.runs;
     return SGX_OK;
 }

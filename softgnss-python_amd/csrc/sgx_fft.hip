@@ -1243,6 +1243,9 @@ struct FineArgs {
     const int* stage_src;
     int* stage_dst;
     int stage_words;
+    // per-detection arg-max ranges (device, [2 d] lo, [2 d + 1] hi, inside [lo, hi)), or null: [lo, hi) for every one;
+    // read by fine_rows_kernel<true> only
+    const long long* win;
 };
 
 #define FINE_DONE_SLOT 80
@@ -1362,6 +1365,8 @@ __global__ __launch_bounds__(FF_TPB) void fine_cols_kernel(FineArgs a, int n_til
 #undef FC_ONE
 }
 
+// WIN: detection d's arg-max runs over its own range a.win[2 d .. 2 d + 1] (inside the common [a.lo, a.hi))
+template <bool WIN>
 __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pairs_host) {
     const int n_det_k = FA_NDET(a);
     const int n_pairs = a.det ? (FF_N1 / 2) * ((n_det_k + 1) / 2) : n_pairs_host;
@@ -1432,6 +1437,17 @@ __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pai
         // 4096 - k2 (k1 = 0, k2 > 0)
         double best[2] = {-1.0, -1.0};
         long long arg[2] = {a.lo, a.lo};
+        long long wlo[2] = {a.lo, a.lo}, whi[2] = {a.hi, a.hi};
+        if (WIN) {
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                if (2 * r + d < n_det_k) {
+                    wlo[d] = a.win[2 * (2 * r + d)];
+                    whi[d] = a.win[2 * (2 * r + d) + 1];
+                }
+                arg[d] = wlo[d];
+            }
+        }
         for (int rr = 0; rr < 2; ++rr) {
             const int k1 = rr == 0 ? rowA : rowB;
             const cplx* __restrict__ me = buf + rr * RP;
@@ -1444,6 +1460,7 @@ __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pai
                 const cplx w = other[ko + (ko >> 4)];
 #pragma unroll
                 for (int d = 0; d < 2; ++d) {
+                    if (WIN && (k < wlo[d] || k >= whi[d])) continue;
                     const double sgn = d ? -1.0 : 1.0;
                     const double re = z.x + sgn * w.x, im = z.y - sgn * w.y;   // z +- conj(w)
                     const double v = re * re + im * im;
@@ -1566,7 +1583,7 @@ int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, cons
                         const int* det_phase, int n_det, long long len, const long long* d_sum, double n_mean, double ts,
                         double tc1, cplx* work, long long lo, long long hi, double* pv, long long* pi, hipStream_t st,
                         const int* d_det, long long* out_bi, unsigned long long* out_seq, unsigned long long seq,
-                        const int* stage_src, int* stage_dst, int stage_words) {
+                        const int* stage_src, int* stage_dst, int stage_words, const long long* win) {
     // d_det != nullptr: device-led - the detection list is in device memory (n_det here = the most it can hold)
     if (!plan->tw_hi || !sgx_fft_fine_supported(plan->n) || n_det < 1 || n_det > 32) {
         sgx_set_error("sgx_fft_fine_search: %lld points not supported", (long long)plan->n);
@@ -1635,6 +1652,7 @@ int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, cons
     a.stage_src = stage_src;
     a.stage_dst = stage_dst;
     a.stage_words = (d_det && stage_src && stage_dst) ? stage_words : 0;
+    a.win = d_det ? nullptr : win;
     a.seq = seq;
     const int n_rows = (n_det + 1) / 2;
     const size_t lds_c = sizeof(cplx) * (FF_N1 * FF_C + FF_N1);
@@ -1642,7 +1660,8 @@ int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, cons
     static std::atomic<bool> once[SGX_MAX_DEVICES];
     if (!once[dev].load()) {
         hipFuncSetAttribute((const void*)fine_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-        hipFuncSetAttribute((const void*)fine_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+        hipFuncSetAttribute((const void*)fine_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+        hipFuncSetAttribute((const void*)fine_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
         once[dev].store(true);
     }
     int cus = 256;
@@ -1656,7 +1675,8 @@ int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, cons
         // persistent workgroups, one per CU (128 KB of LDS each), walking the (spectrum, row pair) list
         const int n_pairs = (FF_N1 / 2) * n_rows;
         const int grid = n_pairs < cus ? n_pairs : cus;
-        fine_rows_kernel<<<grid, FF_TPB, lds_r, st>>>(a, n_pairs);
+        if (a.win) fine_rows_kernel<true><<<grid, FF_TPB, lds_r, st>>>(a, n_pairs);
+        else fine_rows_kernel<false><<<grid, FF_TPB, lds_r, st>>>(a, n_pairs);
     }
     SGX_HIP(hipGetLastError());
     return SGX_OK;

@@ -237,7 +237,9 @@ int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, cons
                         long long* out_bi = nullptr /* device-led: [32] arg-max per detection (pinned page) ... */,
                         unsigned long long* out_seq = nullptr /* ... then this word = seq */, unsigned long long seq = 0,
                         const int* stage_src = nullptr /* device-led: dwords copied to stage_dst (the page) before the word */,
-                        int* stage_dst = nullptr, int stage_words = 0);
+                        int* stage_dst = nullptr, int stage_words = 0,
+                        const long long* win = nullptr /* host-led only: device [2 d] lo, [2 d + 1] hi per detection,
+                                                          inside [lo, hi) */);
 bool sgx_fft4_supported(int64_t n);
 int sgx_fft4_row_blocks(void);
 int sgx_fft4_residues(void);

@@ -89,6 +89,15 @@ _LOCK_DEFAULTS = (
     ("maxLockFail", 25),            # the fail counter (fail +1, pass -1, not below 0) at which a channel is lost
 )
 
+# the coarse search postProcessing() asks for (AcquisitionResult.acquire; INTEGRATION.md, "Coherent acquisition"): the
+# reference's is 2 one-millisecond blocks on a 500 Hz grid
+_ACQ_DEFAULTS = (
+    ("acqCoherentMs", 1),           # ms summed coherently per window
+    ("acqBlocks", 2),               # windows
+    ("acqNonCoherent", False),      # sum |corr|^2 over the windows instead of keeping the larger one
+    ("acqBinStep", None),           # Doppler step in Hz; None: 500 / acqCoherentMs
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -97,7 +106,7 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -197,6 +206,11 @@ class Settings(object):
         plt.ylabel('Number in bin')
         return self.probe
 
+    def acquisitionLength(self):
+        """Samples postProcessing() reads for acquisition: 11 ms (the fine search needs codePhase + 10 ms), or all the
+        coarse search's windows, acqCoherentMs x acqBlocks ms, where that is longer."""
+        return max(11, int(self.acqCoherentMs) * int(self.acqBlocks)) * self.samplesPerCode
+
     def postProcessing(self, fileNameStr=None):
         """acquire -> preRun -> track -> postNavigate on a record file: the call sequence of reference
         initialize.py:420-515 without the plots and without the .npy cache of the tracking results.
@@ -213,10 +227,11 @@ class Settings(object):
                              'postProcessing() always acquires (initialize.py:476-490)')
         with open(name, 'rb') as fid:
             fid.seek(self.skipNumberOfBytes, 0)
-            data = np.fromfile(fid, self.dataType, 11 * self.samplesPerCode)
+            data = np.fromfile(fid, self.dataType, self.acquisitionLength())
             print('   Acquiring satellites...')
             acqResults = acquisition.AcquisitionResult(self)
-            acqResults.acquire(data)
+            acqResults.acquire(data, n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
+                               coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
             if not np.any(acqResults.carrFreq):
                 print('No GNSS signals detected, signal processing finished.')
                 return acqResults, None, None

@@ -1,7 +1,7 @@
 """The reference's main.py (banner, probeData, postProcessing) for this engine:
 
     python -m softgnss-python_amd.main record.bin [--fs 38192000 --IF 9548000 --ms 37000 --channels 8 --skip 0]
-                                                  [--lock-detector]
+                                                  [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -26,12 +26,18 @@ def main(argv=None):
     ap.add_argument("--no-probe", action="store_true", help="skip the raw-data statistics")
     ap.add_argument("--lock-detector", action="store_true",
                     help="estimate C/N0 per channel, print it after tracking and drop the channels lost on the way")
+    ap.add_argument("--acq-coherent-ms", type=int, default=None,
+                    help="acquisition: ms summed coherently per window (weak signals: 10; Doppler step 500 / T Hz)")
+    ap.add_argument("--acq-blocks", type=int, default=None, help="acquisition: number of windows (reference: 2)")
+    ap.add_argument("--acq-noncoh", action="store_true", help="acquisition: sum the windows non-coherently")
     a = ap.parse_args(argv)
     print('\nWelcome to:  softGNSS on MI355X\n')
     settings = initialize.Settings()
     settings.fileName = a.fileName
     for name, val in (("samplingFreq", a.fs), ("IF", a.IF), ("msToProcess", a.ms), ("numberOfChannels", a.channels),
-                      ("skipNumberOfBytes", a.skip), ("lockDetector", True if a.lock_detector else None)):
+                      ("skipNumberOfBytes", a.skip), ("lockDetector", True if a.lock_detector else None),
+                      ("acqCoherentMs", a.acq_coherent_ms), ("acqBlocks", a.acq_blocks),
+                      ("acqNonCoherent", True if a.acq_noncoh else None)):
         if val is not None:
             setattr(settings, name, val)
     if not a.no_probe:

@@ -94,12 +94,16 @@ class LocalGather(object):
         return np.asarray(buf).reshape(1, -1)
 
 
-def acquire_sharded(acq, long_signal, rank, world, gather, n_prn=None, n_blocks=2, noncoh=False):
+def acquire_sharded(acq, long_signal, rank, world, gather, n_prn=None, n_blocks=2, noncoh=False, coherent_ms=1):
     """AcquisitionResult.acquire with the PRN search sharded over `world` ranks.
 
     Every rank searches its contiguous share of PRN indices on its own GPU, the peaks are
     all-gathered, and every rank ends with the same 32-entry result arrays as a single-GPU call.
+    Only the 1-ms search is sharded: coherent_ms != 1 raises ValueError.
     """
+    if int(coherent_ms) != 1:
+        raise ValueError("acquire_sharded searches 1-ms blocks only (coherent_ms=%r); run AcquisitionResult.acquire"
+                         % (coherent_ms,))
     settings = acq.settings
     if n_prn is None:
         n_prn = len(settings.acqSatelliteList)
