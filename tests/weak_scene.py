@@ -26,11 +26,17 @@ def code_drift_samples(doppler, ms, fs=FS):
     return -doppler / L1 * ms * 1e-3 * fs
 
 
-def generate(ms, sats=WEAK_SATS, seed=20261016, sigma=SIGMA, fs=FS, if_=IF, chunk=1 << 21):
+def generate(ms, sats=WEAK_SATS, seed=20261016, sigma=SIGMA, fs=FS, if_=IF, chunk=1 << 21, nav_bits=True):
+    """`sats` rows may carry a fifth entry (first ms, last ms): the satellite is on from sample round(first ms) up to round(last ms) only (the
+    random draws do not depend on it).  nav_bits=False: no data-bit flips (the draws are made all the same)."""
     n_total = int(round(ms * 1e-3 * fs))
     rng = np.random.default_rng(seed)
+    on = {row[0]: row[4] for row in sats if len(row) > 4 and row[4] is not None}
+    sats = tuple(tuple(row[:4]) for row in sats)
     codes = {p: orc.generate_ca_code(p).astype(np.float64) for p, _, _, _ in sats}
     bits = {p: rng.choice([-1.0, 1.0], size=int(ms) // 20 + 3) for p, _, _, _ in sats}
+    if not nav_bits:
+        bits = {p: np.ones_like(b) for p, b in bits.items()}
     bit_off = {p: rng.uniform(0.0, 20.0) for p, _, _, _ in sats}
     ph0 = {p: rng.uniform(0.0, 2 * np.pi) for p, _, _, _ in sats}
     out = np.empty(n_total, dtype=np.int8)
@@ -42,6 +48,9 @@ def generate(ms, sats=WEAK_SATS, seed=20261016, sigma=SIGMA, fs=FS, if_=IF, chun
             fc = CHIP_RATE * (1.0 + dop / L1)
             chip = np.floor((idx - s0) / fs * fc).astype(np.int64) % 1023
             bit = bits[p][np.floor((t * 1e3 + bit_off[p]) / 20.0).astype(np.int64)]
-            y += amplitude(cn0, sigma, fs) * codes[p][chip] * bit * np.cos(2 * np.pi * (if_ + dop) * t + ph0[p])
+            sig = amplitude(cn0, sigma, fs) * codes[p][chip] * bit * np.cos(2 * np.pi * (if_ + dop) * t + ph0[p])
+            if p in on:
+                sig *= (idx >= round(on[p][0] * 1e-3 * fs)) & (idx < round(on[p][1] * 1e-3 * fs))
+            y += sig
         out[start:start + idx.size] = np.clip(np.round(y), -128, 127).astype(np.int8)
     return out
