@@ -367,6 +367,53 @@ int sgx_track_quality(sgx_ctx* c, const double* I_P, const double* Q_P, int64_t 
                       const int32_t* ms_done, const sgx_lock_params* p, double* cno, double* carr_lock, uint8_t* pass,
                       int32_t* lost);
 
+/* ---- multi-correlator replay of tracked channels (no reference counterpart: tracking.py:166-219 forms three arms) ----
+ * Once a channel has been tracked, every block's code rate, carrier rate, start and length are on record, so the
+ * correlation at ANY code offset can be formed afterwards, all blocks at once.  Block k of a channel is rebuilt exactly as
+ * tracking.py:148-251 forms it, from the rows absoluteSample, codeFreq, carrFreq (rows 0, 1, 2 of the channel's series):
+ *   code_freq_k = codeFreq[k-1] (k = 0: codeFreqBasis), carr_freq_k = carrFreq[k-1] (k = 0: acquiredFreq),
+ *   step = code_freq_k / fs, blk = ceil((codeLength - rem_code) / step), start byte pos_k = absoluteSample[k-1]
+ *   (k = 0: skipNumberOfBytes + codePhase), arg_n = carr_freq_k 2.0 pi (n / fs) + rem_carr, and after the block
+ *   rem_code = tp[blk-1] + step - 1023.0 with tp = linspace(rem_code, blk step + rem_code, blk, endpoint=False),
+ *   rem_carr = arg_blk mod 2 pi (both start at 0).
+ * For tap offset d_j (chips) and block k < ms_done[c]:
+ *   t = linspace(rem_code + d_j, blk step + rem_code + d_j, blk, endpoint=False), chip_n = code[(ceil(t_n) - 1) mod 1023],
+ *   I[j][k] = sum_n chip_n sin(arg_n) x_n,  Q[j][k] = sum_n chip_n cos(arg_n) x_n
+ * so d = -dllCorrelatorSpacing, 0, +dllCorrelatorSpacing are the reference's early, prompt and late arms.  Blocks
+ * k >= ms_done[c] and channels with prn == 0 hold 0.  tests/replay_spec.py restates all of it in numpy.
+ *
+ * sgx_replay_state: the per-block state, state[c * ms + k], from the series ([n_ch][SGX_NUM_SERIES][ms], any host memory);
+ * exact host code, needs no GPU.  rec_bytes: bytes of the record behind rec_file_offset (< 0: not checked).  Entries
+ * k >= ms_done[c] (ms_done NULL: ms) and channels that are off are zeroed.  SGX_E_ARG when a rebuilt block end disagrees
+ * with absoluteSample[k] - the series is not a tracking result of these channels - or a rate is not finite; SGX_E_RANGE
+ * when a block starts before the record or ends beyond it; sgx_last_error names the channel and the block.  data_type:
+ * SGX_DT_INT8, SGX_DT_UINT8 or SGX_DT_INT16 (BYTE positions, as sgx_track_ex: an int16 channel may start on an odd byte);
+ * every other SGX_DT_* is SGX_E_ARG (float, wide-integer and complex records are not replayed).
+ *
+ * sgx_track_replay: I and Q of n_taps taps on the resident record (a streaming record is waited for, as sgx_if_wait):
+ * out is [n_ch][n_taps][2][ms] float64, I then Q.  One launch covers every (channel, block); two calls give identical
+ * bytes.  SGX_E_ARG, before anything is launched or written, for n_taps outside [1, SGX_REPLAY_MAX_TAPS], a tap that is
+ * not finite, a NULL pointer, an ms_done entry outside [0, ms], a data_type other than the three above, and whatever
+ * sgx_replay_state refuses (with its code).  sgx_replay_timing: HIP-event times of the last replay on this context - the
+ * kernel alone, and the whole device side (state upload, kernel, result copy). */
+#define SGX_REPLAY_MAX_TAPS 64
+typedef struct sgx_replay_block {
+    int64_t start;      /* file byte position of the block's first sample */
+    double rem_code;    /* chips */
+    double rem_carr;    /* rad */
+    double step;        /* chips per sample */
+    double carr_freq;   /* Hz */
+    int32_t blk;        /* samples */
+    int32_t reserved;
+} sgx_replay_block;     /* 48 bytes */
+int sgx_replay_state(const sgx_settings* s, int32_t data_type, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
+                     const int32_t* ms_done, const double* series, int64_t rec_file_offset, int64_t rec_bytes,
+                     sgx_replay_block* state);
+int sgx_track_replay(sgx_ctx* c, const sgx_if* rec, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
+                     int32_t ms, const int32_t* ms_done, const double* series, int32_t data_type, const double* taps,
+                     int32_t n_taps, double* out);
+int sgx_replay_timing(sgx_ctx* c, float* kernel_ms, float* device_ms);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

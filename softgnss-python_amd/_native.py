@@ -77,6 +77,16 @@ class LockParams(C.Structure):
                 ("max_fail", C.c_int32)]
 
 
+class ReplayBlock(C.Structure):
+    """sgx_replay_block: one block of a tracked channel as sgx_replay_state rebuilds it (48 bytes)."""
+    _fields_ = [("start", C.c_int64), ("rem_code", C.c_double), ("rem_carr", C.c_double), ("step", C.c_double),
+                ("carr_freq", C.c_double), ("blk", C.c_int32), ("reserved", C.c_int32)]
+
+
+REPLAY_MAX_TAPS = 64
+REPLAY_STATE_DTYPE = np.dtype([("start", "<i8"), ("rem_code", "<f8"), ("rem_carr", "<f8"), ("step", "<f8"),
+                               ("carr_freq", "<f8"), ("blk", "<i4"), ("reserved", "<i4")])
+
 # every symbol include/sgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PROTOS = {
@@ -126,6 +136,9 @@ _PROTOS = {
     "sgx_nav_parity_check": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "sgx_track_quality": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(LockParams), _P, _P, _P,
                                     _P]),
+    "sgx_replay_state": (C.c_int, [C.POINTER(Settings), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
+    "sgx_track_replay": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P]),
+    "sgx_replay_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -310,6 +323,38 @@ def lock_params(settings):
     return LockParams(float(settings.codeLength) / float(settings.codeFreqBasis), float(settings.cnoThreshold),
                       float(settings.carrLockThreshold), int(round(float(settings.cnoInterval))),
                       int(settings.maxLockFail))
+
+
+def _chan_array(chans):
+    arr = (ChanInit * len(chans))()
+    for i, (prn, f, cp) in enumerate(chans):
+        arr[i] = ChanInit(float(f), float(cp), int(prn), 0)
+    return arr
+
+
+def _series3(series, n):
+    a = np.ascontiguousarray(series, dtype=np.float64)
+    if a.ndim != 3 or a.shape[0] != n or a.shape[1] != NUM_SERIES:
+        raise ValueError("expected a [%d, %d, ms] series array, got shape %r" % (n, NUM_SERIES, a.shape))
+    return a
+
+
+def replay_state(settings, chans, series, ms_done=None, data_type=DT_INT8, rec_file_offset=0, rec_bytes=-1):
+    """The per-block state of tracked channels (sgx_replay_state; needs no GPU).  chans: (prn, acquiredFreq, codePhase)
+    per channel, series: float64[n_ch, 13, ms] of track(); rec_bytes < 0: the record's extent is not checked.  Returns a
+    structured array [n_ch, ms] with the fields start, rem_code, rem_carr, step, carr_freq, blk."""
+    n = len(chans)
+    a = _series3(series, n)
+    ms = a.shape[2]
+    done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
+    if done is not None and done.shape != (n,):
+        raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+    st = settings_struct(settings)
+    out = np.zeros((n, ms), dtype=REPLAY_STATE_DTYPE)
+    check(lib().sgx_replay_state(C.byref(st), int(data_type), C.cast(_chan_array(chans), _P), n, ms,
+                                 None if done is None else _ptr(done), _ptr(a), int(rec_file_offset), int(rec_bytes),
+                                 _ptr(out)))
+    return out
 
 
 def _rows(a):
@@ -578,6 +623,29 @@ class Context(object):
                                       None if done is None else _ptr(done), C.byref(params), _ptr(cno), _ptr(cl),
                                       _ptr(ok), _ptr(lost)))
         return cno, cl, ok.astype(bool), lost
+
+    def track_replay(self, rec, chans, series, taps, ms_done=None, rec_file_offset=0, data_type=DT_INT8):
+        """Multi-correlator replay of tracked channels (sgx_track_replay).  chans: (prn, acquiredFreq, codePhase) per
+        channel as they were tracked, series: float64[n_ch, 13, ms] of track(), taps: code offsets in chips (1 .. 64 of
+        them), ms_done: int[n_ch] or None.  Returns float64[n_ch, n_taps, 2, ms]: I then Q per tap."""
+        n = len(chans)
+        a = _series3(series, n)
+        ms = a.shape[2]
+        tp = np.ascontiguousarray(taps, dtype=np.float64).ravel()
+        done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
+        if done is not None and done.shape != (n,):
+            raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+        out = np.zeros((n, tp.size, 2, ms))
+        check(lib().sgx_track_replay(self._h, rec._h, int(rec_file_offset), C.cast(_chan_array(chans), _P), n, ms,
+                                     None if done is None else _ptr(done), _ptr(a), int(data_type), _ptr(tp), tp.size,
+                                     _ptr(out)))
+        return out
+
+    def replay_timing(self):
+        """(kernel ms, device ms) of the last track_replay on this context, from HIP events on its stream."""
+        k, d = C.c_float(0), C.c_float(0)
+        check(lib().sgx_replay_timing(self._h, C.byref(k), C.byref(d)))
+        return k.value, d.value
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

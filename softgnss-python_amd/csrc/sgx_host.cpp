@@ -687,6 +687,95 @@ extern "C" int sgx_trk_math_eval(int32_t fn, double a, double b, double* out) {
     return SGX_OK;
 }
 
+// ---- the per-block state of a tracked channel, rebuilt from its recorded series (include/sgx.h: sgx_replay_state) ----------
+// One serial recurrence per channel, in the reference's operation order (tracking.py:148-251; the build is -ffp-contract=off).
+// Only the last element of the prompt linspace is needed: numpy forms it as (blk - 1) * ((stop - start) / blk) + start.
+extern "C" int sgx_replay_state(const sgx_settings* s, int32_t data_type, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
+                                const int32_t* ms_done, const double* series, int64_t rec_file_offset, int64_t rec_bytes,
+                                sgx_replay_block* state) {
+    SGX_CHECK_ARG(s && ch && series && state);
+    SGX_CHECK_ARG(n_ch >= 1 && ms >= 1);
+    SGX_CHECK_ARG(s->samplingFreq > 0 && s->codeFreqBasis > 0);
+    if (data_type != SGX_DT_INT8 && data_type != SGX_DT_UINT8 && data_type != SGX_DT_INT16) {
+        sgx_set_error("bad argument: the replay reads int8, uint8 and int16 records, not data_type %d", (int)data_type);
+        return SGX_E_ARG;
+    }
+    if (ms_done)
+        for (int i = 0; i < n_ch; ++i)
+            if (ms_done[i] < 0 || ms_done[i] > ms) {
+                sgx_set_error("bad argument: ms_done[%d] = %d outside [0, %d]", i, (int)ms_done[i], (int)ms);
+                return SGX_E_ARG;
+            }
+    const long long isz = data_type == SGX_DT_INT16 ? 2 : 1;
+    const double fs = s->samplingFreq;
+    const double two_pi = 2.0 * M_PI;
+    memset(state, 0, sizeof(sgx_replay_block) * (size_t)n_ch * (size_t)ms);
+    for (int c = 0; c < n_ch; ++c) {
+        if (ch[c].prn == 0) continue;
+        if (ch[c].prn < 1 || ch[c].prn > 32 || !isfinite(ch[c].acquiredFreq) || !isfinite(ch[c].codePhase)) {
+            sgx_set_error("bad argument: channel %d (prn %d) is not a channel of preRun", c, (int)ch[c].prn);
+            return SGX_E_ARG;
+        }
+        const double* row_abs = series + (size_t)c * SGX_NUM_SERIES * (size_t)ms;
+        const double* row_code = row_abs + ms;
+        const double* row_carr = row_abs + 2 * (size_t)ms;
+        long long pos = (long long)((double)s->skipNumberOfBytes + ch[c].codePhase);   // int(skip + codePhase), tracking.py:107
+        double code_freq = s->codeFreqBasis, carr_freq = ch[c].acquiredFreq;
+        double rem_code = 0.0, rem_carr = 0.0;
+        const int done = ms_done ? ms_done[c] : ms;
+        for (int k = 0; k < done; ++k) {
+            const double step = code_freq / fs;
+            const double nblk = ceil(((double)s->codeLength - rem_code) / step);
+            if (!(isfinite(carr_freq) && nblk >= 1.0 && nblk < 2147483648.0)) {
+                sgx_set_error("bad argument: channel %d block %d: the recorded rates give no block (codeFreq %g, carrFreq %g)",
+                              c, k, code_freq, carr_freq);
+                return SGX_E_ARG;
+            }
+            const long long blk = (long long)nblk;
+            if (!(row_abs[k] == (double)(pos + blk * isz))) {
+                sgx_set_error("bad argument: channel %d block %d: the rebuilt block ends at byte %lld, absoluteSample says %.17g "
+                              "(not a tracking result of this channel)", c, k, pos + blk * isz, row_abs[k]);
+                return SGX_E_ARG;
+            }
+            if (rec_bytes >= 0 && (pos < rec_file_offset || pos + blk * isz > rec_file_offset + rec_bytes)) {
+                sgx_set_error("channel %d block %d: bytes [%lld, %lld) lie outside the record [%lld, %lld)", c, k, pos,
+                              pos + blk * isz, (long long)rec_file_offset, (long long)(rec_file_offset + rec_bytes));
+                return SGX_E_RANGE;
+            }
+            sgx_replay_block& b = state[(size_t)c * ms + k];
+            b.start = pos;
+            b.rem_code = rem_code;
+            b.rem_carr = rem_carr;
+            b.step = step;
+            b.carr_freq = carr_freq;
+            b.blk = (int32_t)blk;
+            const double stop = nblk * step + rem_code;
+            const double lin = (stop - rem_code) / nblk;
+            const double tp_last = (nblk - 1.0) * lin + rem_code;
+            rem_code = tp_last + step - 1023.0;
+            const double arg = carr_freq * 2.0 * M_PI * (nblk / fs) + rem_carr;
+            double r = fmod(arg, two_pi);             // numpy's %: the sign of the divisor
+            if (r != 0.0) {
+                if (r < 0.0) r += two_pi;
+            } else {
+                r = 0.0;
+            }
+            rem_carr = r;
+            pos += blk * isz;
+            code_freq = row_code[k];
+            carr_freq = row_carr[k];
+        }
+    }
+    return SGX_OK;
+}
+
+extern "C" int sgx_replay_timing(sgx_ctx* c, float* kernel_ms, float* device_ms) {
+    SGX_CHECK_ARG(c && kernel_ms && device_ms);
+    *kernel_ms = c->replay_kernel_ms;
+    *device_ms = c->replay_device_ms;
+    return SGX_OK;
+}
+
 // ---- co-residency budget of cooperative tracking launches ---------------------------------------
 static std::atomic<int> g_cu_used[64];
 

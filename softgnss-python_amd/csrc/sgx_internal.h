@@ -171,6 +171,8 @@ struct sgx_ctx {
     // pinned staging buffers of the file streamer, kept between calls (pinning 64 MiB costs ~15 ms)
     void* stage[2] = {nullptr, nullptr};
     std::atomic<bool> stage_busy{false};
+    // HIP-event times of the last sgx_track_replay (sgx_replay.hip): the kernel, and upload + kernel + result copy
+    float replay_kernel_ms = 0.0f, replay_device_ms = 0.0f;
 };
 
 // sgx_host.cpp

@@ -2,10 +2,12 @@
 
     python -m softgnss-python_amd.main record.bin [--fs 38192000 --IF 9548000 --ms 37000 --channels 8 --skip 0]
                                                   [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
+                                                  [--correlator-bank LO:HI:STEP]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
-ephemerides), the mean position fix."""
+ephemerides), the mean position fix.  --correlator-bank=-1:1:0.25 replays the tracked channels at those code offsets
+(chips) and prints each channel's mean correlation envelope per tap, normalised to its maximum."""
 from __future__ import print_function
 
 import argparse
@@ -30,7 +32,19 @@ def main(argv=None):
                     help="acquisition: ms summed coherently per window (weak signals: 10; Doppler step 500 / T Hz)")
     ap.add_argument("--acq-blocks", type=int, default=None, help="acquisition: number of windows (reference: 2)")
     ap.add_argument("--acq-noncoh", action="store_true", help="acquisition: sum the windows non-coherently")
+    ap.add_argument("--correlator-bank", default=None, metavar="LO:HI:STEP",
+                    help="after tracking, replay every channel at code offsets LO .. HI (chips, at most 64 taps) and "
+                         "print the mean envelope per tap (a negative LO needs the = form: --correlator-bank=-1:1:0.25)")
     a = ap.parse_args(argv)
+    taps = None
+    if a.correlator_bank is not None:
+        try:
+            lo, hi, step = (float(x) for x in a.correlator_bank.split(":"))
+            taps = lo + step * np.arange(int(np.floor((hi - lo) / step + 1e-9)) + 1)
+        except (ValueError, ZeroDivisionError):
+            taps = None
+        if taps is None or not (1 <= taps.size <= 64) or not np.all(np.isfinite(taps)):
+            ap.error("--correlator-bank takes LO:HI:STEP in chips with 1 .. 64 taps, e.g. --correlator-bank=-1:1:0.25")
     print('\nWelcome to:  softGNSS on MI355X\n')
     settings = initialize.Settings()
     settings.fileName = a.fileName
@@ -49,6 +63,11 @@ def main(argv=None):
                   % (p["segments"], p["f_MHz"][k], p["hist_edges"][np.flatnonzero(p["hist"])[0]],
                      p["hist_edges"][np.flatnonzero(p["hist"])[-1]] + 1))
     acq, trk, nav = settings.postProcessing()
+    if taps is not None and trk is not None and trk.has_results():
+        with open(settings.fileName, 'rb') as fid:
+            bank = trk.replay(fid, taps)
+        print('Correlator bank (%d taps, mean envelope over the run, %.3f ms on the GPU):' % (taps.size, bank.kernel_ms))
+        bank.show()
     if nav is not None and nav._solutions is not None:
         sol = nav.solutions[0]
         ok = np.isfinite(sol.X)

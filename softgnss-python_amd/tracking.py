@@ -23,6 +23,36 @@ QUALITY_DTYPE = [('PRN', 'int64'), ('CNo', 'object'), ('carrLock', 'object'), ('
                  ('lostAtMs', 'int64'), ('medianCNo', 'float64')]
 
 
+class ReplayResult(object):
+    """What TrackingResult.replay returns: the correlation of every tracked channel at K code offsets, per ms.
+    taps float64[K] (chips), PRN int[n_active], I / Q float64[n_active, K, ms] (row order of TrackingResult.results)."""
+
+    def __init__(self, taps, prn, out, kernel_ms=None):
+        self.taps = np.array(taps, dtype=np.float64)
+        self.PRN = np.array(prn, dtype=np.int64)
+        self.I = out[:, :, 0, :]
+        self.Q = out[:, :, 1, :]
+        self.kernel_ms = kernel_ms   # HIP-event duration of the replay kernel
+
+    def envelope(self):
+        """sqrt(I^2 + Q^2), float64[n_active, K, ms]."""
+        return np.sqrt(self.I ** 2 + self.Q ** 2)
+
+    def show(self, first_ms=0):
+        """ASCII table: per channel, the mean envelope from first_ms on, normalised to its maximum, one line per tap."""
+        env = self.envelope()[:, :, first_ms:].mean(axis=2) if self.I.shape[2] > first_ms else self.envelope().mean(axis=2)
+        bar = '*=========*=====*==========*==========*'
+        print('\n' + bar)
+        print('| Channel | PRN | tap chips | envelope |')
+        print(bar)
+        for c in range(env.shape[0]):
+            top = env[c].max()
+            for j, d in enumerate(self.taps):
+                print('|      %2d | %3d | %8.3f |  %6.3f  |' % (c, int(self.PRN[c]), d, env[c, j] / top if top > 0 else 0.0))
+            print(bar)
+        print('')
+
+
 class TrackingResult(Result):
     def __init__(self, acqResult, device=None, verbose=False):
         """verbose: print the reference's progress lines (tracking.py:137-143: one per channel and 50 ms) - after the
@@ -112,6 +142,50 @@ class TrackingResult(Result):
             before = before[np.isfinite(before)]
             q[j].medianCNo = float(np.median(before)) if before.size else np.nan
         return q
+
+    def replay(self, fid, taps):
+        """Multi-correlator replay (sgx_track_replay): the correlation of every tracked channel at the code offsets
+        `taps` (chips, 1 .. 64 of them) for every ms, rebuilt from the recorded absoluteSample / codeFreq / carrFreq -
+        taps (-dllCorrelatorSpacing, 0, +dllCorrelatorSpacing) are the early, prompt and late arms themselves.
+        fid: the record track() read (open binary file or DeviceFile).  Works after track() and after .results was
+        assigned from a cache.  Returns a ReplayResult (.taps, .PRN, .I, .Q, .envelope())."""
+        settings = self._settings
+        taps = np.atleast_1d(np.asarray(taps, dtype=np.float64))
+        if self._channels is None and self._acq is not None:
+            self._channels = self._acq.channels
+        channel = self._channels
+        if self.series is not None and not self._assigned:
+            series = self.series
+            active = list(self._active)
+        else:
+            res = self.results
+            series = np.stack([np.stack([np.asarray(r[name], dtype=np.float64) for name in _native.SERIES]) for r in res]) \
+                if len(res) else np.empty((0, _native.NUM_SERIES, 0))
+            active = [i for i in range(len(channel)) if channel[i].PRN != 0][:len(res)]
+            if len(active) != len(res) or [int(channel[i].PRN) for i in active] != [int(p) for p in res.PRN]:
+                raise ValueError("the results' PRNs are not those of the acquisition's channels: replay() needs each "
+                                 "channel's acquiredFreq and codePhase")
+        prn = [int(channel[i].PRN) for i in active]
+        if not active:
+            return ReplayResult(taps, prn, np.zeros((0, taps.size, 2, series.shape[2])))
+        chans = [(int(channel[i].PRN), float(channel[i].acquiredFreq), float(channel[i].codePhase)) for i in active]
+        ctx = engine.get_context(settings, self._device)
+        dtype_code, isz = self._data_type()
+        own = None
+        if isinstance(fid, DeviceFile):
+            rec, file_off = fid.record, fid.file_offset
+        else:
+            first = (int(settings.skipNumberOfBytes + min(c[2] for c in chans)) // 4096) * 4096
+            last = int(series[:, 0, :].max())
+            own = rec = self._window(fid, first, last - first)
+            file_off = first
+        try:
+            out = ctx.track_replay(rec, chans, series, taps, rec_file_offset=file_off, data_type=dtype_code)
+            kernel_ms = ctx.replay_timing()[0]
+        finally:
+            if own is not None:
+                own.free()
+        return ReplayResult(taps, prn, out, kernel_ms)
 
     def showTrackingQuality(self):
         """ASCII table of .quality, in the manner of AcquisitionResult.showChannelStatus."""
