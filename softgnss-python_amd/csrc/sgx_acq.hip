@@ -16,10 +16,25 @@
 
 #include "sgx_internal.h"
 
-#define ACQ_MAX_BINS 128
-#define ACQ_MAX_ROWS 2048
+// ================================ limits and structs ================================
+// (ACQ_MAX_BINS, ACQ_MAX_ROWS, ACQ_COH_MAX_BINS and the structs the small areas hold: sgx_internal.h)
 #define ACQ_DEFAULT_CHUNK_ROWS 348   // correlation rows per chunk (the intermediate then stays in the Infinity Cache)
 
+// The grid of a coherent multi-millisecond search (sgx_acquire_coherent; coh_grid fills it)
+#define ACQ_COH_MAX_MS 20
+#define ACQ_COH_MAX_WINDOWS 64
+#define ACQ_COH_MAX_SPAN_MS 400
+#define ACQ_COH_MAX_PHI 64
+struct CohGrid {
+    int T = 1, M = 1, noncoh = 0;       // coherent_ms, n_windows, rule
+    double step = 500.0, f0 = 0.0;      // f_k = f0 + step k
+    int n_bins = 0, n_phi = 0, path = 0;
+    std::vector<int2> bin_map;          // shift path: (phi index, circular shift) per bin
+    std::vector<double> phi;
+    int prn_chunk = 1, runs = 1, per_run = 1;   // correlation batches (coh_plan): per_run bins (noncoh) or windows
+};
+
+// ================================ kernels ================================
 struct MixArgs {
     double frq[ACQ_MAX_BINS];
     int n_bins;
@@ -153,11 +168,6 @@ __global__ __launch_bounds__(64) void acq_rowmax_finish_kernel(const double* __r
     }
 }
 
-struct SecondArgs {
-    int row[32];          // power row to search, -1 = skip
-    int lo0[32], hi0[32]; // first index range [lo0, hi0)
-    int lo1[32], hi1[32]; // second index range
-};
 
 // acquisition.py:162: max of the chosen frequency row over the exclusion index list
 // (grid (PRNs, SEC_SPLIT): every workgroup takes a slice of the ranges and folds its maximum into out[p] with an integer
@@ -434,40 +444,6 @@ __global__ __launch_bounds__(256) void acq_front_kernel(AcqSetup su, SgxSig x, P
     if (t == 0) sum_next[0] = 0;
 }
 
-static int ensure_buf(void** p, size_t* cap_bytes, size_t need) {
-    if (*p && *cap_bytes >= need) return SGX_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    hipError_t e = hipMalloc(p, need);
-    if (e != hipSuccess) {
-        sgx_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        *cap_bytes = 0;
-        return SGX_E_NOMEM;
-    }
-    *cap_bytes = need;
-    return SGX_OK;
-}
-
-static int acquire_four_step(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0,
-                             int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
-                             double* peakMetric, int32_t* freqBin, int32_t* fineIdx, bool* handled, bool defer = false);
-// The grid of a coherent multi-millisecond search (sgx_acquire_coherent; coh_grid fills it)
-#define ACQ_COH_MAX_MS 20
-#define ACQ_COH_MAX_WINDOWS 64
-#define ACQ_COH_MAX_SPAN_MS 400
-#define ACQ_COH_MAX_BINS 1024
-#define ACQ_COH_MAX_PHI 64
-struct CohGrid {
-    int T = 1, M = 1, noncoh = 0;       // coherent_ms, n_windows, rule
-    double step = 500.0, f0 = 0.0;      // f_k = f0 + step k
-    int n_bins = 0, n_phi = 0, path = 0;
-    std::vector<int2> bin_map;          // shift path: (phi index, circular shift) per bin
-    std::vector<double> phi;
-    int prn_chunk = 1, runs = 1, per_run = 1;   // correlation batches (coh_plan): per_run bins (noncoh) or windows
-};
-static std::vector<long long> coh_fine_windows(const CohGrid& g, const sgx_settings& S, long long N,
-                                               const std::vector<int>& det_bin);
-
 // Direct path of the coherent search: window w of bin k folded as the contract states it (include/sgx.h), every
 // (window, bin) row on its own - the same IEEE operations as acq_mix_kernel, which is the case T = 1:
 //   out[w][k][n] = sum_{m < T} x[(w T + m) n_code + n] (sin + j cos)(frq[k] (((n + m n_code) 2) pi ts))
@@ -530,478 +506,24 @@ __global__ __launch_bounds__(256) void acq_fold_phi_kernel(SgxSig x, cplx* __res
         out[((long long)w * a.n_phi + j) * n + i] = make_double2(__builtin_fma(re, cs, im * sn), __builtin_fma(im, cs, -(re * sn)));
     }
 }
-static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
-                          int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                          int32_t* fineIdx, const CohGrid* g = nullptr);
-static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vector<int>& det_prn,
-                        const std::vector<int>& det_phase, const std::vector<int>& det_slot, long long* d_sum,
-                        double* carrFreq, double* codePhase, int32_t* fineIdx, const std::vector<long long>* win = nullptr);
 
-static int acquire_any(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
-                       int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                       int32_t* fineIdx) {
-    // the four-step path (sub-transforms in registers and LDS, shifted forward spectra) where it applies
-    bool handled = false;
-    const int rc4 = acquire_four_step(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric,
-                                      freqBin, fineIdx, &handled);
-    if (handled) return rc4;
-    return acquire_passes(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-}
-
-extern "C" int sgx_acquire(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
-                           int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
-                           double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && r && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32 && n_blocks >= 1 && n_blocks <= 64);
-    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
-    const long long N = c->n_code;
-    if (offset > r->n || n_samples > r->n - offset || (long long)n_samples < (long long)n_blocks * N) {
-        sgx_set_error("record window too short: %zu samples at offset %zu, %lld needed for the coarse search",
-                      n_samples, offset, (long long)n_blocks * N);
-        return SGX_E_RANGE;
-    }
-    {
-        const int rq = sgx_if_require(r, offset + n_samples);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    SgxSig x;
-    x.i8 = r->d + offset;
-    x.f64 = nullptr;
-    return acquire_any(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-}
-
-// acquire() on a signal that is not int8 (acquisition.py:55-59 takes whatever real dtype numpy hands it): the caller's
-// fp64 samples are copied to HBM and every kernel reads them instead of the int8 record; the arithmetic is the same
-// fp64 arithmetic either way.
-extern "C" int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
-                               int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
-                               int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && signal && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32 && n_blocks >= 1 && n_blocks <= 64);
-    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
-    const long long N = c->n_code;
-    if ((long long)n_samples < (long long)n_blocks * N) {
-        sgx_set_error("signal too short: %zu samples, %lld needed for the coarse search", n_samples, (long long)n_blocks * N);
-        return SGX_E_RANGE;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    const size_t need = sizeof(double) * (n_samples + 64);
-    if (c->cap_sig64 < need) {
-        if (c->d_sig64) hipFree(c->d_sig64);
-        c->d_sig64 = nullptr;
-        c->cap_sig64 = 0;
-        if (hipMalloc((void**)&c->d_sig64, need) != hipSuccess) {
-            sgx_set_error("hipMalloc of %zu signal bytes failed", need);
-            return SGX_E_NOMEM;
-        }
-        c->cap_sig64 = need;
-    }
-    SGX_HIP(hipMemcpyAsync(c->d_sig64, signal, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
-    SGX_HIP(hipStreamSynchronize(c->stream));   // the caller may free `signal` on return
-    SgxSig x;
-    x.i8 = nullptr;
-    x.f64 = c->d_sig64;
-    return acquire_any(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-}
-
-// The round-1 path: one launch per radix pass, every Doppler bin mixed separately (any factorable samplesPerCode).
-// g (coherent search, direct path; else null): n_blocks = the windows, each folded from g->T blocks per Doppler bin of g's
-// grid (acq_fold_direct_kernel) in place of the 1-ms mix
-static int acquire_passes(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, int32_t n_blocks,
-                          int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                          int32_t* fineIdx, const CohGrid* g) {
-    const long long N = c->n_code;
-    const sgx_settings& S = c->s;
-    hipStream_t st = c->stream;
-
-    // A4 frequency grid (acquisition.py:68,99-101)
-    const int n_bins = g ? g->n_bins : (int)(nearbyint(S.acqSearchBand * 2) + 1);
-    SGX_CHECK_ARG(n_bins >= 1 && n_bins <= (g ? ACQ_COH_MAX_BINS : ACQ_MAX_BINS));
-    MixArgs ma;
-    ma.n_bins = n_bins;
-    ma.n_blocks = n_blocks;
-    for (int k = 0; k < n_bins && !g; ++k) ma.frq[k] = S.IF - S.acqSearchBand / 2 * 1000 + 500.0 * k;
-    const double ts = 1.0 / S.samplingFreq;
-    const double tc = 1.0 / S.codeFreqBasis;
-    const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
-
-    int rc = sgx_fft_plan_create(&c->plan_code, N);
-    if (rc != SGX_OK) return rc;
-
-    // ---- scratch ------------------------------------------------------------------------------
-    const int rows_fwd = n_blocks * n_bins;
-    const int rows_per_prn = rows_fwd;
-    SGX_CHECK_ARG(rows_per_prn <= ACQ_MAX_ROWS);
-    int prn_chunk = ACQ_MAX_ROWS / rows_per_prn;
-    if (prn_chunk < 1) prn_chunk = 1;
-    if (prn_chunk > n_prn) prn_chunk = n_prn;
-    const size_t row_bytes = sizeof(cplx) * (size_t)N;
-    size_t work_rows = (size_t)prn_chunk * rows_per_prn;
-    if (work_rows < (size_t)rows_fwd) work_rows = rows_fwd;
-    if (work_rows < (size_t)n_prn) work_rows = n_prn;
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_codefd, &c->cap_code, (size_t)n_prn * row_bytes)) != SGX_OK) return rc;
-    const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : (size_t)ACQ_MAX_ROWS * 64 * 12 + 4096;
-    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, pow_need)) != SGX_OK) return rc;
-
-    char* dsm = (char*)c->d_small;
-    char* hsm = (char*)c->h_small;
-    // d_small layout: [0,8) sum | [64, 64+128) prn list | [256, ...) rowmax doubles | rowarg ints | second | fine
-    long long* d_sum = (long long*)dsm;
-    int* d_prn = (int*)(dsm + 64);
-    double* d_rowmax = (double*)(dsm + 1024);
-    int* d_rowarg = (int*)(dsm + 1024 + 8 * 4096);
-    double* d_second = (double*)(dsm + 1024 + 12 * 4096);
-    int* d_detprn = (int*)(dsm + 1024 + 12 * 4096 + 512);
-    int* d_detph = d_detprn + 32;
-    const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
-    int2* d_map = (int2*)(dsm + 200000);
-    SecondArgs* d_sa = (SecondArgs*)(dsm + 600000);
-
-    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer
-    double* d_pmax = c->d_pow;
-    int* d_parg = (int*)(c->d_pow + (size_t)ACQ_MAX_ROWS * 64);
-    SGX_CHECK_ARG(nblk_last <= 64);
-    hipEventRecord(c->ev[0], st);
-    SGX_HIP(hipMemsetAsync(d_sum, 0, 8, st));
-    SGX_HIP(hipMemcpyAsync(d_prn, prn0, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
-    if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)n_samples, d_sum);
-    else acq_sum_kernel<<<256, 256, 0, st>>>(x.i8, (long long)n_samples, d_sum);
-
-    // ---- PRN-independent part: mix + forward FFTs ------------------------------------------------
-    {
-        dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows_fwd);
-        if (g) {
-            double* h_frq = (double*)(hsm + 800000);
-            double* d_frq = (double*)(dsm + 800000);
-            static_assert(800000 + ACQ_COH_MAX_BINS * sizeof(double) <= (1 << 20), "inside the small buffers");
-            for (int k = 0; k < n_bins; ++k) h_frq[k] = g->f0 + g->step * k;
-            SGX_HIP(hipMemcpyAsync(d_frq, h_frq, sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, st));
-            acq_fold_direct_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, d_frq, n_bins, g->T);
-        } else {
-            acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, ma);
-        }
-        cplx* res = nullptr;
-        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows_fwd, st, &res, N);
-        if (rc != SGX_OK) return rc;
-        SGX_HIP(hipMemcpyAsync(c->d_fwd, res, (size_t)rows_fwd * row_bytes, hipMemcpyDeviceToDevice, st));
-    }
-    // ---- code spectra ---------------------------------------------------------------------------
-    {
-        dim3 grid((unsigned)((N + 255) / 256), (unsigned)n_prn);
-        acq_code_kernel<<<grid, 256, 0, st>>>(c->d_codes, d_prn, c->d_work[0], N, ts, tc);
-        cplx* res = nullptr;
-        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], n_prn, st, &res, N);
-        if (rc != SGX_OK) return rc;
-        SGX_HIP(hipMemcpyAsync(c->d_codefd, res, (size_t)n_prn * row_bytes, hipMemcpyDeviceToDevice, st));
-    }
-
-    // ---- correlation + peak search, PRN chunk by chunk ---------------------------------------------
-    std::vector<int> det_prn, det_phase, det_slot;
-    int status = SGX_OK;
-    for (int i = 0; i < n_prn; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
-    }
-    const double inv_n = 1.0 / (double)N;
-    for (int p0 = 0; p0 < n_prn && status == SGX_OK; p0 += prn_chunk) {
-        const int np = (p0 + prn_chunk <= n_prn) ? prn_chunk : (n_prn - p0);
-        const int rows = np * rows_per_prn;
-        const int rows_out = noncoh ? np * n_bins : rows;
-        cplx* res = nullptr;
-        if (noncoh) {
-            // extension path: the blocks' powers are summed per sample, so rows are materialised
-            dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows);
-            acq_mul_kernel<<<grid, 256, 0, st>>>(c->d_fwd, c->d_codefd, c->d_work[0], N, rows_per_prn, p0);
-            rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N);
-            if (rc != SGX_OK) return rc;
-            acq_power_kernel<<<rows_out, 256, 0, st>>>(res, c->d_pow, d_rowmax, d_rowarg, N, inv_n, n_bins, n_blocks, 1);
-        } else {
-            // reference path, fused: conj(X)*F formed in the first radix pass, |.|^2 and the per-workgroup
-            // maxima taken in the last one; no product rows, no power rows
-            FftFuse fu;
-            fu.mul_x = c->d_fwd;
-            fu.mul_f = c->d_codefd;
-            fu.rows_per_prn = rows_per_prn;
-            fu.prn_base = p0;
-            fu.pmax = d_pmax;
-            fu.parg = d_parg;
-            fu.inv_n = inv_n;
-            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N, &fu);
-            if (rc != SGX_OK) return rc;
-            acq_rowmax_finish_kernel<<<rows, 64, 0, st>>>(d_pmax, d_parg, nblk_last, d_rowmax, d_rowarg);
-        }
-        double* h_rowmax = (double*)(hsm + 1024);
-        int* h_rowarg = (int*)(hsm + 1024 + 8 * 4096);
-        SGX_HIP(hipMemcpyAsync(h_rowmax, d_rowmax, sizeof(double) * (size_t)rows_out, hipMemcpyDeviceToHost, st));
-        SGX_HIP(hipMemcpyAsync(h_rowarg, d_rowarg, sizeof(int) * (size_t)rows_out, hipMemcpyDeviceToHost, st));
-        SGX_HIP(hipStreamSynchronize(st));
-
-        // host: block choice (A7), global peak (A8), exclusion list (A8b)
-        SecondArgs sa;
-        double peak[32];
-        int cph[32], fbi[32];
-        for (int pi = 0; pi < 32; ++pi) sa.row[pi] = -1, sa.lo0[pi] = sa.hi0[pi] = sa.lo1[pi] = sa.hi1[pi] = 0;
-        for (int pi = 0; pi < np; ++pi) {
-            double gmax = -1.0;
-            int gk = 0, gc = 0, grow = 0;
-            bool have = false;
-            for (int k = 0; k < n_bins; ++k) {
-                int row;
-                if (noncoh) {
-                    row = pi * n_bins + k;
-                } else {
-                    int best = 0;   // acquisition.py:129-133 generalised left to right, later block wins ties
-                    for (int b = 1; b < n_blocks; ++b) {
-                        const double vb = h_rowmax[(pi * n_blocks + best) * n_bins + k];
-                        const double vn = h_rowmax[(pi * n_blocks + b) * n_bins + k];
-                        if (!(vb > vn)) best = b;
-                    }
-                    row = (pi * n_blocks + best) * n_bins + k;
-                }
-                const double v = h_rowmax[row];
-                const int a = h_rowarg[row];
-                if (!have || v > gmax) {
-                    gmax = v;
-                    gk = k;          // first row attaining the maximum (results.max(1).argmax())
-                    gc = a;
-                    grow = row;
-                    have = true;
-                } else if (v == gmax && a < gc) {
-                    gc = a;          // results.max(0).argmax(): first column attaining the maximum
-                }
-            }
-            peak[pi] = gmax;
-            cph[pi] = gc;
-            fbi[pi] = gk;
-            const int e1 = gc - spc, e2 = gc + spc;
-            sa.row[pi] = grow;
-            if (e1 <= 0) {
-                if ((long long)N + e1 + 1 > N) {   // index N would be read: the reference's IndexError (Q5)
-                    sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
-                                  "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
-                                  N, N, prn0[p0 + pi], gc);
-                    status = SGX_E_INDEX;
-                    sa.row[pi] = -1;
-                    break;
-                }
-                sa.lo0[pi] = e2;
-                sa.hi0[pi] = (int)(N + e1 + 1);
-            } else if (e2 >= N - 1) {
-                const int lo = (int)(e2 - N);
-                if (lo < 0) {   // arange starts at -1: numpy wraps it to N-1
-                    sa.lo0[pi] = 0;
-                    sa.hi0[pi] = e1;
-                    sa.lo1[pi] = (int)N - 1;
-                    sa.hi1[pi] = (int)N;
-                } else {
-                    sa.lo0[pi] = lo;
-                    sa.hi0[pi] = e1;
-                }
-            } else {
-                sa.lo0[pi] = 0;
-                sa.hi0[pi] = e1 + 1;
-                sa.lo1[pi] = e2;
-                sa.hi1[pi] = (int)N;
-            }
-        }
-        if (status != SGX_OK) break;
-        if (noncoh) {
-            SGX_HIP(hipMemcpyAsync(d_sa, &sa, sizeof(sa), hipMemcpyHostToDevice, st));
-            SGX_HIP(hipMemsetAsync(d_second, 0, sizeof(double) * 32, st));
-            acq_second_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(c->d_pow, d_second, N, d_sa);
-        } else {
-            // recompute only the np rows the second-peak search reads (one per PRN)
-            int2* h_map = (int2*)(hsm + 200000);
-            for (int pi = 0; pi < np; ++pi) {
-                h_map[pi] = make_int2(sa.row[pi] % rows_per_prn, p0 + pi);   // row = (pi*blocks + b)*bins + k
-                sa.row[pi] = pi;
-            }
-            SGX_HIP(hipMemcpyAsync(d_map, h_map, sizeof(int2) * (size_t)np, hipMemcpyHostToDevice, st));
-            FftFuse fu;
-            fu.mul_x = c->d_fwd;
-            fu.mul_f = c->d_codefd;
-            fu.row_map = d_map;
-            cplx* r2 = nullptr;
-            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], np, st, &r2, N, &fu);
-            if (rc != SGX_OK) return rc;
-            SGX_HIP(hipMemcpyAsync(d_sa, &sa, sizeof(sa), hipMemcpyHostToDevice, st));
-            SGX_HIP(hipMemsetAsync(d_second, 0, sizeof(double) * 32, st));
-            acq_second_cplx_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(r2, d_second, N, inv_n, d_sa);
-        }
-        double* h_second = (double*)(hsm + 1024 + 12 * 4096);
-        SGX_HIP(hipMemcpyAsync(h_second, d_second, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, st));
-        SGX_HIP(hipStreamSynchronize(st));
-        for (int pi = 0; pi < np; ++pi) {
-            const int o = p0 + pi;
-            const double ratio = peak[pi] / h_second[pi];
-            peakMetric[o] = ratio;
-            freqBin[o] = fbi[pi];
-            if (ratio > S.acqThreshold) {
-                det_prn.push_back(prn0[o]);
-                det_phase.push_back(cph[pi]);
-                det_slot.push_back(o);
-            }
-        }
-    }
-    hipEventRecord(c->ev[1], st);
-    if (status != SGX_OK) {
-        hipStreamSynchronize(st);
-        return status;
-    }
-
-    // ---- fine frequency search (acquisition.py:167-193) -----------------------------------------------
-    {
-        std::vector<long long> win;
-        if (g && g->T > 1) {
-            std::vector<int> det_bin;
-            for (int o : det_slot) det_bin.push_back(freqBin[o]);
-            win = coh_fine_windows(*g, S, N, det_bin);
-        }
-        const int rcf = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx,
-                                     win.empty() ? nullptr : &win);
-        if (rcf != SGX_OK) return rcf;
-    }
-    hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
-    hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
-    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
-    return SGX_OK;
-}
-
-// Fine frequency search (acquisition.py:167-193) for the detected PRNs; records event ev[2] and synchronises.
-// win (coherent search, else null): [2 d], [2 d + 1] = detection d's own arg-max range in place of [4, uniq - 5)
-static int acquire_fine(sgx_ctx* c, SgxSig x, size_t n_samples, const std::vector<int>& det_prn,
-                        const std::vector<int>& det_phase, const std::vector<int>& det_slot, long long* d_sum,
-                        double* carrFreq, double* codePhase, int32_t* fineIdx, const std::vector<long long>* win) {
-    hipStream_t st = c->stream;
-    const sgx_settings& S = c->s;
-    const long long N = c->n_code;
-    const double ts = 1.0 / S.samplingFreq;
-    char* dsm = (char*)c->d_small;
-    char* hsm = (char*)c->h_small;
-    int* d_detprn = (int*)(dsm + 1024 + 12 * 4096 + 512);
-    int* d_detph = d_detprn + 32;
-    double* d_pv = (double*)(dsm + 65536);
-    long long* d_pi = nullptr;
-    int rc = SGX_OK;
-    const int n_det = (int)det_prn.size();
-    if (n_det > 0) {
-        const long long len = 10 * N;
-        const long long npts = 8ll << (long long)ceil(log2((double)len));
-        const long long uniq = (long long)ceil((double)(npts + 1) / 2.0);
-        for (int d = 0; d < n_det; ++d) {
-            if ((long long)det_phase[d] + len > (long long)n_samples) {
-                sgx_set_error("fine search needs codePhase + 10 ms = %lld samples, record window has %zu "
-                              "(reference acquisition.py:177 would fail to broadcast)",
-                              (long long)det_phase[d] + len, n_samples);
-                return SGX_E_RANGE;
-            }
-        }
-        rc = sgx_fft_plan_create(&c->plan_fine, npts);
-        if (rc != SGX_OK) return rc;
-        const int n_rows = (n_det + 1) / 2;   // two real signals per complex row
-        if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
-            return rc;
-        if ((rc = ensure_buf((void**)&c->d_fine[1], &c->cap_f1, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
-            return rc;
-        const double tc1 = 1.0 / S.codeFreqBasis;
-        const char* fv1 = getenv("SGX_ACQ_FINE_V1");
-        const bool fine2 = sgx_fft_fine_supported(npts) && !(fv1 && fv1[0] == '1');
-        double mean = 0.0;
-        if (!fine2) {
-            long long h_sum = 0;
-            SGX_HIP(hipMemcpyAsync(&h_sum, d_sum, 8, hipMemcpyDeviceToHost, st));
-            SGX_HIP(hipStreamSynchronize(st));
-            double h_sumd;
-            memcpy(&h_sumd, &h_sum, 8);
-            mean = (x.f64 ? h_sumd : (double)h_sum) / (double)n_samples;   // longSignal.mean(), acquisition.py:59
-        }
-        int nblk = 256;
-        double* h_pv = (double*)(hsm + 65536);
-        long long* h_pi = (long long*)(hsm + 400000);   // (behind the row-map area at 200000)
-        d_pi = (long long*)(dsm + 400000);
-        // per-detection ranges (coherent search): to device memory, and their union as the common range
-        long long* d_win = nullptr;
-        long long win_lo = 4, win_hi = uniq - 5;
-        if (win) {
-            long long* h_win = (long long*)(hsm + 810000);
-            d_win = (long long*)(dsm + 810000);
-            static_assert(810000 + 64 * sizeof(long long) <= (1 << 20), "inside the small buffers");
-            memcpy(h_win, win->data(), sizeof(long long) * 2 * (size_t)n_det);
-            SGX_HIP(hipMemcpyAsync(d_win, h_win, sizeof(long long) * 2 * (size_t)n_det, hipMemcpyHostToDevice, st));
-            win_lo = (*win)[0];
-            win_hi = (*win)[1];
-            for (int d = 1; d < n_det; ++d) {
-                win_lo = (*win)[2 * (size_t)d] < win_lo ? (*win)[2 * (size_t)d] : win_lo;
-                win_hi = (*win)[2 * (size_t)d + 1] > win_hi ? (*win)[2 * (size_t)d + 1] : win_hi;
-            }
-        }
-        if (fine2) {
-            // two kernels with LDS-resident sub-transforms, input built on the fly (the mean comes from the device-side
-            // sum: no host look), arg-max fused (sgx_fft.hip)
-            nblk = sgx_fft_fine_partials();
-            rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, det_prn.data(), det_phase.data(), n_det, len, d_sum,
-                                     (double)n_samples, ts, tc1, c->d_fine[0], win_lo, win_hi, d_pv, d_pi, st, nullptr,
-                                     nullptr, nullptr, 0, nullptr, nullptr, 0, d_win);
-            if (rc != SGX_OK) return rc;
-        } else {
-            SGX_HIP(hipMemcpyAsync(d_detprn, det_prn.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
-            SGX_HIP(hipMemcpyAsync(d_detph, det_phase.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
-            dim3 grid((unsigned)((len + 255) / 256), (unsigned)n_rows);
-            acq_fine_prep_kernel<<<grid, 256, 0, st>>>(x, c->d_codes, c->d_fine[0], len, npts, mean, ts, tc1, d_detprn,
-                                                       d_detph, n_det);
-            cplx* res = nullptr;
-            rc = sgx_fft_forward(&c->plan_fine, c->d_fine[0], c->d_fine[1], n_rows, st, &res, len);
-            if (rc != SGX_OK) return rc;
-            dim3 g2((unsigned)nblk, (unsigned)n_det);
-            acq_fine_argmax_kernel<<<g2, 256, 0, st>>>(res, npts, 4, uniq - 5, d_pv, d_pi, d_win);
-        }
-        SGX_HIP(hipMemcpyAsync(h_pv, d_pv, sizeof(double) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
-        SGX_HIP(hipMemcpyAsync(h_pi, d_pi, sizeof(long long) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
-        hipEventRecord(c->ev[2], st);
-        SGX_HIP(hipStreamSynchronize(st));
-        for (int d = 0; d < n_det; ++d) {
-            double bv = -1.0;
-            long long bi = 0;
-            for (int b = 0; b < nblk; ++b) {
-                const double v = h_pv[d * nblk + b];
-                const long long i = h_pi[d * nblk + b];
-                if (v > bv || (v == bv && i < bi)) {
-                    bv = v;
-                    bi = i;
-                }
-            }
-            const long long m = bi - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
-            const int o = det_slot[d];
-            carrFreq[o] = ((double)m * S.samplingFreq) / (double)npts;   // acquisition.py:189-191 (Q3)
-            codePhase[o] = (double)det_phase[d];
-            fineIdx[o] = (int)m;
-        }
-    } else {
-        hipEventRecord(c->ev[2], st);
-        SGX_HIP(hipStreamSynchronize(st));
-    }
-    return SGX_OK;
-}
-
-// Peak logic of one PRN (acquisition.py:129-162) in pieces a wave can share.
+// Peak logic of one PRN (acquisition.py:129-162) in pieces a wave can share; the round-1 passes run the same pieces on the
+// host.
 // One bin's candidate: block choice (A7) and its row's maximum / first index.
 struct AcqCand {
     double v;
     int k, a, b;
 };
 // (the row maxima come from other workgroups of the SAME launch, acq_rowmax_peak_kernel: written and read past the
-// per-XCD L2s with device-scope accesses, no cache write-back or invalidation)
+// per-XCD L2s with device-scope accesses, no cache write-back or invalidation; the host reads its own copy)
+#ifdef __HIP_DEVICE_COMPILE__
 #define ACQ_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#else
+#define ACQ_LD(p) (*(p))
+#endif
 #define ACQ_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-__device__ static inline AcqCand acq_peak_bin(const double* __restrict__ rowmax, const int* __restrict__ rowarg, int n_bins,
-                                              int n_blocks, bool noncoh, int k) {
+__host__ __device__ static inline AcqCand acq_peak_bin(const double* __restrict__ rowmax, const int* __restrict__ rowarg,
+                                                       int n_bins, int n_blocks, bool noncoh, int k) {
     int row = k, bsel = 0;
     if (!noncoh) {
         int best = 0;   // acquisition.py:129-133 generalised left to right, later block wins ties
@@ -1023,7 +545,7 @@ __device__ static inline AcqCand acq_peak_bin(const double* __restrict__ rowmax,
 // A scan over the bins in ascending k keeps: the maximum, the FIRST bin attaining it (results.max(1).argmax()), that
 // bin's block, and the SMALLEST column among the bins attaining it (results.max(0).argmax()) - A8.  The same as a
 // combination of two partial scans (k < 0: an empty one):
-__device__ static inline AcqCand acq_peak_join(const AcqCand& x, const AcqCand& y) {
+__host__ __device__ static inline AcqCand acq_peak_join(const AcqCand& x, const AcqCand& y) {
     if (y.k < 0) return x;
     if (x.k < 0) return y;
     if (x.v > y.v) return x;
@@ -1034,7 +556,7 @@ __device__ static inline AcqCand acq_peak_join(const AcqCand& x, const AcqCand& 
 }
 // The exclusion list around the peak's code phase (A8b, acquisition.py:135-162).  Returns 1 where the reference raises
 // IndexError (Q5), else 0.
-__device__ static inline int acq_peak_ranges(int gc, long long N, int spc, int* lo0, int* hi0, int* lo1, int* hi1) {
+__host__ __device__ static inline int acq_peak_ranges(int gc, long long N, int spc, int* lo0, int* hi0, int* lo1, int* hi1) {
     *lo0 = *hi0 = *lo1 = *hi1 = 0;
     const int e1 = gc - spc, e2 = gc + spc;
     if (e1 <= 0) {
@@ -1061,38 +583,12 @@ __device__ static inline int acq_peak_ranges(int gc, long long N, int spc, int* 
     return 0;
 }
 
-// The same for every PRN of a call on the device: fills the second-peak search's arguments and row map, so the host
-// looks at the coarse search once (after the second peaks).
-struct PeakOut {
-    double peak[32];
-    int cph[32], fbi[32];
-    int index_error[32];
-};
-// The coarse search's outcome, written by one small kernel straight into a coherent pinned page: the host spins on
-// `seq` instead of sleeping in hipStreamSynchronize behind two device-to-host copies (~55 us -> ~10 us between the last
-// coarse kernel and the first fine one).
-struct CoarseLook {
-    PeakOut po;
-    double second[32];
-    unsigned long long seq;
-    // device-led fine search (round 4): the detections the publish kernel found (in PRN order, as the reference's loop
-    // finds them), and what the fine search made of them - the host looks ONCE, at seq2
-    int n_det;
-    int range_error;          // a detection's fine window (code phase + 10 ms) leaves the record: 1 + its slot
-    int det_slot[32];         // position in the call's PRN list
-    int det_phase[32];
-    long long fine_bi[32];    // arg-max of the 2^22-point magnitude spectrum over [4, uniq - 5)
-    unsigned long long seq2;
-};
-static_assert(sizeof(CoarseLook) <= 4096, "one pinned page");
-
-// det (device memory, read by the fine kernels): [0] n_det, [1 + d] PRN index, [33 + d] code phase
 // SAME_LAUNCH: the peaks were written by other waves of this launch (device-scope stores): read them the same way.
 template <bool SAME_LAUNCH>
 __device__ __forceinline__ void acq_publish_body(const PeakOut* __restrict__ po, const double* __restrict__ second, int n_prn,
                                                  CoarseLook* __restrict__ host, const int* __restrict__ prn_list,
                                                  double threshold, long long fine_len, long long n_samples,
-                                                 int* __restrict__ det, int t) {
+                                                 AcqDet* __restrict__ det, int t) {
     const int* src = reinterpret_cast<const int*>(po);
     int* dst = reinterpret_cast<int*>(&host->po);
     for (int i = t; i < (int)(sizeof(PeakOut) / sizeof(int)); i += 64) dst[i] = SAME_LAUNCH ? ACQ_LD(src + i) : src[i];
@@ -1113,14 +609,14 @@ __device__ __forceinline__ void acq_publish_body(const PeakOut* __restrict__ po,
         const bool out = hit && (long long)cp + fine_len > n_samples;   // (the reference would fail to broadcast)
         const unsigned long long mo = __builtin_amdgcn_ballot_w64(out);
         if (hit) {
-            det[1 + d] = prn_list[t];
-            det[33 + d] = cp;
+            det->prn[d] = prn_list[t];
+            det->phase[d] = cp;
             host->det_slot[d] = t;
             host->det_phase[d] = cp;
         }
         if (t == 0) {
-            det[80] = 0;                                    // fine_rows_kernel's arrival counter
-            det[0] = mo ? 0 : __builtin_popcountll(m);      // (an error: the fine kernels have nothing to do)
+            det->fine_done = 0;                                 // fine_rows_kernel's arrival counter
+            det->n_det = mo ? 0 : __builtin_popcountll(m);      // (an error: the fine kernels have nothing to do)
             host->n_det = __builtin_popcountll(m);
             host->range_error = mo ? 1 + __builtin_ctzll(mo) : 0;
             host->seq = 0ull;   // device-led: `host` is a device-side copy of the page; fine_rows_kernel's last workgroup
@@ -1128,55 +624,23 @@ __device__ __forceinline__ void acq_publish_body(const PeakOut* __restrict__ po,
     }
 }
 
+// (det: an AcqDet, or null; an int* in the signature, which is part of the kernel's name in traces and profiles)
 __global__ __launch_bounds__(64) void acq_publish_kernel(const PeakOut* __restrict__ po, const double* __restrict__ second,
                                                          int n_prn, CoarseLook* __restrict__ host, unsigned long long seq,
                                                          const int* __restrict__ prn_list, double threshold,
                                                          long long fine_len, long long n_samples, int* __restrict__ det) {
     const int t = threadIdx.x;
-    acq_publish_body<false>(po, second, n_prn, host, prn_list, threshold, fine_len, n_samples, det, t);
+    acq_publish_body<false>(po, second, n_prn, host, prn_list, threshold, fine_len, n_samples, reinterpret_cast<AcqDet*>(det), t);
     if (det) return;
     __threadfence_system();
     __syncthreads();
     if (t == 0) __hip_atomic_store(&host->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Waits for acq_publish_kernel's `seq`.  Spins (bounded), then falls back to the stream synchronisation, after which the
-// page is complete in any case.
-static int coarse_look_wait(sgx_ctx* c, unsigned long long seq, bool second = false) {
-    const CoarseLook* h0 = (const CoarseLook*)c->h_look;
-    const unsigned long long* word = second ? &h0->seq2 : &h0->seq;
-    const char* sp = getenv("SGX_ACQ_SPIN");
-    if (!(sp && sp[0] == '0')) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned it = 0;; ++it) {
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGX_OK;
-            if ((it & 1023u) == 1023u &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
-                break;
-        }
-    }
-    SGX_HIP(hipStreamSynchronize(c->stream));
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
-        sgx_set_error("acquisition: the search's result page was not written");
-        return SGX_E_HIP;
-    }
-    return SGX_OK;
-}
-
-// One WAVE per PRN, a lane per Doppler bin (one lane per PRN scanning its rows was a chain of dependent loads: 12 us).
-__device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, const int* __restrict__ rowarg, int pi,
-                                             int lane, int n_prn, int out_per_prn, int n_bins, int n_blocks, int noncoh,
-                                             long long N, int spc, PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
-                                             int2* __restrict__ row_map) {
-    if (pi >= n_prn) {
-        if (lane == 0) {
-            sa->row[pi] = -1;
-            sa->lo0[pi] = sa->hi0[pi] = sa->lo1[pi] = sa->hi1[pi] = 0;
-        }
-        return;
-    }
-    const double* __restrict__ pm = rowmax + (long long)pi * out_per_prn;
-    const int* __restrict__ pa = rowarg + (long long)pi * out_per_prn;
+// The peak of one PRN, a lane per Doppler bin (one lane per PRN scanning its rows was a chain of dependent loads: 12 us);
+// lane 0 holds the result.
+__device__ __forceinline__ AcqCand acq_peak_reduce(const double* __restrict__ pm, const int* __restrict__ pa, int lane,
+                                                   int n_bins, int n_blocks, int noncoh) {
     AcqCand c;
     c.v = -1.0;
     c.k = -1;
@@ -1191,6 +655,33 @@ __device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, 
         o.b = __shfl_down(c.b, off);
         c = acq_peak_join(c, o);
     }
+    return c;
+}
+// ... and on every lane of the wave
+__device__ __forceinline__ AcqCand acq_peak_scan(const double* __restrict__ pm, const int* __restrict__ pa, int lane,
+                                                 int n_bins, int n_blocks, int noncoh) {
+    AcqCand c = acq_peak_reduce(pm, pa, lane, n_bins, n_blocks, noncoh);
+    c.v = __shfl(c.v, 0);
+    c.k = __shfl(c.k, 0);
+    c.a = __shfl(c.a, 0);
+    c.b = __shfl(c.b, 0);
+    return c;
+}
+
+// One WAVE per PRN: its peak, exclusion list and the row the second-peak search transforms again.
+__device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, const int* __restrict__ rowarg, int pi,
+                                             int lane, int n_prn, int out_per_prn, int n_bins, int n_blocks, int noncoh,
+                                             long long N, int spc, PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
+                                             int2* __restrict__ row_map) {
+    if (pi >= n_prn) {
+        if (lane == 0) {
+            sa->row[pi] = -1;
+            sa->lo0[pi] = sa->hi0[pi] = sa->lo1[pi] = sa->hi1[pi] = 0;
+        }
+        return;
+    }
+    const AcqCand c = acq_peak_reduce(rowmax + (long long)pi * out_per_prn, rowarg + (long long)pi * out_per_prn, lane, n_bins,
+                                      n_blocks, noncoh);
     if (lane != 0) return;
     int lo0, hi0, lo1, hi1;
     const int bad = acq_peak_ranges(c.a, N, spc, &lo0, &hi0, &lo1, &hi1);
@@ -1210,21 +701,17 @@ __device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, 
     }
 }
 
-// acq_rowmax_finish_kernel and the peak step in one launch (round 4): a wave finishes one output row; the wave that
-// finishes the LAST row of a PRN (arrival counter per PRN, zeroed by the call's set-up) goes on to that PRN's block
-// choice, global peak and exclusion list.  The last PRN's wave also fills the unused slots of the second-peak arguments.
-__global__ __launch_bounds__(64) void acq_rowmax_peak_kernel(const double* __restrict__ pmax, const int* __restrict__ parg,
-                                                             int nblk, double* __restrict__ rowmax, int* __restrict__ rowarg,
-                                                             int* __restrict__ arrived, int n_prn, int out_per_prn,
-                                                             int n_bins, int n_blocks, int noncoh, long long N, int spc,
-                                                             PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
-                                                             int2* __restrict__ row_map) {
-    const int row = blockIdx.x, lane = threadIdx.x;
+// A wave finishes one output row from its `n` partial (maximum, first index) pairs, stores it and counts the arrival at
+// its PRN *pi_out (arrival counter per PRN, zeroed by the call's set-up).  Returns, on every lane, whether this was the
+// LAST row of the PRN.
+__device__ __forceinline__ int acq_row_finish(const double* __restrict__ pv, const int* __restrict__ pidx, int n, int row,
+                                              int lane, double* __restrict__ rowmax, int* __restrict__ rowarg,
+                                              int* __restrict__ arrived, int out_per_prn, int* pi_out) {
     double best = -1.0;
     int arg = 0;
-    for (int b = lane; b < nblk; b += 64) {
-        const double v = pmax[(long long)row * nblk + b];
-        const int i = parg[(long long)row * nblk + b];
+    for (int b = lane; b < n; b += 64) {
+        const double v = pv[(long long)row * n + b];
+        const int i = pidx[(long long)row * n + b];
         if (v > best || (v == best && i < arg)) {
             best = v;
             arg = i;
@@ -1239,6 +726,7 @@ __global__ __launch_bounds__(64) void acq_rowmax_peak_kernel(const double* __res
         }
     }
     const int pi = row / out_per_prn;
+    *pi_out = pi;
     int last = 0;
     if (lane == 0) {
         ACQ_ST(rowmax + row, best);
@@ -1246,35 +734,24 @@ __global__ __launch_bounds__(64) void acq_rowmax_peak_kernel(const double* __res
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // both written through before the arrival is counted
         last = __hip_atomic_fetch_add(arrived + pi, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == out_per_prn;
     }
-    last = __builtin_amdgcn_readfirstlane(last);
-    if (!last) return;
+    return __builtin_amdgcn_readfirstlane(last);
+}
+
+// acq_rowmax_finish_kernel and the peak step in one launch (round 4): a wave finishes one output row; the wave that
+// finishes the LAST row of a PRN goes on to that PRN's block choice, global peak and exclusion list.  The last PRN's wave
+// also fills the unused slots of the second-peak arguments.
+__global__ __launch_bounds__(64) void acq_rowmax_peak_kernel(const double* __restrict__ pmax, const int* __restrict__ parg,
+                                                             int nblk, double* __restrict__ rowmax, int* __restrict__ rowarg,
+                                                             int* __restrict__ arrived, int n_prn, int out_per_prn,
+                                                             int n_bins, int n_blocks, int noncoh, long long N, int spc,
+                                                             PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
+                                                             int2* __restrict__ row_map) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    int pi;
+    if (!acq_row_finish(pmax, parg, nblk, row, lane, rowmax, rowarg, arrived, out_per_prn, &pi)) return;
     acq_peak_one(rowmax, rowarg, pi, lane, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map);
     if (pi == n_prn - 1 && n_prn + lane < 32)
         acq_peak_one(rowmax, rowarg, n_prn + lane, 0, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map);
-}
-
-// The peak of one PRN on every lane of the wave (acq_peak_one's scan, result broadcast).
-__device__ __forceinline__ AcqCand acq_peak_scan(const double* __restrict__ pm, const int* __restrict__ pa, int lane,
-                                                 int n_bins, int n_blocks, int noncoh) {
-    AcqCand c;
-    c.v = -1.0;
-    c.k = -1;
-    c.a = c.b = 0;
-    for (int k = lane; k < n_bins; k += 64) c = acq_peak_join(c, acq_peak_bin(pm, pa, n_bins, n_blocks, noncoh != 0, k));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        AcqCand o;
-        o.v = __shfl_down(c.v, off);
-        o.k = __shfl_down(c.k, off);
-        o.a = __shfl_down(c.a, off);
-        o.b = __shfl_down(c.b, off);
-        c = acq_peak_join(c, o);
-    }
-    c.v = __shfl(c.v, 0);
-    c.k = __shfl(c.k, 0);
-    c.a = __shfl(c.a, 0);
-    c.b = __shfl(c.b, 0);
-    return c;
 }
 
 struct PublishArgs {
@@ -1282,7 +759,7 @@ struct PublishArgs {
     const int* prn_list;
     double threshold;
     long long fine_len, n_samples;
-    int* det;
+    AcqDet* det;
 };
 
 // Round 5: row maxima, peak, SECOND PEAK and the detection list in one launch, from the rows kernel's per-residue
@@ -1300,34 +777,8 @@ __global__ __launch_bounds__(64) void acq_rowtop2_peak_kernel(const double* __re
                                                               PeakOut* __restrict__ po, double* __restrict__ second,
                                                               PublishArgs pub) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    double best = -1.0;
-    int arg = 0;
-    for (int r = lane; r < nres; r += 64) {
-        const double v = b1[(long long)row * nres + r];
-        const int i = i1[(long long)row * nres + r];
-        if (v > best || (v == best && i < arg)) {
-            best = v;
-            arg = i;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_down(best, o);
-        const int oi = __shfl_down(arg, o);
-        if (ov > best || (ov == best && oi < arg)) {
-            best = ov;
-            arg = oi;
-        }
-    }
-    const int pi = row / out_per_prn;
-    int last = 0;
-    if (lane == 0) {
-        ACQ_ST(rowmax + row, best);
-        ACQ_ST(rowarg + row, arg);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // both written through before the arrival is counted
-        last = __hip_atomic_fetch_add(arrived + pi, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == out_per_prn;
-    }
-    last = __builtin_amdgcn_readfirstlane(last);
-    if (!last) return;
+    int pi;
+    if (!acq_row_finish(b1, i1, nres, row, lane, rowmax, rowarg, arrived, out_per_prn, &pi)) return;
     const AcqCand c = acq_peak_scan(rowmax + (long long)pi * out_per_prn, rowarg + (long long)pi * out_per_prn, lane, n_bins,
                                     n_blocks, noncoh);
     int lo0, hi0, lo1, hi1;
@@ -1358,492 +809,6 @@ __global__ __launch_bounds__(64) void acq_rowtop2_peak_kernel(const double* __re
     acq_publish_body<true>(po, second, n_prn, pub.stage, pub.prn_list, pub.threshold, pub.fine_len, pub.n_samples, pub.det,
                            lane);
 }
-
-// How the correlation batch of a call is cut (round 5).  Rows are ordered (PRN, block, bin) - coherent - or (PRN, bin, block)
-// - non-coherent sums; a chunk is whole PRNs (prn_chunk of them) or, for non-coherent sums whose PRN does not fit half a
-// chunk, ONE PRN's rows of a run of Doppler bins (bin_runs runs per PRN: a run is a batch of its own with fewer bins).
-// The chunks alternate between `queues` HIP streams, each with its own intermediate of chunk_rows / queues rows: the columns
-// kernel is bound by its stores and the rows kernel by its loads, and with two chunks in flight the one's stores overlap
-// the other's loads (0.85 -> 0.77 ms for config 2, 3.21 -> 2.89 ms for config 4; both kernels move their bytes at 3-5 TB/s
-// over the same fabric - the intermediate lives in the Infinity Cache - so a producer / consumer fusion has no more to win).
-struct AcqPlan {
-    int prn_chunk, bin_runs, bins_per_run, queues;
-};
-static AcqPlan acq_plan(int n_prn, int n_bins, int n_blocks, bool noncoh, int chunk_rows, int max_queues) {
-    if (chunk_rows > ACQ_MAX_ROWS) chunk_rows = ACQ_MAX_ROWS;
-    if (chunk_rows < 1) chunk_rows = 1;
-    const int rows_per_prn = n_bins * n_blocks;
-    AcqPlan p;
-    p.bin_runs = 1;
-    p.queues = (max_queues >= 2 && n_prn >= 2 && chunk_rows / 2 >= rows_per_prn) ? 2 : 1;
-    if (max_queues >= 2 && p.queues == 1 && noncoh && rows_per_prn > chunk_rows / 2 && rows_per_prn <= chunk_rows && n_bins >= 2) {
-        int runs = (rows_per_prn + chunk_rows / 2 - 1) / (chunk_rows / 2);
-        if (runs > n_bins) runs = n_bins;
-        if (runs >= 2) {
-            p.bin_runs = runs;
-            p.queues = 2;
-        }
-    }
-    if (p.queues == 2 && p.bin_runs == 1) chunk_rows /= 2;
-    p.prn_chunk = p.bin_runs > 1 ? 1 : chunk_rows / rows_per_prn;   // (a run of bins belongs to ONE PRN)
-    if (p.prn_chunk < 1) p.prn_chunk = 1;
-    if (p.prn_chunk > n_prn) p.prn_chunk = n_prn;
-    if (p.queues == 2 && p.bin_runs == 1 && p.prn_chunk > (n_prn + 1) / 2) p.prn_chunk = (n_prn + 1) / 2;   // (both queues get work)
-    p.bins_per_run = (n_bins + p.bin_runs - 1) / p.bin_runs;
-    return p;
-}
-extern "C" int sgx_acquire_plan(int32_t n_prn, int32_t n_bins, int32_t n_blocks, int32_t noncoh, int32_t chunk_rows,
-                                int32_t max_queues, int32_t* prn_chunk, int32_t* bin_runs, int32_t* bins_per_run,
-                                int32_t* queues) {
-    SGX_CHECK_ARG(n_prn >= 1 && n_bins >= 1 && n_blocks >= 1 && prn_chunk && bin_runs && bins_per_run && queues);
-    const AcqPlan p = acq_plan(n_prn, n_bins, n_blocks, noncoh != 0, chunk_rows > 0 ? chunk_rows : ACQ_DEFAULT_CHUNK_ROWS, max_queues);
-    *prn_chunk = p.prn_chunk;
-    *bin_runs = p.bin_runs;
-    *bins_per_run = p.bins_per_run;
-    *queues = p.queues;
-    return SGX_OK;
-}
-
-extern "C" int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows) {
-    SGX_CHECK_ARG(default_chunk_rows && max_rows);
-    *default_chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
-    *max_rows = ACQ_MAX_ROWS;
-    return SGX_OK;
-}
-
-// The acquisition on the four-step transform (sgx_fft.hip): every 38192-point transform is two kernels with register-resident
-// sub-transforms, the mixed-signal spectra are computed once per (block, phi) and read with a circular shift, results
-// land where they are needed (no device-to-device copies) and the host looks at the device ONCE, at the very end of the
-// call (round 4: peaks, second peaks, the detections and their fine-search results arrive in one pinned page), whatever the
-// number of PRN chunks.
-static int acquire_four_step(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0,
-                             int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
-                             double* peakMetric, int32_t* freqBin, int32_t* fineIdx, bool* handled, bool defer) {
-    *handled = false;
-    const long long N = c->n_code;
-    const sgx_settings& S = c->s;
-    const char* v1 = getenv("SGX_ACQ_V1");
-    if ((v1 && v1[0] == '1') || !sgx_fft4_supported(N)) return SGX_OK;
-    const int n_bins = (int)(nearbyint(S.acqSearchBand * 2) + 1);
-    if (n_bins < 1 || n_bins > ACQ_MAX_BINS) return SGX_OK;
-    // f N / fs = shift + phi for every bin; the path needs few distinct phi
-    PhiArgs pa;
-    pa.n_phi = 0;
-    std::vector<int2> bin_map((size_t)n_bins);
-    for (int k = 0; k < n_bins; ++k) {
-        const double f = S.IF - S.acqSearchBand / 2 * 1000 + 500.0 * k;   // A4 (acquisition.py:68,99-101)
-        const double ratio = f * (double)N / S.samplingFreq;
-        double sh = floor(ratio + 1e-9);
-        double phi = ratio - sh;
-        if (phi < 1e-9) phi = 0.0;
-        int j = -1;
-        for (int q = 0; q < pa.n_phi; ++q)
-            if (fabs(pa.phi[q] - phi) < 1e-9) j = q;
-        if (j < 0) {
-            if (pa.n_phi == 4) return SGX_OK;   // too many distinct fractions: the direct path mixes every bin
-            j = pa.n_phi;
-            pa.phi[pa.n_phi++] = phi;
-        }
-        long long shm = (long long)sh % N;
-        if (shm < 0) shm += N;
-        bin_map[(size_t)k] = make_int2(j, (int)shm);
-    }
-    if (pa.n_phi >= n_bins && n_bins > 1) return SGX_OK;
-    *handled = true;
-
-    hipStream_t st = c->stream;
-    const double ts = 1.0 / S.samplingFreq;
-    const double tc = 1.0 / S.codeFreqBasis;
-    const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
-    int rc = sgx_fft_plan_create(&c->plan_code, N);
-    if (rc != SGX_OK) return rc;
-
-    // ---- scratch ------------------------------------------------------------------------------
-    const int n_phi = pa.n_phi;
-    const int rows_fwd = n_blocks * n_phi;
-    const int rows_per_prn = n_blocks * n_bins;
-    SGX_CHECK_ARG(rows_per_prn <= ACQ_MAX_ROWS);
-    // PRN chunks of ~350 rows: a chunk's intermediate (213 MB) then stays in the 256 MiB Infinity Cache between the
-    // columns kernel that writes it and the rows kernel that reads it, and the next chunk overwrites it there.  With the
-    // round-3 kernels - bound by their stores and by the dirty lines on their way out, not by instruction issue or LDS
-    // any more - that is 0.94 -> 0.80 ms for config 2 and 3.43 -> 3.24 ms for config 4 (tools/acq_chunk_probe.py; the
-    // round-2 kernels measured no difference).
-    int chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
-    {
-        const char* ce = getenv("SGX_ACQ_CHUNK_ROWS");
-        if (ce && atoi(ce) > 0) chunk_rows = atoi(ce);
-    }
-    const char* se = getenv("SGX_ACQ_STREAMS");
-    const AcqPlan plan = acq_plan(n_prn, n_bins, n_blocks, noncoh != 0, chunk_rows, (se && se[0] == '1') ? 1 : 2);
-    const bool two_q = plan.queues == 2;
-    const int bin_runs = plan.bin_runs, prn_chunk = plan.prn_chunk;
-    const size_t row_bytes = sizeof(cplx) * (size_t)N;
-    size_t work_rows = (size_t)prn_chunk * rows_per_prn;
-    if (work_rows < (size_t)(rows_fwd + n_prn)) work_rows = (size_t)(rows_fwd + n_prn);
-    if (work_rows < (size_t)n_prn * (noncoh ? n_blocks : 1)) work_rows = (size_t)n_prn * (noncoh ? n_blocks : 1);
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
-    const int nblk = sgx_fft4_row_blocks();
-    const int nres = sgx_fft4_residues();
-    const int rows_out_all = n_prn * (noncoh ? n_bins : rows_per_prn);
-    // Round 5: peak and second peak from ONE pass (acq_rowtop2_peak_kernel) when the exclusion list leaves out fewer than
-    // `nres` consecutive indices (2 spc of them at most: any sampling rate below 111 MHz); SGX_ACQ_TOP2=0: the round-4
-    // sequence, which transforms each PRN's winning row a second time
-    const char* t2e = getenv("SGX_ACQ_TOP2");
-    const bool top2 = 2 * spc + 1 <= nres && !(t2e && t2e[0] == '0');
-    size_t pow_need = (size_t)rows_out_all * nblk * 12 + 4096;
-    if (noncoh && pow_need < (size_t)n_prn * sizeof(double) * (size_t)N) pow_need = (size_t)n_prn * sizeof(double) * (size_t)N;
-    // [per-workgroup maxima | their indices] or [per-residue maxima | second maxima | indices], [row maxima | row indices],
-    // then (non-coherent, round-4 sequence) the second-peak power rows
-    const size_t part_bytes = (((size_t)rows_out_all * (top2 ? (size_t)nres * 20 : (size_t)nblk * 12)) + 255) / 256 * 256;
-    const size_t red_bytes = (part_bytes + (size_t)rows_out_all * 12 + 1023) / 256 * 256;
-    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, red_bytes + pow_need)) != SGX_OK) return rc;
-    char* red = (char*)c->d_pow;
-    double* d_pmax = (double*)red;
-    int* d_parg = (int*)(red + (size_t)rows_out_all * nblk * 8);
-    double* d_t2b1 = (double*)red;
-    double* d_t2b2 = d_t2b1 + (size_t)rows_out_all * nres;
-    int* d_t2i1 = (int*)(d_t2b2 + (size_t)rows_out_all * nres);
-    double* d_rowmax = (double*)(red + part_bytes);
-    int* d_rowarg = (int*)(red + part_bytes + (size_t)rows_out_all * 8);
-    double* d_power = (double*)(red + red_bytes);
-
-    char* dsm = (char*)c->d_small;
-    char* hsm = (char*)c->h_small;
-    long long* d_sum = (long long*)dsm;
-    int* d_prn = (int*)(dsm + 64);
-    double* d_second = (double*)(dsm + 1024 + 12 * 4096);
-    int2* d_binmap = (int2*)(dsm + 1024);              // [n_bins <= 128]
-    int2* d_map = (int2*)(dsm + 200000);
-    int* d_arrived = (int*)(dsm + 51200);              // [32] rows finished per PRN (acq_rowmax_peak_kernel)
-
-    hipEventRecord(c->ev[0], st);
-    cplx* const d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
-    {
-        // ---- set-up, record sum, mixed rows (n_blocks x n_phi, PRN independent) and code rows (n_prn): one launch for
-        //      int8 records; then the forward spectra of all of them as ONE batch, straight into d_fwd = [forward | code]
-        AcqSetup su;
-        memset(&su, 0, sizeof(su));
-        su.n_prn = n_prn;
-        su.n_bins = n_bins;
-        for (int i = 0; i < n_prn; ++i) su.prn[i] = prn0[i];
-        for (int k = 0; k < n_bins; ++k) su.bin[k] = bin_map[(size_t)k];
-        const char* fr0 = getenv("SGX_ACQ_FRONT");
-        static_assert(ACQ_MAX_BINS <= 256, "the set-up workgroup has 256 threads");
-        if (!x.f64 && !(fr0 && fr0[0] == '0')) {
-            const int ph = c->acq_sum_phase & 1;
-            long long* sum_now = (long long*)(dsm + 16) + ph;
-            long long* sum_next = (long long*)(dsm + 16) + (ph ^ 1);
-            if (!c->acq_sum_clean[ph]) SGX_HIP(hipMemsetAsync(sum_now, 0, 8, st));
-            const unsigned gx = (unsigned)((N + 255) / 256);
-            acq_front_kernel<<<(unsigned)(rows_fwd + n_prn) * gx + ACQ_SUM_WGS + 1, 256, 0, st>>>(
-                su, x, pa, c->d_codes, c->d_work[1], N, rows_fwd, ts, tc, (long long)n_samples, d_prn, d_binmap, sum_now,
-                sum_next, d_second, d_arrived);
-            c->acq_sum_clean[ph] = false;
-            c->acq_sum_clean[ph ^ 1] = true;
-            c->acq_sum_phase = ph ^ 1;
-            d_sum = sum_now;
-        } else {
-            acq_setup_kernel<<<1, 128, 0, st>>>(su, d_prn, d_binmap, d_sum, d_second, d_arrived);
-            if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)n_samples, d_sum);
-            else acq_sum_kernel<<<64, 256, 0, st>>>(x.i8, (long long)n_samples, d_sum);
-            dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows_fwd);
-            acq_mixphi_kernel<<<grid, 256, 0, st>>>(x, c->d_work[1], N, pa);
-            dim3 grid2((unsigned)((N + 255) / 256), (unsigned)n_prn);
-            acq_code_kernel<<<grid2, 256, 0, st>>>(c->d_codes, d_prn, c->d_work[1] + (size_t)rows_fwd * (size_t)N, N, ts, tc);
-        }
-        rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
-        if (rc != SGX_OK) return rc;
-    }
-    for (int i = 0; i < n_prn; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
-    }
-    // ---- correlation, all PRN chunks queued back to back; row maxima of every PRN collected on the device -----------
-    const double inv_n = 1.0 / (double)N;
-    const int out_per_prn = noncoh ? n_bins : rows_per_prn;
-    hipStream_t st2 = st;
-    if (two_q) {
-        if (!c->acq_stream2) {
-            // (into locals; the context gets them only when ALL exist - a half-made second queue would fail every later call)
-            int least = 0, greatest = 0;
-            SGX_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            hipStream_t ns = nullptr;
-            hipEvent_t ne[2] = {nullptr, nullptr};
-            hipError_t ce = (c->priority == 0) ? hipStreamCreateWithFlags(&ns, hipStreamNonBlocking)
-                                               : hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, c->priority < 0 ? greatest : least);
-            for (int i = 0; i < 2 && ce == hipSuccess; ++i) ce = hipEventCreateWithFlags(&ne[i], hipEventDisableTiming);
-            if (ce != hipSuccess) {
-                for (int i = 0; i < 2; ++i)
-                    if (ne[i]) hipEventDestroy(ne[i]);
-                if (ns) hipStreamDestroy(ns);
-                sgx_set_error("acquisition: the second queue could not be created: %s", hipGetErrorString(ce));
-                return SGX_E_HIP;
-            }
-            c->acq_stream2 = ns;
-            c->acq_ev2[0] = ne[0];
-            c->acq_ev2[1] = ne[1];
-        }
-        st2 = c->acq_stream2;
-        // (the second queue's intermediate is the buffer the forward transforms read: they are queued in front)
-        SGX_HIP(hipEventRecord(c->acq_ev2[0], st));
-        SGX_HIP(hipStreamWaitEvent(st2, c->acq_ev2[0], 0));
-    }
-    int chunk_no = 0;
-    const int bins_per_run = plan.bins_per_run;
-    for (int p0 = 0; p0 < n_prn; p0 += prn_chunk)
-        for (int bin0 = 0; bin0 < n_bins; bin0 += bins_per_run, ++chunk_no) {
-            const int np = (p0 + prn_chunk <= n_prn) ? prn_chunk : (n_prn - p0);
-            const int nb = bin_runs == 1 ? n_bins : (bin0 + bins_per_run <= n_bins ? bins_per_run : n_bins - bin0);
-            Fft4Fuse fu;
-            fu.mul_x = c->d_fwd;
-            fu.mul_f = d_codefd;
-            fu.bin_map = d_binmap + bin0;    // (a run of bins is a batch of its own with fewer bins)
-            fu.n_bins = nb;
-            fu.n_phi = n_phi;
-            fu.rows_per_prn = bin_runs == 1 ? rows_per_prn : nb * n_blocks;
-            fu.prn_base = p0;
-            fu.n_blocks = n_blocks;
-            fu.blocks_fast = noncoh ? 1 : 0;
-            const size_t out0 = ((size_t)p0 * out_per_prn + (size_t)bin0);
-            if (top2) {
-                fu.t2_b1 = d_t2b1 + out0 * nres;
-                fu.t2_b2 = d_t2b2 + out0 * nres;
-                fu.t2_i1 = d_t2i1 + out0 * nres;
-            } else {
-                fu.pmax = d_pmax + out0 * nblk;
-                fu.parg = d_parg + out0 * nblk;
-            }
-            fu.inv_n = inv_n;
-            fu.sum_blocks = noncoh ? n_blocks : 1;
-            const int q = two_q ? (chunk_no & 1) : 0;
-            rc = sgx_fft4_forward(&c->plan_code, nullptr, c->d_work[q], nullptr, (int64_t)np * fu.rows_per_prn, q ? st2 : st, &fu);
-            if (rc != SGX_OK) {
-                // (the second queue may still hold chunks that write d_work[1]: nothing of the next call may overtake them)
-                if (two_q) hipStreamSynchronize(st2);
-                return rc;
-            }
-        }
-    if (two_q) {
-        SGX_HIP(hipEventRecord(c->acq_ev2[1], st2));
-        SGX_HIP(hipStreamWaitEvent(st, c->acq_ev2[1], 0));
-    }
-    // ---- the fine search is queued right behind the coarse one: the detections are decided on the device
-    //      (acquisition.py:164-166) and the fine kernels read their list, so the host looks ONCE, at the very end ----------
-    const unsigned long long seq = ++c->look_seq;
-    const long long fine_len = 10 * N;
-    const long long npts = 8ll << (long long)ceil(log2((double)fine_len));
-    const long long uniq = (long long)ceil((double)(npts + 1) / 2.0);
-    const char* fv1 = getenv("SGX_ACQ_FINE_V1");
-    const char* dl0 = getenv("SGX_ACQ_DEVICE_LED");
-    const bool device_led = sgx_fft_fine_supported(npts) && !(fv1 && fv1[0] == '1') && !(dl0 && dl0[0] == '0') && n_prn <= 32;
-    int* d_det = (int*)(dsm + 640000);
-    double* d_pv = (double*)(dsm + 65536);
-    long long* d_pi = (long long*)(dsm + 400000);
-    if (device_led) {
-        // (before the last coarse kernels are queued: nothing of the host's between them and the fine kernels)
-        rc = sgx_fft_plan_create(&c->plan_fine, npts);
-        if (rc != SGX_OK) return rc;
-        const int max_rows = (n_prn + 1) / 2;   // two real signals per complex row; only the detections' rows are touched
-        if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)max_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK) return rc;
-    }
-    // (device-led: into a device-side copy of the page - a kernel that writes host memory ends with a flush the next one
-    // waits for, 5 us in front of the fine search)
-    CoarseLook* const d_stage = (CoarseLook*)(dsm + 700000);
-    // ---- device: row maxima, then per PRN block choice, global peak, exclusion list, second peak -----------------------
-    PeakOut* d_po = (PeakOut*)(dsm + 620000);
-    SecondArgs* d_sa = (SecondArgs*)(dsm + 600000);
-    if (top2) {
-        PublishArgs pub;
-        pub.stage = device_led ? d_stage : nullptr;
-        pub.prn_list = d_prn;
-        pub.threshold = S.acqThreshold;
-        pub.fine_len = fine_len;
-        pub.n_samples = (long long)n_samples;
-        pub.det = d_det;
-        acq_rowtop2_peak_kernel<<<rows_out_all, 64, 0, st>>>(d_t2b1, d_t2b2, d_t2i1, nres, d_rowmax, d_rowarg, d_arrived, n_prn,
-                                                             out_per_prn, n_bins, n_blocks, noncoh, N, spc, d_po, d_second, pub);
-    } else {
-        acq_rowmax_peak_kernel<<<rows_out_all, 64, 0, st>>>(d_pmax, d_parg, nblk, d_rowmax, d_rowarg, d_arrived, n_prn,
-                                                            out_per_prn, n_bins, n_blocks, noncoh, N, spc, d_po, d_sa, d_map);
-        // the rows the second-peak search reads, transformed again
-        const int rows2 = n_prn * (noncoh ? n_blocks : 1);
-        Fft4Fuse fu;
-        fu.mul_x = c->d_fwd;
-        fu.mul_f = d_codefd;
-        fu.bin_map = d_binmap;
-        fu.row_map = d_map;
-        fu.n_bins = n_bins;
-        fu.n_phi = n_phi;
-        fu.n_blocks = n_blocks;
-        // the rows kernel folds each row's maximum over the exclusion list into d_second itself (the same powers, formed
-        // by the same arithmetic, as the first pass: peak / second peak is a ratio of consistently rounded values);
-        // neither the rows nor their powers are stored
-        static_assert(sizeof(SecondArgs) == 5 * 32 * sizeof(int), "row / lo0 / hi0 / lo1 / hi1, 32 each");
-        fu.sec = reinterpret_cast<const int*>(d_sa);
-        fu.second_out = d_second;
-        fu.inv_n = inv_n;
-        fu.sum_blocks = noncoh ? n_blocks : 1;
-        rc = sgx_fft4_forward(&c->plan_code, nullptr, c->d_work[0], nullptr, rows2, st, &fu);
-        if (rc != SGX_OK) return rc;
-    }
-    if (!top2 || !device_led)
-        acq_publish_kernel<<<1, 64, 0, st>>>(d_po, d_second, n_prn, device_led ? d_stage : (CoarseLook*)c->d_look, seq, d_prn,
-                                             S.acqThreshold, fine_len, (long long)n_samples, device_led ? d_det : nullptr);
-    // (an event between the coarse and the fine kernels holds the fine search back by 6-8 us: recorded on request only)
-    const char* sev = getenv("SGX_ACQ_SPLIT_EVENT");   // (read per call, like every other SGX_ACQ_* knob)
-    const bool split_event = sev && sev[0] == '1';
-    if (split_event || !device_led) hipEventRecord(c->ev[1], st);
-    SGX_HIP(hipGetLastError());
-    if (device_led) {
-        rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, nullptr, nullptr, n_prn, fine_len, d_sum, (double)n_samples, ts,
-                                 1.0 / S.codeFreqBasis, c->d_fine[0], 4, uniq - 5, d_pv, d_pi, st, d_det,
-                                 ((CoarseLook*)c->d_look)->fine_bi, &((CoarseLook*)c->d_look)->seq2, seq,
-                                 reinterpret_cast<const int*>(d_stage), reinterpret_cast<int*>(c->d_look),
-                                 (int)(offsetof(CoarseLook, fine_bi) / sizeof(int)));
-        if (rc != SGX_OK) return rc;
-        hipEventRecord(c->ev[2], st);
-        SGX_HIP(hipGetLastError());
-        // everything is queued; what the look needs to be decoded later (sgx_acquire_finish)
-        AcqPending& P = c->acq_pending;
-        P.mode = 1;
-        P.seq = seq;
-        P.n_prn = n_prn;
-        for (int i = 0; i < n_prn; ++i) P.prn0[i] = prn0[i];
-        P.N = N;
-        P.npts = npts;
-        P.fine_len = fine_len;
-        P.n_samples = n_samples;
-        if (defer) return SGX_OK;
-        return sgx_acquire_finish(c, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-    }
-    rc = coarse_look_wait(c, seq);
-    if (rc != SGX_OK) return rc;
-    const CoarseLook* look = (const CoarseLook*)c->h_look;
-    const PeakOut* h_po = &look->po;
-    const double* h_second = look->second;
-    const double* peak = h_po->peak;
-    const int* cph = h_po->cph;
-    const int* fbi = h_po->fbi;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        if (h_po->index_error[pi]) {
-            sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
-                          "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
-                          N, N, prn0[pi], cph[pi]);
-            return SGX_E_INDEX;
-        }
-    }
-    std::vector<int> det_prn, det_phase, det_slot;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        const double ratio = peak[pi] / h_second[pi];
-        peakMetric[pi] = ratio;
-        freqBin[pi] = fbi[pi];
-        if (ratio > S.acqThreshold) {
-            det_prn.push_back(prn0[pi]);
-            det_phase.push_back(cph[pi]);
-            det_slot.push_back(pi);
-        }
-    }
-    rc = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx);
-    if (rc != SGX_OK) return rc;
-    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
-    hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
-    hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
-    return SGX_OK;
-}
-
-// The host's ONE look at a device-led acquisition (queued by acquire_four_step; c->acq_pending says what was asked): waits
-// for the result page's second word, then decodes peaks, detections and fine frequencies exactly as the eager call did.
-int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    AcqPending& P = c->acq_pending;
-    if (P.mode == 2) {   // (the search could not be deferred and ran eagerly: its outputs were kept)
-        P.mode = 0;
-        for (int i = 0; i < P.n_prn; ++i) {
-            carrFreq[i] = P.res_carr[i];
-            codePhase[i] = P.res_cph[i];
-            peakMetric[i] = P.res_met[i];
-            freqBin[i] = P.res_fb[i];
-            fineIdx[i] = P.res_fi[i];
-        }
-        return P.rc;
-    }
-    if (P.mode != 1) {
-        sgx_set_error("sgx_acquire_end: no acquisition is pending on this context");
-        return SGX_E_ARG;
-    }
-    P.mode = 0;
-    const sgx_settings& S = c->s;
-    const int n_prn = P.n_prn;
-    const long long N = P.N, npts = P.npts, fine_len = P.fine_len;
-    const size_t n_samples = P.n_samples;
-    const int* prn0 = P.prn0;
-    for (int i = 0; i < n_prn; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
-    }
-    int rc = coarse_look_wait(c, P.seq, true);
-    if (rc != SGX_OK) return rc;
-    const CoarseLook* look = (const CoarseLook*)c->h_look;
-    const PeakOut* h_po = &look->po;
-    const double* h_second = look->second;
-    const double* peak = h_po->peak;
-    const int* cph = h_po->cph;
-    const int* fbi = h_po->fbi;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        if (h_po->index_error[pi]) {
-            sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
-                          "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
-                          N, N, prn0[pi], cph[pi]);
-            return SGX_E_INDEX;
-        }
-    }
-    int n_det_host = 0;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        const double ratio = peak[pi] / h_second[pi];
-        peakMetric[pi] = ratio;
-        freqBin[pi] = fbi[pi];
-        if (ratio > S.acqThreshold) ++n_det_host;
-    }
-    if (look->range_error) {
-        const int o = look->range_error - 1;
-        sgx_set_error("fine search needs codePhase + 10 ms = %lld samples, record window has %zu "
-                      "(reference acquisition.py:177 would fail to broadcast)", (long long)cph[o] + fine_len, n_samples);
-        return SGX_E_RANGE;
-    }
-    if (look->n_det != n_det_host) {   // (the same comparison on the same doubles: cannot differ)
-        sgx_set_error("acquisition: device found %d detections, host %d", look->n_det, n_det_host);
-        return SGX_E_HIP;
-    }
-    for (int d = 0; d < look->n_det; ++d) {
-        const long long m = look->fine_bi[d] - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
-        const int o = look->det_slot[d];
-        carrFreq[o] = ((double)m * S.samplingFreq) / (double)npts;   // acquisition.py:189-191 (Q3)
-        codePhase[o] = (double)look->det_phase[d];
-        fineIdx[o] = (int)m;
-    }
-    // (the result word is stored a moment before the last kernel retires: the device times below need its event)
-    SGX_HIP(hipEventSynchronize(c->ev[2]));
-    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
-    // (SGX_ACQ_SPLIT_EVENT=1 records an event between the coarse and the fine kernels, which holds the fine search back by
-    // 6-8 us; without it the split is NOT measured: NaN, not total / 0)
-    const char* sev = getenv("SGX_ACQ_SPLIT_EVENT");
-    if (sev && sev[0] == '1') {
-        hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
-        hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
-    } else {
-        c->timing.acq_coarse_ms = __builtin_nanf("");
-        c->timing.acq_fine_ms = __builtin_nanf("");
-    }
-    return SGX_OK;
-}
-
 
 // ================================ round 6: deferred acquisition, preRun on the device ================================
 // The reference's caller (initialize.py:484-506) runs acquire -> preRun -> track and looks at each result in between.  A
@@ -1933,75 +898,7 @@ __global__ __launch_bounds__(64) void acq_prerun_kernel(const CoarseLook* __rest
     }
 }
 
-int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes, long long rec_file_offset, int sample_bytes) {
-    const AcqPending& P = c->acq_pending;
-    if (P.mode != 1 || n_ch < 1 || n_ch > 32) return SGX_E_DEFER;
-    char* dsm = (char*)c->d_small;
-    const CoarseLook* d_stage = (const CoarseLook*)(dsm + 700000);
-    const int* d_prn = (const int*)(dsm + 64);
-    StepLook* look = (StepLook*)((char*)c->d_look + SGX_STEP_LOOK_OFFSET);
-    acq_prerun_kernel<<<1, 64, 0, c->stream>>>(d_stage, ((const CoarseLook*)c->d_look)->fine_bi, d_prn, P.n_prn,
-                                               c->s.samplingFreq, (double)P.npts, d_ch, n_ch, skip_bytes, rec_file_offset,
-                                               sample_bytes, look);
-    SGX_HIP(hipGetLastError());
-    return SGX_OK;
-}
-
-extern "C" int sgx_acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
-                                 int32_t n_prn, int32_t n_blocks, int32_t noncoh) {
-    SGX_CHECK_ARG(c && r && prn0);
-    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32 && n_blocks >= 1 && n_blocks <= 64);
-    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
-    const long long N = c->n_code;
-    if (offset > r->n || n_samples > r->n - offset || (long long)n_samples < (long long)n_blocks * N) {
-        sgx_set_error("record window too short: %zu samples at offset %zu, %lld needed for the coarse search",
-                      n_samples, offset, (long long)n_blocks * N);
-        return SGX_E_RANGE;
-    }
-    {
-        const int rq = sgx_if_require(r, offset + n_samples);
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    SgxSig x;
-    x.i8 = r->d + offset;
-    x.f64 = nullptr;
-    AcqPending& P = c->acq_pending;
-    P.mode = 0;
-    bool handled = false;
-    int rc = acquire_four_step(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, P.res_carr, P.res_cph, P.res_met, P.res_fb,
-                               P.res_fi, &handled, true);
-    if (handled && P.mode == 1) return rc;          // queued; nothing has been looked at
-    if (!handled)
-        rc = acquire_passes(c, x, n_samples, prn0, n_prn, n_blocks, noncoh, P.res_carr, P.res_cph, P.res_met, P.res_fb, P.res_fi);
-    // (a path without the device-led sequence: it ran eagerly; sgx_acquire_end hands its outputs over)
-    P.mode = 2;
-    P.n_prn = n_prn;
-    P.rc = rc;
-    return SGX_OK;
-}
-
-extern "C" int sgx_acquire_end(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
-                               int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_HIP(hipSetDevice(c->device));
-    return sgx_acquire_finish(c, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-}
-
-
-// ================================ round 6: the sharded search as ONE call ================================
-// BASELINE configs[3]: the PRN loop (acquisition.py:92) shards over the ranks, the peaks are gathered.  Rounds 1-5 did the
-// pack, the gather and the merge in Python around sgx_acquire (softgnss-python_amd/shard.py): 0.17-0.28 ms of host time per
-// call next to a 0.45 ms shard.  Here the rank's search is queued, its peaks are packed into 40-byte records ON THE DEVICE
-// behind it, one ncclAllGather follows on the same stream, a small kernel copies the gathered records to the result page and
-// the host looks ONCE; the merge into the 32-entry arrays is a loop over at most 32 records.
-struct PeakRec {      // = shard.PEAK_DTYPE, 40 bytes
-    int prn0, freqBin;
-    double carrFreq, codePhase, peakMetric;
-    int fineIdx, valid;   // valid 1; 0 unused slot; -1 the reference's IndexError at this PRN; -2 its fine window leaves the record
-};
-static_assert(sizeof(PeakRec) == 40, "shard.PEAK_DTYPE");
-
+// The sharded search's rank-local peaks as 40-byte records (PeakRec), packed on the device behind the search
 __global__ __launch_bounds__(64) void acq_pack_kernel(const CoarseLook* __restrict__ stage, const long long* __restrict__ fine_bi,
                                                       const int* __restrict__ prn_list, int n_prn, double fs, double npts,
                                                       PeakRec* __restrict__ out, int slots) {
@@ -2037,135 +934,91 @@ __global__ __launch_bounds__(256) void acq_gather_publish_kernel(const int* __re
     if (threadIdx.x == 0) __hip_atomic_store(word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int32_t world, const sgx_if* r, size_t offset,
-                                   size_t n_samples, int32_t n_prn_total, int32_t n_blocks, int32_t noncoh, double* carrFreq,
-                                   double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && r && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_CHECK_ARG(world >= 1 && rank >= 0 && rank < world && n_prn_total >= 1 && n_prn_total <= 32);
-    SGX_CHECK_ARG(!comm || (comm->n_ranks == world && comm->rank == rank && comm->ctx == c));
-    for (int i = 0; i < 32; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
-    }
-    // contiguous balanced partition (shard.plan_shards)
-    const int base = n_prn_total / world, extra = n_prn_total % world;
-    const int first = rank * base + (rank < extra ? rank : extra);
-    const int n_mine = base + (rank < extra ? 1 : 0);
-    const int slots = (n_prn_total + world - 1) / world;
-    int32_t prn0[32];
-    for (int i = 0; i < n_mine; ++i) prn0[i] = first + i;
-    SGX_HIP(hipSetDevice(c->device));
-    const size_t rec_bytes = sizeof(PeakRec) * (size_t)slots;
-    // where the packed records go: the communicator's send buffer, or (no communicator: one rank, or a shard run alone)
-    // the context's small device area
-    char* dsm = (char*)c->d_small;
-    PeakRec* d_send = comm ? (PeakRec*)comm->d_send : (PeakRec*)(dsm + 720000);
-    const PeakRec* d_all = comm ? (const PeakRec*)comm->d_recv : d_send;
-    const int n_ranks_seen = comm ? world : 1;
-    std::vector<PeakRec> host_pack;      // a search that could not be queued: packed on the host
-    bool queued = false;
-    if (n_mine > 0) {
-        const int rb = sgx_acquire_begin(c, r, offset, n_samples, prn0, n_mine, n_blocks, noncoh);
-        if (rb != SGX_OK) return rb;
-        queued = c->acq_pending.mode == 1;
-        if (!queued) {
-            double cf[32], cp[32], pm[32];
-            int fb[32], fi[32];
-            const int re = sgx_acquire_finish(c, cf, cp, pm, fb, fi);
-            if (re != SGX_OK && re != SGX_E_INDEX && re != SGX_E_RANGE) return re;
-            host_pack.resize((size_t)slots);
-            memset(host_pack.data(), 0, rec_bytes);
-            for (int i = 0; i < n_mine; ++i) {
-                PeakRec& q = host_pack[(size_t)i];
-                q.prn0 = prn0[i]; q.freqBin = fb[i]; q.carrFreq = cf[i]; q.codePhase = cp[i]; q.peakMetric = pm[i];
-                q.fineIdx = fi[i]; q.valid = 1;
-            }
-            if (re != SGX_OK) host_pack[0].valid = re == SGX_E_INDEX ? -1 : -2;   // (every rank learns of it)
+// ================================ environment and plans ================================
+// The environment an acquisition call reads, once at its entry: diagnosis switches, and the cross-references of
+// test_acquire_variants_agree.  Each of the older paths is also the only one for some input.
+struct AcqEnv {
+    bool v1;              // SGX_ACQ_V1=1: the round-1 passes (else: lengths the four-step transform does not take)
+    bool one_queue;       // SGX_ACQ_STREAMS=1: the correlation batches on one queue (else: where the plan says so)
+    bool top2_off;        // SGX_ACQ_TOP2=0: the round-4 second-peak search (else: sampling rates above 111 MHz)
+    bool front_off;       // SGX_ACQ_FRONT=0: the four-launch front (else: fp64 signals)
+    bool fine_v1;         // SGX_ACQ_FINE_V1=1: the fine search on the pass-per-launch transform
+    bool device_led_off;  // SGX_ACQ_DEVICE_LED=0: the host looks between the coarse and the fine search
+    bool split_event;     // SGX_ACQ_SPLIT_EVENT=1: an event between them, so that the split is measured
+    bool spin;            // SGX_ACQ_SPIN=0 clears it: the look goes straight to the stream synchronisation
+    int chunk_rows;       // SGX_ACQ_CHUNK_ROWS: correlation rows per chunk
+};
+static AcqEnv acq_env() {
+    auto is = [](const char* name, char v) {
+        const char* e = getenv(name);
+        return e && e[0] == v;
+    };
+    AcqEnv e;
+    e.v1 = is("SGX_ACQ_V1", '1');
+    e.one_queue = is("SGX_ACQ_STREAMS", '1');
+    e.top2_off = is("SGX_ACQ_TOP2", '0');
+    e.front_off = is("SGX_ACQ_FRONT", '0');
+    e.fine_v1 = is("SGX_ACQ_FINE_V1", '1');
+    e.device_led_off = is("SGX_ACQ_DEVICE_LED", '0');
+    e.split_event = is("SGX_ACQ_SPLIT_EVENT", '1');
+    e.spin = !is("SGX_ACQ_SPIN", '0');
+    e.chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
+    const char* ce = getenv("SGX_ACQ_CHUNK_ROWS");
+    if (ce && atoi(ce) > 0) e.chunk_rows = atoi(ce);
+    return e;
+}
+
+// How the correlation batch of a call is cut (round 5).  Rows are ordered (PRN, block, bin) - coherent - or (PRN, bin, block)
+// - non-coherent sums; a chunk is whole PRNs (prn_chunk of them) or, for non-coherent sums whose PRN does not fit half a
+// chunk, ONE PRN's rows of a run of Doppler bins (bin_runs runs per PRN: a run is a batch of its own with fewer bins).
+// The chunks alternate between `queues` HIP streams, each with its own intermediate of chunk_rows / queues rows: the columns
+// kernel is bound by its stores and the rows kernel by its loads, and with two chunks in flight the one's stores overlap
+// the other's loads (0.85 -> 0.77 ms for config 2, 3.21 -> 2.89 ms for config 4; both kernels move their bytes at 3-5 TB/s
+// over the same fabric - the intermediate lives in the Infinity Cache - so a producer / consumer fusion has no more to win).
+struct AcqPlan {
+    int prn_chunk, bin_runs, bins_per_run, queues;
+};
+static AcqPlan acq_plan(int n_prn, int n_bins, int n_blocks, bool noncoh, int chunk_rows, int max_queues) {
+    if (chunk_rows > ACQ_MAX_ROWS) chunk_rows = ACQ_MAX_ROWS;
+    if (chunk_rows < 1) chunk_rows = 1;
+    const int rows_per_prn = n_bins * n_blocks;
+    AcqPlan p;
+    p.bin_runs = 1;
+    p.queues = (max_queues >= 2 && n_prn >= 2 && chunk_rows / 2 >= rows_per_prn) ? 2 : 1;
+    if (max_queues >= 2 && p.queues == 1 && noncoh && rows_per_prn > chunk_rows / 2 && rows_per_prn <= chunk_rows && n_bins >= 2) {
+        int runs = (rows_per_prn + chunk_rows / 2 - 1) / (chunk_rows / 2);
+        if (runs > n_bins) runs = n_bins;
+        if (runs >= 2) {
+            p.bin_runs = runs;
+            p.queues = 2;
         }
     }
-    hipStream_t st = c->stream;
-    if (queued) {
-        const AcqPending& P = c->acq_pending;
-        acq_pack_kernel<<<1, 64, 0, st>>>((const CoarseLook*)(dsm + 700000), ((const CoarseLook*)c->d_look)->fine_bi,
-                                          (const int*)(dsm + 64), P.n_prn, c->s.samplingFreq, (double)P.npts, d_send, slots);
-    } else {
-        if (host_pack.empty()) {
-            host_pack.resize((size_t)slots);
-            memset(host_pack.data(), 0, rec_bytes);
-        }
-        SGX_HIP(hipMemcpyAsync(d_send, host_pack.data(), rec_bytes, hipMemcpyHostToDevice, st));
-    }
-    if (comm) {
-        const int rg = sgx_comm_allgather_device(comm, rec_bytes);
-        if (rg != SGX_OK) return rg;
-    }
-    const size_t all_bytes = rec_bytes * (size_t)n_ranks_seen;
-    if (all_bytes > SGX_TRK_LOOK_OFFSET - SGX_GATHER_LOOK_OFFSET - 16) {
-        sgx_set_error("sgx_acquire_sharded: %d ranks x %d slots do not fit the result page", world, slots);
-        return SGX_E_ARG;
-    }
-    const unsigned long long seq = ++c->look_seq;
-    char* page_d = (char*)c->d_look + SGX_GATHER_LOOK_OFFSET;
-    const char* page_h = (const char*)c->h_look + SGX_GATHER_LOOK_OFFSET;
-    acq_gather_publish_kernel<<<1, 256, 0, st>>>((const int*)d_all, (int)(all_bytes / 4), (int*)(page_d + 16),
-                                                 (unsigned long long*)page_d, seq);
-    SGX_HIP(hipGetLastError());
-    {   // the one look
-        const unsigned long long* word = (const unsigned long long*)page_h;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (unsigned it = 0; !seen; ++it) {
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) seen = true;
-            else if ((it & 1023u) == 1023u && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05) break;
-        }
-        if (!seen) {
-            SGX_HIP(hipStreamSynchronize(st));
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
-                sgx_set_error("sharded acquisition: the gathered peaks were not written");
-                return SGX_E_HIP;
-            }
-        }
-    }
-    if (queued) {   // (device time of this rank's search; the search's own page is complete: the gather came behind it)
-        c->acq_pending.mode = 0;
-        SGX_HIP(hipEventSynchronize(c->ev[2]));
-        hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
-        c->timing.acq_coarse_ms = __builtin_nanf("");
-        c->timing.acq_fine_ms = __builtin_nanf("");
-    }
-    const PeakRec* all = (const PeakRec*)(page_h + 16);
-    const int n_rec = slots * n_ranks_seen;
-    for (int i = 0; i < n_rec; ++i) {
-        const PeakRec& q = all[i];
-        if (q.valid == 0) continue;
-        if (q.valid == -1) {
-            sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
-                          "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
-                          (long long)c->n_code, (long long)c->n_code, q.prn0, (int)q.codePhase);
-            return SGX_E_INDEX;
-        }
-        if (q.valid == -2) {
-            sgx_set_error("fine search needs codePhase + 10 ms = %lld samples, record window has %zu "
-                          "(reference acquisition.py:177 would fail to broadcast)", (long long)q.codePhase + 10 * c->n_code, n_samples);
-            return SGX_E_RANGE;
-        }
-        if (q.prn0 < 0 || q.prn0 >= 32) continue;
-        carrFreq[q.prn0] = q.carrFreq;
-        codePhase[q.prn0] = q.codePhase;
-        peakMetric[q.prn0] = q.peakMetric;
-        freqBin[q.prn0] = q.freqBin;
-        fineIdx[q.prn0] = q.fineIdx;
-    }
+    if (p.queues == 2 && p.bin_runs == 1) chunk_rows /= 2;
+    p.prn_chunk = p.bin_runs > 1 ? 1 : chunk_rows / rows_per_prn;   // (a run of bins belongs to ONE PRN)
+    if (p.prn_chunk < 1) p.prn_chunk = 1;
+    if (p.prn_chunk > n_prn) p.prn_chunk = n_prn;
+    if (p.queues == 2 && p.bin_runs == 1 && p.prn_chunk > (n_prn + 1) / 2) p.prn_chunk = (n_prn + 1) / 2;   // (both queues get work)
+    p.bins_per_run = (n_bins + p.bin_runs - 1) / p.bin_runs;
+    return p;
+}
+extern "C" int sgx_acquire_plan(int32_t n_prn, int32_t n_bins, int32_t n_blocks, int32_t noncoh, int32_t chunk_rows,
+                                int32_t max_queues, int32_t* prn_chunk, int32_t* bin_runs, int32_t* bins_per_run,
+                                int32_t* queues) {
+    SGX_CHECK_ARG(n_prn >= 1 && n_bins >= 1 && n_blocks >= 1 && prn_chunk && bin_runs && bins_per_run && queues);
+    const AcqPlan p = acq_plan(n_prn, n_bins, n_blocks, noncoh != 0, chunk_rows > 0 ? chunk_rows : ACQ_DEFAULT_CHUNK_ROWS, max_queues);
+    *prn_chunk = p.prn_chunk;
+    *bin_runs = p.bin_runs;
+    *bins_per_run = p.bins_per_run;
+    *queues = p.queues;
     return SGX_OK;
 }
 
-// ================================ coherent multi-millisecond acquisition ================================
-// (include/sgx.h, sgx_acquire_coherent; tests/coherent_acq_spec.py is the contract in numpy.)  The search of the reference
-// (acquisition.py:62-166) with T-ms windows in place of its 1-ms blocks, on a finer Doppler grid.
-
+extern "C" int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows) {
+    SGX_CHECK_ARG(default_chunk_rows && max_rows);
+    *default_chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
+    *max_rows = ACQ_MAX_ROWS;
+    return SGX_OK;
+}
 // How the correlation batch is cut: whole PRNs while one PRN's rows fit a chunk (ACQ_DEFAULT_CHUNK_ROWS), else one PRN
 // per batch in runs - of bins for non-coherent sums (rows (bin, window): a run's output rows are whole bins), of windows
 // for the reference rule (rows (window, bin): a run's output rows are whole windows).
@@ -2189,6 +1042,33 @@ static void coh_plan(CohGrid* g, int n_prn) {
     }
     if (g->prn_chunk < 1) g->prn_chunk = 1;
     if (g->prn_chunk > n_prn) g->prn_chunk = n_prn;
+}
+
+// f N / fs = shift + phi (shift integer, 0 <= phi < 1) for every bin f0 + step k of a grid: the distinct fractions to
+// *phi, (phi index, circular shift) per bin to *bin_map.  Returns the number of distinct fractions; a path that shares
+// forward spectra takes the grid if they are few enough for it.
+static int acq_phi_split(double f0, double step, int n_bins, long long N, double fs, std::vector<double>* phi,
+                         std::vector<int2>* bin_map) {
+    phi->clear();
+    bin_map->assign((size_t)n_bins, make_int2(0, 0));
+    for (int k = 0; k < n_bins; ++k) {
+        const double f = f0 + step * k;
+        const double ratio = f * (double)N / fs;
+        const double sh = floor(ratio + 1e-9);
+        double ph = ratio - sh;
+        if (ph < 1e-9) ph = 0.0;
+        int j = -1;
+        for (size_t q = 0; q < phi->size() && j < 0; ++q)
+            if (fabs((*phi)[q] - ph) < 1e-9) j = (int)q;
+        if (j < 0) {
+            j = (int)phi->size();
+            phi->push_back(ph);
+        }
+        long long shm = (long long)sh % N;
+        if (shm < 0) shm += N;
+        (*bin_map)[(size_t)k] = make_int2(j, (int)shm);
+    }
+    return (int)phi->size();
 }
 
 // Parameters -> grid, phi decomposition, path and batches.  SGX_E_ARG (with the reason) for anything out of range.
@@ -2228,26 +1108,7 @@ static int coh_grid(const sgx_settings& S, long long N, const sgx_acq_params* p,
     g->step = step;
     g->f0 = S.IF - S.acqSearchBand / 2 * 1000;
     g->n_bins = (int)nb;
-    g->bin_map.assign((size_t)g->n_bins, make_int2(0, 0));
-    g->phi.clear();
-    for (int k = 0; k < g->n_bins; ++k) {
-        const double f = g->f0 + step * k;
-        const double ratio = f * (double)N / S.samplingFreq;   // f N ts = shift + phi (acquire_four_step's rule)
-        const double sh = floor(ratio + 1e-9);
-        double phi = ratio - sh;
-        if (phi < 1e-9) phi = 0.0;
-        int j = -1;
-        for (size_t q = 0; q < g->phi.size() && j < 0; ++q)
-            if (fabs(g->phi[q] - phi) < 1e-9) j = (int)q;
-        if (j < 0) {
-            j = (int)g->phi.size();
-            g->phi.push_back(phi);
-        }
-        long long shm = (long long)sh % N;
-        if (shm < 0) shm += N;
-        g->bin_map[(size_t)k] = make_int2(j, (int)shm);
-    }
-    g->n_phi = (int)g->phi.size();
+    g->n_phi = acq_phi_split(g->f0, step, g->n_bins, N, S.samplingFreq, &g->phi, &g->bin_map);
     g->path = (sgx_fft4_supported(N) && g->n_phi <= ACQ_COH_MAX_PHI) ? 1 : 0;
     if (g->path == 0 && (long long)M * g->n_bins > ACQ_MAX_ROWS) {
         sgx_set_error("bad argument: the direct path (%d distinct Doppler fractions, %lld samples per code) takes at most "
@@ -2258,13 +1119,24 @@ static int coh_grid(const sgx_settings& S, long long N, const sgx_acq_params* p,
     return SGX_OK;
 }
 
+// The fine search's lengths (acquisition.py:167-187): 10 ms of signal, the padded transform, its one-sided spectrum
+struct FineGeom {
+    long long len, npts, uniq;
+};
+static FineGeom acq_fine_geom(long long N) {
+    FineGeom f;
+    f.len = 10 * N;
+    f.npts = 8ll << (long long)ceil(log2((double)f.len));
+    f.uniq = (long long)ceil((double)(f.npts + 1) / 2.0);
+    return f;
+}
+
 // Detection d's fine-search range for T > 1: the spectrum indices i of the 2^k-point transform (frequency i fs / npts)
 // within one bin step of its coarse bin, inside the reference's [4, uniq - 5).
 static std::vector<long long> coh_fine_windows(const CohGrid& g, const sgx_settings& S, long long N,
                                                const std::vector<int>& det_bin) {
-    const long long len = 10 * N;
-    const long long npts = 8ll << (long long)ceil(log2((double)len));
-    const long long uniq = (long long)ceil((double)(npts + 1) / 2.0);
+    const FineGeom fg = acq_fine_geom(N);
+    const long long npts = fg.npts, uniq = fg.uniq;
     std::vector<long long> win;
     for (int k : det_bin) {
         const double fk = g.f0 + g.step * k;
@@ -2279,11 +1151,859 @@ static std::vector<long long> coh_fine_windows(const CohGrid& g, const sgx_setti
     return win;
 }
 
-// The shift path: folded rows per (window, phi), their forward spectra once, the correlation batches of acquire_four_step
-// (Fft4Fuse reads each bin's row with its circular shift), the same peak kernels, then one host look and the fine search.
-static int acquire_coherent_shift(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn,
-                                  const CohGrid& g, double* carrFreq, double* codePhase, double* peakMetric,
-                                  int32_t* freqBin, int32_t* fineIdx) {
+// ================================ stages ================================
+// One call as every stage and path sees it
+struct AcqCall {
+    sgx_ctx* c;
+    SgxSig x;
+    size_t n_samples;
+    const int32_t* prn0;
+    int n_prn;
+    double *carrFreq, *codePhase, *peakMetric;   // outputs, [n_prn]
+    int32_t *freqBin, *fineIdx;
+    AcqEnv env;
+};
+// The detections of a call (acquisition.py:164-166) in ascending position of its PRN list
+struct AcqDets {
+    std::vector<int> prn, phase, slot;
+};
+
+static int ensure_buf(void** p, size_t* cap_bytes, size_t need) {
+    if (*p && *cap_bytes >= need) return SGX_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    hipError_t e = hipMalloc(p, need);
+    if (e != hipSuccess) {
+        sgx_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+        *cap_bytes = 0;
+        return SGX_E_NOMEM;
+    }
+    *cap_bytes = need;
+    return SGX_OK;
+}
+
+static int acq_check_prns(const int32_t* prn0, int32_t n_prn) {
+    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32);
+    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
+    return SGX_OK;
+}
+
+// The record's window as the kernels read it, once it is resident
+static int acq_record_sig(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, SgxSig* x) {
+    const int rq = sgx_if_require(r, offset + n_samples);   // a record that is still streaming in
+    if (rq != SGX_OK) return rq;
+    SGX_HIP(hipSetDevice(c->device));
+    x->i8 = r->d + offset;
+    x->f64 = nullptr;
+    return SGX_OK;
+}
+
+// What sgx_acquire and sgx_acquire_begin check before they touch the device: PRN list, blocks, the record window
+static int acq_open_record(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                           int32_t n_blocks, SgxSig* x) {
+    SGX_CHECK_ARG(n_blocks >= 1 && n_blocks <= 64);
+    const int rc = acq_check_prns(prn0, n_prn);
+    if (rc != SGX_OK) return rc;
+    const long long N = c->n_code;
+    if (offset > r->n || n_samples > r->n - offset || (long long)n_samples < (long long)n_blocks * N) {
+        sgx_set_error("record window too short: %zu samples at offset %zu, %lld needed for the coarse search",
+                      n_samples, offset, (long long)n_blocks * N);
+        return SGX_E_RANGE;
+    }
+    return acq_record_sig(c, r, offset, n_samples, x);
+}
+
+// acquire() on a signal that is not int8 (acquisition.py:55-59 takes whatever real dtype numpy hands it): the caller's
+// fp64 samples are copied to HBM and every kernel reads them instead of the int8 record; the arithmetic is the same
+// fp64 arithmetic either way.
+static int acq_upload_f64(sgx_ctx* c, const double* signal, size_t n_samples, SgxSig* x) {
+    SGX_HIP(hipSetDevice(c->device));
+    const size_t need = sizeof(double) * (n_samples + 64);
+    if (c->cap_sig64 < need) {
+        if (c->d_sig64) hipFree(c->d_sig64);
+        c->d_sig64 = nullptr;
+        c->cap_sig64 = 0;
+        if (hipMalloc((void**)&c->d_sig64, need) != hipSuccess) {
+            sgx_set_error("hipMalloc of %zu signal bytes failed", need);
+            return SGX_E_NOMEM;
+        }
+        c->cap_sig64 = need;
+    }
+    SGX_HIP(hipMemcpyAsync(c->d_sig64, signal, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
+    SGX_HIP(hipStreamSynchronize(c->stream));   // the caller may free `signal` on return
+    x->i8 = nullptr;
+    x->f64 = c->d_sig64;
+    return SGX_OK;
+}
+
+static void acq_reset_outputs(double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx,
+                              int n) {
+    for (int i = 0; i < n; ++i) {
+        carrFreq[i] = 0.0;
+        codePhase[i] = 0.0;
+        peakMetric[i] = 0.0;
+        freqBin[i] = -1;
+        fineIdx[i] = -1;
+    }
+}
+static void acq_reset_outputs(const AcqCall& a) {
+    acq_reset_outputs(a.carrFreq, a.codePhase, a.peakMetric, a.freqBin, a.fineIdx, a.n_prn);
+}
+
+// Device times of a call from its events ev[0] (start), ev[1] (between coarse and fine search), ev[2] (end).  An event
+// between the coarse and the fine kernels holds the fine search back by 6-8 us, so the device-led sequence records it on
+// request only (SGX_ACQ_SPLIT_EVENT=1); without it the split is NOT measured: NaN, not total / 0
+static void acq_event_times(sgx_ctx* c, bool split_measured) {
+    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
+    if (split_measured) {
+        hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
+        hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
+    } else {
+        c->timing.acq_coarse_ms = __builtin_nanf("");
+        c->timing.acq_fine_ms = __builtin_nanf("");
+    }
+}
+
+// The reference's IndexError (Q5; acquisition.py:152-162) and its failure to broadcast (acquisition.py:177) as errors
+static int acq_index_error(long long N, int prn, int code_phase) {
+    sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
+                  "(PRN index %d, codePhase %d; reference acquisition.py:152-162)", N, N, prn, code_phase);
+    return SGX_E_INDEX;
+}
+static int acq_fine_range_error(long long end, size_t n_samples) {
+    sgx_set_error("fine search needs codePhase + 10 ms = %lld samples, record window has %zu "
+                  "(reference acquisition.py:177 would fail to broadcast)", end, n_samples);
+    return SGX_E_RANGE;
+}
+
+// The first of PRNs [first, first + n) of the call at which the reference raises (po: entry i = PRN first + i)
+static int acq_look_index_error(const AcqCall& a, const PeakOut& po, int first, int n) {
+    for (int i = 0; i < n; ++i)
+        if (po.index_error[i]) return acq_index_error(a.c->n_code, a.prn0[first + i], po.cph[i]);
+    return SGX_OK;
+}
+
+// The look decoded: peaks and second peaks of PRNs [first, first + n) -> peakMetric, freqBin and the detections
+// (acquisition.py:164-166), or the reference's IndexError
+static int acq_look_decode(const AcqCall& a, const PeakOut& po, const double* second, int first, int n, AcqDets* det) {
+    const int rc = acq_look_index_error(a, po, first, n);
+    if (rc != SGX_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        const int o = first + i;
+        const double ratio = po.peak[i] / second[i];
+        a.peakMetric[o] = ratio;
+        a.freqBin[o] = po.fbi[i];
+        if (ratio > a.c->s.acqThreshold) {
+            det->prn.push_back(a.prn0[o]);
+            det->phase.push_back(po.cph[i]);
+            det->slot.push_back(o);
+        }
+    }
+    return SGX_OK;
+}
+
+// Waits for a result word in the pinned page (acq_publish_kernel's `seq`, the fine search's `seq2`, the gathered peaks'
+// word).  Spins (bounded), then falls back to the stream synchronisation, after which the page is complete in any case.
+static int coarse_look_wait(sgx_ctx* c, const unsigned long long* word, unsigned long long seq, bool spin) {
+    if (spin) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned it = 0;; ++it) {
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGX_OK;
+            if ((it & 1023u) == 1023u &&
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
+                break;
+        }
+    }
+    SGX_HIP(hipStreamSynchronize(c->stream));
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
+        sgx_set_error("acquisition: the search's result page was not written");
+        return SGX_E_HIP;
+    }
+    return SGX_OK;
+}
+
+// The second queue of the correlation batches and its two events, created on first use
+static int acq_second_queue(sgx_ctx* c, hipStream_t* st2) {
+    if (!c->acq_stream2) {
+        // (into locals; the context gets them only when ALL exist - a half-made second queue would fail every later call)
+        int least = 0, greatest = 0;
+        SGX_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        hipStream_t ns = nullptr;
+        hipEvent_t ne[2] = {nullptr, nullptr};
+        hipError_t ce = (c->priority == 0) ? hipStreamCreateWithFlags(&ns, hipStreamNonBlocking)
+                                           : hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, c->priority < 0 ? greatest : least);
+        for (int i = 0; i < 2 && ce == hipSuccess; ++i) ce = hipEventCreateWithFlags(&ne[i], hipEventDisableTiming);
+        if (ce != hipSuccess) {
+            for (int i = 0; i < 2; ++i)
+                if (ne[i]) hipEventDestroy(ne[i]);
+            if (ns) hipStreamDestroy(ns);
+            sgx_set_error("acquisition: the second queue could not be created: %s", hipGetErrorString(ce));
+            return SGX_E_HIP;
+        }
+        c->acq_stream2 = ns;
+        c->acq_ev2[0] = ne[0];
+        c->acq_ev2[1] = ne[1];
+    }
+    *st2 = c->acq_stream2;
+    return SGX_OK;
+}
+
+// The correlation of the paths that read shifted forward spectra (four-step, coherent shift): its geometry, and where in
+// the reduction buffer (c->d_pow) its kernels leave their results
+struct AcqCorr {
+    int n_bins, n_phi, n_blocks, noncoh;   // (blocks: 1-ms blocks, or the coherent search's windows)
+    int out_per_prn, rows_out_all;
+    bool top2;                             // peak and second peak from one pass (acq_rowtop2_peak_kernel)
+    int nblk, nres;
+    const cplx* d_codefd;                  // code spectra, behind the forward spectra in c->d_fwd
+    // [per-workgroup maxima | their indices] or [per-residue maxima | second maxima | indices], [row maxima | row indices],
+    // then (non-coherent, round-4 sequence) the second-peak power rows
+    double* pmax;
+    int* parg;
+    double *t2b1, *t2b2;
+    int* t2i1;
+    double* rowmax;
+    int* rowarg;
+    double* power;
+};
+static int acq_corr_carve(sgx_ctx* c, AcqCorr* k, size_t pow_need) {
+    const size_t rows = (size_t)k->rows_out_all;
+    const size_t part_bytes = ((rows * (k->top2 ? (size_t)k->nres * 20 : (size_t)k->nblk * 12)) + 255) / 256 * 256;
+    const size_t red_bytes = (part_bytes + rows * 12 + 1023) / 256 * 256;
+    const int rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, red_bytes + pow_need);
+    if (rc != SGX_OK) return rc;
+    char* red = (char*)c->d_pow;
+    k->pmax = (double*)red;
+    k->parg = (int*)(red + rows * k->nblk * 8);
+    k->t2b1 = (double*)red;
+    k->t2b2 = k->t2b1 + rows * k->nres;
+    k->t2i1 = (int*)(k->t2b2 + rows * k->nres);
+    k->rowmax = (double*)(red + part_bytes);
+    k->rowarg = (int*)(red + part_bytes + rows * 8);
+    k->power = (double*)(red + red_bytes);
+    return SGX_OK;
+}
+
+// One correlation batch: PRNs [p0, p0 + np) x bins [bin0, bin0 + nb) x blocks [blk0, blk0 + nblocks) -> its Fft4Fuse (a
+// run of bins is a batch of its own with fewer bins; a run of blocks reads its blocks' forward rows) and the transform,
+// through intermediate `work` on queue `st`.  Rows are ordered (PRN, block, bin), or (PRN, bin, block) for non-coherent
+// sums, which take all blocks of a bin in one batch.
+static int acq_corr_batch(sgx_ctx* c, const AcqCorr& k, int p0, int np, int bin0, int nb, int blk0, int nblocks, cplx* work,
+                          hipStream_t st) {
+    Fft4Fuse fu;
+    fu.mul_x = c->d_fwd + (size_t)blk0 * k.n_phi * (size_t)c->n_code;
+    fu.mul_f = k.d_codefd;
+    fu.bin_map = c->d_small->bin_map + bin0;
+    fu.n_bins = nb;
+    fu.n_phi = k.n_phi;
+    fu.rows_per_prn = nb * nblocks;
+    fu.prn_base = p0;
+    fu.n_blocks = nblocks;
+    fu.blocks_fast = k.noncoh ? 1 : 0;
+    const size_t out0 = (size_t)p0 * k.out_per_prn + (k.noncoh ? (size_t)bin0 : (size_t)blk0 * k.n_bins + (size_t)bin0);
+    if (k.top2) {
+        fu.t2_b1 = k.t2b1 + out0 * k.nres;
+        fu.t2_b2 = k.t2b2 + out0 * k.nres;
+        fu.t2_i1 = k.t2i1 + out0 * k.nres;
+    } else {
+        fu.pmax = k.pmax + out0 * k.nblk;
+        fu.parg = k.parg + out0 * k.nblk;
+    }
+    fu.inv_n = 1.0 / (double)c->n_code;
+    fu.sum_blocks = k.noncoh ? nblocks : 1;
+    return sgx_fft4_forward(&c->plan_code, nullptr, work, nullptr, (int64_t)np * fu.rows_per_prn, st, &fu);
+}
+
+// Row maxima, block choice, global peak, exclusion list and second peak of every PRN in one launch; with a stage in
+// `pub` the detections too, else a publish kernel follows
+static void acq_queue_top2(const AcqCall& a, const AcqCorr& k, int spc, const PublishArgs& pub) {
+    SgxSmall* dsm = a.c->d_small;
+    acq_rowtop2_peak_kernel<<<k.rows_out_all, 64, 0, a.c->stream>>>(k.t2b1, k.t2b2, k.t2i1, k.nres, k.rowmax, k.rowarg,
+                                                                    dsm->arrived, a.n_prn, k.out_per_prn, k.n_bins, k.n_blocks,
+                                                                    k.noncoh, a.c->n_code, spc, &dsm->peak_out, dsm->second, pub);
+}
+// The coarse search's outcome to `page` (the pinned one; or, device-led with `det`, its device-side copy)
+static void acq_queue_publish(const AcqCall& a, CoarseLook* page, unsigned long long seq, long long fine_len, AcqDet* det) {
+    SgxSmall* dsm = a.c->d_small;
+    acq_publish_kernel<<<1, 64, 0, a.c->stream>>>(&dsm->peak_out, dsm->second, a.n_prn, page, seq, dsm->prn, a.c->s.acqThreshold,
+                                                  fine_len, (long long)a.n_samples, reinterpret_cast<int*>(det));
+}
+
+// Fine frequency search (acquisition.py:167-193) for the detected PRNs; records event ev[2] and synchronises.
+// win (coherent search, else null): [2 d], [2 d + 1] = detection d's own arg-max range in place of [4, uniq - 5)
+static int acquire_fine(const AcqCall& a, const AcqDets& det, long long* d_sum, const std::vector<long long>* win) {
+    sgx_ctx* c = a.c;
+    const SgxSig x = a.x;
+    const size_t n_samples = a.n_samples;
+    hipStream_t st = c->stream;
+    const sgx_settings& S = c->s;
+    const double ts = 1.0 / S.samplingFreq;
+    SgxSmall* dsm = c->d_small;
+    SgxSmall* hsm = c->h_small;
+    int rc = SGX_OK;
+    const int n_det = (int)det.prn.size();
+    if (n_det == 0) {
+        hipEventRecord(c->ev[2], st);
+        SGX_HIP(hipStreamSynchronize(st));
+        return SGX_OK;
+    }
+    const FineGeom fg = acq_fine_geom(c->n_code);
+    const long long len = fg.len, npts = fg.npts, uniq = fg.uniq;
+    for (int d = 0; d < n_det; ++d)
+        if ((long long)det.phase[d] + len > (long long)n_samples) return acq_fine_range_error((long long)det.phase[d] + len, n_samples);
+    rc = sgx_fft_plan_create(&c->plan_fine, npts);
+    if (rc != SGX_OK) return rc;
+    const int n_rows = (n_det + 1) / 2;   // two real signals per complex row
+    if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
+        return rc;
+    if ((rc = ensure_buf((void**)&c->d_fine[1], &c->cap_f1, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
+        return rc;
+    const double tc1 = 1.0 / S.codeFreqBasis;
+    const bool fine2 = sgx_fft_fine_supported(npts) && !a.env.fine_v1;
+    double mean = 0.0;
+    if (!fine2) {
+        long long h_sum = 0;
+        SGX_HIP(hipMemcpyAsync(&h_sum, d_sum, 8, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipStreamSynchronize(st));
+        double h_sumd;
+        memcpy(&h_sumd, &h_sum, 8);
+        mean = (x.f64 ? h_sumd : (double)h_sum) / (double)n_samples;   // longSignal.mean(), acquisition.py:59
+    }
+    int nblk = 256;
+    // per-detection ranges (coherent search): to device memory, and their union as the common range
+    long long* d_win = nullptr;
+    long long win_lo = 4, win_hi = uniq - 5;
+    if (win) {
+        d_win = dsm->fine_win;
+        memcpy(hsm->fine_win, win->data(), sizeof(long long) * 2 * (size_t)n_det);
+        SGX_HIP(hipMemcpyAsync(d_win, hsm->fine_win, sizeof(long long) * 2 * (size_t)n_det, hipMemcpyHostToDevice, st));
+        win_lo = (*win)[0];
+        win_hi = (*win)[1];
+        for (int d = 1; d < n_det; ++d) {
+            win_lo = (*win)[2 * (size_t)d] < win_lo ? (*win)[2 * (size_t)d] : win_lo;
+            win_hi = (*win)[2 * (size_t)d + 1] > win_hi ? (*win)[2 * (size_t)d + 1] : win_hi;
+        }
+    }
+    if (fine2) {
+        // two kernels with LDS-resident sub-transforms, input built on the fly (the mean comes from the device-side
+        // sum: no host look), arg-max fused (sgx_fft.hip)
+        nblk = sgx_fft_fine_partials();
+        rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, det.prn.data(), det.phase.data(), n_det, len, d_sum,
+                                 (double)n_samples, ts, tc1, c->d_fine[0], win_lo, win_hi, dsm->fine_pv, dsm->fine_pi, st,
+                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, d_win);
+        if (rc != SGX_OK) return rc;
+    } else {
+        SGX_HIP(hipMemcpyAsync(dsm->det_prn, det.prn.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemcpyAsync(dsm->det_phase, det.phase.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
+        dim3 grid((unsigned)((len + 255) / 256), (unsigned)n_rows);
+        acq_fine_prep_kernel<<<grid, 256, 0, st>>>(x, c->d_codes, c->d_fine[0], len, npts, mean, ts, tc1, dsm->det_prn,
+                                                   dsm->det_phase, n_det);
+        cplx* res = nullptr;
+        rc = sgx_fft_forward(&c->plan_fine, c->d_fine[0], c->d_fine[1], n_rows, st, &res, len);
+        if (rc != SGX_OK) return rc;
+        dim3 g2((unsigned)nblk, (unsigned)n_det);
+        acq_fine_argmax_kernel<<<g2, 256, 0, st>>>(res, npts, 4, uniq - 5, dsm->fine_pv, dsm->fine_pi, d_win);
+    }
+    const double* h_pv = hsm->fine_pv;
+    const long long* h_pi = hsm->fine_pi;
+    SGX_HIP(hipMemcpyAsync(hsm->fine_pv, dsm->fine_pv, sizeof(double) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
+    SGX_HIP(hipMemcpyAsync(hsm->fine_pi, dsm->fine_pi, sizeof(long long) * (size_t)n_det * nblk, hipMemcpyDeviceToHost, st));
+    hipEventRecord(c->ev[2], st);
+    SGX_HIP(hipStreamSynchronize(st));
+    for (int d = 0; d < n_det; ++d) {
+        double bv = -1.0;
+        long long bi = 0;
+        for (int b = 0; b < nblk; ++b) {
+            const double v = h_pv[d * nblk + b];
+            const long long i = h_pi[d * nblk + b];
+            if (v > bv || (v == bv && i < bi)) {
+                bv = v;
+                bi = i;
+            }
+        }
+        const long long m = bi - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
+        const int o = det.slot[d];
+        a.carrFreq[o] = ((double)m * S.samplingFreq) / (double)npts;   // acquisition.py:189-191 (Q3)
+        a.codePhase[o] = (double)det.phase[d];
+        a.fineIdx[o] = (int)m;
+    }
+    return SGX_OK;
+}
+
+// The tail of a host-led call: the detections' fine search (for a coherent grid with T > 1: inside one bin step of each
+// detection's coarse bin) and the device times
+static int acq_fine_and_times(const AcqCall& a, const AcqDets& det, long long* d_sum, const CohGrid* g) {
+    std::vector<long long> win;
+    if (g && g->T > 1) {
+        std::vector<int> det_bin;
+        for (int o : det.slot) det_bin.push_back(a.freqBin[o]);
+        win = coh_fine_windows(*g, a.c->s, a.c->n_code, det_bin);
+    }
+    const int rc = acquire_fine(a, det, d_sum, win.empty() ? nullptr : &win);
+    if (rc != SGX_OK) return rc;
+    acq_event_times(a.c, true);
+    return SGX_OK;
+}
+
+// ================================ the three paths ================================
+// The round-1 path: one launch per radix pass, every Doppler bin mixed separately (any factorable samplesPerCode).
+// g (coherent search, direct path; else null): n_blocks = the windows, each folded from g->T blocks per Doppler bin of g's
+// grid (acq_fold_direct_kernel) in place of the 1-ms mix
+static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohGrid* g = nullptr) {
+    sgx_ctx* c = a.c;
+    const SgxSig x = a.x;
+    const int n_prn = a.n_prn;
+    const long long N = c->n_code;
+    const sgx_settings& S = c->s;
+    hipStream_t st = c->stream;
+
+    // A4 frequency grid (acquisition.py:68,99-101)
+    const int n_bins = g ? g->n_bins : (int)(nearbyint(S.acqSearchBand * 2) + 1);
+    SGX_CHECK_ARG(n_bins >= 1 && n_bins <= (g ? ACQ_COH_MAX_BINS : ACQ_MAX_BINS));
+    MixArgs ma;
+    ma.n_bins = n_bins;
+    ma.n_blocks = n_blocks;
+    for (int k = 0; k < n_bins && !g; ++k) ma.frq[k] = S.IF - S.acqSearchBand / 2 * 1000 + 500.0 * k;
+    const double ts = 1.0 / S.samplingFreq;
+    const double tc = 1.0 / S.codeFreqBasis;
+    const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
+
+    int rc = sgx_fft_plan_create(&c->plan_code, N);
+    if (rc != SGX_OK) return rc;
+
+    // ---- scratch ------------------------------------------------------------------------------
+    const int rows_fwd = n_blocks * n_bins;
+    const int rows_per_prn = rows_fwd;
+    SGX_CHECK_ARG(rows_per_prn <= ACQ_MAX_ROWS);
+    int prn_chunk = ACQ_MAX_ROWS / rows_per_prn;
+    if (prn_chunk < 1) prn_chunk = 1;
+    if (prn_chunk > n_prn) prn_chunk = n_prn;
+    const size_t row_bytes = sizeof(cplx) * (size_t)N;
+    size_t work_rows = (size_t)prn_chunk * rows_per_prn;
+    if (work_rows < (size_t)rows_fwd) work_rows = rows_fwd;
+    if (work_rows < (size_t)n_prn) work_rows = n_prn;
+    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_codefd, &c->cap_code, (size_t)n_prn * row_bytes)) != SGX_OK) return rc;
+    const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : (size_t)ACQ_MAX_ROWS * 64 * 12 + 4096;
+    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, pow_need)) != SGX_OK) return rc;
+
+    SgxSmall* dsm = c->d_small;
+    SgxSmall* hsm = c->h_small;
+    const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
+    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer
+    double* d_pmax = c->d_pow;
+    int* d_parg = (int*)(c->d_pow + (size_t)ACQ_MAX_ROWS * 64);
+    SGX_CHECK_ARG(nblk_last <= 64);
+    hipEventRecord(c->ev[0], st);
+    SGX_HIP(hipMemsetAsync(&dsm->sum, 0, 8, st));
+    SGX_HIP(hipMemcpyAsync(dsm->prn, a.prn0, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
+    if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)a.n_samples, &dsm->sum);
+    else acq_sum_kernel<<<256, 256, 0, st>>>(x.i8, (long long)a.n_samples, &dsm->sum);
+
+    // ---- PRN-independent part: mix + forward FFTs ------------------------------------------------
+    {
+        dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows_fwd);
+        if (g) {
+            for (int k = 0; k < n_bins; ++k) hsm->frq[k] = g->f0 + g->step * k;
+            SGX_HIP(hipMemcpyAsync(dsm->frq, hsm->frq, sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, st));
+            acq_fold_direct_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, dsm->frq, n_bins, g->T);
+        } else {
+            acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, ma);
+        }
+        cplx* res = nullptr;
+        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows_fwd, st, &res, N);
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipMemcpyAsync(c->d_fwd, res, (size_t)rows_fwd * row_bytes, hipMemcpyDeviceToDevice, st));
+    }
+    // ---- code spectra ---------------------------------------------------------------------------
+    {
+        dim3 grid((unsigned)((N + 255) / 256), (unsigned)n_prn);
+        acq_code_kernel<<<grid, 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[0], N, ts, tc);
+        cplx* res = nullptr;
+        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], n_prn, st, &res, N);
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipMemcpyAsync(c->d_codefd, res, (size_t)n_prn * row_bytes, hipMemcpyDeviceToDevice, st));
+    }
+
+    // ---- correlation + peak search, PRN chunk by chunk ---------------------------------------------
+    AcqDets det;
+    int status = SGX_OK;
+    acq_reset_outputs(a);
+    const double inv_n = 1.0 / (double)N;
+    const int out_per_prn = noncoh ? n_bins : rows_per_prn;
+    for (int p0 = 0; p0 < n_prn && status == SGX_OK; p0 += prn_chunk) {
+        const int np = (p0 + prn_chunk <= n_prn) ? prn_chunk : (n_prn - p0);
+        const int rows = np * rows_per_prn;
+        const int rows_out = np * out_per_prn;
+        cplx* res = nullptr;
+        if (noncoh) {
+            // extension path: the blocks' powers are summed per sample, so rows are materialised
+            dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows);
+            acq_mul_kernel<<<grid, 256, 0, st>>>(c->d_fwd, c->d_codefd, c->d_work[0], N, rows_per_prn, p0);
+            rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N);
+            if (rc != SGX_OK) return rc;
+            acq_power_kernel<<<rows_out, 256, 0, st>>>(res, c->d_pow, dsm->rowmax, dsm->rowarg, N, inv_n, n_bins, n_blocks, 1);
+        } else {
+            // reference path, fused: conj(X)*F formed in the first radix pass, |.|^2 and the per-workgroup
+            // maxima taken in the last one; no product rows, no power rows
+            FftFuse fu;
+            fu.mul_x = c->d_fwd;
+            fu.mul_f = c->d_codefd;
+            fu.rows_per_prn = rows_per_prn;
+            fu.prn_base = p0;
+            fu.pmax = d_pmax;
+            fu.parg = d_parg;
+            fu.inv_n = inv_n;
+            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N, &fu);
+            if (rc != SGX_OK) return rc;
+            acq_rowmax_finish_kernel<<<rows, 64, 0, st>>>(d_pmax, d_parg, nblk_last, dsm->rowmax, dsm->rowarg);
+        }
+        SGX_HIP(hipMemcpyAsync(hsm->rowmax, dsm->rowmax, sizeof(double) * (size_t)rows_out, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipMemcpyAsync(hsm->rowarg, dsm->rowarg, sizeof(int) * (size_t)rows_out, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipStreamSynchronize(st));
+
+        // host: block choice (A7), global peak (A8), exclusion list (A8b) - the device's peak logic, bin by bin
+        SecondArgs sa;
+        PeakOut po;
+        for (int pi = 0; pi < 32; ++pi) sa.row[pi] = -1, sa.lo0[pi] = sa.hi0[pi] = sa.lo1[pi] = sa.hi1[pi] = 0;
+        memset(&po, 0, sizeof(po));
+        for (int pi = 0; pi < np; ++pi) {
+            AcqCand cand = {-1.0, -1, 0, 0};
+            for (int k = 0; k < n_bins; ++k)
+                cand = acq_peak_join(cand, acq_peak_bin(hsm->rowmax + pi * out_per_prn, hsm->rowarg + pi * out_per_prn, n_bins,
+                                                        n_blocks, noncoh != 0, k));
+            po.peak[pi] = cand.v;
+            po.cph[pi] = cand.a;
+            po.fbi[pi] = cand.k;
+            po.index_error[pi] = acq_peak_ranges(cand.a, N, spc, &sa.lo0[pi], &sa.hi0[pi], &sa.lo1[pi], &sa.hi1[pi]);
+            if (po.index_error[pi]) break;
+            sa.row[pi] = pi * out_per_prn + (noncoh ? cand.k : cand.b * n_bins + cand.k);
+        }
+        status = acq_look_index_error(a, po, p0, np);
+        if (status != SGX_OK) break;
+        if (noncoh) {
+            SGX_HIP(hipMemcpyAsync(&dsm->second_args, &sa, sizeof(sa), hipMemcpyHostToDevice, st));
+            SGX_HIP(hipMemsetAsync(dsm->second, 0, sizeof(double) * 32, st));
+            acq_second_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(c->d_pow, dsm->second, N, &dsm->second_args);
+        } else {
+            // recompute only the np rows the second-peak search reads (one per PRN)
+            for (int pi = 0; pi < np; ++pi) {
+                hsm->row_map[pi] = make_int2(sa.row[pi] % rows_per_prn, p0 + pi);   // row = (pi*blocks + b)*bins + k
+                sa.row[pi] = pi;
+            }
+            SGX_HIP(hipMemcpyAsync(dsm->row_map, hsm->row_map, sizeof(int2) * (size_t)np, hipMemcpyHostToDevice, st));
+            FftFuse fu;
+            fu.mul_x = c->d_fwd;
+            fu.mul_f = c->d_codefd;
+            fu.row_map = dsm->row_map;
+            cplx* r2 = nullptr;
+            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], np, st, &r2, N, &fu);
+            if (rc != SGX_OK) return rc;
+            SGX_HIP(hipMemcpyAsync(&dsm->second_args, &sa, sizeof(sa), hipMemcpyHostToDevice, st));
+            SGX_HIP(hipMemsetAsync(dsm->second, 0, sizeof(double) * 32, st));
+            acq_second_cplx_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(r2, dsm->second, N, inv_n, &dsm->second_args);
+        }
+        SGX_HIP(hipMemcpyAsync(hsm->second, dsm->second, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipStreamSynchronize(st));
+        status = acq_look_decode(a, po, hsm->second, p0, np, &det);
+    }
+    hipEventRecord(c->ev[1], st);
+    if (status != SGX_OK) {
+        hipStreamSynchronize(st);
+        return status;
+    }
+    // ---- fine frequency search (acquisition.py:167-193) -----------------------------------------------
+    return acq_fine_and_times(a, det, &dsm->sum, g);
+}
+
+// The acquisition on the four-step transform (sgx_fft.hip): every 38192-point transform is two kernels with register-resident
+// sub-transforms, the mixed-signal spectra are computed once per (block, phi) and read with a circular shift, results
+// land where they are needed (no device-to-device copies) and the host looks at the device ONCE, at the very end of the
+// call (round 4: peaks, second peaks, the detections and their fine-search results arrive in one pinned page), whatever the
+// number of PRN chunks.
+static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* handled, bool defer = false) {
+    *handled = false;
+    sgx_ctx* c = a.c;
+    const SgxSig x = a.x;
+    const int n_prn = a.n_prn;
+    const size_t n_samples = a.n_samples;
+    const long long N = c->n_code;
+    const sgx_settings& S = c->s;
+    if (a.env.v1 || !sgx_fft4_supported(N)) return SGX_OK;
+    const int n_bins = (int)(nearbyint(S.acqSearchBand * 2) + 1);
+    if (n_bins < 1 || n_bins > ACQ_MAX_BINS) return SGX_OK;
+    // f N / fs = shift + phi for every bin of the A4 grid (acquisition.py:68,99-101); the path needs few distinct phi
+    // (more than PhiArgs holds: the direct path mixes every bin)
+    std::vector<double> phi;
+    std::vector<int2> bin_map;
+    const int n_phi = acq_phi_split(S.IF - S.acqSearchBand / 2 * 1000, 500.0, n_bins, N, S.samplingFreq, &phi, &bin_map);
+    if (n_phi > 4 || (n_phi >= n_bins && n_bins > 1)) return SGX_OK;
+    *handled = true;
+    PhiArgs pa;
+    pa.n_phi = n_phi;
+    for (int j = 0; j < n_phi; ++j) pa.phi[j] = phi[(size_t)j];
+
+    hipStream_t st = c->stream;
+    const double ts = 1.0 / S.samplingFreq;
+    const double tc = 1.0 / S.codeFreqBasis;
+    const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
+    int rc = sgx_fft_plan_create(&c->plan_code, N);
+    if (rc != SGX_OK) return rc;
+
+    // ---- scratch ------------------------------------------------------------------------------
+    const int rows_fwd = n_blocks * n_phi;
+    const int rows_per_prn = n_blocks * n_bins;
+    SGX_CHECK_ARG(rows_per_prn <= ACQ_MAX_ROWS);
+    // PRN chunks of ~350 rows: a chunk's intermediate (213 MB) then stays in the 256 MiB Infinity Cache between the
+    // columns kernel that writes it and the rows kernel that reads it, and the next chunk overwrites it there.  With the
+    // round-3 kernels - bound by their stores and by the dirty lines on their way out, not by instruction issue or LDS
+    // any more - that is 0.94 -> 0.80 ms for config 2 and 3.43 -> 3.24 ms for config 4 (tools/acq_chunk_probe.py; the
+    // round-2 kernels measured no difference).
+    const AcqPlan plan = acq_plan(n_prn, n_bins, n_blocks, noncoh != 0, a.env.chunk_rows, a.env.one_queue ? 1 : 2);
+    const bool two_q = plan.queues == 2;
+    const int bin_runs = plan.bin_runs, prn_chunk = plan.prn_chunk;
+    const size_t row_bytes = sizeof(cplx) * (size_t)N;
+    size_t work_rows = (size_t)prn_chunk * rows_per_prn;
+    if (work_rows < (size_t)(rows_fwd + n_prn)) work_rows = (size_t)(rows_fwd + n_prn);
+    if (work_rows < (size_t)n_prn * (noncoh ? n_blocks : 1)) work_rows = (size_t)n_prn * (noncoh ? n_blocks : 1);
+    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
+    AcqCorr k;
+    k.n_bins = n_bins;
+    k.n_phi = n_phi;
+    k.n_blocks = n_blocks;
+    k.noncoh = noncoh;
+    k.out_per_prn = noncoh ? n_bins : rows_per_prn;
+    k.rows_out_all = n_prn * k.out_per_prn;
+    k.nblk = sgx_fft4_row_blocks();
+    k.nres = sgx_fft4_residues();
+    // Round 5: peak and second peak from ONE pass (acq_rowtop2_peak_kernel) when the exclusion list leaves out fewer than
+    // `nres` consecutive indices (2 spc of them at most: any sampling rate below 111 MHz); SGX_ACQ_TOP2=0: the round-4
+    // sequence, which transforms each PRN's winning row a second time
+    k.top2 = 2 * spc + 1 <= k.nres && !a.env.top2_off;
+    k.d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
+    size_t pow_need = (size_t)k.rows_out_all * k.nblk * 12 + 4096;
+    if (noncoh && pow_need < (size_t)n_prn * sizeof(double) * (size_t)N) pow_need = (size_t)n_prn * sizeof(double) * (size_t)N;
+    if ((rc = acq_corr_carve(c, &k, pow_need)) != SGX_OK) return rc;
+
+    SgxSmall* dsm = c->d_small;
+    long long* d_sum = &dsm->sum;
+
+    hipEventRecord(c->ev[0], st);
+    {
+        // ---- set-up, record sum, mixed rows (n_blocks x n_phi, PRN independent) and code rows (n_prn): one launch for
+        //      int8 records; then the forward spectra of all of them as ONE batch, straight into d_fwd = [forward | code]
+        AcqSetup su;
+        memset(&su, 0, sizeof(su));
+        su.n_prn = n_prn;
+        su.n_bins = n_bins;
+        for (int i = 0; i < n_prn; ++i) su.prn[i] = a.prn0[i];
+        for (int b = 0; b < n_bins; ++b) su.bin[b] = bin_map[(size_t)b];
+        static_assert(ACQ_MAX_BINS <= 256, "the set-up workgroup has 256 threads");
+        if (!x.f64 && !a.env.front_off) {
+            const int ph = c->acq_sum_phase & 1;
+            long long* sum_now = dsm->sum2 + ph;
+            long long* sum_next = dsm->sum2 + (ph ^ 1);
+            if (!c->acq_sum_clean[ph]) SGX_HIP(hipMemsetAsync(sum_now, 0, 8, st));
+            const unsigned gx = (unsigned)((N + 255) / 256);
+            acq_front_kernel<<<(unsigned)(rows_fwd + n_prn) * gx + ACQ_SUM_WGS + 1, 256, 0, st>>>(
+                su, x, pa, c->d_codes, c->d_work[1], N, rows_fwd, ts, tc, (long long)n_samples, dsm->prn, dsm->bin_map, sum_now,
+                sum_next, dsm->second, dsm->arrived);
+            c->acq_sum_clean[ph] = false;
+            c->acq_sum_clean[ph ^ 1] = true;
+            c->acq_sum_phase = ph ^ 1;
+            d_sum = sum_now;
+        } else {
+            acq_setup_kernel<<<1, 128, 0, st>>>(su, dsm->prn, dsm->bin_map, d_sum, dsm->second, dsm->arrived);
+            if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)n_samples, d_sum);
+            else acq_sum_kernel<<<64, 256, 0, st>>>(x.i8, (long long)n_samples, d_sum);
+            dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows_fwd);
+            acq_mixphi_kernel<<<grid, 256, 0, st>>>(x, c->d_work[1], N, pa);
+            dim3 grid2((unsigned)((N + 255) / 256), (unsigned)n_prn);
+            acq_code_kernel<<<grid2, 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[1] + (size_t)rows_fwd * (size_t)N, N, ts, tc);
+        }
+        rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
+        if (rc != SGX_OK) return rc;
+    }
+    acq_reset_outputs(a);
+    // ---- correlation, all PRN chunks queued back to back; row maxima of every PRN collected on the device -----------
+    hipStream_t st2 = st;
+    if (two_q) {
+        if ((rc = acq_second_queue(c, &st2)) != SGX_OK) return rc;
+        // (the second queue's intermediate is the buffer the forward transforms read: they are queued in front)
+        SGX_HIP(hipEventRecord(c->acq_ev2[0], st));
+        SGX_HIP(hipStreamWaitEvent(st2, c->acq_ev2[0], 0));
+    }
+    int chunk_no = 0;
+    const int bins_per_run = plan.bins_per_run;
+    for (int p0 = 0; p0 < n_prn; p0 += prn_chunk)
+        for (int bin0 = 0; bin0 < n_bins; bin0 += bins_per_run, ++chunk_no) {
+            const int np = (p0 + prn_chunk <= n_prn) ? prn_chunk : (n_prn - p0);
+            const int nb = bin_runs == 1 ? n_bins : (bin0 + bins_per_run <= n_bins ? bins_per_run : n_bins - bin0);
+            const int q = two_q ? (chunk_no & 1) : 0;
+            rc = acq_corr_batch(c, k, p0, np, bin0, nb, 0, n_blocks, c->d_work[q], q ? st2 : st);
+            if (rc != SGX_OK) {
+                // (the second queue may still hold chunks that write d_work[1]: nothing of the next call may overtake them)
+                if (two_q) hipStreamSynchronize(st2);
+                return rc;
+            }
+        }
+    if (two_q) {
+        SGX_HIP(hipEventRecord(c->acq_ev2[1], st2));
+        SGX_HIP(hipStreamWaitEvent(st, c->acq_ev2[1], 0));
+    }
+    // ---- the fine search is queued right behind the coarse one: the detections are decided on the device
+    //      (acquisition.py:164-166) and the fine kernels read their list, so the host looks ONCE, at the very end ----------
+    const unsigned long long seq = ++c->look_seq;
+    const FineGeom fg = acq_fine_geom(N);
+    const bool device_led = sgx_fft_fine_supported(fg.npts) && !a.env.fine_v1 && !a.env.device_led_off && n_prn <= 32;
+    if (device_led) {
+        // (before the last coarse kernels are queued: nothing of the host's between them and the fine kernels)
+        rc = sgx_fft_plan_create(&c->plan_fine, fg.npts);
+        if (rc != SGX_OK) return rc;
+        const int max_rows = (n_prn + 1) / 2;   // two real signals per complex row; only the detections' rows are touched
+        if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)max_rows * sizeof(cplx) * (size_t)fg.npts)) != SGX_OK) return rc;
+    }
+    // (device-led: into a device-side copy of the page - a kernel that writes host memory ends with a flush the next one
+    // waits for, 5 us in front of the fine search)
+    CoarseLook* const d_stage = &dsm->stage;
+    CoarseLook* const d_look = (CoarseLook*)c->d_look;
+    // ---- device: row maxima, then per PRN block choice, global peak, exclusion list, second peak -----------------------
+    if (k.top2) {
+        PublishArgs pub;
+        pub.stage = device_led ? d_stage : nullptr;
+        pub.prn_list = dsm->prn;
+        pub.threshold = S.acqThreshold;
+        pub.fine_len = fg.len;
+        pub.n_samples = (long long)n_samples;
+        pub.det = &dsm->det;
+        acq_queue_top2(a, k, spc, pub);
+    } else {
+        acq_rowmax_peak_kernel<<<k.rows_out_all, 64, 0, st>>>(k.pmax, k.parg, k.nblk, k.rowmax, k.rowarg, dsm->arrived, n_prn,
+                                                              k.out_per_prn, n_bins, n_blocks, noncoh, N, spc, &dsm->peak_out,
+                                                              &dsm->second_args, dsm->row_map);
+        // the rows the second-peak search reads, transformed again
+        const int rows2 = n_prn * (noncoh ? n_blocks : 1);
+        Fft4Fuse fu;
+        fu.mul_x = c->d_fwd;
+        fu.mul_f = k.d_codefd;
+        fu.bin_map = dsm->bin_map;
+        fu.row_map = dsm->row_map;
+        fu.n_bins = n_bins;
+        fu.n_phi = n_phi;
+        fu.n_blocks = n_blocks;
+        // the rows kernel folds each row's maximum over the exclusion list into d_second itself (the same powers, formed
+        // by the same arithmetic, as the first pass: peak / second peak is a ratio of consistently rounded values);
+        // neither the rows nor their powers are stored
+        static_assert(sizeof(SecondArgs) == 5 * 32 * sizeof(int), "row / lo0 / hi0 / lo1 / hi1, 32 each");
+        fu.sec = reinterpret_cast<const int*>(&dsm->second_args);
+        fu.second_out = dsm->second;
+        fu.inv_n = 1.0 / (double)N;
+        fu.sum_blocks = noncoh ? n_blocks : 1;
+        rc = sgx_fft4_forward(&c->plan_code, nullptr, c->d_work[0], nullptr, rows2, st, &fu);
+        if (rc != SGX_OK) return rc;
+    }
+    if (!k.top2 || !device_led) acq_queue_publish(a, device_led ? d_stage : d_look, seq, fg.len, device_led ? &dsm->det : nullptr);
+    // (an event between the coarse and the fine kernels holds the fine search back by 6-8 us: recorded on request only)
+    if (a.env.split_event || !device_led) hipEventRecord(c->ev[1], st);
+    SGX_HIP(hipGetLastError());
+    if (device_led) {
+        rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, nullptr, nullptr, n_prn, fg.len, d_sum, (double)n_samples, ts,
+                                 1.0 / S.codeFreqBasis, c->d_fine[0], 4, fg.uniq - 5, dsm->fine_pv, dsm->fine_pi, st, &dsm->det,
+                                 d_look->fine_bi, &d_look->seq2, seq, reinterpret_cast<const int*>(d_stage),
+                                 reinterpret_cast<int*>(d_look), (int)(offsetof(CoarseLook, fine_bi) / sizeof(int)));
+        if (rc != SGX_OK) return rc;
+        hipEventRecord(c->ev[2], st);
+        SGX_HIP(hipGetLastError());
+        // everything is queued; what the look needs to be decoded later (sgx_acquire_finish)
+        AcqPending& P = c->acq_pending;
+        P.mode = 1;
+        P.seq = seq;
+        P.n_prn = n_prn;
+        for (int i = 0; i < n_prn; ++i) P.prn0[i] = a.prn0[i];
+        P.npts = fg.npts;
+        P.fine_len = fg.len;
+        P.n_samples = n_samples;
+        P.split_event = a.env.split_event;
+        P.spin = a.env.spin;
+        if (defer) return SGX_OK;
+        return sgx_acquire_finish(c, a.carrFreq, a.codePhase, a.peakMetric, a.freqBin, a.fineIdx);
+    }
+    const CoarseLook* look = (const CoarseLook*)c->h_look;
+    rc = coarse_look_wait(c, &look->seq, seq, a.env.spin);
+    if (rc != SGX_OK) return rc;
+    AcqDets det;
+    rc = acq_look_decode(a, look->po, look->second, 0, n_prn, &det);
+    if (rc != SGX_OK) return rc;
+    return acq_fine_and_times(a, det, d_sum, nullptr);
+}
+
+// The host's ONE look at a device-led acquisition (queued by acquire_four_step; c->acq_pending says what was asked): waits
+// for the result page's second word, then decodes peaks, detections and fine frequencies exactly as the eager call did.
+int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    AcqPending& P = c->acq_pending;
+    if (P.mode == 2) {   // (the search could not be deferred and ran eagerly: its outputs were kept)
+        P.mode = 0;
+        for (int i = 0; i < P.n_prn; ++i) {
+            carrFreq[i] = P.res_carr[i];
+            codePhase[i] = P.res_cph[i];
+            peakMetric[i] = P.res_met[i];
+            freqBin[i] = P.res_fb[i];
+            fineIdx[i] = P.res_fi[i];
+        }
+        return P.rc;
+    }
+    if (P.mode != 1) {
+        sgx_set_error("sgx_acquire_end: no acquisition is pending on this context");
+        return SGX_E_ARG;
+    }
+    P.mode = 0;
+    const sgx_settings& S = c->s;
+    AcqCall a{};
+    a.c = c;
+    a.n_samples = P.n_samples;
+    a.prn0 = P.prn0;
+    a.n_prn = P.n_prn;
+    a.carrFreq = carrFreq;
+    a.codePhase = codePhase;
+    a.peakMetric = peakMetric;
+    a.freqBin = freqBin;
+    a.fineIdx = fineIdx;
+    acq_reset_outputs(a);
+    const CoarseLook* look = (const CoarseLook*)c->h_look;
+    int rc = coarse_look_wait(c, &look->seq2, P.seq, P.spin);
+    if (rc != SGX_OK) return rc;
+    AcqDets det;
+    rc = acq_look_decode(a, look->po, look->second, 0, a.n_prn, &det);
+    if (rc != SGX_OK) return rc;
+    if (look->range_error) return acq_fine_range_error((long long)look->po.cph[look->range_error - 1] + P.fine_len, P.n_samples);
+    if (look->n_det != (int)det.slot.size()) {   // (the same comparison on the same doubles: cannot differ)
+        sgx_set_error("acquisition: device found %d detections, host %d", look->n_det, (int)det.slot.size());
+        return SGX_E_HIP;
+    }
+    for (int d = 0; d < look->n_det; ++d) {
+        const long long m = look->fine_bi[d] - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
+        const int o = look->det_slot[d];
+        carrFreq[o] = ((double)m * S.samplingFreq) / (double)P.npts;   // acquisition.py:189-191 (Q3)
+        codePhase[o] = (double)look->det_phase[d];
+        fineIdx[o] = (int)m;
+    }
+    // (the result word is stored a moment before the last kernel retires: the device times below need its event)
+    SGX_HIP(hipEventSynchronize(c->ev[2]));
+    acq_event_times(c, P.split_event);
+    return SGX_OK;
+}
+
+// The shift path of the coherent search: folded rows per (window, phi), their forward spectra once, the correlation
+// batches of acquire_four_step (Fft4Fuse reads each bin's row with its circular shift), the same peak kernels, then one
+// host look and the fine search.  All on one queue.
+static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
+    sgx_ctx* c = a.c;
+    const SgxSig x = a.x;
+    const int n_prn = a.n_prn;
     const long long N = c->n_code;
     const sgx_settings& S = c->s;
     hipStream_t st = c->stream;
@@ -2304,50 +2024,40 @@ static int acquire_coherent_shift(sgx_ctx* c, SgxSig x, size_t n_samples, const 
     if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
-    const int nres = sgx_fft4_residues();
-    const int out_per_prn = noncoh ? n_bins : rows_per_prn;
-    const int rows_out_all = n_prn * out_per_prn;
+    AcqCorr k;
+    k.n_bins = n_bins;
+    k.n_phi = n_phi;
+    k.n_blocks = M;
+    k.noncoh = noncoh;
+    k.out_per_prn = noncoh ? n_bins : rows_per_prn;
+    k.rows_out_all = n_prn * k.out_per_prn;
+    k.nblk = sgx_fft4_row_blocks();
+    k.nres = sgx_fft4_residues();
+    k.top2 = true;
+    k.d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
     // peak and second peak from one pass (acq_rowtop2_peak_kernel): the four-step length has 217 residues, so any exclusion
     // list (2 spc + 1 = 75 indices at that length's rate) fits
-    if (2 * spc + 1 > nres) {
+    if (2 * spc + 1 > k.nres) {
         sgx_set_error("coherent acquisition: %d samples per chip exceed the one-pass second-peak search", spc);
         return SGX_E_ARG;
     }
-    const size_t part_bytes = (((size_t)rows_out_all * (size_t)nres * 20) + 255) / 256 * 256;
-    const size_t red_bytes = (part_bytes + (size_t)rows_out_all * 12 + 1023) / 256 * 256;
-    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, red_bytes)) != SGX_OK) return rc;
-    char* red = (char*)c->d_pow;
-    double* d_t2b1 = (double*)red;
-    double* d_t2b2 = d_t2b1 + (size_t)rows_out_all * nres;
-    int* d_t2i1 = (int*)(d_t2b2 + (size_t)rows_out_all * nres);
-    double* d_rowmax = (double*)(red + part_bytes);
-    int* d_rowarg = (int*)(red + part_bytes + (size_t)rows_out_all * 8);
+    if ((rc = acq_corr_carve(c, &k, 0)) != SGX_OK) return rc;
 
-    char* dsm = (char*)c->d_small;
-    char* hsm = (char*)c->h_small;
-    long long* d_sum = (long long*)dsm;
-    int* d_prn = (int*)(dsm + 64);
-    int2* d_binmap = (int2*)(dsm + 1024);              // [n_bins <= ACQ_COH_MAX_BINS]
-    double* d_second = (double*)(dsm + 1024 + 12 * 4096);
-    int* d_arrived = (int*)(dsm + 51200);
-    PeakOut* d_po = (PeakOut*)(dsm + 620000);
-    static_assert(1024 + ACQ_COH_MAX_BINS * sizeof(int2) <= 1024 + 12 * 4096, "bin map in front of the second peaks");
+    SgxSmall* dsm = c->d_small;
+    SgxSmall* hsm = c->h_small;
     // (host staging in the pinned small buffer: the copies are queued, the buffer is not touched again before the look)
-    int* h_prn = (int*)(hsm + 800000);
-    int2* h_binmap = (int2*)(hsm + 800000 + 256);
-    for (int i = 0; i < n_prn; ++i) h_prn[i] = prn0[i];
-    for (int k = 0; k < n_bins; ++k) h_binmap[k] = g.bin_map[(size_t)k];
+    for (int i = 0; i < n_prn; ++i) hsm->stage_prn[i] = a.prn0[i];
+    for (int b = 0; b < n_bins; ++b) hsm->stage_bin_map[b] = g.bin_map[(size_t)b];
 
     hipEventRecord(c->ev[0], st);
-    cplx* const d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
     {
-        SGX_HIP(hipMemcpyAsync(d_prn, h_prn, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
-        SGX_HIP(hipMemcpyAsync(d_binmap, h_binmap, sizeof(int2) * (size_t)n_bins, hipMemcpyHostToDevice, st));
-        SGX_HIP(hipMemsetAsync(d_sum, 0, 8, st));
-        SGX_HIP(hipMemsetAsync(d_second, 0, sizeof(double) * 32, st));
-        SGX_HIP(hipMemsetAsync(d_arrived, 0, sizeof(int) * 64, st));
-        if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)n_samples, d_sum);
-        else acq_sum_kernel<<<64, 256, 0, st>>>(x.i8, (long long)n_samples, d_sum);
+        SGX_HIP(hipMemcpyAsync(dsm->prn, hsm->stage_prn, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemcpyAsync(dsm->bin_map, hsm->stage_bin_map, sizeof(int2) * (size_t)n_bins, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemsetAsync(&dsm->sum, 0, 8, st));
+        SGX_HIP(hipMemsetAsync(dsm->second, 0, sizeof(double) * 32, st));
+        SGX_HIP(hipMemsetAsync(dsm->arrived, 0, sizeof(int) * 64, st));
+        if (x.f64) acq_sum_f64_kernel<<<1, 1024, 0, st>>>(x.f64, (long long)a.n_samples, &dsm->sum);
+        else acq_sum_kernel<<<64, 256, 0, st>>>(x.i8, (long long)a.n_samples, &dsm->sum);
         FoldArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.n_phi = n_phi;
@@ -2355,117 +2065,268 @@ static int acquire_coherent_shift(sgx_ctx* c, SgxSig x, size_t n_samples, const 
         for (int j = 0; j < n_phi; ++j) fa.phi[j] = g.phi[(size_t)j];
         const unsigned gx = (unsigned)((N + 255) / 256);
         acq_fold_phi_kernel<<<dim3(gx, (unsigned)M), 256, 0, st>>>(x, c->d_work[1], N, fa);
-        acq_code_kernel<<<dim3(gx, (unsigned)n_prn), 256, 0, st>>>(c->d_codes, d_prn, c->d_work[1] + (size_t)rows_fwd * (size_t)N,
+        acq_code_kernel<<<dim3(gx, (unsigned)n_prn), 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[1] + (size_t)rows_fwd * (size_t)N,
                                                                    N, ts, tc);
         rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
         if (rc != SGX_OK) return rc;
     }
-    for (int i = 0; i < n_prn; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
-    }
+    acq_reset_outputs(a);
     // ---- correlation: batches of whole PRNs, or one PRN in runs of bins (noncoh) / windows (reference rule) ----------
-    const double inv_n = 1.0 / (double)N;
     const int total = noncoh ? n_bins : M;
     for (int p0 = 0; p0 < n_prn; p0 += g.prn_chunk)
         for (int r0 = 0; r0 < total; r0 += (g.runs == 1 ? total : g.per_run)) {
             const int np = (p0 + g.prn_chunk <= n_prn) ? g.prn_chunk : (n_prn - p0);
             const int nr = g.runs == 1 ? total : (r0 + g.per_run <= total ? g.per_run : total - r0);
-            Fft4Fuse fu;
-            fu.mul_f = d_codefd;
-            fu.n_phi = n_phi;
-            fu.prn_base = p0;
-            size_t out0;
-            if (noncoh) {
-                fu.mul_x = c->d_fwd;
-                fu.bin_map = d_binmap + r0;
-                fu.n_bins = nr;
-                fu.n_blocks = M;
-                fu.rows_per_prn = nr * M;
-                fu.blocks_fast = 1;
-                fu.sum_blocks = M;
-                out0 = (size_t)p0 * out_per_prn + (size_t)r0;
-            } else {
-                fu.mul_x = c->d_fwd + (size_t)r0 * n_phi * (size_t)N;   // (a run of windows reads its windows' rows)
-                fu.bin_map = d_binmap;
-                fu.n_bins = n_bins;
-                fu.n_blocks = nr;
-                fu.rows_per_prn = nr * n_bins;
-                fu.blocks_fast = 0;
-                fu.sum_blocks = 1;
-                out0 = (size_t)p0 * out_per_prn + (size_t)r0 * n_bins;
-            }
-            fu.t2_b1 = d_t2b1 + out0 * nres;
-            fu.t2_b2 = d_t2b2 + out0 * nres;
-            fu.t2_i1 = d_t2i1 + out0 * nres;
-            fu.inv_n = inv_n;
-            rc = sgx_fft4_forward(&c->plan_code, nullptr, c->d_work[0], nullptr, (int64_t)np * fu.rows_per_prn, st, &fu);
+            rc = noncoh ? acq_corr_batch(c, k, p0, np, r0, nr, 0, M, c->d_work[0], st)
+                        : acq_corr_batch(c, k, p0, np, 0, n_bins, r0, nr, c->d_work[0], st);
             if (rc != SGX_OK) return rc;
         }
     // ---- row maxima, block (window) choice, global peak, exclusion list, second peak: acquire_four_step's kernels -------
     const unsigned long long seq = ++c->look_seq;
-    const long long fine_len = 10 * N;
-    {
-        PublishArgs pub;
-        memset(&pub, 0, sizeof(pub));   // (no stage: the publish kernel below writes the page)
-        acq_rowtop2_peak_kernel<<<rows_out_all, 64, 0, st>>>(d_t2b1, d_t2b2, d_t2i1, nres, d_rowmax, d_rowarg, d_arrived, n_prn,
-                                                             out_per_prn, n_bins, M, noncoh, N, spc, d_po, d_second, pub);
-    }
-    acq_publish_kernel<<<1, 64, 0, st>>>(d_po, d_second, n_prn, (CoarseLook*)c->d_look, seq, d_prn, S.acqThreshold, fine_len,
-                                         (long long)n_samples, nullptr);
+    PublishArgs pub;
+    memset(&pub, 0, sizeof(pub));   // (no stage: the publish kernel below writes the page)
+    acq_queue_top2(a, k, spc, pub);
+    acq_queue_publish(a, (CoarseLook*)c->d_look, seq, acq_fine_geom(N).len, nullptr);
     hipEventRecord(c->ev[1], st);
     SGX_HIP(hipGetLastError());
-    rc = coarse_look_wait(c, seq);
-    if (rc != SGX_OK) return rc;
     const CoarseLook* look = (const CoarseLook*)c->h_look;
-    const PeakOut* h_po = &look->po;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        if (h_po->index_error[pi]) {
-            sgx_set_error("IndexError: index %lld is out of bounds for axis 1 with size %lld "
-                          "(PRN index %d, codePhase %d; reference acquisition.py:152-162)",
-                          N, N, prn0[pi], h_po->cph[pi]);
-            return SGX_E_INDEX;
-        }
-    }
-    std::vector<int> det_prn, det_phase, det_slot, det_bin;
-    for (int pi = 0; pi < n_prn; ++pi) {
-        const double ratio = h_po->peak[pi] / look->second[pi];
-        peakMetric[pi] = ratio;
-        freqBin[pi] = h_po->fbi[pi];
-        if (ratio > S.acqThreshold) {
-            det_prn.push_back(prn0[pi]);
-            det_phase.push_back(h_po->cph[pi]);
-            det_slot.push_back(pi);
-            det_bin.push_back(h_po->fbi[pi]);
-        }
-    }
-    std::vector<long long> win;
-    if (g.T > 1) win = coh_fine_windows(g, S, N, det_bin);
-    rc = acquire_fine(c, x, n_samples, det_prn, det_phase, det_slot, d_sum, carrFreq, codePhase, fineIdx,
-                      win.empty() ? nullptr : &win);
+    rc = coarse_look_wait(c, &look->seq, seq, a.env.spin);
     if (rc != SGX_OK) return rc;
-    hipEventElapsedTime(&c->timing.acquire_ms, c->ev[0], c->ev[2]);
-    hipEventElapsedTime(&c->timing.acq_coarse_ms, c->ev[0], c->ev[1]);
-    hipEventElapsedTime(&c->timing.acq_fine_ms, c->ev[1], c->ev[2]);
+    AcqDets det;
+    rc = acq_look_decode(a, look->po, look->second, 0, n_prn, &det);
+    if (rc != SGX_OK) return rc;
+    return acq_fine_and_times(a, det, &dsm->sum, &g);
+}
+
+// ================================ entry points ================================
+static AcqCall acq_call(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, double* carrFreq,
+                        double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
+    AcqCall a;
+    a.c = c;
+    a.x = x;
+    a.n_samples = n_samples;
+    a.prn0 = prn0;
+    a.n_prn = n_prn;
+    a.carrFreq = carrFreq;
+    a.codePhase = codePhase;
+    a.peakMetric = peakMetric;
+    a.freqBin = freqBin;
+    a.fineIdx = fineIdx;
+    a.env = env;
+    return a;
+}
+
+static int acquire_any(const AcqCall& a, int n_blocks, int noncoh) {
+    // the four-step path (sub-transforms in registers and LDS, shifted forward spectra) where it applies
+    bool handled = false;
+    const int rc4 = acquire_four_step(a, n_blocks, noncoh, &handled);
+    if (handled) return rc4;
+    return acquire_passes(a, n_blocks, noncoh);
+}
+
+static int acquire_record(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                          int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
+                          int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
+    SGX_CHECK_ARG(c && r && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    SgxSig x;
+    const int rc = acq_open_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, &x);
+    if (rc != SGX_OK) return rc;
+    return acquire_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), n_blocks,
+                       noncoh);
+}
+extern "C" int sgx_acquire(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
+                           int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
+                           double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    return acquire_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin,
+                          fineIdx, acq_env());
+}
+
+static int acquire_signal(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                          int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
+                          int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
+    SGX_CHECK_ARG(c && signal && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    SGX_CHECK_ARG(n_blocks >= 1 && n_blocks <= 64);
+    int rc = acq_check_prns(prn0, n_prn);
+    if (rc != SGX_OK) return rc;
+    const long long N = c->n_code;
+    if ((long long)n_samples < (long long)n_blocks * N) {
+        sgx_set_error("signal too short: %zu samples, %lld needed for the coarse search", n_samples, (long long)n_blocks * N);
+        return SGX_E_RANGE;
+    }
+    SgxSig x;
+    if ((rc = acq_upload_f64(c, signal, n_samples, &x)) != SGX_OK) return rc;
+    return acquire_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), n_blocks,
+                       noncoh);
+}
+extern "C" int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                               int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
+                               int32_t* freqBin, int32_t* fineIdx) {
+    return acquire_signal(c, signal, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx,
+                          acq_env());
+}
+
+int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes, long long rec_file_offset, int sample_bytes) {
+    const AcqPending& P = c->acq_pending;
+    if (P.mode != 1 || n_ch < 1 || n_ch > 32) return SGX_E_DEFER;
+    StepLook* look = (StepLook*)((char*)c->d_look + SGX_STEP_LOOK_OFFSET);
+    acq_prerun_kernel<<<1, 64, 0, c->stream>>>(&c->d_small->stage, ((const CoarseLook*)c->d_look)->fine_bi, c->d_small->prn, P.n_prn,
+                                               c->s.samplingFreq, (double)P.npts, d_ch, n_ch, skip_bytes, rec_file_offset,
+                                               sample_bytes, look);
+    SGX_HIP(hipGetLastError());
     return SGX_OK;
 }
 
-static int acquire_coherent_any(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, const CohGrid& g,
-                                double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    if (g.path == 1)
-        return acquire_coherent_shift(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
-    return acquire_passes(c, x, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx, &g);
+// ---- deferred acquisition (round 6) ----
+// The reference's caller (initialize.py:484-506) runs acquire -> preRun -> track and looks at each result in between.  A
+// caller that only wants the tracking results can queue all three: sgx_acquire_begin queues the search and returns,
+// sgx_track_chained (sgx_trk.hip) queues preRun - acq_prerun_kernel - and the tracking kernel behind it and waits ONCE;
+// sgx_acquire_end then decodes the search's page (no waiting left).  Outputs are those of the eager calls, bit for bit:
+// the same kernels in the same order, and acq_prerun_kernel repeats the host's arithmetic.
+static int acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
+                         int32_t n_blocks, int32_t noncoh, const AcqEnv& env) {
+    SGX_CHECK_ARG(c && r && prn0);
+    SgxSig x;
+    int rc = acq_open_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, &x);
+    if (rc != SGX_OK) return rc;
+    AcqPending& P = c->acq_pending;
+    P.mode = 0;
+    const AcqCall a = acq_call(c, x, n_samples, prn0, n_prn, P.res_carr, P.res_cph, P.res_met, P.res_fb, P.res_fi, env);
+    bool handled = false;
+    rc = acquire_four_step(a, n_blocks, noncoh, &handled, true);
+    if (handled && P.mode == 1) return rc;          // queued; nothing has been looked at
+    if (!handled) rc = acquire_passes(a, n_blocks, noncoh);
+    // (a path without the device-led sequence: it ran eagerly; sgx_acquire_end hands its outputs over)
+    P.mode = 2;
+    P.n_prn = n_prn;
+    P.rc = rc;
+    return SGX_OK;
+}
+extern "C" int sgx_acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
+                                 int32_t n_prn, int32_t n_blocks, int32_t noncoh) {
+    return acquire_begin(c, r, offset, n_samples, prn0, n_prn, n_blocks, noncoh, acq_env());
+}
+
+extern "C" int sgx_acquire_end(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
+                               int32_t* fineIdx) {
+    SGX_CHECK_ARG(c && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    SGX_HIP(hipSetDevice(c->device));
+    return sgx_acquire_finish(c, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+}
+
+// ================================ round 6: the sharded search as ONE call ================================
+// BASELINE configs[3]: the PRN loop (acquisition.py:92) shards over the ranks, the peaks are gathered.  Rounds 1-5 did the
+// pack, the gather and the merge in Python around sgx_acquire (softgnss-python_amd/shard.py): 0.17-0.28 ms of host time per
+// call next to a 0.45 ms shard.  Here the rank's search is queued, its peaks are packed into 40-byte records ON THE DEVICE
+// behind it, one ncclAllGather follows on the same stream, a small kernel copies the gathered records to the result page and
+// the host looks ONCE; the merge into the 32-entry arrays is a loop over at most 32 records.
+extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int32_t world, const sgx_if* r, size_t offset,
+                                   size_t n_samples, int32_t n_prn_total, int32_t n_blocks, int32_t noncoh, double* carrFreq,
+                                   double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+    SGX_CHECK_ARG(c && r && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    SGX_CHECK_ARG(world >= 1 && rank >= 0 && rank < world && n_prn_total >= 1 && n_prn_total <= 32);
+    SGX_CHECK_ARG(!comm || (comm->n_ranks == world && comm->rank == rank && comm->ctx == c));
+    const AcqEnv env = acq_env();
+    acq_reset_outputs(carrFreq, codePhase, peakMetric, freqBin, fineIdx, 32);
+    // contiguous balanced partition (shard.plan_shards)
+    const int base = n_prn_total / world, extra = n_prn_total % world;
+    const int first = rank * base + (rank < extra ? rank : extra);
+    const int n_mine = base + (rank < extra ? 1 : 0);
+    const int slots = (n_prn_total + world - 1) / world;
+    int32_t prn0[32];
+    for (int i = 0; i < n_mine; ++i) prn0[i] = first + i;
+    SGX_HIP(hipSetDevice(c->device));
+    const size_t rec_bytes = sizeof(PeakRec) * (size_t)slots;
+    // where the packed records go: the communicator's send buffer, or (no communicator: one rank, or a shard run alone)
+    // the context's small device area
+    SgxSmall* dsm = c->d_small;
+    PeakRec* d_send = comm ? (PeakRec*)comm->d_send : dsm->shard;
+    const PeakRec* d_all = comm ? (const PeakRec*)comm->d_recv : d_send;
+    const int n_ranks_seen = comm ? world : 1;
+    std::vector<PeakRec> host_pack;      // a search that could not be queued: packed on the host
+    bool queued = false;
+    if (n_mine > 0) {
+        const int rb = acquire_begin(c, r, offset, n_samples, prn0, n_mine, n_blocks, noncoh, env);
+        if (rb != SGX_OK) return rb;
+        queued = c->acq_pending.mode == 1;
+        if (!queued) {
+            double cf[32], cp[32], pm[32];
+            int fb[32], fi[32];
+            const int re = sgx_acquire_finish(c, cf, cp, pm, fb, fi);
+            if (re != SGX_OK && re != SGX_E_INDEX && re != SGX_E_RANGE) return re;
+            host_pack.resize((size_t)slots);
+            memset(host_pack.data(), 0, rec_bytes);
+            for (int i = 0; i < n_mine; ++i) {
+                PeakRec& q = host_pack[(size_t)i];
+                q.prn0 = prn0[i]; q.freqBin = fb[i]; q.carrFreq = cf[i]; q.codePhase = cp[i]; q.peakMetric = pm[i];
+                q.fineIdx = fi[i]; q.valid = 1;
+            }
+            if (re != SGX_OK) host_pack[0].valid = re == SGX_E_INDEX ? -1 : -2;   // (every rank learns of it)
+        }
+    }
+    hipStream_t st = c->stream;
+    if (queued) {
+        const AcqPending& P = c->acq_pending;
+        acq_pack_kernel<<<1, 64, 0, st>>>(&dsm->stage, ((const CoarseLook*)c->d_look)->fine_bi, dsm->prn, P.n_prn, c->s.samplingFreq, (double)P.npts, d_send, slots);
+    } else {
+        if (host_pack.empty()) {
+            host_pack.resize((size_t)slots);
+            memset(host_pack.data(), 0, rec_bytes);
+        }
+        SGX_HIP(hipMemcpyAsync(d_send, host_pack.data(), rec_bytes, hipMemcpyHostToDevice, st));
+    }
+    if (comm) {
+        const int rg = sgx_comm_allgather_device(comm, rec_bytes);
+        if (rg != SGX_OK) return rg;
+    }
+    const size_t all_bytes = rec_bytes * (size_t)n_ranks_seen;
+    if (all_bytes > SGX_TRK_LOOK_OFFSET - SGX_GATHER_LOOK_OFFSET - 16) {
+        sgx_set_error("sgx_acquire_sharded: %d ranks x %d slots do not fit the result page", world, slots);
+        return SGX_E_ARG;
+    }
+    const unsigned long long seq = ++c->look_seq;
+    char* page_d = (char*)c->d_look + SGX_GATHER_LOOK_OFFSET;
+    const char* page_h = (const char*)c->h_look + SGX_GATHER_LOOK_OFFSET;
+    acq_gather_publish_kernel<<<1, 256, 0, st>>>((const int*)d_all, (int)(all_bytes / 4), (int*)(page_d + 16),
+                                                 (unsigned long long*)page_d, seq);
+    SGX_HIP(hipGetLastError());
+    const int rl = coarse_look_wait(c, (const unsigned long long*)page_h, seq, env.spin);   // the one look
+    if (rl != SGX_OK) return rl;
+    if (queued) {   // (device time of this rank's search; the search's own page is complete: the gather came behind it)
+        c->acq_pending.mode = 0;
+        SGX_HIP(hipEventSynchronize(c->ev[2]));
+        acq_event_times(c, false);
+    }
+    const PeakRec* all = (const PeakRec*)(page_h + 16);
+    const int n_rec = slots * n_ranks_seen;
+    for (int i = 0; i < n_rec; ++i) {
+        const PeakRec& q = all[i];
+        if (q.valid == 0) continue;
+        if (q.valid == -1) return acq_index_error(c->n_code, q.prn0, (int)q.codePhase);
+        if (q.valid == -2) return acq_fine_range_error((long long)q.codePhase + acq_fine_geom(c->n_code).len, n_samples);
+        if (q.prn0 < 0 || q.prn0 >= 32) continue;
+        carrFreq[q.prn0] = q.carrFreq;
+        codePhase[q.prn0] = q.codePhase;
+        peakMetric[q.prn0] = q.peakMetric;
+        freqBin[q.prn0] = q.freqBin;
+        fineIdx[q.prn0] = q.fineIdx;
+    }
+    return SGX_OK;
+}
+
+// ---- coherent multi-millisecond acquisition ----
+// (include/sgx.h, sgx_acquire_coherent; tests/coherent_acq_spec.py is the contract in numpy.)  The search of the reference
+// (acquisition.py:62-166) with T-ms windows in place of its 1-ms blocks, on a finer Doppler grid.
+static int acquire_coherent_any(const AcqCall& a, const CohGrid& g) {
+    if (g.path == 1) return acquire_coherent_shift(a, g);
+    return acquire_passes(a, g.M, g.noncoh, &g);
 }
 
 // Everything an entry point checks before it touches the device: arguments, grid, record length.
 static int coherent_checks(sgx_ctx* c, size_t n_samples, const int32_t* prn0, int32_t n_prn, const sgx_acq_params* p,
                            CohGrid* g, bool* legacy) {
-    SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32);
-    for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
-    const int rc = coh_grid(c->s, c->n_code, p, n_prn, g);
+    int rc = acq_check_prns(prn0, n_prn);
+    if (rc != SGX_OK) return rc;
+    rc = coh_grid(c->s, c->n_code, p, n_prn, g);
     if (rc != SGX_OK) return rc;
     const long long need = (long long)g->T * g->M * c->n_code;
     if ((long long)n_samples < need) {
@@ -2482,51 +2343,34 @@ extern "C" int sgx_acquire_coherent(sgx_ctx* c, const sgx_if* r, size_t offset, 
                                     double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
     SGX_CHECK_ARG(c && r && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
     SGX_CHECK_ARG(offset <= r->n && n_samples <= r->n - offset);
+    const AcqEnv env = acq_env();
     CohGrid g;
     bool legacy = false;
     int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
     if (rc != SGX_OK) return rc;
     if (legacy)
-        return sgx_acquire(c, r, offset, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
-                           fineIdx);
-    rc = sgx_if_require(r, offset + n_samples);   // a record that is still streaming in
-    if (rc != SGX_OK) return rc;
-    SGX_HIP(hipSetDevice(c->device));
+        return acquire_record(c, r, offset, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
+                              fineIdx, env);
     SgxSig x;
-    x.i8 = r->d + offset;
-    x.f64 = nullptr;
-    return acquire_coherent_any(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+    if ((rc = acq_record_sig(c, r, offset, n_samples, &x)) != SGX_OK) return rc;
+    return acquire_coherent_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), g);
 }
 
 extern "C" int sgx_acquire_coherent_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0,
                                         int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,
                                         double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
     SGX_CHECK_ARG(c && signal && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    const AcqEnv env = acq_env();
     CohGrid g;
     bool legacy = false;
     int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
     if (rc != SGX_OK) return rc;
     if (legacy)
-        return sgx_acquire_f64(c, signal, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
-                               fineIdx);
-    SGX_HIP(hipSetDevice(c->device));
-    const size_t need = sizeof(double) * (n_samples + 64);
-    if (c->cap_sig64 < need) {
-        if (c->d_sig64) hipFree(c->d_sig64);
-        c->d_sig64 = nullptr;
-        c->cap_sig64 = 0;
-        if (hipMalloc((void**)&c->d_sig64, need) != hipSuccess) {
-            sgx_set_error("hipMalloc of %zu signal bytes failed", need);
-            return SGX_E_NOMEM;
-        }
-        c->cap_sig64 = need;
-    }
-    SGX_HIP(hipMemcpyAsync(c->d_sig64, signal, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
-    SGX_HIP(hipStreamSynchronize(c->stream));   // the caller may free `signal` on return
+        return acquire_signal(c, signal, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
+                              fineIdx, env);
     SgxSig x;
-    x.i8 = nullptr;
-    x.f64 = c->d_sig64;
-    return acquire_coherent_any(c, x, n_samples, prn0, n_prn, g, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+    if ((rc = acq_upload_f64(c, signal, n_samples, &x)) != SGX_OK) return rc;
+    return acquire_coherent_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), g);
 }
 
 extern "C" int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, int32_t* n_bins, int32_t* n_phi,

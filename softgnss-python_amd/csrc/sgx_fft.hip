@@ -1214,9 +1214,9 @@ struct FineArgs {
     int det_prn[32];          // by value: no host-to-device copy between the coarse and the fine search
     int det_phase[32];
     int n_det;
-    const int* det;           // or, device-led (round 4): the list in device memory, written by the coarse search's publish
-                              // kernel - [0] = n_det, [1 + d] = PRN index, [33 + d] = code phase - so that the fine
-                              // kernels are queued right behind the coarse ones without the host looking in between
+    const AcqDet* det;        // or, device-led (round 4): the list in device memory, written by the coarse search's publish
+                              // kernel, so that the fine kernels are queued right behind the coarse ones without the
+                              // host looking in between
     long long len;            // 10 N samples of signal, zeros beyond
     const long long* d_sum;   // sum of the record window (an integer for int8 samples, the bits of a double otherwise);
                               // mean = sum / n_mean (acquisition.py:59)
@@ -1234,7 +1234,7 @@ struct FineArgs {
     double* pv;               // [n_det][FF_N1 / 2] per-workgroup maxima
     long long* pi;
     // device-led: the workgroup of fine_rows_kernel that finishes LAST folds the partial maxima into out_bi[d] and then
-    // stores `seq` into *out_seq (both in the pinned result page the host spins on); det[FINE_DONE_SLOT] counts arrivals
+    // stores `seq` into *out_seq (both in the pinned result page the host spins on); det->fine_done counts arrivals
     long long* out_bi;
     unsigned long long* out_seq;
     unsigned long long seq;
@@ -1248,11 +1248,9 @@ struct FineArgs {
     const long long* win;
 };
 
-#define FINE_DONE_SLOT 80
-
-#define FA_NDET(a) ((a).det ? (a).det[0] : (a).n_det)
-#define FA_PRN(a, d) ((a).det ? (a).det[1 + (d)] : (a).det_prn[d])
-#define FA_PHASE(a, d) ((a).det ? (a).det[33 + (d)] : (a).det_phase[d])
+#define FA_NDET(a) ((a).det ? (a).det->n_det : (a).n_det)
+#define FA_PRN(a, d) ((a).det ? (a).det->prn[d] : (a).det_prn[d])
+#define FA_PHASE(a, d) ((a).det ? (a).det->phase[d] : (a).det_phase[d])
 
 __global__ __launch_bounds__(FF_TPB) void fine_cols_kernel(FineArgs a, int n_tiles_host) {
     const int n_det_k = FA_NDET(a);
@@ -1525,7 +1523,7 @@ __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pai
     __syncthreads();
     if (tid == 0) {
         const unsigned n_active = (unsigned)((int)gridDim.x < n_pairs ? (int)gridDim.x : n_pairs);
-        unsigned* ctr = reinterpret_cast<unsigned*>(const_cast<int*>(a.det)) + FINE_DONE_SLOT;
+        unsigned* ctr = const_cast<unsigned*>(&a.det->fine_done);
         const unsigned ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = ticket + 1u == n_active;
         if (s_last) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1575,14 +1573,15 @@ __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pai
 static cplx* g_ff_tab[SGX_MAX_DEVICES][3] = {{nullptr, nullptr, nullptr}};   // W_1024^t | W_4096^(64 h) | W_4096^l
 
 bool sgx_fft_fine_supported(int64_t npts) { return npts == (int64_t)FF_N1 * FF_N2; }
-int sgx_fft_fine_partials(void) { return FF_N1 / 2; }
+static_assert(FF_N1 / 2 == SGX_FINE_PARTIALS, "the layout of the small areas (sgx_internal.h)");
+int sgx_fft_fine_partials(void) { return SGX_FINE_PARTIALS; }
 
 // Fine search of n_det detections (two per complex row) on the 2^22-point two-kernel transform.  `plan` = the 2^22
 // plan (its two-level table of W_M is used for the inter-step twiddles).  Fills pv / pi [n_det][sgx_fft_fine_partials()].
 int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, const int* det_prn,
                         const int* det_phase, int n_det, long long len, const long long* d_sum, double n_mean, double ts,
                         double tc1, cplx* work, long long lo, long long hi, double* pv, long long* pi, hipStream_t st,
-                        const int* d_det, long long* out_bi, unsigned long long* out_seq, unsigned long long seq,
+                        const AcqDet* d_det, long long* out_bi, unsigned long long* out_seq, unsigned long long seq,
                         const int* stage_src, int* stage_dst, int stage_words, const long long* win) {
     // d_det != nullptr: device-led - the detection list is in device memory (n_det here = the most it can hold)
     if (!plan->tw_hi || !sgx_fft_fine_supported(plan->n) || n_det < 1 || n_det > 32) {

@@ -155,8 +155,8 @@ static int ctx_build(sgx_ctx* c, int priority) {
     for (int p = 0; p < 32; ++p) sgx_host_ca_code(p, codes.data() + p * 1023);
     SGX_HIP(hipMalloc((void**)&c->d_codes, codes.size()));
     SGX_HIP(hipMemcpy(c->d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
-    SGX_HIP(hipMalloc(&c->d_small, 1 << 20));
-    SGX_HIP(hipHostMalloc(&c->h_small, 1 << 20, hipHostMallocDefault));
+    SGX_HIP(hipMalloc((void**)&c->d_small, SGX_SMALL_BYTES));
+    SGX_HIP(hipHostMalloc((void**)&c->h_small, SGX_SMALL_BYTES, hipHostMallocDefault));
     SGX_HIP(hipHostMalloc(&c->h_look, SGX_LOOK_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
     memset(c->h_look, 0, SGX_LOOK_BYTES);
     SGX_HIP(hipHostGetDevicePointer(&c->d_look, c->h_look, 0));

@@ -88,6 +88,90 @@ int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
                       double* out, int32_t* ms_done);
 #define SGX_IF_PAD 256
 
+// ---- acquisition (sgx_acq.hip): the limits and the small structs its kernels hand to each other and to the host ----
+#define ACQ_MAX_BINS 128          // Doppler bins of the 1-ms search
+#define ACQ_MAX_ROWS 2048         // correlation rows of one batch
+#define ACQ_COH_MAX_BINS 1024     // Doppler bins of the coherent search
+#define SGX_FINE_PARTIALS 512     // per-detection partial maxima of the fine search (sgx_fft_fine_partials())
+
+struct SecondArgs {
+    int row[32];          // power row to search, -1 = skip
+    int lo0[32], hi0[32]; // first index range [lo0, hi0)
+    int lo1[32], hi1[32]; // second index range
+};
+
+// The peak logic's outcome for every PRN of a call (acquisition.py:129-162)
+struct PeakOut {
+    double peak[32];
+    int cph[32], fbi[32];
+    int index_error[32];
+};
+// The coarse search's outcome, written by one small kernel straight into a coherent pinned page: the host spins on
+// `seq` instead of sleeping in hipStreamSynchronize behind two device-to-host copies (~55 us -> ~10 us between the last
+// coarse kernel and the first fine one).
+struct CoarseLook {
+    PeakOut po;
+    double second[32];
+    unsigned long long seq;
+    // device-led fine search (round 4): the detections the publish kernel found (in PRN order, as the reference's loop
+    // finds them), and what the fine search made of them - the host looks ONCE, at seq2
+    int n_det;
+    int range_error;          // a detection's fine window (code phase + 10 ms) leaves the record: 1 + its slot
+    int det_slot[32];         // position in the call's PRN list
+    int det_phase[32];
+    long long fine_bi[32];    // arg-max of the 2^22-point magnitude spectrum over [4, uniq - 5)
+    unsigned long long seq2;
+};
+static_assert(sizeof(CoarseLook) <= 4096, "one pinned page");
+
+// The detection list in device memory: the coarse search's publish step (sgx_acq.hip) writes it, the device-led fine
+// kernels (sgx_fft.hip) read it, so that they are queued right behind the coarse ones without the host looking in between
+struct AcqDet {
+    int n_det;                // (0 on a range error: the fine kernels have nothing to do)
+    int prn[32];              // PRN index of detection d, in ascending position of the call's PRN list
+    int phase[32];            // its code phase
+    int pad[15];
+    unsigned fine_done;       // fine_rows_kernel's arrival counter (zero between calls)
+};
+
+struct PeakRec {      // a rank's peak in the sharded search = shard.PEAK_DTYPE, 40 bytes
+    int prn0, freqBin;
+    double carrFreq, codePhase, peakMetric;
+    int fineIdx, valid;   // valid 1; 0 unused slot; -1 the reference's IndexError at this PRN; -2 its fine window leaves the record
+};
+static_assert(sizeof(PeakRec) == 40, "shard.PEAK_DTYPE");
+
+// The context's small device area (d_small) and its pinned mirror (h_small): one layout for both.  Every slot reaches the
+// kernels as a pointer argument.  A slot is used through the device area, the mirror or both as its comment says.  (alignas:
+// what hipMemsetAsync clears - a fill of an unaligned range takes the runtime several launches instead of one)
+struct SgxSmall {
+    long long sum;                          // record sum (mean for acquisition.py:59) of the paths that clear it themselves
+    alignas(16) long long sum2[2];          // acq_front_kernel's two alternating slots (sgx_ctx::acq_sum_phase)
+    int prn[32];                            // the call's PRN list
+    int2 bin_map[ACQ_COH_MAX_BINS];         // (phi index, circular shift) per Doppler bin (four-step, coherent shift path)
+    double rowmax[ACQ_MAX_ROWS];            // round-1 passes: row maxima of a chunk; both
+    int rowarg[ACQ_MAX_ROWS];
+    alignas(256) double second[32];         // second peaks; both
+    int det_prn[32], det_phase[32];         // host-led fine search on the pass-per-launch transform
+    alignas(256) int arrived[64];           // [32] rows finished per PRN, [32] PRNs finished
+    double fine_pv[32 * SGX_FINE_PARTIALS]; // fine search: per-detection partial maxima and their indices; both
+    long long fine_pi[32 * SGX_FINE_PARTIALS];
+    int2 row_map[32 * 64];                  // rows the second-peak search transforms again (PRNs x blocks); both
+    SecondArgs second_args;
+    PeakOut peak_out;
+    AcqDet det;
+    CoarseLook stage;                       // device-side copy of the result page (device-led search)
+    PeakRec shard[32];                      // sgx_acquire_sharded without a communicator: the packed records
+    double frq[ACQ_COH_MAX_BINS];           // coherent search, direct path: the frequency table; both
+    long long fine_win[64];                 // coherent search: arg-max range per detection; both
+    int stage_prn[32];                      // mirror only: staging of the PRN list and the bin map (coherent shift path)
+    int2 stage_bin_map[ACQ_COH_MAX_BINS];
+    int trk_mag;                            // sgx_trk.hip: the record's magnitude bound
+    uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
+};
+#define SGX_SMALL_BYTES (1 << 20)
+static_assert(sizeof(SgxSmall) <= SGX_SMALL_BYTES, "the small areas hold the layout");
+
 // A DEFERRED acquisition (sgx_acquire_begin, round 6): every kernel of the search is queued, the host has not looked.
 // mode 1: the device-led sequence is in flight (the result page's seq2 will equal `seq`); mode 2: the path could not be
 // deferred, the search ran eagerly and its outputs wait in res_* for sgx_acquire_end.
@@ -96,9 +180,10 @@ struct AcqPending {
     unsigned long long seq = 0;
     int n_prn = 0;
     int prn0[32];
-    long long N = 0, npts = 0, fine_len = 0;
+    long long npts = 0, fine_len = 0;
     size_t n_samples = 0;
-    int rc = 0;                 // mode 2: the eager search's return code
+    bool split_event = false, spin = true;   // SGX_ACQ_SPLIT_EVENT / SGX_ACQ_SPIN as the queued call read them
+    int rc = 0;                // mode 2: the eager search's return code
     double res_carr[32], res_cph[32], res_met[32];
     int res_fb[32], res_fi[32];
 };
@@ -147,10 +232,10 @@ struct sgx_ctx {
     double* d_sig64 = nullptr;   // fp64 copy of a non-int8 signal handed to sgx_acquire_f64
     size_t cap_sig64 = 0;
     size_t cap_fwd = 0, cap_code = 0, cap_w0 = 0, cap_w1 = 0, cap_pow = 0, cap_f0 = 0, cap_f1 = 0;   // bytes
-    void* d_small = nullptr;     // small result area
+    SgxSmall* d_small = nullptr; // small device area
     int acq_sum_phase = 0;       // acq_front_kernel: which of the two record-sum slots this call adds into ...
     bool acq_sum_clean[2] = {false, false};   // ... and whether a slot is known to hold zero (the other call's set-up zeroed it)
-    void* h_small = nullptr;     // pinned mirror
+    SgxSmall* h_small = nullptr; // pinned mirror
     void* h_look = nullptr;      // coherent pinned page a kernel publishes the coarse search's outcome to (host spins on it)
     void* d_look = nullptr;      // its device address
     unsigned long long look_seq = 0;
@@ -234,8 +319,7 @@ int sgx_fft_fine_partials(void);
 int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, const int* det_prn /* host, <= 32 */,
                         const int* d_det_phase, int n_det, long long len, const long long* d_sum, double n_mean, double ts,
                         double tc1, cplx* work, long long lo, long long hi, double* pv, long long* pi, hipStream_t st,
-                        const int* d_det = nullptr /* device-led: [0] n_det, [1 + d] PRN index, [33 + d] code phase,
-                                                      [80] arrival counter (zero) */,
+                        const AcqDet* d_det = nullptr /* device-led: the list in device memory */,
                         long long* out_bi = nullptr /* device-led: [32] arg-max per detection (pinned page) ... */,
                         unsigned long long* out_seq = nullptr /* ... then this word = seq */, unsigned long long seq = 0,
                         const int* stage_src = nullptr /* device-led: dwords copied to stage_dst (the page) before the word */,

@@ -91,7 +91,7 @@ extern "C" int sgx_if_synth(sgx_ctx* c, const sgx_scene* scene, uint64_t offset,
     a.nav_mode = scene->nav_mode;
     memcpy(a.sats, scene->sats, sizeof(a.sats));
     memcpy(a.cos_lut, scene->cos_lut, sizeof(a.cos_lut));
-    uint8_t* d_nav = (uint8_t*)c->d_small + 512 * 1024;   // upper half of the context's small device area
+    uint8_t* d_nav = &c->d_small->nav_bits[0][0];
     SGX_HIP(hipMemcpyAsync(d_nav, scene->nav_bits, sizeof(scene->nav_bits), hipMemcpyHostToDevice, c->stream));
     const uint64_t groups = (n + 15) / 16;
     int blocks = (int)((groups + 255) / 256);

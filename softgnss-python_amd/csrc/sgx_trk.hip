@@ -83,7 +83,7 @@ static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
     long long known = r->mag_max.load();
     if (known >= 0) return known;
     if (r->loader && !r->load_done.load() && r->host_mark.load() < r->n) return -1;
-    int* d_max = (int*)((char*)c->d_small + 730000);
+    int* d_max = &c->d_small->trk_mag;
     if (hipMemsetAsync(d_max, 0, sizeof(int), c->stream) != hipSuccess) return -1;
     const long long n_blocks128 = ((long long)r->n + 127) / 128;
     const unsigned grid = (unsigned)((n_blocks128 + 255) / 256);
