@@ -238,6 +238,136 @@ def pre_run(s, acq):
     return dict(PRN=prn, acquiredFreq=freq, codePhase=cph, status=status)
 
 
+ARMS = ("E", "P", "L")                 # early, prompt, late: the three code replicas of tracking.py:166-188
+_FLOAT_ZERO = ("absoluteSample", "I_P", "I_E", "I_L", "Q_E", "Q_P", "Q_L")
+
+
+def flip_direction(t):
+    """Which way the chip index ceil(t) of a sample at code phase t moves when the sample is put on the OTHER side of the
+    chip boundary nearest to it: +1 if t lies just below an integer, -1 if just above.  A sample exactly on a boundary
+    has no other side within rounding (the reference's value there is unambiguous): ValueError."""
+    r = np.round(t)
+    if t == r:
+        raise ValueError("a sample exactly on a chip boundary cannot be flipped")
+    return 1 if t < r else -1
+
+
+class TrackStepper(object):
+    """One channel of track() (tracking.py:107-255), one block per step() call.
+
+    track() below is written on top of it.  It also lets a checker that compares another implementation with the
+    reference tell a rounding tie from a defect: ramps() / eligible() give the code phases of the block about to run (the
+    oracle's own linspace values), step(flips=...) runs that block with named samples on the other side of their nearest
+    chip boundary (everything else, and every later block, in the reference's arithmetic), state() / restore() are the
+    handful of scalars a block hands to the next one.
+    """
+
+    def __init__(self, s, prn, acquired_freq, code_phase, record):
+        self.s = s
+        self.dt = np.dtype(getattr(s, "dataType", "int8"))
+        self.rec = np.ascontiguousarray(record).view(np.uint8).ravel()      # the file's bytes
+        self.t1c, self.t2c = calc_loop_coef(s.dllNoiseBandwidth, s.dllDampingRatio, 1.0)     # tracking.py:45
+        self.t1p, self.t2p = calc_loop_coef(s.pllNoiseBandwidth, s.pllDampingRatio, 0.25)    # tracking.py:52
+        self.pos = int(s.skipNumberOfBytes + code_phase)                # tracking.py:107
+        code = generate_ca_code(int(prn) - 1)
+        self.code = np.r_[code[-1], code, code[0]]                      # tracking.py:111
+        self.code_freq = s.codeFreqBasis
+        self.rem_code = 0.0
+        self.carr_freq = acquired_freq
+        self.carr_basis = acquired_freq
+        self.rem_carr = 0.0
+        self.old_code_nco = self.old_code_err = self.old_carr_nco = self.old_carr_err = 0.0
+        self.block = 0
+
+    _STATE = ("pos", "code_freq", "rem_code", "carr_freq", "rem_carr", "old_code_nco", "old_code_err", "old_carr_nco",
+              "old_carr_err", "block")
+
+    def state(self):
+        """Everything a block hands to the next one (a tuple of scalars); restore() puts it back."""
+        return tuple(getattr(self, k) for k in self._STATE)
+
+    def restore(self, state):
+        for k, v in zip(self._STATE, state):
+            setattr(self, k, v)
+
+    def ramps(self):
+        """(code step per sample, block length, {arm: code phase t_n of every sample}) of the block about to run."""
+        spc_el = self.s.dllCorrelatorSpacing
+        rem_code = self.rem_code
+        step = self.code_freq / self.s.samplingFreq                     # tracking.py:148 (T1)
+        blk = int(np.ceil((self.s.codeLength - rem_code) / step))
+        # tracking.py:166-188 (T3): three linspace ramps
+        te = np.linspace(rem_code - spc_el, blk * step + rem_code - spc_el, blk, endpoint=False)
+        tl = np.linspace(rem_code + spc_el, blk * step + rem_code + spc_el, blk, endpoint=False)
+        tp = np.linspace(rem_code, blk * step + rem_code, blk, endpoint=False)
+        return step, blk, {"E": te, "P": tp, "L": tl}
+
+    def samples(self, blk):
+        """The block's samples, or None on a short read (tracking.py:154-163, T2: whole items)."""
+        isz = self.dt.itemsize
+        chunk = self.rec[self.pos:self.pos + blk * isz].tobytes()
+        raw = np.frombuffer(chunk[:len(chunk) - len(chunk) % isz], dtype=self.dt)
+        return raw if len(raw) == blk else None
+
+    def eligible(self, dist):
+        """[(arm, n, |t_n - round(t_n)|)] of the block about to run with 0 < |t_n - round(t_n)| <= dist, nearest first."""
+        out = []
+        for arm, t in self.ramps()[2].items():
+            d = np.abs(t - np.round(t))
+            out += [(arm, int(n), float(d[n])) for n in np.nonzero((d > 0) & (d <= dist))[0]]
+        return sorted(out, key=lambda e: e[2])
+
+    def step(self, flips=()):
+        """Run one block; -> its 13 values in SERIES order, or None on a short read (nothing changes then).
+        flips: (arm, n) pairs whose chip index is ceil(t_n) moved across the boundary nearest to t_n."""
+        s = self.s
+        pdi = 0.001
+        step, blk, t = self.ramps()
+        raw = self.samples(blk)
+        if raw is None:
+            return None
+        idx = {arm: np.ceil(t[arm]).astype(np.int64) for arm in ARMS}
+        for arm, n in flips:
+            idx[arm][n] += flip_direction(t[arm][n])
+            if not 0 <= idx[arm][n] < len(self.code):
+                raise ValueError("flip beyond the replica's ends")
+        self.pos += blk * self.dt.itemsize
+        early = self.code[idx["E"]]
+        late = self.code[idx["L"]]
+        prompt = self.code[idx["P"]]
+        self.rem_code = t["P"][blk - 1] + step - 1023.0                 # tracking.py:190 (T4)
+        tm = np.arange(0, blk + 1) / s.samplingFreq                     # tracking.py:193 (T5)
+        arg = self.carr_freq * 2.0 * np.pi * tm + self.rem_carr
+        self.rem_carr = arg[blk] % (2 * np.pi)
+        ccos = np.cos(arg[0:blk])
+        csin = np.sin(arg[0:blk])
+        qbb = ccos * raw                                                # tracking.py:205-219 (T6)
+        ibb = csin * raw
+        i_e = (early * ibb).sum()
+        q_e = (early * qbb).sum()
+        i_p = (prompt * ibb).sum()
+        q_p = (prompt * qbb).sum()
+        i_l = (late * ibb).sum()
+        q_l = (late * qbb).sum()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            carr_err = np.arctan(q_p / i_p) / 2.0 / np.pi               # tracking.py:223 (T7)
+        carr_nco = self.old_carr_nco + self.t2p / self.t1p * (carr_err - self.old_carr_err) + carr_err * (pdi / self.t1p)
+        self.old_carr_nco = carr_nco
+        self.old_carr_err = carr_err
+        self.carr_freq = self.carr_basis + carr_nco
+        ee = np.sqrt(i_e * i_e + q_e * q_e)                             # tracking.py:238 (T8)
+        ll = np.sqrt(i_l * i_l + q_l * q_l)
+        code_err = (ee - ll) / (ee + ll)
+        code_nco = self.old_code_nco + self.t2c / self.t1c * (code_err - self.old_code_err) + code_err * (pdi / self.t1c)
+        self.old_code_nco = code_nco
+        self.old_code_err = code_err
+        self.code_freq = s.codeFreqBasis - code_nco
+        self.block += 1
+        # tracking.py:255 (T9) and the series in SERIES order
+        return (self.pos, self.code_freq, self.carr_freq, i_p, i_e, i_l, q_e, q_p, q_l, code_err, code_nco, carr_err,
+                carr_nco)
+
+
 def track(s, channels, record, ms=None):
     """DLL/PLL tracking of every active channel.  Follows tracking.py:35-294.
 
@@ -249,85 +379,20 @@ def track(s, channels, record, ms=None):
     Returns None on a short read (tracking.py:159-163), else a list with one dict per ACTIVE
     channel (Q8) holding PRN, status and the 13 per-ms float64 series.
     """
-    dt = np.dtype(getattr(s, "dataType", "int8"))
-    isz = dt.itemsize
     rec = np.ascontiguousarray(record).view(np.uint8).ravel()      # the file's bytes
     n_ms = int(s.msToProcess if ms is None else ms)
-    spc_el = s.dllCorrelatorSpacing
-    pdi = 0.001
-    t1c, t2c = calc_loop_coef(s.dllNoiseBandwidth, s.dllDampingRatio, 1.0)     # tracking.py:45
-    t1p, t2p = calc_loop_coef(s.pllNoiseBandwidth, s.pllDampingRatio, 0.25)    # tracking.py:52
-    fs = s.samplingFreq
     out = []
     for ch in range(int(s.numberOfChannels)):
         if channels["PRN"][ch] == 0:
             continue
-        ser = {k: (np.zeros(n_ms) if k in ("absoluteSample", "I_P", "I_E", "I_L", "Q_E", "Q_P", "Q_L")
-                   else np.inf * np.ones(n_ms)) for k in SERIES}       # tracking.py:65-94
-        pos = int(s.skipNumberOfBytes + channels["codePhase"][ch])     # tracking.py:107
-        code = generate_ca_code(int(channels["PRN"][ch]) - 1)
-        code = np.r_[code[-1], code, code[0]]                          # tracking.py:111
-        code_freq = s.codeFreqBasis
-        rem_code = 0.0
-        carr_freq = channels["acquiredFreq"][ch]
-        carr_basis = channels["acquiredFreq"][ch]
-        rem_carr = 0.0
-        old_code_nco = old_code_err = old_carr_nco = old_carr_err = 0.0
+        ser = {k: (np.zeros(n_ms) if k in _FLOAT_ZERO else np.inf * np.ones(n_ms)) for k in SERIES}   # tracking.py:65-94
+        st = TrackStepper(s, channels["PRN"][ch], channels["acquiredFreq"][ch], channels["codePhase"][ch], rec)
         for it in range(n_ms):
-            step = code_freq / fs                                       # tracking.py:148 (T1)
-            blk = int(np.ceil((s.codeLength - rem_code) / step))
-            chunk = rec[pos:pos + blk * isz].tobytes()
-            raw = np.frombuffer(chunk[:len(chunk) - len(chunk) % isz], dtype=dt)   # tracking.py:154 (T2): whole items
-            if len(raw) != blk:
+            row = st.step()
+            if row is None:
                 return None
-            pos += blk * isz
-            # tracking.py:166-188 (T3): three linspace ramps, ceil, gather
-            te = np.linspace(rem_code - spc_el, blk * step + rem_code - spc_el, blk, endpoint=False)
-            early = code[np.ceil(te).astype(np.int64)]
-            tl = np.linspace(rem_code + spc_el, blk * step + rem_code + spc_el, blk, endpoint=False)
-            late = code[np.ceil(tl).astype(np.int64)]
-            tp = np.linspace(rem_code, blk * step + rem_code, blk, endpoint=False)
-            prompt = code[np.ceil(tp).astype(np.int64)]
-            rem_code = tp[blk - 1] + step - 1023.0                      # tracking.py:190 (T4)
-            tm = np.arange(0, blk + 1) / fs                             # tracking.py:193 (T5)
-            arg = carr_freq * 2.0 * np.pi * tm + rem_carr
-            rem_carr = arg[blk] % (2 * np.pi)
-            ccos = np.cos(arg[0:blk])
-            csin = np.sin(arg[0:blk])
-            qbb = ccos * raw                                            # tracking.py:205-219 (T6)
-            ibb = csin * raw
-            i_e = (early * ibb).sum()
-            q_e = (early * qbb).sum()
-            i_p = (prompt * ibb).sum()
-            q_p = (prompt * qbb).sum()
-            i_l = (late * ibb).sum()
-            q_l = (late * qbb).sum()
-            with np.errstate(divide="ignore", invalid="ignore"):
-                carr_err = np.arctan(q_p / i_p) / 2.0 / np.pi           # tracking.py:223 (T7)
-            carr_nco = old_carr_nco + t2p / t1p * (carr_err - old_carr_err) + carr_err * (pdi / t1p)
-            old_carr_nco = carr_nco
-            old_carr_err = carr_err
-            carr_freq = carr_basis + carr_nco
-            ee = np.sqrt(i_e * i_e + q_e * q_e)                         # tracking.py:238 (T8)
-            ll = np.sqrt(i_l * i_l + q_l * q_l)
-            code_err = (ee - ll) / (ee + ll)
-            code_nco = old_code_nco + t2c / t1c * (code_err - old_code_err) + code_err * (pdi / t1c)
-            old_code_nco = code_nco
-            old_code_err = code_err
-            code_freq = s.codeFreqBasis - code_nco
-            ser["absoluteSample"][it] = pos                             # tracking.py:255 (T9)
-            ser["codeFreq"][it] = code_freq
-            ser["carrFreq"][it] = carr_freq
-            ser["I_P"][it] = i_p
-            ser["I_E"][it] = i_e
-            ser["I_L"][it] = i_l
-            ser["Q_E"][it] = q_e
-            ser["Q_P"][it] = q_p
-            ser["Q_L"][it] = q_l
-            ser["dllDiscr"][it] = code_err
-            ser["dllDiscrFilt"][it] = code_nco
-            ser["pllDiscr"][it] = carr_err
-            ser["pllDiscrFilt"][it] = carr_nco
+            for k, v in zip(SERIES, row):
+                ser[k][it] = v
         ser["PRN"] = int(channels["PRN"][ch])
         ser["status"] = channels["status"][ch]
         out.append(ser)

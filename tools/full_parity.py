@@ -7,16 +7,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from oracle_helpers import oracle_channel   # (the tests' helper; tests never import from tools/)
-
-
-def random_scene(m, seed):
-    """Eight satellites with random PRNs, Dopplers, code phases and amplitudes (scene seed != the default's)."""
-    rng = np.random.default_rng(seed)
-    prns = sorted(rng.choice(np.arange(1, 33), size=8, replace=False).tolist())
-    return m.synth.Scene.make(0x50AC0000 + seed, 38192000.0, 9548000.0, prns,
-                              [float(rng.uniform(-6500, 6500)) for _ in prns],
-                              [int(rng.integers(0, 38192)) for _ in prns], [int(rng.integers(5, 10)) for _ in prns])
+from oracle_helpers import oracle_channel   # (the tests' helpers; tests never import from tools/)
+from tie_follow import random_scene
 
 
 def main():

@@ -13,39 +13,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 from oracle_helpers import oracle_channel
-from full_parity import random_scene
-
-FS = 38.192e6
-
-
-def rem_at(x, k_end):
-    """remCodePhase at the start of block k_end and the code rate used in it, from a channel's recorded series x[13, ms]
-    (absoluteSample, codeFreq), with the reference's own arithmetic."""
-    pos = np.concatenate([[x[0, 0] - 38192.0], x[0]])
-    rem, cf = 0.0, 1.023e6
-    for k in range(k_end):
-        blk = int(pos[k + 1] - pos[k])
-        step = cf / FS
-        stp = ((blk * step + rem) - rem) / blk
-        rem = ((blk - 1) * stp + rem) + step - 1023.0
-        cf = x[1, k]
-    return rem, cf
-
-
-def nearest_boundary(rem, cf):
-    """min over samples and arms of the distance from a sample's code phase to an integer (a chip boundary of ceil)."""
-    step = cf / FS
-    blk = int(np.ceil((1023.0 - rem) / step))
-    best = (1.0, None, None)
-    for arm, off in (("E", -0.5), ("L", 0.5), ("P", 0.0)):
-        t = np.linspace(rem + off, blk * step + rem + off, blk, endpoint=False)
-        d = np.abs(t - np.round(t))
-        i = int(np.argmin(d))
-        if d[i] < best[0]:
-            best = (float(d[i]), arm, i)
-    return best
+from tie_follow import nearest_boundary, random_scene, rem_at   # (the tests' helpers; tests never import from tools/)
 
 
 def main():
