@@ -313,6 +313,12 @@ int sgx_acquire_plan(int32_t n_prn, int32_t n_bins, int32_t n_blocks, int32_t no
 /* The two constants behind that rule: the default chunk size (rows; SGX_ACQ_CHUNK_ROWS overrides it) and the largest batch
  * of rows one launch takes. */
 int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows);
+/* The transform length the search of sgx_acquire runs on for n_code = samplesPerCode; needs no GPU.  n_code itself where
+ * it factors into 2..31 (every radix the library has).  Any other n_code - the reference takes np.fft.fft of any length
+ * (acquisition.py:120-124) - has its circular correlation computed inside a longer one: *length >= 2 n_code - 1, factors
+ * into 2..31, is at most the next power of two, and is the cheapest such length by the rule csrc/sgx_fft.hip states
+ * (sgx_fft_corr_length).  Results are the reference's either way; a padded search moves about twice the bytes. */
+int sgx_acquire_fft_length(int64_t n_code, int64_t* length);
 
 /* Measured HBM rates of this device for the roofline report (no reference counterpart): a read-only stream and a
  * copy (read + write bytes counted) over `bytes` of device memory, `reps` timed launches each, GB/s. */

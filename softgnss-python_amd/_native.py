@@ -130,6 +130,7 @@ _PROTOS = {
     "sgx_track_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sgx_acquire_plan": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4),
     "sgx_acquire_plan_limits": (C.c_int, [C.POINTER(C.c_int32)] * 2),
+    "sgx_acquire_fft_length": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "sgx_stream_rates": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sgx_probe_stats": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, _P, _P, _P, C.POINTER(C.c_int32)]),
     "sgx_find_preambles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
@@ -241,6 +242,14 @@ def acquire_plan_limits():
     a, b = C.c_int32(0), C.c_int32(0)
     check(lib().sgx_acquire_plan_limits(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def acquire_fft_length(n_code):
+    """The transform length sgx_acquire's search runs on for samplesPerCode = n_code: n_code where it factors into 2..31,
+    else the padded length (>= 2 n_code - 1) its circular correlation is embedded in (include/sgx.h); needs no GPU."""
+    m = C.c_int64(0)
+    check(lib().sgx_acquire_fft_length(int(n_code), C.byref(m)))
+    return m.value
 
 
 def scene_struct(scene):

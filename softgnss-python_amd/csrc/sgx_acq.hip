@@ -11,6 +11,8 @@
 //            second peak over the exclusion list (device)
 //   fine     (x - mean) * code(floor((ts*k)/tc) mod 1023), zero-padded 2^22-point FFT, argmax of |X|
 // HBM-resident scratch replaces the reference's per-PRN numpy temporaries.
+// A samplesPerCode with a prime factor above 31 has no transform of its own length here: its circular correlation runs
+// inside a longer one (acquire_passes, "padded length").
 #include <math.h>
 #include <chrono>
 
@@ -42,8 +44,9 @@ struct MixArgs {
 };
 
 // acquisition.py:62-117: phasePoints[n] = ((n*2)*pi)*ts ; theta = frq*phasePoints ; I = sin*x, Q = cos*x
+// (stride: elements between the rows of `out` - n, or the padded length of a row whose tail the transform takes as zero)
 __global__ __launch_bounds__(256) void acq_mix_kernel(SgxSig x, cplx* __restrict__ out,
-                                                      long long n, double ts, MixArgs a) {
+                                                      long long n, long long stride, double ts, MixArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int k = blockIdx.y % a.n_bins;
@@ -53,20 +56,38 @@ __global__ __launch_bounds__(256) void acq_mix_kernel(SgxSig x, cplx* __restrict
     double s, c;
     sincos(th, &s, &c);
     const double xv = x.at((long long)b * n + i);
-    out[((long long)b * a.n_bins + k) * n + i] = make_double2(s * xv, c * xv);
+    out[((long long)b * a.n_bins + k) * stride + i] = make_double2(s * xv, c * xv);
 }
 
 // initialize.py:210-226 (A3) on the device, same IEEE operations: idx = ceil((ts*k)/tc) - 1
+__device__ __forceinline__ double acq_code_sample(const int8_t* __restrict__ codes, int p, long long i, long long n,
+                                                  double ts, double tc) {
+    int idx = (int)ceil((ts * (double)(i + 1)) / tc) - 1;
+    if (i == n - 1) idx = 1022;
+    idx = idx < 0 ? 0 : (idx > 1022 ? 1022 : idx);
+    return (double)codes[p * 1023 + idx];
+}
 __global__ __launch_bounds__(256) void acq_code_kernel(const int8_t* __restrict__ codes,
                                                        const int* __restrict__ prn0, cplx* __restrict__ out,
                                                        long long n, double ts, double tc) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int p = prn0[blockIdx.y];
-    int idx = (int)ceil((ts * (double)(i + 1)) / tc) - 1;
-    if (i == n - 1) idx = 1022;
-    idx = idx < 0 ? 0 : (idx > 1022 ? 1022 : idx);
-    out[(long long)blockIdx.y * n + i] = make_double2((double)codes[p * 1023 + idx], 0.0);
+    out[(long long)blockIdx.y * n + i] = make_double2(acq_code_sample(codes, p, i, n, ts, tc), 0.0);
+}
+// The code row of a padded correlation, length len >= 2 n - 1: the sampled code at [0, n), its wrap-around copy
+// code[1 .. n - 1] at [len - n + 1, len), zero between them.  Against a signal that is zero from n on, the circular
+// correlation of length len then reads code[(i - k) mod n] for every lag k < n: the length-n circular correlation,
+// term for term.  One launch writes the whole row.
+__global__ __launch_bounds__(256) void acq_code_pad_kernel(const int8_t* __restrict__ codes,
+                                                           const int* __restrict__ prn0, cplx* __restrict__ out,
+                                                           long long n, long long len, double ts, double tc) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= len) return;
+    const int p = prn0[blockIdx.y];
+    const long long j = i < n ? i : i - (len - n);   // (the copy: j = 1 .. n - 1)
+    const double v = (i < n || j >= 1) ? acq_code_sample(codes, p, j, n, ts, tc) : 0.0;
+    out[(long long)blockIdx.y * len + i] = make_double2(v, 0.0);
 }
 
 // rows r = (pi, b, k): Y = conj(X[b][k]) * F[pi]
@@ -87,9 +108,10 @@ __global__ __launch_bounds__(256) void acq_mul_kernel(const cplx* __restrict__ X
 
 // |fft|^2 / N^2 per output row (optionally summed over the blocks: noncoherent extension),
 // plus row max and FIRST argmax (numpy argmax semantics, acquisition.py:139-143).
+// (zs: elements between the rows of Z - n, or the padded length, of which the first n outputs are the correlation)
 __global__ __launch_bounds__(256) void acq_power_kernel(const cplx* __restrict__ Z, double* __restrict__ P,
                                                         double* __restrict__ rowmax, int* __restrict__ rowarg,
-                                                        long long n, double inv_n, int n_bins, int n_blocks,
+                                                        long long n, long long zs, double inv_n, int n_bins, int n_blocks,
                                                         int noncoh) {
     const int ro = blockIdx.x;   // output row
     double best = -1.0;
@@ -101,13 +123,13 @@ __global__ __launch_bounds__(256) void acq_power_kernel(const cplx* __restrict__
             const int pi = ro / n_bins, k = ro % n_bins;
             v = 0.0;
             for (int b = 0; b < n_blocks; ++b) {
-                const cplx z = Z[(((long long)pi * n_blocks + b) * n_bins + k) * n + i];
+                const cplx z = Z[(((long long)pi * n_blocks + b) * n_bins + k) * zs + i];
                 const double re = z.x * inv_n, im = z.y * inv_n;
                 const double pw = re * re + im * im;
                 v = (b == 0) ? pw : v + pw;
             }
         } else {
-            const cplx z = Z[(long long)ro * n + i];
+            const cplx z = Z[(long long)ro * zs + i];
             const double re = z.x * inv_n, im = z.y * inv_n;
             v = re * re + im * im;
         }
@@ -196,6 +218,7 @@ __global__ __launch_bounds__(256) void acq_second_kernel(const double* __restric
 
 // the same on a recomputed complex correlation row: |z|^2 / N^2 formed on the fly, identical arithmetic to
 // the fused last pass, so peak / second peak is a ratio of consistently rounded values
+// (n: elements between the rows of Z; the ranges lie inside the correlation's own length)
 __global__ __launch_bounds__(256) void acq_second_cplx_kernel(const cplx* __restrict__ Z, double* __restrict__ out,
                                                               long long n, double inv_n, const SecondArgs* __restrict__ ap) {
     const SecondArgs& a = *ap;
@@ -447,7 +470,8 @@ __global__ __launch_bounds__(256) void acq_front_kernel(AcqSetup su, SgxSig x, P
 // Direct path of the coherent search: window w of bin k folded as the contract states it (include/sgx.h), every
 // (window, bin) row on its own - the same IEEE operations as acq_mix_kernel, which is the case T = 1:
 //   out[w][k][n] = sum_{m < T} x[(w T + m) n_code + n] (sin + j cos)(frq[k] (((n + m n_code) 2) pi ts))
-__global__ __launch_bounds__(256) void acq_fold_direct_kernel(SgxSig x, cplx* __restrict__ out, long long n, double ts,
+__global__ __launch_bounds__(256) void acq_fold_direct_kernel(SgxSig x, cplx* __restrict__ out, long long n,
+                                                              long long stride, double ts,
                                                               const double* __restrict__ frq, int n_bins, int T) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -463,7 +487,7 @@ __global__ __launch_bounds__(256) void acq_fold_direct_kernel(SgxSig x, cplx* __
         re += sn * xv;
         im += cs * xv;
     }
-    out[(long long)blockIdx.y * n + i] = make_double2(re, im);
+    out[(long long)blockIdx.y * stride + i] = make_double2(re, im);
 }
 
 // Shift path of the coherent search.  With f_k n_code ts = shift_k + phi_k the window's carrier is
@@ -1013,6 +1037,30 @@ extern "C" int sgx_acquire_plan(int32_t n_prn, int32_t n_bins, int32_t n_blocks,
     return SGX_OK;
 }
 
+// PRNs per correlation batch of acquire_passes: whole PRNs, ACQ_MAX_ROWS rows at most - and, on a padded length len > n, no
+// more rows than keep a batch's intermediate at the bytes ACQ_MAX_ROWS rows of the code's own length take (padding at
+// least doubles a row; the batch shrinks instead of the context's two intermediates growing).  A batch is never less than
+// one PRN: where one PRN's rows alone exceed that share (more than about 1 000 blocks x bins, a large coherent grid on
+// the direct path), its intermediate is rows_per_prn padded rows, up to twice those bytes.
+static int acq_passes_chunk(long long n, long long len, int rows_per_prn, int n_prn) {
+    const long long max_rows = len > n ? (long long)ACQ_MAX_ROWS * n / len : ACQ_MAX_ROWS;
+    int chunk = (int)(max_rows / rows_per_prn);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_prn) chunk = n_prn;
+    return chunk;
+}
+
+extern "C" int sgx_acquire_fft_length(int64_t n_code, int64_t* length) {
+    SGX_CHECK_ARG(length);
+    const int64_t len = sgx_fft_corr_length(n_code);
+    if (len == 0) {
+        sgx_set_error("bad argument: %lld samples per code (2 .. 2^29)", (long long)n_code);
+        return SGX_E_ARG;
+    }
+    *length = len;
+    return SGX_OK;
+}
+
 extern "C" int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows) {
     SGX_CHECK_ARG(default_chunk_rows && max_rows);
     *default_chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
@@ -1022,11 +1070,11 @@ extern "C" int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max
 // How the correlation batch is cut: whole PRNs while one PRN's rows fit a chunk (ACQ_DEFAULT_CHUNK_ROWS), else one PRN
 // per batch in runs - of bins for non-coherent sums (rows (bin, window): a run's output rows are whole bins), of windows
 // for the reference rule (rows (window, bin): a run's output rows are whole windows).
-static void coh_plan(CohGrid* g, int n_prn) {
+static void coh_plan(CohGrid* g, int n_prn, long long N) {
     const int chunk = ACQ_DEFAULT_CHUNK_ROWS;
     const int rows_per_prn = g->M * g->n_bins;
-    if (g->path == 0) {   // (acquire_passes: its own chunks of whole PRNs, ACQ_MAX_ROWS rows)
-        g->prn_chunk = ACQ_MAX_ROWS / rows_per_prn;
+    if (g->path == 0) {   // (acquire_passes: its own chunks of whole PRNs)
+        g->prn_chunk = acq_passes_chunk(N, sgx_fft_corr_length(N), rows_per_prn, n_prn);
         g->runs = 1;
         g->per_run = g->noncoh ? g->n_bins : g->M;
     } else if (rows_per_prn <= chunk) {
@@ -1098,7 +1146,7 @@ static int coh_grid(const sgx_settings& S, long long N, const sgx_acq_params* p,
                       nb, ACQ_COH_MAX_BINS);
         return SGX_E_ARG;
     }
-    if (N < 2) {
+    if (sgx_fft_corr_length(N) == 0) {
         sgx_set_error("bad argument: %lld samples per code", N);
         return SGX_E_ARG;
     }
@@ -1115,7 +1163,7 @@ static int coh_grid(const sgx_settings& S, long long N, const sgx_acq_params* p,
                       "%d windows x bins, asked for %d x %d", g->n_phi, N, ACQ_MAX_ROWS, M, g->n_bins);
         return SGX_E_ARG;
     }
-    coh_plan(g, n_prn);
+    coh_plan(g, n_prn, N);
     return SGX_OK;
 }
 
@@ -1546,7 +1594,13 @@ static int acq_fine_and_times(const AcqCall& a, const AcqDets& det, long long* d
 }
 
 // ================================ the three paths ================================
-// The round-1 path: one launch per radix pass, every Doppler bin mixed separately (any factorable samplesPerCode).
+// The round-1 path: one launch per radix pass, every Doppler bin mixed separately (any samplesPerCode).
+// Padded length: N with a prime factor above 31 has no transform here, and the search needs none - it needs the circular
+// correlation of length N.  That one is computed inside a circular correlation of length L = sgx_fft_corr_length(N) >=
+// 2 N - 1: the mixed rows hold the signal at [0, N) and count as zero from there (the first pass reads no further: nothing
+// is filled), the code rows hold the code and its wrap-around copy (acq_code_pad_kernel), and outputs k < N of the length-L
+// correlation are the reference's ifft(fft(x) conj(fft(c)))[k], the same N products each.  Everything below then runs on
+// rows of L elements scaled by 1 / L, and only looks at k < N.  L = N: the path as it always was.
 // g (coherent search, direct path; else null): n_blocks = the windows, each folded from g->T blocks per Doppler bin of g's
 // grid (acq_fold_direct_kernel) in place of the 1-ms mix
 static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohGrid* g = nullptr) {
@@ -1568,17 +1622,21 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     const double tc = 1.0 / S.codeFreqBasis;
     const int spc = (int)llround(S.samplingFreq / S.codeFreqBasis);   // acquisition.py:145
 
-    int rc = sgx_fft_plan_create(&c->plan_code, N);
+    const long long L = sgx_fft_corr_length(N);   // rows and transforms have this length
+    if (L == 0) {
+        sgx_set_error("bad argument: %lld samples per code (2 .. 2^29)", N);
+        return SGX_E_ARG;
+    }
+    const bool padded = L != N;
+    int rc = sgx_fft_plan_create(&c->plan_code, L);
     if (rc != SGX_OK) return rc;
 
     // ---- scratch ------------------------------------------------------------------------------
     const int rows_fwd = n_blocks * n_bins;
     const int rows_per_prn = rows_fwd;
     SGX_CHECK_ARG(rows_per_prn <= ACQ_MAX_ROWS);
-    int prn_chunk = ACQ_MAX_ROWS / rows_per_prn;
-    if (prn_chunk < 1) prn_chunk = 1;
-    if (prn_chunk > n_prn) prn_chunk = n_prn;
-    const size_t row_bytes = sizeof(cplx) * (size_t)N;
+    const int prn_chunk = acq_passes_chunk(N, L, rows_per_prn, n_prn);
+    const size_t row_bytes = sizeof(cplx) * (size_t)L;
     size_t work_rows = (size_t)prn_chunk * rows_per_prn;
     if (work_rows < (size_t)rows_fwd) work_rows = rows_fwd;
     if (work_rows < (size_t)n_prn) work_rows = n_prn;
@@ -1586,16 +1644,19 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_codefd, &c->cap_code, (size_t)n_prn * row_bytes)) != SGX_OK) return rc;
-    const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : (size_t)ACQ_MAX_ROWS * 64 * 12 + 4096;
+    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer: 64 slots for each of
+    // ACQ_MAX_ROWS rows, or - a padded length is chosen for its cost, not for this - what its last pass needs for the
+    // rows of one batch
+    const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
+    SGX_CHECK_ARG(nblk_last <= 64 || padded);
+    const size_t part_slots = padded ? work_rows * (size_t)nblk_last : (size_t)ACQ_MAX_ROWS * 64;
+    const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : part_slots * 12 + 4096;
     if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, pow_need)) != SGX_OK) return rc;
 
     SgxSmall* dsm = c->d_small;
     SgxSmall* hsm = c->h_small;
-    const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
-    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer
     double* d_pmax = c->d_pow;
-    int* d_parg = (int*)(c->d_pow + (size_t)ACQ_MAX_ROWS * 64);
-    SGX_CHECK_ARG(nblk_last <= 64);
+    int* d_parg = (int*)(c->d_pow + part_slots);
     hipEventRecord(c->ev[0], st);
     SGX_HIP(hipMemsetAsync(&dsm->sum, 0, 8, st));
     SGX_HIP(hipMemcpyAsync(dsm->prn, a.prn0, sizeof(int) * (size_t)n_prn, hipMemcpyHostToDevice, st));
@@ -1608,9 +1669,9 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
         if (g) {
             for (int k = 0; k < n_bins; ++k) hsm->frq[k] = g->f0 + g->step * k;
             SGX_HIP(hipMemcpyAsync(dsm->frq, hsm->frq, sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, st));
-            acq_fold_direct_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, dsm->frq, n_bins, g->T);
+            acq_fold_direct_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, L, ts, dsm->frq, n_bins, g->T);
         } else {
-            acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, ts, ma);
+            acq_mix_kernel<<<grid, 256, 0, st>>>(x, c->d_work[0], N, L, ts, ma);
         }
         cplx* res = nullptr;
         rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows_fwd, st, &res, N);
@@ -1619,10 +1680,11 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     }
     // ---- code spectra ---------------------------------------------------------------------------
     {
-        dim3 grid((unsigned)((N + 255) / 256), (unsigned)n_prn);
-        acq_code_kernel<<<grid, 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[0], N, ts, tc);
+        dim3 grid((unsigned)((L + 255) / 256), (unsigned)n_prn);
+        if (padded) acq_code_pad_kernel<<<grid, 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[0], N, L, ts, tc);
+        else acq_code_kernel<<<grid, 256, 0, st>>>(c->d_codes, dsm->prn, c->d_work[0], N, ts, tc);
         cplx* res = nullptr;
-        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], n_prn, st, &res, N);
+        rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], n_prn, st, &res, L);
         if (rc != SGX_OK) return rc;
         SGX_HIP(hipMemcpyAsync(c->d_codefd, res, (size_t)n_prn * row_bytes, hipMemcpyDeviceToDevice, st));
     }
@@ -1631,7 +1693,7 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     AcqDets det;
     int status = SGX_OK;
     acq_reset_outputs(a);
-    const double inv_n = 1.0 / (double)N;
+    const double inv_n = 1.0 / (double)L;
     const int out_per_prn = noncoh ? n_bins : rows_per_prn;
     for (int p0 = 0; p0 < n_prn && status == SGX_OK; p0 += prn_chunk) {
         const int np = (p0 + prn_chunk <= n_prn) ? prn_chunk : (n_prn - p0);
@@ -1640,11 +1702,11 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
         cplx* res = nullptr;
         if (noncoh) {
             // extension path: the blocks' powers are summed per sample, so rows are materialised
-            dim3 grid((unsigned)((N + 255) / 256), (unsigned)rows);
-            acq_mul_kernel<<<grid, 256, 0, st>>>(c->d_fwd, c->d_codefd, c->d_work[0], N, rows_per_prn, p0);
-            rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N);
+            dim3 grid((unsigned)((L + 255) / 256), (unsigned)rows);
+            acq_mul_kernel<<<grid, 256, 0, st>>>(c->d_fwd, c->d_codefd, c->d_work[0], L, rows_per_prn, p0);
+            rc = sgx_fft_forward(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, L);
             if (rc != SGX_OK) return rc;
-            acq_power_kernel<<<rows_out, 256, 0, st>>>(res, c->d_pow, dsm->rowmax, dsm->rowarg, N, inv_n, n_bins, n_blocks, 1);
+            acq_power_kernel<<<rows_out, 256, 0, st>>>(res, c->d_pow, dsm->rowmax, dsm->rowarg, N, L, inv_n, n_bins, n_blocks, 1);
         } else {
             // reference path, fused: conj(X)*F formed in the first radix pass, |.|^2 and the per-workgroup
             // maxima taken in the last one; no product rows, no power rows
@@ -1656,7 +1718,8 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
             fu.pmax = d_pmax;
             fu.parg = d_parg;
             fu.inv_n = inv_n;
-            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, N, &fu);
+            fu.n_valid = padded ? N : 0;
+            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], rows, st, &res, L, &fu);
             if (rc != SGX_OK) return rc;
             acq_rowmax_finish_kernel<<<rows, 64, 0, st>>>(d_pmax, d_parg, nblk_last, dsm->rowmax, dsm->rowarg);
         }
@@ -1699,11 +1762,11 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
             fu.mul_f = c->d_codefd;
             fu.row_map = dsm->row_map;
             cplx* r2 = nullptr;
-            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], np, st, &r2, N, &fu);
+            rc = sgx_fft_forward_fused(&c->plan_code, c->d_work[0], c->d_work[1], np, st, &r2, L, &fu);
             if (rc != SGX_OK) return rc;
             SGX_HIP(hipMemcpyAsync(&dsm->second_args, &sa, sizeof(sa), hipMemcpyHostToDevice, st));
             SGX_HIP(hipMemsetAsync(dsm->second, 0, sizeof(double) * 32, st));
-            acq_second_cplx_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(r2, dsm->second, N, inv_n, &dsm->second_args);
+            acq_second_cplx_kernel<<<dim3((unsigned)np, SEC_SPLIT), 256, 0, st>>>(r2, dsm->second, L, inv_n, &dsm->second_args);
         }
         SGX_HIP(hipMemcpyAsync(hsm->second, dsm->second, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, st));
         SGX_HIP(hipStreamSynchronize(st));

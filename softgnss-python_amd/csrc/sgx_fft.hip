@@ -57,6 +57,8 @@ struct PassArgs {
     double* pmax;           // [rows][gridDim.x]
     int* parg;
     double inv_n;
+    // MODE 3: MODE 2 over the outputs below n_valid only (a correlation on a padded length: the rest is not the caller's)
+    long long n_valid;
 };
 
 __device__ __forceinline__ cplx twiddle(const PassArgs& a, long long t) {
@@ -169,14 +171,16 @@ __device__ __forceinline__ void dft_small(cplx (&v)[R], const cplx* __restrict__
 
 // MODE 0: plain pass.  MODE 1: first pass of the correlation batch, the pointwise product conj(X) * F is formed
 // on load (no separate multiply kernel, no product buffer).  MODE 2: last pass of the correlation batch, the
-// outputs are squared, scaled and max-reduced in place (no output rows, no separate power kernel).
+// outputs are squared, scaled and max-reduced in place (no output rows, no separate power kernel).  MODE 3: MODE 2 that
+// looks at the outputs k < n_valid only.
 template <int R, int TPB, int MODE>
 __global__ __launch_bounds__(TPB) void fft_pass_kernel(PassArgs a) {
     const long long m = a.n / R;
     const long long j = (long long)blockIdx.x * TPB + threadIdx.x;
     const long long row = blockIdx.y;
     const bool live = j < m;
-    if (MODE != 2 && !live) return;
+    constexpr bool kReduce = MODE == 2 || MODE == 3;
+    if (!kReduce && !live) return;
     const cplx* __restrict__ in = a.in + row * a.n;
     cplx* __restrict__ out = a.out + row * a.n;
     const long long k = j % a.ns;
@@ -218,7 +222,7 @@ __global__ __launch_bounds__(TPB) void fft_pass_kernel(PassArgs a) {
     }
     const long long j0 = (j / a.ns) * a.ns * R + k;
     constexpr bool kEmit = (R % 2 == 1) && (R >= 11);   // large odd radix: consume outputs as they are produced
-    if (MODE == 2) {
+    if (kReduce) {
         // acquisition.py:124-126 abs(ifft(.))**2 for this thread's outputs, then (max, FIRST index)
         double best = -1.0;
         int arg = 0;
@@ -226,6 +230,7 @@ __global__ __launch_bounds__(TPB) void fft_pass_kernel(PassArgs a) {
             const double re = V.x * a.inv_n, im = V.y * a.inv_n;
             const double pw = re * re + im * im;
             const int idx = (int)(j0 + q * a.ns);
+            if (MODE == 3 && idx >= a.n_valid) return;
             if (pw > best || (pw == best && idx < arg)) {
                 best = pw;
                 arg = idx;
@@ -298,6 +303,72 @@ static int ensure_roots(int R) {
     return SGX_OK;
 }
 
+// The radix passes of a length, in the order they run (16, 8, 4, 2, then the odd ones ascending); false where n has a
+// prime factor above 31.
+static bool fft_factor(int64_t n, std::vector<int>* radices) {
+    int64_t rem = n;
+    radices->clear();
+    std::vector<int> odd;
+    for (int r : kRadixList) {
+        while (rem % r == 0) {
+            if (r % 2 == 0)
+                radices->push_back(r);
+            else
+                odd.push_back(r);
+            rem /= r;
+        }
+    }
+    for (int r : odd) radices->push_back(r);
+    return rem == 1;
+}
+
+// ---- the length a circular correlation of n points is computed on ---------------------------------------------------
+// n itself where it factors into 2..31.  Otherwise the correlation is embedded in a longer one (sgx_acq.hip, acquire_passes:
+// signal zero-padded, code with its wrap-around copy at the row's end), which any length L >= 2 n - 1 takes; L is the
+// cheapest 2..31-smooth one up to the next power of two.  Cost of a length = L x the sum of its passes' weights: every
+// pass moves the row through memory once, which is what a pass of radix 2..8 or 16 costs (weight 1); the odd radices from
+// 11 on are direct DFTs of (R - 1)^2 / 2 multiply-adds per butterfly and weigh 1 + (R - 8) / 24 (radix 31: two passes).
+// Powers of two run as ceil(log2 / 4) passes (16 first).  Equal cost: the shorter length.  0: n out of range.
+static double fft_pass_weight(int r) { return (r <= 8 || r == 16) ? 1.0 : 1.0 + (double)(r - 8) / 24.0; }
+static double fft_length_cost(int64_t len) {
+    std::vector<int> rad;
+    if (!fft_factor(len, &rad)) return -1.0;
+    double w = 0.0;
+    for (int r : rad) w += fft_pass_weight(r);
+    return (double)len * w;
+}
+static void fft_smooth_search(int64_t v, int first, int64_t lo, int64_t hi, int64_t* best, double* best_cost) {
+    static const int kPrimes[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31};
+    if (v >= lo) {
+        const double cost = fft_length_cost(v);
+        if (cost < *best_cost || (cost == *best_cost && v < *best)) {
+            *best = v;
+            *best_cost = cost;
+        }
+    }
+    for (int i = first; i < 11; ++i) {
+        if (v * kPrimes[i] > hi) break;
+        fft_smooth_search(v * kPrimes[i], i, lo, hi, best, best_cost);
+    }
+}
+int64_t sgx_fft_corr_length(int64_t n) {
+    if (n < 2 || n > (1ll << 29)) return 0;   // (2 n - 1 rounded up to a power of two stays an int index)
+    std::vector<int> rad;
+    if (fft_factor(n, &rad)) return n;
+    // (every call of a context asks for the same n, and the search below visits every smooth number up to `hi`)
+    static thread_local int64_t last_n = 0, last_len = 0;
+    if (last_n == n) return last_len;
+    const int64_t lo = 2 * n - 1;
+    int64_t hi = 1;
+    while (hi < lo) hi <<= 1;
+    int64_t best = hi;
+    double best_cost = fft_length_cost(hi);
+    fft_smooth_search(1, 0, lo, hi, &best, &best_cost);
+    last_n = n;
+    last_len = best;
+    return best;
+}
+
 int sgx_fft_plan_create(FftPlan* p, int64_t n) {
     if (p->n == n && p->tw_hi) return SGX_OK;
     sgx_fft_plan_destroy(p);
@@ -305,24 +376,12 @@ int sgx_fft_plan_create(FftPlan* p, int64_t n) {
         sgx_set_error("FFT length %lld not supported", (long long)n);
         return SGX_E_ARG;
     }
-    int64_t rem = n;
-    p->radices.clear();
-    std::vector<int> odd;
-    for (int r : kRadixList) {
-        while (rem % r == 0) {
-            if (r % 2 == 0)
-                p->radices.push_back(r);
-            else
-                odd.push_back(r);
-            rem /= r;
-        }
-    }
-    if (rem != 1) {
-        sgx_set_error("FFT length %lld has a prime factor above 31 (samplesPerCode must factor into 2..31)",
+    if (!fft_factor(n, &p->radices)) {
+        p->radices.clear();
+        sgx_set_error("FFT length %lld has a prime factor above 31 (a transform length must factor into 2..31)",
                       (long long)n);
         return SGX_E_ARG;
     }
-    for (int r : odd) p->radices.push_back(r);
     for (int r : p->radices) {
         int rc = ensure_roots(r);
         if (rc != SGX_OK) return rc;
@@ -364,6 +423,8 @@ static void launch_pass(const PassArgs& a, int64_t rows, hipStream_t st, int mod
         fft_pass_kernel<R, TPB, 1><<<grid, TPB, 0, st>>>(a);
     else if (mode == 2)
         fft_pass_kernel<R, TPB, 2><<<grid, TPB, 0, st>>>(a);
+    else if (mode == 3)
+        fft_pass_kernel<R, TPB, 3><<<grid, TPB, 0, st>>>(a);
     else
         fft_pass_kernel<R, TPB, 0><<<grid, TPB, 0, st>>>(a);
 }
@@ -406,6 +467,7 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
         pa.pmax = nullptr;
         pa.parg = nullptr;
         pa.inv_n = 0.0;
+        pa.n_valid = p->n;
         if (fuse && first && fuse->mul_x) {
             mode = 1;
             pa.mul_x = fuse->mul_x;
@@ -419,10 +481,11 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
                 sgx_set_error("single-pass FFT cannot fuse both ends");
                 return SGX_E_ARG;
             }
-            mode = 2;
+            mode = (fuse->n_valid > 0 && fuse->n_valid < p->n) ? 3 : 2;
             pa.pmax = fuse->pmax;
             pa.parg = fuse->parg;
             pa.inv_n = fuse->inv_n;
+            if (mode == 3) pa.n_valid = fuse->n_valid;
         }
         pa.in = src;
         pa.out = dst;

@@ -270,6 +270,9 @@ int64_t sgx_host_samples_per_code(const sgx_settings* s);
 
 // sgx_fft.hip
 int sgx_fft_plan_create(FftPlan* p, int64_t n);
+// The length a circular correlation of n points runs on: n where it factors into 2..31, else a padded length >= 2 n - 1
+// that does (sgx_fft.hip states the rule); 0 where n is out of range.  Host arithmetic only.
+int64_t sgx_fft_corr_length(int64_t n);
 void sgx_fft_plan_destroy(FftPlan* p);
 // Forward DFT of `rows` contiguous rows of length p->n. Result lands in *result (a or b).
 int sgx_fft_forward(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipStream_t st, cplx** result,
@@ -285,6 +288,7 @@ struct FftFuse {
     double* pmax = nullptr;        // last pass: per-workgroup (max, first index) of |.|^2 * inv_n^2
     int* parg = nullptr;
     double inv_n = 0.0;
+    int64_t n_valid = 0;           // last pass: only outputs k < n_valid count (0: all of them)
 };
 int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipStream_t st, cplx** result,
                           int64_t nonzero_len, const FftFuse* fuse);
