@@ -319,6 +319,26 @@ int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows);
  * into 2..31, is at most the next power of two, and is the cheapest such length by the rule csrc/sgx_fft.hip states
  * (sgx_fft_corr_length).  Results are the reference's either way; a padded search moves about twice the bytes. */
 int sgx_acquire_fft_length(int64_t n_code, int64_t* length);
+/* The radix passes that transform runs as (csrc/sgx_fft.hip), for the tests of the pass kernels; needs no GPU.
+ * *length as sgx_acquire_fft_length gives it; radices_out[i] and tpb_out[i], i < *n_passes <= SGX_FFT_MAX_PASSES: the
+ * radix and the workgroup width of pass i in the order the passes run; *last_pass_blocks: workgroups per row of the last
+ * pass, each leaving one partial maximum where that pass is fused with the peak search. */
+#define SGX_FFT_MAX_PASSES 32
+int sgx_acquire_fft_passes(int64_t n_code, int32_t* radices_out, int32_t* n_passes, int64_t* length,
+                           int32_t* last_pass_blocks, int32_t* tpb_out);
+/* Diagnostics for the transform tests: the radix-pass kernels of the search on the caller's rows, through the plan and the
+ * pass loop sgx_acquire uses (a length that does not factor into 2..31 is refused as there).  Host pointers, complex128 as
+ * (re, im) pairs, rows of n elements; rows <= 4096, n <= 2^24.
+ *   plain (mul_x null): out_rows[rows][n] = DFT of in[rows][n], the input taken as zero from element nonzero_len on
+ *     (1 <= nonzero_len <= n);
+ *   fused (mul_x[n_x][n], mul_f[n_f][n], in null): row r is the DFT of conj(mul_x[b]) * mul_f[p], formed in the first
+ *     pass, with (b, p) = (row_map[2 r], row_map[2 r + 1]) or, row_map null, (r % rows_per_prn, prn_base + r / rows_per_prn).
+ *     out_max / out_arg given: the last pass squares, scales by 1 / n^2 and max-reduces; out_max[r] is the largest power
+ *     among the outputs k < n_valid (0 or n: all of them) and out_arg[r] its first index.  out_rows given instead: the
+ *     rows themselves (the route the second-peak search takes).  A one-pass length cannot fuse both ends. */
+int sgx_fft_run_passes(sgx_ctx* c, int64_t n, int32_t rows, const double* in, int64_t nonzero_len, const double* mul_x,
+                       int32_t n_x, const double* mul_f, int32_t n_f, int32_t rows_per_prn, int32_t prn_base,
+                       const int32_t* row_map, int64_t n_valid, double* out_rows, double* out_max, int32_t* out_arg);
 
 /* Measured HBM rates of this device for the roofline report (no reference counterpart): a read-only stream and a
  * copy (read + write bytes counted) over `bytes` of device memory, `reps` timed launches each, GB/s. */

@@ -131,6 +131,10 @@ _PROTOS = {
     "sgx_acquire_plan": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4),
     "sgx_acquire_plan_limits": (C.c_int, [C.POINTER(C.c_int32)] * 2),
     "sgx_acquire_fft_length": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "sgx_acquire_fft_passes": (C.c_int, [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sgx_fft_run_passes": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int32,
+                                     C.c_int32, _P, C.c_int64, _P, _P, _P]),
     "sgx_stream_rates": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sgx_probe_stats": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, _P, _P, _P, C.POINTER(C.c_int32)]),
     "sgx_find_preambles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
@@ -250,6 +254,58 @@ def acquire_fft_length(n_code):
     m = C.c_int64(0)
     check(lib().sgx_acquire_fft_length(int(n_code), C.byref(m)))
     return m.value
+
+
+FFT_MAX_PASSES = 32
+
+
+def acquire_fft_passes(n_code):
+    """The radix passes sgx_acquire's search runs for samplesPerCode = n_code (include/sgx.h); needs no GPU.  Returns
+    dict(length, radices, tpb (workgroup width per pass), last_pass_blocks)."""
+    rad, tpb = (C.c_int32 * FFT_MAX_PASSES)(), (C.c_int32 * FFT_MAX_PASSES)()
+    k, blocks, length = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(lib().sgx_acquire_fft_passes(int(n_code), rad, C.byref(k), C.byref(length), C.byref(blocks), tpb))
+    return dict(length=length.value, radices=list(rad[:k.value]), tpb=list(tpb[:k.value]), last_pass_blocks=blocks.value)
+
+
+def _c128(a, n):
+    a = np.ascontiguousarray(a, dtype=np.complex128)
+    if a.ndim != 2 or a.shape[1] != n:
+        raise ValueError("rows of %d complex128 expected, got shape %s" % (n, a.shape))
+    return a
+
+
+def fft_forward(ctx, rows, nonzero_len=None):
+    """DFT of every row of `rows` [rows][n] by the radix-pass kernels (sgx_fft_run_passes, plain form), the input taken
+    as zero from element nonzero_len on.  ctx: a device context handle."""
+    x = _c128(rows, np.shape(rows)[1])
+    n = x.shape[1]
+    out = np.empty_like(x)
+    check(lib().sgx_fft_run_passes(ctx, n, x.shape[0], x.ctypes.data, n if nonzero_len is None else int(nonzero_len),
+                                   None, 0, None, 0, 1, 0, None, 0, out.ctypes.data, None, None))
+    return out
+
+
+def fft_fused(ctx, mul_x, mul_f, rows, rows_per_prn=1, prn_base=0, row_map=None, n_valid=0, want_rows=False):
+    """The fused correlation passes on spectra mul_x [n_x][n] and mul_f [n_f][n] (sgx_fft_run_passes, fused form): row r
+    transforms conj(mul_x[b]) * mul_f[p], (b, p) from row_map [rows][2] or the regular layout.  Returns (max, arg) per
+    row over the outputs below n_valid (0: all), or the rows themselves with want_rows."""
+    n = np.shape(mul_x)[1]
+    x, f = _c128(mul_x, n), _c128(mul_f, n)
+    rm = None
+    if row_map is not None:
+        rm = np.ascontiguousarray(row_map, dtype=np.int32)
+        if rm.shape != (int(rows), 2):
+            raise ValueError("row_map of shape (%d, 2) expected" % int(rows))
+    args = (ctx, n, int(rows), None, n, x.ctypes.data, x.shape[0], f.ctypes.data, f.shape[0], int(rows_per_prn),
+            int(prn_base), None if rm is None else rm.ctypes.data, int(n_valid))
+    if want_rows:
+        out = np.empty((int(rows), n), dtype=np.complex128)
+        check(lib().sgx_fft_run_passes(*args, out.ctypes.data, None, None))
+        return out
+    mx, arg = np.empty(int(rows), dtype=np.float64), np.empty(int(rows), dtype=np.int32)
+    check(lib().sgx_fft_run_passes(*args, None, mx.ctypes.data, arg.ctypes.data))
+    return mx, arg
 
 
 def scene_struct(scene):
@@ -438,6 +494,14 @@ class Context(object):
         r, w = C.c_double(0), C.c_double(0)
         check(lib().sgx_stream_rates(self._h, int(nbytes), int(reps), C.byref(r), C.byref(w)))
         return r.value, w.value
+
+    def fft_forward(self, rows, nonzero_len=None):
+        """The module-level fft_forward on this context's device."""
+        return fft_forward(self._h, rows, nonzero_len)
+
+    def fft_fused(self, mul_x, mul_f, rows, **kw):
+        """The module-level fft_fused on this context's device."""
+        return fft_fused(self._h, mul_x, mul_f, rows, **kw)
 
     # ---- records ----
     def upload(self, samples):

@@ -1061,6 +1061,143 @@ extern "C" int sgx_acquire_fft_length(int64_t n_code, int64_t* length) {
     return SGX_OK;
 }
 
+extern "C" int sgx_acquire_fft_passes(int64_t n_code, int32_t* radices_out, int32_t* n_passes, int64_t* length,
+                                      int32_t* last_pass_blocks, int32_t* tpb_out) {
+    SGX_CHECK_ARG(radices_out && n_passes && length && last_pass_blocks && tpb_out);
+    const int64_t len = sgx_fft_corr_length(n_code);
+    if (len == 0) {
+        sgx_set_error("bad argument: %lld samples per code (2 .. 2^29)", (long long)n_code);
+        return SGX_E_ARG;
+    }
+    FftPlan p;   // (host fields only: no tables, nothing to destroy)
+    std::vector<int> tpb;
+    if (!sgx_fft_pass_list(len, &p.radices, &tpb) || p.radices.size() > SGX_FFT_MAX_PASSES) {
+        sgx_set_error("no pass list for length %lld", (long long)len);
+        return SGX_E_ARG;
+    }
+    p.n = len;
+    for (size_t i = 0; i < p.radices.size(); ++i) {
+        radices_out[i] = p.radices[i];
+        tpb_out[i] = tpb[i];
+    }
+    *n_passes = (int32_t)p.radices.size();
+    *length = len;
+    *last_pass_blocks = sgx_fft_last_pass_blocks(&p);
+    return SGX_OK;
+}
+
+// The radix passes on caller data (include/sgx.h): the tests' way to the kernels behind sgx_fft_forward_fused, through the
+// plan and the pass loop the search uses.  Everything is allocated and freed here; the context lends device and stream.
+namespace {
+struct ProbeBufs {
+    static constexpr int kMax = 12;   // (the fused form with a row map and maxima takes nine)
+    void* p[kMax] = {nullptr};
+    int n = 0;
+    ~ProbeBufs() {
+        for (int i = 0; i < n; ++i) hipFree(p[i]);
+    }
+    int get(void** out, size_t bytes) {
+        *out = nullptr;
+        if (n >= kMax) {
+            sgx_set_error("sgx_fft_run_passes: more than %d buffers", kMax);
+            return SGX_E_NOMEM;
+        }
+        hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) {
+            sgx_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+            return SGX_E_NOMEM;
+        }
+        p[n++] = *out;
+        return SGX_OK;
+    }
+};
+struct ProbePlan {
+    FftPlan plan;
+    ~ProbePlan() { sgx_fft_plan_destroy(&plan); }
+};
+}   // namespace
+
+extern "C" int sgx_fft_run_passes(sgx_ctx* c, int64_t n, int32_t rows, const double* in, int64_t nonzero_len,
+                                  const double* mul_x, int32_t n_x, const double* mul_f, int32_t n_f, int32_t rows_per_prn,
+                                  int32_t prn_base, const int32_t* row_map, int64_t n_valid, double* out_rows,
+                                  double* out_max, int32_t* out_arg) {
+    SGX_CHECK_ARG(c && n >= 2 && n <= (1ll << 24) && rows >= 1 && rows <= 4096);
+    const bool fused = mul_x != nullptr;
+    if (fused) {
+        SGX_CHECK_ARG(mul_f && !in && n_x >= 1 && n_x <= 4096 && n_f >= 1 && n_f <= 4096 && n_valid >= 0 && n_valid <= n);
+        SGX_CHECK_ARG((out_max != nullptr) == (out_arg != nullptr) && (out_max != nullptr) != (out_rows != nullptr));
+        if (row_map) {
+            for (int r = 0; r < rows; ++r)
+                SGX_CHECK_ARG(row_map[2 * r] >= 0 && row_map[2 * r] < n_x && row_map[2 * r + 1] >= 0 && row_map[2 * r + 1] < n_f);
+        } else {
+            SGX_CHECK_ARG(rows_per_prn >= 1 && rows_per_prn <= n_x && prn_base >= 0 &&
+                          prn_base + (rows - 1) / rows_per_prn < n_f);
+        }
+    } else {
+        SGX_CHECK_ARG(in && out_rows && !mul_f && !out_max && !out_arg && nonzero_len >= 1 && nonzero_len <= n);
+    }
+    SGX_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    ProbePlan pp;
+    int rc = sgx_fft_plan_create(&pp.plan, n);   // (refuses what the search's plan refuses)
+    if (rc != SGX_OK) return rc;
+    const size_t row_bytes = sizeof(cplx) * (size_t)n;
+    ProbeBufs bufs;
+    cplx *wa = nullptr, *wb = nullptr, *res = nullptr;
+    if ((rc = bufs.get((void**)&wa, (size_t)rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = bufs.get((void**)&wb, (size_t)rows * row_bytes)) != SGX_OK) return rc;
+    if (!fused) {
+        SGX_HIP(hipMemcpyAsync(wa, in, (size_t)rows * row_bytes, hipMemcpyHostToDevice, st));
+        rc = sgx_fft_forward(&pp.plan, wa, wb, rows, st, &res, nonzero_len);
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipMemcpyAsync(out_rows, res, (size_t)rows * row_bytes, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipStreamSynchronize(st));
+        return SGX_OK;
+    }
+    cplx *dx = nullptr, *df = nullptr;
+    if ((rc = bufs.get((void**)&dx, (size_t)n_x * row_bytes)) != SGX_OK) return rc;
+    if ((rc = bufs.get((void**)&df, (size_t)n_f * row_bytes)) != SGX_OK) return rc;
+    SGX_HIP(hipMemcpyAsync(dx, mul_x, (size_t)n_x * row_bytes, hipMemcpyHostToDevice, st));
+    SGX_HIP(hipMemcpyAsync(df, mul_f, (size_t)n_f * row_bytes, hipMemcpyHostToDevice, st));
+    FftFuse fu;
+    fu.mul_x = dx;
+    fu.mul_f = df;
+    fu.rows_per_prn = row_map ? 1 : rows_per_prn;
+    fu.prn_base = row_map ? 0 : prn_base;
+    if (row_map) {
+        int2* dm = nullptr;
+        if ((rc = bufs.get((void**)&dm, sizeof(int2) * (size_t)rows)) != SGX_OK) return rc;
+        SGX_HIP(hipMemcpyAsync(dm, row_map, sizeof(int2) * (size_t)rows, hipMemcpyHostToDevice, st));
+        fu.row_map = dm;
+    }
+    if (out_rows) {
+        rc = sgx_fft_forward_fused(&pp.plan, wa, wb, rows, st, &res, n, &fu);
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipMemcpyAsync(out_rows, res, (size_t)rows * row_bytes, hipMemcpyDeviceToHost, st));
+        SGX_HIP(hipStreamSynchronize(st));
+        return SGX_OK;
+    }
+    const int nblk = sgx_fft_last_pass_blocks(&pp.plan);
+    double *d_pmax = nullptr, *d_max = nullptr;
+    int *d_parg = nullptr, *d_arg = nullptr;
+    if ((rc = bufs.get((void**)&d_pmax, sizeof(double) * (size_t)rows * (size_t)nblk)) != SGX_OK) return rc;
+    if ((rc = bufs.get((void**)&d_parg, sizeof(int) * (size_t)rows * (size_t)nblk)) != SGX_OK) return rc;
+    if ((rc = bufs.get((void**)&d_max, sizeof(double) * (size_t)rows)) != SGX_OK) return rc;
+    if ((rc = bufs.get((void**)&d_arg, sizeof(int) * (size_t)rows)) != SGX_OK) return rc;
+    fu.pmax = d_pmax;
+    fu.parg = d_parg;
+    fu.inv_n = 1.0 / (double)n;
+    fu.n_valid = n_valid;
+    rc = sgx_fft_forward_fused(&pp.plan, wa, wb, rows, st, &res, n, &fu);
+    if (rc != SGX_OK) return rc;
+    acq_rowmax_finish_kernel<<<rows, 64, 0, st>>>(d_pmax, d_parg, nblk, d_max, d_arg);
+    SGX_HIP(hipGetLastError());
+    SGX_HIP(hipMemcpyAsync(out_max, d_max, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, st));
+    SGX_HIP(hipMemcpyAsync(out_arg, d_arg, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, st));
+    SGX_HIP(hipStreamSynchronize(st));
+    return SGX_OK;
+}
+
 extern "C" int sgx_acquire_plan_limits(int32_t* default_chunk_rows, int32_t* max_rows) {
     SGX_CHECK_ARG(default_chunk_rows && max_rows);
     *default_chunk_rows = ACQ_DEFAULT_CHUNK_ROWS;
@@ -1644,12 +1781,10 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
     if ((rc = ensure_buf((void**)&c->d_codefd, &c->cap_code, (size_t)n_prn * row_bytes)) != SGX_OK) return rc;
-    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer: 64 slots for each of
-    // ACQ_MAX_ROWS rows, or - a padded length is chosen for its cost, not for this - what its last pass needs for the
-    // rows of one batch
+    // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer: what the plan's last pass
+    // writes for the rows of one batch, whatever the length (acq_rowmax_finish_kernel strides over any number of them)
     const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
-    SGX_CHECK_ARG(nblk_last <= 64 || padded);
-    const size_t part_slots = padded ? work_rows * (size_t)nblk_last : (size_t)ACQ_MAX_ROWS * 64;
+    const size_t part_slots = work_rows * (size_t)nblk_last;
     const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : part_slots * 12 + 4096;
     if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, pow_need)) != SGX_OK) return rc;
 

@@ -415,6 +415,9 @@ void sgx_fft_plan_destroy(FftPlan* p) {
     p->radices.clear();
 }
 
+// workgroup width of a radix's pass kernels (every MODE)
+static constexpr int fft_pass_tpb(int r) { return (r == 16 || (r >= 11 && r <= 19)) ? 128 : (r >= 23 ? 64 : 256); }
+
 template <int R, int TPB>
 static void launch_pass(const PassArgs& a, int64_t rows, hipStream_t st, int mode) {
     const long long m = a.n / R;
@@ -431,9 +434,16 @@ static void launch_pass(const PassArgs& a, int64_t rows, hipStream_t st, int mod
 
 int sgx_fft_last_pass_blocks(const FftPlan* p) {
     const int r = p->radices.back();
-    const int tpb = (r == 16 || (r >= 11 && r <= 19)) ? 128 : (r >= 23 ? 64 : 256);
+    const int tpb = fft_pass_tpb(r);
     const long long m = p->n / r;
     return (int)((m + tpb - 1) / tpb);
+}
+
+bool sgx_fft_pass_list(int64_t n, std::vector<int>* radices, std::vector<int>* tpb) {
+    if (n < 2 || !fft_factor(n, radices)) return false;
+    tpb->clear();
+    for (int r : *radices) tpb->push_back(fft_pass_tpb(r));
+    return true;
 }
 
 int sgx_fft_forward(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipStream_t st, cplx** result,
@@ -497,20 +507,20 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
         pa.nonzero_len = first ? nonzero_len : p->n;
         pa.lo_bits = p->lo_bits;
         switch (r) {
-            case 16: launch_pass<16, 128>(pa, rows, st, mode); break;
-            case 8: launch_pass<8, 256>(pa, rows, st, mode); break;
-            case 4: launch_pass<4, 256>(pa, rows, st, mode); break;
-            case 2: launch_pass<2, 256>(pa, rows, st, mode); break;
-            case 3: launch_pass<3, 256>(pa, rows, st, mode); break;
-            case 5: launch_pass<5, 256>(pa, rows, st, mode); break;
-            case 7: launch_pass<7, 256>(pa, rows, st, mode); break;
-            case 11: launch_pass<11, 128>(pa, rows, st, mode); break;
-            case 13: launch_pass<13, 128>(pa, rows, st, mode); break;
-            case 17: launch_pass<17, 128>(pa, rows, st, mode); break;
-            case 19: launch_pass<19, 128>(pa, rows, st, mode); break;
-            case 23: launch_pass<23, 64>(pa, rows, st, mode); break;
-            case 29: launch_pass<29, 64>(pa, rows, st, mode); break;
-            case 31: launch_pass<31, 64>(pa, rows, st, mode); break;
+            case 16: launch_pass<16, fft_pass_tpb(16)>(pa, rows, st, mode); break;
+            case 8: launch_pass<8, fft_pass_tpb(8)>(pa, rows, st, mode); break;
+            case 4: launch_pass<4, fft_pass_tpb(4)>(pa, rows, st, mode); break;
+            case 2: launch_pass<2, fft_pass_tpb(2)>(pa, rows, st, mode); break;
+            case 3: launch_pass<3, fft_pass_tpb(3)>(pa, rows, st, mode); break;
+            case 5: launch_pass<5, fft_pass_tpb(5)>(pa, rows, st, mode); break;
+            case 7: launch_pass<7, fft_pass_tpb(7)>(pa, rows, st, mode); break;
+            case 11: launch_pass<11, fft_pass_tpb(11)>(pa, rows, st, mode); break;
+            case 13: launch_pass<13, fft_pass_tpb(13)>(pa, rows, st, mode); break;
+            case 17: launch_pass<17, fft_pass_tpb(17)>(pa, rows, st, mode); break;
+            case 19: launch_pass<19, fft_pass_tpb(19)>(pa, rows, st, mode); break;
+            case 23: launch_pass<23, fft_pass_tpb(23)>(pa, rows, st, mode); break;
+            case 29: launch_pass<29, fft_pass_tpb(29)>(pa, rows, st, mode); break;
+            case 31: launch_pass<31, fft_pass_tpb(31)>(pa, rows, st, mode); break;
             default:
                 sgx_set_error("radix %d not instantiated", r);
                 return SGX_E_ARG;

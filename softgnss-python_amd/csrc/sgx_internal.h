@@ -293,6 +293,9 @@ struct FftFuse {
 int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipStream_t st, cplx** result,
                           int64_t nonzero_len, const FftFuse* fuse);
 int sgx_fft_last_pass_blocks(const FftPlan* p);
+// The radix passes sgx_fft_plan_create would set up for length n, in the order they run, and each pass's workgroup width;
+// false where n does not factor into 2..31.  Host arithmetic only.
+bool sgx_fft_pass_list(int64_t n, std::vector<int>* radices, std::vector<int>* tpb);
 
 // Four-step transform with LDS-resident sub-transforms (sgx_fft.hip), for the lengths it is instantiated for.
 struct Fft4Fuse {

@@ -125,12 +125,14 @@ def search_cases():
     return out
 
 
-def conditioned(s, x, n_blocks, noncoh):
+def conditioned(s, x, n_blocks, noncoh, prns=None):
     """spec.acquire (the 1-ms grid: oracle.acquire's search) with what decides every arg-max.  Returns (outputs, smallest
-    relative gap over the bin, sample and fine arg-maxes of every searched PRN, closest |peakMetric / threshold - 1|)."""
-    w = spec.acquire(s, x, 1, n_blocks, noncoh, 500.0, prn_indices=[p - 1 for p in PRNS], details=True)
+    relative gap over the bin, sample and fine arg-maxes of every searched PRN, closest |peakMetric / threshold - 1|).
+    prns: the searched PRNs (default: PRNS)."""
+    prns = PRNS if prns is None else prns
+    w = spec.acquire(s, x, 1, n_blocks, noncoh, 500.0, prn_indices=[p - 1 for p in prns], details=True)
     gaps, room = [], []
-    for p in (q - 1 for q in PRNS):
+    for p in (q - 1 for q in prns):
         d = w["details"][p]
         gaps += [spec.rel_gap(d["bins"]), spec.rel_gap(d["samples"])]
         if d["fine"] is not None:
