@@ -945,9 +945,7 @@ __device__ __forceinline__ void wg_argmax(double& best, int& arg, double* __rest
 // 27 LDS accesses per thread, 21 KB of LDS.  The round-2 kernel staged the tile through LDS and ran Stockham passes on it:
 // 84 LDS accesses per thread, the radix-16 pass writing with a stride of 16 elements - the counters showed the LDS pipe
 // busy for the whole 345 us of config 2, more than a third of that in bank conflicts.  This one: 231-253 us.
-#ifndef F4R_WAVES_NB
 #define F4R_WAVES_NB 2
-#endif
 template <int MODE, bool NB1>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(F4R_WAVES_NB))) void fft4_rows176_kernel(F4Args a) {
     constexpr int N1 = F4W_N1, N2 = F4W_N2, CB = 7, DP = 17, RP = 11 * DP;

@@ -339,12 +339,8 @@ __global__ void if_mark_kernel(unsigned long long* mark, unsigned long long valu
 
 #define SGX_STAGE_BYTES (32u << 20)   // a pinned staging buffer: two slots
 #define SGX_SLOT_BYTES (16u << 20)    // a multiple of every cache-line size: a line is never fetched half written
-#ifndef SGX_PIPE_SLOTS
 #define SGX_PIPE_SLOTS 4
-#endif
-#ifndef SGX_PIPE_READERS
 #define SGX_PIPE_READERS 3
-#endif
 
 struct FilePipe {
     int fd = -1;

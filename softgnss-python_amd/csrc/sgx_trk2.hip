@@ -590,24 +590,6 @@ __device__ __forceinline__ int t2_pll_role(T2Shared& S, const TrkConst& K, const
         unsigned long long x = 0;
         int budget = T2_POLL_BUDGET;
         bool gave_up = false;
-#ifdef T2_POLL2
-        {   // two polls in flight, half a round trip apart
-            unsigned long long xa_ = 0, xb_ = 0;
-            if (mine) xa_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (;;) {
-                if (mine) xb_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__all(!mine || (xa_ >> 48) == tag)) { x = xa_; break; }
-                if (mine) xa_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__all(!mine || (xb_ >> 48) == tag)) { x = xb_; break; }
-                if ((--budget & 31) == 0) {
-                    if (budget == 0 || lds_peek(&S.flag[1]) != 0) {
-                        gave_up = true;
-                        break;
-                    }
-                }
-            }
-        }
-#else
         for (;;) {
             if (mine) x = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__all(!mine || (x >> 48) == tag)) break;
@@ -618,7 +600,6 @@ __device__ __forceinline__ int t2_pll_role(T2Shared& S, const TrkConst& K, const
                 }
             }
         }
-#endif
         T2STAMP(prof_on, 8);   // waiting for the sums
         if (prof) {
             t_arr = (long long)__builtin_amdgcn_s_memtime();
@@ -794,25 +775,6 @@ __device__ __forceinline__ int t2_dll_role(T2Shared& S, const TrkConst& K, const
         unsigned long long x = 0, xa = 0;
         int budget = T2_POLL_BUDGET;
         bool gave_up = false;
-#ifdef T2_POLL2
-        {
-            unsigned long long xa_ = 0, xb_ = 0;
-            if (mine) xa_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (;;) {
-                if (mine) xb_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__all(!mine || (xa_ >> 48) == tag)) { x = xa_; break; }
-                if (mine) xa_ = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__all(!mine || (xb_ >> 48) == tag)) { x = xb_; break; }
-                if ((--budget & 15) == 0) {
-                    xa = __hip_atomic_load(xabort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (xa != 0 || budget == 0) {
-                        gave_up = true;
-                        break;
-                    }
-                }
-            }
-        }
-#else
         for (;;) {
             if (mine) x = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__all(!mine || (x >> 48) == tag)) break;
@@ -824,7 +786,6 @@ __device__ __forceinline__ int t2_dll_role(T2Shared& S, const TrkConst& K, const
                 }
             }
         }
-#endif
         T2STAMP(prof_on, 12);  // waiting for the sums
         // T8 DLL (tracking.py:238-251).  Row r of the wave holds the units' payloads of I_E | Q_E | I_L | Q_L: integer
         // row sums (exact, order-free; lanes that poll nothing hold 0), every lane of a row then has its row's total.

@@ -52,22 +52,14 @@
 // sgx_trk2.hip.
 #include "sgx_trk2_parts.h"
 
-// issue priorities off the chain: the speculative pass (parts A and B) and the filter waves' work in front of their polls;
+// issue priorities off the chain: the speculative pass (parts A and B) 0, the filter waves' work in front of their polls 1;
 // on the chain: the final pass 2, the filter waves from their poll to the barrier 3
-#ifndef T3_PRIO_SPEC
-#define T3_PRIO_SPEC 0
-#endif
-#ifndef T3_PRIO_PRE
-#define T3_PRIO_PRE 1
-#endif
 #define T3_STR2(x) #x
 #define T3_STR(x) T3_STR2(x)
 #define T3_LANES 128               // map lanes = groups per unit (two waves)
 #define T3_UNIT (T3_LANES * 16)    // samples per unit
 #define T3_THREADS 448             // 2 x 2 map waves (two SETS, alternating blocks) + PLL wave (4) + DLL wave (5) + record wave (6)
-#ifndef T3_XLINE
 #define T3_XLINE 32                // granules per line: [2 parities][6 sums] lines of 32 units
-#endif
 #define T3_XABORT (12 * T3_XLINE)
 #define T3_XPLACE (12 * T3_XLINE + 8)
 // (T3_MAXP units per channel, T3_XCH_STRIDE exchange words per channel: sgx_trk_common.h)
@@ -87,9 +79,9 @@
 // launch with sgx_trk2.hip and says so.  Offset-binary records (uint8, read as they lie: a DC of 128 that the correlation
 // cancels but a magnitude bound cannot) keep the round-5 guard: the units' prompt payloads beyond HALF the room, seen by the
 // PLL wave behind the barrier.
-#ifndef T3_FIX
 #define T3_FIX 1073741824.0
-#endif
+// the largest TWO-block carrier rate step the map's expansion takes (t3_pll_role says why)
+#define T3_DW2_HZ 20.0
 
 struct __attribute__((aligned(128))) T3Code {   // code side of a block's parameters (DLL wave -> everybody), by block parity
     // chain part: written right before the barrier that starts the block
@@ -133,10 +125,7 @@ struct T3Shared {
 
 // -DTRK_WAVEPROF: how long after the barrier's release each wave of (channel 0, member 0) arrives at the next one
 #ifdef TRK_WAVEPROF
-#ifndef T3_WB_UNIT
-#define T3_WB_UNIT 0
-#endif
-#define T3_WB_ON(unit, ch) ((unit) == T3_WB_UNIT && (ch) == 0)
+#define T3_WB_ON(unit, ch) ((unit) == 0 && (ch) == 0)
 #define T3_WB_DECL long long wb_acc[2] = {0, 0}, wb_t = (long long)__builtin_amdgcn_s_memtime();
 #define T3_WB(on)                                                                \
     do {                                                                         \
@@ -914,7 +903,7 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
         }
         T2STAMP(prof_on, 5);   // published (or handed to the lanes that publish)
         T3_TL(T3_TL_MAP, tl_on, tid >> 6, 5);
-        __builtin_amdgcn_s_setprio(T3_PRIO_SPEC);
+        __builtin_amdgcn_s_setprio(0);
         if (it + 2 < ms) {
             // ======== part A of the pass of this set's NEXT block, it + 2, with this block's rates (in the shadow of this
             // block's exchange and loop filter).  Its first sample is pos + blk + (the length block it + 1 will most likely
@@ -937,9 +926,6 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
             pend_b = true;
         }
         } else if (pend_b) {
-#if T3_NOP_SPEC > 0
-            asm volatile(".rept " T3_STR(T3_NOP_SPEC) "\n\ts_nop 3\n\t.endr");   // (diagnosis) part B starts 16 cycles later each
-#endif
             // ======== part B of that pass: the table is the one part A ran with - the block before this one's
             spec_b(S.carr[par ^ 1], true);
             pend_b = false;
@@ -971,38 +957,9 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
 // the disassembly), and the next poll starts by waiting for what the last one left.
 // Returns the number of rounds left (0: nothing found in `rounds` rounds - the caller looks at the abort word and polls
 // again); x: the granule of every active lane.  Call with the lanes that poll as the active lanes.
-#ifndef T3_POLL_GAP
-#define T3_POLL_GAP 5              // (the round-4 DLL poll's gap between its two pairs of loads; unused since round 5)
-#endif
-#ifndef T3_POLL_GAP3
-#define T3_POLL_GAP3 2             // ... between the PLL wave's three loads
-#endif
+#define T3_LOOK_GAP 2              // s_sleep units between a poll's three loads
 #ifndef T3_POLL2
 #define T3_POLL2 3                 // bit 0: the PLL wave, bit 1: the DLL wave (0: one load at a time, for comparison)
-#endif
-// s_sleep units (64 cycles) the filter waves rest behind the barrier before their off-chain work
-#ifndef T3_SLEEP_PLL
-#define T3_SLEEP_PLL 0
-#endif
-#ifndef T3_SLEEP_DLL
-#define T3_SLEEP_DLL 0
-#endif
-#ifndef T3_NOP_PLL
-#define T3_NOP_PLL 0
-#endif
-#ifndef T3_NOP_DLL
-#define T3_NOP_DLL 0
-#endif
-#ifndef T3_NOP_SPEC
-#define T3_NOP_SPEC 0
-#endif
-#ifndef T3_NOP_REC
-#define T3_NOP_REC 0
-#endif
-#ifdef T3_ALIGN_POLL   // (diagnosis) the polls' loops start on a 64-byte line of the instruction cache
-#define T3_POLL_ALIGN ".p2align 6\n"
-#else
-#define T3_POLL_ALIGN
 #endif
 __device__ __forceinline__ int t3_poll1(unsigned long long& x, const unsigned long long* p, unsigned long long tag, int rounds) {
     unsigned long long t;
@@ -1011,12 +968,11 @@ __device__ __forceinline__ int t3_poll1(unsigned long long& x, const unsigned lo
     asm volatile(
         "s_waitcnt vmcnt(0)\n\t"
         "global_load_dwordx2 v[250:251], %[p], off sc1\n\t"
-        "s_sleep " T3_STR(T3_POLL_GAP3) "\n\t"
+        "s_sleep " T3_STR(T3_LOOK_GAP) "\n\t"
         "global_load_dwordx2 v[252:253], %[p], off sc1\n\t"
-        "s_sleep " T3_STR(T3_POLL_GAP3) "\n\t"
+        "s_sleep " T3_STR(T3_LOOK_GAP) "\n\t"
         "global_load_dwordx2 v[254:255], %[p], off sc1\n\t"
         "s_mov_b32 %[n], %[r]\n"
-        T3_POLL_ALIGN
         "1:\n\t"
         "s_waitcnt vmcnt(2)\n\t"
         "v_lshrrev_b64 %[t], 48, v[250:251]\n\t"
@@ -1058,9 +1014,6 @@ __device__ __forceinline__ int t3_poll1(unsigned long long& x, const unsigned lo
 // The DLL wave's poll: an arm's I and Q granules of a unit lie side by side and ONE 16-byte load per look fetches both
 // (round 5; before: two 8-byte loads per look, two looks in flight - this wave found its sums 430 cycles after the PLL wave
 // found its own and was the last at the barrier of every block, profiles/r05_trk_phase_profile.txt).  Three in flight.
-#ifndef T3_POLL_GAPD
-#define T3_POLL_GAPD T3_POLL_GAP3    // s_sleep units between the DLL wave's three loads
-#endif
 #define T3_TAGSEL 0x07060302u      // v_perm_b32: {upper half of the first source, upper half of the second}
 __device__ __forceinline__ int t3_poll2(unsigned long long& x1, unsigned long long& x2, const unsigned long long* p1,
                                         const unsigned long long* p2, unsigned long long tag, int rounds) {
@@ -1078,12 +1031,11 @@ __device__ __forceinline__ int t3_poll2(unsigned long long& x1, unsigned long lo
     asm volatile(
         "s_waitcnt vmcnt(0)\n\t"
         "global_load_dwordx4 v[244:247], %[p], off sc1\n\t"
-        "s_sleep " T3_STR(T3_POLL_GAPD) "\n\t"
+        "s_sleep " T3_STR(T3_LOOK_GAP) "\n\t"
         "global_load_dwordx4 v[248:251], %[p], off sc1\n\t"
-        "s_sleep " T3_STR(T3_POLL_GAPD) "\n\t"
+        "s_sleep " T3_STR(T3_LOOK_GAP) "\n\t"
         "global_load_dwordx4 v[252:255], %[p], off sc1\n\t"
         "s_mov_b32 %[n], %[r]\n"
-        T3_POLL_ALIGN
         "1:\n\t"
         T3_P2_CHECK(244, 245, 247, "2f")
         T3_P2_CHECK(248, 249, 251, "3f")
@@ -1142,9 +1094,6 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
     // pull-in (steps of 50 Hz and more) and stayed there - the code phase then drifts from the reference's by 1e-15 chips
     // per block for the rest of the run.  Beyond 20 Hz (1e-12 left out; 3.4 sigma of a locked 45 dB-Hz channel's steps) the
     // tables are evaluated in full and the map accumulates again, exactly.
-#ifndef T3_DW2_HZ
-#define T3_DW2_HZ 20.0
-#endif
     double dw2_lim = 2.0 * M_PI * T3_DW2_HZ;
     T2_PIN(dw2_lim);
     const int ms = K.ms;
@@ -1264,13 +1213,8 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
         if (prof) {
             t_arr = (long long)__builtin_amdgcn_s_memtime();
             const long long tp = lds_peek64(&S.tpub[par]);
-#ifdef T3_PROF_PAR   // (diagnosis) phase times of the even (0) / odd (1) blocks only: figures are per TWO blocks then
-            if ((it & 1) == T3_PROF_PAR)
-#endif
-            {
             acc_map += tp - t_top;       // barrier release -> this member's publish
             acc_xch += t_arr - tp;       // this member's publish -> every member's sums visible
-            }
         }
         // sum of the units' payloads (integers: exact, order-free); lanes that poll nothing hold 0
         const double v = t3_sum48_half(x);   // rows 1 and 3: the sums over lanes 0..31 / 32..63 (in units of the fixed point)
@@ -1325,13 +1269,7 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
         T2STAMP(prof_on, 10);  // carrier tables
         T3_TL(T3_TL_PLL, tl_on, 4, 4);   // at the barrier
         T3_WB(wb_on);
-#if T3_SLEEP_PLL > 0
-        __builtin_amdgcn_s_sleep(T3_SLEEP_PLL);    // the final pass has the SIMD to itself for a moment (see T3_SLEEP_PLL)
-#endif
-#if T3_NOP_PLL > 0
-        asm volatile(".rept " T3_STR(T3_NOP_PLL) "\n\ts_nop 3\n\t.endr");   // 16 cycles each
-#endif
-        __builtin_amdgcn_s_setprio(T3_PRIO_PRE);   // what follows until the next poll is off the chain: the final pass (2) issues first,
+        __builtin_amdgcn_s_setprio(1);   // what follows until the next poll is off the chain: the final pass (2) issues first,
                                          // the speculative pass (0) after it
         __builtin_amdgcn_sched_barrier(0);
         // (a unit's prompt sum beyond half the room of the 48-bit payload, see T3_FIX: the guard of offset-binary records;
@@ -1346,9 +1284,6 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
         s2_blk = __builtin_fma(-10.625 * eps_next, eps_next, 1.0);
         r_err = carrError;
         r_nco = carrNco;
-#ifdef T3_PROF_PAR
-        if ((it & 1) == T3_PROF_PAR)
-#endif
         if (prof) acc_flt += (long long)__builtin_amdgcn_s_memtime() - t_arr;   // sums visible -> barrier released
         T2STAMP(prof_on, 11);
     }
@@ -1592,25 +1527,14 @@ __device__ __forceinline__ int t3_dll_role(T3Shared& S, const TrkConst& K, const
         T2STAMP(prof_on, 14);  // next block's code parameters
 #ifdef T3_PROF_DLL
         if (prof) {
-#ifdef T3_PROF_PAR   // (even (0) / odd (1) blocks only: figures are per TWO blocks then)
-            if ((it & 1) == T3_PROF_PAR)
-#endif
-            {
             dp_in += dp_t1 - dp_t0;
             dp_wait += dp_t2 - dp_t1;
             dp_post += (long long)__builtin_amdgcn_s_memtime() - dp_t2;
-            }
         }
 #endif
         T3_TL(T3_TL_DLL, tl_on, 5, 4);   // at the barrier
         T3_WB(wb_on);
-#if T3_SLEEP_DLL > 0
-        __builtin_amdgcn_s_sleep(T3_SLEEP_DLL);
-#endif
-#if T3_NOP_DLL > 0
-        asm volatile(".rept " T3_STR(T3_NOP_DLL) "\n\ts_nop 3\n\t.endr");
-#endif
-        __builtin_amdgcn_s_setprio(T3_PRIO_PRE);
+        __builtin_amdgcn_s_setprio(1);
         __builtin_amdgcn_sched_barrier(0);
         r_ve = vi * (s2_blk * unfix);    // (the block's record values: nobody waits for these)
         r_vl = vq * (s2_blk * unfix);
@@ -1673,25 +1597,18 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
     const long long span = 2ll * K.n_units * T3_UNIT + 64;   // bytes: a block and the window of the prefetch behind it
     const long long limit = K.rec_alloc - 16;
     unsigned dummy = 0;
-#ifdef T3_REC_LAT
-    long long rl_acc = 0;
-#endif
     T3_WB_DECL
     int it = 0;
     for (; it < ms; ++it) {
         const int par = it & 1;
         const T3Code& C = S.code[par];
         if (C.stop) break;
-#if T3_NOP_REC > 0
-        asm volatile(".rept " T3_STR(T3_NOP_REC) "\n\ts_nop 3\n\t.endr");   // (diagnosis) the far prefetch leaves 16 cycles later each
-#endif
         if (lane < 20) {
             long long a = ((C.pos + 6ll * C.blk) & ~127ll) + (long long)unit * T3_UNIT + 128ll * (lane - 1);
             a = a < 0 ? 0 : (a > limit ? limit : a);
             if (K.mark == nullptr || (unsigned long long)(a + 128) <= mark_seen)   // (a streaming record: only what is resident)
                 asm volatile("global_load_dword %0, %1, off" : "+v"(dummy) : "v"(rec + a) : "memory");
         }
-#ifndef T3_NO_GUARD
         if (K.mark != nullptr && K.uns == 0) {
             // THE SCALE GUARD (see T3_FIX) of a STREAMING int8 record (a resident one has been scanned once by the host,
             // sgx_trk.hip: if_mag_bound): the magnitudes of the unit's 2 048 bytes of THIS block (its aligned window: an
@@ -1728,14 +1645,6 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
                 }
             }
         }
-#endif
-#ifdef T3_REC_LAT   // (diagnosis) how long the far prefetch is under way: the CU returns vector loads in order
-        {
-            const long long t0_ = (long long)__builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(dummy) : : "memory");
-            rl_acc += (long long)__builtin_amdgcn_s_memtime() - t0_;
-        }
-#endif
         if (owner && it > 0) t3_rec_store(S, it - 1, m, lane, o, err, ch);
         {   // (a resident record: mark_seen is all ones and this returns at once)
             const long long need = C.pos + 4 * span;
@@ -1743,9 +1652,6 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
         }
         T3_WB(wb_on);
     }
-#ifdef T3_REC_LAT
-    if (lane == 0 && ch == 0 && (unit == 0 || unit == 10)) printf("[t3 rec] unit %d: the far prefetch returns %.0f cycles after its issue (mean of %d blocks)\n", unit, (double)rl_acc / it, it);
-#endif
     T3_WB_PRINT(wb_on, "rec", ms)
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(dummy) : : "memory");   // (no request outlives the wave's registers)
     return it;
@@ -1758,9 +1664,6 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
                                                           long long* __restrict__ prof,
                                                           unsigned long long* __restrict__ xch, int* __restrict__ err) {
     __shared__ T3Shared S;
-#ifdef T3_PAD   // (diagnosis) moves every instruction behind this point by 4 T3_PAD bytes: does the code's placement matter?
-    asm volatile(".rept " T3_STR(T3_PAD) "\n\ts_nop 0\n\t.endr");
-#endif
     const int P = K.split;
     const int bq = blockIdx.x >> 3, br = blockIdx.x & 7;
     const int ch = br + 8 * (bq / P);

@@ -65,15 +65,11 @@ struct TrkConst {
 // The exchange area of a trk2_kernel channel, in 64-bit words: 12 granule lines [2 parities][6 sums] of 16 units each,
 // T2_XLINE words apart, then the abort word and 48 placement granules (sgx_trk2_parts.h).  trk3_kernel's: T3_XCH_STRIDE
 // words (sgx_trk3.hip).  Profile words per channel: [3 phases][64 members].
-#ifndef T2_XLINE
 #define T2_XLINE 16                // 128 bytes: the lines are adjacent
-#endif
 #define T2_XCH_STRIDE (((12 * T2_XLINE + 8 + 48) + 255) / 256 * 256)
 #define T2_PROF_STRIDE 192
 #define T3_MAXP 32                 // trk3_kernel: units per channel
-#ifndef T3_XCH_STRIDE
 #define T3_XCH_STRIDE 512
-#endif
 
 // sgx_trk2.hip: the latency-mode kernel; arms = 1: one workgroup per unit and correlator arm, 3: one per unit
 void sgx_trk2_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,

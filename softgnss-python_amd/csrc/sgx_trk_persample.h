@@ -1,14 +1,17 @@
 // Body of the per-sample cooperative tracking kernel (the round-1 kernel body: map / reduce / exchange / filter with two
 // barriers per block).  Every sample looks its replicas up (tracking.py:166-188).  Two instances:
-//   sgx_trk_multi.hip  int8 records at low sampling rates (fewer than ~15.4 samples per chip), 16-byte groups;
-//   sgx_trk_any.hip    (TRK_ANY) any sample type numpy reads (K.kind), each sample fetched where it lies: float32 /
+//   sgx_trk_multi.hip  <false> int8 records at low sampling rates (fewer than ~15.4 samples per chip), 16-byte groups;
+//   sgx_trk_any.hip    <true>  any sample type numpy reads (K.kind), each sample fetched where it lies: float32 /
 //                      float64 records of arbitrary values, the wider integers, and int16 / uint8 at low rates.
-__global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const int8_t* __restrict__ rec,
-                                                          const int8_t* __restrict__ codes,
-                                                          const TrkChan* __restrict__ chans,
-                                                          double* __restrict__ out, int* __restrict__ ms_done,
-                                                          TrkConst K, long long* __restrict__ prof,
-                                                          unsigned long long* __restrict__ xch,
+#pragma once
+#include "sgx_trk_common.h"
+
+// (static: an instance's LDS variables then have internal linkage, like those a kernel declares itself)
+template <bool ANY>
+static __device__ __forceinline__ void trk_persample_body(const int8_t* __restrict__ rec, const int8_t* __restrict__ codes,
+                                                          const TrkChan* __restrict__ chans, double* __restrict__ out,
+                                                          int* __restrict__ ms_done, const TrkConst& K,
+                                                          long long* __restrict__ prof, unsigned long long* __restrict__ xch,
                                                           int* __restrict__ err) {
     __shared__ unsigned s_code_hi[1028];   // hi dword of +-1.0 for [c1022, c0..c1022, c0] (tracking.py:111)
     __shared__ TrkBlock s_blk;
@@ -40,15 +43,10 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
         if (tid == 0 && member == 0) ms_done[ch] = 0;
         return;
     }
-#ifdef TRK_ANY
-    // K.rec_len is in bytes: this channel's sample grid starts at byte cc.pad of the record (tracking.py:107 seeks bytes)
-    const int any_sb = sgx_dt_bytes(K.kind);
-    const int8_t* __restrict__ const recc = rec + cc.pad;
-    const long long any_len = (K.rec_len - cc.pad) / any_sb;
-#define TRK_RL , any_len
-#else
-#define TRK_RL
-#endif
+    // ANY: K.rec_len is in bytes: this channel's sample grid starts at byte cc.pad of the record (tracking.py:107 seeks bytes)
+    const int any_sb = ANY ? sgx_dt_bytes(K.kind) : 1;
+    const int8_t* __restrict__ const recc = rec + (ANY ? cc.pad : 0);
+    const long long rec_len = ANY ? (K.rec_len - cc.pad) / any_sb : -1;   // in samples (-1: K.rec_len, see prep_code)
     if (tid == 0) s_abort = 0;
     __syncthreads();
     // exchange area of the channel: [2 epoch parities][TRK_MAX_SPLIT members][12 granules], then one
@@ -104,14 +102,13 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
     }
     __syncthreads();
     if (wave == 0) prep_carr(K, s_st.w, s_st.remCarr, (int)(cc.pos0 & 15), s_blk, lane);
-    if (wave == 1) prep_code(K, s_st.codeFreq, s_st.remCode, s_st.pos, s_st, s_blk, lane == 0 TRK_RL);
+    if (wave == 1) prep_code(K, s_st.codeFreq, s_st.remCode, s_st.pos, s_st, s_blk, lane == 0, rec_len);
     __syncthreads();
 
-#ifndef TRK_ANY
     const long long limit = K.rec_alloc - 16;
     const long long lane_off = (long long)(tid + member * TRK_THREADS) * 16;   // byte offset of the lane's first unit
-    uint4 cur = load_group(rec, (s_blk.pos & ~15ll) + lane_off, limit);
-#endif
+    uint4 cur = make_uint4(0u, 0u, 0u, 0u);                                    // (16-byte groups: the int8 instance only)
+    if constexpr (!ANY) cur = load_group(rec, (s_blk.pos & ~15ll) + lane_off, limit);
     double* __restrict__ o = out + (long long)ch * SGX_NUM_SERIES * K.ms;
     const double two_pi = 2 * M_PI;
     int done = 0;
@@ -141,9 +138,7 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
         for (int b = 0; b < 16; ++b) B[b] = s_blk.B[b];
 
         const long long abase = pos & ~15ll;
-#ifndef TRK_ANY
         const long long abase_next = (pos + blk) & ~15ll;
-#endif
         const int head = (int)(pos - abase);              // bytes of the first group before the block
         const int n_groups = (head + blk + 15) >> 4;
         double aIE = 0.0, aQE = 0.0, aIP = 0.0, aQP = 0.0, aIL = 0.0, aQL = 0.0;
@@ -157,19 +152,17 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
 
 #pragma unroll 1
         for (int u = member; u < K.n_units; u += P) {
-#ifndef TRK_ANY
             // issue the load of the lane's next unit (this block's, or the first one of the next block)
             const int un = u + P;
-            const uint4 nxt = (un < K.n_units) ? load_group(rec, abase + (long long)(tid + un * TRK_THREADS) * 16, limit)
+            const uint4 nxt = ANY ? cur
+                            : (un < K.n_units) ? load_group(rec, abase + (long long)(tid + un * TRK_THREADS) * 16, limit)
                                                : load_group(rec, abase_next + lane_off, limit);
-#endif
             const int g = tid + u * TRK_THREADS;
             PROBE(0);   // block parameters, B table, lane phasor, next-unit load issued, current unit landed
             if (g < n_groups) {
                 const int i0 = g * 16 - head;             // sample index of byte 0 of this group
-#ifndef TRK_ANY
                 unsigned wd[4] = {cur.x, cur.y, cur.z, cur.w};
-                if (i0 < 0 || i0 + 16 > blk) {
+                if (!ANY && (i0 < 0 || i0 + 16 > blk)) {
                     // zero the bytes outside [0, blk): they then add nothing to the sums
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
@@ -182,13 +175,11 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
                         wd[d] &= m;
                     }
                 }
-#endif
                 // group-start phasor G = (lane part) * W3[u]
                 const double2 w3 = s_blk.W3[u];
                 const double gc = __builtin_fma(lc, w3.x, -(ls * w3.y));
                 const double gs = __builtin_fma(lc, w3.y, ls * w3.x);
-#ifdef TRK_ANY
-                if (!K.multi) {
+                if (ANY && !K.multi) {
                     // A group meets at most one switch of a ramp (16 samples span less than a chip): the three ramps' index
                     // and switch sample at the group's first sample by the exact reference arithmetic (ramp_setup), then
                     // the group as a sum over all its samples plus a sum over those behind the switch - when the ramps that
@@ -252,9 +243,7 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
                         aIL = __builtin_fma(dL, tlI, __builtin_fma(cL1, allI, aIL));
                         aQL = __builtin_fma(dL, tlQ, __builtin_fma(cL1, allQ, aQL));
                     }
-                } else
-#endif
-                {
+                } else {
                     // Low sampling rates (under ~15 samples per chip): a group can hold several chip switches of a
                     // ramp, so the replicas are indexed sample by sample exactly as the reference does,
                     // code[ceil(linspace(...))] (tracking.py:166-188).  Its own kernel (sgx_trk_multi.hip): correctness over speed.
@@ -262,12 +251,8 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
                     for (int b = 0; b < 16; ++b) {
                         const int i = i0 + b;
                         if (i < 0 || i >= blk) continue;
-#ifdef TRK_ANY
-                        const double xd = any_sample(recc + (pos + i) * any_sb, K.kind);
-#else
-                        const unsigned wv = wd[b >> 2];
-                        const double xd = (double)(int)(signed char)((wv >> (8 * (b & 3))) & 0xFF);
-#endif
+                        const double xd = ANY ? any_sample(recc + (pos + i) * any_sb, K.kind)
+                                              : (double)(int)(signed char)((wd[b >> 2] >> (8 * (b & 3))) & 0xFF);
                         const double2 Bb = s_blk.B[b];
                         const double c = __builtin_fma(gc, Bb.x, -(gs * Bb.y));
                         const double sn = __builtin_fma(gs, Bb.x, gc * Bb.y);
@@ -284,9 +269,7 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
                     }
                 }
             }
-#ifndef TRK_ANY
             cur = nxt;
-#endif
             PROBE(4);   // group finalisation
         }
         const long long tk1 = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -432,16 +415,13 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
                 s_st.codeFreq = codeFreq;
             }
             if (lane == 0 && member == 0) {
-#ifdef TRK_ANY
-                s_out[it & 1][4] = (double)(pos_after * any_sb + cc.pad + K.file_off);   // fid.tell(): bytes (tracking.py:255)
-#else
-                s_out[it & 1][4] = (double)(pos_after + K.file_off);
-#endif
+                if constexpr (ANY) s_out[it & 1][4] = (double)(pos_after * any_sb + cc.pad + K.file_off);   // fid.tell(): bytes (tracking.py:255)
+                else s_out[it & 1][4] = (double)(pos_after + K.file_off);
                 s_out[it & 1][5] = codeFreq;
                 s_out[it & 1][6] = codeError;
                 s_out[it & 1][7] = codeNco;
             }
-            if (more) prep_code(K, codeFreq, rem_next, pos_after, s_st, s_blk, lane == 0 TRK_RL);
+            if (more) prep_code(K, codeFreq, rem_next, pos_after, s_st, s_blk, lane == 0, rec_len);
         }
         else if (wave == 2 && member == 0) {
             // record (T9) of the PREVIOUS block: its six sums and scalar series were staged in LDS by the
@@ -490,4 +470,3 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW) void TRK_KERNEL_NAME(const i
 #endif
     if (tid == 0 && member == 0) ms_done[ch] = done;
 }
-#undef TRK_RL

@@ -31,21 +31,10 @@
 // Threads per workgroup (one channel) and workgroups per CU the register budget is cut for.  Measured on 2048 channels
 // x 500 ms: 256 x 2 13.8 ms (13.4 with the weight dwords kept in registers, which only this budget allows); 256 x 3 (168
 // registers, spills) 15.3 ms; 128 x 4 (both waves busy in every phase) 15.4 ms.
-#ifndef TP_THREADS
 #define TP_THREADS 256
-#endif
-// workgroups per CU the register allocation is cut for, per sample type (MODE 0 int8, 1 uint8, 2 int16): -DTP_OCC2=1 gives
-// the int16 instance - two planes of samples in flight - the registers of a whole SIMD lane
-#ifndef TP_OCC2
-#define TP_OCC2 2
-#endif
-#ifndef TP_OCC1
-#define TP_OCC1 2
-#endif
-#define TP_OCC_MODE(M) ((M) == 2 ? TP_OCC2 : ((M) == 1 ? TP_OCC1 : TP_OCC))
-#ifndef TP_OCC
+// ... for every sample type: one workgroup per CU for the int16 instance - two planes of samples in flight, the registers
+// of a whole SIMD lane, no spills - ran 41 500 channel-s/s against 52 300
 #define TP_OCC 2
-#endif
 
 // workgroup barrier that waits for LDS traffic only: __syncthreads() also waits for the wave's global loads and stores
 // (the record stores of a block, the look-ahead loads behind the last chip), whose round trips nobody here depends on
@@ -304,7 +293,7 @@ __device__ __forceinline__ void tp_apply(double2 gh, double2 gt, double Hc, doub
 }
 
 template <int MODE>
-__global__ __launch_bounds__(TP_THREADS, TP_OCC_MODE(MODE)) void trk_kernel_tp(const int8_t* __restrict__ rec0,
+__global__ __launch_bounds__(TP_THREADS, TP_OCC) void trk_kernel_tp(const int8_t* __restrict__ rec0,
                                                                 const int8_t* __restrict__ codes,
                                                                 const TrkChan* __restrict__ chans,
                                                                 double* __restrict__ out, int* __restrict__ ms_done,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # (diagnosis) side-by-side build of the library with one translation unit recompiled with extra flags:
-#   bash tools/build_variant.sh NAME sgx_fft.hip "-DF4W_NOSTORE"   -> softgnss-python_amd/lib/variants/libsgx_NAME.so
+#   bash tools/build_variant.sh NAME sgx_trk3.hip "-DT3_POLLSTAT"   -> softgnss-python_amd/lib/variants/libsgx_NAME.so
 # (run a variant with SGX_LIB=<path>; lib/variants is git-ignored and travels to the GPU box)
 set -e
 cd "$(dirname "$0")/.."
