@@ -440,6 +440,44 @@ int sgx_track_replay(sgx_ctx* c, const sgx_if* rec, int64_t rec_file_offset, con
                      int32_t n_taps, double* out);
 int sgx_replay_timing(sgx_ctx* c, float* kernel_ms, float* device_ms);
 
+/* ---- narrowband interference excision ahead of acquisition (no reference counterpart: initialize.py:330-417 only plots
+ * the spectrum a continuous-wave line shows up in) ----------------------------------------------------------------------
+ * Opt-in.  A resident int8 record goes through a zero-phase integer FIR and comes out as a NEW int8 record of the same
+ * length: sample n of the output lines up with sample n of the input, so code phases, absoluteSample and byte seeks mean
+ * what they did, and acquisition, tracking, replay, quality and navigation run on the new record unchanged.
+ * tests/notch_spec.py restates all of it in numpy.
+ *
+ * sgx_if_filter: taps h[n_taps] (n_taps = L odd, 1 .. SGX_FILTER_MAX_TAPS), c = (L - 1) / 2, x = 0 outside the record:
+ *   y[n] = clip((sum_k h[k] x[n + c - k] + (shift ? 2^(shift-1) : 0)) >> shift, -127, 127)
+ * with an arithmetic (floor) shift and a sum that is exact in int32 - pure integer, so the output is the contract's byte
+ * for byte.  The whole record is filtered on the context's stream (a record that is still streaming in is waited for,
+ * as sgx_if_wait to its full length); *out is an ordinary record (its own magnitude-bound cache; sgx_if_free).
+ * SGX_E_ARG, before anything is launched: n_taps even or out of range, shift outside 0 .. 30, a |h[k]| > 32 512 (a tap must
+ * split into two signed bytes, h = 256 hi + lo), 128 sum|h| >= 2^31, a NULL pointer.  The record's bytes are read as
+ * int8: records of other sample types (uint8, int16, ...) are not filtered.
+ * sgx_filter_timing: HIP-event time of the last sgx_if_filter's kernel on this context.
+ *
+ * sgx_notch_design: the lines of a one-sided PSD (f_mhz, pxx of n_bins >= 2 bins, as sgx_probe_stats gives them) and the
+ * notch that removes them; exact host code, needs no GPU.
+ *   detect  baseline b[i] = median(pxx[max(0, i-128) : min(n, i+129)]); bin i is flagged when pxx[i] > 10^(threshold_db/10)
+ *           b[i]; flagged bins with at most 2 unflagged bins between them form one line; centre = frequency of its largest
+ *           bin, width = max(width_hz, the run's extent + 2 bin widths); at most SGX_NOTCH_MAX_LINES lines are kept, the
+ *           strongest by peak / baseline, reported in ascending frequency in line_hz / line_width_hz (8 entries each).
+ *   design  with m = k - c: h_ideal[k] = delta[m] - sum_i 2 (w_i / fs) sinc(w_i m / fs) cos(2 pi f_i m / fs), fs =
+ *           s->samplingFreq, times a symmetric Hann window of n_taps points, times 2^SGX_NOTCH_SHIFT, rounded half to even
+ *           into taps[n_taps]; *shift = SGX_NOTCH_SHIFT.  *n_lines == 0 is not an error: the taps are then the identity.
+ * SGX_E_ARG for n_taps even or outside 1 .. SGX_FILTER_MAX_TAPS, n_bins < 2, a threshold or width that is not finite, a
+ * width <= 0, a PSD entry that is negative or not finite, a NULL pointer, and for lines so wide that the taps leave what
+ * sgx_if_filter takes. */
+#define SGX_FILTER_MAX_TAPS 4095
+#define SGX_NOTCH_MAX_LINES 8
+#define SGX_NOTCH_SHIFT 14
+int sgx_notch_design(const sgx_settings* s, const double* f_mhz, const double* pxx, int32_t n_bins, double threshold_db,
+                     double width_hz, int32_t n_taps, int16_t* taps, int32_t* shift, double* line_hz,
+                     double* line_width_hz, int32_t* n_lines);
+int sgx_if_filter(sgx_ctx* c, const sgx_if* in, const int16_t* taps, int32_t n_taps, int32_t shift, sgx_if** out);
+int sgx_filter_timing(sgx_ctx* c, float* kernel_ms);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -144,6 +144,10 @@ _PROTOS = {
     "sgx_replay_state": (C.c_int, [C.POINTER(Settings), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
     "sgx_track_replay": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P]),
     "sgx_replay_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sgx_notch_design": (C.c_int, [C.POINTER(Settings), _P, _P, C.c_int32, C.c_double, C.c_double, C.c_int32, _P,
+                                   C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32)]),
+    "sgx_if_filter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "sgx_filter_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -420,6 +424,27 @@ def replay_state(settings, chans, series, ms_done=None, data_type=DT_INT8, rec_f
                                  None if done is None else _ptr(done), _ptr(a), int(rec_file_offset), int(rec_bytes),
                                  _ptr(out)))
     return out
+
+
+FILTER_MAX_TAPS = 4095
+NOTCH_MAX_LINES = 8
+
+
+def notch_design(settings, f_mhz, pxx, threshold_db=8.0, width_hz=80e3, n_taps=1025):
+    """Lines of a one-sided PSD and the integer notch that removes them (sgx_notch_design; needs no GPU).  f_mhz, pxx: the
+    spectrum as probe_stats gives it.  Returns (taps int16[n_taps], shift, lines): lines is a list of (centre Hz, width Hz)
+    in ascending frequency, at most 8; with no line the taps are the identity filter."""
+    f = np.ascontiguousarray(f_mhz, dtype=np.float64).ravel()
+    p = np.ascontiguousarray(pxx, dtype=np.float64).ravel()
+    if f.size != p.size:
+        raise ValueError("f_mhz has %d entries, pxx %d" % (f.size, p.size))
+    st = settings_struct(settings)
+    taps = np.zeros(max(int(n_taps), 1), dtype=np.int16)
+    hz, wd = np.zeros(NOTCH_MAX_LINES), np.zeros(NOTCH_MAX_LINES)
+    shift, n = C.c_int32(0), C.c_int32(0)
+    check(lib().sgx_notch_design(C.byref(st), _ptr(f), _ptr(p), f.size, float(threshold_db), float(width_hz), int(n_taps),
+                                 _ptr(taps), C.byref(shift), _ptr(hz), _ptr(wd), C.byref(n)))
+    return taps, shift.value, [(float(hz[i]), float(wd[i])) for i in range(n.value)]
 
 
 def _rows(a):
@@ -719,6 +744,23 @@ class Context(object):
         k, d = C.c_float(0), C.c_float(0)
         check(lib().sgx_replay_timing(self._h, C.byref(k), C.byref(d)))
         return k.value, d.value
+
+    def filter_record(self, rec, taps, shift):
+        """A new int8 record of the same length: `rec` through the zero-phase integer FIR of sgx_if_filter (taps: int16, an
+        odd number of them up to 4095; y = clip((sum_k h[k] x[n + c - k] + 2^(shift-1)) >> shift, -127, 127))."""
+        a = np.asarray(taps)
+        if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
+            raise ValueError("taps must be integers that fit int16")
+        h16 = np.ascontiguousarray(a, dtype=np.int16).ravel()
+        h = _P()
+        check(lib().sgx_if_filter(self._h, rec._h, _ptr(h16), h16.size, int(shift), C.byref(h)))
+        return Record(self, h, len(rec))
+
+    def filter_timing(self):
+        """Kernel ms of the last filter_record on this context, from HIP events on its stream."""
+        k = C.c_float(0)
+        check(lib().sgx_filter_timing(self._h, C.byref(k)))
+        return k.value
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

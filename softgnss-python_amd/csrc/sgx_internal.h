@@ -168,6 +168,7 @@ struct SgxSmall {
     int2 stage_bin_map[ACQ_COH_MAX_BINS];
     int trk_mag;                            // sgx_trk.hip: the record's magnitude bound
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
+    alignas(16) unsigned filter_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];   // sgx_filter.hip: (hi, lo) tap dwords; both
 };
 #define SGX_SMALL_BYTES (1 << 20)
 static_assert(sizeof(SgxSmall) <= SGX_SMALL_BYTES, "the small areas hold the layout");
@@ -258,6 +259,7 @@ struct sgx_ctx {
     std::atomic<bool> stage_busy{false};
     // HIP-event times of the last sgx_track_replay (sgx_replay.hip): the kernel, and upload + kernel + result copy
     float replay_kernel_ms = 0.0f, replay_device_ms = 0.0f;
+    float filter_kernel_ms = 0.0f;   // HIP-event time of the last sgx_if_filter's kernel (sgx_filter.hip)
 };
 
 // sgx_host.cpp

@@ -98,6 +98,15 @@ _ACQ_DEFAULTS = (
     ("acqBinStep", None),           # Doppler step in Hz; None: 500 / acqCoherentMs
 )
 
+# narrowband interference excision ahead of acquisition (Settings.mitigate; INTEGRATION.md, "Interference excision"):
+# continuous-wave lines found in the Welch spectrum of probeData are notched out of the record by a zero-phase integer FIR
+_NOTCH_DEFAULTS = (
+    ("interferenceMitigation", False),   # postProcessing() filters the record before acquisition and tracking
+    ("notchThresholdDb", 8.0),           # a PSD bin this far above the running median of its neighbourhood is a line
+    ("notchWidthHz", 80e3),              # least width of a notch
+    ("notchTaps", 1025),                 # filter length (odd, at most 4095)
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -106,7 +115,7 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -206,6 +215,66 @@ class Settings(object):
         plt.ylabel('Number in bin')
         return self.probe
 
+    def mitigate(self, record, offset=0, device=None):
+        """Narrowband interference excision of a resident int8 record (a _native.Record): the Welch spectrum of the 10 code
+        periods from sample `offset` (probe_stats, as probeData), its lines by notchThresholdDb / notchWidthHz, a notch of
+        notchTaps taps (notch_design) and, if there is a line, the whole record through it (filter_record).  Returns
+        (record, lines): a NEW record of the same length - sample n lines up with sample n of the old one - or the SAME
+        record when no line was found; lines is a list of (centre Hz, width Hz).  The caller frees what it gets."""
+        from . import engine
+        if np.dtype(self.dataType) != np.dtype(np.int8):
+            raise ValueError("interference excision filters int8 records only, not Settings.dataType %r" % (self.dataType,))
+        ctx = record.ctx if device is None else engine.get_context(self, device)
+        n = min(10 * self.samplesPerCode, len(record) - int(offset))
+        f, pxx, _, _ = ctx.probe_stats(record, int(offset), n, self.samplingFreq / 1000000.0)
+        taps, shift, lines = _native.notch_design(self, f, pxx, self.notchThresholdDb, self.notchWidthHz, self.notchTaps)
+        if not lines:
+            return record, lines
+        return ctx.filter_record(record, taps, shift), lines
+
+    def _mitigated_processing(self, name):
+        """postProcessing()'s acquire -> preRun -> track with interferenceMitigation: the record is uploaded once, filtered
+        on the GPU, and both stages read the filtered record where it lies."""
+        from . import acquisition, engine, tracking
+        from .record import DeviceFile, DeviceSignal
+        n = self.samplesPerCode
+        skip = int(self.skipNumberOfBytes)
+        need = skip + max(self.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
+        ctx = engine.get_context(self, None)
+        raw = ctx.upload_file(name, 0, need)
+        rec = raw
+        try:
+            print('   Looking for narrowband interference...')
+            rec, lines = self.mitigate(raw, offset=min(skip, len(raw)))
+            for f_hz, w_hz in lines:
+                print('   Removed a line at %.4f MHz (notch %.1f kHz wide)' % (f_hz / 1e6, w_hz / 1e3))
+            if not lines:
+                print('   No narrowband interference found')
+            self.lastNotchLines = lines
+            print('   Acquiring satellites...')
+            acqResults = acquisition.AcquisitionResult(self)
+            acqResults.acquire(DeviceSignal(rec, skip, min(self.acquisitionLength(), max(0, len(rec) - skip))),
+                               n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
+                               coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
+            if not np.any(acqResults.carrFreq):
+                print('No GNSS signals detected, signal processing finished.')
+                return acqResults, None
+            acqResults.preRun()
+            acqResults.showChannelStatus()
+            trackResults = tracking.TrackingResult(acqResults)
+            start = datetime.datetime.now()
+            print('   Tracking started at %s' % start.strftime('%X'))
+            trackResults.track(DeviceFile(rec))
+            self.lastTrackingSeconds = (datetime.datetime.now() - start).total_seconds()
+            print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
+            if self.lockDetector and trackResults.has_results():
+                trackResults.showTrackingQuality()
+            return acqResults, trackResults
+        finally:
+            if rec is not raw:
+                rec.free()
+            raw.free()
+
     def acquisitionLength(self):
         """Samples postProcessing() reads for acquisition: 11 ms (the fine search needs codePhase + 10 ms), or all the
         coarse search's windows, acqCoherentMs x acqBlocks ms, where that is longer."""
@@ -216,7 +285,7 @@ class Settings(object):
         initialize.py:420-515 without the plots and without the .npy cache of the tracking results.
         Returns (acqResults, trackResults, navResults); navResults.solutions is unset when the record is too short
         or too few satellites carry ephemerides, as in the reference."""
-        from . import acquisition, postNavigation, tracking
+        from . import acquisition, tracking
         print('Starting processing...')
         name = self.fileName if not fileNameStr else fileNameStr
         if not isinstance(name, str):
@@ -225,6 +294,11 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
+        if self.interferenceMitigation:
+            acqResults, trackResults = self._mitigated_processing(name)
+            if trackResults is None:
+                return acqResults, None, None
+            return self._navigate(acqResults, trackResults)
         with open(name, 'rb') as fid:
             fid.seek(self.skipNumberOfBytes, 0)
             data = np.fromfile(fid, self.dataType, self.acquisitionLength())
@@ -245,6 +319,12 @@ class Settings(object):
             print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
             if self.lockDetector and trackResults.has_results():
                 trackResults.showTrackingQuality()
+        return self._navigate(acqResults, trackResults)
+
+    @staticmethod
+    def _navigate(acqResults, trackResults):
+        """The tail of postProcessing(): the navigation solution from the tracking results."""
+        from . import postNavigation
         if not trackResults.has_results():   # (the reference's short-read exit: results were not set, tracking.py:159-163)
             return acqResults, trackResults, None
         print('   Calculating navigation solutions...')
