@@ -478,6 +478,48 @@ int sgx_notch_design(const sgx_settings* s, const double* f_mhz, const double* p
 int sgx_if_filter(sgx_ctx* c, const sgx_if* in, const int16_t* taps, int32_t n_taps, int32_t shift, sgx_if** out);
 int sgx_filter_timing(sgx_ctx* c, float* kernel_ms);
 
+/* ---- interleaved I/Q baseband records (no reference counterpart: every stage of the reference reads a real IF record) ----
+ * Opt-in.  A resident record holding the raw BYTES of an interleaved 8-bit I/Q file (I0 Q0 I1 Q1 ...) at complex rate fs_c
+ * comes out as a NEW int8 record of the same length: the equivalent REAL record at 2 fs_c whose IF is IF_bb + fs_c / 2.
+ * z = I + jQ is interpolated by 2, shifted up by a quarter of the new rate and its real part kept; the spectrum of the
+ * result lies in (0, fs_c) clear of its mirror image.  Acquisition, tracking, replay, quality, the notch and navigation run
+ * on the new record unchanged, with samplingFreq = 2 fs_c and IF = IF_bb + fs_c / 2.  tests/iq_spec.py restates all of it
+ * in numpy.
+ *
+ * sgx_if_from_iq: N bytes b (N even), pairs m = 0 .. N/2 - 1: I[m] = b[2m], Q[m] = b[2m+1]; SGX_IQ_Q_FIRST swaps the two
+ * roles; SGX_IQ_OFFSET_BINARY first turns every byte into byte - 128 (uint8 files: XOR 0x80 read as int8), without it
+ * the bytes are int8 as they stand and -128 is a legal value.  Taps h[n_taps] (n_taps = L odd, 1 .. SGX_IQ_MAX_TAPS),
+ * c = (L - 1) / 2:
+ *   u[2m] = I[m] + j Q[m], u[odd] = 0, u = 0 outside [0, N);   w[n] = sum_k h[k] u[n + c - k]
+ *   a[n] = Re w[n], -Im w[n], -Re w[n], Im w[n]  for n mod 4 = 0, 1, 2, 3
+ *   y[n] = clip((a[n] + (shift ? 2^(shift-1) : 0)) >> shift, -127, 127)
+ * with an arithmetic (floor) shift and a sum that is exact in int32 - pure integer, so the output is the contract's byte
+ * for byte.  Output sample n is the instant of byte n's pair (half an input period later for odd n): a byte offset into
+ * the file is a sample offset into the new record, so skipNumberOfBytes (even), code phases and absoluteSample keep their
+ * meaning.  The whole record is converted on the context's stream (a record that is still streaming in is waited for, as
+ * sgx_if_wait to its full length); the input is left alone; *out is an ordinary record (its own magnitude-bound cache;
+ * sgx_if_free).  SGX_E_ARG, before anything is launched: n_taps even or out of range, shift outside 0 .. 30, a
+ * |h[k]| > 32 512 (a tap must split into two signed bytes, h = 256 hi + lo), 128 sum|h| >= 2^31, an unknown flag bit, a
+ * NULL pointer, N odd.
+ * sgx_iq_timing: HIP-event time of the last sgx_if_from_iq's kernel on this context.
+ * sgx_iq_tile: the output bytes one workgroup of the kernel makes (the lengths at which its tile seams lie).
+ *
+ * sgx_iq_design: the default interpolation filter, exact host code, needs no GPU.  With m = k - c:
+ *   h[k] = rint(2^SGX_IQ_SHIFT sinc(m / 2) hann_L[k]),  sinc(t) = sin(pi t) / (pi t), rounded half to even,
+ * hann_L the symmetric Hann window of L points (1 for L = 1): a half-band low-pass at the input's Nyquist frequency with
+ * the gain of 2 that zero-stuffing needs.  sinc(m / 2) is taken in closed form - 1 at m = 0, (-1)^((m-1)/2) 2 / (pi m) at
+ * odd m - so the centre tap is 2^SGX_IQ_SHIFT and every other even-m tap exactly 0.  *shift = SGX_IQ_SHIFT.  SGX_E_ARG
+ * for n_taps even or outside 1 .. SGX_IQ_MAX_TAPS, a NULL pointer. */
+#define SGX_IQ_MAX_TAPS 255
+#define SGX_IQ_SHIFT 14
+#define SGX_IQ_Q_FIRST 1
+#define SGX_IQ_OFFSET_BINARY 2
+int sgx_iq_design(int32_t n_taps, int16_t* taps, int32_t* shift);
+int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t* taps, int32_t n_taps, int32_t shift, int32_t flags,
+                   sgx_if** out);
+int sgx_iq_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_iq_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

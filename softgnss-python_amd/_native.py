@@ -148,6 +148,10 @@ _PROTOS = {
                                    C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32)]),
     "sgx_if_filter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "sgx_filter_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_iq_design": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "sgx_if_from_iq": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "sgx_iq_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_iq_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -445,6 +449,32 @@ def notch_design(settings, f_mhz, pxx, threshold_db=8.0, width_hz=80e3, n_taps=1
     check(lib().sgx_notch_design(C.byref(st), _ptr(f), _ptr(p), f.size, float(threshold_db), float(width_hz), int(n_taps),
                                  _ptr(taps), C.byref(shift), _ptr(hz), _ptr(wd), C.byref(n)))
     return taps, shift.value, [(float(hz[i]), float(wd[i])) for i in range(n.value)]
+
+
+IQ_MAX_TAPS = 255
+IQ_Q_FIRST, IQ_OFFSET_BINARY = 1, 2
+
+
+def iq_design(n_taps=63):
+    """(taps int16[n_taps], shift): the half-band interpolation filter of the I/Q converter (sgx_iq_design; needs no GPU)."""
+    taps = np.zeros(max(int(n_taps), 1), dtype=np.int16)
+    shift = C.c_int32(0)
+    check(lib().sgx_iq_design(int(n_taps), _ptr(taps), C.byref(shift)))
+    return taps, shift.value
+
+
+def iq_tile():
+    """Output bytes one workgroup of the I/Q converter makes: its tile seams lie at the multiples."""
+    t = C.c_int32(0)
+    check(lib().sgx_iq_tile(C.byref(t)))
+    return t.value
+
+
+def _int16_taps(taps):
+    a = np.asarray(taps)
+    if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
+        raise ValueError("taps must be integers that fit int16")
+    return np.ascontiguousarray(a, dtype=np.int16).ravel()
 
 
 def _rows(a):
@@ -748,10 +778,7 @@ class Context(object):
     def filter_record(self, rec, taps, shift):
         """A new int8 record of the same length: `rec` through the zero-phase integer FIR of sgx_if_filter (taps: int16, an
         odd number of them up to 4095; y = clip((sum_k h[k] x[n + c - k] + 2^(shift-1)) >> shift, -127, 127))."""
-        a = np.asarray(taps)
-        if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
-            raise ValueError("taps must be integers that fit int16")
-        h16 = np.ascontiguousarray(a, dtype=np.int16).ravel()
+        h16 = _int16_taps(taps)
         h = _P()
         check(lib().sgx_if_filter(self._h, rec._h, _ptr(h16), h16.size, int(shift), C.byref(h)))
         return Record(self, h, len(rec))
@@ -760,6 +787,23 @@ class Context(object):
         """Kernel ms of the last filter_record on this context, from HIP events on its stream."""
         k = C.c_float(0)
         check(lib().sgx_filter_timing(self._h, C.byref(k)))
+        return k.value
+
+    def iq_to_if(self, rec, taps, shift, q_first=False, offset_binary=False):
+        """A new int8 record of the same length: `rec`, the raw bytes of an interleaved 8-bit I/Q file at complex rate fs_c,
+        as the equivalent real record at 2 fs_c with IF = IF_bb + fs_c / 2 (sgx_if_from_iq: interpolation by 2 through the
+        int16 taps, an odd number of them up to 255, a quarter-rate shift, the real part).  q_first: the file holds Q before
+        I; offset_binary: its bytes are uint8 around 128."""
+        h16 = _int16_taps(taps)
+        flags = (IQ_Q_FIRST if q_first else 0) | (IQ_OFFSET_BINARY if offset_binary else 0)
+        h = _P()
+        check(lib().sgx_if_from_iq(self._h, rec._h, _ptr(h16), h16.size, int(shift), flags, C.byref(h)))
+        return Record(self, h, len(rec))
+
+    def iq_timing(self):
+        """Kernel ms of the last iq_to_if on this context, from HIP events on its stream."""
+        k = C.c_float(0)
+        check(lib().sgx_iq_timing(self._h, C.byref(k)))
         return k.value
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):

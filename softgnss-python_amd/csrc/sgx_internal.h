@@ -55,6 +55,9 @@ struct FftPlan {
     std::vector<int> radices;
 };
 
+// sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
+#define SGX_IQ_LP_MAX 136
+
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
     size_t n = 0;
@@ -169,6 +172,7 @@ struct SgxSmall {
     int trk_mag;                            // sgx_trk.hip: the record's magnitude bound
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
     alignas(16) unsigned filter_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];   // sgx_filter.hip: (hi, lo) tap dwords; both
+    alignas(16) unsigned iq_taps[2 * 2 * (SGX_IQ_LP_MAX / 4)];   // sgx_iq.hip: (hi, lo) tap dwords of the two branches; both
 };
 #define SGX_SMALL_BYTES (1 << 20)
 static_assert(sizeof(SgxSmall) <= SGX_SMALL_BYTES, "the small areas hold the layout");
@@ -260,6 +264,7 @@ struct sgx_ctx {
     // HIP-event times of the last sgx_track_replay (sgx_replay.hip): the kernel, and upload + kernel + result copy
     float replay_kernel_ms = 0.0f, replay_device_ms = 0.0f;
     float filter_kernel_ms = 0.0f;   // HIP-event time of the last sgx_if_filter's kernel (sgx_filter.hip)
+    float iq_kernel_ms = 0.0f;       // HIP-event time of the last sgx_if_from_iq's kernel (sgx_iq.hip)
 };
 
 // sgx_host.cpp

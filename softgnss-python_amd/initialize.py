@@ -3,6 +3,7 @@
 The three helpers the hot path calls - generateCAcode, makeCaTable, calcLoopCoef - are answered
 by libsgx.so's exact host routines (include/sgx.h), not by Python arithmetic.
 """
+import copy
 import ctypes as C
 import datetime
 
@@ -107,6 +108,15 @@ _NOTCH_DEFAULTS = (
     ("notchTaps", 1025),                 # filter length (odd, at most 4095)
 )
 
+# interleaved 8-bit I/Q baseband records (Settings.convertIQ; INTEGRATION.md, "I/Q baseband records"): the file is turned
+# into the equivalent real IF record on the GPU and every stage runs on that, under Settings.realEquivalent()
+_IQ_DEFAULTS = (
+    ("iqRecord", False),                 # fileName holds interleaved I/Q: samplingFreq is the COMPLEX rate, IF the baseband
+                                         # offset (0 or negative allowed), dataType 'int8' or 'uint8' (offset binary)
+    ("iqQFirst", False),                 # the file holds Q before I (also: spectral inversion of an I-first file)
+    ("iqTaps", 63),                      # length of the interpolation filter (odd, at most 255)
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -115,7 +125,7 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -232,28 +242,75 @@ class Settings(object):
             return record, lines
         return ctx.filter_record(record, taps, shift), lines
 
-    def _mitigated_processing(self, name):
-        """postProcessing()'s acquire -> preRun -> track with interferenceMitigation: the record is uploaded once, filtered
-        on the GPU, and both stages read the filtered record where it lies."""
+    def _iq_format(self):
+        """(q_first, offset_binary) of the I/Q file these settings describe."""
+        dt = np.dtype(self.dataType)
+        if dt not in (np.dtype(np.int8), np.dtype(np.uint8)):
+            raise ValueError("an I/Q record (Settings.iqRecord) holds int8 samples, or uint8 for offset binary, not "
+                             "Settings.dataType %r: int16 and float32 I/Q are not converted" % (self.dataType,))
+        return bool(self.iqQFirst), dt == np.dtype(np.uint8)
+
+    def realEquivalent(self):
+        """The settings of the real IF record that convertIQ makes of the I/Q file these settings describe: a copy with
+        samplingFreq * 2, IF + samplingFreq / 2, iqRecord = False and dataType 'int8' (what the converter writes).
+        Without iqRecord the record is real already: a plain copy."""
+        real = copy.copy(self)
+        if self.iqRecord:
+            real.samplingFreq = 2.0 * self.samplingFreq
+            real.IF = self.IF + self.samplingFreq / 2.0
+            real.iqRecord = False
+            real.dataType = 'int8'
+        return real
+
+    def convertIQ(self, record):
+        """A resident record holding the raw bytes of an interleaved 8-bit I/Q file (a _native.Record) as the equivalent
+        real IF record (iq_to_if through the iqTaps-tap filter of iq_design): a NEW int8 record of the same length whose
+        sample n is the instant of byte n's pair, to be read under realEquivalent().  The caller frees both."""
+        q_first, offset_binary = self._iq_format()
+        taps, shift = _native.iq_design(self.iqTaps)
+        return record.ctx.iq_to_if(record, taps, shift, q_first=q_first, offset_binary=offset_binary)
+
+    def _resident_processing(self, name):
+        """postProcessing()'s acquire -> preRun -> track on a record that is uploaded once and prepared on the GPU: with
+        iqRecord converted to real IF, with interferenceMitigation cleared of narrowband lines - the conversion first, the
+        notch is designed at the real rate - and both stages read the prepared record where it lies.  The results carry
+        realEquivalent(): positions are samples of the prepared record, which are bytes of the file."""
         from . import acquisition, engine, tracking
         from .record import DeviceFile, DeviceSignal
-        n = self.samplesPerCode
+        real = self.realEquivalent() if self.iqRecord else self
+        n = real.samplesPerCode
         skip = int(self.skipNumberOfBytes)
-        need = skip + max(self.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
-        ctx = engine.get_context(self, None)
-        raw = ctx.upload_file(name, 0, need)
-        rec = raw
+        need = skip + max(real.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
+        if self.iqRecord:
+            self._iq_format()
+            if skip % 2:
+                raise ValueError("skipNumberOfBytes = %d splits an I/Q pair: it must be even" % skip)
+            need += need % 2
+        ctx = engine.get_context(real, None)
+        rec = ctx.upload_file(name, 0, need)
         try:
-            print('   Looking for narrowband interference...')
-            rec, lines = self.mitigate(raw, offset=min(skip, len(raw)))
-            for f_hz, w_hz in lines:
-                print('   Removed a line at %.4f MHz (notch %.1f kHz wide)' % (f_hz / 1e6, w_hz / 1e3))
-            if not lines:
-                print('   No narrowband interference found')
-            self.lastNotchLines = lines
+            if self.iqRecord:
+                print('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
+                      % (self.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
+                raw, rec = rec, None
+                try:
+                    rec = self.convertIQ(raw)
+                finally:
+                    raw.free()
+            if self.interferenceMitigation:
+                print('   Looking for narrowband interference...')
+                raw = rec
+                rec, lines = real.mitigate(raw, offset=min(skip, len(raw)))
+                if rec is not raw:
+                    raw.free()
+                for f_hz, w_hz in lines:
+                    print('   Removed a line at %.4f MHz (notch %.1f kHz wide)' % (f_hz / 1e6, w_hz / 1e3))
+                if not lines:
+                    print('   No narrowband interference found')
+                self.lastNotchLines = lines
             print('   Acquiring satellites...')
-            acqResults = acquisition.AcquisitionResult(self)
-            acqResults.acquire(DeviceSignal(rec, skip, min(self.acquisitionLength(), max(0, len(rec) - skip))),
+            acqResults = acquisition.AcquisitionResult(real)
+            acqResults.acquire(DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip))),
                                n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
                                coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
             if not np.any(acqResults.carrFreq):
@@ -271,9 +328,8 @@ class Settings(object):
                 trackResults.showTrackingQuality()
             return acqResults, trackResults
         finally:
-            if rec is not raw:
+            if rec is not None:
                 rec.free()
-            raw.free()
 
     def acquisitionLength(self):
         """Samples postProcessing() reads for acquisition: 11 ms (the fine search needs codePhase + 10 ms), or all the
@@ -294,8 +350,8 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.interferenceMitigation:
-            acqResults, trackResults = self._mitigated_processing(name)
+        if self.iqRecord or self.interferenceMitigation:
+            acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None
             return self._navigate(acqResults, trackResults)
