@@ -76,6 +76,8 @@ struct sgx_if {
 };
 // Block until samples [0, end) of a (possibly still streaming) record are resident; returns the loader's status.
 int sgx_if_require(const sgx_if* r, size_t end);
+// A new record of n samples on the context's device (sgx_host.cpp), for the stages that write one
+int sgx_if_alloc_internal(sgx_ctx* c, size_t n, sgx_if** out);
 // Tracking (sgx_trk.hip).  kind: SGX_DT_*.  int8 / uint8 / int16 run the typed kernels (sgx_trk2 / sgx_trk3 / sgx_trk_tp);
 // every other type - and int16 / uint8 at sampling rates below 16 x the chip rate - the per-sample kernel of sgx_trk_any.hip.
 // skip_bytes: Settings.skipNumberOfBytes, or what stands in for it (sgx_trk_f32.hip tracks a narrowed copy of a window).
@@ -171,9 +173,11 @@ struct SgxSmall {
     int2 stage_bin_map[ACQ_COH_MAX_BINS];
     int trk_mag;                            // sgx_trk.hip: the record's magnitude bound
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
-    alignas(16) unsigned filter_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];   // sgx_filter.hip: (hi, lo) tap dwords; both
-    alignas(16) unsigned iq_taps[2 * 2 * (SGX_IQ_LP_MAX / 4)];   // sgx_iq.hip: (hi, lo) tap dwords of the two branches; both
+    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter or sgx_if_from_iq call, which waits before it returns; both
+    alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
 };
+static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
+              "the two branches of sgx_iq.hip fit the tap staging too");
 #define SGX_SMALL_BYTES (1 << 20)
 static_assert(sizeof(SgxSmall) <= SGX_SMALL_BYTES, "the small areas hold the layout");
 

@@ -7,103 +7,42 @@
 //   y[2p + 1] = -(-1)^p sum_d h[c + 1 - 2d] Q[p + d]      (odd outputs see only Q and the taps with k = c + 1 mod 2)
 // each rounded, shifted and clipped as sgx_if_filter does: two real polyphase FIRs over the de-interleaved bytes.
 //
-// Formulation, after fir_dot4_kernel (sgx_filter.hip): v_dot4_i32_i8 on byte windows, every int16 tap split into two signed
-// bytes (h = 256 hi + lo) that accumulate separately, all arithmetic modulo 2^32 under the contract's int32 bound.
+// The dot4 core is sgx_fir_dot4.h's, on 8-byte slots, once per branch.  Particular to this file:
 //   * Both branches are written against one image origin: g_X[j] is the tap of branch X at d = j - cp, cp = floor(c / 2)
 //     rounded up to 8, zero where the branch has no tap; Lp (a multiple of 8) covers both.  The first byte a workgroup
 //     needs, 2 (p0 - cp), is then a multiple of 16: global loads and the record's 16-byte stores are aligned.
-//   * A workgroup of 256 lanes makes IQ_TILE = 4096 output bytes = 2048 pairs.  It loads the tile's bytes plus the halo in
-//     16-byte chunks (8 pairs), XORs 0x80 into them for offset binary, splits each chunk IN REGISTERS into 8 I bytes and 8
-//     Q bytes (four v_perm_b32) and writes one 8-byte slot to each of two LDS images.  Lanes write consecutive slots and,
-//     in the filter, read consecutive slots (ds_write_b64 / ds_read_b64 over 512 contiguous bytes per wave): no bank
-//     conflict on either side - scattering single bytes into the images would put four lanes on every bank.
-//   * Lane l owns pairs 8 l .. 8 l + 7.  Per branch and step of 8 taps it reads ONE new slot, forms the 12 byte-shifted
-//     dwords of its 16-byte window (3 aligned, 9 one v_alignbyte_b32 each) and issues 32 dot4 (8 outputs x 2 tap dwords x
-//     hi / lo).  A branch runs only over the steps that hold a non-zero tap, so the single-tap branch of a half-band
-//     design costs one step.  The 8 + 8 results are interleaved in registers and leave as one 16-byte store.
-// Bounds: global reads are guarded per 16-byte chunk (bytes outside [0, N) are zero, never read); stores are guarded per
-// lane (a 16-byte store only when all 16 outputs exist, byte stores on the record's last partial group).
+//   * A workgroup makes FIR_TILE output bytes = 2048 pairs.  It loads the tile's bytes plus the halo in 16-byte chunks (8
+//     pairs), XORs 0x80 into them for offset binary, splits each chunk IN REGISTERS into 8 I bytes and 8 Q bytes (four
+//     v_perm_b32) and writes one 8-byte slot to each of two LDS images.  Lanes write consecutive slots and, in the filter,
+//     read consecutive slots (ds_write_b64 / ds_read_b64 over 512 contiguous bytes per wave): no bank conflict on either
+//     side - scattering single bytes into the images would put four lanes on every bank.
+//   * Lane l owns pairs 8 l .. 8 l + 7.  Per branch and step of 8 taps it reads one slot, forms 12 window dwords (9
+//     v_alignbyte_b32) and issues 32 dot4.  A branch runs only over the steps that hold a non-zero tap, so the single-tap
+//     branch of a half-band design costs one step.  The 8 + 8 results are interleaved in registers and leave as one
+//     16-byte store.
 #include <math.h>
 
-#include "sgx_internal.h"
+#include "sgx_fir_dot4.h"
 
-int sgx_if_alloc_internal(sgx_ctx* c, size_t n, sgx_if** out);
-
-#define IQ_THREADS 256
-#define IQ_PAIRS_PER_LANE 8
-#define IQ_TILE_PAIRS (IQ_THREADS * IQ_PAIRS_PER_LANE)
-#define IQ_TILE (2 * IQ_TILE_PAIRS)                             // output bytes per workgroup
+#define IQ_TILE_PAIRS (FIR_TILE / 2)
 #define IQ_MAX_LP SGX_IQ_LP_MAX                                 // 136: cp = 64, d up to 64, rounded up to 8
 #define IQ_SLOTS ((IQ_TILE_PAIRS + IQ_MAX_LP) / 8)              // 8-byte slots per image
 static_assert(((((SGX_IQ_MAX_TAPS - 1) / 4 + 7) / 8) * 8 + (SGX_IQ_MAX_TAPS + 1) / 4 + 1 + 7) / 8 * 8 <= IQ_MAX_LP,
               "the padded branch length of the longest filter fits the staging area and the LDS images");
 
-// 8 outputs of one branch: acc[r] = sum over steps [q_lo, q_hi) of g[8 q + t] image[8 (lane + q) + r + t]
-__device__ __forceinline__ void iq_branch(const uint2* s_x, const uint2* __restrict__ taps, int q_lo, int q_hi,
-                                          int (&sum)[IQ_PAIRS_PER_LANE]) {
-    int acc_hi[IQ_PAIRS_PER_LANE], acc_lo[IQ_PAIRS_PER_LANE];
-#pragma unroll
-    for (int r = 0; r < IQ_PAIRS_PER_LANE; ++r) acc_hi[r] = acc_lo[r] = 0;
-    if (q_lo < q_hi) {
-        unsigned w[4];
-        {
-            const uint2 v = s_x[threadIdx.x + q_lo];
-            w[2] = v.x, w[3] = v.y;
-        }
-        for (int q = q_lo; q < q_hi; ++q) {
-            w[0] = w[2], w[1] = w[3];
-            const uint2 v = s_x[threadIdx.x + q + 1];
-            w[2] = v.x, w[3] = v.y;
-            unsigned win[12];   // win[b] = image bytes [8 (lane + q) + b, + 4)
-#pragma unroll
-            for (int b = 0; b < 12; ++b)
-                win[b] = (b & 3) ? __builtin_amdgcn_alignbyte(w[(b >> 2) + 1], w[b >> 2], b & 3) : w[b >> 2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const uint2 g = taps[2 * q + t];   // wave-uniform
-#pragma unroll
-                for (int r = 0; r < IQ_PAIRS_PER_LANE; ++r) {
-                    acc_hi[r] = __builtin_amdgcn_sdot4((int)win[4 * t + r], (int)g.x, acc_hi[r], false);
-                    acc_lo[r] = __builtin_amdgcn_sdot4((int)win[4 * t + r], (int)g.y, acc_lo[r], false);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < IQ_PAIRS_PER_LANE; ++r) sum[r] = (int)(((unsigned)acc_hi[r] << 8) + (unsigned)acc_lo[r]);
-}
-
-__device__ __forceinline__ unsigned iq_round_clip(int sum, bool negate, long long rnd, int shift) {
-    // (exact: the contract bounds |sum| below 2^31, so the negation cannot overflow; rounding in 64 bits as the contract)
-    const long long s = (negate ? -(long long)sum : (long long)sum) + rnd;
-    int v = (int)(s >> shift);
-    v = v < -127 ? -127 : (v > 127 ? 127 : v);
-    return (unsigned)(v & 0xFF);
-}
-
 // taps: [2][lp / 4] pairs (hi dword, lo dword), the even-output (I) branch first; byte j of dword q = tap g[4 q + j].
 // steps: (first, end) step of the I branch in x, y and of the Q branch in z, w.  flip: 0x80808080 for offset binary.
-__global__ __launch_bounds__(IQ_THREADS) void iq_to_if_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
-                                                              unsigned long long n, const uint2* __restrict__ taps,
-                                                              int lp, int cp, int4 steps, int shift, unsigned flip,
-                                                              int q_first) {
+__global__ __launch_bounds__(FIR_THREADS) void iq_to_if_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
+                                                               unsigned long long n, const uint2* __restrict__ taps,
+                                                               int lp, int cp, int4 steps, int shift, unsigned flip,
+                                                               int q_first) {
     __shared__ uint2 s_i[IQ_SLOTS];
     __shared__ uint2 s_q[IQ_SLOTS];
-    const unsigned long long n0 = (unsigned long long)blockIdx.x * IQ_TILE;
+    const unsigned long long n0 = (unsigned long long)blockIdx.x * FIR_TILE;
     const int slots = (IQ_TILE_PAIRS + lp) / 8;
     // image byte i of a component = that component of pair n0 / 2 - cp + i; chunk i holds the pairs of slot i
-    for (int i = threadIdx.x; i < slots; i += IQ_THREADS) {
-        const long long a = (long long)n0 - 2ll * cp + 16ll * i;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (a >= 0 && (unsigned long long)a + 16 <= n) {
-            v = *reinterpret_cast<const uint4*>(x + a);
-            v.x ^= flip, v.y ^= flip, v.z ^= flip, v.w ^= flip;
-        } else if (a >= 0 && (unsigned long long)a < n) {
-            unsigned w[4] = {0u, 0u, 0u, 0u};
-            const int left = (int)(n - (unsigned long long)a);   // 2 .. 14
-            for (int b = 0; b < left; ++b) w[b >> 2] |= (((unsigned)(uint8_t)x[a + b]) ^ (flip & 0xFFu)) << ((b & 3) * 8);
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+    for (int i = threadIdx.x; i < slots; i += FIR_THREADS) {
+        const uint4 v = fir_load_chunk(x, (long long)n0 - 2ll * cp + 16ll * i, n, flip);
         // v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first
         const uint2 even = make_uint2(__builtin_amdgcn_perm(v.y, v.x, 0x06040200u), __builtin_amdgcn_perm(v.w, v.z, 0x06040200u));
         const uint2 odd = make_uint2(__builtin_amdgcn_perm(v.y, v.x, 0x07050301u), __builtin_amdgcn_perm(v.w, v.z, 0x07050301u));
@@ -112,20 +51,20 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_to_if_kernel(const int8_t* __re
     }
     __syncthreads();
 
-    int sum_i[IQ_PAIRS_PER_LANE], sum_q[IQ_PAIRS_PER_LANE];
-    iq_branch(s_i, taps, steps.x, steps.y, sum_i);
-    iq_branch(s_q, taps + lp / 4, steps.z, steps.w, sum_q);
+    int sum_i[8], sum_q[8];
+    fir_steps<8>(s_i, taps, steps.x, steps.y, sum_i);
+    fir_steps<8>(s_q, taps + lp / 4, steps.z, steps.w, sum_q);
 
     const long long rnd = shift ? (1ll << (shift - 1)) : 0ll;
     unsigned out[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int r = 0; r < IQ_PAIRS_PER_LANE; ++r) {
+    for (int r = 0; r < 8; ++r) {
         // the tile starts on an even pair and a lane on a multiple of 8: (-1)^p = (-1)^r
-        const unsigned e = iq_round_clip(sum_i[r], (r & 1) != 0, rnd, shift);
-        const unsigned o = iq_round_clip(sum_q[r], (r & 1) == 0, rnd, shift);
+        const unsigned e = fir_round_clip(sum_i[r], (r & 1) != 0, rnd, shift);
+        const unsigned o = fir_round_clip(sum_q[r], (r & 1) == 0, rnd, shift);
         out[r >> 1] |= (e | (o << 8)) << ((r & 1) * 16);
     }
-    const unsigned long long o = n0 + (unsigned long long)threadIdx.x * (2 * IQ_PAIRS_PER_LANE);
+    const unsigned long long o = n0 + 16ull * threadIdx.x;
     if (o + 16 <= n) {
         *reinterpret_cast<uint4*>(y + o) = make_uint4(out[0], out[1], out[2], out[3]);
     } else {
@@ -155,7 +94,7 @@ extern "C" int sgx_iq_design(int32_t n_taps, int16_t* taps, int32_t* shift) {
 
 extern "C" int sgx_iq_tile(int32_t* tile_bytes) {
     SGX_CHECK_ARG(tile_bytes);
-    *tile_bytes = IQ_TILE;
+    *tile_bytes = FIR_TILE;
     return SGX_OK;
 }
 
@@ -166,19 +105,8 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
     SGX_CHECK_ARG(n_taps >= 1 && n_taps <= SGX_IQ_MAX_TAPS && (n_taps & 1) == 1);
     SGX_CHECK_ARG(shift >= 0 && shift <= 30);
     SGX_CHECK_ARG((flags & ~(SGX_IQ_Q_FIRST | SGX_IQ_OFFSET_BINARY)) == 0);
-    long long sum_abs = 0;
-    for (int k = 0; k < n_taps; ++k) {
-        const int a = taps[k] < 0 ? -(int)taps[k] : (int)taps[k];
-        if (a > 32512) {
-            sgx_set_error("bad argument: |taps[%d]| = %d > 32512 (a tap must split into two signed bytes)", k, a);
-            return SGX_E_ARG;
-        }
-        sum_abs += a;
-    }
-    if (128 * sum_abs >= (1ll << 31)) {
-        sgx_set_error("bad argument: 128 sum|taps| = %lld >= 2^31 (the int32 accumulator)", 128 * sum_abs);
-        return SGX_E_ARG;
-    }
+    const int bad = fir_check_taps(taps, n_taps);
+    if (bad != SGX_OK) return bad;
     SGX_CHECK_ARG(c && iq_bytes && out);
     if (iq_bytes->n & 1) {
         sgx_set_error("bad argument: an I/Q record holds whole pairs, not %zu bytes", iq_bytes->n);
@@ -194,8 +122,7 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
     const int L = n_taps, cc = (L - 1) / 2;
     const int cp = ((cc / 2 + 7) / 8) * 8;
     const int lp = ((cp + (cc + 1) / 2 + 1 + 7) / 8) * 8;
-    uint2* h_taps = reinterpret_cast<uint2*>(c->h_small->iq_taps);
-    memset(h_taps, 0, (size_t)(2 * lp / 4) * sizeof(uint2));
+    uint2* g = fir_tap_image(c, 2 * lp / 4);
     int4 steps = make_int4(lp / 8, 0, lp / 8, 0);
     for (int br = 0; br < 2; ++br) {
         int* lo_step = br ? &steps.z : &steps.x;
@@ -203,45 +130,21 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
         for (int j = 0; j < lp; ++j) {
             const int k = cc + br - 2 * (j - cp);
             if (k < 0 || k >= L || taps[k] == 0) continue;
-            const int h = taps[k];
-            const int hi = (h + 128) >> 8, lo = h - 256 * hi;
-            uint2& g = h_taps[br * (lp / 4) + (j >> 2)];
-            g.x |= ((unsigned)(hi & 0xFF)) << ((j & 3) * 8);
-            g.y |= ((unsigned)(lo & 0xFF)) << ((j & 3) * 8);
+            fir_pack_tap(g + br * (lp / 4), j, taps[k]);
             if (j / 8 < *lo_step) *lo_step = j / 8;
             if (j / 8 + 1 > *end_step) *end_step = j / 8 + 1;
         }
         if (*end_step == 0) *lo_step = 0;   // a branch without a tap: no step
     }
-    sgx_if* r = nullptr;
-    const int rc = sgx_if_alloc_internal(c, iq_bytes->n, &r);
-    if (rc != SGX_OK) return rc;
-    uint2* d_taps = reinterpret_cast<uint2*>(c->d_small->iq_taps);
-    hipError_t err = hipMemcpyAsync(d_taps, h_taps, (size_t)(2 * lp / 4) * sizeof(uint2), hipMemcpyHostToDevice, c->stream);
-    c->iq_kernel_ms = 0.0f;
-    const unsigned long long blocks = ((unsigned long long)iq_bytes->n + IQ_TILE - 1) / IQ_TILE;
-    if (err == hipSuccess && blocks > 0x7FFFFFFFull) {
-        sgx_if_free(c, r);
-        sgx_set_error("record of %zu bytes is beyond one launch of the I/Q converter", iq_bytes->n);
-        return SGX_E_ARG;
-    }
-    if (err == hipSuccess && blocks) {
-        hipEventRecord(c->ev[0], c->stream);
-        iq_to_if_kernel<<<(unsigned)blocks, IQ_THREADS, 0, c->stream>>>(
-            iq_bytes->d, r->d, (unsigned long long)iq_bytes->n, d_taps, lp, cp, steps, shift,
-            (flags & SGX_IQ_OFFSET_BINARY) ? 0x80808080u : 0u, (flags & SGX_IQ_Q_FIRST) ? 1 : 0);
-        hipEventRecord(c->ev[1], c->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);   // (h_small's staging is free again on return)
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_if_free(c, r);
-        sgx_set_error("I/Q conversion kernel failed: %s", hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    if (blocks) hipEventElapsedTime(&c->iq_kernel_ms, c->ev[0], c->ev[1]);
-    *out = r;
-    return SGX_OK;
+    return fir_run(
+        c, iq_bytes->n, 2 * lp / 4,
+        [&](unsigned blocks, sgx_if* r, const uint2* d_taps) {
+            iq_to_if_kernel<<<blocks, FIR_THREADS, 0, c->stream>>>(
+                iq_bytes->d, r->d, (unsigned long long)iq_bytes->n, d_taps, lp, cp, steps, shift,
+                (flags & SGX_IQ_OFFSET_BINARY) ? 0x80808080u : 0u, (flags & SGX_IQ_Q_FIRST) ? 1 : 0);
+        },
+        &c->iq_kernel_ms, "record of %zu bytes is beyond one launch of the I/Q converter", "I/Q conversion kernel failed: %s",
+        out);
 }
 
 extern "C" int sgx_iq_timing(sgx_ctx* c, float* kernel_ms) {

@@ -2,8 +2,6 @@
 // Integer arithmetic only. HBM-write bound: 16 samples per lane, one 16-byte store each.
 #include "sgx_internal.h"
 
-int sgx_if_alloc_internal(sgx_ctx* c, size_t n, sgx_if** out);
-
 #define GOLDEN 0x9E3779B97F4A7C15ull
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {

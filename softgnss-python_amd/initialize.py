@@ -3,6 +3,7 @@
 The three helpers the hot path calls - generateCAcode, makeCaTable, calcLoopCoef - are answered
 by libsgx.so's exact host routines (include/sgx.h), not by Python arithmetic.
 """
+import contextlib
 import copy
 import ctypes as C
 import datetime
@@ -270,12 +271,69 @@ class Settings(object):
         taps, shift = _native.iq_design(self.iqTaps)
         return record.ctx.iq_to_if(record, taps, shift, q_first=q_first, offset_binary=offset_binary)
 
+    @contextlib.contextmanager
+    def _prepared_record(self, name, offset, count, mitigate_at=None, verbose=False):
+        """Bytes [offset, offset + count) of a record file, uploaded once and prepared on the GPU, for the length of the
+        block: with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation)
+        cleared of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the
+        real rate.  Yields the prepared record, to be read under realEquivalent(), and frees it afterwards."""
+        from . import engine
+        say = print if verbose else (lambda *args: None)
+        real = self.realEquivalent() if self.iqRecord else self
+        rec = engine.get_context(real, None).upload_file(name, offset, count)
+        try:
+            if self.iqRecord:
+                say('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
+                    % (self.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
+                raw, rec = rec, None
+                try:
+                    rec = self.convertIQ(raw)
+                finally:
+                    raw.free()
+            if mitigate_at is not None:
+                say('   Looking for narrowband interference...')
+                raw = rec
+                rec, lines = real.mitigate(raw, offset=min(mitigate_at, len(raw)))
+                if rec is not raw:
+                    raw.free()
+                for f_hz, w_hz in lines:
+                    say('   Removed a line at %.4f MHz (notch %.1f kHz wide)' % (f_hz / 1e6, w_hz / 1e3))
+                if not lines:
+                    say('   No narrowband interference found')
+                self.lastNotchLines = lines
+            yield rec
+        finally:
+            if rec is not None:
+                rec.free()
+
+    def _acquire_and_track(self, results, acq_source, track_source):
+        """postProcessing()'s acquire -> preRun -> track.  results: the settings the results carry (self, or
+        realEquivalent()); the sources: an ndarray and the open record file, or a DeviceSignal and a DeviceFile.  Returns
+        (acqResults, trackResults), trackResults None where no satellite was found."""
+        from . import acquisition, tracking
+        print('   Acquiring satellites...')
+        acqResults = acquisition.AcquisitionResult(results)
+        acqResults.acquire(acq_source, n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
+                           coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
+        if not np.any(acqResults.carrFreq):
+            print('No GNSS signals detected, signal processing finished.')
+            return acqResults, None
+        acqResults.preRun()
+        acqResults.showChannelStatus()
+        trackResults = tracking.TrackingResult(acqResults)
+        start = datetime.datetime.now()
+        print('   Tracking started at %s' % start.strftime('%X'))
+        trackResults.track(track_source)
+        self.lastTrackingSeconds = (datetime.datetime.now() - start).total_seconds()
+        print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
+        if self.lockDetector and trackResults.has_results():
+            trackResults.showTrackingQuality()
+        return acqResults, trackResults
+
     def _resident_processing(self, name):
-        """postProcessing()'s acquire -> preRun -> track on a record that is uploaded once and prepared on the GPU: with
-        iqRecord converted to real IF, with interferenceMitigation cleared of narrowband lines - the conversion first, the
-        notch is designed at the real rate - and both stages read the prepared record where it lies.  The results carry
-        realEquivalent(): positions are samples of the prepared record, which are bytes of the file."""
-        from . import acquisition, engine, tracking
+        """postProcessing()'s acquire -> preRun -> track on a record that _prepared_record uploads once and prepares on the
+        GPU; both stages read the prepared record where it lies.  The results carry realEquivalent(): positions are samples
+        of the prepared record, which are bytes of the file."""
         from .record import DeviceFile, DeviceSignal
         real = self.realEquivalent() if self.iqRecord else self
         n = real.samplesPerCode
@@ -286,50 +344,9 @@ class Settings(object):
             if skip % 2:
                 raise ValueError("skipNumberOfBytes = %d splits an I/Q pair: it must be even" % skip)
             need += need % 2
-        ctx = engine.get_context(real, None)
-        rec = ctx.upload_file(name, 0, need)
-        try:
-            if self.iqRecord:
-                print('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
-                      % (self.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
-                raw, rec = rec, None
-                try:
-                    rec = self.convertIQ(raw)
-                finally:
-                    raw.free()
-            if self.interferenceMitigation:
-                print('   Looking for narrowband interference...')
-                raw = rec
-                rec, lines = real.mitigate(raw, offset=min(skip, len(raw)))
-                if rec is not raw:
-                    raw.free()
-                for f_hz, w_hz in lines:
-                    print('   Removed a line at %.4f MHz (notch %.1f kHz wide)' % (f_hz / 1e6, w_hz / 1e3))
-                if not lines:
-                    print('   No narrowband interference found')
-                self.lastNotchLines = lines
-            print('   Acquiring satellites...')
-            acqResults = acquisition.AcquisitionResult(real)
-            acqResults.acquire(DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip))),
-                               n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
-                               coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
-            if not np.any(acqResults.carrFreq):
-                print('No GNSS signals detected, signal processing finished.')
-                return acqResults, None
-            acqResults.preRun()
-            acqResults.showChannelStatus()
-            trackResults = tracking.TrackingResult(acqResults)
-            start = datetime.datetime.now()
-            print('   Tracking started at %s' % start.strftime('%X'))
-            trackResults.track(DeviceFile(rec))
-            self.lastTrackingSeconds = (datetime.datetime.now() - start).total_seconds()
-            print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
-            if self.lockDetector and trackResults.has_results():
-                trackResults.showTrackingQuality()
-            return acqResults, trackResults
-        finally:
-            if rec is not None:
-                rec.free()
+        with self._prepared_record(name, 0, need, skip if self.interferenceMitigation else None, verbose=True) as rec:
+            window = DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip)))
+            return self._acquire_and_track(real, window, DeviceFile(rec))
 
     def acquisitionLength(self):
         """Samples postProcessing() reads for acquisition: 11 ms (the fine search needs codePhase + 10 ms), or all the
@@ -341,7 +358,6 @@ class Settings(object):
         initialize.py:420-515 without the plots and without the .npy cache of the tracking results.
         Returns (acqResults, trackResults, navResults); navResults.solutions is unset when the record is too short
         or too few satellites carry ephemerides, as in the reference."""
-        from . import acquisition, tracking
         print('Starting processing...')
         name = self.fileName if not fileNameStr else fileNameStr
         if not isinstance(name, str):
@@ -358,23 +374,9 @@ class Settings(object):
         with open(name, 'rb') as fid:
             fid.seek(self.skipNumberOfBytes, 0)
             data = np.fromfile(fid, self.dataType, self.acquisitionLength())
-            print('   Acquiring satellites...')
-            acqResults = acquisition.AcquisitionResult(self)
-            acqResults.acquire(data, n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent),
-                               coherent_ms=int(self.acqCoherentMs), bin_step_hz=self.acqBinStep)
-            if not np.any(acqResults.carrFreq):
-                print('No GNSS signals detected, signal processing finished.')
-                return acqResults, None, None
-            acqResults.preRun()
-            acqResults.showChannelStatus()
-            trackResults = tracking.TrackingResult(acqResults)
-            start = datetime.datetime.now()
-            print('   Tracking started at %s' % start.strftime('%X'))
-            trackResults.track(fid)
-            self.lastTrackingSeconds = (datetime.datetime.now() - start).total_seconds()
-            print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
-            if self.lockDetector and trackResults.has_results():
-                trackResults.showTrackingQuality()
+            acqResults, trackResults = self._acquire_and_track(self, data, fid)
+        if trackResults is None:
+            return acqResults, None, None
         return self._navigate(acqResults, trackResults)
 
     @staticmethod

@@ -25,19 +25,11 @@ from . import initialize
 
 def probe_iq(settings):
     """probeData() of an I/Q file: the first 10 code periods converted on the GPU, probed as the real record they become."""
-    from . import engine
     from .record import DeviceSignal
     real = settings.realEquivalent()
     skip = int(settings.skipNumberOfBytes)
-    raw = engine.get_context(real, None).upload_file(settings.fileName, skip - skip % 2, 10 * real.samplesPerCode)
-    try:
-        rec = settings.convertIQ(raw)
-        try:
-            return real.probeData(DeviceSignal(rec))
-        finally:
-            rec.free()
-    finally:
-        raw.free()
+    with settings._prepared_record(settings.fileName, skip - skip % 2, 10 * real.samplesPerCode) as rec:
+        return real.probeData(DeviceSignal(rec))
 
 
 def main(argv=None):

@@ -10,7 +10,7 @@ import iq_cases as cases
 import iq_spec as spec
 from conftest import pkg
 from oracle import softgnss_oracle as orc
-from test_gpu_parity import TRK_TOL      # max |delta| of the correlator series over max(1, RMS |P|) per channel
+from record_stage import full_scale, same_tracking
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +32,6 @@ def tile():
 
 def lengths(tile):
     return [2, 4, 6, 254, 510, 4098, 65538, tile - 2, tile, tile + 2, 3 * tile + 2]
-
-
-def full_scale(rng, n):
-    x = rng.integers(-128, 128, n).astype(np.int8)
-    x[::97] = -128
-    x[5::101] = 127
-    return x
 
 
 def dense_taps(rng, L, S):
@@ -248,13 +241,7 @@ def _same_search(a, ref):
 
 
 def _same_tracking(t, series):
-    assert t.series.shape == series.shape == (len(SCENE.prns), 13, TRK_MS)
-    assert np.array_equal(t.series[:, 0], series[:, 0])                 # absoluteSample: every block boundary
-    worst = 0.0
-    for ch in range(series.shape[0]):
-        scale = max(1.0, float(np.sqrt(np.mean(series[ch, 3] ** 2 + series[ch, 7] ** 2))))
-        worst = max(worst, float(np.max(np.abs(t.series[ch, 3:9] - series[ch, 3:9]))) / scale)
-    assert worst < TRK_TOL, worst
+    same_tracking(t, series, len(SCENE.prns), TRK_MS)
 
 
 def test_scene_converts_acquires_and_tracks_as_the_oracle(reference):

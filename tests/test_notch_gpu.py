@@ -10,10 +10,10 @@ import notch_cases as cases
 import notch_spec as spec
 from conftest import pkg
 from oracle import softgnss_oracle as orc
+from record_stage import full_scale, same_tracking
 
 pytestmark = pytest.mark.gpu
 
-TRK_TOL = 1e-6      # tests/test_gpu_parity.py: max |delta| of the correlator series over max(1, RMS |P|) per channel
 TRK_MS = 100
 
 
@@ -49,13 +49,6 @@ def fine_taps(rng, L, S):
     pos = rng.choice(L, size=min(L, 4), replace=False)
     h[pos] = rng.choice([-1, 1], size=pos.size)
     return h
-
-
-def full_scale(rng, n):
-    x = rng.integers(-128, 128, n).astype(np.int8)
-    x[::97] = -128
-    x[5::101] = 127
-    return x
 
 
 def run(ctx, x, h, S):
@@ -139,6 +132,21 @@ def test_many_workgroups_and_tile_seams(ctx):
     assert ga.tobytes() == want.tobytes(), "first difference at sample %d" % int(np.flatnonzero(ga != want)[0])
     assert ga.tobytes() == gb.tobytes()
     assert ctx.filter_timing() > 0.0
+
+
+@pytest.mark.parametrize("L", [3, 255])
+def test_lengths_around_a_tile_seam(ctx, L):
+    """The load and store guards where they can be wrong: a record that ends one sample before, on and one sample after a
+    16-byte group and a workgroup's tile (_native.iq_tile(): the tile the two stages share)."""
+    tile = pkg()._native.iq_tile()
+    rng = np.random.default_rng(2000 + L)
+    for h in (fine_taps(rng, L, 14), random_taps(rng, L, 40000 * L)):
+        for n in (15, 16, 17, tile - 1, tile, tile + 1, 3 * tile + 1):
+            x = full_scale(rng, n)
+            want = spec.apply(x, h, 14)
+            got = run(ctx, x, h, 14)
+            assert got.tobytes() == want.tobytes(), \
+                "N = %d: first difference at sample %d" % (n, int(np.flatnonzero(got != want)[0]))
 
 
 def test_refusals_on_the_device(ctx):
@@ -225,13 +233,7 @@ def test_tracking_on_the_mitigated_record(mitigated):
     t = m.TrackingResult(a, device=0)
     t.track(m.DeviceFile(new))
     series = orc.stack_series(orc.track(os_, chans_ref, want))
-    assert t.series.shape == series.shape == (8, 13, TRK_MS)
-    assert np.array_equal(t.series[:, 0], series[:, 0])                 # every block boundary
-    worst = 0.0
-    for ch in range(8):
-        scale = max(1.0, float(np.sqrt(np.mean(series[ch, 3] ** 2 + series[ch, 7] ** 2))))
-        worst = max(worst, float(np.max(np.abs(t.series[ch, 3:9] - series[ch, 3:9]))) / scale)
-    assert worst < TRK_TOL, worst
+    same_tracking(t, series, 8, TRK_MS)
     assert np.max(np.abs(t.series[:, 1] - series[:, 1])) < 1e-6        # codeFreq, Hz
 
 
