@@ -1568,6 +1568,35 @@ static int acq_corr_carve(sgx_ctx* c, AcqCorr* k, size_t pow_need) {
     k->power = (double*)(red + red_bytes);
     return SGX_OK;
 }
+// The scratch of such a correlation - two intermediates of work_rows rows (the forward batch's rows at least) and d_fwd =
+// [forward | code] spectra - and its AcqCorr.  power_rows: room behind the reductions for the round-4 sequence's second-peak
+// power rows.
+static int acq_corr_setup(sgx_ctx* c, AcqCorr* k, int n_prn, int n_bins, int n_phi, int n_blocks, int noncoh, bool top2,
+                          size_t work_rows, bool power_rows) {
+    const size_t N = (size_t)c->n_code, row_bytes = sizeof(cplx) * N;
+    const size_t rows_fwd = (size_t)n_blocks * n_phi;
+    if (work_rows < rows_fwd + n_prn) work_rows = rows_fwd + n_prn;
+    int rc;
+    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
+    k->n_bins = n_bins;
+    k->n_phi = n_phi;
+    k->n_blocks = n_blocks;
+    k->noncoh = noncoh;
+    k->out_per_prn = noncoh ? n_bins : n_blocks * n_bins;
+    k->rows_out_all = n_prn * k->out_per_prn;
+    k->nblk = sgx_fft4_row_blocks();
+    k->nres = sgx_fft4_residues();
+    k->top2 = top2;
+    k->d_codefd = c->d_fwd + rows_fwd * N;
+    size_t pow_need = 0;
+    if (power_rows) {
+        pow_need = (size_t)k->rows_out_all * k->nblk * 12 + 4096;
+        if (noncoh && pow_need < (size_t)n_prn * sizeof(double) * N) pow_need = (size_t)n_prn * sizeof(double) * N;
+    }
+    return acq_corr_carve(c, k, pow_need);
+}
 
 // One correlation batch: PRNs [p0, p0 + np) x bins [bin0, bin0 + nb) x blocks [blk0, blk0 + nblocks) -> its Fft4Fuse (a
 // run of bins is a batch of its own with fewer bins; a run of blocks reads its blocks' forward rows) and the transform,
@@ -1673,9 +1702,24 @@ static int acquire_fine(const AcqCall& a, const AcqDets& det, long long* d_sum, 
         // two kernels with LDS-resident sub-transforms, input built on the fly (the mean comes from the device-side
         // sum: no host look), arg-max fused (sgx_fft.hip)
         nblk = sgx_fft_fine_partials();
-        rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, det.prn.data(), det.phase.data(), n_det, len, d_sum,
-                                 (double)n_samples, ts, tc1, c->d_fine[0], win_lo, win_hi, dsm->fine_pv, dsm->fine_pi, st,
-                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, d_win);
+        FineSearch f;
+        f.x = x;
+        f.codes = c->d_codes;
+        f.len = len;
+        f.d_sum = d_sum;
+        f.n_mean = (double)n_samples;
+        f.ts = ts;
+        f.tc1 = tc1;
+        f.work = c->d_fine[0];
+        f.n_det = n_det;
+        f.det_prn = det.prn.data();
+        f.det_phase = det.phase.data();
+        f.lo = win_lo;
+        f.hi = win_hi;
+        f.win = d_win;
+        f.pv = dsm->fine_pv;
+        f.pi = dsm->fine_pi;
+        rc = sgx_fft_fine_search(&c->plan_fine, f, st);
         if (rc != SGX_OK) return rc;
     } else {
         SGX_HIP(hipMemcpyAsync(dsm->det_prn, det.prn.data(), sizeof(int) * (size_t)n_det, hipMemcpyHostToDevice, st));
@@ -1728,6 +1772,16 @@ static int acq_fine_and_times(const AcqCall& a, const AcqDets& det, long long* d
     if (rc != SGX_OK) return rc;
     acq_event_times(a.c, true);
     return SGX_OK;
+}
+// ... behind the host's look at the page the publish kernel wrote with `seq`, decoded into the detections
+static int acq_host_tail(const AcqCall& a, unsigned long long seq, long long* d_sum, const CohGrid* g) {
+    const CoarseLook* look = (const CoarseLook*)a.c->h_look;
+    int rc = coarse_look_wait(a.c, &look->seq, seq, a.env.spin);
+    if (rc != SGX_OK) return rc;
+    AcqDets det;
+    rc = acq_look_decode(a, look->po, look->second, 0, a.n_prn, &det);
+    if (rc != SGX_OK) return rc;
+    return acq_fine_and_times(a, det, d_sum, g);
 }
 
 // ================================ the three paths ================================
@@ -1962,30 +2016,14 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
     const AcqPlan plan = acq_plan(n_prn, n_bins, n_blocks, noncoh != 0, a.env.chunk_rows, a.env.one_queue ? 1 : 2);
     const bool two_q = plan.queues == 2;
     const int bin_runs = plan.bin_runs, prn_chunk = plan.prn_chunk;
-    const size_t row_bytes = sizeof(cplx) * (size_t)N;
     size_t work_rows = (size_t)prn_chunk * rows_per_prn;
-    if (work_rows < (size_t)(rows_fwd + n_prn)) work_rows = (size_t)(rows_fwd + n_prn);
     if (work_rows < (size_t)n_prn * (noncoh ? n_blocks : 1)) work_rows = (size_t)n_prn * (noncoh ? n_blocks : 1);
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
-    AcqCorr k;
-    k.n_bins = n_bins;
-    k.n_phi = n_phi;
-    k.n_blocks = n_blocks;
-    k.noncoh = noncoh;
-    k.out_per_prn = noncoh ? n_bins : rows_per_prn;
-    k.rows_out_all = n_prn * k.out_per_prn;
-    k.nblk = sgx_fft4_row_blocks();
-    k.nres = sgx_fft4_residues();
     // Round 5: peak and second peak from ONE pass (acq_rowtop2_peak_kernel) when the exclusion list leaves out fewer than
     // `nres` consecutive indices (2 spc of them at most: any sampling rate below 111 MHz); SGX_ACQ_TOP2=0: the round-4
     // sequence, which transforms each PRN's winning row a second time
-    k.top2 = 2 * spc + 1 <= k.nres && !a.env.top2_off;
-    k.d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
-    size_t pow_need = (size_t)k.rows_out_all * k.nblk * 12 + 4096;
-    if (noncoh && pow_need < (size_t)n_prn * sizeof(double) * (size_t)N) pow_need = (size_t)n_prn * sizeof(double) * (size_t)N;
-    if ((rc = acq_corr_carve(c, &k, pow_need)) != SGX_OK) return rc;
+    const bool top2 = 2 * spc + 1 <= sgx_fft4_residues() && !a.env.top2_off;
+    AcqCorr k;
+    if ((rc = acq_corr_setup(c, &k, n_prn, n_bins, n_phi, n_blocks, noncoh, top2, work_rows, true)) != SGX_OK) return rc;
 
     SgxSmall* dsm = c->d_small;
     long long* d_sum = &dsm->sum;
@@ -2109,10 +2147,28 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
     if (a.env.split_event || !device_led) hipEventRecord(c->ev[1], st);
     SGX_HIP(hipGetLastError());
     if (device_led) {
-        rc = sgx_fft_fine_search(&c->plan_fine, x, c->d_codes, nullptr, nullptr, n_prn, fg.len, d_sum, (double)n_samples, ts,
-                                 1.0 / S.codeFreqBasis, c->d_fine[0], 4, fg.uniq - 5, dsm->fine_pv, dsm->fine_pi, st, &dsm->det,
-                                 d_look->fine_bi, &d_look->seq2, seq, reinterpret_cast<const int*>(d_stage),
-                                 reinterpret_cast<int*>(d_look), (int)(offsetof(CoarseLook, fine_bi) / sizeof(int)));
+        FineSearch f;
+        f.x = x;
+        f.codes = c->d_codes;
+        f.len = fg.len;
+        f.d_sum = d_sum;
+        f.n_mean = (double)n_samples;
+        f.ts = ts;
+        f.tc1 = 1.0 / S.codeFreqBasis;
+        f.work = c->d_fine[0];
+        f.n_det = n_prn;
+        f.lo = 4;
+        f.hi = fg.uniq - 5;
+        f.d_det = &dsm->det;
+        f.stage_src = reinterpret_cast<const int*>(d_stage);
+        f.stage_dst = reinterpret_cast<int*>(d_look);
+        f.stage_words = (int)(offsetof(CoarseLook, fine_bi) / sizeof(int));
+        f.out_bi = d_look->fine_bi;
+        f.out_seq = &d_look->seq2;
+        f.seq = seq;
+        f.pv = dsm->fine_pv;
+        f.pi = dsm->fine_pi;
+        rc = sgx_fft_fine_search(&c->plan_fine, f, st);
         if (rc != SGX_OK) return rc;
         hipEventRecord(c->ev[2], st);
         SGX_HIP(hipGetLastError());
@@ -2130,13 +2186,7 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
         if (defer) return SGX_OK;
         return sgx_acquire_finish(c, a.carrFreq, a.codePhase, a.peakMetric, a.freqBin, a.fineIdx);
     }
-    const CoarseLook* look = (const CoarseLook*)c->h_look;
-    rc = coarse_look_wait(c, &look->seq, seq, a.env.spin);
-    if (rc != SGX_OK) return rc;
-    AcqDets det;
-    rc = acq_look_decode(a, look->po, look->second, 0, n_prn, &det);
-    if (rc != SGX_OK) return rc;
-    return acq_fine_and_times(a, det, d_sum, nullptr);
+    return acq_host_tail(a, seq, d_sum, nullptr);
 }
 
 // The host's ONE look at a device-led acquisition (queued by acquire_four_step; c->acq_pending says what was asked): waits
@@ -2216,30 +2266,14 @@ static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
     const int rows_fwd = M * n_phi;
     const int rows_per_prn = M * n_bins;
     const int run_rows = g.runs == 1 ? g.prn_chunk * rows_per_prn : g.per_run * (noncoh ? M : n_bins);
-    const size_t row_bytes = sizeof(cplx) * (size_t)N;
-    size_t work_rows = (size_t)run_rows;
-    if (work_rows < (size_t)(rows_fwd + n_prn)) work_rows = (size_t)(rows_fwd + n_prn);
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)(rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
-    AcqCorr k;
-    k.n_bins = n_bins;
-    k.n_phi = n_phi;
-    k.n_blocks = M;
-    k.noncoh = noncoh;
-    k.out_per_prn = noncoh ? n_bins : rows_per_prn;
-    k.rows_out_all = n_prn * k.out_per_prn;
-    k.nblk = sgx_fft4_row_blocks();
-    k.nres = sgx_fft4_residues();
-    k.top2 = true;
-    k.d_codefd = c->d_fwd + (size_t)rows_fwd * (size_t)N;
     // peak and second peak from one pass (acq_rowtop2_peak_kernel): the four-step length has 217 residues, so any exclusion
     // list (2 spc + 1 = 75 indices at that length's rate) fits
-    if (2 * spc + 1 > k.nres) {
+    if (2 * spc + 1 > sgx_fft4_residues()) {
         sgx_set_error("coherent acquisition: %d samples per chip exceed the one-pass second-peak search", spc);
         return SGX_E_ARG;
     }
-    if ((rc = acq_corr_carve(c, &k, 0)) != SGX_OK) return rc;
+    AcqCorr k;
+    if ((rc = acq_corr_setup(c, &k, n_prn, n_bins, n_phi, M, noncoh, true, (size_t)run_rows, false)) != SGX_OK) return rc;
 
     SgxSmall* dsm = c->d_small;
     SgxSmall* hsm = c->h_small;
@@ -2287,13 +2321,7 @@ static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
     acq_queue_publish(a, (CoarseLook*)c->d_look, seq, acq_fine_geom(N).len, nullptr);
     hipEventRecord(c->ev[1], st);
     SGX_HIP(hipGetLastError());
-    const CoarseLook* look = (const CoarseLook*)c->h_look;
-    rc = coarse_look_wait(c, &look->seq, seq, a.env.spin);
-    if (rc != SGX_OK) return rc;
-    AcqDets det;
-    rc = acq_look_decode(a, look->po, look->second, 0, n_prn, &det);
-    if (rc != SGX_OK) return rc;
-    return acq_fine_and_times(a, det, &dsm->sum, &g);
+    return acq_host_tail(a, seq, &dsm->sum, &g);
 }
 
 // ================================ entry points ================================

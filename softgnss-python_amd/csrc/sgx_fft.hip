@@ -11,9 +11,6 @@
 // MFMA is deliberately unused (BASELINE.json north_star).
 #include <math.h>
 
-#include <mutex>
-
-#include <atomic>
 #include "sgx_internal.h"
 
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) {
@@ -279,30 +276,6 @@ __global__ __launch_bounds__(TPB) void fft_pass_kernel(PassArgs a) {
 // ---- plan -----------------------------------------------------------------------------------
 
 static const int kRadixList[] = {16, 8, 4, 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31};
-#define SGX_MAX_DEVICES 16
-static cplx* g_wr[SGX_MAX_DEVICES][32] = {{nullptr}};   // per-device, per-radix root tables
-
-static std::mutex g_wr_lock;   // contexts of several host threads share the tables
-
-static int ensure_roots(int R) {
-    std::lock_guard<std::mutex> hold(g_wr_lock);
-    int dev = 0;
-    SGX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SGX_MAX_DEVICES) {
-        sgx_set_error("device index %d not supported (max %d)", dev, SGX_MAX_DEVICES - 1);
-        return SGX_E_ARG;
-    }
-    if (g_wr[dev][R]) return SGX_OK;
-    std::vector<cplx> w((size_t)R);
-    for (int m = 0; m < R; ++m) {
-        const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)R;
-        w[(size_t)m] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    SGX_HIP(hipMalloc((void**)&g_wr[dev][R], sizeof(cplx) * (size_t)R));
-    SGX_HIP(hipMemcpy(g_wr[dev][R], w.data(), sizeof(cplx) * (size_t)R, hipMemcpyHostToDevice));
-    return SGX_OK;
-}
-
 // The radix passes of a length, in the order they run (16, 8, 4, 2, then the odd ones ascending); false where n has a
 // prime factor above 31.
 static bool fft_factor(int64_t n, std::vector<int>* radices) {
@@ -369,52 +342,6 @@ int64_t sgx_fft_corr_length(int64_t n) {
     return best;
 }
 
-int sgx_fft_plan_create(FftPlan* p, int64_t n) {
-    if (p->n == n && p->tw_hi) return SGX_OK;
-    sgx_fft_plan_destroy(p);
-    if (n < 2) {
-        sgx_set_error("FFT length %lld not supported", (long long)n);
-        return SGX_E_ARG;
-    }
-    if (!fft_factor(n, &p->radices)) {
-        p->radices.clear();
-        sgx_set_error("FFT length %lld has a prime factor above 31 (a transform length must factor into 2..31)",
-                      (long long)n);
-        return SGX_E_ARG;
-    }
-    for (int r : p->radices) {
-        int rc = ensure_roots(r);
-        if (rc != SGX_OK) return rc;
-    }
-    p->lo_bits = (n > (1 << 18)) ? 11 : 8;
-    const int64_t lo_n = 1ll << p->lo_bits;
-    const int64_t hi_n = (n + lo_n - 1) / lo_n + 1;
-    std::vector<cplx> lo((size_t)lo_n), hi((size_t)hi_n);
-    const long double twopi = 2.0L * 3.14159265358979323846264338327950288L;
-    for (int64_t t = 0; t < lo_n; ++t) {
-        const long double ang = -twopi * (long double)t / (long double)n;
-        lo[(size_t)t] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    for (int64_t h = 0; h < hi_n; ++h) {
-        const long double ang = -twopi * (long double)((h << p->lo_bits) % n) / (long double)n;
-        hi[(size_t)h] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    SGX_HIP(hipMalloc((void**)&p->tw_lo, sizeof(cplx) * (size_t)lo_n));
-    SGX_HIP(hipMalloc((void**)&p->tw_hi, sizeof(cplx) * (size_t)hi_n));
-    SGX_HIP(hipMemcpy(p->tw_lo, lo.data(), sizeof(cplx) * (size_t)lo_n, hipMemcpyHostToDevice));
-    SGX_HIP(hipMemcpy(p->tw_hi, hi.data(), sizeof(cplx) * (size_t)hi_n, hipMemcpyHostToDevice));
-    p->n = n;
-    return SGX_OK;
-}
-
-void sgx_fft_plan_destroy(FftPlan* p) {
-    if (p->tw_hi) hipFree(p->tw_hi);
-    if (p->tw_lo) hipFree(p->tw_lo);
-    p->tw_hi = p->tw_lo = nullptr;
-    p->n = 0;
-    p->radices.clear();
-}
-
 // workgroup width of a radix's pass kernels (every MODE)
 static constexpr int fft_pass_tpb(int r) { return (r == 16 || (r >= 11 && r <= 19)) ? 128 : (r >= 23 ? 64 : 256); }
 
@@ -457,9 +384,6 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
         sgx_set_error("sgx_fft_forward: bad plan or row count %lld", (long long)rows);
         return SGX_E_ARG;
     }
-    int cur_dev = 0;
-    SGX_HIP(hipGetDevice(&cur_dev));
-    if (cur_dev < 0 || cur_dev >= SGX_MAX_DEVICES) return SGX_E_ARG;
     cplx* src = a;
     cplx* dst = b;
     long long ns = 1;
@@ -469,14 +393,8 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
     for (int r : p->radices) {
         const bool last = (++ipass == n_pass);
         int mode = 0;
-        PassArgs pa;
-        pa.mul_x = pa.mul_f = nullptr;
-        pa.row_map = nullptr;
+        PassArgs pa = {};
         pa.rows_per_prn = 1;
-        pa.prn_base = 0;
-        pa.pmax = nullptr;
-        pa.parg = nullptr;
-        pa.inv_n = 0.0;
         pa.n_valid = p->n;
         if (fuse && first && fuse->mul_x) {
             mode = 1;
@@ -501,7 +419,7 @@ int sgx_fft_forward_fused(const FftPlan* p, cplx* a, cplx* b, int64_t rows, hipS
         pa.out = dst;
         pa.tw_hi = p->tw_hi;
         pa.tw_lo = p->tw_lo;
-        pa.wr = g_wr[cur_dev][r];
+        pa.wr = p->wr[r];
         pa.n = p->n;
         pa.ns = ns;
         pa.nonzero_len = first ? nonzero_len : p->n;
@@ -1133,23 +1051,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(F4R_WAVES_N
 
 bool sgx_fft4_supported(int64_t n) { return n == (int64_t)F4_N1 * F4_N2; }
 
-static cplx* g_f4_sub[SGX_MAX_DEVICES][2] = {{nullptr, nullptr}};   // W_N1^t and W_N2^t per device
-static int f4_ensure_sub_tables(int dev) {
-    std::lock_guard<std::mutex> hold(g_wr_lock);
-    if (g_f4_sub[dev][0]) return SGX_OK;
-    const long double twopi = 2.0L * 3.14159265358979323846264338327950288L;
-    const int len[2] = {F4_N1, F4_N2};
-    for (int i = 0; i < 2; ++i) {
-        std::vector<cplx> w((size_t)len[i]);
-        for (int t = 0; t < len[i]; ++t) {
-            const long double ang = -twopi * (long double)t / (long double)len[i];
-            w[(size_t)t] = make_double2((double)cosl(ang), (double)sinl(ang));
-        }
-        SGX_HIP(hipMalloc((void**)&g_f4_sub[dev][i], sizeof(cplx) * w.size()));
-        SGX_HIP(hipMemcpy(g_f4_sub[dev][i], w.data(), sizeof(cplx) * w.size(), hipMemcpyHostToDevice));
-    }
-    return SGX_OK;
-}
 int sgx_fft4_row_blocks(void) { return F4_N1 / F4_CB; }
 int sgx_fft4_residues(void) { return F4_N1; }
 
@@ -1157,9 +1058,8 @@ template <int MODE>
 static void f4_launch_cols(const F4Args& a, int64_t rows, hipStream_t st) {
     dim3 grid(F4_N2 / F4_C, (unsigned)rows);
     if constexpr (MODE == 1) {
-        static const bool plain = getenv("SGX_ACQ_XCD") && atoi(getenv("SGX_ACQ_XCD")) == 0;
         F4Args b = a;
-        b.xcd_order = (!plain && !a.row_map && a.n_bins >= 1 && a.rows_per_prn == a.n_bins * a.n_blocks &&
+        b.xcd_order = (!a.row_map && a.n_bins >= 1 && a.rows_per_prn == a.n_bins * a.n_blocks &&
                        rows % a.rows_per_prn == 0 && (grid.x * (unsigned)rows) % 8u == 0u) ? 1 : 0;
         fft4_cols217_kernel<1><<<grid, 128, 0, st>>>(b);
         return;
@@ -1187,20 +1087,9 @@ int sgx_fft4_forward(const FftPlan* p, const cplx* in, cplx* work, cplx* out, in
         sgx_set_error("sgx_fft4_forward: length %lld / %lld rows not supported", (long long)p->n, (long long)rows);
         return SGX_E_ARG;
     }
-    int dev = 0;
-    SGX_HIP(hipGetDevice(&dev));
-    for (int r : {16, 11, 7, 31}) {
-        const int rc = ensure_roots(r);
-        if (rc != SGX_OK) return rc;
-    }
-    if (dev < 0 || dev >= SGX_MAX_DEVICES) return SGX_E_ARG;
-    {
-        const int rc = f4_ensure_sub_tables(dev);
-        if (rc != SGX_OK) return rc;
-    }
     F4Args a;
     memset(&a, 0, sizeof(a));
-    a.tw_sub = g_f4_sub[dev][0];
+    a.tw_sub = p->f4_sub[0];
     a.tw_hi = p->tw_hi;
     a.tw_lo = p->tw_lo;
     a.lo_bits = p->lo_bits;
@@ -1208,8 +1097,8 @@ int sgx_fft4_forward(const FftPlan* p, const cplx* in, cplx* work, cplx* out, in
     a.nonzero_len = p->n;
     a.in = in;
     a.out = work;
-    a.wr[0] = g_wr[dev][7];
-    a.wr[1] = g_wr[dev][31];
+    a.wr[0] = p->wr[7];
+    a.wr[1] = p->wr[31];
     const int sum_blocks = (fuse && fuse->sum_blocks > 1) ? fuse->sum_blocks : 1;
     if (fuse && fuse->mul_x) {
         a.mul_x = fuse->mul_x;
@@ -1228,9 +1117,9 @@ int sgx_fft4_forward(const FftPlan* p, const cplx* in, cplx* work, cplx* out, in
     }
     a.in = work;
     a.out = out;
-    a.tw_sub = g_f4_sub[dev][1];
-    a.wr[0] = g_wr[dev][16];
-    a.wr[1] = g_wr[dev][11];
+    a.tw_sub = p->f4_sub[1];
+    a.wr[0] = p->wr[16];
+    a.wr[1] = p->wr[11];
     if (fuse && fuse->second_out) {
         a.sec = fuse->sec;
         a.second_out = fuse->second_out;
@@ -1641,112 +1530,155 @@ __global__ __launch_bounds__(FF_TPB) void fine_rows_kernel(FineArgs a, int n_pai
 
 #undef FR_REQUEST
 
-static cplx* g_ff_tab[SGX_MAX_DEVICES][3] = {{nullptr, nullptr, nullptr}};   // W_1024^t | W_4096^(64 h) | W_4096^l
-
 bool sgx_fft_fine_supported(int64_t npts) { return npts == (int64_t)FF_N1 * FF_N2; }
 static_assert(FF_N1 / 2 == SGX_FINE_PARTIALS, "the layout of the small areas (sgx_internal.h)");
 int sgx_fft_fine_partials(void) { return SGX_FINE_PARTIALS; }
 
-// Fine search of n_det detections (two per complex row) on the 2^22-point two-kernel transform.  `plan` = the 2^22
-// plan (its two-level table of W_M is used for the inter-step twiddles).  Fills pv / pi [n_det][sgx_fft_fine_partials()].
-int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, const int* det_prn,
-                        const int* det_phase, int n_det, long long len, const long long* d_sum, double n_mean, double ts,
-                        double tc1, cplx* work, long long lo, long long hi, double* pv, long long* pi, hipStream_t st,
-                        const AcqDet* d_det, long long* out_bi, unsigned long long* out_seq, unsigned long long seq,
-                        const int* stage_src, int* stage_dst, int stage_words, const long long* win) {
-    // d_det != nullptr: device-led - the detection list is in device memory (n_det here = the most it can hold)
-    if (!plan->tw_hi || !sgx_fft_fine_supported(plan->n) || n_det < 1 || n_det > 32) {
+// dynamic LDS of the fine kernels (128 KB each: one persistent workgroup per CU)
+static constexpr size_t kFineLdsCols = sizeof(cplx) * (FF_N1 * FF_C + FF_N1);
+static constexpr size_t kFineLdsRows =
+    sizeof(cplx) * (2 * (FF_N2 + FF_N2 / 16) + 128) + (sizeof(double) + sizeof(long long)) * 2 * (FF_TPB / 64);
+
+// ---- the plan: a length, its passes and every table the kernels launched with it read ---------------------------------
+namespace {
+// The tables of one plan in host memory, each at a 256-byte boundary (the kernels load double2 entries), and where each
+// one's device address goes once the upload has succeeded
+struct TableStage {
+    std::vector<cplx> host;
+    std::vector<std::pair<cplx**, size_t>> slots;
+    // W_den^(num(t)), t in [0, count)
+    template <class Num>
+    void add(cplx** slot, int64_t count, int64_t den, Num num) {
+        host.resize((host.size() + 15) / 16 * 16);
+        slots.emplace_back(slot, host.size());
+        const long double twopi = 2.0L * 3.14159265358979323846264338327950288L;
+        for (int64_t t = 0; t < count; ++t) {
+            const long double ang = -twopi * (long double)num(t) / (long double)den;
+            host.push_back(make_double2((double)cosl(ang), (double)sinl(ang)));
+        }
+    }
+    void add(cplx** slot, int64_t count, int64_t den) {
+        add(slot, count, den, [](int64_t t) { return t; });
+    }
+};
+}   // namespace
+
+// The plan of length n on the current device.  All tables are staged on the host and reach the device in one allocation and
+// one copy; the plan's fields are set after the last call that can fail, so a failed create leaves the plan empty.
+int sgx_fft_plan_create(FftPlan* p, int64_t n) {
+    if (p->n == n && p->tw_hi) return SGX_OK;
+    sgx_fft_plan_destroy(p);
+    if (n < 2) {
+        sgx_set_error("FFT length %lld not supported", (long long)n);
+        return SGX_E_ARG;
+    }
+    FftPlan q;
+    if (!fft_factor(n, &q.radices)) {
+        sgx_set_error("FFT length %lld has a prime factor above 31 (a transform length must factor into 2..31)",
+                      (long long)n);
+        return SGX_E_ARG;
+    }
+    q.n = n;
+    q.lo_bits = (n > (1 << 18)) ? 11 : 8;
+    const int lo_bits = q.lo_bits;
+    const int64_t lo_n = 1ll << lo_bits;
+    TableStage ts;
+    ts.add(&q.tw_lo, lo_n, n);
+    ts.add(&q.tw_hi, (n + lo_n - 1) / lo_n + 1, n, [=](int64_t h) { return (h << lo_bits) % n; });
+    for (size_t i = 0; i < q.radices.size(); ++i) {   // (fft_factor lists equal radices next to each other)
+        const int r = q.radices[i];
+        if (i == 0 || r != q.radices[i - 1]) ts.add(&q.wr[r], r, r);
+    }
+    if (sgx_fft4_supported(n)) {
+        ts.add(&q.f4_sub[0], F4_N1, F4_N1);
+        ts.add(&q.f4_sub[1], F4_N2, F4_N2);
+    }
+    if (sgx_fft_fine_supported(n)) {
+        ts.add(&q.fine[0], FF_N1, FF_N1);
+        ts.add(&q.fine[1], 64, FF_N2, [](int64_t h) { return 64 * h; });
+        ts.add(&q.fine[2], 64, FF_N2);
+        // what the fine kernels need of the plan's device: its CU count, and leave to take their LDS (idempotent)
+        int dev = 0;
+        SGX_HIP(hipGetDevice(&dev));
+        SGX_HIP(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, dev));
+        SGX_HIP(hipFuncSetAttribute((const void*)fine_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLdsCols));
+        SGX_HIP(hipFuncSetAttribute((const void*)fine_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLdsRows));
+        SGX_HIP(hipFuncSetAttribute((const void*)fine_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLdsRows));
+    }
+    const size_t bytes = sizeof(cplx) * ts.host.size();
+    SGX_HIP(hipMalloc(&q.tables, bytes));
+    const hipError_t e = hipMemcpy(q.tables, ts.host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(q.tables);
+        sgx_set_error("hipMemcpy of the FFT tables failed: %s", hipGetErrorString(e));
+        return SGX_E_HIP;
+    }
+    for (const auto& s : ts.slots) *s.first = (cplx*)q.tables + s.second;
+    *p = q;
+    return SGX_OK;
+}
+
+void sgx_fft_plan_destroy(FftPlan* p) {
+    if (p->tables) hipFree(p->tables);
+    *p = FftPlan();
+}
+
+// Fine search of f.n_det detections (two per complex row) on the 2^22-point two-kernel transform.  `plan` = the 2^22
+// plan (its two-level table of W_M is used for the inter-step twiddles).  Fills f.pv / f.pi [n_det][sgx_fft_fine_partials()].
+int sgx_fft_fine_search(const FftPlan* plan, const FineSearch& f, hipStream_t st) {
+    // f.d_det != nullptr: device-led - the detection list is in device memory (n_det here = the most it can hold)
+    if (!plan->tw_hi || !sgx_fft_fine_supported(plan->n) || f.n_det < 1 || f.n_det > 32) {
         sgx_set_error("sgx_fft_fine_search: %lld points not supported", (long long)plan->n);
         return SGX_E_ARG;
     }
-    int dev = 0;
-    SGX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SGX_MAX_DEVICES) return SGX_E_ARG;
-    for (int r : {16, 4}) {
-        const int rc = ensure_roots(r);
-        if (rc != SGX_OK) return rc;
-    }
-    {
-        std::lock_guard<std::mutex> hold(g_wr_lock);
-        if (!g_ff_tab[dev][0]) {
-            const long double twopi = 2.0L * 3.14159265358979323846264338327950288L;
-            std::vector<cplx> t1(FF_N1), th(64), tl(64);
-            for (int t = 0; t < FF_N1; ++t) {
-                const long double ang = -twopi * (long double)t / (long double)FF_N1;
-                t1[(size_t)t] = make_double2((double)cosl(ang), (double)sinl(ang));
-            }
-            for (int t = 0; t < 64; ++t) {
-                const long double ah = -twopi * (long double)(64 * t) / (long double)FF_N2;
-                const long double al = -twopi * (long double)t / (long double)FF_N2;
-                th[(size_t)t] = make_double2((double)cosl(ah), (double)sinl(ah));
-                tl[(size_t)t] = make_double2((double)cosl(al), (double)sinl(al));
-            }
-            SGX_HIP(hipMalloc((void**)&g_ff_tab[dev][0], sizeof(cplx) * FF_N1));
-            SGX_HIP(hipMalloc((void**)&g_ff_tab[dev][1], sizeof(cplx) * 64));
-            SGX_HIP(hipMalloc((void**)&g_ff_tab[dev][2], sizeof(cplx) * 64));
-            SGX_HIP(hipMemcpy(g_ff_tab[dev][0], t1.data(), sizeof(cplx) * FF_N1, hipMemcpyHostToDevice));
-            SGX_HIP(hipMemcpy(g_ff_tab[dev][1], th.data(), sizeof(cplx) * 64, hipMemcpyHostToDevice));
-            SGX_HIP(hipMemcpy(g_ff_tab[dev][2], tl.data(), sizeof(cplx) * 64, hipMemcpyHostToDevice));
-        }
-    }
     FineArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.codes = codes;
-    for (int d = 0; d < n_det && !d_det; ++d) {
-        a.det_prn[d] = det_prn[d];
-        a.det_phase[d] = det_phase[d];
+    a.x = f.x;
+    a.codes = f.codes;
+    for (int d = 0; d < f.n_det && !f.d_det; ++d) {
+        a.det_prn[d] = f.det_prn[d];
+        a.det_phase[d] = f.det_phase[d];
     }
-    a.n_det = n_det;
-    a.det = d_det;
-    a.len = len;
-    a.d_sum = d_sum;
-    a.n_mean = n_mean;
-    a.ts = ts;
-    a.tc1 = tc1;
-    a.work = work;
+    a.n_det = f.n_det;
+    a.det = f.d_det;
+    a.len = f.len;
+    a.d_sum = f.d_sum;
+    a.n_mean = f.n_mean;
+    a.ts = f.ts;
+    a.tc1 = f.tc1;
+    a.work = f.work;
     a.tw_hi = plan->tw_hi;
     a.tw_lo = plan->tw_lo;
     a.lo_bits = plan->lo_bits;
-    a.wr16 = g_wr[dev][16];
-    a.wr4 = g_wr[dev][4];
-    a.tw_n1 = g_ff_tab[dev][0];
-    a.tw_n2_hi = g_ff_tab[dev][1];
-    a.tw_n2_lo = g_ff_tab[dev][2];
-    a.lo = lo;
-    a.hi = hi;
-    a.pv = pv;
-    a.pi = pi;
-    a.out_bi = d_det ? out_bi : nullptr;
-    a.out_seq = d_det ? out_seq : nullptr;
-    a.stage_src = stage_src;
-    a.stage_dst = stage_dst;
-    a.stage_words = (d_det && stage_src && stage_dst) ? stage_words : 0;
-    a.win = d_det ? nullptr : win;
-    a.seq = seq;
-    const int n_rows = (n_det + 1) / 2;
-    const size_t lds_c = sizeof(cplx) * (FF_N1 * FF_C + FF_N1);
-    const size_t lds_r = sizeof(cplx) * (2 * (FF_N2 + FF_N2 / 16) + 128) + (sizeof(double) + sizeof(long long)) * 2 * (FF_TPB / 64);
-    static std::atomic<bool> once[SGX_MAX_DEVICES];
-    if (!once[dev].load()) {
-        hipFuncSetAttribute((const void*)fine_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-        hipFuncSetAttribute((const void*)fine_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-        hipFuncSetAttribute((const void*)fine_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-        once[dev].store(true);
-    }
-    int cus = 256;
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    a.wr16 = plan->wr[16];
+    a.wr4 = plan->wr[4];
+    a.tw_n1 = plan->fine[0];
+    a.tw_n2_hi = plan->fine[1];
+    a.tw_n2_lo = plan->fine[2];
+    a.lo = f.lo;
+    a.hi = f.hi;
+    a.pv = f.pv;
+    a.pi = f.pi;
+    a.out_bi = f.d_det ? f.out_bi : nullptr;
+    a.out_seq = f.d_det ? f.out_seq : nullptr;
+    a.stage_src = f.stage_src;
+    a.stage_dst = f.stage_dst;
+    a.stage_words = (f.d_det && f.stage_src && f.stage_dst) ? f.stage_words : 0;
+    a.win = f.d_det ? nullptr : f.win;
+    a.seq = f.seq;
+    const int n_rows = (f.n_det + 1) / 2;
+    const int cus = plan->cus;
     {
         // persistent workgroups, one per CU (128 KB of LDS each), walking the (spectrum, column tile) list
         const int n_tiles = (FF_N2 / FF_C) * n_rows;
-        fine_cols_kernel<<<n_tiles < cus ? n_tiles : cus, FF_TPB, lds_c, st>>>(a, n_tiles);
+        fine_cols_kernel<<<n_tiles < cus ? n_tiles : cus, FF_TPB, kFineLdsCols, st>>>(a, n_tiles);
     }
     {
         // persistent workgroups, one per CU (128 KB of LDS each), walking the (spectrum, row pair) list
         const int n_pairs = (FF_N1 / 2) * n_rows;
         const int grid = n_pairs < cus ? n_pairs : cus;
-        if (a.win) fine_rows_kernel<true><<<grid, FF_TPB, lds_r, st>>>(a, n_pairs);
-        else fine_rows_kernel<false><<<grid, FF_TPB, lds_r, st>>>(a, n_pairs);
+        if (a.win) fine_rows_kernel<true><<<grid, FF_TPB, kFineLdsRows, st>>>(a, n_pairs);
+        else fine_rows_kernel<false><<<grid, FF_TPB, kFineLdsRows, st>>>(a, n_pairs);
     }
     SGX_HIP(hipGetLastError());
     return SGX_OK;

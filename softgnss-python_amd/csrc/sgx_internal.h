@@ -46,13 +46,20 @@ struct SgxSig {
 #endif
 };
 
-// Twiddle tables for one FFT length: W_N^t = hi[t >> lo_bits] * lo[t & lo_mask]
+// One FFT length and every table the kernels launched with this plan read, W_N^t = hi[t >> lo_bits] * lo[t & lo_mask] among
+// them.  sgx_fft_plan_create uploads them as ONE device allocation (`tables`), which sgx_fft_plan_destroy frees; the other
+// pointers are carved from it.  A plan without tables (n set by hand) serves host arithmetic only.
 struct FftPlan {
     int64_t n = 0;
     int lo_bits = 0;
-    cplx* tw_hi = nullptr;   // device
-    cplx* tw_lo = nullptr;   // device
     std::vector<int> radices;
+    void* tables = nullptr;             // device
+    cplx* tw_hi = nullptr;
+    cplx* tw_lo = nullptr;
+    cplx* wr[32] = {};                  // wr[R][m] = W_R^m, m < R, for every radix R of the plan
+    cplx* f4_sub[2] = {};               // four-step length only: W_217^t | W_176^t
+    cplx* fine[3] = {};                 // fine-search length only: W_1024^t | W_4096^(64 h) | W_4096^l
+    int cus = 0;                        // fine-search length only: compute units of the plan's device
 };
 
 // sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
@@ -334,16 +341,36 @@ struct Fft4Fuse {
 };
 bool sgx_fft_fine_supported(int64_t npts);
 int sgx_fft_fine_partials(void);
-int sgx_fft_fine_search(const FftPlan* plan, SgxSig x, const int8_t* codes, const int* det_prn /* host, <= 32 */,
-                        const int* d_det_phase, int n_det, long long len, const long long* d_sum, double n_mean, double ts,
-                        double tc1, cplx* work, long long lo, long long hi, double* pv, long long* pi, hipStream_t st,
-                        const AcqDet* d_det = nullptr /* device-led: the list in device memory */,
-                        long long* out_bi = nullptr /* device-led: [32] arg-max per detection (pinned page) ... */,
-                        unsigned long long* out_seq = nullptr /* ... then this word = seq */, unsigned long long seq = 0,
-                        const int* stage_src = nullptr /* device-led: dwords copied to stage_dst (the page) before the word */,
-                        int* stage_dst = nullptr, int stage_words = 0,
-                        const long long* win = nullptr /* host-led only: device [2 d] lo, [2 d + 1] hi per detection,
-                                                          inside [lo, hi) */);
+// One fine search on the two-kernel 2^22-point transform (sgx_fft.hip): n_det detections, two per complex row.
+struct FineSearch {
+    // the signal and the codes
+    SgxSig x = {nullptr, nullptr};
+    const int8_t* codes = nullptr;          // device [32][1023]
+    long long len = 0;                      // 10 N samples of signal, zeros beyond
+    const long long* d_sum = nullptr;       // device: sum of the record window; mean = sum / n_mean
+    double n_mean = 0.0, ts = 0.0, tc1 = 0.0;
+    cplx* work = nullptr;                   // [(n_det + 1) / 2][2^22] intermediate
+    // the detections, host-led: the list (host memory, <= 32) and the arg-max range [lo, hi), or per detection the device
+    // ranges win[2 d], win[2 d + 1] inside it
+    int n_det = 0;                          // (device-led: the most the list can hold)
+    const int* det_prn = nullptr;
+    const int* det_phase = nullptr;
+    long long lo = 0, hi = 0;
+    const long long* win = nullptr;
+    // ... or device-led: the list in device memory; the last workgroup copies stage_words dwords from stage_src (device) to
+    // stage_dst (the pinned page), folds the partial maxima into out_bi[32] (the page) and then stores seq to *out_seq
+    const AcqDet* d_det = nullptr;
+    const int* stage_src = nullptr;
+    int* stage_dst = nullptr;
+    int stage_words = 0;
+    long long* out_bi = nullptr;
+    unsigned long long* out_seq = nullptr;
+    unsigned long long seq = 0;
+    // the outputs: per-detection partial maxima and their indices, [n_det][sgx_fft_fine_partials()] each (device)
+    double* pv = nullptr;
+    long long* pi = nullptr;
+};
+int sgx_fft_fine_search(const FftPlan* plan, const FineSearch& f, hipStream_t st);
 bool sgx_fft4_supported(int64_t n);
 int sgx_fft4_row_blocks(void);
 int sgx_fft4_residues(void);

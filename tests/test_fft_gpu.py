@@ -3,14 +3,16 @@ tests/fft_cover.py: every radix as first, middle and last pass, plain and fused,
 The transforms themselves against numpy's FFT on long double (80-bit extended: complex256) through sgx_fft_run_passes, to a
 bound derived from the plan (fft_cover.error_bound); then acquisition against oracle.acquire at every length, to the bars
 of tests/test_any_rate_gpu.py, with a detection in every output slot of the last radix.  tests/test_fft_cover_host.py
-asserts the table's coverage and conditions every scene in numpy.  Run with -m gpu."""
+asserts the table's coverage and conditions every scene in numpy.  Last, whose tables a transform reads: a plan's own
+(sgx_fft_plan_create), through contexts that close, lengths that alternate and a context's first call.  Run with -m gpu."""
 import numpy as np
 import pytest
 
 import fft_cover as fc
-from conftest import pkg
+from conftest import load_golden, pkg
 from oracle import softgnss_oracle as orc
 from test_any_rate_gpu import _same_search
+from test_gpu_parity import check_acq_default_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -171,3 +173,68 @@ def test_deferred_and_queued_entry_with_more_than_64_last_pass_workgroups():
         assert np.sum(a.carrFreq > 0) == len(prns)
     finally:
         rec.free()
+
+
+# ---- the tables belong to the plan that reads them (sgx_fft_plan_create), and so to one context or one call ----
+
+def _random_rows(n, rows, seed):
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((rows, n)) + 1j * rng.standard_normal((rows, n))
+
+
+def _within_bound(got, rows, n):
+    err, bound = fc.rel_err(got, fc.fft_long(rows)), fc.error_bound(fc.plan(n).radices)
+    print("%d: kernel %.2e, bound %.2e" % (n, err.max(), bound))
+    return np.all(err <= bound)
+
+
+def test_tables_die_with_their_owner_and_with_no_one_elses():
+    """Two contexts on one device, 496 = 16 x 31 on both; closing one leaves the other's transform as it was, bit for bit."""
+    m = pkg()
+    s = m.Settings()
+    rows = _random_rows(496, 3, 0x7AB1E)
+    with m.engine.private_context(s, 0) as second:
+        with m.engine.private_context(s, 0) as first:
+            assert first is not second
+            got_first = first.fft_forward(rows)
+            before = second.fft_forward(rows)
+        after = second.fft_forward(rows)     # (`first` and everything it owned is gone)
+    assert np.array_equal(after, before) and np.array_equal(got_first, before)
+    assert _within_bound(after, rows, 496)
+
+
+def test_a_plan_that_changes_length_rebuilds_all_of_its_tables():
+    """210 = 2 3 5 7, 899 = 29 31, 210 again on one context: no radix, and no table, is shared between the two lengths."""
+    ctx = _ctx()
+    x210, x899 = _random_rows(210, 3, 0x210), _random_rows(899, 3, 0x899)
+    a = ctx.fft_forward(x210)
+    b = ctx.fft_forward(x899)
+    c = ctx.fft_forward(x210)
+    assert np.array_equal(c, a)
+    assert _within_bound(a, x210, 210) and _within_bound(b, x899, 899) and _within_bound(c, x210, 210)
+
+
+def test_a_search_is_the_same_after_a_transform_of_another_length(default_record):
+    """The context's own plans (code length, fine search) with another length's transform between two searches."""
+    ctx = _ctx()
+    x = default_record[:11 * 38192].astype(np.float64)
+    first = ctx.acquire_f64(x, range(32))
+    ctx.fft_forward(_random_rows(899, 1, 0x899))
+    again = ctx.acquire_f64(x, range(32))
+    assert sorted(first) == ["carrFreq", "codePhase", "fineIdx", "freqBin", "peakMetric"]
+    for k in first:
+        assert np.array_equal(again[k], first[k]), k
+    assert np.any(first["carrFreq"] > 0)      # (the fine search ran)
+
+
+def test_four_step_and_fine_tables_on_a_fresh_context(default_record):
+    """A new context's very first call is the search of all 32 PRNs (four-step and fine-search tables); twice in one
+    process, each context closed before the next opens: the second finds nothing the first left behind."""
+    g = load_golden("acq_default.npz")
+    m = pkg()
+    s = m.Settings()
+    for _ in range(2):
+        with m.engine.private_context(s, 0):
+            a = m.AcquisitionResult(s, device=0)     # (engine.get_context hands out the thread's private context)
+            a.acquire(default_record[:int(g["n_samples"])])
+            check_acq_default_golden(a, g)

@@ -71,6 +71,11 @@ def test_acquire_all_prns_and_prerun_golden(default_record):
     s = m.Settings()
     a = m.AcquisitionResult(s, device=0)
     a.acquire(default_record[:int(g["n_samples"])])
+    check_acq_default_golden(a, g)
+
+
+def check_acq_default_golden(a, g):
+    """The search of all 32 PRNs on the default record, and its preRun, against acq_default.npz."""
     assert np.array_equal(a.codePhase, g["codePhase"])
     assert np.array_equal(a.carrFreq, g["carrFreq"])
     assert np.array_equal(a.internals["freqBin"], g["freqBin"])
