@@ -520,6 +520,59 @@ int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t* taps, int3
 int sgx_iq_timing(sgx_ctx* c, float* kernel_ms);
 int sgx_iq_tile(int32_t* tile_bytes);
 
+/* ---- int16 / float32 records through a fixed-gain requantiser (no reference counterpart; the stage in front of
+ * sgx_if_from_iq for sc16 and fc32 captures) -----------------------------------------------------------------------------
+ * Opt-in.  A resident record holding the raw BYTES of a file of little-endian int16 (w = 2) or IEEE float32 (w = 4)
+ * elements, N bytes = n = N / w elements x[i], comes out as a NEW int8 record of n bytes, element i -> byte i, through one
+ * fixed gain (a digital AGC that does not vary in time).  I and Q of an interleaved file share the gain, so the stage is
+ * elementwise and knows nothing of pairs; it reads real records of these types just as well.  data_type is SGX_DT_INT16 or
+ * SGX_DT_FLOAT32.  tests/requant_spec.py restates all of it in numpy.
+ *
+ * sgx_requant_stats_of: elements [offset, offset + count) of the record.  NaN and +-inf elements are counted in n_nonfinite
+ * and left out of everything else; n_finite + n_nonfinite = count; max_abs = max |x| (0 for an empty window); the counts and
+ * max_abs are exact.
+ *   int16    sum and sum_sq are accumulated exactly in integers and converted to double once: float(int(...)).
+ *   float32  each element is promoted to double and squared there (exact) and the doubles are summed in a FIXED order: two
+ *            calls on the same bytes and window give the same bits.  Against the correctly rounded sums the results differ
+ *            by at most count 2^-52 sum|x| (sum) and count 2^-52 sum_sq (sum_sq), the worst case of recursive summation in
+ *            any order.  Denormal elements count with their value.
+ * The window is read on the context's stream (a record that is still streaming in is waited for up to the window's end).
+ *
+ * sgx_requant_gain: the gain that brings a record with these statistics to target_rms, in (0, 127]; exact host code, needs
+ * no GPU.  rms = sqrt(sum_sq / n_finite), g = target_rms / rms; g = 1 for n_finite <= 0 or an rms that is not > 0.
+ *   *shift = the largest S in 0 .. 30 with rint(g 2^S) <= 32767 (half to even), *mult = max(1, rint(g 2^S)); if even S = 0
+ *            gives more than 32767: *mult = 32767, *shift = 0.  |x mult| + 2^(shift-1) < 2^31 then holds for every int16 x.
+ *   *scale = (float)g, clamped to [SGX_REQUANT_SCALE_MIN, SGX_REQUANT_SCALE_MAX] = [2^-100, 2^100].
+ * All three are filled for either data_type; sgx_if_requantize reads the pair or the scale by its own data_type.
+ *
+ * sgx_if_requantize:
+ *   int16    y = clip((x mult + ((1 << shift) >> 1)) >> shift, -127, 127), arithmetic (floor) shift, exact in int32.
+ *   float32  y = clip(rint(x * scale), -127, 127): ONE float32 multiply, round to nearest even; NaN -> 0, +-inf -> +-127.
+ *            With scale <= 2^100 a denormal element (below 2^-126) times scale lies below 2^-26 and rounds to 0, as does a
+ *            denormal product: the output does not depend on whether the hardware flushes denormals.
+ * The whole record is requantised on the context's stream (a record that is still streaming in is waited for, as
+ * sgx_if_wait to its full length); the input is left alone; *out is an ordinary record (sgx_if_free); N = 0 gives an empty
+ * record.  *n_clipped (may be NULL): the outputs that are +-127.
+ * sgx_requant_timing: HIP-event times of the last sgx_requant_stats_of's and the last sgx_if_requantize's kernel on this
+ * context.  sgx_requant_tile: the output bytes one workgroup of the quantiser makes (where its tile seams lie).
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: a data_type other than the two, N not a
+ * multiple of w, a window that leaves the record, mult outside 1 .. 32767 or shift outside 0 .. 30 (int16), a scale that is
+ * not finite or outside [2^-100, 2^100] (float32), target_rms outside (0, 127], a NULL pointer. */
+#define SGX_REQUANT_SCALE_MIN 0x1p-100f
+#define SGX_REQUANT_SCALE_MAX 0x1p+100f
+typedef struct sgx_requant_stats {
+    int64_t n_finite, n_nonfinite;
+    double max_abs, sum, sum_sq;
+} sgx_requant_stats;        /* 40 bytes */
+int sgx_requant_stats_of(sgx_ctx* c, const sgx_if* rec, int32_t data_type, size_t offset, size_t count,
+                         sgx_requant_stats* out);
+int sgx_requant_gain(const sgx_requant_stats* st, int32_t data_type, double target_rms, int32_t* mult, int32_t* shift,
+                     float* scale);
+int sgx_if_requantize(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t mult, int32_t shift, float scale,
+                      sgx_if** out, int64_t* n_clipped);
+int sgx_requant_timing(sgx_ctx* c, float* stats_ms, float* kernel_ms);
+int sgx_requant_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

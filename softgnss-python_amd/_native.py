@@ -83,6 +83,12 @@ class ReplayBlock(C.Structure):
                 ("carr_freq", C.c_double), ("blk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RequantStats(C.Structure):
+    """sgx_requant_stats: the statistics of a window of int16 / float32 elements (sgx_requant_stats_of, 40 bytes)."""
+    _fields_ = [("n_finite", C.c_int64), ("n_nonfinite", C.c_int64), ("max_abs", C.c_double), ("sum", C.c_double),
+                ("sum_sq", C.c_double)]
+
+
 REPLAY_MAX_TAPS = 64
 REPLAY_STATE_DTYPE = np.dtype([("start", "<i8"), ("rem_code", "<f8"), ("rem_carr", "<f8"), ("step", "<f8"),
                                ("carr_freq", "<f8"), ("blk", "<i4"), ("reserved", "<i4")])
@@ -152,6 +158,13 @@ _PROTOS = {
     "sgx_if_from_iq": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "sgx_iq_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_iq_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_requant_stats_of": (C.c_int, [_P, _P, C.c_int32, C.c_size_t, C.c_size_t, C.POINTER(RequantStats)]),
+    "sgx_requant_gain": (C.c_int, [C.POINTER(RequantStats), C.c_int32, C.c_double, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "sgx_if_requantize": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(_P),
+                                    C.POINTER(C.c_int64)]),
+    "sgx_requant_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sgx_requant_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -467,6 +480,39 @@ def iq_tile():
     """Output bytes one workgroup of the I/Q converter makes: its tile seams lie at the multiples."""
     t = C.c_int32(0)
     check(lib().sgx_iq_tile(C.byref(t)))
+    return t.value
+
+
+REQUANT_SCALE_MIN, REQUANT_SCALE_MAX = 2.0 ** -100, 2.0 ** 100
+
+
+def requant_type(dtype):
+    """(sgx data_type, bytes per element) of a sample type the requantiser reads: int16 or float32."""
+    dt = np.dtype(dtype)
+    if dt == np.dtype(np.int16):
+        return DT_INT16, 2
+    if dt == np.dtype(np.float32):
+        return DT_FLOAT32, 4
+    raise ValueError("the requantiser reads int16 and float32 records, not %r" % (dtype,))
+
+
+def requant_gain(stats, dtype, target_rms=12.0):
+    """(mult, shift, scale): the fixed gain that brings a record with these statistics (the dict of Context.requant_stats,
+    or anything with n_finite and sum_sq) to target_rms, in (0, 127] (sgx_requant_gain; exact host code, needs no GPU).
+    int16 records are requantised with mult / 2^shift, float32 records with the float32 scale."""
+    get = stats.get if isinstance(stats, dict) else (lambda k, d=0: getattr(stats, k, d))
+    st = RequantStats(int(get("n_finite", 0)), int(get("n_nonfinite", 0)), float(get("max_abs", 0.0)),
+                      float(get("sum", 0.0)), float(get("sum_sq", 0.0)))
+    m, sh, sc = C.c_int32(0), C.c_int32(0), C.c_float(0)
+    check(lib().sgx_requant_gain(C.byref(st), requant_type(dtype)[0], float(target_rms), C.byref(m), C.byref(sh),
+                                 C.byref(sc)))
+    return m.value, sh.value, np.float32(sc.value)
+
+
+def requant_tile():
+    """Output bytes (= elements) one workgroup of the requantiser makes: its tile seams lie at the multiples."""
+    t = C.c_int32(0)
+    check(lib().sgx_requant_tile(C.byref(t)))
     return t.value
 
 
@@ -805,6 +851,38 @@ class Context(object):
         k = C.c_float(0)
         check(lib().sgx_iq_timing(self._h, C.byref(k)))
         return k.value
+
+    def requant_stats(self, rec, dtype, offset=0, count=None):
+        """Statistics of elements [offset, offset + count) (count None: to the end) of `rec`, the raw bytes of a file of
+        int16 or float32 samples (sgx_requant_stats_of): dict(n_finite, n_nonfinite, max_abs, sum, sum_sq).  NaN and
+        infinite samples are counted in n_nonfinite and left out of the rest; int16 sums are exact, float32 sums are
+        taken in double in a fixed order (two calls agree bit for bit)."""
+        dt, w = requant_type(dtype)
+        if count is None:
+            count = max(0, len(rec) // w - int(offset))
+        st = RequantStats()
+        check(lib().sgx_requant_stats_of(self._h, rec._h, dt, int(offset), int(count), C.byref(st)))
+        return dict(n_finite=int(st.n_finite), n_nonfinite=int(st.n_nonfinite), max_abs=st.max_abs, sum=st.sum,
+                    sum_sq=st.sum_sq)
+
+    def requantize(self, rec, dtype, mult=1, shift=0, scale=1.0):
+        """A new int8 record, one byte per element of `rec` (the raw bytes of a file of int16 or float32 samples), through
+        one fixed gain (sgx_if_requantize).  int16: y = clip((x mult + 2^(shift-1)) >> shift, -127, 127); float32:
+        y = clip(rint(x * float32(scale)), -127, 127), NaN -> 0.  The number of outputs on +-127 is left in the new
+        record's `clipped`."""
+        dt, w = requant_type(dtype)
+        h = _P()
+        nc = C.c_int64(0)
+        check(lib().sgx_if_requantize(self._h, rec._h, dt, int(mult), int(shift), float(scale), C.byref(h), C.byref(nc)))
+        out = Record(self, h, len(rec) // w)
+        out.clipped = int(nc.value)
+        return out
+
+    def requant_timing(self):
+        """(statistics kernel ms, quantiser kernel ms) of the last requant_stats and the last requantize on this context."""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib().sgx_requant_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

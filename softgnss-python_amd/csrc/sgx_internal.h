@@ -65,6 +65,13 @@ struct FftPlan {
 // sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
 #define SGX_IQ_LP_MAX 136
 
+// sgx_requant.hip: the fixed grid of the statistics pass (the float sums are reproducible because it is fixed), its loads
+// in flight per lane, and the counters the quantiser spreads its per-wave counts of clipped outputs over
+#define RQ_STATS_BLOCKS 2048
+#define RQ_STATS_UNROLL 4
+#define RQ_CLIP_SLOTS 256
+#define RQ_CLIP_STRIDE 32    // words between two counters: one 128-byte line each
+
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
     size_t n = 0;
@@ -182,6 +189,10 @@ struct SgxSmall {
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
     // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter or sgx_if_from_iq call, which waits before it returns; both
     alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
+    // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass, and
+    // the quantiser's counters of outputs on +-127; both entry points wait before they return; both
+    alignas(256) unsigned long long requant_part[RQ_STATS_BLOCKS * 4];
+    alignas(256) unsigned requant_clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");
@@ -276,6 +287,8 @@ struct sgx_ctx {
     float replay_kernel_ms = 0.0f, replay_device_ms = 0.0f;
     float filter_kernel_ms = 0.0f;   // HIP-event time of the last sgx_if_filter's kernel (sgx_filter.hip)
     float iq_kernel_ms = 0.0f;       // HIP-event time of the last sgx_if_from_iq's kernel (sgx_iq.hip)
+    // HIP-event times of the last sgx_requant_stats_of's and the last sgx_if_requantize's kernel (sgx_requant.hip)
+    float requant_stats_ms = 0.0f, requant_kernel_ms = 0.0f;
 };
 
 // sgx_host.cpp

@@ -116,6 +116,10 @@ _IQ_DEFAULTS = (
                                          # offset (0 or negative allowed), dataType 'int8' or 'uint8' (offset binary)
     ("iqQFirst", False),                 # the file holds Q before I (also: spectral inversion of an I-first file)
     ("iqTaps", 63),                      # length of the interpolation filter (odd, at most 255)
+    # int16 (sc16) and float32 (fc32) I/Q files (Settings.requantizeIQ; INTEGRATION.md, "int16 / float32 I/Q"): the file is
+    # brought to int8 on the GPU through one fixed gain, ahead of the converter
+    ("iqRequantize", False),             # with iqRecord: dataType 'int16' and 'float32' are read through the requantiser
+    ("iqTargetRms", 12.0),               # rms of the int8 record it makes, LSB, in (0, 127]
 )
 
 
@@ -246,10 +250,60 @@ class Settings(object):
     def _iq_format(self):
         """(q_first, offset_binary) of the I/Q file these settings describe."""
         dt = np.dtype(self.dataType)
+        if self.iqRequantize and dt in (np.dtype(np.int16), np.dtype(np.float32)):
+            return bool(self.iqQFirst), False        # (what requantizeIQ makes of the file is int8)
         if dt not in (np.dtype(np.int8), np.dtype(np.uint8)):
+            if self.iqRequantize:
+                raise ValueError("an I/Q record (Settings.iqRecord) holds int8 samples, uint8 for offset binary or, with "
+                                 "Settings.iqRequantize, int16 or float32, not Settings.dataType %r" % (self.dataType,))
             raise ValueError("an I/Q record (Settings.iqRecord) holds int8 samples, or uint8 for offset binary, not "
                              "Settings.dataType %r: int16 and float32 I/Q are not converted" % (self.dataType,))
         return bool(self.iqQFirst), dt == np.dtype(np.uint8)
+
+    def _iq_width(self):
+        """Bytes per component of the I/Q file: 2 or 4 where it goes through the requantiser, else 1."""
+        self._iq_format()
+        return np.dtype(self.dataType).itemsize if self.iqRecord else 1
+
+    def _prepared_settings(self):
+        """The settings the PREPARED record is read under: realEquivalent(), with skipNumberOfBytes turned from a byte of a
+        file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w."""
+        if not self.iqRecord:
+            return self
+        real = self.realEquivalent()
+        w = self._iq_width()
+        skip = int(self.skipNumberOfBytes)
+        if skip % (2 * w):
+            raise ValueError("skipNumberOfBytes = %d splits an I/Q pair: it must be %s" %
+                             (skip, "even" if w == 1 else "a multiple of %d (pairs of %d-byte components)" % (2 * w, w)))
+        real.skipNumberOfBytes = skip // w
+        return real
+
+    def requantizeIQ(self, record):
+        """A resident record holding the raw bytes of an int16 or float32 file (a _native.Record; Settings.dataType says
+        which) as a NEW int8 record, one sample per component: the statistics of the whole record (requant_stats), the
+        fixed gain that brings its rms to iqTargetRms (requant_gain), the record through it (requantize).  Sample n of the
+        new record is component n of the file, i.e. file byte n w for w-byte components.  Returns (record8, info) and keeps
+        info as self.lastRequant: the statistics (n_finite, n_nonfinite, max_abs, sum, sum_sq), rms, mult and shift (int16)
+        or scale (float32), gain_db, and clipped, the share of the samples that landed on +-127.  The caller frees both."""
+        if not self.iqRequantize:
+            raise ValueError("Settings.iqRequantize is off: int16 and float32 I/Q are not converted to int8")
+        dt = np.dtype(self.dataType)
+        ctx = record.ctx
+        info = ctx.requant_stats(record, dt)
+        mult, shift, scale = _native.requant_gain(info, dt, self.iqTargetRms)
+        rec8 = ctx.requantize(record, dt, mult=mult, shift=shift, scale=scale)
+        info["rms"] = float(np.sqrt(info["sum_sq"] / info["n_finite"])) if info["n_finite"] else 0.0
+        if dt == np.dtype(np.int16):
+            info["mult"], info["shift"] = mult, shift
+            gain = float(mult) / float(1 << shift)
+        else:
+            info["scale"] = scale
+            gain = float(scale)
+        info["gain_db"] = 20.0 * float(np.log10(gain))
+        info["clipped"] = float(rec8.clipped) / len(rec8) if len(rec8) else 0.0
+        self.lastRequant = info
+        return rec8, info
 
     def realEquivalent(self):
         """The settings of the real IF record that convertIQ makes of the I/Q file these settings describe: a copy with
@@ -273,15 +327,29 @@ class Settings(object):
 
     @contextlib.contextmanager
     def _prepared_record(self, name, offset, count, mitigate_at=None, verbose=False):
-        """Bytes [offset, offset + count) of a record file, uploaded once and prepared on the GPU, for the length of the
-        block: with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation)
-        cleared of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the
-        real rate.  Yields the prepared record, to be read under realEquivalent(), and frees it afterwards."""
+        """Samples [offset, offset + count) of the prepared record of a record file, uploaded once and prepared on the
+        GPU, for the length of the block: with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
+        with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation) cleared
+        of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the real
+        rate.  offset and count are in BYTES OF THE PREPARED RECORD: for a file of w-byte components the bytes
+        [w offset, w (offset + count)) are read, and sample n of the prepared record is file byte n w.  Each intermediate
+        record is freed as soon as the next one exists.  Yields the prepared record, to be read under
+        _prepared_settings(), and frees it afterwards."""
         from . import engine
         say = print if verbose else (lambda *args: None)
-        real = self.realEquivalent() if self.iqRecord else self
-        rec = engine.get_context(real, None).upload_file(name, offset, count)
+        real = self._prepared_settings()
+        w = self._iq_width() if self.iqRecord else 1
+        rec = engine.get_context(real, None).upload_file(name, w * offset, w * count)
         try:
+            if w > 1:
+                say('   Requantising %s samples to int8...' % np.dtype(self.dataType).name)
+                raw, rec = rec, None
+                try:
+                    rec, info = self.requantizeIQ(raw)
+                finally:
+                    raw.free()
+                say('   rms %.6g, peak %.6g, %d non-finite samples, gain %+.2f dB, %.4f %% of the samples clipped'
+                    % (info["rms"], info["max_abs"], info["n_nonfinite"], info["gain_db"], 100.0 * info["clipped"]))
             if self.iqRecord:
                 say('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
                     % (self.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
@@ -332,17 +400,15 @@ class Settings(object):
 
     def _resident_processing(self, name):
         """postProcessing()'s acquire -> preRun -> track on a record that _prepared_record uploads once and prepares on the
-        GPU; both stages read the prepared record where it lies.  The results carry realEquivalent(): positions are samples
-        of the prepared record, which are bytes of the file."""
+        GPU; both stages read the prepared record where it lies.  The results carry _prepared_settings(): positions
+        (codePhase, absoluteSample, skipNumberOfBytes) are samples of the prepared record, which are bytes of an 8-bit file
+        and file byte / w of a file of w-byte components (int16: w = 2, float32: w = 4, with iqRequantize)."""
         from .record import DeviceFile, DeviceSignal
-        real = self.realEquivalent() if self.iqRecord else self
+        real = self._prepared_settings()
         n = real.samplesPerCode
-        skip = int(self.skipNumberOfBytes)
+        skip = int(real.skipNumberOfBytes)
         need = skip + max(real.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
         if self.iqRecord:
-            self._iq_format()
-            if skip % 2:
-                raise ValueError("skipNumberOfBytes = %d splits an I/Q pair: it must be even" % skip)
             need += need % 2
         with self._prepared_record(name, 0, need, skip if self.interferenceMitigation else None, verbose=True) as rec:
             window = DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip)))

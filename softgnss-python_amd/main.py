@@ -3,7 +3,7 @@
     python -m softgnss-python_amd.main record.bin [--fs 38192000 --IF 9548000 --ms 37000 --channels 8 --skip 0]
                                                   [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]]
-                                                  [--iq[=qi]] [--dtype int8]
+                                                  [--iq[=qi]] [--dtype int8] [--iq-requantize[=RMS]]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -13,7 +13,11 @@ continuous-wave lines in the record's spectrum (8 dB above the local median, or 
 the GPU before acquisition and tracking, and prints the lines it removed.  --iq reads the file as interleaved 8-bit I/Q
 (--iq=qi: Q before I; --dtype uint8: offset binary, as an RTL-SDR writes it): --fs is then the COMPLEX rate and --IF the
 baseband offset of the carrier (0 for a zero-IF front end); the GPU turns the file into the equivalent real record at
-twice the rate, whose rate and IF are printed, and everything else runs on that."""
+twice the rate, whose rate and IF are printed, and everything else runs on that.  --iq-requantize (with --iq and --dtype
+int16 or float32: sc16 and fc32 captures) first brings the file to int8 on the GPU through one fixed gain that puts its rms
+at 12 LSB (or --iq-requantize=RMS), and prints the record's rms, peak, count of non-finite samples, the gain in dB and the
+share of clipped samples; --skip stays a byte of the file (a multiple of 4 for int16, 8 for float32), the positions in the
+results are samples of the converted record, file byte / 2 or / 4."""
 from __future__ import print_function
 
 import argparse
@@ -26,9 +30,8 @@ from . import initialize
 def probe_iq(settings):
     """probeData() of an I/Q file: the first 10 code periods converted on the GPU, probed as the real record they become."""
     from .record import DeviceSignal
-    real = settings.realEquivalent()
-    skip = int(settings.skipNumberOfBytes)
-    with settings._prepared_record(settings.fileName, skip - skip % 2, 10 * real.samplesPerCode) as rec:
+    real = settings._prepared_settings()
+    with settings._prepared_record(settings.fileName, int(real.skipNumberOfBytes), 10 * real.samplesPerCode) as rec:
         return real.probeData(DeviceSignal(rec))
 
 
@@ -56,8 +59,17 @@ def main(argv=None):
     ap.add_argument("--iq", nargs="?", const="iq", default=None, choices=("iq", "qi"), metavar="qi",
                     help="the file is interleaved 8-bit I/Q (--iq=qi: Q first): --fs is the complex rate, --IF the "
                          "baseband offset; it is converted to real IF at twice the rate on the GPU")
-    ap.add_argument("--dtype", default=None, help="dataType of the file's samples (numpy name; with --iq: int8 or uint8)")
+    ap.add_argument("--dtype", default=None,
+                    help="dataType of the file's samples (numpy name; with --iq: int8 or uint8, with --iq-requantize also "
+                         "int16 or float32)")
+    ap.add_argument("--iq-requantize", nargs="?", type=float, const=-1.0, default=None, metavar="RMS",
+                    help="with --iq and --dtype int16 or float32: bring the file to int8 on the GPU through one fixed gain "
+                         "that puts its rms at RMS LSB (default: Settings.iqTargetRms, 12)")
     a = ap.parse_args(argv)
+    if a.iq_requantize is not None and a.iq is None:
+        ap.error("--iq-requantize prepares an I/Q file for the converter: it needs --iq")
+    if a.iq_requantize is not None and not (a.iq_requantize == -1.0 or 0.0 < a.iq_requantize <= 127.0):
+        ap.error("--iq-requantize takes the rms of the int8 record in LSB, above 0 and at most 127")
     if a.iq is not None and a.correlator_bank is not None:
         ap.error("--correlator-bank replays from the record file, which --iq converts on the way in: not both")
     taps = None
@@ -78,6 +90,8 @@ def main(argv=None):
                       ("acqNonCoherent", True if a.acq_noncoh else None),
                       ("iqRecord", True if a.iq is not None else None), ("iqQFirst", True if a.iq == "qi" else None),
                       ("dataType", a.dtype),
+                      ("iqRequantize", True if a.iq_requantize is not None else None),
+                      ("iqTargetRms", a.iq_requantize if a.iq_requantize is not None and a.iq_requantize > 0 else None),
                       ("interferenceMitigation", True if a.notch is not None else None),
                       ("notchThresholdDb", a.notch if a.notch is not None and a.notch >= 0 else None)):
         if val is not None:
