@@ -432,14 +432,11 @@ def replay_state(settings, chans, series, ms_done=None, data_type=DT_INT8, rec_f
     n = len(chans)
     a = _series3(series, n)
     ms = a.shape[2]
-    done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
-    if done is not None and done.shape != (n,):
-        raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+    done, done_p = _ms_done(ms_done, n)
     st = settings_struct(settings)
     out = np.zeros((n, ms), dtype=REPLAY_STATE_DTYPE)
     check(lib().sgx_replay_state(C.byref(st), int(data_type), C.cast(_chan_array(chans), _P), n, ms,
-                                 None if done is None else _ptr(done), _ptr(a), int(rec_file_offset), int(rec_bytes),
-                                 _ptr(out)))
+                                 done_p, _ptr(a), int(rec_file_offset), int(rec_bytes), _ptr(out)))
     return out
 
 
@@ -543,6 +540,30 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ms_done(ms_done, n):
+    """(int32[n] array, its pointer argument) of a per-channel ms_done, or (None, None); the caller holds the array
+    until its call has returned."""
+    if ms_done is None:
+        return None, None
+    done = np.ascontiguousarray(ms_done, dtype=np.int32)
+    if done.shape != (n,):
+        raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+    return done, _ptr(done)
+
+
+_ACQ_FIELDS = ("carrFreq", "codePhase", "peakMetric", "freqBin", "fineIdx")
+
+
+def _acq_out(n):
+    """(the five output arrays of a search over n PRNs, their pointers in the order every sgx_acquire* takes them)."""
+    arrays = tuple(np.zeros(n, dtype=np.int32 if k in ("freqBin", "fineIdx") else np.float64) for k in _ACQ_FIELDS)
+    return arrays, tuple(_ptr(a) for a in arrays)
+
+
+def _acq_dict(arrays):
+    return dict(zip(_ACQ_FIELDS, arrays))
+
+
 def nav_bits(i_p_row, sub_frame_start):
     """uint8 bits (1 = positive 20-ms sum) of I_P[start-20 : start+30000], reference postNavigation.py:125-138."""
     a = np.ascontiguousarray(i_p_row, dtype=np.float64)
@@ -640,45 +661,38 @@ class Context(object):
         return Record(self, h, int(n))
 
     # ---- hot path ----
+    def _supersede(self):
+        """Any search supersedes a deferred one nobody has looked at: one search may be pending per context."""
+        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        return self._acq_token
+
     def acquire(self, rec, offset, n_samples, prn0, n_blocks=2, noncoh=False):
-        self._acq_token = getattr(self, "_acq_token", 0) + 1   # (any search supersedes a deferred one nobody has looked at)
+        self._supersede()
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        n = prn.size
-        carr = np.zeros(n)
-        cph = np.zeros(n)
-        met = np.zeros(n)
-        fb = np.zeros(n, dtype=np.int32)
-        fi = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_acquire(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), n, int(n_blocks),
-                                1 if noncoh else 0, _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+        out, ptrs = _acq_out(prn.size)
+        check(lib().sgx_acquire(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
+                                1 if noncoh else 0, *ptrs))
+        return _acq_dict(out)
 
     def acquire_coherent(self, rec, offset, n_samples, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
         """acquire() with coherent_ms-ms windows (n_windows of them) on a bin_step_hz grid (None: 500 / coherent_ms)."""
-        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        self._supersede()
         pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        n = prn.size
-        carr, cph, met = np.zeros(n), np.zeros(n), np.zeros(n)
-        fb = np.zeros(n, dtype=np.int32)
-        fi = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_acquire_coherent(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), n, C.byref(pa),
-                                         _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+        out, ptrs = _acq_out(prn.size)
+        check(lib().sgx_acquire_coherent(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, C.byref(pa),
+                                         *ptrs))
+        return _acq_dict(out)
 
     def acquire_coherent_f64(self, signal, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
         """acquire_coherent() on a host signal of any real dtype (copied to HBM as fp64)."""
-        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        self._supersede()
         pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
         sig = np.ascontiguousarray(signal, dtype=np.float64)
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        n = prn.size
-        carr, cph, met = np.zeros(n), np.zeros(n), np.zeros(n)
-        fb = np.zeros(n, dtype=np.int32)
-        fi = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_acquire_coherent_f64(self._h, _ptr(sig), sig.size, _ptr(prn), n, C.byref(pa),
-                                             _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+        out, ptrs = _acq_out(prn.size)
+        check(lib().sgx_acquire_coherent_f64(self._h, _ptr(sig), sig.size, _ptr(prn), prn.size, C.byref(pa), *ptrs))
+        return _acq_dict(out)
 
     @staticmethod
     def acquire_coherent_plan(settings, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
@@ -691,17 +705,12 @@ class Context(object):
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
         check(lib().sgx_acquire_begin(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
                                       1 if noncoh else 0))
-        self._acq_token = getattr(self, "_acq_token", 0) + 1   # (one search may be pending per context)
-        return self._acq_token
+        return self._supersede()   # (only a search that was queued takes the token)
 
     def acquire_end(self, n):
-        carr = np.zeros(n)
-        cph = np.zeros(n)
-        met = np.zeros(n)
-        fb = np.zeros(n, dtype=np.int32)
-        fi = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_acquire_end(self._h, _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+        out, ptrs = _acq_out(n)
+        check(lib().sgx_acquire_end(self._h, *ptrs))
+        return _acq_dict(out)
 
     def track_chained(self, rec, n_ch, ms, rec_file_offset=0, data_type=DT_INT8):
         """preRun on the device behind the pending acquisition + the tracking kernel behind it, one wait.
@@ -723,31 +732,22 @@ class Context(object):
     def acquire_sharded(self, comm, rank, world, rec, offset, n_samples, n_prn_total=32, n_blocks=2, noncoh=False):
         """This rank's share of the PRN search + the peak gather as ONE library call (sgx_acquire_sharded): packed on the
         device, one ncclAllGather (comm: a Comm, or None for no collective), one look.  Returns the merged 32-entry arrays."""
-        self._acq_token = getattr(self, "_acq_token", 0) + 1
-        carr = np.zeros(32)
-        cph = np.zeros(32)
-        met = np.zeros(32)
-        fb = np.zeros(32, dtype=np.int32)
-        fi = np.zeros(32, dtype=np.int32)
+        self._supersede()
+        out, ptrs = _acq_out(32)
         check(lib().sgx_acquire_sharded(self._h, comm._h if comm is not None else None, int(rank), int(world), rec._h,
                                         int(offset), int(n_samples), int(n_prn_total), int(n_blocks), 1 if noncoh else 0,
-                                        _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb.astype(np.int64), fineIdx=fi.astype(np.int64))
+                                        *ptrs))
+        return _acq_dict(out[:3] + (out[3].astype(np.int64), out[4].astype(np.int64)))
 
     def acquire_f64(self, signal, prn0, n_blocks=2, noncoh=False):
         """acquire() on a host signal of any real dtype (copied to HBM as fp64)."""
-        self._acq_token = getattr(self, "_acq_token", 0) + 1
+        self._supersede()
         sig = np.ascontiguousarray(signal, dtype=np.float64)
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        n = prn.size
-        carr = np.zeros(n)
-        cph = np.zeros(n)
-        met = np.zeros(n)
-        fb = np.zeros(n, dtype=np.int32)
-        fi = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_acquire_f64(self._h, _ptr(sig), sig.size, _ptr(prn), n, int(n_blocks), 1 if noncoh else 0,
-                                    _ptr(carr), _ptr(cph), _ptr(met), _ptr(fb), _ptr(fi)))
-        return dict(carrFreq=carr, codePhase=cph, peakMetric=met, freqBin=fb, fineIdx=fi)
+        out, ptrs = _acq_out(prn.size)
+        check(lib().sgx_acquire_f64(self._h, _ptr(sig), sig.size, _ptr(prn), prn.size, int(n_blocks), 1 if noncoh else 0,
+                                    *ptrs))
+        return _acq_dict(out)
 
     def probe_stats(self, rec, offset, n, fs_mhz):
         """(f, Pxx, hist, n_segments) of the record window: Welch PSD and histogram of Settings.probeData."""
@@ -790,12 +790,9 @@ class Context(object):
         cl = np.empty((n, nw))
         ok = np.empty((n, nw), dtype=np.uint8)
         lost = np.empty(n, dtype=np.int32)
-        done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
-        if done is not None and done.shape != (n,):
-            raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+        done, done_p = _ms_done(ms_done, n)
         check(lib().sgx_track_quality(self._h, _ptr(a), _ptr(b), int(sa), int(n), int(ms),
-                                      None if done is None else _ptr(done), C.byref(params), _ptr(cno), _ptr(cl),
-                                      _ptr(ok), _ptr(lost)))
+                                      done_p, C.byref(params), _ptr(cno), _ptr(cl), _ptr(ok), _ptr(lost)))
         return cno, cl, ok.astype(bool), lost
 
     def track_replay(self, rec, chans, series, taps, ms_done=None, rec_file_offset=0, data_type=DT_INT8):
@@ -806,13 +803,10 @@ class Context(object):
         a = _series3(series, n)
         ms = a.shape[2]
         tp = np.ascontiguousarray(taps, dtype=np.float64).ravel()
-        done = None if ms_done is None else np.ascontiguousarray(ms_done, dtype=np.int32)
-        if done is not None and done.shape != (n,):
-            raise ValueError("ms_done has shape %r, expected (%d,)" % (done.shape, n))
+        done, done_p = _ms_done(ms_done, n)
         out = np.zeros((n, tp.size, 2, ms))
         check(lib().sgx_track_replay(self._h, rec._h, int(rec_file_offset), C.cast(_chan_array(chans), _P), n, ms,
-                                     None if done is None else _ptr(done), _ptr(a), int(data_type), _ptr(tp), tp.size,
-                                     _ptr(out)))
+                                     done_p, _ptr(a), int(data_type), _ptr(tp), tp.size, _ptr(out)))
         return out
 
     def replay_timing(self):

@@ -1344,10 +1344,21 @@ struct AcqCall {
     size_t n_samples;
     const int32_t* prn0;
     int n_prn;
-    double *carrFreq, *codePhase, *peakMetric;   // outputs, [n_prn]
-    int32_t *freqBin, *fineIdx;
+    AcqOut out;   // [n_prn]
     AcqEnv env;
 };
+static AcqCall acq_call(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, const AcqOut& out,
+                        const AcqEnv& env) {
+    AcqCall a;
+    a.c = c;
+    a.x = x;
+    a.n_samples = n_samples;
+    a.prn0 = prn0;
+    a.n_prn = n_prn;
+    a.out = out;
+    a.env = env;
+    return a;
+}
 // The detections of a call (acquisition.py:164-166) in ascending position of its PRN list
 struct AcqDets {
     std::vector<int> prn, phase, slot;
@@ -1383,21 +1394,6 @@ static int acq_record_sig(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_s
     return SGX_OK;
 }
 
-// What sgx_acquire and sgx_acquire_begin check before they touch the device: PRN list, blocks, the record window
-static int acq_open_record(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
-                           int32_t n_blocks, SgxSig* x) {
-    SGX_CHECK_ARG(n_blocks >= 1 && n_blocks <= 64);
-    const int rc = acq_check_prns(prn0, n_prn);
-    if (rc != SGX_OK) return rc;
-    const long long N = c->n_code;
-    if (offset > r->n || n_samples > r->n - offset || (long long)n_samples < (long long)n_blocks * N) {
-        sgx_set_error("record window too short: %zu samples at offset %zu, %lld needed for the coarse search",
-                      n_samples, offset, (long long)n_blocks * N);
-        return SGX_E_RANGE;
-    }
-    return acq_record_sig(c, r, offset, n_samples, x);
-}
-
 // acquire() on a signal that is not int8 (acquisition.py:55-59 takes whatever real dtype numpy hands it): the caller's
 // fp64 samples are copied to HBM and every kernel reads them instead of the int8 record; the arithmetic is the same
 // fp64 arithmetic either way.
@@ -1421,18 +1417,56 @@ static int acq_upload_f64(sgx_ctx* c, const double* signal, size_t n_samples, Sg
     return SGX_OK;
 }
 
-static void acq_reset_outputs(double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx,
-                              int n) {
+// Where a search's samples come from: n_samples at `offset` of a resident record, or (r null) of the caller's fp64 signal
+struct AcqSource {
+    const sgx_if* r;
+    size_t offset;
+    const double* signal;
+    size_t n_samples;
+};
+static int acq_source_sig(sgx_ctx* c, const AcqSource& src, SgxSig* x) {
+    return src.r ? acq_record_sig(c, src.r, src.offset, src.n_samples, x) : acq_upload_f64(c, src.signal, src.n_samples, x);
+}
+
+// What the searches on the reference's grid check before they touch the device: PRN list, blocks, the source's length
+static int acq_open_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0, int32_t n_prn, int32_t n_blocks, SgxSig* x) {
+    SGX_CHECK_ARG(c && (src.r || src.signal) && prn0);
+    SGX_CHECK_ARG(n_blocks >= 1 && n_blocks <= 64);
+    const int rc = acq_check_prns(prn0, n_prn);
+    if (rc != SGX_OK) return rc;
+    const long long need = (long long)n_blocks * c->n_code;
+    const bool outside = src.r && (src.offset > src.r->n || src.n_samples > src.r->n - src.offset);
+    if (outside || (long long)src.n_samples < need) {
+        if (src.r)
+            sgx_set_error("record window too short: %zu samples at offset %zu, %lld needed for the coarse search",
+                          src.n_samples, src.offset, need);
+        else
+            sgx_set_error("signal too short: %zu samples, %lld needed for the coarse search", src.n_samples, need);
+        return SGX_E_RANGE;
+    }
+    return acq_source_sig(c, src, x);
+}
+
+static bool acq_out_non_null(const AcqOut& o) {
+    return o.carrFreq && o.codePhase && o.peakMetric && o.freqBin && o.fineIdx;
+}
+static void acq_reset_outputs(const AcqOut& o, int n) {
     for (int i = 0; i < n; ++i) {
-        carrFreq[i] = 0.0;
-        codePhase[i] = 0.0;
-        peakMetric[i] = 0.0;
-        freqBin[i] = -1;
-        fineIdx[i] = -1;
+        o.carrFreq[i] = 0.0;
+        o.codePhase[i] = 0.0;
+        o.peakMetric[i] = 0.0;
+        o.freqBin[i] = -1;
+        o.fineIdx[i] = -1;
     }
 }
-static void acq_reset_outputs(const AcqCall& a) {
-    acq_reset_outputs(a.carrFreq, a.codePhase, a.peakMetric, a.freqBin, a.fineIdx, a.n_prn);
+static void acq_copy_results(const AcqOut& dst, const AcqOut& src, int n) {
+    for (int i = 0; i < n; ++i) {
+        dst.carrFreq[i] = src.carrFreq[i];
+        dst.codePhase[i] = src.codePhase[i];
+        dst.peakMetric[i] = src.peakMetric[i];
+        dst.freqBin[i] = src.freqBin[i];
+        dst.fineIdx[i] = src.fineIdx[i];
+    }
 }
 
 // Device times of a call from its events ev[0] (start), ev[1] (between coarse and fine search), ev[2] (end).  An event
@@ -1476,8 +1510,8 @@ static int acq_look_decode(const AcqCall& a, const PeakOut& po, const double* se
     for (int i = 0; i < n; ++i) {
         const int o = first + i;
         const double ratio = po.peak[i] / second[i];
-        a.peakMetric[o] = ratio;
-        a.freqBin[o] = po.fbi[i];
+        a.out.peakMetric[o] = ratio;
+        a.out.freqBin[o] = po.fbi[i];
         if (ratio > a.c->s.acqThreshold) {
             det->prn.push_back(a.prn0[o]);
             det->phase.push_back(po.cph[i]);
@@ -1752,9 +1786,9 @@ static int acquire_fine(const AcqCall& a, const AcqDets& det, long long* d_sum, 
         }
         const long long m = bi - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
         const int o = det.slot[d];
-        a.carrFreq[o] = ((double)m * S.samplingFreq) / (double)npts;   // acquisition.py:189-191 (Q3)
-        a.codePhase[o] = (double)det.phase[d];
-        a.fineIdx[o] = (int)m;
+        a.out.carrFreq[o] = ((double)m * S.samplingFreq) / (double)npts;   // acquisition.py:189-191 (Q3)
+        a.out.codePhase[o] = (double)det.phase[d];
+        a.out.fineIdx[o] = (int)m;
     }
     return SGX_OK;
 }
@@ -1765,7 +1799,7 @@ static int acq_fine_and_times(const AcqCall& a, const AcqDets& det, long long* d
     std::vector<long long> win;
     if (g && g->T > 1) {
         std::vector<int> det_bin;
-        for (int o : det.slot) det_bin.push_back(a.freqBin[o]);
+        for (int o : det.slot) det_bin.push_back(a.out.freqBin[o]);
         win = coh_fine_windows(*g, a.c->s, a.c->n_code, det_bin);
     }
     const int rc = acquire_fine(a, det, d_sum, win.empty() ? nullptr : &win);
@@ -1881,7 +1915,7 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     // ---- correlation + peak search, PRN chunk by chunk ---------------------------------------------
     AcqDets det;
     int status = SGX_OK;
-    acq_reset_outputs(a);
+    acq_reset_outputs(a.out, a.n_prn);
     const double inv_n = 1.0 / (double)L;
     const int out_per_prn = noncoh ? n_bins : rows_per_prn;
     for (int p0 = 0; p0 < n_prn && status == SGX_OK; p0 += prn_chunk) {
@@ -2064,7 +2098,7 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
         rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
         if (rc != SGX_OK) return rc;
     }
-    acq_reset_outputs(a);
+    acq_reset_outputs(a.out, a.n_prn);
     // ---- correlation, all PRN chunks queued back to back; row maxima of every PRN collected on the device -----------
     hipStream_t st2 = st;
     if (two_q) {
@@ -2184,24 +2218,18 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
         P.split_event = a.env.split_event;
         P.spin = a.env.spin;
         if (defer) return SGX_OK;
-        return sgx_acquire_finish(c, a.carrFreq, a.codePhase, a.peakMetric, a.freqBin, a.fineIdx);
+        return sgx_acquire_finish(c, a.out);
     }
     return acq_host_tail(a, seq, d_sum, nullptr);
 }
 
 // The host's ONE look at a device-led acquisition (queued by acquire_four_step; c->acq_pending says what was asked): waits
 // for the result page's second word, then decodes peaks, detections and fine frequencies exactly as the eager call did.
-int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
+int sgx_acquire_finish(sgx_ctx* c, const AcqOut& out) {
     AcqPending& P = c->acq_pending;
     if (P.mode == 2) {   // (the search could not be deferred and ran eagerly: its outputs were kept)
         P.mode = 0;
-        for (int i = 0; i < P.n_prn; ++i) {
-            carrFreq[i] = P.res_carr[i];
-            codePhase[i] = P.res_cph[i];
-            peakMetric[i] = P.res_met[i];
-            freqBin[i] = P.res_fb[i];
-            fineIdx[i] = P.res_fi[i];
-        }
+        acq_copy_results(out, P.res.out(), P.n_prn);
         return P.rc;
     }
     if (P.mode != 1) {
@@ -2210,17 +2238,11 @@ int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* 
     }
     P.mode = 0;
     const sgx_settings& S = c->s;
-    AcqCall a{};
-    a.c = c;
-    a.n_samples = P.n_samples;
-    a.prn0 = P.prn0;
-    a.n_prn = P.n_prn;
-    a.carrFreq = carrFreq;
-    a.codePhase = codePhase;
-    a.peakMetric = peakMetric;
-    a.freqBin = freqBin;
-    a.fineIdx = fineIdx;
-    acq_reset_outputs(a);
+    AcqEnv env{};   // (only what the queued call left for its look: the environment is not read again)
+    env.split_event = P.split_event;
+    env.spin = P.spin;
+    const AcqCall a = acq_call(c, SgxSig{nullptr, nullptr}, P.n_samples, P.prn0, P.n_prn, out, env);
+    acq_reset_outputs(a.out, a.n_prn);
     const CoarseLook* look = (const CoarseLook*)c->h_look;
     int rc = coarse_look_wait(c, &look->seq2, P.seq, P.spin);
     if (rc != SGX_OK) return rc;
@@ -2235,9 +2257,9 @@ int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* 
     for (int d = 0; d < look->n_det; ++d) {
         const long long m = look->fine_bi[d] - 4;   // index inside the [4:uniq-5] slice (acquisition.py:187)
         const int o = look->det_slot[d];
-        carrFreq[o] = ((double)m * S.samplingFreq) / (double)P.npts;   // acquisition.py:189-191 (Q3)
-        codePhase[o] = (double)look->det_phase[d];
-        fineIdx[o] = (int)m;
+        out.carrFreq[o] = ((double)m * S.samplingFreq) / (double)P.npts;   // acquisition.py:189-191 (Q3)
+        out.codePhase[o] = (double)look->det_phase[d];
+        out.fineIdx[o] = (int)m;
     }
     // (the result word is stored a moment before the last kernel retires: the device times below need its event)
     SGX_HIP(hipEventSynchronize(c->ev[2]));
@@ -2302,7 +2324,7 @@ static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
         rc = sgx_fft4_forward(&c->plan_code, c->d_work[1], c->d_work[0], c->d_fwd, rows_fwd + n_prn, st, nullptr);
         if (rc != SGX_OK) return rc;
     }
-    acq_reset_outputs(a);
+    acq_reset_outputs(a.out, a.n_prn);
     // ---- correlation: batches of whole PRNs, or one PRN in runs of bins (noncoh) / windows (reference rule) ----------
     const int total = noncoh ? n_bins : M;
     for (int p0 = 0; p0 < n_prn; p0 += g.prn_chunk)
@@ -2325,23 +2347,6 @@ static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
 }
 
 // ================================ entry points ================================
-static AcqCall acq_call(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, double* carrFreq,
-                        double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
-    AcqCall a;
-    a.c = c;
-    a.x = x;
-    a.n_samples = n_samples;
-    a.prn0 = prn0;
-    a.n_prn = n_prn;
-    a.carrFreq = carrFreq;
-    a.codePhase = codePhase;
-    a.peakMetric = peakMetric;
-    a.freqBin = freqBin;
-    a.fineIdx = fineIdx;
-    a.env = env;
-    return a;
-}
-
 static int acquire_any(const AcqCall& a, int n_blocks, int noncoh) {
     // the four-step path (sub-transforms in registers and LDS, shifted forward spectra) where it applies
     bool handled = false;
@@ -2350,45 +2355,25 @@ static int acquire_any(const AcqCall& a, int n_blocks, int noncoh) {
     return acquire_passes(a, n_blocks, noncoh);
 }
 
-static int acquire_record(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
-                          int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
-                          int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
-    SGX_CHECK_ARG(c && r && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+static int acquire_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0, int32_t n_prn, int32_t n_blocks, int32_t noncoh,
+                          const AcqOut& out, const AcqEnv& env) {
+    SGX_CHECK_ARG(acq_out_non_null(out));
     SgxSig x;
-    const int rc = acq_open_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, &x);
+    const int rc = acq_open_source(c, src, prn0, n_prn, n_blocks, &x);
     if (rc != SGX_OK) return rc;
-    return acquire_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), n_blocks,
-                       noncoh);
+    return acquire_any(acq_call(c, x, src.n_samples, prn0, n_prn, out, env), n_blocks, noncoh);
 }
 extern "C" int sgx_acquire(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
                            int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
                            double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    return acquire_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin,
-                          fineIdx, acq_env());
-}
-
-static int acquire_signal(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
-                          int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
-                          int32_t* freqBin, int32_t* fineIdx, const AcqEnv& env) {
-    SGX_CHECK_ARG(c && signal && prn0 && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_CHECK_ARG(n_blocks >= 1 && n_blocks <= 64);
-    int rc = acq_check_prns(prn0, n_prn);
-    if (rc != SGX_OK) return rc;
-    const long long N = c->n_code;
-    if ((long long)n_samples < (long long)n_blocks * N) {
-        sgx_set_error("signal too short: %zu samples, %lld needed for the coarse search", n_samples, (long long)n_blocks * N);
-        return SGX_E_RANGE;
-    }
-    SgxSig x;
-    if ((rc = acq_upload_f64(c, signal, n_samples, &x)) != SGX_OK) return rc;
-    return acquire_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), n_blocks,
-                       noncoh);
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    return acquire_source(c, AcqSource{r, offset, nullptr, n_samples}, prn0, n_prn, n_blocks, noncoh, out, acq_env());
 }
 extern "C" int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0, int32_t n_prn,
                                int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase, double* peakMetric,
                                int32_t* freqBin, int32_t* fineIdx) {
-    return acquire_signal(c, signal, n_samples, prn0, n_prn, n_blocks, noncoh, carrFreq, codePhase, peakMetric, freqBin, fineIdx,
-                          acq_env());
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    return acquire_source(c, AcqSource{nullptr, 0, signal, n_samples}, prn0, n_prn, n_blocks, noncoh, out, acq_env());
 }
 
 int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes, long long rec_file_offset, int sample_bytes) {
@@ -2410,13 +2395,12 @@ int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes
 // the same kernels in the same order, and acq_prerun_kernel repeats the host's arithmetic.
 static int acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
                          int32_t n_blocks, int32_t noncoh, const AcqEnv& env) {
-    SGX_CHECK_ARG(c && r && prn0);
     SgxSig x;
-    int rc = acq_open_record(c, r, offset, n_samples, prn0, n_prn, n_blocks, &x);
+    int rc = acq_open_source(c, AcqSource{r, offset, nullptr, n_samples}, prn0, n_prn, n_blocks, &x);
     if (rc != SGX_OK) return rc;
     AcqPending& P = c->acq_pending;
     P.mode = 0;
-    const AcqCall a = acq_call(c, x, n_samples, prn0, n_prn, P.res_carr, P.res_cph, P.res_met, P.res_fb, P.res_fi, env);
+    const AcqCall a = acq_call(c, x, n_samples, prn0, n_prn, P.res.out(), env);
     bool handled = false;
     rc = acquire_four_step(a, n_blocks, noncoh, &handled, true);
     if (handled && P.mode == 1) return rc;          // queued; nothing has been looked at
@@ -2434,9 +2418,10 @@ extern "C" int sgx_acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, siz
 
 extern "C" int sgx_acquire_end(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin,
                                int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    SGX_CHECK_ARG(c && acq_out_non_null(out));
     SGX_HIP(hipSetDevice(c->device));
-    return sgx_acquire_finish(c, carrFreq, codePhase, peakMetric, freqBin, fineIdx);
+    return sgx_acquire_finish(c, out);
 }
 
 // ================================ round 6: the sharded search as ONE call ================================
@@ -2448,11 +2433,12 @@ extern "C" int sgx_acquire_end(sgx_ctx* c, double* carrFreq, double* codePhase, 
 extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int32_t world, const sgx_if* r, size_t offset,
                                    size_t n_samples, int32_t n_prn_total, int32_t n_blocks, int32_t noncoh, double* carrFreq,
                                    double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && r && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    SGX_CHECK_ARG(c && r && acq_out_non_null(out));
     SGX_CHECK_ARG(world >= 1 && rank >= 0 && rank < world && n_prn_total >= 1 && n_prn_total <= 32);
     SGX_CHECK_ARG(!comm || (comm->n_ranks == world && comm->rank == rank && comm->ctx == c));
     const AcqEnv env = acq_env();
-    acq_reset_outputs(carrFreq, codePhase, peakMetric, freqBin, fineIdx, 32);
+    acq_reset_outputs(out, 32);
     // contiguous balanced partition (shard.plan_shards)
     const int base = n_prn_total / world, extra = n_prn_total % world;
     const int first = rank * base + (rank < extra ? rank : extra);
@@ -2475,17 +2461,12 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
         if (rb != SGX_OK) return rb;
         queued = c->acq_pending.mode == 1;
         if (!queued) {
-            double cf[32], cp[32], pm[32];
-            int fb[32], fi[32];
-            const int re = sgx_acquire_finish(c, cf, cp, pm, fb, fi);
+            AcqResults mine;
+            const int re = sgx_acquire_finish(c, mine.out());
             if (re != SGX_OK && re != SGX_E_INDEX && re != SGX_E_RANGE) return re;
             host_pack.resize((size_t)slots);
             memset(host_pack.data(), 0, rec_bytes);
-            for (int i = 0; i < n_mine; ++i) {
-                PeakRec& q = host_pack[(size_t)i];
-                q.prn0 = prn0[i]; q.freqBin = fb[i]; q.carrFreq = cf[i]; q.codePhase = cp[i]; q.peakMetric = pm[i];
-                q.fineIdx = fi[i]; q.valid = 1;
-            }
+            for (int i = 0; i < n_mine; ++i) host_pack[(size_t)i] = peak_rec_pack(prn0[i], mine.out(), i);
             if (re != SGX_OK) host_pack[0].valid = re == SGX_E_INDEX ? -1 : -2;   // (every rank learns of it)
         }
     }
@@ -2530,11 +2511,7 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
         if (q.valid == -1) return acq_index_error(c->n_code, q.prn0, (int)q.codePhase);
         if (q.valid == -2) return acq_fine_range_error((long long)q.codePhase + acq_fine_geom(c->n_code).len, n_samples);
         if (q.prn0 < 0 || q.prn0 >= 32) continue;
-        carrFreq[q.prn0] = q.carrFreq;
-        codePhase[q.prn0] = q.codePhase;
-        peakMetric[q.prn0] = q.peakMetric;
-        freqBin[q.prn0] = q.freqBin;
-        fineIdx[q.prn0] = q.fineIdx;
+        peak_rec_merge(q, out);
     }
     return SGX_OK;
 }
@@ -2564,39 +2541,31 @@ static int coherent_checks(sgx_ctx* c, size_t n_samples, const int32_t* prn0, in
     return SGX_OK;
 }
 
+static int acquire_coherent_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0, int32_t n_prn, const sgx_acq_params* p,
+                                   const AcqOut& out) {
+    SGX_CHECK_ARG(c && (src.r || src.signal) && prn0 && p && acq_out_non_null(out));
+    if (src.r) SGX_CHECK_ARG(src.offset <= src.r->n && src.n_samples <= src.r->n - src.offset);
+    const AcqEnv env = acq_env();
+    CohGrid g;
+    bool legacy = false;
+    int rc = coherent_checks(c, src.n_samples, prn0, n_prn, p, &g, &legacy);
+    if (rc != SGX_OK) return rc;
+    if (legacy) return acquire_source(c, src, prn0, n_prn, g.M, g.noncoh, out, env);
+    SgxSig x;
+    if ((rc = acq_source_sig(c, src, &x)) != SGX_OK) return rc;
+    return acquire_coherent_any(acq_call(c, x, src.n_samples, prn0, n_prn, out, env), g);
+}
 extern "C" int sgx_acquire_coherent(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
                                     int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,
                                     double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && r && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    SGX_CHECK_ARG(offset <= r->n && n_samples <= r->n - offset);
-    const AcqEnv env = acq_env();
-    CohGrid g;
-    bool legacy = false;
-    int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
-    if (rc != SGX_OK) return rc;
-    if (legacy)
-        return acquire_record(c, r, offset, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
-                              fineIdx, env);
-    SgxSig x;
-    if ((rc = acq_record_sig(c, r, offset, n_samples, &x)) != SGX_OK) return rc;
-    return acquire_coherent_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), g);
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    return acquire_coherent_source(c, AcqSource{r, offset, nullptr, n_samples}, prn0, n_prn, p, out);
 }
-
 extern "C" int sgx_acquire_coherent_f64(sgx_ctx* c, const double* signal, size_t n_samples, const int32_t* prn0,
                                         int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,
                                         double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
-    SGX_CHECK_ARG(c && signal && prn0 && p && carrFreq && codePhase && peakMetric && freqBin && fineIdx);
-    const AcqEnv env = acq_env();
-    CohGrid g;
-    bool legacy = false;
-    int rc = coherent_checks(c, n_samples, prn0, n_prn, p, &g, &legacy);
-    if (rc != SGX_OK) return rc;
-    if (legacy)
-        return acquire_signal(c, signal, n_samples, prn0, n_prn, g.M, g.noncoh, carrFreq, codePhase, peakMetric, freqBin,
-                              fineIdx, env);
-    SgxSig x;
-    if ((rc = acq_upload_f64(c, signal, n_samples, &x)) != SGX_OK) return rc;
-    return acquire_coherent_any(acq_call(c, x, n_samples, prn0, n_prn, carrFreq, codePhase, peakMetric, freqBin, fineIdx, env), g);
+    const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
+    return acquire_coherent_source(c, AcqSource{nullptr, 0, signal, n_samples}, prn0, n_prn, p, out);
 }
 
 extern "C" int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, int32_t* n_bins, int32_t* n_phi,

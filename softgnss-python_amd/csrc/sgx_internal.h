@@ -153,12 +153,35 @@ struct AcqDet {
     unsigned fine_done;       // fine_rows_kernel's arrival counter (zero between calls)
 };
 
+// Where an acquisition call leaves its results: the caller's five arrays, one entry per PRN of the call's list
+struct AcqOut {
+    double *carrFreq, *codePhase, *peakMetric;
+    int32_t *freqBin, *fineIdx;
+};
+// ... and the same results kept by the library for up to 32 PRNs
+struct AcqResults {
+    double carrFreq[32], codePhase[32], peakMetric[32];
+    int32_t freqBin[32], fineIdx[32];
+    AcqOut out() { return AcqOut{carrFreq, codePhase, peakMetric, freqBin, fineIdx}; }
+};
+
 struct PeakRec {      // a rank's peak in the sharded search = shard.PEAK_DTYPE, 40 bytes
     int prn0, freqBin;
     double carrFreq, codePhase, peakMetric;
     int fineIdx, valid;   // valid 1; 0 unused slot; -1 the reference's IndexError at this PRN; -2 its fine window leaves the record
 };
 static_assert(sizeof(PeakRec) == 40, "shard.PEAK_DTYPE");
+// Entry i of a call's results as the valid record of PRN prn0, and a record into entry q.prn0 of the merged results
+inline PeakRec peak_rec_pack(int prn0, const AcqOut& o, int i) {
+    return PeakRec{prn0, o.freqBin[i], o.carrFreq[i], o.codePhase[i], o.peakMetric[i], o.fineIdx[i], 1};
+}
+inline void peak_rec_merge(const PeakRec& q, const AcqOut& o) {
+    o.carrFreq[q.prn0] = q.carrFreq;
+    o.codePhase[q.prn0] = q.codePhase;
+    o.peakMetric[q.prn0] = q.peakMetric;
+    o.freqBin[q.prn0] = q.freqBin;
+    o.fineIdx[q.prn0] = q.fineIdx;
+}
 
 // The context's small device area (d_small) and its pinned mirror (h_small): one layout for both.  Every slot reaches the
 // kernels as a pointer argument.  A slot is used through the device area, the mirror or both as its comment says.  (alignas:
@@ -201,7 +224,7 @@ static_assert(sizeof(SgxSmall) <= SGX_SMALL_BYTES, "the small areas hold the lay
 
 // A DEFERRED acquisition (sgx_acquire_begin, round 6): every kernel of the search is queued, the host has not looked.
 // mode 1: the device-led sequence is in flight (the result page's seq2 will equal `seq`); mode 2: the path could not be
-// deferred, the search ran eagerly and its outputs wait in res_* for sgx_acquire_end.
+// deferred, the search ran eagerly and its outputs wait in `res` for sgx_acquire_end.
 struct AcqPending {
     int mode = 0;
     unsigned long long seq = 0;
@@ -211,8 +234,7 @@ struct AcqPending {
     size_t n_samples = 0;
     bool split_event = false, spin = true;   // SGX_ACQ_SPLIT_EVENT / SGX_ACQ_SPIN as the queued call read them
     int rc = 0;                // mode 2: the eager search's return code
-    double res_carr[32], res_cph[32], res_met[32];
-    int res_fb[32], res_fi[32];
+    AcqResults res;
 };
 
 // What the device-side preRun + a chained tracking launch leave in the upper half of the result page (offset 2048)
@@ -400,7 +422,7 @@ struct TrkChan {      // one channel as the tracking kernels read it
 };
 int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes, long long rec_file_offset, int sample_bytes);
 // Wait for a deferred acquisition and decode it (the tail of the eager call); clears c->acq_pending.
-int sgx_acquire_finish(sgx_ctx* c, double* carrFreq, double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx);
+int sgx_acquire_finish(sgx_ctx* c, const AcqOut& out);
 
 // sgx_host.cpp: the RCCL communicator of a context (librccl.so by dlopen)
 struct sgx_comm {

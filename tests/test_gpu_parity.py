@@ -2132,3 +2132,42 @@ def test_sharded_search_reports_the_references_index_error_from_the_rank_that_me
     finally:
         comm.close()
     rec.free()
+
+
+@pytest.fixture(scope="module")
+def unqueued_search():
+    """(context, record, sgx_acquire's results) at 16.3676 Msps: N = 16 368 is not the four-step length, so no search on it
+    can be queued.  11 ms, PRNs 1 and 3 at the amplitudes of test_other_front_ends_against_oracle, PRN 2 absent."""
+    m = pkg()
+    s = m.Settings()
+    s.samplingFreq, s.IF = 16367600.0, 4130400.0
+    n = s.samplesPerCode
+    assert n == 16368
+    ctx = m.engine.get_context(s, 0)
+    rec = ctx.synth(m.synth.Scene.make(0xFE000 + n, s.samplingFreq, s.IF, [1, 3], [1750.0, -3300.0], [n // 3, n - 5], [9, 8]),
+                    11 * n)
+    want = ctx.acquire(rec, 0, 11 * n, [0, 1, 2])
+    assert list(want["carrFreq"] > 0) == [True, False, True]
+    yield ctx, rec, want
+    rec.free()
+
+
+def test_a_deferred_search_that_ran_eagerly_hands_over_what_the_eager_call_returns(unqueued_search):
+    """sgx_acquire_begin on a path without the device-led sequence keeps its results in the context; sgx_acquire_end copies
+    them out: all five arrays bit for bit."""
+    ctx, rec, want = unqueued_search
+    ctx.acquire_begin(rec, 0, rec.n, [0, 1, 2])
+    got = ctx.acquire_end(3)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+
+
+def test_a_sharded_search_packed_on_the_host_equals_the_eager_call(unqueued_search):
+    """sgx_acquire_sharded for one rank without a communicator, its share packed into peak records on the host and merged
+    back: entries 0..2 are sgx_acquire's, every other entry keeps its reset value."""
+    ctx, rec, want = unqueued_search
+    got = ctx.acquire_sharded(None, 0, 1, rec, 0, rec.n, n_prn_total=3)
+    for k, reset in (("carrFreq", 0.0), ("codePhase", 0.0), ("peakMetric", 0.0), ("freqBin", -1), ("fineIdx", -1)):
+        ref = want[k].astype(np.int64) if reset == -1 else want[k]
+        assert got[k].shape == (32,) and got[k].dtype == ref.dtype, k
+        assert np.array_equal(got[k][:3], ref) and np.all(got[k][3:] == reset), k
