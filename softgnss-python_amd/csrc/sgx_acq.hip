@@ -949,7 +949,7 @@ __global__ __launch_bounds__(64) void acq_pack_kernel(const CoarseLook* __restri
     out[t] = r;
 }
 
-// gathered records -> the result page (its upper half), then the word the host spins on
+// gathered records -> the result page (LookPage::gather), then the word the host spins on
 __global__ __launch_bounds__(256) void acq_gather_publish_kernel(const int* __restrict__ src, int n_words, int* __restrict__ dst,
                                                                  unsigned long long* __restrict__ word, unsigned long long seq) {
     for (int i = threadIdx.x; i < n_words; i += 256) dst[i] = src[i];
@@ -1364,20 +1364,6 @@ struct AcqDets {
     std::vector<int> prn, phase, slot;
 };
 
-static int ensure_buf(void** p, size_t* cap_bytes, size_t need) {
-    if (*p && *cap_bytes >= need) return SGX_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    hipError_t e = hipMalloc(p, need);
-    if (e != hipSuccess) {
-        sgx_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        *cap_bytes = 0;
-        return SGX_E_NOMEM;
-    }
-    *cap_bytes = need;
-    return SGX_OK;
-}
-
 static int acq_check_prns(const int32_t* prn0, int32_t n_prn) {
     SGX_CHECK_ARG(n_prn >= 1 && n_prn <= 32);
     for (int i = 0; i < n_prn; ++i) SGX_CHECK_ARG(prn0[i] >= 0 && prn0[i] < 32);
@@ -1399,17 +1385,8 @@ static int acq_record_sig(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_s
 // fp64 arithmetic either way.
 static int acq_upload_f64(sgx_ctx* c, const double* signal, size_t n_samples, SgxSig* x) {
     SGX_HIP(hipSetDevice(c->device));
-    const size_t need = sizeof(double) * (n_samples + 64);
-    if (c->cap_sig64 < need) {
-        if (c->d_sig64) hipFree(c->d_sig64);
-        c->d_sig64 = nullptr;
-        c->cap_sig64 = 0;
-        if (hipMalloc((void**)&c->d_sig64, need) != hipSuccess) {
-            sgx_set_error("hipMalloc of %zu signal bytes failed", need);
-            return SGX_E_NOMEM;
-        }
-        c->cap_sig64 = need;
-    }
+    const int rc = c->d_sig64.ensure(sizeof(double) * (n_samples + 64));
+    if (rc != SGX_OK) return rc;
     SGX_HIP(hipMemcpyAsync(c->d_sig64, signal, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
     SGX_HIP(hipStreamSynchronize(c->stream));   // the caller may free `signal` on return
     x->i8 = nullptr;
@@ -1521,24 +1498,9 @@ static int acq_look_decode(const AcqCall& a, const PeakOut& po, const double* se
     return SGX_OK;
 }
 
-// Waits for a result word in the pinned page (acq_publish_kernel's `seq`, the fine search's `seq2`, the gathered peaks'
-// word).  Spins (bounded), then falls back to the stream synchronisation, after which the page is complete in any case.
-static int coarse_look_wait(sgx_ctx* c, const unsigned long long* word, unsigned long long seq, bool spin) {
-    if (spin) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned it = 0;; ++it) {
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGX_OK;
-            if ((it & 1023u) == 1023u &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05)
-                break;
-        }
-    }
-    SGX_HIP(hipStreamSynchronize(c->stream));
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
-        sgx_set_error("acquisition: the search's result page was not written");
-        return SGX_E_HIP;
-    }
-    return SGX_OK;
+// Waits for a result word in the pinned page (acq_publish_kernel's `seq`, the fine search's `seq2`, the gathered peaks' word)
+static int acq_look_wait(sgx_ctx* c, const unsigned long long* word, unsigned long long seq, bool spin) {
+    return sgx_look_wait(c->stream, word, seq, spin, 0.05, 1024, "acquisition: the search's result page was not written", nullptr);
 }
 
 // The second queue of the correlation batches and its two events, created on first use
@@ -1589,9 +1551,9 @@ static int acq_corr_carve(sgx_ctx* c, AcqCorr* k, size_t pow_need) {
     const size_t rows = (size_t)k->rows_out_all;
     const size_t part_bytes = ((rows * (k->top2 ? (size_t)k->nres * 20 : (size_t)k->nblk * 12)) + 255) / 256 * 256;
     const size_t red_bytes = (part_bytes + rows * 12 + 1023) / 256 * 256;
-    const int rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, red_bytes + pow_need);
+    const int rc = c->d_pow.ensure(red_bytes + pow_need);
     if (rc != SGX_OK) return rc;
-    char* red = (char*)c->d_pow;
+    char* red = (char*)c->d_pow.get();
     k->pmax = (double*)red;
     k->parg = (int*)(red + rows * k->nblk * 8);
     k->t2b1 = (double*)red;
@@ -1611,9 +1573,9 @@ static int acq_corr_setup(sgx_ctx* c, AcqCorr* k, int n_prn, int n_bins, int n_p
     const size_t rows_fwd = (size_t)n_blocks * n_phi;
     if (work_rows < rows_fwd + n_prn) work_rows = rows_fwd + n_prn;
     int rc;
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_work[0].ensure(work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_work[1].ensure(work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_fwd.ensure((rows_fwd + n_prn) * row_bytes)) != SGX_OK) return rc;
     k->n_bins = n_bins;
     k->n_phi = n_phi;
     k->n_blocks = n_blocks;
@@ -1702,9 +1664,9 @@ static int acquire_fine(const AcqCall& a, const AcqDets& det, long long* d_sum, 
     rc = sgx_fft_plan_create(&c->plan_fine, npts);
     if (rc != SGX_OK) return rc;
     const int n_rows = (n_det + 1) / 2;   // two real signals per complex row
-    if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
+    if ((rc = c->d_fine[0].ensure((size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
         return rc;
-    if ((rc = ensure_buf((void**)&c->d_fine[1], &c->cap_f1, (size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
+    if ((rc = c->d_fine[1].ensure((size_t)n_rows * sizeof(cplx) * (size_t)npts)) != SGX_OK)
         return rc;
     const double tc1 = 1.0 / S.codeFreqBasis;
     const bool fine2 = sgx_fft_fine_supported(npts) && !a.env.fine_v1;
@@ -1809,8 +1771,8 @@ static int acq_fine_and_times(const AcqCall& a, const AcqDets& det, long long* d
 }
 // ... behind the host's look at the page the publish kernel wrote with `seq`, decoded into the detections
 static int acq_host_tail(const AcqCall& a, unsigned long long seq, long long* d_sum, const CohGrid* g) {
-    const CoarseLook* look = (const CoarseLook*)a.c->h_look;
-    int rc = coarse_look_wait(a.c, &look->seq, seq, a.env.spin);
+    const CoarseLook* look = &a.c->h_look->coarse;
+    int rc = acq_look_wait(a.c, &look->seq, seq, a.env.spin);
     if (rc != SGX_OK) return rc;
     AcqDets det;
     rc = acq_look_decode(a, look->po, look->second, 0, a.n_prn, &det);
@@ -1865,16 +1827,16 @@ static int acquire_passes(const AcqCall& a, int n_blocks, int noncoh, const CohG
     size_t work_rows = (size_t)prn_chunk * rows_per_prn;
     if (work_rows < (size_t)rows_fwd) work_rows = rows_fwd;
     if (work_rows < (size_t)n_prn) work_rows = n_prn;
-    if ((rc = ensure_buf((void**)&c->d_work[0], &c->cap_w0, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_work[1], &c->cap_w1, work_rows * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_fwd, &c->cap_fwd, (size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
-    if ((rc = ensure_buf((void**)&c->d_codefd, &c->cap_code, (size_t)n_prn * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_work[0].ensure(work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_work[1].ensure(work_rows * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_fwd.ensure((size_t)rows_fwd * row_bytes)) != SGX_OK) return rc;
+    if ((rc = c->d_codefd.ensure((size_t)n_prn * row_bytes)) != SGX_OK) return rc;
     // per-workgroup maxima of the fused last pass live in the (otherwise unused) power buffer: what the plan's last pass
     // writes for the rows of one batch, whatever the length (acq_rowmax_finish_kernel strides over any number of them)
     const int nblk_last = sgx_fft_last_pass_blocks(&c->plan_code);
     const size_t part_slots = work_rows * (size_t)nblk_last;
     const size_t pow_need = noncoh ? work_rows * sizeof(double) * (size_t)N : part_slots * 12 + 4096;
-    if ((rc = ensure_buf((void**)&c->d_pow, &c->cap_pow, pow_need)) != SGX_OK) return rc;
+    if ((rc = c->d_pow.ensure(pow_need)) != SGX_OK) return rc;
 
     SgxSmall* dsm = c->d_small;
     SgxSmall* hsm = c->h_small;
@@ -2135,12 +2097,12 @@ static int acquire_four_step(const AcqCall& a, int n_blocks, int noncoh, bool* h
         rc = sgx_fft_plan_create(&c->plan_fine, fg.npts);
         if (rc != SGX_OK) return rc;
         const int max_rows = (n_prn + 1) / 2;   // two real signals per complex row; only the detections' rows are touched
-        if ((rc = ensure_buf((void**)&c->d_fine[0], &c->cap_f0, (size_t)max_rows * sizeof(cplx) * (size_t)fg.npts)) != SGX_OK) return rc;
+        if ((rc = c->d_fine[0].ensure((size_t)max_rows * sizeof(cplx) * (size_t)fg.npts)) != SGX_OK) return rc;
     }
     // (device-led: into a device-side copy of the page - a kernel that writes host memory ends with a flush the next one
     // waits for, 5 us in front of the fine search)
     CoarseLook* const d_stage = &dsm->stage;
-    CoarseLook* const d_look = (CoarseLook*)c->d_look;
+    CoarseLook* const d_look = &c->d_look->coarse;
     // ---- device: row maxima, then per PRN block choice, global peak, exclusion list, second peak -----------------------
     if (k.top2) {
         PublishArgs pub;
@@ -2243,8 +2205,8 @@ int sgx_acquire_finish(sgx_ctx* c, const AcqOut& out) {
     env.spin = P.spin;
     const AcqCall a = acq_call(c, SgxSig{nullptr, nullptr}, P.n_samples, P.prn0, P.n_prn, out, env);
     acq_reset_outputs(a.out, a.n_prn);
-    const CoarseLook* look = (const CoarseLook*)c->h_look;
-    int rc = coarse_look_wait(c, &look->seq2, P.seq, P.spin);
+    const CoarseLook* look = &c->h_look->coarse;
+    int rc = acq_look_wait(c, &look->seq2, P.seq, P.spin);
     if (rc != SGX_OK) return rc;
     AcqDets det;
     rc = acq_look_decode(a, look->po, look->second, 0, a.n_prn, &det);
@@ -2340,7 +2302,7 @@ static int acquire_coherent_shift(const AcqCall& a, const CohGrid& g) {
     PublishArgs pub;
     memset(&pub, 0, sizeof(pub));   // (no stage: the publish kernel below writes the page)
     acq_queue_top2(a, k, spc, pub);
-    acq_queue_publish(a, (CoarseLook*)c->d_look, seq, acq_fine_geom(N).len, nullptr);
+    acq_queue_publish(a, &c->d_look->coarse, seq, acq_fine_geom(N).len, nullptr);
     hipEventRecord(c->ev[1], st);
     SGX_HIP(hipGetLastError());
     return acq_host_tail(a, seq, &dsm->sum, &g);
@@ -2379,10 +2341,9 @@ extern "C" int sgx_acquire_f64(sgx_ctx* c, const double* signal, size_t n_sample
 int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes, long long rec_file_offset, int sample_bytes) {
     const AcqPending& P = c->acq_pending;
     if (P.mode != 1 || n_ch < 1 || n_ch > 32) return SGX_E_DEFER;
-    StepLook* look = (StepLook*)((char*)c->d_look + SGX_STEP_LOOK_OFFSET);
-    acq_prerun_kernel<<<1, 64, 0, c->stream>>>(&c->d_small->stage, ((const CoarseLook*)c->d_look)->fine_bi, c->d_small->prn, P.n_prn,
+    acq_prerun_kernel<<<1, 64, 0, c->stream>>>(&c->d_small->stage, c->d_look->coarse.fine_bi, c->d_small->prn, P.n_prn,
                                                c->s.samplingFreq, (double)P.npts, d_ch, n_ch, skip_bytes, rec_file_offset,
-                                               sample_bytes, look);
+                                               sample_bytes, &c->d_look->step);
     SGX_HIP(hipGetLastError());
     return SGX_OK;
 }
@@ -2451,8 +2412,8 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
     // where the packed records go: the communicator's send buffer, or (no communicator: one rank, or a shard run alone)
     // the context's small device area
     SgxSmall* dsm = c->d_small;
-    PeakRec* d_send = comm ? (PeakRec*)comm->d_send : dsm->shard;
-    const PeakRec* d_all = comm ? (const PeakRec*)comm->d_recv : d_send;
+    PeakRec* d_send = comm ? (PeakRec*)comm->d_send.get() : dsm->shard;
+    const PeakRec* d_all = comm ? (const PeakRec*)comm->d_recv.get() : d_send;
     const int n_ranks_seen = comm ? world : 1;
     std::vector<PeakRec> host_pack;      // a search that could not be queued: packed on the host
     bool queued = false;
@@ -2473,7 +2434,7 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
     hipStream_t st = c->stream;
     if (queued) {
         const AcqPending& P = c->acq_pending;
-        acq_pack_kernel<<<1, 64, 0, st>>>(&dsm->stage, ((const CoarseLook*)c->d_look)->fine_bi, dsm->prn, P.n_prn, c->s.samplingFreq, (double)P.npts, d_send, slots);
+        acq_pack_kernel<<<1, 64, 0, st>>>(&dsm->stage, c->d_look->coarse.fine_bi, dsm->prn, P.n_prn, c->s.samplingFreq, (double)P.npts, d_send, slots);
     } else {
         if (host_pack.empty()) {
             host_pack.resize((size_t)slots);
@@ -2485,28 +2446,26 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
         const int rg = sgx_comm_allgather_device(comm, rec_bytes);
         if (rg != SGX_OK) return rg;
     }
-    const size_t all_bytes = rec_bytes * (size_t)n_ranks_seen;
-    if (all_bytes > SGX_TRK_LOOK_OFFSET - SGX_GATHER_LOOK_OFFSET - 16) {
+    const int n_rec = slots * n_ranks_seen;
+    if ((size_t)n_rec > sizeof(GatherLook::rec) / sizeof(PeakRec)) {
         sgx_set_error("sgx_acquire_sharded: %d ranks x %d slots do not fit the result page", world, slots);
         return SGX_E_ARG;
     }
     const unsigned long long seq = ++c->look_seq;
-    char* page_d = (char*)c->d_look + SGX_GATHER_LOOK_OFFSET;
-    const char* page_h = (const char*)c->h_look + SGX_GATHER_LOOK_OFFSET;
-    acq_gather_publish_kernel<<<1, 256, 0, st>>>((const int*)d_all, (int)(all_bytes / 4), (int*)(page_d + 16),
-                                                 (unsigned long long*)page_d, seq);
+    GatherLook* const d_gather = &c->d_look->gather;
+    const GatherLook* gather = &c->h_look->gather;
+    acq_gather_publish_kernel<<<1, 256, 0, st>>>((const int*)d_all, (int)(sizeof(PeakRec) * (size_t)n_rec / 4), (int*)d_gather->rec,
+                                                 &d_gather->seq, seq);
     SGX_HIP(hipGetLastError());
-    const int rl = coarse_look_wait(c, (const unsigned long long*)page_h, seq, env.spin);   // the one look
+    const int rl = acq_look_wait(c, &gather->seq, seq, env.spin);   // the one look
     if (rl != SGX_OK) return rl;
     if (queued) {   // (device time of this rank's search; the search's own page is complete: the gather came behind it)
         c->acq_pending.mode = 0;
         SGX_HIP(hipEventSynchronize(c->ev[2]));
         acq_event_times(c, false);
     }
-    const PeakRec* all = (const PeakRec*)(page_h + 16);
-    const int n_rec = slots * n_ranks_seen;
     for (int i = 0; i < n_rec; ++i) {
-        const PeakRec& q = all[i];
+        const PeakRec& q = gather->rec[i];
         if (q.valid == 0) continue;
         if (q.valid == -1) return acq_index_error(c->n_code, q.prn0, (int)q.codePhase);
         if (q.valid == -2) return acq_fine_range_error((long long)q.codePhase + acq_fine_geom(c->n_code).len, n_samples);

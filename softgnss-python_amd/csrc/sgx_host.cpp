@@ -157,9 +157,9 @@ static int ctx_build(sgx_ctx* c, int priority) {
     SGX_HIP(hipMemcpy(c->d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
     SGX_HIP(hipMalloc((void**)&c->d_small, SGX_SMALL_BYTES));
     SGX_HIP(hipHostMalloc((void**)&c->h_small, SGX_SMALL_BYTES, hipHostMallocDefault));
-    SGX_HIP(hipHostMalloc(&c->h_look, SGX_LOOK_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
-    memset(c->h_look, 0, SGX_LOOK_BYTES);
-    SGX_HIP(hipHostGetDevicePointer(&c->d_look, c->h_look, 0));
+    SGX_HIP(hipHostMalloc((void**)&c->h_look, sizeof(LookPage), hipHostMallocCoherent | hipHostMallocMapped));
+    memset(c->h_look, 0, sizeof(LookPage));
+    SGX_HIP(hipHostGetDevicePointer((void**)&c->d_look, c->h_look, 0));
     return SGX_OK;
 }
 
@@ -175,54 +175,74 @@ extern "C" int sgx_ctx_create_prio(const sgx_settings* s, int device, int priori
     c->priority = priority;
     const int rc = ctx_build(c, priority);
     if (rc != SGX_OK) {
-        // a partially built context: release what exists (the message of the failing call is kept)
-        if (c->stream) hipStreamDestroy(c->stream);
-        for (int i = 0; i < 6; ++i)
-            if (c->ev[i]) hipEventDestroy(c->ev[i]);
-        if (c->d_codes) hipFree(c->d_codes);
-        if (c->d_small) hipFree(c->d_small);
-        if (c->h_small) hipHostFree(c->h_small);
-        if (c->h_look) hipHostFree(c->h_look);
-        delete c;
+        delete c;   // (a partially built context; the message of the failing call is kept)
         return rc;
     }
     *out = c;
     return SGX_OK;
 }
 
+// Device and pinned memory first, events and streams last
+sgx_ctx::~sgx_ctx() {
+    sgx_fft_plan_destroy(&plan_code);
+    sgx_fft_plan_destroy(&plan_fine);
+    sgx_fft_plan_destroy(&plan_probe);
+    for (int i = 0; i < 2; ++i)
+        if (stage[i]) hipHostFree(stage[i]);
+    if (d_codes) hipFree(d_codes);
+    d_sig64.release();
+    d_fwd.release();
+    d_codefd.release();
+    d_work[0].release();
+    d_work[1].release();
+    d_pow.release();
+    d_fine[0].release();
+    d_fine[1].release();
+    if (d_small) hipFree(d_small);
+    d_trk_out.release();
+    d_trk_aux.release();
+    if (spare_d) hipFree(spare_d);
+    if (spare_mark) hipFree(spare_mark);
+    if (spare_copy_stream) hipStreamDestroy(spare_copy_stream);
+    if (acq_stream2) hipStreamDestroy(acq_stream2);
+    for (int i = 0; i < 2; ++i)
+        if (acq_ev2[i]) hipEventDestroy(acq_ev2[i]);
+    if (h_small) hipHostFree(h_small);
+    if (h_look) hipHostFree(h_look);
+    for (int i = 0; i < 6; ++i)
+        if (ev[i]) hipEventDestroy(ev[i]);
+    if (stream) hipStreamDestroy(stream);
+}
+
 extern "C" int sgx_ctx_destroy(sgx_ctx* c) {
     if (!c) return SGX_OK;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    sgx_fft_plan_destroy(&c->plan_code);
-    sgx_fft_plan_destroy(&c->plan_fine);
-    sgx_fft_plan_destroy(&c->plan_probe);
-    for (int i = 0; i < 2; ++i)
-        if (c->stage[i]) hipHostFree(c->stage[i]);
-    hipFree(c->d_codes);
-    if (c->d_sig64) hipFree(c->d_sig64);
-    hipFree(c->d_fwd);
-    hipFree(c->d_codefd);
-    hipFree(c->d_work[0]);
-    hipFree(c->d_work[1]);
-    hipFree(c->d_pow);
-    hipFree(c->d_fine[0]);
-    hipFree(c->d_fine[1]);
-    hipFree(c->d_small);
-    hipFree(c->d_trk_out);
-    hipFree(c->d_trk_aux);
-    if (c->spare_d) hipFree(c->spare_d);
-    if (c->spare_mark) hipFree(c->spare_mark);
-    if (c->spare_copy_stream) hipStreamDestroy(c->spare_copy_stream);
-    if (c->acq_stream2) hipStreamDestroy(c->acq_stream2);
-    for (int i = 0; i < 2; ++i)
-        if (c->acq_ev2[i]) hipEventDestroy(c->acq_ev2[i]);
-    if (c->h_small) hipHostFree(c->h_small);
-    if (c->h_look) hipHostFree(c->h_look);
-    for (int i = 0; i < 6; ++i)
-        if (c->ev[i]) hipEventDestroy(c->ev[i]);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
+    return SGX_OK;
+}
+
+int sgx_look_wait(hipStream_t st, const unsigned long long* word, unsigned long long seq, bool spin, double budget_s,
+                  unsigned stride, const char* unwritten, hipError_t* sync_err) {
+    if (spin) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned it = 0;; ++it) {
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGX_OK;
+            if ((it & (stride - 1)) == stride - 1 &&
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > budget_s)
+                break;
+        }
+    }
+    if (sync_err) {
+        *sync_err = hipStreamSynchronize(st);
+        if (*sync_err != hipSuccess) return SGX_OK;
+    } else {
+        SGX_HIP(hipStreamSynchronize(st));
+    }
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
+        sgx_set_error("%s", unwritten);
+        return SGX_E_HIP;
+    }
     return SGX_OK;
 }
 
@@ -915,8 +935,12 @@ extern "C" int sgx_comm_create(sgx_ctx* c, int32_t n_ranks, int32_t rank, const 
     m->n_ranks = n_ranks;
     m->rank = rank;
     m->cap = 1 << 16;
-    SGX_HIP(hipMalloc(&m->d_send, m->cap));
-    SGX_HIP(hipMalloc(&m->d_recv, m->cap * (size_t)n_ranks));
+    rc = m->d_send.ensure(m->cap);
+    if (rc == SGX_OK) rc = m->d_recv.ensure(m->cap * (size_t)n_ranks);
+    if (rc != SGX_OK) {
+        sgx_comm_destroy(m);
+        return rc;
+    }
     *out = m;
     return SGX_OK;
 }
@@ -950,8 +974,6 @@ extern "C" int sgx_comm_destroy(sgx_comm* m) {
     hipSetDevice(m->ctx->device);
     hipStreamSynchronize(m->ctx->stream);
     if (m->comm && g_rccl.destroy) g_rccl.destroy(m->comm);
-    hipFree(m->d_send);
-    hipFree(m->d_recv);
     delete m;
     return SGX_OK;
 }

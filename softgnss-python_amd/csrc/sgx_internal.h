@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libsgx.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -35,6 +36,39 @@ void sgx_set_error(const char* fmt, ...);
     } while (0)
 
 typedef double2 cplx;   // complex128 as (re, im)
+
+// A device allocation and its size: the context's grow-only scratch as members, a call's temporaries as locals.  Frees
+// itself; not copyable.  Reads as the pointer it holds.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    // Room for `bytes`: the allocation is kept where it is large enough, else freed and made anew (the contents are lost).
+    // On failure the buffer is empty.
+    int ensure(size_t bytes) {
+        if (p && cap >= bytes) return SGX_OK;
+        release();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            sgx_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+            return SGX_E_NOMEM;
+        }
+        cap = bytes;
+        return SGX_OK;
+    }
+    void release() {
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+};
 
 // The samples an acquisition reads: the int8 record (Settings.dataType 'int8'), or - acquire() handed any other real
 // array (acquisition.py:55-59 works on whatever numpy dtype it gets) - an fp64 copy of it.
@@ -141,7 +175,6 @@ struct CoarseLook {
     long long fine_bi[32];    // arg-max of the 2^22-point magnitude spectrum over [4, uniq - 5)
     unsigned long long seq2;
 };
-static_assert(sizeof(CoarseLook) <= 4096, "one pinned page");
 
 // The detection list in device memory: the coarse search's publish step (sgx_acq.hip) writes it, the device-led fine
 // kernels (sgx_fft.hip) read it, so that they are queued right behind the coarse ones without the host looking in between
@@ -237,7 +270,7 @@ struct AcqPending {
     AcqResults res;
 };
 
-// What the device-side preRun + a chained tracking launch leave in the upper half of the result page (offset 2048)
+// What the device-side preRun + a chained tracking launch leave in the result page
 struct StepLook {
     int n_ch, n_active;         // channels of the table, channels that are on (acquisition.py:289)
     int flags;                  // 1 a NaN among the metrics (the host sorts); 2 IndexError / range error of the search (no
@@ -246,16 +279,33 @@ struct StepLook {
     int prn[32];
     double acquiredFreq[32], codePhase[32];
 };
-static_assert(sizeof(StepLook) <= 2048, "upper half of the result page");
-#define SGX_STEP_LOOK_OFFSET 2048
-// the result "page" is two pages: [0, 2048) the search's CoarseLook, [2048, 4096) StepLook, [4096, 8192) the gathered peak
-// records of sgx_acquire_sharded behind the word the host spins on
-#define SGX_GATHER_LOOK_OFFSET 4096
-// ... and [6144, 8192): what a tracking launch leaves for the host's look (sgx_trk.hip: trk_finish_kernel) - the word, the
-// two error words, ms_done of up to SGX_TRK_LOOK_CH channels
-#define SGX_TRK_LOOK_OFFSET 6144
+// The gathered peak records of sgx_acquire_sharded behind the word the host spins on: as many as the part has room for
+struct GatherLook {
+    unsigned long long seq;
+    unsigned long long pad;
+    PeakRec rec[(2048 - 16) / sizeof(PeakRec)];
+};
+// What a tracking launch leaves for the host's look (sgx_trk.hip: trk_finish_kernel, round 6): the word the host spins on,
+// the two error words and ms_done of up to SGX_TRK_LOOK_CH channels, copied here by ONE small kernel behind the tracking
+// kernel - instead of two copies to pageable memory with a stream synchronisation each (~80 us behind every launch)
 #define SGX_TRK_LOOK_CH 256
-#define SGX_LOOK_BYTES 8192
+struct TrkLook {
+    unsigned long long seq;
+    int err[2];
+    int done[SGX_TRK_LOOK_CH];
+};
+// The result "page" (two pages of coherent pinned memory): every part a kernel publishes to and the host looks at, each
+// at a fixed offset that no neighbour can grow into
+struct LookPage {
+    alignas(2048) CoarseLook coarse;
+    alignas(2048) StepLook step;
+    alignas(2048) GatherLook gather;
+    alignas(2048) TrkLook trk;
+};
+static_assert(offsetof(LookPage, coarse) == 0 && offsetof(LookPage, step) == 2048 && offsetof(LookPage, gather) == 4096 &&
+                  offsetof(LookPage, trk) == 6144 && sizeof(LookPage) == 8192,
+              "every part of the result page where it has always been");
+static_assert(offsetof(GatherLook, rec) == 16, "the gathered records start 16 bytes behind their word");
 
 struct sgx_ctx {
     sgx_settings s;
@@ -273,26 +323,23 @@ struct sgx_ctx {
     FftPlan plan_code;           // length samplesPerCode
     FftPlan plan_fine;           // length 8 * 2^ceil(log2(10 N))
     FftPlan plan_probe;          // length 16384 (Welch segments of sgx_probe_stats)
-    cplx* d_fwd = nullptr;       // [n_blocks][n_bins][N] mixed-signal spectra
-    cplx* d_codefd = nullptr;    // [32][N] code spectra
-    cplx* d_work[2] = {nullptr, nullptr};   // ping-pong [rows][N]
-    double* d_pow = nullptr;     // [rows][N] correlation power
-    cplx* d_fine[2] = {nullptr, nullptr};
-    double* d_sig64 = nullptr;   // fp64 copy of a non-int8 signal handed to sgx_acquire_f64
-    size_t cap_sig64 = 0;
-    size_t cap_fwd = 0, cap_code = 0, cap_w0 = 0, cap_w1 = 0, cap_pow = 0, cap_f0 = 0, cap_f1 = 0;   // bytes
+    DevBuf<cplx> d_fwd;          // [n_blocks][n_bins][N] mixed-signal spectra
+    DevBuf<cplx> d_codefd;       // [32][N] code spectra
+    DevBuf<cplx> d_work[2];      // ping-pong [rows][N]
+    DevBuf<double> d_pow;        // [rows][N] correlation power
+    DevBuf<cplx> d_fine[2];
+    DevBuf<double> d_sig64;      // fp64 copy of a non-int8 signal handed to sgx_acquire_f64
     SgxSmall* d_small = nullptr; // small device area
     int acq_sum_phase = 0;       // acq_front_kernel: which of the two record-sum slots this call adds into ...
     bool acq_sum_clean[2] = {false, false};   // ... and whether a slot is known to hold zero (the other call's set-up zeroed it)
     SgxSmall* h_small = nullptr; // pinned mirror
-    void* h_look = nullptr;      // coherent pinned page a kernel publishes the coarse search's outcome to (host spins on it)
-    void* d_look = nullptr;      // its device address
+    LookPage* h_look = nullptr;  // coherent pinned page the kernels publish their outcomes to (the host spins on its words)
+    LookPage* d_look = nullptr;  // its device address
     unsigned long long look_seq = 0;
     unsigned long long trk_seq = 0;
     // tracking
-    double* d_trk_out = nullptr;
-    size_t trk_out_elems = 0;
-    void* d_trk_aux = nullptr;   // per-call device state of sgx_track (channels, done, exchange, err, profile)
+    DevBuf<double> d_trk_out;    // the series of a call whose result buffer is pageable
+    DevBuf<char> d_trk_aux;      // per-call device state of sgx_track (channels, done, exchange, err, profile)
     // One record allocation, streaming watermark and copy stream kept from the last sgx_if_free: a caller that opens a
     // record file per step (the reference's, initialize.py:466-506) would otherwise pay hipMalloc + hipFree of 1.4 GB and
     // a stream creation every time (milliseconds against a 50 ms step).
@@ -301,7 +348,6 @@ struct sgx_ctx {
     unsigned long long* spare_mark = nullptr;
     hipStream_t spare_copy_stream = nullptr;
     std::mutex spare_mu;
-    size_t trk_aux_cap = 0;
     // pinned staging buffers of the file streamer, kept between calls (pinning 64 MiB costs ~15 ms)
     void* stage[2] = {nullptr, nullptr};
     std::atomic<bool> stage_busy{false};
@@ -311,9 +357,17 @@ struct sgx_ctx {
     float iq_kernel_ms = 0.0f;       // HIP-event time of the last sgx_if_from_iq's kernel (sgx_iq.hip)
     // HIP-event times of the last sgx_requant_stats_of's and the last sgx_if_requantize's kernel (sgx_requant.hip)
     float requant_stats_ms = 0.0f, requant_kernel_ms = 0.0f;
+    // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
+    ~sgx_ctx();
 };
 
 // sgx_host.cpp
+// The host's wait for a word of the result page: spins on it (where `spin`; the clock is read every `stride` looks) for
+// up to budget_s seconds, then sleeps in the stream synchronisation, after which the page is complete in any case, and
+// looks once more; `unwritten` is the error text if the word still differs from seq.  A synchronisation that fails is an
+// error here where sync_err is null; else it is handed back in *sync_err for the caller to report, with SGX_OK.
+int sgx_look_wait(hipStream_t st, const unsigned long long* word, unsigned long long seq, bool spin, double budget_s,
+                  unsigned stride, const char* unwritten, hipError_t* sync_err);
 // Compute units claimed by this process's cooperative tracking launches (all contexts of a device): `want` CUs are
 // granted (returned) only if they fit next to what is already running, else 0.
 int sgx_cu_reserve(int device, int cus_total, int want);
@@ -429,8 +483,8 @@ struct sgx_comm {
     sgx_ctx* ctx;
     void* comm;
     int n_ranks, rank;
-    void* d_send;
-    void* d_recv;
+    DevBuf<char> d_send;   // cap bytes
+    DevBuf<char> d_recv;   // cap bytes per rank
     size_t cap;
 };
 int sgx_comm_allgather_device(sgx_comm* m, size_t bytes);

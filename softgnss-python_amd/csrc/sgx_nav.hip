@@ -47,17 +47,13 @@ extern "C" int sgx_find_preambles(sgx_ctx* c, const double* I_P, int32_t n_ch, i
     SGX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t n = (size_t)n_ch * (size_t)ms;
-    double* d_ip = nullptr;
-    short* d_c = nullptr;
-    SGX_HIP(hipMalloc((void**)&d_ip, n * sizeof(double)));
-    hipError_t e = hipMalloc((void**)&d_c, n * sizeof(short));
-    if (e != hipSuccess) {
-        hipFree(d_ip);
-        sgx_set_error("hipMalloc failed in sgx_find_preambles");
-        return SGX_E_NOMEM;
-    }
+    DevBuf<double> d_ip;
+    DevBuf<short> d_c;
+    int rc = d_ip.ensure(n * sizeof(double));
+    if (rc == SGX_OK) rc = d_c.ensure(n * sizeof(short));
+    if (rc != SGX_OK) return rc;
     std::vector<short> corr(n);
-    e = hipMemcpyAsync(d_ip, I_P, n * sizeof(double), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(d_ip, I_P, n * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         dim3 grid((unsigned)((ms - search_start + 255) / 256), (unsigned)n_ch);
         nav_corr_kernel<<<grid, 256, 0, st>>>(d_ip, d_c, ms, search_start);
@@ -65,8 +61,6 @@ extern "C" int sgx_find_preambles(sgx_ctx* c, const double* I_P, int32_t n_ch, i
     }
     if (e == hipSuccess) e = hipMemcpyAsync(corr.data(), d_c, n * sizeof(short), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    hipFree(d_ip);
-    hipFree(d_c);
     if (e != hipSuccess) {
         sgx_set_error("preamble correlation failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;

@@ -93,11 +93,12 @@ extern "C" int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, siz
     if (rc != SGX_OK) return rc;
 
     const size_t row_bytes = sizeof(cplx) * (size_t)PROBE_NSEG;
-    char* d_all = nullptr;
     const size_t bytes = 2 * (size_t)n_seg * row_bytes + sizeof(double) * (size_t)PROBE_NSEG +
                          sizeof(double) * (size_t)PROBE_BINS + 256 * sizeof(unsigned long long);
-    SGX_HIP(hipMalloc((void**)&d_all, bytes));
-    cplx* d_a = (cplx*)d_all;
+    DevBuf<char> d_all;
+    rc = d_all.ensure(bytes);
+    if (rc != SGX_OK) return rc;
+    cplx* d_a = (cplx*)d_all.get();
     cplx* d_b = d_a + (size_t)n_seg * PROBE_NSEG;
     double* d_win = (double*)(d_b + (size_t)n_seg * PROBE_NSEG);
     double* d_pxx = d_win + PROBE_NSEG;
@@ -112,7 +113,6 @@ extern "C" int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, siz
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-        hipFree(d_all);
         sgx_set_error("probe histogram failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;
     }
@@ -125,16 +125,12 @@ extern "C" int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, siz
     probe_segment_kernel<<<n_seg, 256, 0, st>>>(x, d_a, d_win, mean, step);
     cplx* res = nullptr;
     rc = sgx_fft_forward(&c->plan_probe, d_a, d_b, n_seg, st, &res, PROBE_NSEG);
-    if (rc != SGX_OK) {
-        hipFree(d_all);
-        return rc;
-    }
+    if (rc != SGX_OK) return rc;
     probe_psd_kernel<<<(PROBE_BINS + 255) / 256, 256, 0, st>>>(res, d_pxx, n_seg, scale);
     hipEventRecord(c->ev[1], st);
     e = hipMemcpyAsync(pxx, d_pxx, sizeof(double) * (size_t)PROBE_BINS, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipGetLastError();
-    hipFree(d_all);
     if (e != hipSuccess) {
         sgx_set_error("probe spectrum failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;

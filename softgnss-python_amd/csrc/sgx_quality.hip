@@ -179,12 +179,10 @@ extern "C" int sgx_track_quality(sgx_ctx* c, const double* I_P, const double* Q_
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_in = up(n_in * sizeof(double)), b_out = up(n_out * sizeof(double));
     const size_t b_pass = up(n_out), b_ch = up((size_t)n_ch * sizeof(int32_t));
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, 2 * b_in + 2 * b_out + b_pass + 2 * b_ch) != hipSuccess) {
-        sgx_set_error("hipMalloc failed in sgx_track_quality (%zu bytes)", 2 * b_in + 2 * b_out + b_pass + 2 * b_ch);
-        return SGX_E_NOMEM;
-    }
-    double* d_i = (double*)d;
+    DevBuf<char> d;
+    const int rc = d.ensure(2 * b_in + 2 * b_out + b_pass + 2 * b_ch);
+    if (rc != SGX_OK) return rc;
+    double* d_i = (double*)d.get();
     double* d_q = (double*)(d + b_in);
     double* d_cno = (double*)(d + 2 * b_in);
     double* d_carr = (double*)(d + 2 * b_in + b_out);
@@ -209,7 +207,6 @@ extern "C" int sgx_track_quality(sgx_ctx* c, const double* I_P, const double* Q_
     if (e == hipSuccess) e = hipMemcpyAsync(pass, d_pass, n_out, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(lost, d_lost, (size_t)n_ch * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    hipFree(d);
     if (e != hipSuccess) {
         sgx_set_error("sgx_track_quality failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;

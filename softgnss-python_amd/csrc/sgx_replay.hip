@@ -163,12 +163,10 @@ extern "C" int sgx_track_replay(sgx_ctx* c, const sgx_if* r, int64_t rec_file_of
     const size_t b_state = up(n_blocks * sizeof(sgx_replay_block)), b_meta = up(meta.size() * sizeof(int));
     const size_t b_taps = up((size_t)n_taps * sizeof(double));
     const size_t n_out = n_blocks * (size_t)n_taps * 2;
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, b_state + b_meta + b_taps + n_out * sizeof(double)) != hipSuccess) {
-        sgx_set_error("hipMalloc failed in sgx_track_replay (%zu bytes)", b_state + b_meta + b_taps + n_out * sizeof(double));
-        return SGX_E_NOMEM;
-    }
-    sgx_replay_block* d_state = (sgx_replay_block*)d;
+    DevBuf<char> d;
+    const int rd = d.ensure(b_state + b_meta + b_taps + n_out * sizeof(double));
+    if (rd != SGX_OK) return rd;
+    sgx_replay_block* d_state = (sgx_replay_block*)d.get();
     int* d_meta = (int*)(d + b_state);
     double* d_taps = (double*)(d + b_state + b_meta);
     double* d_out = (double*)(d + b_state + b_meta + b_taps);
@@ -206,7 +204,6 @@ extern "C" int sgx_track_replay(sgx_ctx* c, const sgx_if* r, int64_t rec_file_of
     }
     for (int i = 0; i < 4; ++i)
         if (ev[i]) (void)hipEventDestroy(ev[i]);
-    (void)hipFree(d);
     if (e != hipSuccess) {
         sgx_set_error("sgx_track_replay failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;

@@ -130,21 +130,18 @@ extern "C" int sgx_stream_rates(sgx_ctx* c, size_t bytes, int reps, double* read
     SGX_CHECK_ARG(c && read_gbs && copy_gbs && bytes >= (1u << 20) && reps >= 1);
     SGX_HIP(hipSetDevice(c->device));
     const size_t n16 = bytes / 16;
-    uint4 *a = nullptr, *b = nullptr;
-    SGX_HIP(hipMalloc((void**)&a, n16 * 16));
-    if (hipMalloc((void**)&b, n16 * 16) != hipSuccess) {
-        hipFree(a);
-        sgx_set_error("hipMalloc of %zu bytes failed in sgx_stream_rates", n16 * 16);
-        return SGX_E_NOMEM;
-    }
+    DevBuf<uint4> a, b;
+    int rc = a.ensure(n16 * 16);
+    if (rc == SGX_OK) rc = b.ensure(n16 * 16);
+    if (rc != SGX_OK) return rc;
     hipStream_t st = c->stream;
     hipMemsetAsync(a, 0x5A, n16 * 16, st);
     hipMemsetAsync(b, 0, n16 * 16, st);
     const int blocks = 256 * 16;
     float ms_r = 0.f, ms_c = 0.f;
-    stream_read_kernel<<<blocks, 256, 0, st>>>(a, n16, (unsigned*)b);
+    stream_read_kernel<<<blocks, 256, 0, st>>>(a, n16, (unsigned*)b.get());
     hipEventRecord(c->ev[0], st);
-    for (int i = 0; i < reps; ++i) stream_read_kernel<<<blocks, 256, 0, st>>>(a, n16, (unsigned*)b);
+    for (int i = 0; i < reps; ++i) stream_read_kernel<<<blocks, 256, 0, st>>>(a, n16, (unsigned*)b.get());
     hipEventRecord(c->ev[1], st);
     stream_copy_kernel<<<blocks, 256, 0, st>>>(a, b, n16);
     hipEventRecord(c->ev[2], st);
@@ -156,8 +153,6 @@ extern "C" int sgx_stream_rates(sgx_ctx* c, size_t bytes, int reps, double* read
         hipEventElapsedTime(&ms_r, c->ev[0], c->ev[1]);
         hipEventElapsedTime(&ms_c, c->ev[2], c->ev[3]);
     }
-    hipFree(a);
-    hipFree(b);
     if (e != hipSuccess) {
         sgx_set_error("stream rate kernels failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;

@@ -21,15 +21,7 @@ __global__ __launch_bounds__(256) void trk_fill_kernel(double* __restrict__ out,
     out[i] = zero ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
 }
 
-// What a tracking launch leaves for the host (round 6): the error words and every channel's ms_done, copied to the pinned
-// result page by ONE small kernel behind the tracking kernel, then the word the host spins on - instead of two copies to
-// pageable memory with a stream synchronisation each (~80 us behind every launch).
-struct TrkLook {
-    unsigned long long seq;
-    int err[2];
-    int done[SGX_TRK_LOOK_CH];
-};
-static_assert(sizeof(TrkLook) <= SGX_LOOK_BYTES - SGX_TRK_LOOK_OFFSET, "the tracking look fits its part of the page");
+// What a tracking launch leaves for the host: the result page's TrkLook (sgx_internal.h), then the word the host spins on
 __global__ __launch_bounds__(SGX_TRK_LOOK_CH) void trk_finish_kernel(const int* __restrict__ d_err, const int* __restrict__ d_done,
                                                                      int n_ch, TrkLook* __restrict__ look, unsigned long long seq) {
     const int t = threadIdx.x;
@@ -349,16 +341,8 @@ static int trk_buffers(TrkCall& T) {
         T.d_out = (double*)pa.devicePointer;
     } else {
         (void)hipGetLastError();   // a pageable pointer is not an error
-        if (c->trk_out_elems < T.elems) {
-            if (c->d_trk_out) hipFree(c->d_trk_out);
-            c->d_trk_out = nullptr;
-            c->trk_out_elems = 0;
-            if (hipMalloc((void**)&c->d_trk_out, T.elems * sizeof(double)) != hipSuccess) {
-                sgx_set_error("hipMalloc of %zu tracking output bytes failed", T.elems * sizeof(double));
-                return SGX_E_NOMEM;
-            }
-            c->trk_out_elems = T.elems;
-        }
+        const int rc = c->d_trk_out.ensure(T.elems * sizeof(double));
+        if (rc != SGX_OK) return rc;
         T.d_out = c->d_trk_out;
     }
     const size_t sz_ch = ((sizeof(TrkChan) * (size_t)T.n_ch + 255) / 256) * 256;
@@ -368,18 +352,9 @@ static int trk_buffers(TrkCall& T) {
     const size_t sz_xch = ((xch_bytes + 255) / 256) * 256;
     T.sz_clear = sz_done + sz_xch + 256;
     T.sz_prof = sizeof(long long) * T2_PROF_STRIDE * (size_t)T.n_ch;
-    const size_t need = sz_ch + T.sz_clear + T.sz_prof;
-    if (c->trk_aux_cap < need) {
-        if (c->d_trk_aux) hipFree(c->d_trk_aux);
-        c->d_trk_aux = nullptr;
-        c->trk_aux_cap = 0;
-        if (hipMalloc(&c->d_trk_aux, need) != hipSuccess) {
-            sgx_set_error("hipMalloc of %zu tracking state bytes failed", need);
-            return SGX_E_NOMEM;
-        }
-        c->trk_aux_cap = need;
-    }
-    char* aux = (char*)c->d_trk_aux;
+    const int rc = c->d_trk_aux.ensure(sz_ch + T.sz_clear + T.sz_prof);
+    if (rc != SGX_OK) return rc;
+    char* aux = c->d_trk_aux;
     T.d_ch = (TrkChan*)aux;
     T.d_done = (int*)(aux + sz_ch);
     T.d_xch = (unsigned long long*)(aux + sz_ch + sz_done);
@@ -404,26 +379,14 @@ static int trk_collect(TrkCall& T, int words[2]) {
     }
     const unsigned long long seq = ++c->trk_seq;
     if (e == hipSuccess) {
-        trk_finish_kernel<<<1, SGX_TRK_LOOK_CH, 0, st>>>(T.d_err, T.d_done, T.n_ch, (TrkLook*)((char*)c->d_look + SGX_TRK_LOOK_OFFSET), seq);
+        trk_finish_kernel<<<1, SGX_TRK_LOOK_CH, 0, st>>>(T.d_err, T.d_done, T.n_ch, &c->d_look->trk, seq);
         e = hipGetLastError();
     }
     T.stamp("finish kernel queued");
     if (e == hipSuccess) {
-        const TrkLook* look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (unsigned sp = 0; !seen; ++sp) {
-            if (__atomic_load_n(&look->seq, __ATOMIC_ACQUIRE) == seq) seen = true;
-            else if ((sp & 4095u) == 4095u &&
-                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.25) break;
-        }
-        if (!seen) {
-            e = hipStreamSynchronize(st);
-            if (e == hipSuccess && __atomic_load_n(&look->seq, __ATOMIC_ACQUIRE) != seq) {
-                sgx_set_error("tracking: the launch's result words were not written");
-                return SGX_E_HIP;
-            }
-        }
+        const TrkLook* look = &c->h_look->trk;
+        const int rc = sgx_look_wait(st, &look->seq, seq, true, 0.25, 4096, "tracking: the launch's result words were not written", &e);
+        if (rc != SGX_OK) return rc;
         words[0] = look->err[0];
         words[1] = look->err[1];
     }
@@ -571,8 +534,7 @@ static int trk_finish(TrkCall& T) {
     const int n_ch = T.n_ch, ms = T.ms;
     hipError_t e = T.e;
     if (T.fast_look && e == hipSuccess) {
-        const TrkLook* look = (const TrkLook*)((const char*)c->h_look + SGX_TRK_LOOK_OFFSET);
-        for (int i = 0; i < n_ch; ++i) T.ms_done[i] = look->done[i];
+        for (int i = 0; i < n_ch; ++i) T.ms_done[i] = c->h_look->trk.done[i];
         e = hipEventSynchronize(c->ev[4]);   // (the word is stored a moment before the kernels retire: the times need the event)
     } else {
         if (e == hipSuccess && !T.direct) e = hipMemcpyAsync(T.out, T.d_out, T.elems * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -602,7 +564,7 @@ static int trk_finish(TrkCall& T) {
     }
     if (T.direct) {
         // entries never reached keep the reference's initial values (tracking.py:65-94): zeros or +Inf
-        const StepLook* slook = (const StepLook*)((const char*)c->h_look + SGX_STEP_LOOK_OFFSET);   // (chained: preRun's table)
+        const StepLook* slook = &c->h_look->step;   // (chained: preRun's table)
         for (int i = 0; i < n_ch; ++i) {
             if (T.chained && slook->prn[i] == 0) continue;      // (a channel that is off: the caller gets the first n_active rows)
             const int dn = T.chained ? T.ms_done[i] : ((T.ch[i].prn == 0) ? 0 : T.ms_done[i]);
@@ -706,7 +668,7 @@ extern "C" int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_o
                                    (long long)c->s.skipNumberOfBytes, 0.0, true);
     if (rc != SGX_OK) return rc;
     // (the stream has been synchronised: the page is complete)
-    const StepLook* look = (const StepLook*)((const char*)c->h_look + SGX_STEP_LOOK_OFFSET);
+    const StepLook* look = &c->h_look->step;
     if (look->n_ch != n_ch || look->flags != 0) return SGX_E_DEFER;   // a NaN metric, a failed search, a channel in front of
                                                                        // the record: nothing was tracked, the eager calls report it
     *n_active = look->n_active;

@@ -112,8 +112,9 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
         if (rq != SGX_OK) return rq;
     }
     SGX_HIP(hipSetDevice(c->device));
-    unsigned* d_st = nullptr;
-    SGX_HIP(hipMalloc((void**)&d_st, 4 * sizeof(unsigned) + sizeof(double)));   // [3 words | pad | sum of |x|]
+    DevBuf<unsigned> d_st;   // [3 words | pad | sum of |x|]
+    int rc = d_st.ensure(4 * sizeof(unsigned) + sizeof(double));
+    if (rc != SGX_OK) return rc;
     const unsigned h_init[6] = {0u, 0x7FFFFFFFu, 0u, 0u, 0u, 0u};
     unsigned h_st[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     const float* x = reinterpret_cast<const float*>(r->d + first);
@@ -124,7 +125,6 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
         e = hipMemcpyAsync(h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_st);
     if (e != hipSuccess) {
         sgx_set_error("float32 record scan: %s", hipGetErrorString(e));
         return SGX_E_HIP;
@@ -155,12 +155,10 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
     sgx_if tmp;
     tmp.device = c->device;
     tmp.n = (size_t)n_samp * (size_t)sb;
-    e = hipMalloc((void**)&tmp.d, tmp.n + SGX_IF_PAD);
-    if (e != hipSuccess) {
-        sgx_set_error("hipMalloc(%zu) for the narrowed float32 record failed: %s", tmp.n + SGX_IF_PAD, hipGetErrorString(e));
-        return SGX_E_NOMEM;
-    }
-    int rc = SGX_OK;
+    DevBuf<int8_t> narrowed;   // (owns the record's memory: tmp is a handle for sgx_track_kind only)
+    rc = narrowed.ensure(tmp.n + SGX_IF_PAD);
+    if (rc != SGX_OK) return rc;
+    tmp.d = narrowed;
     {
         const int grid = (int)((n_samp + 255) / 256 < 8192 ? (n_samp + 255) / 256 : 8192);
         if (narrow8) f32_narrow_kernel<int8_t><<<grid, 256, 0, c->stream>>>(x, n_samp, k, tmp.d);
@@ -201,8 +199,6 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
             }
         }
     }
-    hipFree(tmp.d);
-    tmp.d = nullptr;
     return rc;
 }
 
@@ -261,8 +257,9 @@ int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
         if (rq != SGX_OK) return rq;
     }
     SGX_HIP(hipSetDevice(c->device));
-    unsigned long long* d_st = nullptr;
-    SGX_HIP(hipMalloc((void**)&d_st, 3 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_st;
+    const int rc = d_st.ensure(3 * sizeof(unsigned long long));
+    if (rc != SGX_OK) return rc;
     unsigned long long h_st[3] = {0ull, 0ull, 0ull};
     hipError_t e = hipMemsetAsync(d_st, 0, sizeof(h_st), c->stream);
     if (e == hipSuccess) {
@@ -271,7 +268,6 @@ int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
         e = hipMemcpyAsync(h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_st);
     if (e != hipSuccess) {
         sgx_set_error("float64 record scan: %s", hipGetErrorString(e));
         return SGX_E_HIP;
