@@ -573,6 +573,63 @@ int sgx_if_requantize(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t 
 int sgx_requant_timing(sgx_ctx* c, float* stats_ms, float* kernel_ms);
 int sgx_requant_tile(int32_t* tile_bytes);
 
+/* ---- block-wise front-end conditioning: DC removal, AGC and pulse blanking (no reference counterpart; the stage in front
+ * of sgx_if_from_iq, where the fixed-gain requantiser sits otherwise) ------------------------------------------------------
+ * Opt-in.  A resident record holding the raw BYTES of a file of int8 (w = 1) or little-endian int16 (w = 2) elements,
+ * n = N / w of them, comes out as a NEW int8 record of n bytes, element i -> byte i.  data_type is SGX_DT_INT8 or
+ * SGX_DT_INT16; with SGX_COND_OFFSET_BINARY (w = 1 only) an element is byte - 128.  lanes L is 1 or 2: frame f holds
+ * elements x[f L + l], L = 2 is interleaved I/Q; n must be a multiple of L, F = n / L frames.  float32 is out of scope: its
+ * sums are not order-free, so there is no byte-exact contract.  Blocks of `block` = B frames, 256 <= B <= 16384, a multiple
+ * of 16: block k holds frames [k B, min(F, (k + 1) B)), n_k >= 1 of them, K = ceil(F / B); F = 0 gives K = 0 and an empty
+ * output.  tests/cond_spec.py restates all of it in numpy.
+ *
+ * sgx_cond_block_stats (device): per block, in exact integers, with S_l the sum of lane l over the block:
+ *   dc_l = (16 S_l + (n_k >> 1)) // n_k   (floor division; the DC in 1/16 LSB)
+ *   d_l[f] = 16 x - dc_l, |d| < 2^21;  e[f] = sum_l d_l[f]^2 < 2^43;  P_0 = sum_f e[f] < 2^57, m_0 = n_k, e_max = max e[f]
+ * and two clipping rounds r = 1, 2 with blank_q4 = 16 c^2, an integer that is 0 or 16 .. 4096:
+ *   theta_r = ((P_{r-1} // m_{r-1}) blank_q4) >> 4;  the frames with e[f] <= theta_r are kept: m_r of them, P_r their sum
+ * (blank_q4 >= 16 keeps every frame at or below the mean, so m_r >= 1; blank_q4 = 0 skips the rounds: m_2 = n_k, P_2 = P_0).
+ * out[k] = {n_k, m_2, dc_0, dc_1 (0 for L = 1), P_2, P_0, e_max, 0}.  out must hold out_cap >= K entries; *n_blocks = K.
+ * The record is read on the context's stream (a record that is still streaming in is waited for).
+ *
+ * sgx_cond_plan: DC, gain and blanking threshold per block; exact host code in doubles, in this order, needs no GPU.
+ *   v_k = p_kept / (kept L 256.0);  D_lk = (double)dc_l;  alpha = 1 / agc_blocks (agc_blocks real, >= 1)
+ *   a_0 = v_0, a_k = a_{k-1} + alpha (v_k - a_{k-1});  A_lk from D_lk by the same recursion
+ *   g_k = target_rms / sqrt(a_k), 1 where a_k is not > 0;  (mult, shift) from g_k by sgx_requant_gain's rule: the largest
+ *   shift in 0 .. 30 with rint(g 2^shift) <= 32767, mult = max(1, that);  dc_l = (int)rint(A_lk)
+ *   theta = (int64)floor(a_k (16 L blank_q4)), INT64_MAX for blank_q4 = 0.   target_rms lies in (0, 127].
+ *
+ * sgx_if_condition (device): with k the block of frame f and plan[k] = {dc0, dc1, mult, shift, theta}:
+ *   d_l = 16 x - dc_l;  hit[f] = sum_l d_l^2 > theta;  frame f is BLANKED if any frame within `guard` G (0 .. 64) of it is
+ *   hit - the dilation crosses block boundaries and the kernel's tile seams and is cut only by the ends of the record.
+ *   A blanked element gives 0, any other y = clip((d mult + (1 << (shift + 3))) >> (shift + 4), -127, 127), a floor shift
+ *   of a 64-bit intermediate.  *blanked_frames and *clipped (elements on +-127; either may be NULL) are exact.
+ * n_plan must be K; a plan entry has mult 1 .. 32767, shift 0 .. 30, |dc| <= 2^20, theta >= 0.  The input is left alone;
+ * *out is an ordinary record (sgx_if_free).
+ * sgx_cond_timing: HIP-event times of the last sgx_cond_block_stats' and the last sgx_if_condition's kernel on this context.
+ * sgx_cond_tile: the frames one workgroup of the apply kernel makes (where its tile seams lie).
+ * SGX_E_ARG, before anything is launched: a data_type other than the two, an unknown flag, offset binary with int16, lanes
+ * other than 1 or 2, a block outside 256 .. 16384 or no multiple of 16, blank_q4 other than 0 or 16 .. 4096, N that does not
+ * hold whole frames, guard outside 0 .. 64, out_cap or n_plan that is not K, a plan entry out of range, kept < 1,
+ * target_rms outside (0, 127], agc_blocks that is not finite or below 1, a NULL pointer. */
+#define SGX_COND_OFFSET_BINARY 1
+typedef struct sgx_cond_stats {
+    int64_t n, kept, dc0, dc1, p_kept, p_all, e_max, reserved;
+} sgx_cond_stats;           /* 64 bytes */
+typedef struct sgx_cond_entry {
+    int32_t dc0, dc1, mult, shift;
+    int64_t theta;
+} sgx_cond_entry;           /* 24 bytes */
+int sgx_cond_block_stats(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t lanes, int32_t block, int32_t blank_q4,
+                         int32_t flags, sgx_cond_stats* out, size_t out_cap, size_t* n_blocks);
+int sgx_cond_plan(const sgx_cond_stats* stats, size_t n_blocks, int32_t lanes, int32_t blank_q4, double target_rms,
+                  double agc_blocks, sgx_cond_entry* plan);
+int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t lanes, int32_t block, int32_t flags,
+                     const sgx_cond_entry* plan, size_t n_plan, int32_t guard, sgx_if** out, int64_t* blanked_frames,
+                     int64_t* clipped);
+int sgx_cond_timing(sgx_ctx* c, float* stats_ms, float* apply_ms);
+int sgx_cond_tile(int32_t* tile_frames);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -89,6 +89,19 @@ class RequantStats(C.Structure):
                 ("sum_sq", C.c_double)]
 
 
+class CondStats(C.Structure):
+    """sgx_cond_stats: the statistics of one block of the conditioning stage (sgx_cond_block_stats, 64 bytes)."""
+    _fields_ = [(k, C.c_int64) for k in ("n", "kept", "dc0", "dc1", "p_kept", "p_all", "e_max", "reserved")]
+
+
+class CondEntry(C.Structure):
+    """sgx_cond_entry: DC, gain and blanking threshold of one block (sgx_cond_plan -> sgx_if_condition, 24 bytes)."""
+    _fields_ = [("dc0", C.c_int32), ("dc1", C.c_int32), ("mult", C.c_int32), ("shift", C.c_int32), ("theta", C.c_int64)]
+
+
+COND_STATS_DTYPE = np.dtype([(k, "<i8") for k in ("n", "kept", "dc0", "dc1", "p_kept", "p_all", "e_max", "reserved")])
+COND_PLAN_DTYPE = np.dtype([("dc0", "<i4"), ("dc1", "<i4"), ("mult", "<i4"), ("shift", "<i4"), ("theta", "<i8")])
+COND_OFFSET_BINARY = 1
 REPLAY_MAX_TAPS = 64
 REPLAY_STATE_DTYPE = np.dtype([("start", "<i8"), ("rem_code", "<f8"), ("rem_carr", "<f8"), ("step", "<f8"),
                                ("carr_freq", "<f8"), ("blk", "<i4"), ("reserved", "<i4")])
@@ -165,6 +178,13 @@ _PROTOS = {
                                     C.POINTER(C.c_int64)]),
     "sgx_requant_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sgx_requant_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_cond_block_stats": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
+    "sgx_cond_plan": (C.c_int, [_P, C.c_size_t, C.c_int32, C.c_int32, C.c_double, C.c_double, _P]),
+    "sgx_if_condition": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, C.c_int32,
+                                   C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sgx_cond_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sgx_cond_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -510,6 +530,37 @@ def requant_tile():
     """Output bytes (= elements) one workgroup of the requantiser makes: its tile seams lie at the multiples."""
     t = C.c_int32(0)
     check(lib().sgx_requant_tile(C.byref(t)))
+    return t.value
+
+
+def cond_type(dtype, offset_binary=False):
+    """(sgx data_type, bytes per element, flags) of a sample type the conditioning stage reads: int8, uint8 (offset binary:
+    element = byte - 128) or int16."""
+    dt = np.dtype(dtype)
+    if dt == np.dtype(np.uint8):
+        return DT_INT8, 1, COND_OFFSET_BINARY
+    if dt == np.dtype(np.int8):
+        return DT_INT8, 1, COND_OFFSET_BINARY if offset_binary else 0
+    if dt == np.dtype(np.int16):
+        return DT_INT16, 2, COND_OFFSET_BINARY if offset_binary else 0   # (the library refuses the flag with int16)
+    raise ValueError("the conditioning stage reads int8, uint8 and int16 records, not %r" % (dtype,))
+
+
+def cond_plan(stats, lanes, blank_q4, target_rms=12.0, agc_blocks=32.0):
+    """The per-block plan of the conditioning stage (sgx_cond_plan; exact host code, needs no GPU): stats, the
+    COND_STATS_DTYPE array of Context.cond_stats, smoothed over agc_blocks blocks into a COND_PLAN_DTYPE array of
+    (dc0, dc1, mult, shift, theta) per block."""
+    st = np.ascontiguousarray(stats, dtype=COND_STATS_DTYPE).ravel()
+    plan = np.zeros(st.size, dtype=COND_PLAN_DTYPE)
+    check(lib().sgx_cond_plan(_ptr(st), st.size, int(lanes), int(blank_q4), float(target_rms), float(agc_blocks),
+                              _ptr(plan)))
+    return plan
+
+
+def cond_tile():
+    """Frames one workgroup of the conditioning kernel makes: its tile seams lie at the multiples."""
+    t = C.c_int32(0)
+    check(lib().sgx_cond_tile(C.byref(t)))
     return t.value
 
 
@@ -876,6 +927,38 @@ class Context(object):
         """(statistics kernel ms, quantiser kernel ms) of the last requant_stats and the last requantize on this context."""
         a, b = C.c_float(0), C.c_float(0)
         check(lib().sgx_requant_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def cond_stats(self, rec, dtype, lanes, block, blank_q4, offset_binary=False):
+        """Per-block statistics of `rec`, the raw bytes of a file of int8, uint8 (offset binary) or int16 samples in
+        frames of `lanes` elements and blocks of `block` frames (sgx_cond_block_stats): a COND_STATS_DTYPE array, one
+        entry per block, every field an exact integer."""
+        dt, w, flags = cond_type(dtype, offset_binary)
+        cap = len(rec) // (w * max(int(lanes), 1) * max(int(block), 1)) + 1
+        out = np.zeros(cap, dtype=COND_STATS_DTYPE)
+        k = C.c_size_t(0)
+        check(lib().sgx_cond_block_stats(self._h, rec._h, dt, int(lanes), int(block), int(blank_q4), flags, _ptr(out), cap,
+                                         C.byref(k)))
+        return out[:k.value]
+
+    def condition(self, rec, dtype, lanes, block, plan, guard, offset_binary=False):
+        """A new int8 record, one byte per element of `rec`: DC removed, scaled and blanked block by block as `plan` (a
+        COND_PLAN_DTYPE array, one entry per block) says, hits dilated by `guard` frames (sgx_if_condition).  The blanked
+        frames and the outputs on +-127 are left in the new record's `blanked` and `clipped`."""
+        dt, w, flags = cond_type(dtype, offset_binary)
+        p = np.ascontiguousarray(plan, dtype=COND_PLAN_DTYPE).ravel()
+        h = _P()
+        nb, nc = C.c_int64(0), C.c_int64(0)
+        check(lib().sgx_if_condition(self._h, rec._h, dt, int(lanes), int(block), flags, _ptr(p), p.size, int(guard),
+                                     C.byref(h), C.byref(nb), C.byref(nc)))
+        out = Record(self, h, len(rec) // w)
+        out.blanked, out.clipped = int(nb.value), int(nc.value)
+        return out
+
+    def cond_timing(self):
+        """(statistics kernel ms, apply kernel ms) of the last cond_stats and the last condition on this context."""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib().sgx_cond_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):

@@ -106,6 +106,11 @@ struct FftPlan {
 #define RQ_CLIP_SLOTS 256
 #define RQ_CLIP_STRIDE 32    // words between two counters: one 128-byte line each
 
+// sgx_cond.hip: the slots the apply kernel spreads its per-workgroup counts over; a slot is one 128-byte line that holds
+// the blanked frames (word 0) and the elements on +-127 (word 1)
+#define CD_COUNT_SLOTS 256
+#define CD_COUNT_STRIDE 16   // 64-bit words between two slots
+
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
     size_t n = 0;
@@ -249,6 +254,8 @@ struct SgxSmall {
     // the quantiser's counters of outputs on +-127; both entry points wait before they return; both
     alignas(256) unsigned long long requant_part[RQ_STATS_BLOCKS * 4];
     alignas(256) unsigned requant_clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE];
+    // sgx_cond.hip: the apply kernel's counters; sgx_if_condition waits before it returns; both
+    alignas(256) unsigned long long cond_count[CD_COUNT_SLOTS * CD_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");
@@ -357,6 +364,11 @@ struct sgx_ctx {
     float iq_kernel_ms = 0.0f;       // HIP-event time of the last sgx_if_from_iq's kernel (sgx_iq.hip)
     // HIP-event times of the last sgx_requant_stats_of's and the last sgx_if_requantize's kernel (sgx_requant.hip)
     float requant_stats_ms = 0.0f, requant_kernel_ms = 0.0f;
+    // front-end conditioning (sgx_cond.hip): the per-block statistics and the plan as the kernels write and read them
+    // (grow-only), and the HIP-event times of the last sgx_cond_block_stats' and the last sgx_if_condition's kernel
+    DevBuf<sgx_cond_stats> d_cond_stats;
+    DevBuf<sgx_cond_entry> d_cond_plan;
+    float cond_stats_ms = 0.0f, cond_apply_ms = 0.0f;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

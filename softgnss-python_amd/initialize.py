@@ -122,6 +122,17 @@ _IQ_DEFAULTS = (
     ("iqTargetRms", 12.0),               # rms of the int8 record it makes, LSB, in (0, 127]
 )
 
+# block-wise front-end conditioning (Settings.conditionRecord; INTEGRATION.md, "Front-end conditioning"): DC removal, a
+# time-varying AGC and pulse blanking per short block, first of all stages, where the fixed-gain requantiser sits otherwise
+_COND_DEFAULTS = (
+    ("frontEndConditioning", False),     # the stage is off
+    ("condBlockUs", 100.0),              # block length: that many frames at samplingFreq, to a multiple of 16 in 256 .. 16384
+    ("condAgcBlocks", 32.0),             # the AGC's smoothing length in blocks
+    ("condBlankFactor", 4.0),            # c: a frame beyond c x the smoothed rms is blanked; blank_q4 = rint(16 c^2); 0: off
+    ("condGuardFrames", 8),              # frames blanked either side of a hit
+    ("condTargetRms", 12.0),             # rms of the int8 record it makes, LSB, in (0, 127]
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -130,7 +141,7 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS + _COND_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -250,6 +261,9 @@ class Settings(object):
     def _iq_format(self):
         """(q_first, offset_binary) of the I/Q file these settings describe."""
         dt = np.dtype(self.dataType)
+        if self.frontEndConditioning:
+            self._cond_format()
+            return bool(self.iqQFirst), False        # (what conditionRecord makes of the file is int8, its offset removed)
         if self.iqRequantize and dt in (np.dtype(np.int16), np.dtype(np.float32)):
             return bool(self.iqQFirst), False        # (what requantizeIQ makes of the file is int8)
         if dt not in (np.dtype(np.int8), np.dtype(np.uint8)):
@@ -261,16 +275,43 @@ class Settings(object):
         return bool(self.iqQFirst), dt == np.dtype(np.uint8)
 
     def _iq_width(self):
-        """Bytes per component of the I/Q file: 2 or 4 where it goes through the requantiser, else 1."""
+        """Bytes per component of the I/Q file: 2 or 4 where it goes through the requantiser or the conditioning stage,
+        else 1."""
         self._iq_format()
         return np.dtype(self.dataType).itemsize if self.iqRecord else 1
 
+    def _cond_format(self):
+        """(bytes per component, lanes, block in frames, blank_q4) of the conditioning stage for these settings."""
+        dt = np.dtype(self.dataType)
+        if self.iqRequantize:
+            raise ValueError("Settings.frontEndConditioning stands where the fixed-gain requantiser (Settings.iqRequantize) "
+                             "does: not both")
+        if dt == np.dtype(np.float32):
+            raise ValueError("Settings.frontEndConditioning reads int8, uint8 and int16 records: float32 sums are not "
+                             "order-free, so Settings.dataType 'float32' goes through Settings.iqRequantize instead")
+        w = _native.cond_type(dt)[1]
+        block = 16 * int(np.rint(float(self.condBlockUs) * 1e-6 * float(self.samplingFreq) / 16.0))
+        c = float(self.condBlankFactor)
+        return w, 2 if self.iqRecord else 1, min(16384, max(256, block)), int(np.rint(16.0 * c * c))
+
     def _prepared_settings(self):
         """The settings the PREPARED record is read under: realEquivalent(), with skipNumberOfBytes turned from a byte of a
-        file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w."""
+        file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w.  A real record
+        that goes through the conditioning stage comes out as int8 in the same way."""
         if not self.iqRecord:
-            return self
+            if not self.frontEndConditioning:
+                return self
+            w = self._cond_format()[0]
+            real = copy.copy(self)
+            real.frontEndConditioning = False
+            real.dataType = 'int8'
+            skip = int(self.skipNumberOfBytes)
+            if skip % w:
+                raise ValueError("skipNumberOfBytes = %d splits a sample: it must be a multiple of %d" % (skip, w))
+            real.skipNumberOfBytes = skip // w
+            return real
         real = self.realEquivalent()
+        real.frontEndConditioning = False            # (the prepared record has been through the stage)
         w = self._iq_width()
         skip = int(self.skipNumberOfBytes)
         if skip % (2 * w):
@@ -278,6 +319,38 @@ class Settings(object):
                              (skip, "even" if w == 1 else "a multiple of %d (pairs of %d-byte components)" % (2 * w, w)))
         real.skipNumberOfBytes = skip // w
         return real
+
+    def conditionRecord(self, record):
+        """A resident record holding the raw bytes of an int8, uint8 or int16 file (a _native.Record; Settings.dataType
+        says which; with iqRecord interleaved I/Q) as a NEW int8 record, one sample per component, conditioned block by
+        block: the statistics of every block of condBlockUs (cond_stats), smoothed over condAgcBlocks blocks into a DC per
+        rail, a gain that brings the rms to condTargetRms and a blanking threshold of condBlankFactor x the rms
+        (cond_plan), and the record through them, frames within condGuardFrames of a hit set to zero (condition).  Sample
+        n of the new record is component n of the file.  Returns (record8, info) and keeps info as self.lastConditioning:
+        samples, block, blocks, blank_q4, blanked (share of the frames), clipped (share of the samples on +-127), gain_db_min,
+        gain_db_max, dc_min and dc_max (a tuple per lane, LSB).  The caller frees both."""
+        if not self.frontEndConditioning:
+            raise ValueError("Settings.frontEndConditioning is off")
+        w, lanes, block, blank_q4 = self._cond_format()
+        dt = np.dtype(self.dataType)
+        ctx = record.ctx
+        stats = ctx.cond_stats(record, dt, lanes, block, blank_q4)
+        plan = _native.cond_plan(stats, lanes, blank_q4, self.condTargetRms, self.condAgcBlocks)
+        rec8 = ctx.condition(record, dt, lanes, block, plan, int(self.condGuardFrames))
+        frames = len(rec8) // lanes
+        info = dict(samples=len(rec8), block=block, blocks=int(plan.size), blank_q4=blank_q4,
+                    blanked=float(rec8.blanked) / frames if frames else 0.0,
+                    clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0)
+        if plan.size:
+            gain_db = 20.0 * np.log10(plan["mult"].astype(np.float64) / np.exp2(plan["shift"].astype(np.float64)))
+            info["gain_db_min"], info["gain_db_max"] = float(gain_db.min()), float(gain_db.max())
+            dcs = [plan[k].astype(np.float64) / 16.0 for k in ("dc0", "dc1")[:lanes]]
+            info["dc_min"], info["dc_max"] = tuple(float(d.min()) for d in dcs), tuple(float(d.max()) for d in dcs)
+        else:
+            info["gain_db_min"] = info["gain_db_max"] = 0.0
+            info["dc_min"] = info["dc_max"] = (0.0,) * lanes
+        self.lastConditioning = info
+        return rec8, info
 
     def requantizeIQ(self, record):
         """A resident record holding the raw bytes of an int16 or float32 file (a _native.Record; Settings.dataType says
@@ -328,7 +401,8 @@ class Settings(object):
     @contextlib.contextmanager
     def _prepared_record(self, name, offset, count, mitigate_at=None, verbose=False):
         """Samples [offset, offset + count) of the prepared record of a record file, uploaded once and prepared on the
-        GPU, for the length of the block: with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
+        GPU, for the length of the block: with frontEndConditioning brought to int8 block by block (conditionRecord), first
+        of all; with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
         with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation) cleared
         of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the real
         rate.  offset and count are in BYTES OF THE PREPARED RECORD: for a file of w-byte components the bytes
@@ -338,10 +412,20 @@ class Settings(object):
         from . import engine
         say = print if verbose else (lambda *args: None)
         real = self._prepared_settings()
-        w = self._iq_width() if self.iqRecord else 1
+        w = self._iq_width() if self.iqRecord else (self._cond_format()[0] if self.frontEndConditioning else 1)
         rec = engine.get_context(real, None).upload_file(name, w * offset, w * count)
         try:
-            if w > 1:
+            if self.frontEndConditioning:
+                say('   Conditioning %s samples block by block...' % np.dtype(self.dataType).name)
+                raw, rec = rec, None
+                try:
+                    rec, info = self.conditionRecord(raw)
+                finally:
+                    raw.free()
+                say('   %d blocks of %d frames: gain %+.2f .. %+.2f dB, %.4f %% of the frames blanked, %.4f %% of the '
+                    'samples clipped' % (info["blocks"], info["block"], info["gain_db_min"], info["gain_db_max"],
+                                         100.0 * info["blanked"], 100.0 * info["clipped"]))
+            elif w > 1:
                 say('   Requantising %s samples to int8...' % np.dtype(self.dataType).name)
                 raw, rec = rec, None
                 try:
@@ -432,7 +516,7 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.iqRecord or self.interferenceMitigation:
+        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning:
             acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None

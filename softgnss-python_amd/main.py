@@ -4,6 +4,7 @@
                                                   [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]]
                                                   [--iq[=qi]] [--dtype int8] [--iq-requantize[=RMS]]
+                                                  [--condition[=BLANK_FACTOR]]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -17,7 +18,11 @@ twice the rate, whose rate and IF are printed, and everything else runs on that.
 int16 or float32: sc16 and fc32 captures) first brings the file to int8 on the GPU through one fixed gain that puts its rms
 at 12 LSB (or --iq-requantize=RMS), and prints the record's rms, peak, count of non-finite samples, the gain in dB and the
 share of clipped samples; --skip stays a byte of the file (a multiple of 4 for int16, 8 for float32), the positions in the
-results are samples of the converted record, file byte / 2 or / 4."""
+results are samples of the converted record, file byte / 2 or / 4.  --condition (--dtype int8, uint8 or int16, real or
+with --iq) first conditions the file block by block on the GPU: per 100 us it removes the DC of each rail, sets the gain
+that puts the rms at 12 LSB (a time-varying AGC) and zeroes the frames that stand 4 x (or --condition=BLANK_FACTOR, 1 .. 16;
+0: no blanking) above the rms, and prints the span of the gain and the shares of blanked frames and clipped samples; it
+stands where --iq-requantize does, so not both; an int16 file is then read as int8, positions are file byte / 2."""
 from __future__ import print_function
 
 import argparse
@@ -65,7 +70,14 @@ def main(argv=None):
     ap.add_argument("--iq-requantize", nargs="?", type=float, const=-1.0, default=None, metavar="RMS",
                     help="with --iq and --dtype int16 or float32: bring the file to int8 on the GPU through one fixed gain "
                          "that puts its rms at RMS LSB (default: Settings.iqTargetRms, 12)")
+    ap.add_argument("--condition", nargs="?", type=float, const=-1.0, default=None, metavar="BLANK_FACTOR",
+                    help="condition the file block by block on the GPU before anything else: DC removal, AGC and pulse "
+                         "blanking at BLANK_FACTOR x the rms (default: Settings.condBlankFactor, 4; 0: no blanking)")
     a = ap.parse_args(argv)
+    if a.condition is not None and a.iq_requantize is not None:
+        ap.error("--condition stands where --iq-requantize does: not both")
+    if a.condition is not None and not (a.condition in (-1.0, 0.0) or 1.0 <= a.condition <= 16.0):
+        ap.error("--condition takes the blanking threshold in units of the rms, 1 .. 16, or 0 for no blanking")
     if a.iq_requantize is not None and a.iq is None:
         ap.error("--iq-requantize prepares an I/Q file for the converter: it needs --iq")
     if a.iq_requantize is not None and not (a.iq_requantize == -1.0 or 0.0 < a.iq_requantize <= 127.0):
@@ -92,6 +104,8 @@ def main(argv=None):
                       ("dataType", a.dtype),
                       ("iqRequantize", True if a.iq_requantize is not None else None),
                       ("iqTargetRms", a.iq_requantize if a.iq_requantize is not None and a.iq_requantize > 0 else None),
+                      ("frontEndConditioning", True if a.condition is not None else None),
+                      ("condBlankFactor", a.condition if a.condition is not None and a.condition >= 0 else None),
                       ("interferenceMitigation", True if a.notch is not None else None),
                       ("notchThresholdDb", a.notch if a.notch is not None and a.notch >= 0 else None)):
         if val is not None:
