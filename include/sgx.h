@@ -124,8 +124,17 @@ int sgx_make_ca_table(const sgx_settings* s, double* out);
 int sgx_calc_loop_coef(double lbw, double zeta, double k, double* tau1, double* tau2);
 /* Host evaluation of the short-chain arithmetic the tracking kernel's loop-filter waves use (csrc/sgx_trk_math.h; on the
  * host the hardware reciprocal seeds are replaced by float-precision ones).  Diagnostics for the parity tests:
- * fn 0: 1/a   1: a/b   2: sqrt(a)   3: atan(a/b)   4: out[0..1] = sin, cos of 2 pi a   5: ceil(a/b) */
+ * fn 0: 1/a   1: a/b   2: sqrt(a)   3: atan(a/b)   4: out[0..1] = sin, cos of 2 pi a   5: ceil(a/b)
+ * 6: sgx_div1   7: sgx_sqrt1   8: sgx_atan_ratio_k   9: sgx_rot_small -> sin, cos
+ * 10: sgx_block_length(a = 1023 - rem, b = codeFreq) at fs = 38.192 MHz -> block length, step_a */
 int sgx_trk_math_eval(int32_t fn, double a, double b, double* out);
+/* The same for n elements with up to four operands each (host arrays; an unused operand may be null) and two results per
+ * element: fn 0 .. 9 as above, and
+ *   10: sgx_block_length(a = 1023 - rem, b = codeFreq, c = fs, d = RN(1 / fs)) -> block length, step_a
+ *   11: sgx_sqrt1_pos(a)   12: sgx_div_rn(a, b, c = RN(1 / b))   13: as 10 -> block length, ~1 / step_a
+ * Both entries run the ONE fn -> call table of csrc/sgx_trk_math_eval.h. */
+int sgx_trk_math_eval_batch(int32_t fn, int64_t n, const double* a, const double* b, const double* c, const double* d,
+                            double* out0, double* out1);
 
 /* ---- device context and IF records --------------------------------------------------------- */
 int sgx_device_count(int* n);
@@ -137,6 +146,17 @@ int sgx_ctx_create_prio(const sgx_settings* s, int device, int priority, sgx_ctx
 int sgx_ctx_destroy(sgx_ctx* c);
 int sgx_ctx_sync(sgx_ctx* c);                     /* hipStreamSynchronize on the context stream */
 int sgx_get_timing(sgx_ctx* c, sgx_timing* out);
+/* sgx_trk_math_eval_batch on the device (csrc/sgx_trk_math_dev.hip; 1 <= n <= 2^20): the same table as the device
+ * compiles it, and the __device__ helpers of csrc/sgx_trk_common.h:
+ *   16: div_rn(a, b, c = RN(1 / b))   17: sincos_turns(a) -> sin, cos
+ *   18: ramp_setup(start a, ramp step b, ilo = (int)d), its reciprocal estimate formed from the code step c as prep_code
+ *       forms it -> k1, isw
+ *   20 .. 24: prep_code(codeFreq a, rem b) with the kernels' constants for fs = c[0] and correlator spacing = d[0] (c and d
+ *       hold that one value in every element) -> 20: blk, remCode   21: stepE, startE   22: stepP, startP
+ *       23: stepL, startL   24: the reciprocal estimate, stop
+ * Test support: nothing on the processing path calls it. */
+int sgx_trk_math_eval_device(sgx_ctx* ctx, int32_t fn, int64_t n, const double* a, const double* b, const double* c,
+                             const double* d, double* out0, double* out1);
 
 /* Optional pinned host memory for the big result buffer of sgx_track (a plain pageable buffer works too,
  * it only copies slower). */

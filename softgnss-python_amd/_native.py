@@ -117,6 +117,8 @@ _PROTOS = {
     "sgx_calc_loop_coef": (C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double)]),
     "sgx_trk_math_eval": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P]),
+    "sgx_trk_math_eval_batch": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "sgx_trk_math_eval_device": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "sgx_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "sgx_ctx_create": (C.c_int, [C.POINTER(Settings), C.c_int, C.POINTER(_P)]),
     "sgx_ctx_create_prio": (C.c_int, [C.POINTER(Settings), C.c_int, C.c_int, C.POINTER(_P)]),
@@ -260,6 +262,24 @@ def track_plan(settings, data_type=0, n_channels=8, n_cus=256, float_in_range=Fa
     check(lib().sgx_track_plan(C.byref(st), int(data_type), int(n_channels), int(n_cus), 1 if float_in_range else 0,
                                C.byref(k), C.byref(mbr)))
     return k.value, mbr.value
+
+
+def trk_math_eval(fn, a, b=None, c=None, d=None, ctx=None):
+    """(out0, out1): function fn of the tracking chain's arithmetic (include/sgx.h: sgx_trk_math_eval_batch) on every
+    element of the float64 operand arrays, on the host - or, with ctx (a Context), on its device as the device compiles it
+    (sgx_trk_math_eval_device, which also knows the device-only functions)."""
+    ops = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (a, b, c, d)]
+    n = ops[0].size
+    for x in ops[1:]:
+        if x is not None and x.size != n:
+            raise ValueError("operands of %d and %d elements" % (n, x.size))
+    out0, out1 = np.zeros(n), np.zeros(n)
+    ptrs = [None if x is None else _ptr(x) for x in ops] + [_ptr(out0), _ptr(out1)]
+    if ctx is None:
+        check(lib().sgx_trk_math_eval_batch(int(fn), n, *ptrs))
+    else:
+        check(lib().sgx_trk_math_eval_device(ctx._h, int(fn), n, *ptrs))
+    return out0, out1
 
 
 def acquire_plan(n_prn=32, n_bins=29, n_blocks=2, noncoh=False, chunk_rows=0, max_queues=2):

@@ -14,7 +14,7 @@
 #include <string>
 
 #include "sgx_internal.h"
-#include "sgx_trk_math.h"
+#include "sgx_trk_math_eval.h"
 
 static thread_local char g_err[512] = "";
 
@@ -683,22 +683,21 @@ extern "C" int sgx_if_download(sgx_ctx* c, const sgx_if* r, size_t offset, size_
 
 extern "C" int sgx_trk_math_eval(int32_t fn, double a, double b, double* out) {
     SGX_CHECK_ARG(out && fn >= 0 && fn <= 10);
-    switch (fn) {
-        case 6: out[0] = sgx_div1(a, b); break;
-        case 7: out[0] = sgx_sqrt1(a); break;
-        case 8: out[0] = sgx_atan_ratio_k(a, b, sgx_atan_coef()); break;
-        case 9: sgx_rot_small(a, sgx_rot_coef(), out[0], out[1]); break;
-        case 10: {   // a = 1023 - rem, b = codeFreq, at fs = 38.192 MHz: block length, and step_a in out[1]
-            double inv_step;
-            out[0] = (double)sgx_block_length(a, b, 38192000.0, 1.0 / 38192000.0, out[1], inv_step);
-            break;
-        }
-        case 0: out[0] = sgx_fast_rcp(a); break;
-        case 1: out[0] = sgx_fast_div(a, b); break;
-        case 2: out[0] = sgx_fast_sqrt(a); break;
-        case 3: out[0] = sgx_atan_ratio(a, b); break;
-        case 4: sgx_sincos_turns_short(a, out[0], out[1]); break;
-        default: out[0] = (double)sgx_ceil_div(a, b); break;
+    // (fn 10: the block length at fs = 38.192 MHz; sgx_trk_math_eval_batch takes the rate as an operand)
+    sgx_trk_math_call(fn, a, b, 38192000.0, 1.0 / 38192000.0, out[0], out[1]);
+    return SGX_OK;
+}
+
+extern "C" int sgx_trk_math_eval_batch(int32_t fn, int64_t n, const double* a, const double* b, const double* c,
+                                       const double* d, double* out0, double* out1) {
+    SGX_CHECK_ARG(fn >= 0 && fn < SGX_MATH_FN_HD_END);
+    SGX_CHECK_ARG(n >= 0 && out0 && out1);
+    SGX_CHECK_ARG(n == 0 || a);
+    for (int64_t i = 0; i < n; ++i) {
+        double o0 = 0.0, o1 = 0.0;
+        sgx_trk_math_call(fn, a[i], b ? b[i] : 0.0, c ? c[i] : 0.0, d ? d[i] : 0.0, o0, o1);
+        out0[i] = o0;
+        out1[i] = o1;
     }
     return SGX_OK;
 }

@@ -111,8 +111,9 @@ struct TrkState {
 };
 
 // a / b correctly rounded, given y = RN(1/b): reciprocal multiply plus two FMA corrections (Markstein).
-// Bit-identical to IEEE division for the divisors used here (pi, fs, block lengths) - checked against exact
-// rational arithmetic in tests/test_cabi_and_host.py - at a quarter of the dependent latency of v_div_*.
+// Bit-identical to IEEE division for the divisors used here (pi, fs, block lengths) - the identity is checked in exact
+// rational arithmetic (an emulation, tests/test_cabi_and_host.py), this function as the device compiles it against
+// numpy's division (tests/test_trk_math_gpu.py, next to sgx_div_rn) - at a quarter of the dependent latency of v_div_*.
 __device__ __forceinline__ double div_rn(double a, double b, double y) {
     const double q0 = a * y;
     const double r0 = __builtin_fma(-q0, b, a);
@@ -125,7 +126,8 @@ __device__ __forceinline__ double ramp_at(int i, double step, double start) {
     return (double)i * step + start;   // two roundings, like numpy's y = arange*step; y += start
 }
 
-// chip index at sample ilo and first sample whose chip index is larger (exact reference arithmetic).
+// chip index at sample ilo and first sample whose chip index is larger (exact reference arithmetic; against a
+// sample-by-sample search in tests/test_trk_math_gpu.py, like prep_code below against the reference's expressions).
 // (A one-FMA estimate guarded by near-integer tests was tried: it needs a full-precision 1/step and
 // measured slower than these two exact probes.)
 __device__ __forceinline__ void ramp_setup(double start, double step, double inv_step, int ilo, int& k1,

@@ -6,7 +6,10 @@
 // ulp, which is far inside what the discriminators need (the loop inputs are continuous in them),
 // while everything that feeds an integer rounding (block length, chip indices) keeps the reference's exact
 // arithmetic elsewhere.  The functions compile for the host as well (the hardware seeds are replaced by
-// float-precision ones, i.e. WORSE seeds), so tests/test_cabi_and_host.py checks the ulp bounds on the CPU.
+// float-precision ones, atan is glibc's instead of ocml's).  Both compilations are tested, each against 50-digit
+// arithmetic and numpy's IEEE fp64 and neither against the other: the host's in tests/test_cabi_and_host.py and
+// tests/test_trk_math_host.py, the device's in tests/test_trk_math_gpu.py through the evaluator of
+// sgx_trk_math_dev.hip (same bounds, same operands; measured worst cases side by side in DESIGN.md 4.1).
 #pragma once
 #include <math.h>
 
@@ -229,8 +232,10 @@ SGX_HD void sgx_rot_small(double ph, const SgxRotCoef& k, double& sn, double& cs
 }
 
 // a / b correctly rounded, given y = RN(1/b): reciprocal multiply plus two FMA corrections (Markstein).  Bit-identical
-// to IEEE division for the divisors used here (pi, fs, block lengths), checked against exact rational arithmetic in
-// tests/test_cabi_and_host.py
+// to IEEE division for the divisors used here (pi, every sampling rate of the suite, its block lengths; also blk / fs):
+// the identity is checked in exact rational arithmetic (an emulation, tests/test_cabi_and_host.py), this code as compiled
+// against numpy's division on the same operand classes - host: tests/test_trk_math_host.py, device:
+// tests/test_trk_math_gpu.py
 SGX_HD double sgx_div_rn(double a, double b, double y) {
     const double q0 = a * y;
     const double r0 = __builtin_fma(-q0, b, a);

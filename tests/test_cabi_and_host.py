@@ -170,10 +170,15 @@ def test_synth_scene_is_integer_and_deterministic(built):
 
 def test_reciprocal_division_identity_used_by_the_kernels():
     """csrc/sgx_trk_common.h div_rn: a*y with two FMA corrections (y = RN(1/b)) equals IEEE a/b for the
-    divisors on the tracking path (pi, fs, block lengths).  Emulated with exact rational arithmetic."""
+    divisors on the tracking path (pi, fs, block lengths).  Emulated with exact rational arithmetic: the two rates and
+    eight block lengths this test has always had, then every divisor class of tests/trk_math_cases.py at all thirteen
+    rates of the suite - blk / fs, which the PLL waves of sgx_trk2.hip and sgx_trk3.hip form, among them.  (The same
+    operands go through the COMPILED sgx_div_rn in tests/test_trk_math_host.py and, on the device, through both copies
+    in tests/test_trk_math_gpu.py.)"""
     import math
     import random
     from fractions import Fraction as F
+    import trk_math_cases as tm
 
     def rn(x):
         return float(x)          # Fraction -> nearest double, ties to even
@@ -197,6 +202,15 @@ def test_reciprocal_division_identity_used_by_the_kernels():
             else:
                 a = 1023.0 + random.uniform(-2e-3, 2e-3)
             assert div_rn(a, b, y) == rn(F(a) / F(b))
+    classes = tm.div_rn_operands(per_divisor=400, per_block_length=60, seed=11)
+    assert set(np.unique(classes["blk_over_fs"][1])) == set(tm.FS) and classes["blk_over_fs"][0].size == 13 * 121
+    for name, (aa, bb) in classes.items():
+        recip = {}
+        for a, b in zip(aa.tolist(), bb.tolist()):
+            if b not in recip:
+                recip[b] = rn(F(1) / F(b))
+                assert recip[b] == 1.0 / b
+            assert div_rn(a, b, recip[b]) == rn(F(a) / F(b)) == a / b, (name, a, b)
 
 
 def test_nav_parity_check_matches_oracle():
@@ -408,7 +422,8 @@ def _math_eval(fn, a, b=0.0):
 def test_short_chain_loop_filter_arithmetic_ulp_bounds(built):
     """csrc/sgx_trk_math.h (the loop-filter waves' reciprocal-based division and square root, short atan, Estrin
     sincos, division-free ceil) against 50-digit arithmetic.  The host build starts its Newton iterations from a
-    float-precision seed (worse than v_rcp_f64 / v_rsq_f64), so these bounds hold on the device too."""
+    float-precision seed and calls glibc's atan; the device compilation (v_rcp_f64 / v_rsq_f64, ocml's atan) is held to the
+    same bounds by tests/test_trk_math_gpu.py."""
     import math
     import mpmath as mp
     mp.mp.dps = 50
@@ -449,7 +464,8 @@ def test_short_chain_loop_filter_arithmetic_ulp_bounds(built):
 def test_one_step_division_sqrt_atan_and_small_rotation_ulp_bounds(built):
     """Round 3's shorter chain arithmetic (csrc/sgx_trk_math.h): sgx_div1 / sgx_sqrt1 (one Newton step + one residual
     step), the atan with the quotient by sgx_div1, and the Taylor pair that turns a carrier-table entry by the rate
-    step (|angle| <= 0.34 rad), against 50-digit arithmetic; host seeds are float precision (worse than the GPU's)."""
+    step (|angle| <= 0.34 rad), against 50-digit arithmetic; host seeds are float precision (the device compilation:
+    tests/test_trk_math_gpu.py)."""
     import math
     import mpmath as mp
     mp.mp.dps = 50
@@ -480,8 +496,10 @@ def test_one_step_division_sqrt_atan_and_small_rotation_ulp_bounds(built):
 
 def test_block_length_without_a_division_equals_the_reference(built):
     """sgx_block_length == ceil((1023 - rem) / (codeFreq / fs)) as numpy evaluates tracking.py:148-151 (two correctly
-    rounded divisions), for code frequencies around the basis, including quotients that are integers or a few ulp off."""
+    rounded divisions), for code frequencies around the basis, including quotients that are integers or a few ulp off -
+    at 38.192 MHz one call at a time, then at all thirteen rates of the suite through the batch entry's fs operand."""
     import math
+    import trk_math_cases as tm
     rng = np.random.default_rng(77)
     fs = 38192000.0
     assert int(_math_eval(10, 1023.0, 1023000.0)[0]) == 38192          # block 0: the quotient IS an integer
@@ -498,12 +516,24 @@ def test_block_length_without_a_division_equals_the_reference(built):
         got, step_a = _math_eval(10, a, cf)
         assert int(got) == math.ceil(a / step), (a, cf)
         assert abs(step_a - step) <= 3 * np.spacing(step)
+    a, cf, fs = tm.block_length_operands(40000, 78)
+    blk, step_a = pkg()._native.trk_math_eval(tm.FN["block_length"], a, cf, fs, 1.0 / fs)
+    step = cf / fs
+    assert not (msg := tm.first_mismatch(blk, np.ceil(a / step), a=a, codeFreq=cf, fs=fs)), msg
+    bad = np.flatnonzero(~(np.abs(step_a - step) <= 3 * np.spacing(step)))
+    assert bad.size == 0, (float(cf[bad[0]]), float(fs[bad[0]]), float(step_a[bad[0]]), float(step[bad[0]]))
+    first = np.flatnonzero(np.r_[True, fs[1:] != fs[:-1]])              # block 0 of every rate
+    assert np.all(a[first] == 1023.0) and np.all(cf[first] == 1.023e6) and first.size == 13
+    # (26 MHz: RN(1023 / RN(1.023e6 / fs)) = 26000.000000000004, so the reference's first block there has 26 001 samples)
+    assert np.array_equal(blk[first] - [tm.n_code(f) for f in tm.FS], [0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
 
 
 def test_division_free_ceil_equals_ieee_ceil(built):
     """sgx_ceil_div(a, b) == ceil(a / b) for the block-length computation blksize = ceil((1023 - rem) / step)
-    (tracking.py:148-151), including quotients that are exact integers or within a few ulp of one."""
+    (tracking.py:148-151), including quotients that are exact integers or within a few ulp of one - at 38.192 MHz one call
+    at a time, then at all thirteen rates of the suite through the batch entry."""
     import math
+    import trk_math_cases as tm
     rng = np.random.default_rng(7)
     fs = 38.192e6
     for k in range(20000):
@@ -518,6 +548,10 @@ def test_division_free_ceil_equals_ieee_ceil(built):
         else:
             a = 1023.0 - rng.uniform(-0.05, 0.05)
         assert int(_math_eval(5, a, step)[0]) == math.ceil(a / step), (a, step)
+    a, cf, fs = tm.block_length_operands(40000, 8)
+    step = cf / fs
+    got = pkg()._native.trk_math_eval(tm.FN["ceil_div"], a, step)[0]
+    assert not (msg := tm.first_mismatch(got, np.ceil(a / step), a=a, step=step, fs=fs)), msg
 
 
 def test_tracking_kernel_selection_table(built):
