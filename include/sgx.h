@@ -473,8 +473,9 @@ int sgx_replay_timing(sgx_ctx* c, float* kernel_ms, float* device_ms);
  * for byte.  The whole record is filtered on the context's stream (a record that is still streaming in is waited for,
  * as sgx_if_wait to its full length); *out is an ordinary record (its own magnitude-bound cache; sgx_if_free).
  * SGX_E_ARG, before anything is launched: n_taps even or out of range, shift outside 0 .. 30, a |h[k]| > 32 512 (a tap must
- * split into two signed bytes, h = 256 hi + lo), 128 sum|h| >= 2^31, a NULL pointer.  The record's bytes are read as
- * int8: records of other sample types (uint8, int16, ...) are not filtered.
+ * split into two signed bytes, h = 256 hi + lo), 128 sum|h| >= 2^31, a NULL pointer, a record that lies on another device
+ * than the context's (as the requantiser and the conditioning stage refuse it).  The record's bytes are read as int8:
+ * records of other sample types (uint8, int16, ...) are not filtered.
  * sgx_filter_timing: HIP-event time of the last sgx_if_filter's kernel on this context.
  *
  * sgx_notch_design: the lines of a one-sided PSD (f_mhz, pxx of n_bins >= 2 bins, as sgx_probe_stats gives them) and the
@@ -520,7 +521,7 @@ int sgx_filter_timing(sgx_ctx* c, float* kernel_ms);
  * sgx_if_wait to its full length); the input is left alone; *out is an ordinary record (its own magnitude-bound cache;
  * sgx_if_free).  SGX_E_ARG, before anything is launched: n_taps even or out of range, shift outside 0 .. 30, a
  * |h[k]| > 32 512 (a tap must split into two signed bytes, h = 256 hi + lo), 128 sum|h| >= 2^31, an unknown flag bit, a
- * NULL pointer, N odd.
+ * NULL pointer, a record that lies on another device than the context's, N odd.
  * sgx_iq_timing: HIP-event time of the last sgx_if_from_iq's kernel on this context.
  * sgx_iq_tile: the output bytes one workgroup of the kernel makes (the lengths at which its tile seams lie).
  *

@@ -513,11 +513,16 @@ def iq_design(n_taps=63):
     return taps, shift.value
 
 
+def _tile(name):
+    """What one workgroup of a record stage makes, as its sgx_*_tile getter reports it."""
+    t = C.c_int32(0)
+    check(getattr(lib(), name)(C.byref(t)))
+    return t.value
+
+
 def iq_tile():
     """Output bytes one workgroup of the I/Q converter makes: its tile seams lie at the multiples."""
-    t = C.c_int32(0)
-    check(lib().sgx_iq_tile(C.byref(t)))
-    return t.value
+    return _tile("sgx_iq_tile")
 
 
 REQUANT_SCALE_MIN, REQUANT_SCALE_MAX = 2.0 ** -100, 2.0 ** 100
@@ -548,9 +553,7 @@ def requant_gain(stats, dtype, target_rms=12.0):
 
 def requant_tile():
     """Output bytes (= elements) one workgroup of the requantiser makes: its tile seams lie at the multiples."""
-    t = C.c_int32(0)
-    check(lib().sgx_requant_tile(C.byref(t)))
-    return t.value
+    return _tile("sgx_requant_tile")
 
 
 def cond_type(dtype, offset_binary=False):
@@ -579,9 +582,7 @@ def cond_plan(stats, lanes, blank_q4, target_rms=12.0, agc_blocks=32.0):
 
 def cond_tile():
     """Frames one workgroup of the conditioning kernel makes: its tile seams lie at the multiples."""
-    t = C.c_int32(0)
-    check(lib().sgx_cond_tile(C.byref(t)))
-    return t.value
+    return _tile("sgx_cond_tile")
 
 
 def _int16_taps(taps):
@@ -880,25 +881,35 @@ class Context(object):
                                      done_p, _ptr(a), int(data_type), _ptr(tp), tp.size, _ptr(out)))
         return out
 
+    def _timing(self, getter, n):
+        """The n HIP-event times (ms) the library's sgx_*_timing `getter` reports for this context."""
+        ms = [C.c_float(0) for _ in range(n)]
+        check(getattr(lib(), getter)(self._h, *[C.byref(v) for v in ms]))
+        return tuple(v.value for v in ms)
+
     def replay_timing(self):
         """(kernel ms, device ms) of the last track_replay on this context, from HIP events on its stream."""
-        k, d = C.c_float(0), C.c_float(0)
-        check(lib().sgx_replay_timing(self._h, C.byref(k), C.byref(d)))
-        return k.value, d.value
+        return self._timing("sgx_replay_timing", 2)
+
+    def _stage(self, fn, n, args, counters=()):
+        """The new Record of n bytes that the record stage fn(ctx, *args, &record, &counter ...) makes, with its int64
+        counters as the attributes named in `counters`."""
+        h, cnt = _P(), [C.c_int64(0) for _ in counters]
+        check(getattr(lib(), fn)(self._h, *args, C.byref(h), *[C.byref(v) for v in cnt]))
+        out = Record(self, h, n)
+        for k, v in zip(counters, cnt):
+            setattr(out, k, v.value)
+        return out
 
     def filter_record(self, rec, taps, shift):
         """A new int8 record of the same length: `rec` through the zero-phase integer FIR of sgx_if_filter (taps: int16, an
         odd number of them up to 4095; y = clip((sum_k h[k] x[n + c - k] + 2^(shift-1)) >> shift, -127, 127))."""
         h16 = _int16_taps(taps)
-        h = _P()
-        check(lib().sgx_if_filter(self._h, rec._h, _ptr(h16), h16.size, int(shift), C.byref(h)))
-        return Record(self, h, len(rec))
+        return self._stage("sgx_if_filter", len(rec), (rec._h, _ptr(h16), h16.size, int(shift)))
 
     def filter_timing(self):
         """Kernel ms of the last filter_record on this context, from HIP events on its stream."""
-        k = C.c_float(0)
-        check(lib().sgx_filter_timing(self._h, C.byref(k)))
-        return k.value
+        return self._timing("sgx_filter_timing", 1)[0]
 
     def iq_to_if(self, rec, taps, shift, q_first=False, offset_binary=False):
         """A new int8 record of the same length: `rec`, the raw bytes of an interleaved 8-bit I/Q file at complex rate fs_c,
@@ -907,15 +918,11 @@ class Context(object):
         I; offset_binary: its bytes are uint8 around 128."""
         h16 = _int16_taps(taps)
         flags = (IQ_Q_FIRST if q_first else 0) | (IQ_OFFSET_BINARY if offset_binary else 0)
-        h = _P()
-        check(lib().sgx_if_from_iq(self._h, rec._h, _ptr(h16), h16.size, int(shift), flags, C.byref(h)))
-        return Record(self, h, len(rec))
+        return self._stage("sgx_if_from_iq", len(rec), (rec._h, _ptr(h16), h16.size, int(shift), flags))
 
     def iq_timing(self):
         """Kernel ms of the last iq_to_if on this context, from HIP events on its stream."""
-        k = C.c_float(0)
-        check(lib().sgx_iq_timing(self._h, C.byref(k)))
-        return k.value
+        return self._timing("sgx_iq_timing", 1)[0]
 
     def requant_stats(self, rec, dtype, offset=0, count=None):
         """Statistics of elements [offset, offset + count) (count None: to the end) of `rec`, the raw bytes of a file of
@@ -936,18 +943,12 @@ class Context(object):
         y = clip(rint(x * float32(scale)), -127, 127), NaN -> 0.  The number of outputs on +-127 is left in the new
         record's `clipped`."""
         dt, w = requant_type(dtype)
-        h = _P()
-        nc = C.c_int64(0)
-        check(lib().sgx_if_requantize(self._h, rec._h, dt, int(mult), int(shift), float(scale), C.byref(h), C.byref(nc)))
-        out = Record(self, h, len(rec) // w)
-        out.clipped = int(nc.value)
-        return out
+        return self._stage("sgx_if_requantize", len(rec) // w, (rec._h, dt, int(mult), int(shift), float(scale)),
+                           ("clipped",))
 
     def requant_timing(self):
         """(statistics kernel ms, quantiser kernel ms) of the last requant_stats and the last requantize on this context."""
-        a, b = C.c_float(0), C.c_float(0)
-        check(lib().sgx_requant_timing(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._timing("sgx_requant_timing", 2)
 
     def cond_stats(self, rec, dtype, lanes, block, blank_q4, offset_binary=False):
         """Per-block statistics of `rec`, the raw bytes of a file of int8, uint8 (offset binary) or int16 samples in
@@ -967,19 +968,12 @@ class Context(object):
         frames and the outputs on +-127 are left in the new record's `blanked` and `clipped`."""
         dt, w, flags = cond_type(dtype, offset_binary)
         p = np.ascontiguousarray(plan, dtype=COND_PLAN_DTYPE).ravel()
-        h = _P()
-        nb, nc = C.c_int64(0), C.c_int64(0)
-        check(lib().sgx_if_condition(self._h, rec._h, dt, int(lanes), int(block), flags, _ptr(p), p.size, int(guard),
-                                     C.byref(h), C.byref(nb), C.byref(nc)))
-        out = Record(self, h, len(rec) // w)
-        out.blanked, out.clipped = int(nb.value), int(nc.value)
-        return out
+        return self._stage("sgx_if_condition", len(rec) // w,
+                           (rec._h, dt, int(lanes), int(block), flags, _ptr(p), p.size, int(guard)), ("blanked", "clipped"))
 
     def cond_timing(self):
         """(statistics kernel ms, apply kernel ms) of the last cond_stats and the last condition on this context."""
-        a, b = C.c_float(0), C.c_float(0)
-        check(lib().sgx_cond_timing(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._timing("sgx_cond_timing", 2)
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

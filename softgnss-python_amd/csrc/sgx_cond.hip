@@ -22,7 +22,9 @@
 //                      lines.
 #include <limits.h>
 
-#include "sgx_internal.h"
+#include <type_traits>
+
+#include "sgx_stage.h"
 
 #define CD_THREADS 256
 #define CD_WAVES (CD_THREADS / 64)
@@ -408,9 +410,20 @@ extern "C" int sgx_cond_tile(int32_t* tile_frames) {
 
 extern "C" int sgx_cond_timing(sgx_ctx* c, float* stats_ms, float* apply_ms) {
     SGX_CHECK_ARG(c && stats_ms && apply_ms);
-    *stats_ms = c->cond_stats_ms;
-    *apply_ms = c->cond_apply_ms;
+    *stats_ms = c->stage_ms[SGX_STAGE_COND_STATS];
+    *apply_ms = c->stage_ms[SGX_STAGE_COND_APPLY];
     return SGX_OK;
+}
+
+// f(W, L) with the element width and the lanes of a frame as compile-time constants (std::integral_constant)
+template <typename F>
+static void cd_dispatch(int w, int lanes, F f) {
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    if (w == 1 && lanes == 1) f(I1(), I1());
+    else if (w == 1) f(I1(), I2());
+    else if (lanes == 1) f(I2(), I1());
+    else f(I2(), I2());
 }
 
 template <int W, int L>
@@ -438,38 +451,22 @@ extern "C" int sgx_cond_block_stats(sgx_ctx* c, const sgx_if* rec, int32_t data_
         sgx_set_error("bad argument: out holds %zu entries, the record has %zu blocks", out ? out_cap : (size_t)0, sh.blocks);
         return SGX_E_ARG;
     }
-    if (sh.blocks > 0x7FFFFFFFull) {
-        sgx_set_error("bad argument: a record of %zu blocks is beyond one launch of the statistics kernel", sh.blocks);
-        return SGX_E_ARG;
-    }
-    {
-        const int rq = sgx_if_require(rec, rec->n);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    c->cond_stats_ms = 0.0f;
+    int rc = sgx_stage_one_launch(sh.blocks, "bad argument: a record of %zu blocks is beyond one launch of the statistics kernel",
+                                  sh.blocks);
+    if (rc == SGX_OK) rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
+    c->stage_ms[SGX_STAGE_COND_STATS] = 0.0f;
     *n_blocks = sh.blocks;
-    if (sh.blocks == 0) return SGX_OK;
-    {
-        const int rc = c->d_cond_stats.ensure(sh.blocks * sizeof(sgx_cond_stats));
-        if (rc != SGX_OK) return rc;
-    }
-    hipEventRecord(c->ev[0], c->stream);
-    if (sh.w == 1 && lanes == 1) cd_launch_stats<1, 1>(c, rec, sh, block, blank_q4, c->d_cond_stats);
-    else if (sh.w == 1) cd_launch_stats<1, 2>(c, rec, sh, block, blank_q4, c->d_cond_stats);
-    else if (lanes == 1) cd_launch_stats<2, 1>(c, rec, sh, block, blank_q4, c->d_cond_stats);
-    else cd_launch_stats<2, 2>(c, rec, sh, block, blank_q4, c->d_cond_stats);
-    hipEventRecord(c->ev[1], c->stream);
-    hipError_t err = hipMemcpyAsync(out, c->d_cond_stats.get(), sh.blocks * sizeof(sgx_cond_stats), hipMemcpyDeviceToHost,
-                                    c->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_set_error("conditioning statistics kernel failed: %s", hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    hipEventElapsedTime(&c->cond_stats_ms, c->ev[0], c->ev[1]);
-    return SGX_OK;
+    if (sh.blocks == 0) return SGX_OK;   // (an empty record: nothing is queued, nothing to wait for)
+    rc = c->d_cond_stats.ensure(sh.blocks * sizeof(sgx_cond_stats));
+    if (rc != SGX_OK) return rc;
+    SgxStage st(SGX_STAGE_COND_STATS, (unsigned)sh.blocks, "conditioning statistics kernel failed: %s");
+    st.down = {out, c->d_cond_stats.get(), sh.blocks * sizeof(sgx_cond_stats)};
+    return sgx_stage_run(c, st, [&](sgx_if*) {
+        cd_dispatch(sh.w, lanes, [&](auto W, auto L) {
+            cd_launch_stats<decltype(W)::value, decltype(L)::value>(c, rec, sh, block, blank_q4, c->d_cond_stats);
+        });
+    });
 }
 
 extern "C" int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t lanes, int32_t block, int32_t flags,
@@ -495,66 +492,25 @@ extern "C" int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type
         }
     }
     const unsigned long long tiles = ((unsigned long long)sh.frames + CD_TILE - 1) / CD_TILE;
-    if (tiles > 0x7FFFFFFFull) {
-        sgx_set_error("bad argument: a record of %zu frames is beyond one launch of the conditioning kernel", sh.frames);
-        return SGX_E_ARG;
-    }
-    {
-        const int rq = sgx_if_require(rec, rec->n);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    if (n_plan) {
-        const int rc = c->d_cond_plan.ensure(n_plan * sizeof(sgx_cond_entry));
-        if (rc != SGX_OK) return rc;
-    }
-    sgx_if* r = nullptr;
-    const int rc = sgx_if_alloc_internal(c, sh.frames * (size_t)lanes, &r);
+    int rc = sgx_stage_one_launch(tiles, "bad argument: a record of %zu frames is beyond one launch of the conditioning kernel",
+                                  sh.frames);
+    if (rc == SGX_OK) rc = sgx_stage_open(c, rec, rec->n);
+    if (rc == SGX_OK && n_plan) rc = c->d_cond_plan.ensure(n_plan * sizeof(sgx_cond_entry));
     if (rc != SGX_OK) return rc;
-    c->cond_apply_ms = 0.0f;
+    sgx_cond_entry* d_plan = c->d_cond_plan;
     unsigned long long* d_cnt = c->d_small->cond_count;
     unsigned long long* h_cnt = c->h_small->cond_count;
-    memset(h_cnt, 0, sizeof(SgxSmall::cond_count));
-    hipError_t err = hipSuccess;
-    if (tiles) {
-        const unsigned grid = (unsigned)tiles;
-        sgx_cond_entry* d_plan = c->d_cond_plan;
-        err = hipMemcpyAsync(d_plan, plan, n_plan * sizeof(sgx_cond_entry), hipMemcpyHostToDevice, c->stream);
-        if (err == hipSuccess) err = hipMemsetAsync(d_cnt, 0, sizeof(SgxSmall::cond_count), c->stream);
-        hipEventRecord(c->ev[0], c->stream);
-        if (err != hipSuccess) {
-        } else if (sh.w == 1 && lanes == 1) {
-            cond_apply_kernel<1, 1><<<grid, CD_THREADS, 0, c->stream>>>(rec->d, r->d, sh.frames, block, d_plan, n_plan, guard,
-                                                                       sh.xmask, d_cnt);
-        } else if (sh.w == 1) {
-            cond_apply_kernel<1, 2><<<grid, CD_THREADS, 0, c->stream>>>(rec->d, r->d, sh.frames, block, d_plan, n_plan, guard,
-                                                                       sh.xmask, d_cnt);
-        } else if (lanes == 1) {
-            cond_apply_kernel<2, 1><<<grid, CD_THREADS, 0, c->stream>>>(rec->d, r->d, sh.frames, block, d_plan, n_plan, guard,
-                                                                       sh.xmask, d_cnt);
-        } else {
-            cond_apply_kernel<2, 2><<<grid, CD_THREADS, 0, c->stream>>>(rec->d, r->d, sh.frames, block, d_plan, n_plan, guard,
-                                                                       sh.xmask, d_cnt);
-        }
-        hipEventRecord(c->ev[1], c->stream);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(h_cnt, d_cnt, sizeof(SgxSmall::cond_count), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_if_free(c, r);
-        sgx_set_error("conditioning kernel failed: %s", hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    if (tiles) hipEventElapsedTime(&c->cond_apply_ms, c->ev[0], c->ev[1]);
-    int64_t nb = 0, nc = 0;
-    for (int i = 0; i < CD_COUNT_SLOTS; ++i) {
-        nb += (int64_t)h_cnt[i * CD_COUNT_STRIDE];
-        nc += (int64_t)h_cnt[i * CD_COUNT_STRIDE + 1];
-    }
-    if (blanked_frames) *blanked_frames = nb;
-    if (clipped) *clipped = nc;
-    *out = r;
+    SgxStage st(SGX_STAGE_COND_APPLY, (unsigned)tiles, "conditioning kernel failed: %s", out, sh.frames * (size_t)lanes);
+    st.up = {d_plan, plan, n_plan * sizeof(sgx_cond_entry)};
+    st.count_into(h_cnt, d_cnt, sizeof(SgxSmall::cond_count));
+    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
+        cd_dispatch(sh.w, lanes, [&](auto W, auto L) {
+            cond_apply_kernel<decltype(W)::value, decltype(L)::value><<<st.grid, CD_THREADS, 0, c->stream>>>(
+                rec->d, r->d, sh.frames, block, d_plan, n_plan, guard, sh.xmask, d_cnt);
+        });
+    });
+    if (rc != SGX_OK) return rc;
+    if (blanked_frames) *blanked_frames = sgx_sum_slots(h_cnt, CD_COUNT_SLOTS, CD_COUNT_STRIDE);
+    if (clipped) *clipped = sgx_sum_slots(h_cnt + 1, CD_COUNT_SLOTS, CD_COUNT_STRIDE);
     return SGX_OK;
 }

@@ -48,11 +48,12 @@ extern "C" int sgx_if_filter(sgx_ctx* c, const sgx_if* in, const int16_t* taps, 
     const int bad = fir_check_taps(taps, n_taps);
     if (bad != SGX_OK) return bad;
     SGX_CHECK_ARG(c && in && out);
-    {
-        const int rq = sgx_if_require(in, in->n);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
+    SGX_CHECK_ARG(in->device == c->device);
+    int rc = sgx_stage_open(c, in, in->n);
+    if (rc != SGX_OK) return rc;
+    const unsigned long long blocks = ((unsigned long long)in->n + FIR_TILE - 1) / FIR_TILE;
+    rc = sgx_stage_one_launch(blocks, "record of %zu samples is beyond one launch of the filter", in->n);
+    if (rc != SGX_OK) return rc;
 
     // reversed taps behind e zero taps
     const int L = n_taps, cc = (L - 1) / 2;
@@ -60,16 +61,16 @@ extern "C" int sgx_if_filter(sgx_ctx* c, const sgx_if* in, const int16_t* taps, 
     const int lp = ((L + e + 15) / 16) * 16;
     uint2* g = fir_tap_image(c, lp / 4);
     for (int j = 0; j < L; ++j) fir_pack_tap(g, j + e, taps[L - 1 - j]);
-    return fir_run(
-        c, in->n, lp / 4,
-        [&](unsigned blocks, sgx_if* r, const uint2* d_taps) {
-            fir_dot4_kernel<<<blocks, FIR_THREADS, 0, c->stream>>>(in->d, r->d, (unsigned long long)in->n, d_taps, lp, cp, shift);
-        },
-        &c->filter_kernel_ms, "record of %zu samples is beyond one launch of the filter", "filter kernel failed: %s", out);
+    const uint2* d_taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
+    SgxStage st(SGX_STAGE_FILTER, (unsigned)blocks, "filter kernel failed: %s", out, in->n);
+    st.up = {c->d_small->fir_taps, g, (size_t)(lp / 4) * sizeof(uint2)};
+    return sgx_stage_run(c, st, [&](sgx_if* r) {
+        fir_dot4_kernel<<<st.grid, FIR_THREADS, 0, c->stream>>>(in->d, r->d, (unsigned long long)in->n, d_taps, lp, cp, shift);
+    });
 }
 
 extern "C" int sgx_filter_timing(sgx_ctx* c, float* kernel_ms) {
     SGX_CHECK_ARG(c && kernel_ms);
-    *kernel_ms = c->filter_kernel_ms;
+    *kernel_ms = c->stage_ms[SGX_STAGE_FILTER];
     return SGX_OK;
 }

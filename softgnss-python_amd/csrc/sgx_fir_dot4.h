@@ -11,7 +11,7 @@
 // written out in each kernel: behind a helper the compiler packs the bytes before the branch and unpacks them again for
 // the byte stores, a different epilogue from the one both kernels have always had.
 #pragma once
-#include "sgx_internal.h"
+#include "sgx_stage.h"
 
 #define FIR_THREADS 256
 #define FIR_TILE (FIR_THREADS * 16)   // output bytes per workgroup
@@ -115,45 +115,10 @@ static inline void fir_pack_tap(uint2* g, int j, int h) {
     g[j >> 2].y |= ((unsigned)(lo & 0xFF)) << ((j & 3) * 8);
 }
 
-// The tap image the caller packs: the context's pinned staging area, zeroed over n_pairs (hi, lo) pairs
+// The tap image the caller packs: the context's pinned staging area, zeroed over n_pairs (hi, lo) pairs.  The stage's
+// upload (sgx_stage.h) takes it to c->d_small->fir_taps, where the kernel reads it.
 static inline uint2* fir_tap_image(sgx_ctx* c, int n_pairs) {
     uint2* g = reinterpret_cast<uint2*>(c->h_small->fir_taps);
     memset(g, 0, (size_t)n_pairs * sizeof(uint2));
     return g;
-}
-
-// The tail of an entry point: a new record of n bytes, the n_pairs packed tap pairs to the device, launch(blocks, record,
-// device taps) between two events on the context's stream, and the wait.  too_long: the refusal of a record beyond one
-// launch, a format with one %zu for n; failed: the message of a HIP failure, a format with one %s for HIP's text.
-template <typename Launch>
-static int fir_run(sgx_ctx* c, size_t n, int n_pairs, Launch launch, float* kernel_ms, const char* too_long,
-                   const char* failed, sgx_if** out) {
-    sgx_if* r = nullptr;
-    const int rc = sgx_if_alloc_internal(c, n, &r);
-    if (rc != SGX_OK) return rc;
-    uint2* d_taps = reinterpret_cast<uint2*>(c->d_small->fir_taps);
-    hipError_t err = hipMemcpyAsync(d_taps, c->h_small->fir_taps, (size_t)n_pairs * sizeof(uint2), hipMemcpyHostToDevice,
-                                    c->stream);
-    *kernel_ms = 0.0f;
-    const unsigned long long blocks = ((unsigned long long)n + FIR_TILE - 1) / FIR_TILE;
-    if (err == hipSuccess && blocks > 0x7FFFFFFFull) {
-        sgx_if_free(c, r);
-        sgx_set_error(too_long, n);
-        return SGX_E_ARG;
-    }
-    if (err == hipSuccess && blocks) {
-        hipEventRecord(c->ev[0], c->stream);
-        launch((unsigned)blocks, r, d_taps);
-        hipEventRecord(c->ev[1], c->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);   // (the staging area is free again on return)
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_if_free(c, r);
-        sgx_set_error(failed, hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    if (blocks) hipEventElapsedTime(kernel_ms, c->ev[0], c->ev[1]);
-    *out = r;
-    return SGX_OK;
 }

@@ -111,6 +111,11 @@ struct FftPlan {
 #define CD_COUNT_SLOTS 256
 #define CD_COUNT_STRIDE 16   // 64-bit words between two slots
 
+// The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
+// sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition
+enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
+                    SGX_STAGE_COND_APPLY, SGX_STAGE_SLOTS };
+
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
     size_t n = 0;
@@ -248,13 +253,15 @@ struct SgxSmall {
     int2 stage_bin_map[ACQ_COH_MAX_BINS];
     int trk_mag;                            // sgx_trk.hip: the record's magnitude bound
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
-    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter or sgx_if_from_iq call, which waits before it returns; both
+    // The record front-end stages: what sgx_stage_run (sgx_stage.h) copies up in front of a stage's kernel or down behind
+    // it.  Every stage waits before it returns, so one call owns a slot at a time; both.
+    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter or sgx_if_from_iq call
     alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
     // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass, and
-    // the quantiser's counters of outputs on +-127; both entry points wait before they return; both
+    // the quantiser's counters of outputs on +-127
     alignas(256) unsigned long long requant_part[RQ_STATS_BLOCKS * 4];
     alignas(256) unsigned requant_clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE];
-    // sgx_cond.hip: the apply kernel's counters; sgx_if_condition waits before it returns; both
+    // sgx_cond.hip: the apply kernel's counters
     alignas(256) unsigned long long cond_count[CD_COUNT_SLOTS * CD_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
@@ -360,15 +367,13 @@ struct sgx_ctx {
     std::atomic<bool> stage_busy{false};
     // HIP-event times of the last sgx_track_replay (sgx_replay.hip): the kernel, and upload + kernel + result copy
     float replay_kernel_ms = 0.0f, replay_device_ms = 0.0f;
-    float filter_kernel_ms = 0.0f;   // HIP-event time of the last sgx_if_filter's kernel (sgx_filter.hip)
-    float iq_kernel_ms = 0.0f;       // HIP-event time of the last sgx_if_from_iq's kernel (sgx_iq.hip)
-    // HIP-event times of the last sgx_requant_stats_of's and the last sgx_if_requantize's kernel (sgx_requant.hip)
-    float requant_stats_ms = 0.0f, requant_kernel_ms = 0.0f;
+    // HIP-event time of the kernel of the last call of each record front-end stage, 0 where that call had no work
+    // (sgx_stage.h: sgx_stage_run writes them, the four sgx_*_timing getters read them)
+    float stage_ms[SGX_STAGE_SLOTS] = {};
     // front-end conditioning (sgx_cond.hip): the per-block statistics and the plan as the kernels write and read them
-    // (grow-only), and the HIP-event times of the last sgx_cond_block_stats' and the last sgx_if_condition's kernel
+    // (grow-only)
     DevBuf<sgx_cond_stats> d_cond_stats;
     DevBuf<sgx_cond_entry> d_cond_plan;
-    float cond_stats_ms = 0.0f, cond_apply_ms = 0.0f;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

@@ -108,15 +108,16 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
     const int bad = fir_check_taps(taps, n_taps);
     if (bad != SGX_OK) return bad;
     SGX_CHECK_ARG(c && iq_bytes && out);
+    SGX_CHECK_ARG(iq_bytes->device == c->device);
     if (iq_bytes->n & 1) {
         sgx_set_error("bad argument: an I/Q record holds whole pairs, not %zu bytes", iq_bytes->n);
         return SGX_E_ARG;
     }
-    {
-        const int rq = sgx_if_require(iq_bytes, iq_bytes->n);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
+    int rc = sgx_stage_open(c, iq_bytes, iq_bytes->n);
+    if (rc != SGX_OK) return rc;
+    const unsigned long long blocks = ((unsigned long long)iq_bytes->n + FIR_TILE - 1) / FIR_TILE;
+    rc = sgx_stage_one_launch(blocks, "record of %zu bytes is beyond one launch of the I/Q converter", iq_bytes->n);
+    if (rc != SGX_OK) return rc;
 
     // g_X[j] = the tap of branch X at d = j - cp: h[cc - 2 d] for the even outputs, h[cc + 1 - 2 d] for the odd ones
     const int L = n_taps, cc = (L - 1) / 2;
@@ -136,19 +137,18 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
         }
         if (*end_step == 0) *lo_step = 0;   // a branch without a tap: no step
     }
-    return fir_run(
-        c, iq_bytes->n, 2 * lp / 4,
-        [&](unsigned blocks, sgx_if* r, const uint2* d_taps) {
-            iq_to_if_kernel<<<blocks, FIR_THREADS, 0, c->stream>>>(
-                iq_bytes->d, r->d, (unsigned long long)iq_bytes->n, d_taps, lp, cp, steps, shift,
-                (flags & SGX_IQ_OFFSET_BINARY) ? 0x80808080u : 0u, (flags & SGX_IQ_Q_FIRST) ? 1 : 0);
-        },
-        &c->iq_kernel_ms, "record of %zu bytes is beyond one launch of the I/Q converter", "I/Q conversion kernel failed: %s",
-        out);
+    const uint2* d_taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
+    SgxStage st(SGX_STAGE_IQ, (unsigned)blocks, "I/Q conversion kernel failed: %s", out, iq_bytes->n);
+    st.up = {c->d_small->fir_taps, g, (size_t)(2 * lp / 4) * sizeof(uint2)};
+    return sgx_stage_run(c, st, [&](sgx_if* r) {
+        iq_to_if_kernel<<<st.grid, FIR_THREADS, 0, c->stream>>>(
+            iq_bytes->d, r->d, (unsigned long long)iq_bytes->n, d_taps, lp, cp, steps, shift,
+            (flags & SGX_IQ_OFFSET_BINARY) ? 0x80808080u : 0u, (flags & SGX_IQ_Q_FIRST) ? 1 : 0);
+    });
 }
 
 extern "C" int sgx_iq_timing(sgx_ctx* c, float* kernel_ms) {
     SGX_CHECK_ARG(c && kernel_ms);
-    *kernel_ms = c->iq_kernel_ms;
+    *kernel_ms = c->stage_ms[SGX_STAGE_IQ];
     return SGX_OK;
 }

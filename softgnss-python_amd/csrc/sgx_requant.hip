@@ -20,7 +20,7 @@
 //                         over the workgroup, one integer atomic per workgroup into one of RQ_CLIP_SLOTS counters.
 #include <math.h>
 
-#include "sgx_internal.h"
+#include "sgx_stage.h"
 
 #define RQ_THREADS 256
 #define RQ_TILE (RQ_THREADS * 16)   // output bytes (= elements) per workgroup
@@ -269,8 +269,8 @@ extern "C" int sgx_requant_tile(int32_t* tile_bytes) {
 
 extern "C" int sgx_requant_timing(sgx_ctx* c, float* stats_ms, float* kernel_ms) {
     SGX_CHECK_ARG(c && stats_ms && kernel_ms);
-    *stats_ms = c->requant_stats_ms;
-    *kernel_ms = c->requant_kernel_ms;
+    *stats_ms = c->stage_ms[SGX_STAGE_REQUANT_STATS];
+    *kernel_ms = c->stage_ms[SGX_STAGE_REQUANT];
     return SGX_OK;
 }
 
@@ -313,32 +313,24 @@ extern "C" int sgx_requant_stats_of(sgx_ctx* c, const sgx_if* rec, int32_t data_
                       n_el);
         return SGX_E_ARG;
     }
-    {
-        const int rq = sgx_if_require(rec, (offset + count) * (size_t)w);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    c->requant_stats_ms = 0.0f;
+    int rc = sgx_stage_open(c, rec, (offset + count) * (size_t)w);
+    if (rc != SGX_OK) return rc;
+    c->stage_ms[SGX_STAGE_REQUANT_STATS] = 0.0f;
     memset(out, 0, sizeof(*out));
-    if (count == 0) return SGX_OK;
+    if (count == 0) return SGX_OK;   // (an empty window: nothing is queued, nothing to wait for)
     const unsigned long long b0 = (unsigned long long)offset * w, b1 = b0 + (unsigned long long)count * w;
     unsigned long long* d_part = c->d_small->requant_part;
     unsigned long long* h_part = c->h_small->requant_part;
-    hipEventRecord(c->ev[0], c->stream);
-    if (data_type == SGX_DT_INT16) {
-        requant_stats_kernel<SGX_DT_INT16><<<RQ_STATS_BLOCKS, RQ_THREADS, 0, c->stream>>>(rec->d, b0, b1, d_part);
-    } else {
-        requant_stats_kernel<SGX_DT_FLOAT32><<<RQ_STATS_BLOCKS, RQ_THREADS, 0, c->stream>>>(rec->d, b0, b1, d_part);
-    }
-    hipEventRecord(c->ev[1], c->stream);
-    hipError_t err = hipMemcpyAsync(h_part, d_part, sizeof(SgxSmall::requant_part), hipMemcpyDeviceToHost, c->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_set_error("requantiser statistics kernel failed: %s", hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    hipEventElapsedTime(&c->requant_stats_ms, c->ev[0], c->ev[1]);
+    SgxStage st(SGX_STAGE_REQUANT_STATS, RQ_STATS_BLOCKS, "requantiser statistics kernel failed: %s");
+    st.down = {h_part, d_part, sizeof(SgxSmall::requant_part)};
+    rc = sgx_stage_run(c, st, [&](sgx_if*) {
+        if (data_type == SGX_DT_INT16) {
+            requant_stats_kernel<SGX_DT_INT16><<<st.grid, RQ_THREADS, 0, c->stream>>>(rec->d, b0, b1, d_part);
+        } else {
+            requant_stats_kernel<SGX_DT_FLOAT32><<<st.grid, RQ_THREADS, 0, c->stream>>>(rec->d, b0, b1, d_part);
+        }
+    });
+    if (rc != SGX_OK) return rc;
     // the partials in workgroup order
     unsigned long long bad = 0, mx = 0;
     if (data_type == SGX_DT_INT16) {
@@ -388,51 +380,25 @@ extern "C" int sgx_if_requantize(sgx_ctx* c, const sgx_if* rec, int32_t data_typ
     SGX_CHECK_ARG(c && rec && out);
     SGX_CHECK_ARG(rec->device == c->device);
     if (rq_whole_elements(rec, w) != SGX_OK) return SGX_E_ARG;
-    {
-        const int rq = sgx_if_require(rec, rec->n);   // a record that is still streaming in
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
+    int rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
     const size_t n = rec->n / (size_t)w;
     const unsigned long long blocks = ((unsigned long long)n + RQ_TILE - 1) / RQ_TILE;
-    if (blocks > 0x7FFFFFFFull) {
-        sgx_set_error("bad argument: a record of %zu elements is beyond one launch of the requantiser", n);
-        return SGX_E_ARG;
-    }
-    sgx_if* r = nullptr;
-    const int rc = sgx_if_alloc_internal(c, n, &r);
+    rc = sgx_stage_one_launch(blocks, "bad argument: a record of %zu elements is beyond one launch of the requantiser", n);
     if (rc != SGX_OK) return rc;
-    c->requant_kernel_ms = 0.0f;
     unsigned* d_clip = c->d_small->requant_clip;
     unsigned* h_clip = c->h_small->requant_clip;
-    memset(h_clip, 0, sizeof(SgxSmall::requant_clip));
-    hipError_t err = hipSuccess;
-    if (blocks) {
-        const RqGain g = {mult, (1 << shift) >> 1, shift, scale};
-        err = hipMemsetAsync(d_clip, 0, sizeof(SgxSmall::requant_clip), c->stream);
-        hipEventRecord(c->ev[0], c->stream);
+    const RqGain g = {mult, (1 << shift) >> 1, shift, scale};
+    SgxStage st(SGX_STAGE_REQUANT, (unsigned)blocks, "requantiser kernel failed: %s", out, n);
+    st.count_into(h_clip, d_clip, sizeof(SgxSmall::requant_clip));
+    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         if (data_type == SGX_DT_INT16) {
-            requant_kernel<SGX_DT_INT16><<<(unsigned)blocks, RQ_THREADS, 0, c->stream>>>(rec->d, r->d, n, g, d_clip);
+            requant_kernel<SGX_DT_INT16><<<st.grid, RQ_THREADS, 0, c->stream>>>(rec->d, r->d, n, g, d_clip);
         } else {
-            requant_kernel<SGX_DT_FLOAT32><<<(unsigned)blocks, RQ_THREADS, 0, c->stream>>>(rec->d, r->d, n, g, d_clip);
+            requant_kernel<SGX_DT_FLOAT32><<<st.grid, RQ_THREADS, 0, c->stream>>>(rec->d, r->d, n, g, d_clip);
         }
-        hipEventRecord(c->ev[1], c->stream);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(h_clip, d_clip, sizeof(SgxSmall::requant_clip), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        sgx_if_free(c, r);
-        sgx_set_error("requantiser kernel failed: %s", hipGetErrorString(err));
-        return SGX_E_HIP;
-    }
-    if (blocks) hipEventElapsedTime(&c->requant_kernel_ms, c->ev[0], c->ev[1]);
-    if (n_clipped) {
-        int64_t total = 0;
-        for (int i = 0; i < RQ_CLIP_SLOTS * RQ_CLIP_STRIDE; ++i) total += (int64_t)h_clip[i];
-        *n_clipped = total;
-    }
-    *out = r;
+    });
+    if (rc != SGX_OK) return rc;
+    if (n_clipped) *n_clipped = sgx_sum_slots(h_clip, RQ_CLIP_SLOTS, RQ_CLIP_STRIDE);
     return SGX_OK;
 }
