@@ -10,8 +10,7 @@
 #include <vector>
 
 #include "sgx.h"
-
-void sgx_set_error(const char* fmt, ...);
+#include "sgx_check.h"
 
 namespace {
 

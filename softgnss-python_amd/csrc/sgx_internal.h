@@ -4,18 +4,17 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "sgx.h"
-
-#define SGX_VERSION_STR "sgx 0.1 (gfx950)"
-
-void sgx_set_error(const char* fmt, ...);
+#include "sgx_check.h"   // sgx_set_error, SGX_CHECK_ARG, SGX_VERSION_STR: all that the HIP-free host files need
 
 #define SGX_HIP(call)                                                                          \
     do {                                                                                       \
@@ -25,14 +24,6 @@ void sgx_set_error(const char* fmt, ...);
                           __LINE__);                                                           \
             return SGX_E_HIP;                                                                  \
         }                                                                                      \
-    } while (0)
-
-#define SGX_CHECK_ARG(cond)                                                 \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            sgx_set_error("bad argument: %s (%s:%d)", #cond, __FILE__, __LINE__); \
-            return SGX_E_ARG;                                               \
-        }                                                                   \
     } while (0)
 
 typedef double2 cplx;   // complex128 as (re, im)
@@ -132,10 +123,70 @@ struct sgx_if {
     hipStream_t copy_stream = nullptr;
     char load_err[256] = {0};
 };
+// sgx_record.cpp
 // Block until samples [0, end) of a (possibly still streaming) record are resident; returns the loader's status.
 int sgx_if_require(const sgx_if* r, size_t end);
-// A new record of n samples on the context's device (sgx_host.cpp), for the stages that write one
+// A new record of n samples on the context's device, for the stages that write one.  sgx_if_free is the one way out of it.
 int sgx_if_alloc_internal(sgx_ctx* c, size_t n, sgx_if** out);
+// One record allocation, streaming watermark and copy stream kept from the last sgx_if_free: a caller that opens a
+// record file per step (the reference's, initialize.py:466-506) would otherwise pay hipMalloc + hipFree of 1.4 GB and
+// a stream creation every time (milliseconds against a 50 ms step).  Every method locks; release() is the teardown.
+#define SGX_IF_PAD 256
+struct RecordSpare {
+    // The parked allocation where it fits a record of n samples (large enough and not absurdly larger), else null
+    int8_t* take(size_t n, size_t* cap_out) {
+        std::lock_guard<std::mutex> g(mu);
+        if (!d || cap < n + SGX_IF_PAD || cap > 2 * (n + SGX_IF_PAD) + (1u << 20)) return nullptr;
+        *cap_out = std::exchange(cap, 0);
+        return std::exchange(d, nullptr);
+    }
+    // Gives the parked allocation back to the device (it may be what is in the way of a hipMalloc); false: none was parked
+    bool drop() {
+        std::lock_guard<std::mutex> g(mu);
+        if (!d) return false;
+        hipFree(std::exchange(d, nullptr));
+        cap = 0;
+        return true;
+    }
+    unsigned long long* take_mark() {
+        std::lock_guard<std::mutex> g(mu);
+        return std::exchange(mark, nullptr);
+    }
+    hipStream_t take_stream() {
+        std::lock_guard<std::mutex> g(mu);
+        return std::exchange(stream, nullptr);
+    }
+    // What a freed record leaves: the larger allocation wins, the first watermark and the first stream are kept.  What is
+    // parked is taken out of *r.  SGX_IF_SPARE=0 parks no allocation, SGX_STREAM_PRIO (set) no stream.
+    void park(sgx_if* r) {
+        std::lock_guard<std::mutex> g(mu);
+        const char* sp = getenv("SGX_IF_SPARE");   // '0': nothing is parked, a freed record's memory goes back at once
+        if (r->d && r->cap > cap && !(sp && sp[0] == '0')) {
+            if (d) hipFree(d);
+            d = std::exchange(r->d, nullptr);
+            cap = r->cap;
+        }
+        if (r->d_mark && !mark) mark = std::exchange(r->d_mark, nullptr);
+        if (r->copy_stream && !stream && !getenv("SGX_STREAM_PRIO")) stream = std::exchange(r->copy_stream, nullptr);
+    }
+    // Device memory first, then the stream
+    void release() {
+        drop();
+        if (unsigned long long* m = take_mark()) hipFree(m);
+        if (hipStream_t s = take_stream()) hipStreamDestroy(s);
+    }
+    RecordSpare() = default;
+    RecordSpare(const RecordSpare&) = delete;
+    RecordSpare& operator=(const RecordSpare&) = delete;
+    ~RecordSpare() { release(); }
+
+private:
+    std::mutex mu;
+    int8_t* d = nullptr;
+    size_t cap = 0;
+    unsigned long long* mark = nullptr;
+    hipStream_t stream = nullptr;
+};
 // Tracking (sgx_trk.hip).  kind: SGX_DT_*.  int8 / uint8 / int16 run the typed kernels (sgx_trk2 / sgx_trk3 / sgx_trk_tp);
 // every other type - and int16 / uint8 at sampling rates below 16 x the chip rate - the per-sample kernel of sgx_trk_any.hip.
 // skip_bytes: Settings.skipNumberOfBytes, or what stands in for it (sgx_trk_f32.hip tracks a narrowed copy of a window).
@@ -149,7 +200,6 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
                       double* out, int32_t* ms_done);
 int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
                       double* out, int32_t* ms_done);
-#define SGX_IF_PAD 256
 
 // ---- acquisition (sgx_acq.hip): the limits and the small structs its kernels hand to each other and to the host ----
 #define ACQ_MAX_BINS 128          // Doppler bins of the 1-ms search
@@ -354,14 +404,7 @@ struct sgx_ctx {
     // tracking
     DevBuf<double> d_trk_out;    // the series of a call whose result buffer is pageable
     DevBuf<char> d_trk_aux;      // per-call device state of sgx_track (channels, done, exchange, err, profile)
-    // One record allocation, streaming watermark and copy stream kept from the last sgx_if_free: a caller that opens a
-    // record file per step (the reference's, initialize.py:466-506) would otherwise pay hipMalloc + hipFree of 1.4 GB and
-    // a stream creation every time (milliseconds against a 50 ms step).
-    int8_t* spare_d = nullptr;
-    size_t spare_cap = 0;
-    unsigned long long* spare_mark = nullptr;
-    hipStream_t spare_copy_stream = nullptr;
-    std::mutex spare_mu;
+    RecordSpare spare;           // what the last freed record left for the next one
     // pinned staging buffers of the file streamer, kept between calls (pinning 64 MiB costs ~15 ms)
     void* stage[2] = {nullptr, nullptr};
     std::atomic<bool> stage_busy{false};
@@ -389,6 +432,7 @@ int sgx_look_wait(hipStream_t st, const unsigned long long* word, unsigned long 
 // granted (returned) only if they fit next to what is already running, else 0.
 int sgx_cu_reserve(int device, int cus_total, int want);
 void sgx_cu_release(int device, int n);
+// sgx_core.cpp
 int sgx_host_ca_code(int prn0, int8_t* out /*1023*/);
 int64_t sgx_host_samples_per_code(const sgx_settings* s);
 
@@ -495,7 +539,7 @@ int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes
 // Wait for a deferred acquisition and decode it (the tail of the eager call); clears c->acq_pending.
 int sgx_acquire_finish(sgx_ctx* c, const AcqOut& out);
 
-// sgx_host.cpp: the RCCL communicator of a context (librccl.so by dlopen)
+// sgx_comm.cpp: the RCCL communicator of a context (librccl.so by dlopen)
 struct sgx_comm {
     sgx_ctx* ctx;
     void* comm;

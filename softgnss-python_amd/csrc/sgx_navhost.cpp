@@ -10,16 +10,7 @@
 #include <vector>
 
 #include "sgx.h"
-
-void sgx_set_error(const char* fmt, ...);
-
-#define SGX_CHECK_ARG(cond)                                                       \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            sgx_set_error("bad argument: %s (%s:%d)", #cond, __FILE__, __LINE__); \
-            return SGX_E_ARG;                                                     \
-        }                                                                         \
-    } while (0)
+#include "sgx_check.h"
 
 // numpy's reduction order for reshape(20, -1, order='F').sum(0): the 20 contiguous values of a column go through
 // the unrolled pairwise sum (8 accumulators over two rounds, tree combine, then the last 4 in sequence)

@@ -1,6 +1,6 @@
 // Multi-correlator replay of tracked channels (include/sgx.h: sgx_track_replay; the contract in numpy: tests/replay_spec.py).
 //
-// A tracked channel's blocks are on record: sgx_replay_state (sgx_host.cpp) rebuilds, per block, its start byte, length,
+// A tracked channel's blocks are on record: sgx_replay_state (sgx_core.cpp) rebuilds, per block, its start byte, length,
 // code and carrier remainders and rates from the series sgx_track_ex wrote.  Nothing chains the blocks any more, so ONE
 // launch covers every (channel, block): workgroup b = channel * ms + block, 256 threads, thread t takes the samples
 // n = t, t + 256, ... of its block (a wave reads 64 consecutive samples per load).

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // (__forceinline__; a host-only file such as sgx_core.cpp has not included it)
 #define SGX_HD __host__ __device__ __forceinline__
 #else
 #define SGX_HD static inline

@@ -1,5 +1,5 @@
 // The fn -> call table of the evaluators of csrc/sgx_trk_math.h (include/sgx.h: sgx_trk_math_eval, sgx_trk_math_eval_batch,
-// sgx_trk_math_eval_device).  ONE function, compiled for the host by sgx_host.cpp and for the device by
+// sgx_trk_math_eval_device).  ONE function, compiled for the host by sgx_core.cpp and for the device by
 // sgx_trk_math_dev.hip: both evaluate literally this source, each with its own seeds, libm and code generator.
 // Test support only: no tracking kernel includes this file.
 #pragma once

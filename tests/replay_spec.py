@@ -1,5 +1,5 @@
 """numpy restatement of the multi-correlator replay (include/sgx.h, sgx_replay_state / sgx_track_replay): the contract the
-host recurrence of csrc/sgx_host.cpp and the HIP kernel of csrc/sgx_replay.hip are tested against.  Test infrastructure
+host recurrence of csrc/sgx_core.cpp and the HIP kernel of csrc/sgx_replay.hip are tested against.  Test infrastructure
 only; the package never imports it.
 
 A tracked channel has, per block k, the rows absoluteSample[k], codeFreq[k], carrFreq[k] of its tracking result.  Block

@@ -585,7 +585,7 @@ def test_second_front_end_golden():
 
 
 def test_streaming_file_ingest_matches_file_bytes():
-    """sgx_if_upload_file: several 32 MiB chunks, an unaligned offset, a short file."""
+    """sgx_if_upload_file: several 16 MiB chunks, an unaligned offset, a short file."""
     m, s, ctx = _ctx()
     rng = np.random.default_rng(5)
     data = rng.integers(-128, 128, size=(32 << 20) * 2 + 12345, dtype=np.int8)
