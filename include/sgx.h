@@ -651,6 +651,50 @@ int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type, int32_t l
 int sgx_cond_timing(sgx_ctx* c, float* stats_ms, float* apply_ms);
 int sgx_cond_tile(int32_t* tile_frames);
 
+/* ---- 1-, 2- and 4-bit packed records through an unpacker (no reference counterpart; first of all front-end stages, ahead
+ * of sgx_if_from_iq and sgx_if_filter) ----------------------------------------------------------------------------------------
+ * Opt-in.  A resident record holding the raw BYTES of a packed file, N bytes B[0 .. N) of b-bit fields, b = bits in
+ * {1, 2, 4}, comes out as a NEW int8 record, one byte per selected field.  tests/unpack_spec.py restates all of it in numpy.
+ *
+ * Field j, j = 0 .. 8N/b - 1, lies in byte j b / 8 at position p = j mod (8 / b); its code is
+ *   (B >> (8 - b (p + 1))) & (2^b - 1)   first field in the high bits, or with SGX_UNPACK_LSB_FIRST
+ *   (B >> (b p)) & (2^b - 1)             first field in the low bits.
+ * A frame is `frame` = F consecutive fields, F in {1, 2, 4, 8, 16} (a frame never straddles a byte partially); 8N/b must be a
+ * multiple of F.  Of every frame the stage takes `take` fields from field `first` on, take >= 1, first >= 0,
+ * first + take <= F:
+ *   n_out = (8N / b / F) take,   out[q take + t] = table[code(q F + first + t)]
+ * A real or an interleaved I/Q file is F = 1 (the converter sorts I and Q out); one of four interleaved streams is F = 4,
+ * first = s, take = 1; the second antenna of a two-antenna I/Q file F = 4, first = 2, take = 2.  table holds 2^b int8
+ * values, any mapping.  code_counts (16 int64; may be NULL) receives the exact count of each code among the selected fields,
+ * entries 2^b and above 0: the histogram of the ADC's levels.
+ * The whole record is unpacked on the context's stream (a record that is still streaming in is waited for, as sgx_if_wait
+ * to its full length); the input is left alone; *out is an ordinary record (sgx_if_free); N = 0 gives an empty record and
+ * launches nothing.
+ *
+ * sgx_unpack_table: the table of the three usual encodings as symmetric odd levels times one integer scale,
+ * table[c] = level(c) (peak / (2^b - 1)) with an integer (floor) division, peak in 2^b - 1 .. 127; exact host code, needs
+ * no GPU.
+ *   SGX_UNPACK_SIGN_MAGNITUDE   s = c >> (b - 1), mu = c & (2^(b-1) - 1): level (1 - 2 s)(2 mu + 1)
+ *   SGX_UNPACK_OFFSET_BINARY    level 2 c - (2^b - 1)
+ *   SGX_UNPACK_TWOS_COMPLEMENT  k = c, or c - 2^b for c >= 2^(b-1): level 2 k + 1
+ * 2 bits, sign/magnitude, peak 48: {16, 48, -16, -48}.  A peak of 63 or below keeps the sum of magnitudes of every
+ * 2 048-sample window below the bound at which tracking leaves its fastest kernel.
+ * sgx_unpack_timing: HIP-event time of the last sgx_if_unpack's kernel on this context.
+ * sgx_unpack_tile: the output bytes one workgroup of the kernel makes (where its tile seams lie).
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: bits other than 1, 2 or 4, an unknown flag
+ * or encoding, frame outside the five values, take < 1, first < 0 or first + take > frame, fields that do not fill whole
+ * frames, peak out of range, a NULL record, table or out, a record that lies on another device than the context's, a record
+ * beyond one launch. */
+#define SGX_UNPACK_LSB_FIRST 1
+#define SGX_UNPACK_SIGN_MAGNITUDE 0
+#define SGX_UNPACK_OFFSET_BINARY 1
+#define SGX_UNPACK_TWOS_COMPLEMENT 2
+int sgx_unpack_table(int32_t bits, int32_t encoding, int32_t peak, int8_t* table);
+int sgx_if_unpack(sgx_ctx* c, const sgx_if* rec, int32_t bits, int32_t flags, int32_t frame, int32_t first, int32_t take,
+                  const int8_t* table, sgx_if** out, int64_t* code_counts);
+int sgx_unpack_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_unpack_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -187,6 +187,10 @@ _PROTOS = {
                                    C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sgx_cond_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sgx_cond_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_unpack_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
+    "sgx_if_unpack": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P), _P]),
+    "sgx_unpack_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_unpack_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -585,6 +589,27 @@ def cond_tile():
     return _tile("sgx_cond_tile")
 
 
+UNPACK_LSB_FIRST = 1
+UNPACK_ENCODINGS = {"sign-magnitude": 0, "offset-binary": 1, "twos-complement": 2}
+
+
+def unpack_table(bits, encoding="sign-magnitude", peak=48):
+    """int8[2^bits]: the level of every code of a packed record in one of the three usual encodings ('sign-magnitude',
+    'offset-binary', 'twos-complement', or the library's number), symmetric odd levels times peak // (2^bits - 1)
+    (sgx_unpack_table; exact host code, needs no GPU)."""
+    enc = UNPACK_ENCODINGS.get(encoding, encoding) if isinstance(encoding, str) else encoding
+    if isinstance(enc, str):
+        raise ValueError("the encoding of a packed record is one of %s, not %r" % (", ".join(sorted(UNPACK_ENCODINGS)), encoding))
+    table = np.zeros(16, dtype=np.int8)
+    check(lib().sgx_unpack_table(int(bits), int(enc), int(peak), _ptr(table)))
+    return table[:1 << int(bits)].copy()
+
+
+def unpack_tile():
+    """Output bytes one workgroup of the unpacker makes: its tile seams lie at the multiples."""
+    return _tile("sgx_unpack_tile")
+
+
 def _int16_taps(taps):
     a = np.asarray(taps)
     if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
@@ -974,6 +999,33 @@ class Context(object):
     def cond_timing(self):
         """(statistics kernel ms, apply kernel ms) of the last cond_stats and the last condition on this context."""
         return self._timing("sgx_cond_timing", 2)
+
+    def unpack(self, rec, bits, table, lsb_first=False, frame=1, first=0, take=1):
+        """A new int8 record, one byte per selected field of `rec`, the raw bytes of a file of `bits`-bit samples (1, 2 or
+        4) packed first field in the high bits (lsb_first: in the low bits), through `table` (2^bits int8 values, one per
+        code; unpack_table makes the usual ones) (sgx_if_unpack).  Of every frame of `frame` fields (1, 2, 4, 8 or 16) the
+        `take` fields from field `first` on are kept.  The exact count of each code among them is left in the new record's
+        `code_counts` (int64[2^bits])."""
+        b = int(bits)
+        tab = np.zeros(16, dtype=np.int8)
+        if b in (1, 2, 4):                         # (any other width is the library's to refuse)
+            a = np.asarray(table)
+            if a.ndim != 1 or a.size != 1 << b or a.dtype.kind not in "iu" or a.min() < -128 or a.max() > 127:
+                raise ValueError("the table of a %d-bit record holds %d integers that fit int8" % (b, 1 << b))
+            tab[:a.size] = a
+        counts = np.zeros(16, dtype=np.int64)
+        h = _P()
+        check(lib().sgx_if_unpack(self._h, rec._h, b, UNPACK_LSB_FIRST if lsb_first else 0, int(frame), int(first),
+                                  int(take), _ptr(tab), C.byref(h), _ptr(counts)))
+        ln = C.c_size_t(0)
+        check(lib().sgx_if_length(h, C.byref(ln)))
+        out = Record(self, h, int(ln.value))
+        out.code_counts = counts[:1 << b].copy()
+        return out
+
+    def unpack_timing(self):
+        """Kernel ms of the last unpack on this context, from HIP events on its stream."""
+        return self._timing("sgx_unpack_timing", 1)[0]
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

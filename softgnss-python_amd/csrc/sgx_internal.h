@@ -102,10 +102,15 @@ struct FftPlan {
 #define CD_COUNT_SLOTS 256
 #define CD_COUNT_STRIDE 16   // 64-bit words between two slots
 
+// sgx_unpack.hip: the slots the unpacker spreads its per-workgroup code counts over; a slot is one 128-byte line that holds
+// the 16 counters
+#define UP_COUNT_SLOTS 256
+#define UP_COUNT_STRIDE 16   // 64-bit words between two slots
+
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
-// sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition
+// sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
-                    SGX_STAGE_COND_APPLY, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -313,6 +318,8 @@ struct SgxSmall {
     alignas(256) unsigned requant_clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE];
     // sgx_cond.hip: the apply kernel's counters
     alignas(256) unsigned long long cond_count[CD_COUNT_SLOTS * CD_COUNT_STRIDE];
+    // sgx_unpack.hip: the unpacker's code counters
+    alignas(256) unsigned long long unpack_count[UP_COUNT_SLOTS * UP_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");

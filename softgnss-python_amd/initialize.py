@@ -7,6 +7,7 @@ import contextlib
 import copy
 import ctypes as C
 import datetime
+import os
 
 import numpy as np
 
@@ -133,6 +134,18 @@ _COND_DEFAULTS = (
     ("condTargetRms", 12.0),             # rms of the int8 record it makes, LSB, in (0, 127]
 )
 
+# 1-, 2- and 4-bit packed records (Settings.unpackRecord; INTEGRATION.md, "Packed records"): the file is unpacked to one int8
+# sample per selected field on the GPU, first of all stages
+_PACK_DEFAULTS = (
+    ("packedBits", 0),                   # bits per sample of the file: 1, 2 or 4; 0: the stage is off
+    ("packedEncoding", 'sign-magnitude'),   # or 'offset-binary', 'twos-complement': what a code means
+    ("packedLsbFirst", False),           # the first sample of a byte lies in its low bits
+    ("packedFrame", 1),                  # F: fields per frame (1, 2, 4, 8 or 16) of a file that interleaves several streams
+    ("packedFirst", 0),                  # the field of a frame the selection starts at
+    ("packedPeak", 48),                  # the largest level of the int8 record it makes, LSB, in 2^bits - 1 .. 127
+    ("packedTable", None),               # an explicit sequence of 2^bits int8 levels, one per code: overrides encoding and peak
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -141,7 +154,8 @@ class Settings(object):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS + _COND_DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS + _COND_DEFAULTS \
+                + _PACK_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -294,10 +308,89 @@ class Settings(object):
         c = float(self.condBlankFactor)
         return w, 2 if self.iqRecord else 1, min(16384, max(256, block)), int(np.rint(16.0 * c * c))
 
+    def _pack_format(self):
+        """(bits, lsb_first, frame, first, take, table) of the unpacker for these settings.  take: a frame of several
+        fields (packedFrame > 1) gives its I/Q pair with iqRecord, else one field; with packedFrame = 1 every field is
+        taken (I and Q simply alternate, the converter sorts them out)."""
+        b = int(self.packedBits)
+        if b not in (1, 2, 4):
+            raise ValueError("Settings.packedBits = %r: packed records hold 1-, 2- or 4-bit samples (0: not packed)"
+                             % (self.packedBits,))
+        if self.iqRequantize:
+            raise ValueError("Settings.packedBits with Settings.iqRequantize: the requantiser reads int16 and float32 "
+                             "files, a packed file is neither")
+        if self.frontEndConditioning:
+            raise ValueError("Settings.packedBits with Settings.frontEndConditioning: the front end's own AGC has set the "
+                             "levels of a packed file; conditioning it is out of scope")
+        if np.dtype(self.dataType) != np.dtype(np.int8):
+            raise ValueError("Settings.packedBits makes an int8 record of the file: Settings.dataType stays 'int8', not %r"
+                             % (self.dataType,))
+        F, first = int(self.packedFrame), int(self.packedFirst)
+        if F not in (1, 2, 4, 8, 16):
+            raise ValueError("Settings.packedFrame = %r: a frame holds 1, 2, 4, 8 or 16 fields" % (self.packedFrame,))
+        take = 2 if (self.iqRecord and F > 1) else 1
+        if first < 0 or first + take > F:
+            raise ValueError("Settings.packedFirst = %d: %d field%s from there on do not lie inside a frame of %d"
+                             % (first, take, "s" if take > 1 else "", F))
+        if self.packedTable is not None:
+            t = np.asarray(self.packedTable)
+            if t.ndim != 1 or t.size != 1 << b or t.dtype.kind not in "iu" or t.min() < -128 or t.max() > 127:
+                raise ValueError("Settings.packedTable holds 2^packedBits = %d integers that fit int8" % (1 << b))
+            table = t.astype(np.int8)
+        else:
+            if self.packedEncoding not in _native.UNPACK_ENCODINGS:
+                raise ValueError("Settings.packedEncoding = %r is none of %s"
+                                 % (self.packedEncoding, ", ".join(sorted(_native.UNPACK_ENCODINGS))))
+            peak = int(self.packedPeak)
+            if not ((1 << b) - 1 <= peak <= 127):
+                raise ValueError("Settings.packedPeak = %r lies outside %d .. 127" % (self.packedPeak, (1 << b) - 1))
+            table = _native.unpack_table(b, self.packedEncoding, peak)
+        return b, bool(self.packedLsbFirst), F, first, take, table
+
+    def _pack_units(self):
+        """(bytes of the file, samples of the unpacked record they become): the smallest run of whole bytes that holds
+        whole frames, max(1, F b / 8) bytes."""
+        b, _, F, _, take, _ = self._pack_format()
+        unit = max(1, F * b // 8)
+        return unit, unit * 8 * take // (b * F)
+
+    def _unpacked_settings(self):
+        """The settings the UNPACKED record is read under: a copy with the stage off, int8, and skipNumberOfBytes turned
+        from a byte of the packed file (on a frame boundary) into the sample it becomes, skip 8 take / (b F)."""
+        unit, samples = self._pack_units()
+        skip = int(self.skipNumberOfBytes)
+        if skip % unit:
+            raise ValueError("skipNumberOfBytes = %d splits a frame of the packed file: it must be a multiple of %d"
+                             % (skip, unit))
+        un = copy.copy(self)
+        un.packedBits = 0
+        un.skipNumberOfBytes = skip // unit * samples
+        return un
+
+    def unpackRecord(self, record):
+        """A resident record holding the raw bytes of a packed file (a _native.Record; packedBits, packedLsbFirst,
+        packedFrame, packedFirst say how, packedEncoding and packedPeak, or packedTable, what a code means) as a NEW int8
+        record, one sample per selected field (Context.unpack).  Returns (record8, info) and keeps info as
+        self.lastUnpack: samples, bits, table (int8 per code), code_counts (int64 per code, exact) and shares (each code's
+        share of the samples - the histogram of the ADC's levels: of a 2-bit front end whose AGC works about one third
+        lies in the outer levels).  The caller frees both."""
+        if not self.packedBits:
+            raise ValueError("Settings.packedBits is 0: the record is not packed")
+        b, lsb, F, first, take, table = self._pack_format()
+        rec8 = record.ctx.unpack(record, b, table, lsb_first=lsb, frame=F, first=first, take=take)
+        counts = rec8.code_counts
+        info = dict(samples=len(rec8), bits=b, table=table.copy(), code_counts=counts.copy(),
+                    shares=counts / float(len(rec8)) if len(rec8) else np.zeros(counts.size))
+        self.lastUnpack = info
+        return rec8, info
+
     def _prepared_settings(self):
         """The settings the PREPARED record is read under: realEquivalent(), with skipNumberOfBytes turned from a byte of a
         file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w.  A real record
-        that goes through the conditioning stage comes out as int8 in the same way."""
+        that goes through the conditioning stage comes out as int8 in the same way; a packed record (packedBits) is read
+        as the int8 record the unpacker makes of it (_unpacked_settings), whatever follows."""
+        if self.packedBits:
+            return self._unpacked_settings()._prepared_settings()
         if not self.iqRecord:
             if not self.frontEndConditioning:
                 return self
@@ -401,7 +494,9 @@ class Settings(object):
     @contextlib.contextmanager
     def _prepared_record(self, name, offset, count, mitigate_at=None, verbose=False):
         """Samples [offset, offset + count) of the prepared record of a record file, uploaded once and prepared on the
-        GPU, for the length of the block: with frontEndConditioning brought to int8 block by block (conditionRecord), first
+        GPU, for the length of the block: with packedBits unpacked to int8 (unpackRecord), first of all - offset must then
+        fall on a frame boundary of the file, and count is rounded up to whole frames; with
+        frontEndConditioning brought to int8 block by block (conditionRecord), first
         of all; with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
         with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation) cleared
         of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the real
@@ -413,8 +508,27 @@ class Settings(object):
         say = print if verbose else (lambda *args: None)
         real = self._prepared_settings()
         w = self._iq_width() if self.iqRecord else (self._cond_format()[0] if self.frontEndConditioning else 1)
-        rec = engine.get_context(real, None).upload_file(name, w * offset, w * count)
+        if self.packedBits:
+            unit, samples = self._pack_units()
+            if offset % samples:
+                raise ValueError("sample %d of the unpacked record does not start a frame of the packed file: it must be a "
+                                 "multiple of %d" % (offset, samples))
+            units = -(-count // samples)                                  # (with iqRecord `samples` is even: whole pairs)
+            file_off = offset // samples * unit
+            whole = max(0, os.path.getsize(name) - file_off) // unit      # (a file that ends inside a frame: the frame is left)
+            rec = engine.get_context(real, None).upload_file(name, file_off, min(units, whole) * unit)
+        else:
+            rec = engine.get_context(real, None).upload_file(name, w * offset, w * count)
         try:
+            if self.packedBits:
+                say('   Unpacking %d-bit samples to int8...' % int(self.packedBits))
+                raw, rec = rec, None
+                try:
+                    rec, info = self.unpackRecord(raw)
+                finally:
+                    raw.free()
+                say('   %d samples; levels %s' % (info["samples"], ", ".join(
+                    "%+d: %.2f %%" % (int(lv), 100.0 * sh) for lv, sh in sorted(zip(info["table"], info["shares"])))))
             if self.frontEndConditioning:
                 say('   Conditioning %s samples block by block...' % np.dtype(self.dataType).name)
                 raw, rec = rec, None
@@ -486,7 +600,8 @@ class Settings(object):
         """postProcessing()'s acquire -> preRun -> track on a record that _prepared_record uploads once and prepares on the
         GPU; both stages read the prepared record where it lies.  The results carry _prepared_settings(): positions
         (codePhase, absoluteSample, skipNumberOfBytes) are samples of the prepared record, which are bytes of an 8-bit file
-        and file byte / w of a file of w-byte components (int16: w = 2, float32: w = 4, with iqRequantize)."""
+        and file byte / w of a file of w-byte components (int16: w = 2, float32: w = 4, with iqRequantize); of a packed
+        file (packedBits = b, frames of F fields of which `take` are kept) sample n is byte n b F / (8 take)."""
         from .record import DeviceFile, DeviceSignal
         real = self._prepared_settings()
         n = real.samplesPerCode
@@ -516,7 +631,7 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning:
+        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning or self.packedBits:
             acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None

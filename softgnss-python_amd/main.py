@@ -5,6 +5,8 @@
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]]
                                                   [--iq[=qi]] [--dtype int8] [--iq-requantize[=RMS]]
                                                   [--condition[=BLANK_FACTOR]]
+                                                  [--packed BITS --packed-encoding ENC --packed-lsb-first
+                                                   --packed-frame F[:FIRST] --packed-peak PEAK]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -22,7 +24,13 @@ results are samples of the converted record, file byte / 2 or / 4.  --condition 
 with --iq) first conditions the file block by block on the GPU: per 100 us it removes the DC of each rail, sets the gain
 that puts the rms at 12 LSB (a time-varying AGC) and zeroes the frames that stand 4 x (or --condition=BLANK_FACTOR, 1 .. 16;
 0: no blanking) above the rms, and prints the span of the gain and the shares of blanked frames and clipped samples; it
-stands where --iq-requantize does, so not both; an int16 file is then read as int8, positions are file byte / 2."""
+stands where --iq-requantize does, so not both; an int16 file is then read as int8, positions are file byte / 2.
+--packed BITS (1, 2 or 4; real or with --iq) reads a file of packed samples: the GPU unpacks it first of all into one int8
+sample per field, through the levels of --packed-encoding (sign-magnitude, offset-binary or twos-complement) scaled to
+--packed-peak (48), the first sample of a byte in its high bits (--packed-lsb-first: in its low bits), and prints the share
+of the samples on each level.  --packed-frame F[:FIRST] is for files that interleave several streams: of every F fields (2,
+4, 8 or 16) the one at FIRST is kept (with --iq the pair from FIRST on).  --skip stays a byte of the file, on a frame
+boundary; positions in the results are samples of the unpacked record.  Not with --iq-requantize or --condition."""
 from __future__ import print_function
 
 import argparse
@@ -33,7 +41,8 @@ from . import initialize
 
 
 def probe_iq(settings):
-    """probeData() of an I/Q file: the first 10 code periods converted on the GPU, probed as the real record they become."""
+    """probeData() of an I/Q or a packed file: the first 10 code periods prepared on the GPU, probed as the real int8
+    record they become."""
     from .record import DeviceSignal
     real = settings._prepared_settings()
     with settings._prepared_record(settings.fileName, int(real.skipNumberOfBytes), 10 * real.samplesPerCode) as rec:
@@ -73,7 +82,41 @@ def main(argv=None):
     ap.add_argument("--condition", nargs="?", type=float, const=-1.0, default=None, metavar="BLANK_FACTOR",
                     help="condition the file block by block on the GPU before anything else: DC removal, AGC and pulse "
                          "blanking at BLANK_FACTOR x the rms (default: Settings.condBlankFactor, 4; 0: no blanking)")
+    ap.add_argument("--packed", type=int, default=None, choices=(1, 2, 4), metavar="BITS",
+                    help="the file holds packed BITS-bit samples (1, 2 or 4): unpack it to int8 on the GPU before anything "
+                         "else")
+    ap.add_argument("--packed-encoding", default=None, choices=("sign-magnitude", "offset-binary", "twos-complement"),
+                    help="with --packed: what a code means (default: Settings.packedEncoding, sign-magnitude)")
+    ap.add_argument("--packed-lsb-first", action="store_true",
+                    help="with --packed: the first sample of a byte lies in its low bits")
+    ap.add_argument("--packed-frame", default=None, metavar="F[:FIRST]",
+                    help="with --packed: the file interleaves streams in frames of F fields (1, 2, 4, 8 or 16); keep the "
+                         "field at FIRST (default 0; with --iq the I/Q pair from there on)")
+    ap.add_argument("--packed-peak", type=int, default=None, metavar="PEAK",
+                    help="with --packed: the largest level of the int8 record (default: Settings.packedPeak, 48)")
     a = ap.parse_args(argv)
+    frame = first = None
+    if a.packed is None:
+        if a.packed_encoding is not None or a.packed_lsb_first or a.packed_frame is not None or a.packed_peak is not None:
+            ap.error("--packed-encoding, --packed-lsb-first, --packed-frame and --packed-peak describe a packed file: "
+                     "they need --packed")
+    else:
+        if a.iq_requantize is not None or a.condition is not None:
+            ap.error("--packed makes the int8 record itself: not with --iq-requantize or --condition")
+        if a.dtype not in (None, "int8"):
+            ap.error("--packed makes an int8 record of the file: --dtype stays int8")
+        if a.packed_frame is not None:
+            try:
+                parts = [int(x) for x in a.packed_frame.split(":")]
+                frame, first = parts[0], (parts[1] if len(parts) > 1 else 0)
+                ok = len(parts) <= 2 and frame in (1, 2, 4, 8, 16) and \
+                    0 <= first <= frame - (2 if a.iq is not None and frame > 1 else 1)
+            except ValueError:
+                ok = False
+            if not ok:
+                ap.error("--packed-frame takes F[:FIRST] with F one of 1, 2, 4, 8, 16 and the kept fields inside the frame")
+        if a.packed_peak is not None and not ((1 << a.packed) - 1 <= a.packed_peak <= 127):
+            ap.error("--packed-peak takes the largest level in LSB, %d .. 127" % ((1 << a.packed) - 1))
     if a.condition is not None and a.iq_requantize is not None:
         ap.error("--condition stands where --iq-requantize does: not both")
     if a.condition is not None and not (a.condition in (-1.0, 0.0) or 1.0 <= a.condition <= 16.0):
@@ -106,6 +149,9 @@ def main(argv=None):
                       ("iqTargetRms", a.iq_requantize if a.iq_requantize is not None and a.iq_requantize > 0 else None),
                       ("frontEndConditioning", True if a.condition is not None else None),
                       ("condBlankFactor", a.condition if a.condition is not None and a.condition >= 0 else None),
+                      ("packedBits", a.packed), ("packedEncoding", a.packed_encoding),
+                      ("packedLsbFirst", True if a.packed_lsb_first else None), ("packedFrame", frame),
+                      ("packedFirst", first), ("packedPeak", a.packed_peak),
                       ("interferenceMitigation", True if a.notch is not None else None),
                       ("notchThresholdDb", a.notch if a.notch is not None and a.notch >= 0 else None)):
         if val is not None:
@@ -116,7 +162,7 @@ def main(argv=None):
               % (settings.samplingFreq / 1e6, settings.IF / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
     if not a.no_probe:
         print('Probing data "%s"...' % settings.fileName)
-        p = probe_iq(settings) if settings.iqRecord else settings.probeData()
+        p = probe_iq(settings) if settings.iqRecord or settings.packedBits else settings.probeData()
         if p is not None:
             k = int(np.argmax(p["Pxx"]))
             print('  %d Welch segments, spectral peak at %.3f MHz, samples within [%d, %d]'
