@@ -695,6 +695,60 @@ int sgx_if_unpack(sgx_ctx* c, const sgx_if* rec, int32_t bits, int32_t flags, in
 int sgx_unpack_timing(sgx_ctx* c, float* kernel_ms);
 int sgx_unpack_tile(int32_t* tile_bytes);
 
+/* ---- band selection and integer decimation ahead of acquisition (no reference counterpart; behind the unpacker, the
+ * conditioning stage and the requantiser, in front of sgx_if_from_iq and sgx_if_filter) -----------------------------------
+ * Opt-in.  A resident int8 record of N bytes goes through an integer FIR that selects a band and comes out as a NEW int8
+ * record at 1 / D of the rate, D = 2 .. 16.  Every later stage then runs at the lower rate.  tests/decim_spec.py restates
+ * all of it in numpy.
+ *
+ * sgx_if_decimate: n_taps = L odd, 1 .. SGX_DECIM_MAX_TAPS, c = (L - 1) / 2, x = 0 outside the record, rnd = shift ?
+ * 2^(shift-1) : 0, q(a) = clip((a + rnd) >> shift, -127, 127) with an arithmetic (floor) shift.
+ *   lanes = 1  a real record x[0 .. N); taps int16 h[L]:
+ *                y[m] = q(sum_k h[k] x[m D + c - k]),  m = 0 .. ceil(N / D) - 1
+ *   lanes = 2  interleaved I/Q, N even, z[n] = b[2n] + j b[2n+1]; taps COMPLEX, int16 h[2 L], re and im interleaved:
+ *                w[m] = sum_k h[k] z[m D + c - k],  output bytes q(Re w[m]), q(Im w[m]),  m = 0 .. ceil(N/2 / D) - 1
+ *              Complex taps select a band that is not centred on zero.
+ * SGX_DECIM_OFFSET_BINARY first turns every input byte into byte - 128 (XOR 0x80 read as int8).  There is no Q-first flag:
+ * for a Q-first file the caller conjugates the taps and the output is Q-first again (filtering Q + jI with conj(h) gives
+ * Im w + j Re w).  Output frame m is the instant of input frame m D (zero phase): a frame offset into the input that is a
+ * multiple of D is a frame offset into the output.  *clipped (may be NULL): the exact count of output bytes whose value
+ * before the clip lay outside [-127, 127].  The sums are exact in int32 - pure integer, so the output is the contract's
+ * byte for byte.  The whole record is read on the context's stream (a record that is still streaming in is waited for, as
+ * sgx_if_wait to its full length); the input is left alone; *out is an ordinary record (sgx_if_free); N = 0 gives an empty
+ * record and launches nothing.
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: L even or out of range, D outside 2 .. 16,
+ * lanes not 1 or 2, shift outside 0 .. 30, a tap component beyond 32 512 in magnitude, 128 sum|h| >= 2^31 (lanes = 2: the
+ * sum of |re| + |im|, so that both output sums stay in int32), an unknown flag bit, a NULL pointer, N odd with lanes = 2, a
+ * record that lies on another device than the context's, a record beyond one launch.
+ * sgx_decim_timing: HIP-event time of the last sgx_if_decimate's kernel on this context.
+ * sgx_decim_tile: the output bytes one workgroup of the kernel makes (where its tile seams lie).
+ *
+ * sgx_decim_design: the band-pass that selects f0 +- bandwidth_hz / 2 of a record at rate fs (lanes = 2: the complex rate,
+ * f0 the offset from the centre, either sign); exact host code, needs no GPU.  With m = k - c, in doubles, in this order:
+ *   t = bandwidth_hz m / fs;  sinc = sin(pi t) / (pi t), 1 at m = 0;  hann = 0.5 - 0.5 cos(2 pi k / (L - 1)), 1 for L = 1
+ *   lp = (bandwidth_hz / fs) sinc hann;  ph = 2 pi f0 m / fs;  a = 2^SGX_DECIM_SHIFT g lp
+ *   lanes = 1: h[k] = rint(a (2 cos ph));   lanes = 2: h[2k] = rint(a cos ph), h[2k+1] = rint(a sin ph)   (half to even)
+ * g = gain, or for gain <= 0 the gain that keeps a white input's rms: sqrt((fs / l) / bandwidth_hz), l = 2 for a real
+ * record and 1 for I/Q.  *shift = SGX_DECIM_SHIFT, *fs_out = fs / D, and where the band lands:
+ *   lanes = 2: *f_out = ((f0 + fs_out / 2) mod fs_out) - fs_out / 2 (mod as floor), *inverted = 0
+ *   lanes = 1: z = floor(f0 / (fs_out / 2)), *inverted = z & 1, *f_out = f0 - z fs_out / 2 where upright, else
+ *              (z + 1) fs_out / 2 - f0.  An inverted band acquires and tracks like any other; the sign of the Doppler it
+ *              reports is flipped.
+ * SGX_E_ARG: fs or bandwidth_hz not finite or not > 0, f0 or gain not finite, lanes not 1 or 2, D outside 2 .. 16, n_taps
+ * even or out of range, a NULL pointer, a tap that leaves what sgx_if_decimate takes, and a band that aliases onto itself:
+ * lanes = 1, f0 +- bandwidth_hz / 2 does not lie strictly inside one Nyquist zone [z, z + 1) fs_out / 2, 0 <= z < D (the
+ * default record, 38.192 Msps with the IF at 9.548 MHz, at D = 2 or 4: the IF sits on a zone edge); lanes = 2,
+ * bandwidth_hz >= fs_out. */
+#define SGX_DECIM_MAX_TAPS 511
+#define SGX_DECIM_SHIFT 14
+#define SGX_DECIM_OFFSET_BINARY 1
+int sgx_decim_design(double fs, double f0, double bandwidth_hz, int32_t lanes, int32_t D, int32_t n_taps, double gain,
+                     int16_t* taps, int32_t* shift, double* fs_out, double* f_out, int32_t* inverted);
+int sgx_if_decimate(sgx_ctx* c, const sgx_if* rec, int32_t lanes, const int16_t* taps, int32_t n_taps, int32_t shift,
+                    int32_t D, int32_t flags, sgx_if** out, int64_t* clipped);
+int sgx_decim_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_decim_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -191,6 +191,13 @@ _PROTOS = {
     "sgx_if_unpack": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P), _P]),
     "sgx_unpack_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_unpack_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_decim_design": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, _P,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_int32)]),
+    "sgx_if_decimate": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P),
+                                  C.POINTER(C.c_int64)]),
+    "sgx_decim_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_decim_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -610,6 +617,31 @@ def unpack_tile():
     return _tile("sgx_unpack_tile")
 
 
+DECIM_MAX_TAPS = 511
+DECIM_MIN_FACTOR, DECIM_MAX_FACTOR = 2, 16
+DECIM_OFFSET_BINARY = 1
+
+
+def decim_design(fs, f0, bandwidth_hz, lanes, factor, n_taps=127, gain=0.0):
+    """The band-pass of the decimation stage and where the band lands (sgx_decim_design; exact host code, needs no GPU):
+    the band f0 +- bandwidth_hz / 2 of a record at rate fs - lanes 1: a real record, lanes 2: interleaved I/Q at the complex
+    rate fs with f0 the offset from the centre - for decimation by `factor`.  gain <= 0: the gain that keeps a white
+    input's rms.  Returns (taps, shift, info): taps int16[n_taps], or for lanes 2 int16[2 n_taps] with re and im
+    interleaved; info = dict(fs_out, f_out, inverted)."""
+    taps = np.zeros(2 * max(int(n_taps), 1), dtype=np.int16)
+    shift, inv = C.c_int32(0), C.c_int32(0)
+    fs_out, f_out = C.c_double(0), C.c_double(0)
+    check(lib().sgx_decim_design(float(fs), float(f0), float(bandwidth_hz), int(lanes), int(factor), int(n_taps),
+                                 float(gain), _ptr(taps), C.byref(shift), C.byref(fs_out), C.byref(f_out), C.byref(inv)))
+    return taps[:int(lanes) * int(n_taps)].copy(), shift.value, dict(fs_out=fs_out.value, f_out=f_out.value,
+                                                                   inverted=bool(inv.value))
+
+
+def decim_tile():
+    """Output bytes one workgroup of the decimator makes: its tile seams lie at the multiples."""
+    return _tile("sgx_decim_tile")
+
+
 def _int16_taps(taps):
     a = np.asarray(taps)
     if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
@@ -1026,6 +1058,29 @@ class Context(object):
     def unpack_timing(self):
         """Kernel ms of the last unpack on this context, from HIP events on its stream."""
         return self._timing("sgx_unpack_timing", 1)[0]
+
+    def decimate(self, rec, lanes, taps, shift, factor, offset_binary=False):
+        """A new int8 record at 1 / factor of the rate: `rec` through the band-selecting integer FIR of sgx_if_decimate
+        (factor 2 .. 16).  lanes 1: a real int8 record, taps int16[L]; lanes 2: interleaved I/Q, COMPLEX taps as
+        int16[2 L], re and im interleaved.  L is odd, at most 511; decim_design makes the usual taps.  offset_binary: the
+        input bytes are uint8 around 128.  Output frame m is the instant of input frame m factor.  The exact count of
+        outputs whose value before the clip lay outside [-127, 127] is left in the new record's `clipped`."""
+        h16 = _int16_taps(taps)
+        la = int(lanes)
+        if la == 2 and h16.size % 2:
+            raise ValueError("the complex taps of an I/Q record are pairs (re, im): %d values are not" % h16.size)
+        h, cnt = _P(), C.c_int64(0)
+        check(lib().sgx_if_decimate(self._h, rec._h, la, _ptr(h16), h16.size // 2 if la == 2 else h16.size, int(shift),
+                                    int(factor), DECIM_OFFSET_BINARY if offset_binary else 0, C.byref(h), C.byref(cnt)))
+        ln = C.c_size_t(0)
+        check(lib().sgx_if_length(h, C.byref(ln)))
+        out = Record(self, h, int(ln.value))
+        out.clipped = cnt.value
+        return out
+
+    def decim_timing(self):
+        """Kernel ms of the last decimate on this context, from HIP events on its stream."""
+        return self._timing("sgx_decim_timing", 1)[0]
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

@@ -146,6 +146,16 @@ _PACK_DEFAULTS = (
     ("packedTable", None),               # an explicit sequence of 2^bits int8 levels, one per code: overrides encoding and peak
 )
 
+# band selection and decimation ahead of acquisition (Settings.decimateRecord; INTEGRATION.md, "Decimation"): the int8 record
+# goes through a band-pass around the carrier and comes out at 1 / decimation of the rate, behind the unpacker, the
+# conditioning stage and the requantiser, in front of the I/Q converter and the notch
+_DECIM_DEFAULTS = (
+    ("decimation", 0),                   # the factor D, 2 .. 16; 0: the stage is off
+    ("decimTaps", 127),                  # filter length (odd, at most 511)
+    ("decimBandwidth", 2.046e6),         # two-sided bandwidth of the band that is kept, Hz
+    ("decimGain", 0.0),                  # 0: the gain that keeps a white input's rms
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -155,7 +165,7 @@ class Settings(object):
 
     def __init__(self):
         for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS + _COND_DEFAULTS \
-                + _PACK_DEFAULTS:
+                + _PACK_DEFAULTS + _DECIM_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -388,9 +398,12 @@ class Settings(object):
         """The settings the PREPARED record is read under: realEquivalent(), with skipNumberOfBytes turned from a byte of a
         file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w.  A real record
         that goes through the conditioning stage comes out as int8 in the same way; a packed record (packedBits) is read
-        as the int8 record the unpacker makes of it (_unpacked_settings), whatever follows."""
+        as the int8 record the unpacker makes of it (_unpacked_settings), whatever follows; a record that is decimated
+        (decimation) as the int8 record the decimator makes of it (_decimated_settings), whatever follows that."""
         if self.packedBits:
             return self._unpacked_settings()._prepared_settings()
+        if self.decimation:
+            return self._decimated_settings()._prepared_settings()
         if not self.iqRecord:
             if not self.frontEndConditioning:
                 return self
@@ -412,6 +425,90 @@ class Settings(object):
                              (skip, "even" if w == 1 else "a multiple of %d (pairs of %d-byte components)" % (2 * w, w)))
         real.skipNumberOfBytes = skip // w
         return real
+
+    def _decim_format(self):
+        """(lanes, D, taps, offset_binary, q_first) of the decimation stage for these settings: what the record is where
+        the stage sees it, behind the unpacker, the conditioning stage and the requantiser."""
+        try:
+            D = int(self.decimation)
+            ok = D == self.decimation and _native.DECIM_MIN_FACTOR <= D <= _native.DECIM_MAX_FACTOR
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.decimation = %r: the factor is an integer in %d .. %d (0: the stage is off)"
+                             % (self.decimation, _native.DECIM_MIN_FACTOR, _native.DECIM_MAX_FACTOR))
+        L = int(self.decimTaps)
+        if L != self.decimTaps or not (1 <= L <= _native.DECIM_MAX_TAPS and L % 2 == 1):
+            raise ValueError("Settings.decimTaps = %r: the filter length is odd, 1 .. %d" % (self.decimTaps,
+                                                                                           _native.DECIM_MAX_TAPS))
+        if self.iqRecord:
+            q_first, offset_binary = self._iq_format()       # (raises for what does not reach the converter either)
+            return 2, D, L, offset_binary, q_first
+        if self.frontEndConditioning:
+            self._cond_format()                              # (what conditionRecord makes of the file is int8)
+        elif np.dtype(self.dataType) != np.dtype(np.int8):
+            raise ValueError("Settings.decimation reads a real record as int8: Settings.dataType %r is decimated only behind "
+                             "Settings.frontEndConditioning (int8, uint8, int16) or as a packed file (Settings.packedBits)"
+                             % (self.dataType,))
+        return 1, D, L, False, False
+
+    def _decim_design(self):
+        """(taps, shift, info) of the decimation filter for these settings: the band decimBandwidth wide around IF
+        (_native.decim_design; info: fs_out, f_out, inverted).  For a Q-first I/Q file the taps are conjugated: filtering
+        Q + jI with conj(h) gives Im w + j Re w, a Q-first record again."""
+        lanes, D, L, _, q_first = self._decim_format()
+        try:
+            taps, shift, info = _native.decim_design(self.samplingFreq, self.IF, self.decimBandwidth, lanes, D, L,
+                                                     self.decimGain)
+        except _native.SgxError as e:
+            raise ValueError("Settings.decimation = %d, decimTaps = %d, decimBandwidth = %r, decimGain = %r at samplingFreq "
+                             "%r, IF %r: %s" % (D, L, self.decimBandwidth, self.decimGain, self.samplingFreq, self.IF, e))
+        if q_first:
+            taps[1::2] = -taps[1::2]
+        return taps, shift, info
+
+    def _decimated_settings(self):
+        """The settings the DECIMATED record is read under: a copy with the stage off, int8 (conditioned and requantised
+        where the settings say so), samplingFreq / decimation, the IF where the band lands (info f_out of _decim_design)
+        and skipNumberOfBytes turned from a byte of a file of w-byte components - on a multiple of `decimation` frames -
+        into the byte of the decimated record it becomes."""
+        lanes, D, _, _, _ = self._decim_format()
+        _, _, info = self._decim_design()
+        if self.iqRecord:
+            w = self._iq_width()
+        else:
+            w = self._cond_format()[0] if self.frontEndConditioning else 1
+        skip = int(self.skipNumberOfBytes)
+        if skip % (w * lanes * D):
+            raise ValueError("skipNumberOfBytes = %d does not fall on a multiple of Settings.decimation = %d %s: it must be a "
+                             "multiple of %d" % (skip, D, "I/Q pairs" if lanes == 2 else "samples", w * lanes * D))
+        dec = copy.copy(self)
+        dec.decimation = 0
+        dec.frontEndConditioning = False
+        dec.iqRequantize = False
+        dec.dataType = 'int8'
+        dec.samplingFreq = info["fs_out"]
+        dec.IF = info["f_out"]
+        dec.skipNumberOfBytes = skip // (w * D)
+        return dec
+
+    def decimateRecord(self, record):
+        """A resident int8 record (a _native.Record; with iqRecord interleaved I/Q, uint8 read as offset binary) as a NEW
+        int8 record at 1 / decimation of the rate: the band decimBandwidth wide around IF through a decimTaps-tap band-pass
+        (decim_design), every decimation-th output kept (Context.decimate).  Output frame m is the instant of input frame
+        m decimation.  Returns (record8, info) and keeps info as self.lastDecimation: factor, taps (the filter length),
+        fs_out, f_out (rate and IF - for I/Q the offset - of the new record), inverted (the band came out mirrored: the
+        Doppler it shows has the other sign), clipped (share of the samples that left the int8 range) and samples.  The
+        caller frees both."""
+        if not self.decimation:
+            raise ValueError("Settings.decimation is 0: the stage is off")
+        lanes, D, L, offset_binary, _ = self._decim_format()
+        taps, shift, out = self._decim_design()
+        rec8 = record.ctx.decimate(record, lanes, taps, shift, D, offset_binary=offset_binary)
+        info = dict(factor=D, taps=L, fs_out=out["fs_out"], f_out=out["f_out"], inverted=out["inverted"],
+                    clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0, samples=len(rec8))
+        self.lastDecimation = info
+        return rec8, info
 
     def conditionRecord(self, record):
         """A resident record holding the raw bytes of an int8, uint8 or int16 file (a _native.Record; Settings.dataType
@@ -498,16 +595,23 @@ class Settings(object):
         fall on a frame boundary of the file, and count is rounded up to whole frames; with
         frontEndConditioning brought to int8 block by block (conditionRecord), first
         of all; with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
-        with iqRecord converted to real IF, with mitigate_at (a sample of the prepared record; None: no mitigation) cleared
+        with decimation brought to 1 / decimation of the rate (decimateRecord), with iqRecord converted to real IF, with
+        mitigate_at (a sample of the prepared record; None: no mitigation) cleared
         of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the real
         rate.  offset and count are in BYTES OF THE PREPARED RECORD: for a file of w-byte components the bytes
-        [w offset, w (offset + count)) are read, and sample n of the prepared record is file byte n w.  Each intermediate
+        [w offset, w (offset + count)) are read, and sample n of the prepared record is file byte n w; with decimation = D
+        the bytes [w D offset, w D (offset + count)), whole groups of D frames.  Each intermediate
         record is freed as soon as the next one exists.  Yields the prepared record, to be read under
         _prepared_settings(), and frees it afterwards."""
         from . import engine
         say = print if verbose else (lambda *args: None)
         real = self._prepared_settings()
         w = self._iq_width() if self.iqRecord else (self._cond_format()[0] if self.frontEndConditioning else 1)
+        front = self                                 # the settings the converter reads its input under
+        if self.decimation:
+            # sample n of the prepared record is sample n D of the record the decimator reads
+            front = (self._unpacked_settings() if self.packedBits else self)._decimated_settings()
+            offset, count = offset * int(self.decimation), count * int(self.decimation)
         if self.packedBits:
             unit, samples = self._pack_units()
             if offset % samples:
@@ -548,12 +652,23 @@ class Settings(object):
                     raw.free()
                 say('   rms %.6g, peak %.6g, %d non-finite samples, gain %+.2f dB, %.4f %% of the samples clipped'
                     % (info["rms"], info["max_abs"], info["n_nonfinite"], info["gain_db"], 100.0 * info["clipped"]))
-            if self.iqRecord:
-                say('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
-                    % (self.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
+            if self.decimation:
+                say('   Decimating by %d through %d taps...' % (int(self.decimation), int(self.decimTaps)))
                 raw, rec = rec, None
                 try:
-                    rec = self.convertIQ(raw)
+                    rec, info = self.decimateRecord(raw)
+                finally:
+                    raw.free()
+                say('   %d samples at %.6g Msps, %s %.6g MHz, band %s, %.4f %% of the samples clipped'
+                    % (info["samples"], info["fs_out"] / 1e6, "carrier at" if self.iqRecord else "IF", info["f_out"] / 1e6,
+                       "INVERTED (Doppler shows with the other sign)" if info["inverted"] else "upright",
+                       100.0 * info["clipped"]))
+            if self.iqRecord:
+                say('   Converting I/Q at %.6g Msps to real IF: %.6g Msps, IF %.6g MHz...'
+                    % (front.samplingFreq / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
+                raw, rec = rec, None
+                try:
+                    rec = front.convertIQ(raw)
                 finally:
                     raw.free()
             if mitigate_at is not None:
@@ -601,14 +716,16 @@ class Settings(object):
         GPU; both stages read the prepared record where it lies.  The results carry _prepared_settings(): positions
         (codePhase, absoluteSample, skipNumberOfBytes) are samples of the prepared record, which are bytes of an 8-bit file
         and file byte / w of a file of w-byte components (int16: w = 2, float32: w = 4, with iqRequantize); of a packed
-        file (packedBits = b, frames of F fields of which `take` are kept) sample n is byte n b F / (8 take)."""
+        file (packedBits = b, frames of F fields of which `take` are kept) sample n is byte n b F / (8 take).  With
+        decimation = D a sample of the prepared record is D samples of the record in front of the stage (I/Q: D pairs),
+        so the upload holds whole groups of D frames."""
         from .record import DeviceFile, DeviceSignal
         real = self._prepared_settings()
         n = real.samplesPerCode
         skip = int(real.skipNumberOfBytes)
         need = skip + max(real.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
         if self.iqRecord:
-            need += need % 2
+            need += need % 2                         # (whole pairs; with decimation: whole groups of D pairs)
         with self._prepared_record(name, 0, need, skip if self.interferenceMitigation else None, verbose=True) as rec:
             window = DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip)))
             return self._acquire_and_track(real, window, DeviceFile(rec))
@@ -631,7 +748,7 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning or self.packedBits:
+        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning or self.packedBits or self.decimation:
             acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None

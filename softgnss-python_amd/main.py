@@ -7,6 +7,7 @@
                                                   [--condition[=BLANK_FACTOR]]
                                                   [--packed BITS --packed-encoding ENC --packed-lsb-first
                                                    --packed-frame F[:FIRST] --packed-peak PEAK]
+                                                  [--decimate D[:TAPS] --decimate-bandwidth HZ]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -30,7 +31,14 @@ sample per field, through the levels of --packed-encoding (sign-magnitude, offse
 --packed-peak (48), the first sample of a byte in its high bits (--packed-lsb-first: in its low bits), and prints the share
 of the samples on each level.  --packed-frame F[:FIRST] is for files that interleave several streams: of every F fields (2,
 4, 8 or 16) the one at FIRST is kept (with --iq the pair from FIRST on).  --skip stays a byte of the file, on a frame
-boundary; positions in the results are samples of the unpacked record.  Not with --iq-requantize or --condition."""
+boundary; positions in the results are samples of the unpacked record.  Not with --iq-requantize or --condition.
+--decimate D[:TAPS] (D = 2 .. 16; real int8 records, or with --iq, --condition, --packed) selects the band
+--decimate-bandwidth wide (2.046 MHz) around the carrier with a TAPS-tap band-pass (127) on the GPU and keeps every D-th
+sample, behind the other preparing stages and in front of the I/Q converter and the notch: everything else runs at 1 / D of
+the rate.  The new rate, where the carrier lands, whether the band came out inverted (the Doppler then shows with the other
+sign) and the share of clipped samples are printed.  --skip stays a byte of the file, on a multiple of D frames; positions in
+the results are samples of the prepared record, D input frames each.  A --fs / --IF pair whose band would alias onto itself at
+this D is refused (the default record at D = 2 or 4: use 3 or 5)."""
 from __future__ import print_function
 
 import argparse
@@ -41,7 +49,7 @@ from . import initialize
 
 
 def probe_iq(settings):
-    """probeData() of an I/Q or a packed file: the first 10 code periods prepared on the GPU, probed as the real int8
+    """probeData() of an I/Q, a packed or a decimated file: the first 10 code periods prepared on the GPU, probed as the real int8
     record they become."""
     from .record import DeviceSignal
     real = settings._prepared_settings()
@@ -94,8 +102,30 @@ def main(argv=None):
                          "field at FIRST (default 0; with --iq the I/Q pair from there on)")
     ap.add_argument("--packed-peak", type=int, default=None, metavar="PEAK",
                     help="with --packed: the largest level of the int8 record (default: Settings.packedPeak, 48)")
+    ap.add_argument("--decimate", default=None, metavar="D[:TAPS]",
+                    help="select the band around the carrier and decimate the record by D (2 .. 16) on the GPU, through a "
+                         "band-pass of TAPS taps (odd, at most 511; default: Settings.decimTaps, 127)")
+    ap.add_argument("--decimate-bandwidth", type=float, default=None, metavar="HZ",
+                    help="with --decimate: the two-sided bandwidth that is kept (default: Settings.decimBandwidth, 2.046e6)")
     a = ap.parse_args(argv)
     frame = first = None
+    decim = decim_taps = None
+    if a.decimate is None:
+        if a.decimate_bandwidth is not None:
+            ap.error("--decimate-bandwidth describes the band --decimate keeps: it needs --decimate")
+    else:
+        try:
+            parts = [int(x) for x in a.decimate.split(":")]
+            decim, decim_taps = parts[0], (parts[1] if len(parts) > 1 else None)
+            ok = len(parts) <= 2 and 2 <= decim <= 16 and (decim_taps is None or (1 <= decim_taps <= 511 and decim_taps % 2 == 1))
+        except ValueError:
+            ok = False
+        if not ok:
+            ap.error("--decimate takes D[:TAPS] with D in 2 .. 16 and TAPS odd, 1 .. 511")
+        if a.decimate_bandwidth is not None and not (np.isfinite(a.decimate_bandwidth) and a.decimate_bandwidth > 0):
+            ap.error("--decimate-bandwidth takes the two-sided bandwidth in Hz, above 0")
+        if a.correlator_bank is not None:
+            ap.error("--correlator-bank replays from the record file, which --decimate resamples on the way in: not both")
     if a.packed is None:
         if a.packed_encoding is not None or a.packed_lsb_first or a.packed_frame is not None or a.packed_peak is not None:
             ap.error("--packed-encoding, --packed-lsb-first, --packed-frame and --packed-peak describe a packed file: "
@@ -152,17 +182,22 @@ def main(argv=None):
                       ("packedBits", a.packed), ("packedEncoding", a.packed_encoding),
                       ("packedLsbFirst", True if a.packed_lsb_first else None), ("packedFrame", frame),
                       ("packedFirst", first), ("packedPeak", a.packed_peak),
+                      ("decimation", decim), ("decimTaps", decim_taps), ("decimBandwidth", a.decimate_bandwidth),
                       ("interferenceMitigation", True if a.notch is not None else None),
                       ("notchThresholdDb", a.notch if a.notch is not None and a.notch >= 0 else None)):
         if val is not None:
             setattr(settings, name, val)
-    if settings.iqRecord:
+    if settings.decimation:
+        real = settings._prepared_settings()
+        print('Decimated by %d: read as a real record at %.6f Msps, IF %.6f MHz'
+              % (settings.decimation, real.samplingFreq / 1e6, real.IF / 1e6))
+    elif settings.iqRecord:
         real = settings.realEquivalent()
         print('I/Q record at %.6f Msps, carrier at %+.6f MHz: read as a real record at %.6f Msps, IF %.6f MHz'
               % (settings.samplingFreq / 1e6, settings.IF / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
     if not a.no_probe:
         print('Probing data "%s"...' % settings.fileName)
-        p = probe_iq(settings) if settings.iqRecord or settings.packedBits else settings.probeData()
+        p = probe_iq(settings) if settings.iqRecord or settings.packedBits or settings.decimation else settings.probeData()
         if p is not None:
             k = int(np.argmax(p["Pxx"]))
             print('  %d Welch segments, spectral peak at %.3f MHz, samples within [%d, %d]'
