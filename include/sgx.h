@@ -749,6 +749,47 @@ int sgx_if_decimate(sgx_ctx* c, const sgx_if* rec, int32_t lanes, const int16_t*
 int sgx_decim_timing(sgx_ctx* c, float* kernel_ms);
 int sgx_decim_tile(int32_t* tile_bytes);
 
+/* ---- rational resampling by L / M ahead of acquisition (no reference counterpart; behind the unpacker, the conditioning
+ * stage or requantiser, the decimator and sgx_if_from_iq, in front of sgx_if_filter) ---------------------------------------
+ * Opt-in.  A resident REAL int8 record of N bytes is brought to L / M of its rate, 1 <= M <= 3, M < L <= 16, gcd(L, M) = 1
+ * (31 pairs), as a NEW int8 record: a capture below the 15.4 samples per chip the fast tracking kernels need reaches them
+ * (4.096 Msps x 10, 16.368 Msps x 7/3, 2.048 Msps x 8).  tests/resamp_spec.py restates all of it in numpy.
+ *
+ * sgx_if_resample: n_taps = Lh odd, 1 .. SGX_RESAMP_MAX_TAPS, c = (Lh - 1) / 2, taps int16 h[Lh], rnd = shift ?
+ * 2^(shift-1) : 0, q(a) = clip((a + rnd) >> shift, -127, 127) with an arithmetic (floor) shift.  With the zero-stuffed
+ * record u[i] = x[i / L] where L divides i and 0 <= i / L < N, else 0:
+ *   y[m] = q(sum_k h[k] u[m M + c - k]),  m = 0 .. ceil(N L / M) - 1
+ * Output sample m is the instant of input position m M / L (zero phase): a sample offset into the input that is a multiple
+ * of M is the output offset (offset L / M).  *clipped (may be NULL): the exact count of outputs whose value before the clip
+ * lay outside [-127, 127].  The sums are exact in int32 - pure integer, so the output is the contract's byte for byte.  No
+ * multiply-accumulate is spent on a stuffed zero: the kernel runs the L sub-filters h[phi + j L] on the input.  The whole
+ * record is read on the context's stream (a record that is still streaming in is waited for, as sgx_if_wait to its full
+ * length); the input is left alone; *out is an ordinary record (sgx_if_free); N = 0 gives an empty record and launches
+ * nothing.  SGX_E_NOMEM when the output cannot be allocated.
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: a pair L / M outside the 31, n_taps even or
+ * out of range, shift outside 0 .. 30, a tap beyond 32 512 in magnitude, 128 sum|h| >= 2^31, a NULL pointer, a record that
+ * lies on another device than the context's, an output beyond one launch.
+ * sgx_resamp_timing: HIP-event time of the last sgx_if_resample's kernel on this context.
+ * sgx_resamp_tile: the output bytes one workgroup of the kernel makes at L = 16, the largest; at a pair L / M a workgroup
+ * makes tile_bytes L / 16 (where its tile seams lie).
+ *
+ * sgx_resamp_design: the low-pass at the stuffed rate fu = fs L; exact host code, needs no GPU.  fc = cutoff_hz, or for
+ * cutoff_hz = 0 min(fs, fs L / M) / 2.  With m = k - c, in doubles, in this order:
+ *   fu = fs L;  t = 2 fc m / fu;  sinc = sin(pi t) / (pi t), 1 at m = 0;  hann = 0.5 - 0.5 cos(2 pi k / (Lh - 1)), 1 for
+ *   Lh = 1;  lp = (2 fc / fu) sinc hann;  h[k] = rint((2^SGX_RESAMP_SHIFT g L) lp)   (half to even; g = gain)
+ * *shift = SGX_RESAMP_SHIFT, *fs_out = fs L / M.  The usual length is 24 L + 1: beyond fc + 2 fu / (Lh - 1) the taps are
+ * 44 dB down; with M = 1 and the default cutoff phase 0 is the single tap 2^14, y[m L] = x[m].
+ * SGX_E_ARG: fs, gain not finite or not > 0, cutoff_hz not finite, negative or above min(fs, fs_out) / 2, a pair outside
+ * the 31, n_taps even or out of range, a NULL pointer, a tap that leaves what sgx_if_resample takes. */
+#define SGX_RESAMP_MAX_TAPS 1023
+#define SGX_RESAMP_SHIFT 14
+int sgx_resamp_design(double fs, int32_t L, int32_t M, int32_t n_taps, double cutoff_hz, double gain, int16_t* taps,
+                      int32_t* shift, double* fs_out);
+int sgx_if_resample(sgx_ctx* c, const sgx_if* rec, const int16_t* taps, int32_t n_taps, int32_t shift, int32_t L, int32_t M,
+                    sgx_if** out, int64_t* clipped);
+int sgx_resamp_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_resamp_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

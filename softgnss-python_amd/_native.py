@@ -198,6 +198,12 @@ _PROTOS = {
                                   C.POINTER(C.c_int64)]),
     "sgx_decim_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_decim_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_resamp_design": (C.c_int, [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "sgx_if_resample": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P),
+                                  C.POINTER(C.c_int64)]),
+    "sgx_resamp_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_resamp_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -642,6 +648,35 @@ def decim_tile():
     return _tile("sgx_decim_tile")
 
 
+RESAMP_MAX_TAPS = 1023
+RESAMP_MAX_UP, RESAMP_MAX_DOWN = 16, 3
+RESAMP_SHIFT = 14
+
+
+def resamp_pair_ok(up, down):
+    """Whether up / down is one of the 31 ratios the resampler takes: 1 <= down <= 3, down < up <= 16, coprime."""
+    import math
+    return 1 <= down <= RESAMP_MAX_DOWN and down < up <= RESAMP_MAX_UP and math.gcd(up, down) == 1
+
+
+def resamp_design(fs, up, down=1, n_taps=0, cutoff_hz=0.0, gain=1.0):
+    """The low-pass of the resampling stage (sgx_resamp_design; exact host code, needs no GPU): a Hann-windowed sinc at the
+    stuffed rate fs up, cutoff cutoff_hz (0: half the lower of the two rates), n_taps taps (0: 24 up + 1).  Returns
+    (taps int16[n_taps], shift, info); info = dict(fs_out)."""
+    n = int(n_taps) if n_taps else 24 * int(up) + 1
+    taps = np.zeros(max(n, 1), dtype=np.int16)
+    shift, fs_out = C.c_int32(0), C.c_double(0)
+    check(lib().sgx_resamp_design(float(fs), int(up), int(down), n, float(cutoff_hz), float(gain), _ptr(taps),
+                                  C.byref(shift), C.byref(fs_out)))
+    return taps[:n].copy(), shift.value, dict(fs_out=fs_out.value)
+
+
+def resamp_tile():
+    """Output bytes one workgroup of the resampler makes at up = 16; at another ratio its tile seams lie at the multiples
+    of resamp_tile() * up // 16."""
+    return _tile("sgx_resamp_tile")
+
+
 def _int16_taps(taps):
     a = np.asarray(taps)
     if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
@@ -1081,6 +1116,25 @@ class Context(object):
     def decim_timing(self):
         """Kernel ms of the last decimate on this context, from HIP events on its stream."""
         return self._timing("sgx_decim_timing", 1)[0]
+
+    def resample(self, rec, taps, shift, up, down=1):
+        """A new int8 record at up / down of the rate: the real int8 record `rec` through the polyphase integer FIR of
+        sgx_if_resample (1 <= down <= 3, down < up <= 16, coprime).  taps int16[Lh], Lh odd, at most 1023, at the stuffed
+        rate; resamp_design makes the usual ones.  Output sample m is the instant of input position m down / up.  The
+        exact count of outputs whose value before the clip lay outside [-127, 127] is left in the new record's `clipped`."""
+        h16 = _int16_taps(taps)
+        h, cnt = _P(), C.c_int64(0)
+        check(lib().sgx_if_resample(self._h, rec._h, _ptr(h16), h16.size, int(shift), int(up), int(down), C.byref(h),
+                                    C.byref(cnt)))
+        ln = C.c_size_t(0)
+        check(lib().sgx_if_length(h, C.byref(ln)))
+        out = Record(self, h, int(ln.value))
+        out.clipped = cnt.value
+        return out
+
+    def resamp_timing(self):
+        """Kernel ms of the last resample on this context, from HIP events on its stream."""
+        return self._timing("sgx_resamp_timing", 1)[0]
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

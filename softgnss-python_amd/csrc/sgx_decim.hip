@@ -51,13 +51,6 @@ static constexpr bool dc_taps_fit() {
 }
 static_assert(dc_taps_fit(), "the sub-filter images of the longest filter fit the tap staging at every D");
 
-// bytes (a >> 2 . a & 3) and (b >> 2 . b & 3) of raw[] as bytes 0 and 1 of the result
-// (v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first)
-template <int NR>
-__device__ __forceinline__ unsigned dc_pick2(const unsigned (&raw)[NR], int a, int b) {
-    return __builtin_amdgcn_perm(raw[b >> 2], raw[a >> 2], (unsigned)((a & 3) | ((4 + (b & 3)) << 8)) | 0x0c0c0000u);
-}
-
 template <int LANES, int D>
 __global__ __launch_bounds__(FIR_THREADS) void decim_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
                                                             unsigned long long n, unsigned long long n_out,
@@ -86,8 +79,8 @@ __global__ __launch_bounds__(FIR_THREADS) void decim_kernel(const int8_t* __rest
             unsigned o[W / 4];
 #pragma unroll
             for (int g = 0; g < W / 4; ++g) {
-                const unsigned lo = dc_pick2(raw, (4 * g) * P + pp, (4 * g + 1) * P + pp);
-                const unsigned hi = dc_pick2(raw, (4 * g + 2) * P + pp, (4 * g + 3) * P + pp);
+                const unsigned lo = fir_pick2(raw, (4 * g) * P + pp, (4 * g + 1) * P + pp);
+                const unsigned hi = fir_pick2(raw, (4 * g + 2) * P + pp, (4 * g + 3) * P + pp);
                 o[g] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
             }
             if constexpr (W == 16) {

@@ -1,5 +1,6 @@
-// The integer FIR core of the stages that rewrite a whole resident int8 record: the notch (sgx_filter.hip) and the I/Q ->
-// real-IF converter (sgx_iq.hip).  Each piece is here once; the two files keep their tap-image layouts and their kernels.
+// The integer FIR core of the stages that rewrite a whole resident int8 record: the notch (sgx_filter.hip), the I/Q ->
+// real-IF converter (sgx_iq.hip), the decimator (sgx_decim.hip) and the resampler (sgx_resamp.hip).  Each piece is here
+// once; the files keep their tap-image layouts and their kernels.
 //
 // Formulation: v_dot4_i32_i8 on byte windows (DESIGN.md section 4.11 says why not the int8 matrix cores).  Each int16 tap
 // is two signed bytes, h = 256 hi + lo; the two byte filters accumulate separately and are combined as 256 acc_hi + acc_lo.
@@ -30,6 +31,13 @@ __device__ __forceinline__ uint4 fir_load_chunk(const int8_t* __restrict__ x, lo
         v = make_uint4(w[0], w[1], w[2], w[3]);
     }
     return v;
+}
+
+// The register transposes of the decimator and the resampler: bytes (a >> 2 . a & 3) and (b >> 2 . b & 3) of raw[] as bytes 0 and 1 of the result
+// (v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first)
+template <int NR>
+__device__ __forceinline__ unsigned fir_pick2(const unsigned (&raw)[NR], int a, int b) {
+    return __builtin_amdgcn_perm(raw[b >> 2], raw[a >> 2], (unsigned)((a & 3) | ((4 + (b & 3)) << 8)) | 0x0c0c0000u);
 }
 
 template <int W> struct FirSlot;

@@ -112,9 +112,10 @@ struct FftPlan {
 #define DC_COUNT_STRIDE 16   // 64-bit words between two slots
 
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
-// sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate
+// sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
+// sgx_if_resample
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
-                    SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -314,7 +315,7 @@ struct SgxSmall {
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
     // The record front-end stages: what sgx_stage_run (sgx_stage.h) copies up in front of a stage's kernel or down behind
     // it.  Every stage waits before it returns, so one call owns a slot at a time; both.
-    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter, sgx_if_from_iq or sgx_if_decimate call
+    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter, sgx_if_from_iq, sgx_if_decimate or sgx_if_resample call
     alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
     // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass, and
     // the quantiser's counters of outputs on +-127
@@ -326,6 +327,8 @@ struct SgxSmall {
     alignas(256) unsigned long long unpack_count[UP_COUNT_SLOTS * UP_COUNT_STRIDE];
     // sgx_decim.hip: the decimator's counters of clipped outputs
     alignas(256) unsigned long long decim_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
+    // sgx_resamp.hip: the resampler's counters of clipped outputs, in the decimator's layout
+    alignas(256) unsigned long long resamp_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");

@@ -156,6 +156,18 @@ _DECIM_DEFAULTS = (
     ("decimGain", 0.0),                  # 0: the gain that keeps a white input's rms
 )
 
+# rational resampling ahead of acquisition (Settings.resampleRecord; INTEGRATION.md, "Resampling"): the real int8 record goes
+# through a polyphase low-pass and comes out at resampleUp / resampleDown of the rate, behind the unpacker, the conditioning
+# stage or requantiser, the decimator and the I/Q converter, in front of the notch - a capture below the 15.4 samples per
+# chip the fast tracking kernels need reaches them
+_RESAMP_DEFAULTS = (
+    ("resampleUp", 0),                   # the up factor L, 2 .. 16; 0: the stage is off
+    ("resampleDown", 1),                 # the down factor M, 1 .. 3, below L and coprime to it
+    ("resampTaps", 0),                   # filter length at the stuffed rate (odd, at most 1023); 0: 24 L + 1
+    ("resampCutoff", 0.0),               # cutoff of the low-pass, Hz; 0: half the lower of the two rates
+    ("resampGain", 1.0),
+)
+
 
 class Settings(object):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173."""
@@ -165,7 +177,7 @@ class Settings(object):
 
     def __init__(self):
         for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _NOTCH_DEFAULTS + _IQ_DEFAULTS + _COND_DEFAULTS \
-                + _PACK_DEFAULTS + _DECIM_DEFAULTS:
+                + _PACK_DEFAULTS + _DECIM_DEFAULTS + _RESAMP_DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -399,7 +411,10 @@ class Settings(object):
         file of w-byte components into the sample of the prepared record it becomes, skipNumberOfBytes / w.  A real record
         that goes through the conditioning stage comes out as int8 in the same way; a packed record (packedBits) is read
         as the int8 record the unpacker makes of it (_unpacked_settings), whatever follows; a record that is decimated
-        (decimation) as the int8 record the decimator makes of it (_decimated_settings), whatever follows that."""
+        (decimation) as the int8 record the decimator makes of it (_decimated_settings), whatever follows that; a record
+        that is resampled (resampleUp) as the record the resampler makes of all that (_resampled_settings)."""
+        if self.resampleUp:
+            return self._resampled_settings()
         if self.packedBits:
             return self._unpacked_settings()._prepared_settings()
         if self.decimation:
@@ -425,6 +440,91 @@ class Settings(object):
                              (skip, "even" if w == 1 else "a multiple of %d (pairs of %d-byte components)" % (2 * w, w)))
         real.skipNumberOfBytes = skip // w
         return real
+
+    def _resamp_front(self):
+        """The settings of the record the resampler READS: the prepared settings of a copy with the stage off."""
+        off = copy.copy(self)
+        off.resampleUp = 0
+        front = off._prepared_settings()
+        if np.dtype(front.dataType) != np.dtype(np.int8):
+            raise ValueError("Settings.resampleUp reads a real record as int8: Settings.dataType %r is resampled only behind a "
+                             "stage that makes int8 of it (Settings.frontEndConditioning, Settings.packedBits, "
+                             "Settings.iqRecord)" % (self.dataType,))
+        return front
+
+    def _resamp_format(self):
+        """(L, M, taps) of the resampling stage for these settings: the pair resampleUp / resampleDown and the filter
+        length, resampTaps or 24 L + 1."""
+        try:
+            L, M = int(self.resampleUp), int(self.resampleDown)
+            ok = L == self.resampleUp and M == self.resampleDown and _native.resamp_pair_ok(L, M)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.resampleUp / Settings.resampleDown = %r / %r: the ratio L / M has 1 <= M <= %d, "
+                             "M < L <= %d and no common factor (resampleUp = 0: the stage is off)"
+                             % (self.resampleUp, self.resampleDown, _native.RESAMP_MAX_DOWN, _native.RESAMP_MAX_UP))
+        try:
+            Lh = int(self.resampTaps)
+            ok = Lh == self.resampTaps and (Lh == 0 or (1 <= Lh <= _native.RESAMP_MAX_TAPS and Lh % 2 == 1))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.resampTaps = %r: the filter length is odd, 1 .. %d (0: 24 resampleUp + 1)"
+                             % (self.resampTaps, _native.RESAMP_MAX_TAPS))
+        return L, M, Lh if Lh else 24 * L + 1
+
+    def _resamp_design(self):
+        """(taps, shift, info) of the resampling filter for these settings (_native.resamp_design at the rate of the
+        record the stage reads; info: fs_out, cutoff).  The C/A band of that record, up to IF + 1.023 MHz, must lie below
+        the cutoff."""
+        L, M, Lh = self._resamp_format()
+        front = self._resamp_front()
+        fs = float(front.samplingFreq)
+        try:
+            taps, shift, info = _native.resamp_design(fs, L, M, Lh, self.resampCutoff, self.resampGain)
+        except (_native.SgxError, TypeError, ValueError) as e:
+            raise ValueError("Settings.resampleUp / resampleDown = %d / %d, resampTaps = %d, resampCutoff = %r, resampGain = %r "
+                             "at samplingFreq %r: %s" % (L, M, Lh, self.resampCutoff, self.resampGain, fs, e))
+        cutoff = float(self.resampCutoff) if self.resampCutoff else min(fs, info["fs_out"]) / 2.0
+        if not float(front.IF) + 1.023e6 < cutoff:
+            raise ValueError("Settings.resampCutoff: the low-pass of the resampler cuts off at %.6g Hz, at or below the upper "
+                             "edge of the C/A band, IF + 1.023 MHz = %.6g Hz" % (cutoff, float(front.IF) + 1.023e6))
+        info["cutoff"] = cutoff
+        return taps, shift, info
+
+    def _resampled_settings(self):
+        """The settings the RESAMPLED record is read under: those of the record the stage reads (_resamp_front), with
+        samplingFreq L / M, the IF unchanged, and skipNumberOfBytes - there a sample, on a multiple of M - turned into the
+        sample of the resampled record it becomes, skip L / M."""
+        L, M, _ = self._resamp_format()
+        front = self._resamp_front()
+        _, _, info = self._resamp_design()
+        skip = int(front.skipNumberOfBytes)
+        if skip % M:
+            raise ValueError("skipNumberOfBytes = %d: sample %d of the record the resampler reads does not map to a whole "
+                             "sample at %d / %d of the rate: it must be a multiple of Settings.resampleDown = %d"
+                             % (int(self.skipNumberOfBytes), skip, L, M, M))
+        res = copy.copy(front)
+        res.samplingFreq = info["fs_out"]
+        res.skipNumberOfBytes = skip // M * L
+        return res
+
+    def resampleRecord(self, record):
+        """A resident real int8 record (a _native.Record) as a NEW int8 record at resampleUp / resampleDown of the rate,
+        through the resampTaps-tap low-pass of resamp_design (Context.resample).  Output sample m is the instant of input
+        position m resampleDown / resampleUp.  Returns (record8, info) and keeps info as self.lastResampling: up, down,
+        taps (the filter length), fs_out, clipped (share of the samples that left the int8 range) and samples.  The
+        caller frees both."""
+        if not self.resampleUp:
+            raise ValueError("Settings.resampleUp is 0: the stage is off")
+        L, M, Lh = self._resamp_format()
+        taps, shift, out = self._resamp_design()
+        rec8 = record.ctx.resample(record, taps, shift, L, M)
+        info = dict(up=L, down=M, taps=Lh, fs_out=out["fs_out"],
+                    clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0, samples=len(rec8))
+        self.lastResampling = info
+        return rec8, info
 
     def _decim_format(self):
         """(lanes, D, taps, offset_binary, q_first) of the decimation stage for these settings: what the record is where
@@ -596,6 +696,8 @@ class Settings(object):
         frontEndConditioning brought to int8 block by block (conditionRecord), first
         of all; with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
         with decimation brought to 1 / decimation of the rate (decimateRecord), with iqRecord converted to real IF, with
+        resampleUp = L brought to L / M of the rate (resampleRecord; offset must then be a multiple of L: sample offset of
+        the prepared record is sample offset M / L of the record the stage reads), with
         mitigate_at (a sample of the prepared record; None: no mitigation) cleared
         of the narrowband lines in the spectrum from there on - the conversion first, the notch is designed at the real
         rate.  offset and count are in BYTES OF THE PREPARED RECORD: for a file of w-byte components the bytes
@@ -608,6 +710,15 @@ class Settings(object):
         real = self._prepared_settings()
         w = self._iq_width() if self.iqRecord else (self._cond_format()[0] if self.frontEndConditioning else 1)
         front = self                                 # the settings the converter reads its input under
+        if self.resampleUp:
+            # sample n L of the prepared record is sample n M of the record the resampler reads
+            L, M, _ = self._resamp_format()
+            if offset % L:
+                raise ValueError("sample %d of the resampled record is not a sample of the record the resampler reads: it "
+                                 "must be a multiple of Settings.resampleUp = %d" % (offset, L))
+            offset, count = offset // L * M, -(-count * M // L)
+            if self.iqRecord:
+                count += count % 2                   # (whole pairs)
         if self.decimation:
             # sample n of the prepared record is sample n D of the record the decimator reads
             front = (self._unpacked_settings() if self.packedBits else self)._decimated_settings()
@@ -671,6 +782,16 @@ class Settings(object):
                     rec = front.convertIQ(raw)
                 finally:
                     raw.free()
+            if self.resampleUp:
+                L, M, Lh = self._resamp_format()
+                say('   Resampling by %d/%d through %d taps...' % (L, M, Lh))
+                raw, rec = rec, None
+                try:
+                    rec, info = self.resampleRecord(raw)
+                finally:
+                    raw.free()
+                say('   %d samples at %.6g Msps, %.4f %% of the samples clipped'
+                    % (info["samples"], info["fs_out"] / 1e6, 100.0 * info["clipped"]))
             if mitigate_at is not None:
                 say('   Looking for narrowband interference...')
                 raw = rec
@@ -748,7 +869,8 @@ class Settings(object):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning or self.packedBits or self.decimation:
+        if self.iqRecord or self.interferenceMitigation or self.frontEndConditioning or self.packedBits or self.decimation \
+                or self.resampleUp:
             acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None

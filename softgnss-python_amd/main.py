@@ -8,6 +8,7 @@
                                                   [--packed BITS --packed-encoding ENC --packed-lsb-first
                                                    --packed-frame F[:FIRST] --packed-peak PEAK]
                                                   [--decimate D[:TAPS] --decimate-bandwidth HZ]
+                                                  [--resample L[/M][:TAPS] --resample-cutoff HZ]
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
 was lost, lost channels leaving the navigation) and, when the record is long enough (36 s, four satellites with
@@ -38,7 +39,13 @@ sample, behind the other preparing stages and in front of the I/Q converter and 
 the rate.  The new rate, where the carrier lands, whether the band came out inverted (the Doppler then shows with the other
 sign) and the share of clipped samples are printed.  --skip stays a byte of the file, on a multiple of D frames; positions in
 the results are samples of the prepared record, D input frames each.  A --fs / --IF pair whose band would alias onto itself at
-this D is refused (the default record at D = 2 or 4: use 3 or 5)."""
+this D is refused (the default record at D = 2 or 4: use 3 or 5).
+--resample L[/M][:TAPS] (L = 2 .. 16, M = 1 .. 3 below L and coprime to it) brings the real int8 record - the file, or what
+the stages above make of it - to L / M of its rate on the GPU through a TAPS-tap low-pass (24 L + 1) that cuts off at
+--resample-cutoff (half the lower of the two rates), in front of the notch: a capture below the 15.4 samples per chip the
+fast tracking kernels need reaches them (4.096 Msps: 10, 16.368 Msps: 7/3, 2.048 Msps I/Q: --iq with 10).  The new rate and
+the share of clipped samples are printed.  --skip stays a byte of the file, on a sample that maps to a whole one (a
+multiple of M); positions in the results are samples of the resampled record."""
 from __future__ import print_function
 
 import argparse
@@ -107,8 +114,34 @@ def main(argv=None):
                          "band-pass of TAPS taps (odd, at most 511; default: Settings.decimTaps, 127)")
     ap.add_argument("--decimate-bandwidth", type=float, default=None, metavar="HZ",
                     help="with --decimate: the two-sided bandwidth that is kept (default: Settings.decimBandwidth, 2.046e6)")
+    ap.add_argument("--resample", default=None, metavar="L[/M][:TAPS]",
+                    help="bring the real int8 record to L / M of its rate on the GPU (L 2 .. 16, M 1 .. 3, M < L, coprime), "
+                         "through a low-pass of TAPS taps (odd, at most 1023; default: 24 L + 1)")
+    ap.add_argument("--resample-cutoff", type=float, default=None, metavar="HZ",
+                    help="with --resample: the cutoff of the low-pass (default: half the lower of the two rates)")
     a = ap.parse_args(argv)
     frame = first = None
+    up = down = resamp_taps = None
+    if a.resample is None:
+        if a.resample_cutoff is not None:
+            ap.error("--resample-cutoff describes the low-pass of --resample: it needs --resample")
+    else:
+        try:
+            ratio, _, tail = a.resample.partition(":")
+            num, _, den = ratio.partition("/")
+            up, down = int(num), (int(den) if "/" in ratio else 1)
+            resamp_taps = int(tail) if ":" in a.resample else None
+            ok = initialize._native.resamp_pair_ok(up, down) and \
+                (resamp_taps is None or (1 <= resamp_taps <= 1023 and resamp_taps % 2 == 1))
+        except ValueError:
+            ok = False
+        if not ok:
+            ap.error("--resample takes L[/M][:TAPS] with L in 2 .. 16, M in 1 .. 3 below L and coprime to it, and TAPS odd, "
+                     "1 .. 1023")
+        if a.resample_cutoff is not None and not (np.isfinite(a.resample_cutoff) and a.resample_cutoff > 0):
+            ap.error("--resample-cutoff takes the cutoff in Hz, above 0")
+        if a.correlator_bank is not None:
+            ap.error("--correlator-bank replays from the record file, which --resample resamples on the way in: not both")
     decim = decim_taps = None
     if a.decimate is None:
         if a.decimate_bandwidth is not None:
@@ -183,11 +216,17 @@ def main(argv=None):
                       ("packedLsbFirst", True if a.packed_lsb_first else None), ("packedFrame", frame),
                       ("packedFirst", first), ("packedPeak", a.packed_peak),
                       ("decimation", decim), ("decimTaps", decim_taps), ("decimBandwidth", a.decimate_bandwidth),
+                      ("resampleUp", up), ("resampleDown", down), ("resampTaps", resamp_taps),
+                      ("resampCutoff", a.resample_cutoff),
                       ("interferenceMitigation", True if a.notch is not None else None),
                       ("notchThresholdDb", a.notch if a.notch is not None and a.notch >= 0 else None)):
         if val is not None:
             setattr(settings, name, val)
-    if settings.decimation:
+    if settings.resampleUp:
+        real = settings._prepared_settings()
+        print('Resampled by %d/%d: read as a real record at %.6f Msps, IF %.6f MHz'
+              % (settings.resampleUp, settings.resampleDown, real.samplingFreq / 1e6, real.IF / 1e6))
+    elif settings.decimation:
         real = settings._prepared_settings()
         print('Decimated by %d: read as a real record at %.6f Msps, IF %.6f MHz'
               % (settings.decimation, real.samplingFreq / 1e6, real.IF / 1e6))
@@ -197,7 +236,8 @@ def main(argv=None):
               % (settings.samplingFreq / 1e6, settings.IF / 1e6, real.samplingFreq / 1e6, real.IF / 1e6))
     if not a.no_probe:
         print('Probing data "%s"...' % settings.fileName)
-        p = probe_iq(settings) if settings.iqRecord or settings.packedBits or settings.decimation else settings.probeData()
+        p = probe_iq(settings) if settings.iqRecord or settings.packedBits or settings.decimation \
+            or settings.resampleUp else settings.probeData()
         if p is not None:
             k = int(np.argmax(p["Pxx"]))
             print('  %d Welch segments, spectral peak at %.3f MHz, samples within [%d, %d]'
