@@ -695,7 +695,8 @@ class Settings(object):
         fall on a frame boundary of the file, and count is rounded up to whole frames; with
         frontEndConditioning brought to int8 block by block (conditionRecord), first
         of all; with iqRequantize and an int16 / float32 dataType brought to int8 (requantizeIQ),
-        with decimation brought to 1 / decimation of the rate (decimateRecord), with iqRecord converted to real IF, with
+        with decimation brought to 1 / decimation of the rate (decimateRecord), with iqRecord converted to real IF (the sample
+        of the converter's record that offset stands for must then be even, the first byte of a pair), with
         resampleUp = L brought to L / M of the rate (resampleRecord; offset must then be a multiple of L: sample offset of
         the prepared record is sample offset M / L of the record the stage reads), with
         mitigate_at (a sample of the prepared record; None: no mitigation) cleared
@@ -719,6 +720,11 @@ class Settings(object):
             offset, count = offset // L * M, -(-count * M // L)
             if self.iqRecord:
                 count += count % 2                   # (whole pairs)
+        if self.iqRecord and offset % 2:
+            # byte n of the converted record is the instant of byte n's pair; ahead of the decimator's * D, behind which an
+            # odd sample of an even D would pass as a pair - and the upload would start on a Q, read as I from there on
+            raise ValueError("sample %d of the record the I/Q converter makes splits an I/Q pair of the record it reads: it "
+                             "must be even" % offset)
         if self.decimation:
             # sample n of the prepared record is sample n D of the record the decimator reads
             front = (self._unpacked_settings() if self.packedBits else self)._decimated_settings()

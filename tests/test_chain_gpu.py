@@ -1,0 +1,343 @@
+"""The record stages composed, and prepared records at an offset, on the GPU: Settings._prepared_record for every accepted
+chain of tests/test_chain_host.py's table against the composed contract of tests/chain_cases.py, byte for byte - the whole
+file, the smallest legal offset, an offset beyond the first tile seam with a count that needs every rounding the chain has,
+a file that ends early - with each stage's counts; the same chains ending in the notch; three variants (Q-first offset
+binary, a multi-stream packed frame, an inverted band) in one chain each; then the two scenes of tests/chain_scenes.py end
+to end - postProcessing, main.probe_iq and main.main behind a skip - against the composed contract and the oracle on it.
+Run with -m gpu."""
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import chain_cases as cases
+import chain_scenes as scenes
+import notch_spec
+import requant_spec
+from conftest import ROOT, pkg
+from oracle import softgnss_oracle as orc
+from record_stage import same_tracking
+from test_gpu_parity import PSD_TOL
+from test_chain_host import accepted
+
+pytestmark = pytest.mark.gpu
+
+MATRIX = accepted()
+
+
+def largest_tile(chain):
+    return cases.largest_tile(chain, pkg()._native)
+
+
+def step_of(chain):
+    return cases.smallest_offset(chain)
+
+
+def prepared_size(chain):
+    return cases.prepared_size(chain, pkg()._native)
+
+
+def write_file(tmp_path, chain, make=cases.full_scale_file, seed=0xC4A1):
+    b = make(chain, np.random.default_rng(seed), cases.file_components(chain, prepared_size(chain)))
+    path = tmp_path / (chain.name + ".bin")
+    b.tofile(str(path))
+    return b, str(path)
+
+
+def same_bytes(got, want, what):
+    assert got.size == want.size, (what, got.size, want.size)
+    assert got.tobytes() == want.tobytes(), \
+        "%r: first difference at byte %d of %d" % (what, int(np.flatnonzero(got != want)[0]), want.size)
+
+
+def check_counts(s, chain, want, what):
+    """The last* records the stages left against the contracts' counts of this very slice."""
+    if chain.first == "packed":
+        info, c = s.lastUnpack, want["unpack"]
+        assert info["samples"] == c["samples"] and info["bits"] == chain.bits, what
+        assert np.array_equal(info["code_counts"], c["code_counts"][:info["code_counts"].size]), what
+        assert int(c["code_counts"][info["code_counts"].size:].sum()) == 0
+        assert np.array_equal(info["table"], c["table"]), what
+    if chain.first == "cond":
+        info, c = s.lastConditioning, want["cond"]
+        frames = c["samples"] // chain.lanes
+        assert (info["samples"], info["block"], info["blocks"]) == (c["samples"], c["block"], c["blocks"]), what
+        assert info["blanked"] == c["blanked"] / float(frames) and info["clipped"] == c["clipped"] / float(c["samples"]), what
+    if chain.first == "requant":
+        info, c = s.lastRequant, want["requant"]
+        assert info["n_finite"] + info["n_nonfinite"] == c["samples"] and info["clipped"] == c["clipped"] / float(c["samples"])
+        if chain.dtype == "int16":
+            assert (info["mult"], info["shift"], info["sum_sq"]) == (c["mult"], c["shift"], c["stats"]["sum_sq"]), what
+        else:
+            assert np.float32(info["scale"]).tobytes() == np.float32(c["scale"]).tobytes(), what
+    if chain.D:
+        info, c = s.lastDecimation, want["decim"]
+        assert (info["samples"], info["factor"], info["taps"]) == (c["samples"], chain.D, chain.decim_taps), what
+        assert info["clipped"] == c["clipped"] / float(c["samples"]), (what, info["clipped"], c["clipped"])
+        assert (info["fs_out"], info["f_out"], info["inverted"]) == (c["fs_out"], c["f_out"], c["inverted"]), what
+    if chain.resamp:
+        info, c = s.lastResampling, want["resamp"]
+        assert (info["samples"], info["up"], info["down"]) == (c["samples"],) + chain.resamp, what
+        assert info["clipped"] == c["clipped"] / float(c["samples"]) and info["fs_out"] == c["fs_out"], what
+
+
+def contract_for(s, chain, b, offset, count):
+    """chain_cases.prepare for the slice the run just prepared.  A float32 file takes the gain the way
+    tests/test_requant_gpu.py does: from the library's own sums, once they lie within the contract's bounds of the correctly
+    rounded ones."""
+    if chain.dtype != "float32":
+        return cases.prepare(b, chain, offset, count)
+    want = cases.prepare(b, chain, offset, count)
+    info, st = s.lastRequant, want["requant"]["stats"]
+    assert (info["n_finite"], info["n_nonfinite"], info["max_abs"]) == (st["n_finite"], st["n_nonfinite"], st["max_abs"])
+    b_sum, b_sq = requant_spec.bounds(st, want["requant"]["samples"])
+    assert abs(info["sum"] - st["sum"]) <= b_sum and abs(info["sum_sq"] - st["sum_sq"]) <= b_sq, (info, st)
+    return cases.prepare(b, chain, offset, count, requant_sums=(info["n_finite"], info["sum_sq"]))
+
+
+def forget(s):
+    for k in ("lastUnpack", "lastConditioning", "lastRequant", "lastDecimation", "lastResampling", "lastNotchLines"):
+        if hasattr(s, k):
+            delattr(s, k)
+
+
+def prepared(s, chain, path, b, offset, count, exact=True):
+    """_prepared_record(path, offset, count) is the contract's record of that slice of b, with the contract's counts - or,
+    where the contract has no record for the slice (a file that ends inside an element or a pair), an error.  Returns the
+    contract, or None."""
+    m = pkg()
+    what = (chain.name, offset, count)
+    try:
+        cases.prepare(b, chain, offset, count)
+    except ValueError:
+        with pytest.raises((ValueError, m._native.SgxError)):
+            with s._prepared_record(path, offset, count):
+                pass
+        return None
+    forget(s)
+    with s._prepared_record(path, offset, count) as rec:
+        got = rec.download()
+        assert len(rec) == got.size
+    want = contract_for(s, chain, b, offset, count)
+    same_bytes(got, want["record"], what)
+    check_counts(s, chain, want, what)
+    if exact:                                            # the file holds all that was asked for
+        assert count <= got.size <= count + cases.rounding_unit(chain), (what, got.size)
+    return want
+
+
+def rounding_count(chain, most):
+    """The largest count <= most that needs every rounding the chain has: count M not a multiple of L, an odd number of
+    samples in front of the resampler where the converter needs pairs, a part of a frame of the packed file (but where whole
+    pairs times D are whole frames anyway)."""
+    per_unit, _ = cases.components_per_unit(chain)
+    for frames in (True, False):
+        for count in range(most, most - 4096, -1):
+            n = count
+            if chain.resamp:
+                L, M = chain.resamp
+                if (count * M) % L == 0:
+                    continue
+                n = -(-count * M // L)
+                if chain.iq and n % 2 == 0:
+                    continue
+                n += n % 2 if chain.iq else 0
+            elif chain.iq and count % 2:
+                continue                                 # (no rounding here: an odd count is the caller's mistake)
+            if frames and per_unit > 1 and (n * (chain.D or 1)) % per_unit == 0:
+                continue
+            return count
+        assert per_unit > 1 and chain.iq and chain.D, chain.name
+    raise AssertionError(chain.name)
+
+
+def run_chain(tmp_path, chain):
+    m = pkg()
+    s = chain.settings(m)
+    b, path = write_file(tmp_path, chain)
+    total = cases.prepared_length(chain, b.size)
+    assert total >= prepared_size(chain) and b.size < 1 << 20
+    step = step_of(chain)
+    # the whole file
+    want = prepared(s, chain, path, b, 0, total)
+    assert want["file_range"] == (0, b.size), chain.name
+    real = s._prepared_settings()
+    assert (real.samplingFreq, real.IF) == (want["fs"], want["IF"])
+    # the smallest legal offset
+    prepared(s, chain, path, b, step, total - 2 * step)
+    # beyond the first tile seam, a count that needs every rounding the chain has
+    offset = (largest_tile(chain) // step + 3) * step
+    count = rounding_count(chain, total - offset - 2 * step - 2 * cases.rounding_unit(chain))
+    want = prepared(s, chain, path, b, offset, count)
+    if chain.resamp or (cases.components_per_unit(chain)[0] > chain.lanes and not (chain.iq and chain.D)):
+        assert want["record"].size > count, chain.name
+    if chain.iq and not chain.resamp:                    # an odd count: whatever the contract makes of it
+        prepared(s, chain, path, b, offset, count + 1)
+    # a file that ends inside that range: on a whole unit, and one byte later
+    first, n_bytes = want["file_range"]
+    unit = cases.skip_unit(chain)
+    cut = (first + (3 * n_bytes) // 5) // unit * unit
+    for end in (cut, cut + 1):
+        short = path + ".%d" % end
+        b[:end].tofile(short)
+        w = prepared(s, chain, short, b[:end], offset, count, exact=False)
+        assert w is not None or end > cut, chain.name    # (whole units: there is a record)
+        if w is not None:
+            assert w["file_range"][0] == first and first + w["file_range"][1] <= end
+            assert w["file_range"][1] > n_bytes // 2 and w["record"].size < count
+    # illegal offsets: refused before the file is looked at
+    for bad in range(1, 2 * step + 2):
+        if bad % step:
+            with pytest.raises(ValueError):
+                with s._prepared_record(str(tmp_path / "no_such_file.bin"), bad, count):
+                    pass
+
+
+@pytest.mark.parametrize("chain", MATRIX, ids=[c.name for c in MATRIX])
+def test_chain(tmp_path, chain):
+    run_chain(tmp_path, chain)
+
+
+@pytest.mark.parametrize("chain", MATRIX, ids=[c.name for c in MATRIX])
+def test_chain_into_the_notch(tmp_path, chain):
+    """The chain's record of a file with a line, then the notch: the lines the contract finds in the oracle's spectrum of
+    the composed record (no bin within 1 dB of the threshold, so the GPU's spectrum flags the same bins), the contract's
+    filter of those lines, the composed record through it."""
+    m = pkg()
+    s = chain.settings(m, interferenceMitigation=True)
+    b, path = write_file(tmp_path, chain, make=cases.line_file, seed=cases.LINE_SEED)
+    total = cases.prepared_length(chain, b.size)
+    at = step_of(chain)
+    with s._prepared_record(path, 0, total, mitigate_at=at) as rec:
+        got = rec.download()
+    found = s.lastNotchLines
+    composed = contract_for(s, chain, b, 0, total)
+    check_counts(s, chain, composed, (chain.name, "notch"))
+    x = composed["record"]
+    lines, taps = cases.notch_contract(chain, composed, at, s.notchThresholdDb, s.notchWidthHz, s.notchTaps)
+    assert found == lines, (chain.name, found, lines)
+    want = notch_spec.apply(x, taps, notch_spec.DESIGN_SHIFT)
+    same_bytes(got, want, (chain.name, "notch"))
+
+
+# ---- variants: one chain each ---------------------------------------------------------------------------------------------
+
+def test_q_first_offset_binary_with_decimation_and_resampling(tmp_path):
+    """A uint8 Q-first file through decimation by 4, the converter and a 3/1 resampler: the decimator takes the offset
+    binary and conjugated taps, the converter is told Q first - and the record is the plain file's (I first, int8) too."""
+    chain, plain = cases.VARIANT_QI_U8, cases.VARIANT_QI_U8_PLAIN
+    run_chain(tmp_path, chain)
+    b = np.fromfile(str(tmp_path / (chain.name + ".bin")), dtype=np.uint8)
+    swapped = (b ^ 0x80).reshape(-1, 2)[:, ::-1].ravel()
+    path = str(tmp_path / "plain.bin")
+    swapped.tofile(path)
+    total = cases.prepared_length(chain, b.size)
+    want = cases.prepare(b, chain, 0, total)["record"]
+    same_bytes(cases.prepare(swapped, plain, 0, total)["record"], want, "the two contracts")
+    with plain.settings(pkg())._prepared_record(path, 0, total) as rec:
+        same_bytes(rec.download(), want, "the plain file")
+
+
+@pytest.mark.parametrize("chain", [cases.VARIANT_FRAME, cases.VARIANT_FRAME_IQ, cases.VARIANT_INVERTED],
+                         ids=lambda c: c.name)
+def test_variant(tmp_path, chain):
+    """One stream of a 2-bit frame of four with the decimator behind it; the I/Q pair of a 4-bit frame of eight, LSB first,
+    offset binary, decimated and converted; the default front end decimated by 3 - the band inverted - and resampled."""
+    run_chain(tmp_path, chain)
+
+
+# ---- end to end: the two scenes ---------------------------------------------------------------------------------------------
+
+TRK_MS = scenes.TRK_MS
+
+
+def scene_file(tmp_path, scene):
+    b = scene.file_of(TRK_MS + 4)
+    path = str(tmp_path / (scene.name + ".bin"))
+    b.tofile(path)
+    return b, path
+
+
+@pytest.mark.parametrize("skipped", [False, True], ids=["start", "skip"])
+@pytest.mark.parametrize("name", sorted(scenes.SCENES))
+def test_post_processing_of_a_scene(tmp_path, name, skipped):
+    m = pkg()
+    scene = scenes.SCENES[name]
+    chain = scene.chain
+    b, path = scene_file(tmp_path, scene)
+    skip_bytes = scene.skip_bytes if skipped else 0
+    skip = scene.skip_out(skip_bytes)                                          # samples of the prepared record
+    s = scene.settings(m, msToProcess=float(TRK_MS), skipNumberOfBytes=skip_bytes)
+    acq, trk, nav = s.postProcessing(path)
+    assert nav is None or nav._solutions is None                               # 0.2 s carries no subframe
+    assert s.skipNumberOfBytes == skip_bytes and s.resampleUp == chain.resamp[0]                      # left alone
+    p = cases.prepared_settings(chain, skip_bytes)
+    assert dict((k, getattr(acq.settings, k)) for k in p) == p
+    n = p["samplesPerCode"]
+    # what the run prepared is the composed contract's record of the bytes it read, with every stage's counts
+    count = s.lastResampling["samples"]
+    assert skip + TRK_MS * n < count <= cases.prepared_length(chain, b.size)
+    want = cases.prepare(b, chain, 0, count)
+    assert want["record"].size == count
+    check_counts(s, chain, want, (name, "postProcessing"))
+    with s._prepared_record(path, 0, count) as rec:
+        got = rec.download()
+    same_bytes(got, want["record"], (name, skip_bytes))
+    check_counts(s, chain, want, (name, "_prepared_record"))
+    # acquisition and tracking against the oracle on those bytes
+    y = want["record"]
+    o = scene.oracle_settings(msToProcess=float(TRK_MS), skipNumberOfBytes=skip)
+    ref = orc.acquire(o, y[skip:skip + 11 * n])
+    assert np.array_equal(acq.codePhase, ref["codePhase"]) and np.array_equal(acq.carrFreq, ref["carrFreq"])
+    assert sorted(np.flatnonzero(acq.carrFreq) + 1) == sorted(scene.prns)      # the scene's satellites and no others
+    chans = orc.pre_run(o, ref)
+    assert np.array_equal(acq.channels.PRN, chans["PRN"]) and np.count_nonzero(acq.channels.PRN) == len(scene.prns)
+    same_tracking(trk, orc.stack_series(orc.track(o, chans, y)), len(scene.prns), TRK_MS)
+    # the rate the chain exists for: the speculative kernel, not the per-sample one
+    assert int(m.engine.get_context(acq.settings, 0).timing()["track_kernel"]) == 5
+
+
+def main_args(scene, path, skip_bytes):
+    c = scene.chain
+    args = [path, "--fs", repr(c.fs), "--IF", repr(c.f0), "--ms", str(TRK_MS), "--channels", str(len(scene.prns)),
+            "--skip", str(skip_bytes), "--resample", "%d/%d" % c.resamp]
+    if c.first == "packed":
+        args += ["--packed", str(c.bits)]
+    if c.first == "cond":
+        args += ["--condition", "--dtype", c.dtype]
+    if c.iq:
+        args += ["--iq"]
+    if c.D:
+        args += ["--decimate", str(c.D)]
+    return args
+
+
+@pytest.mark.parametrize("name", sorted(scenes.SCENES))
+def test_probe_of_a_scene_behind_a_skip(tmp_path, name):
+    """main.probe_iq, the one production caller of _prepared_record with an offset: the statistics of the ten code periods
+    from skipNumberOfBytes on are the oracle's on the composed contract's preparation of that slice; then the same through
+    main.main with the probe on, in a process of its own."""
+    m = pkg()
+    scene = scenes.SCENES[name]
+    chain = scene.chain
+    b, path = scene_file(tmp_path, scene)
+    skip_bytes = scene.skip_bytes
+    s = scene.settings(m, msToProcess=float(TRK_MS), skipNumberOfBytes=skip_bytes, fileName=path)
+    p = cases.prepared_settings(chain, skip_bytes)
+    out = pkg("main").probe_iq(s)
+    want = cases.prepare(b, chain, p["skipNumberOfBytes"], 10 * p["samplesPerCode"])
+    check_counts(s, chain, want, (name, "probe"))
+    y = want["record"]
+    assert 10 * p["samplesPerCode"] <= y.size <= 10 * p["samplesPerCode"] + cases.rounding_unit(chain)
+    n = min(y.size, 10 * p["samplesPerCode"])
+    f, pxx, hist = orc.probe_stats(scene.oracle_settings(), y[:n])
+    assert out["segments"] == (n - 1024) // 15360
+    assert np.array_equal(out["hist"], hist) and np.array_equal(out["f_MHz"], f)
+    assert np.max(np.abs(out["Pxx"] - pxx) / pxx) < PSD_TOL
+    assert np.array_equal(out["timeData"], y[1:p["samplesPerCode"] // 50])
+    r = subprocess.run([sys.executable, "-m", "softgnss-python_amd.main"] + main_args(scene, path, skip_bytes), cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, text[-2000:]
+    assert "%d Welch segments" % out["segments"] in text and "Tracking is over" in text, text[-2000:]
