@@ -1,5 +1,6 @@
-"""The code that joins the record stages, as far as it runs without a GPU (Settings._prepared_settings, and the refusals of
-Settings._prepared_record, which come before anything is uploaded), against the composed contract of tests/chain_cases.py:
+"""The code that joins the record stages, as far as it runs without a GPU (Settings._prepared_settings, Settings._file_range
+and the refusals of Settings._prepared_record, which come before anything is uploaded), against the composed contract of
+tests/chain_cases.py:
 which chains of stages are accepted - the table is written out below - what rate, IF, sample type and skip each prepared
 record is read under, and which skipNumberOfBytes and offsets a chain refuses; the inputs of the notch tests and the two
 end-to-end scenes of tests/chain_scenes.py shown to be well conditioned by the contracts and the oracle alone.  Run with
@@ -93,7 +94,7 @@ def test_the_designs_are_the_contracts():
         s = chain.settings(m)
         r = cases.rates(chain)
         if chain.D:
-            front = s._unpacked_settings() if chain.first == "packed" else s
+            front = s._walk(upto="decimate")[1] if chain.first == "packed" else s
             taps, shift, info = front._decim_design()
             h, S, fs_out, f_out, inverted = r["decim"]
             assert taps.tobytes() == h.tobytes() and shift == S, chain.name
@@ -175,6 +176,37 @@ def test_illegal_offsets_are_refused_before_the_file_is_touched(chain):
                     pass
     if chain.iq or chain.resamp or (chain.first == "packed" and not chain.D and not chain.resamp):
         assert refused > 0, chain.name
+
+
+@pytest.mark.parametrize("chain", accepted() + _variants(), ids=[c.name for c in accepted() + _variants()])
+def test_file_range(chain):
+    """The walk back, without a card: Settings._file_range(offset, count) is the contract's file_range() - or both refuse -
+    for every offset up to two legal steps and one far beyond, an even, an odd and an off-step count; and it undoes the
+    walk forwards: the sample a legal skipNumberOfBytes becomes is made of the file from that byte on."""
+    m = pkg()
+    s = chain.settings(m)
+    unit = cases.skip_unit(chain)
+    step = cases.prepared_skip(chain, unit)
+    legal = 0
+    for offset in list(range(0, 2 * step + 2)) + [1237 * step, 1237 * step + 1]:
+        for count in (1000, 1001, step + 1):
+            try:
+                want = cases.file_range(chain, offset, count)
+            except ValueError:
+                with pytest.raises(ValueError):
+                    s._file_range(offset, count)
+                continue
+            legal += 1
+            assert s._file_range(offset, count) == want, (chain.name, offset, count)
+    assert legal >= 9, chain.name                                               # offsets 0, step, 2 step at the least
+    for skip in range(0, 2 * unit + 1):
+        try:
+            want = cases.prepared_skip(chain, skip)
+        except ValueError:
+            continue
+        s.skipNumberOfBytes = skip
+        assert s._prepared_settings().skipNumberOfBytes == want
+        assert s._file_range(want, 1)[0] == skip, (chain.name, skip)
 
 
 def test_an_offset_that_splits_a_pair_names_the_pair():

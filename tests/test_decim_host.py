@@ -416,7 +416,7 @@ def test_settings_surface(built):
     assert (real.samplingFreq, real.IF, real.iqRecord, real.dataType, real.decimation) == (8184000.0, 1154000.0, False, 'int8', 0)
     s.dataType, s.iqQFirst = 'uint8', True
     assert s._decim_format() == (2, 4, 63, True, True)
-    front = s._decimated_settings()
+    front = s._walk(upto="convert")[1]
     assert (front.dataType, front.iqRecord, front.iqQFirst, front.samplingFreq, front.IF) == ('int8', True, True, 4092000.0,
                                                                                               -892000.0)
     assert front._iq_format() == (True, False)
