@@ -983,11 +983,15 @@ class Context(object):
         """(kernel ms, device ms) of the last track_replay on this context, from HIP events on its stream."""
         return self._timing("sgx_replay_timing", 2)
 
-    def _stage(self, fn, n, args, counters=()):
-        """The new Record of n bytes that the record stage fn(ctx, *args, &record, &counter ...) makes, with its int64
-        counters as the attributes named in `counters`."""
+    def _stage(self, fn, args, n=None, counters=(), tail=()):
+        """The new Record that the record stage fn(ctx, *args, &record, *tail, &counter ...) makes - of n bytes; None: as many
+        as sgx_if_length says - with its int64 counters as the attributes named in `counters`."""
         h, cnt = _P(), [C.c_int64(0) for _ in counters]
-        check(getattr(lib(), fn)(self._h, *args, C.byref(h), *[C.byref(v) for v in cnt]))
+        check(getattr(lib(), fn)(self._h, *args, C.byref(h), *tail, *[C.byref(v) for v in cnt]))
+        if n is None:
+            ln = C.c_size_t(0)
+            check(lib().sgx_if_length(h, C.byref(ln)))
+            n = int(ln.value)
         out = Record(self, h, n)
         for k, v in zip(counters, cnt):
             setattr(out, k, v.value)
@@ -997,7 +1001,7 @@ class Context(object):
         """A new int8 record of the same length: `rec` through the zero-phase integer FIR of sgx_if_filter (taps: int16, an
         odd number of them up to 4095; y = clip((sum_k h[k] x[n + c - k] + 2^(shift-1)) >> shift, -127, 127))."""
         h16 = _int16_taps(taps)
-        return self._stage("sgx_if_filter", len(rec), (rec._h, _ptr(h16), h16.size, int(shift)))
+        return self._stage("sgx_if_filter", (rec._h, _ptr(h16), h16.size, int(shift)), len(rec))
 
     def filter_timing(self):
         """Kernel ms of the last filter_record on this context, from HIP events on its stream."""
@@ -1010,7 +1014,7 @@ class Context(object):
         I; offset_binary: its bytes are uint8 around 128."""
         h16 = _int16_taps(taps)
         flags = (IQ_Q_FIRST if q_first else 0) | (IQ_OFFSET_BINARY if offset_binary else 0)
-        return self._stage("sgx_if_from_iq", len(rec), (rec._h, _ptr(h16), h16.size, int(shift), flags))
+        return self._stage("sgx_if_from_iq", (rec._h, _ptr(h16), h16.size, int(shift), flags), len(rec))
 
     def iq_timing(self):
         """Kernel ms of the last iq_to_if on this context, from HIP events on its stream."""
@@ -1035,7 +1039,7 @@ class Context(object):
         y = clip(rint(x * float32(scale)), -127, 127), NaN -> 0.  The number of outputs on +-127 is left in the new
         record's `clipped`."""
         dt, w = requant_type(dtype)
-        return self._stage("sgx_if_requantize", len(rec) // w, (rec._h, dt, int(mult), int(shift), float(scale)),
+        return self._stage("sgx_if_requantize", (rec._h, dt, int(mult), int(shift), float(scale)), len(rec) // w,
                            ("clipped",))
 
     def requant_timing(self):
@@ -1060,8 +1064,8 @@ class Context(object):
         frames and the outputs on +-127 are left in the new record's `blanked` and `clipped`."""
         dt, w, flags = cond_type(dtype, offset_binary)
         p = np.ascontiguousarray(plan, dtype=COND_PLAN_DTYPE).ravel()
-        return self._stage("sgx_if_condition", len(rec) // w,
-                           (rec._h, dt, int(lanes), int(block), flags, _ptr(p), p.size, int(guard)), ("blanked", "clipped"))
+        return self._stage("sgx_if_condition", (rec._h, dt, int(lanes), int(block), flags, _ptr(p), p.size, int(guard)),
+                           len(rec) // w, ("blanked", "clipped"))
 
     def cond_timing(self):
         """(statistics kernel ms, apply kernel ms) of the last cond_stats and the last condition on this context."""
@@ -1081,12 +1085,8 @@ class Context(object):
                 raise ValueError("the table of a %d-bit record holds %d integers that fit int8" % (b, 1 << b))
             tab[:a.size] = a
         counts = np.zeros(16, dtype=np.int64)
-        h = _P()
-        check(lib().sgx_if_unpack(self._h, rec._h, b, UNPACK_LSB_FIRST if lsb_first else 0, int(frame), int(first),
-                                  int(take), _ptr(tab), C.byref(h), _ptr(counts)))
-        ln = C.c_size_t(0)
-        check(lib().sgx_if_length(h, C.byref(ln)))
-        out = Record(self, h, int(ln.value))
+        out = self._stage("sgx_if_unpack", (rec._h, b, UNPACK_LSB_FIRST if lsb_first else 0, int(frame), int(first), int(take),
+                                            _ptr(tab)), tail=(_ptr(counts),))
         out.code_counts = counts[:1 << b].copy()
         return out
 
@@ -1104,14 +1104,8 @@ class Context(object):
         la = int(lanes)
         if la == 2 and h16.size % 2:
             raise ValueError("the complex taps of an I/Q record are pairs (re, im): %d values are not" % h16.size)
-        h, cnt = _P(), C.c_int64(0)
-        check(lib().sgx_if_decimate(self._h, rec._h, la, _ptr(h16), h16.size // 2 if la == 2 else h16.size, int(shift),
-                                    int(factor), DECIM_OFFSET_BINARY if offset_binary else 0, C.byref(h), C.byref(cnt)))
-        ln = C.c_size_t(0)
-        check(lib().sgx_if_length(h, C.byref(ln)))
-        out = Record(self, h, int(ln.value))
-        out.clipped = cnt.value
-        return out
+        return self._stage("sgx_if_decimate", (rec._h, la, _ptr(h16), h16.size // 2 if la == 2 else h16.size, int(shift),
+                                               int(factor), DECIM_OFFSET_BINARY if offset_binary else 0), counters=("clipped",))
 
     def decim_timing(self):
         """Kernel ms of the last decimate on this context, from HIP events on its stream."""
@@ -1123,14 +1117,8 @@ class Context(object):
         rate; resamp_design makes the usual ones.  Output sample m is the instant of input position m down / up.  The
         exact count of outputs whose value before the clip lay outside [-127, 127] is left in the new record's `clipped`."""
         h16 = _int16_taps(taps)
-        h, cnt = _P(), C.c_int64(0)
-        check(lib().sgx_if_resample(self._h, rec._h, _ptr(h16), h16.size, int(shift), int(up), int(down), C.byref(h),
-                                    C.byref(cnt)))
-        ln = C.c_size_t(0)
-        check(lib().sgx_if_length(h, C.byref(ln)))
-        out = Record(self, h, int(ln.value))
-        out.clipped = cnt.value
-        return out
+        return self._stage("sgx_if_resample", (rec._h, _ptr(h16), h16.size, int(shift), int(up), int(down)),
+                           counters=("clipped",))
 
     def resamp_timing(self):
         """Kernel ms of the last resample on this context, from HIP events on its stream."""

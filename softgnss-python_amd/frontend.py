@@ -3,7 +3,7 @@
 STAGES is the one ordered table: unpack | condition | requantise -> decimate -> convert -> resample (the notch follows them
 and changes no position); what an entry says of its stage is listed at _Stage.  FrontEnd._walk folds the table forwards over
 the file's settings, _file_range walks the same pairs backwards and _prepared_record runs the stages in one loop: the shape
-of the composed contract, tests/chain_cases.py.
+of the composed contract, tests/chain_cases.py.  main.py builds its command line and its banner from the same table.
 """
 import contextlib
 import copy
@@ -27,14 +27,32 @@ class _Stage(object):
     are, for the refusals.  step(s) -> (n_in, n_out, out), under the settings s the stage reads under: the format check, the
     design and the position rule - positions of the record it reads are legal on multiples of n_in, and n_in of them become
     n_out of the record it writes - and the settings its output is read under (the walk maps skipNumberOfBytes).
-    run(s, raw, say, prepared) -> (record, info) through the public method, between the two lines `say` prints."""
-    last = None
+    run(s, raw, say, prepared) -> (record, info) through the public method, between the two lines `say` prints.
+    The command line: options: (flag, add_argument's keywords), first the one that switches the stage on; usage: its
+    paragraph of main's docstring; needs: the refusal of the others without the first; settings_from(args, fail), where the
+    first is given -> the settings asked for (None: left alone), by the options' own syntax and the checks _walk() does not
+    make - fail(message) does not return; replays_file: --correlator-bank can replay from the file behind it (else verb:
+    what it does to its positions); announce(file): its line of the banner, which main.py ends with the prepared rate and IF."""
+    last = needs = announce = None
+    replays_file = True
 
     def on(self, s):
         return bool(getattr(s, self.flag))
 
     def count_in(self, file, count, n_in, n_out):    # positions of its input that `count` of its output are made of
         return -(-count * n_in // n_out)
+
+
+def _numbers(text, seps):
+    """[A, B, C] of an option's text 'A[/B][:C]' (seps '/:'; None for a part that is left out), or None for any other text."""
+    out = []
+    try:
+        for sep in reversed(seps):                   # the last part first: '7/3:127' -> '7/3', 127 -> '7', 3, 127
+            text, found, tail = text.partition(sep)
+            out.insert(0, int(tail) if found else None)
+        return [int(text)] + out
+    except ValueError:
+        return None
 
 
 # 1-, 2- and 4-bit packed records (Settings.unpackRecord; INTEGRATION.md, "Packed records"): the file is unpacked to one int8
@@ -51,6 +69,31 @@ class _Unpack(_Stage):
         ("packedPeak", 48),                  # the largest level of the int8 record it makes, LSB, in 2^bits - 1 .. 127
         ("packedTable", None),               # an explicit sequence of 2^bits int8 levels, one per code: overrides encoding and peak
     )
+    options = (("--packed", dict(type=int, default=None, choices=(1, 2, 4), metavar="BITS",
+                    help="the file holds packed BITS-bit samples (1, 2 or 4): unpack it to int8 on the GPU before anything "
+                         "else")),
+               ("--packed-encoding", dict(default=None, choices=("sign-magnitude", "offset-binary", "twos-complement"),
+                    help="with --packed: what a code means (default: Settings.packedEncoding, sign-magnitude)")),
+               ("--packed-lsb-first", dict(action="store_true",
+                    help="with --packed: the first sample of a byte lies in its low bits")),
+               ("--packed-frame", dict(default=None, metavar="F[:FIRST]",
+                    help="with --packed: the file interleaves streams in frames of F fields (1, 2, 4, 8 or 16); keep the "
+                         "field at FIRST (default 0; with --iq the I/Q pair from there on)")),
+               ("--packed-peak", dict(type=int, default=None, metavar="PEAK",
+                    help="with --packed: the largest level of the int8 record (default: Settings.packedPeak, 48)")))
+    needs = "--packed-encoding, --packed-lsb-first, --packed-frame and --packed-peak describe a packed file: they need --packed"
+    usage = """--packed BITS (1, 2 or 4; real or with --iq) reads a file of packed samples: the GPU unpacks it first of all into
+one int8 sample per field, through the levels of --packed-encoding (sign-magnitude, offset-binary or twos-complement) scaled to
+--packed-peak (48), the first sample of a byte in its high bits (--packed-lsb-first: in its low bits), and prints the share of the
+samples on each level.  --packed-frame F[:FIRST] is for files that interleave several streams: of every F fields (2, 4, 8 or 16)
+the one at FIRST is kept (with --iq the pair from FIRST on).  --skip stays a byte of the file, on a frame boundary; positions in
+the results are samples of the unpacked record.  Not with --iq-requantize or --condition."""
+
+    def settings_from(self, args, fail):
+        frame, first = _numbers("1" if args.packed_frame is None else args.packed_frame, ":") or \
+            fail("--packed-frame takes F[:FIRST] with F one of 1, 2, 4, 8, 16 and the kept fields inside the frame")
+        return dict(packedBits=args.packed, packedEncoding=args.packed_encoding, packedLsbFirst=args.packed_lsb_first or None,
+                    packedFrame=frame, packedFirst=first or 0, packedPeak=args.packed_peak)
 
     def step(self, s):
         unit, samples = s._pack_units()
@@ -80,6 +123,19 @@ class _Condition(_Stage):
         ("condGuardFrames", 8),              # frames blanked either side of a hit
         ("condTargetRms", 12.0),             # rms of the int8 record it makes, LSB, in (0, 127]
     )
+    options = (("--condition", dict(nargs="?", type=float, const=-1.0, default=None, metavar="BLANK_FACTOR",
+                    help="condition the file block by block on the GPU before anything else: DC removal, AGC and pulse "
+                         "blanking at BLANK_FACTOR x the rms (default: Settings.condBlankFactor, 4; 0: no blanking)")),)
+    usage = """--condition (--dtype int8, uint8 or int16, real or with --iq) first conditions the file block by block on the GPU:
+per 100 us it removes the DC of each rail, sets the gain that puts the rms at 12 LSB (a time-varying AGC) and zeroes the frames
+that stand 4 x (or --condition=BLANK_FACTOR, 1 .. 16; 0: no blanking) above the rms, and prints the span of the gain and the
+shares of blanked frames and clipped samples; it stands where --iq-requantize does, so not both; an int16 file is then read as
+int8, positions are file byte / 2."""
+
+    def settings_from(self, args, fail):
+        if not (args.condition in (-1.0, 0.0) or 1.0 <= args.condition <= 16.0):     # (-1: no value given, the default)
+            fail("--condition takes the blanking threshold in units of the rms, 1 .. 16, or 0 for no blanking")
+        return dict(frontEndConditioning=True, condBlankFactor=args.condition if args.condition >= 0 else None)
 
     def step(self, s):
         return s._cond_format()[0], 1, _with(s, frontEndConditioning=False, dataType='int8')
@@ -102,6 +158,20 @@ class _Requantise(_Stage):
         ("iqRequantize", False),             # with iqRecord: dataType 'int16' and 'float32' are read through the requantiser
         ("iqTargetRms", 12.0),               # rms of the int8 record it makes, LSB, in (0, 127]
     )
+    options = (("--iq-requantize", dict(nargs="?", type=float, const=-1.0, default=None, metavar="RMS",
+                    help="with --iq and --dtype int16 or float32: bring the file to int8 on the GPU through one fixed gain "
+                         "that puts its rms at RMS LSB (default: Settings.iqTargetRms, 12)")),)
+    usage = """--iq-requantize (with --iq and --dtype int16 or float32: sc16 and fc32 captures) first brings the file to int8 on
+the GPU through one fixed gain that puts its rms at 12 LSB (or --iq-requantize=RMS), and prints the record's rms, peak, count of
+non-finite samples, the gain in dB and the share of clipped samples; --skip stays a byte of the file (a multiple of 4 for int16, 8
+for float32), the positions in the results are samples of the converted record, file byte / 2 or / 4."""
+
+    def settings_from(self, args, fail):
+        if args.iq is None:                 # (_walk() lets it pass: without iqRecord the setting switches nothing on)
+            fail("--iq-requantize prepares an I/Q file for the converter: it needs --iq")
+        if not (args.iq_requantize == -1.0 or 0.0 < args.iq_requantize <= 127.0):       # (-1: no value given, the default)
+            fail("--iq-requantize takes the rms of the int8 record in LSB, above 0 and at most 127")
+        return dict(iqRequantize=True, iqTargetRms=args.iq_requantize if args.iq_requantize > 0 else None)
 
     def on(self, s):                         # (without iqRecord the flag switches nothing on; an 8-bit file needs no gain)
         return bool(s.iqRecord and s.iqRequantize) and np.dtype(s.dataType).itemsize > 1
@@ -128,6 +198,32 @@ class _Decimate(_Stage):
         ("decimBandwidth", 2.046e6),         # two-sided bandwidth of the band that is kept, Hz
         ("decimGain", 0.0),                  # 0: the gain that keeps a white input's rms
     )
+    options = (("--decimate", dict(default=None, metavar="D[:TAPS]",
+                    help="select the band around the carrier and decimate the record by D (2 .. 16) on the GPU, through a "
+                         "band-pass of TAPS taps (odd, at most 511; default: Settings.decimTaps, 127)")),
+               ("--decimate-bandwidth", dict(type=float, default=None, metavar="HZ",
+                    help="with --decimate: the two-sided bandwidth that is kept (default: Settings.decimBandwidth, 2.046e6)")))
+    needs = "--decimate-bandwidth describes the band --decimate keeps: it needs --decimate"
+    replays_file, verb = False, "resamples"
+    usage = """--decimate D[:TAPS] (D = 2 .. 16; real int8 records, or with --iq, --condition, --packed) selects the band
+--decimate-bandwidth wide (2.046 MHz) around the carrier with a TAPS-tap band-pass (127) on the GPU and keeps every D-th sample,
+behind the other preparing stages and in front of the I/Q converter and the notch: everything else runs at 1 / D of the rate.  The
+new rate, where the carrier lands, whether the band came out inverted (the Doppler then shows with the other sign) and the share
+of clipped samples are printed.  --skip stays a byte of the file, on a multiple of D frames; positions in the results are samples
+of the prepared record, D input frames each.  A --fs / --IF pair whose band would alias onto itself at this D is refused (the
+default record at D = 2 or 4: use 3 or 5)."""
+
+    def settings_from(self, args, fail):
+        D, taps = _numbers(args.decimate, ":") or (0, None)
+        if not D:                            # (D = 0 is Settings.decimation's word for "the stage is off")
+            fail("--decimate takes D[:TAPS] with D in 2 .. 16 and TAPS odd, 1 .. 511")
+        bandwidth = args.decimate_bandwidth
+        if bandwidth is not None and not (np.isfinite(bandwidth) and bandwidth > 0):
+            fail("--decimate-bandwidth takes the two-sided bandwidth in Hz, above 0")
+        return dict(decimation=D, decimTaps=taps, decimBandwidth=bandwidth)
+
+    def announce(self, file):
+        return 'Decimated by %d' % file.decimation
 
     def step(self, s):
         lanes, D = s._decim_format()[:2]
@@ -148,13 +244,26 @@ class _Decimate(_Stage):
 # of the converted record is the instant of byte n's pair: an upload from an odd one would start on a Q, read as I from there on
 class _Convert(_Stage):
     name, flag = "convert", "iqRecord"
-    reads = makes = "an I/Q pair"
+    reads = makes = "an I/Q pair (Settings.iqRecord)"
     defaults = (
         ("iqRecord", False),                 # fileName holds interleaved I/Q: samplingFreq is the COMPLEX rate, IF the baseband
                                              # offset (0 or negative allowed), dataType 'int8' or 'uint8' (offset binary)
         ("iqQFirst", False),                 # the file holds Q before I (also: spectral inversion of an I-first file)
         ("iqTaps", 63),                      # length of the interpolation filter (odd, at most 255)
     )
+    options = (("--iq", dict(nargs="?", const="iq", default=None, choices=("iq", "qi"), metavar="qi",
+                    help="the file is interleaved 8-bit I/Q (--iq=qi: Q first): --fs is the complex rate, --IF the "
+                         "baseband offset; it is converted to real IF at twice the rate on the GPU")),)
+    replays_file, verb = False, "converts"
+    usage = """--iq reads the file as interleaved 8-bit I/Q (--iq=qi: Q before I; --dtype uint8: offset binary, as an RTL-SDR
+writes it): --fs is then the COMPLEX rate and --IF the baseband offset of the carrier (0 for a zero-IF front end); the GPU turns
+the file into the equivalent real record at twice the rate, whose rate and IF are printed, and everything else runs on that."""
+
+    def settings_from(self, args, fail):
+        return dict(iqRecord=True, iqQFirst=args.iq == "qi" or None)
+
+    def announce(self, file):
+        return 'I/Q record at %.6f Msps, carrier at %+.6f MHz' % (file.samplingFreq / 1e6, file.IF / 1e6)
 
     def step(self, s):
         s._iq_format()
@@ -180,6 +289,31 @@ class _Resample(_Stage):
         ("resampCutoff", 0.0),               # cutoff of the low-pass, Hz; 0: half the lower of the two rates
         ("resampGain", 1.0),
     )
+    options = (("--resample", dict(default=None, metavar="L[/M][:TAPS]",
+                    help="bring the real int8 record to L / M of its rate on the GPU (L 2 .. 16, M 1 .. 3, M < L, coprime), "
+                         "through a low-pass of TAPS taps (odd, at most 1023; default: 24 L + 1)")),
+               ("--resample-cutoff", dict(type=float, default=None, metavar="HZ",
+                    help="with --resample: the cutoff of the low-pass (default: half the lower of the two rates)")))
+    needs = "--resample-cutoff describes the low-pass of --resample: it needs --resample"
+    replays_file, verb = False, "resamples"
+    usage = """--resample L[/M][:TAPS] (L = 2 .. 16, M = 1 .. 3 below L and coprime to it) brings the real int8 record - the
+file, or what the stages above make of it - to L / M of its rate on the GPU through a TAPS-tap low-pass (24 L + 1) that cuts off
+at --resample-cutoff (half the lower of the two rates), in front of the notch: a capture below the 15.4 samples per chip the fast
+tracking kernels need reaches them (4.096 Msps: 10, 16.368 Msps: 7/3, 2.048 Msps I/Q: --iq with 10).  The new rate and the share
+of clipped samples are printed.  --skip stays a byte of the file, on a sample that maps to a whole one (a multiple of M);
+positions in the results are samples of the resampled record."""
+
+    def settings_from(self, args, fail):
+        (L, M, taps), cutoff = _numbers(args.resample, "/:") or (0, 0, 0), args.resample_cutoff
+        if not L or taps == 0:               # (0 is Settings' word for "the stage is off" and for "the default length")
+            fail("--resample takes L[/M][:TAPS] with L in 2 .. 16, M in 1 .. 3 below L and coprime to it, and TAPS odd, "
+                 "1 .. 1023")
+        if cutoff is not None and not (np.isfinite(cutoff) and cutoff > 0):
+            fail("--resample-cutoff takes the cutoff in Hz, above 0")
+        return dict(resampleUp=L, resampleDown=1 if M is None else M, resampTaps=taps, resampCutoff=cutoff)
+
+    def announce(self, file):
+        return 'Resampled by %d/%d' % (file.resampleUp, file.resampleDown)
 
     def step(self, s):
         L, M, _ = s._resamp_format()
@@ -210,6 +344,8 @@ _NOTCH_DEFAULTS = (
 )
 
 DEFAULTS = sum((stage.defaults for stage in STAGES), ()) + _NOTCH_DEFAULTS
+# help of main's --dtype: no stage's own option, but which sample types a file may hold is what the stages above read
+DTYPE_HELP = "dataType of the file's samples (numpy name; with --iq: int8 or uint8, with --iq-requantize also int16 or float32)"
 
 
 def _multiple(n):

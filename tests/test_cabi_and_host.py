@@ -684,3 +684,56 @@ def test_acquisition_chunk_plan_covers_every_row_exactly_once():
                         assert len(seen) == n_prn * n_bins and set(seen.values()) == {1}, what
                         if queues == 2:
                             assert chunks >= 2, what
+
+
+def test_the_record_stages_share_one_binding_tail(monkeypatch):
+    """Context._stage, which all seven record stage methods go through, against a stand-in library: the record pointer
+    follows the stage's arguments, unpack's count array the record pointer, the int64 counters come last and become the
+    record's attributes; a stage whose output length the host knows says so, the others ask sgx_if_length."""
+    import weakref
+    native = pkg("_native")
+    calls = []
+
+    class Lib(object):
+        def __getattr__(self, name):
+            def fn(*args):
+                calls.append((name, args))
+                if name == "sgx_if_length":
+                    args[1]._obj.value = 4321
+                counters = [a for a in args if isinstance(getattr(a, "_obj", None), ctypes.c_int64)]
+                assert counters == list(args[len(args) - len(counters):])
+                for k, a in enumerate(counters):
+                    a._obj.value = 100 + k
+                return native.SGX_OK
+            return fn
+
+    monkeypatch.setattr(native, "lib", lambda: Lib())
+    ctx = native.Context.__new__(native.Context)
+    ctx._h, ctx._records = native._P(), weakref.WeakSet()
+    rec = native.Record(ctx, native._P(), 1000)
+    taps = np.ones(3, dtype=np.int16)
+
+    def stage_call():
+        names = [name for name, _ in calls]
+        args = calls[0][1]
+        del calls[:]
+        return names, args, [k for k, a in enumerate(args) if isinstance(getattr(a, "_obj", None), ctypes.c_void_p)]
+
+    for run, fn, asks, counters in (
+            (lambda: ctx.filter_record(rec, taps, 2), "sgx_if_filter", False, {}),
+            (lambda: ctx.iq_to_if(rec, taps, 2), "sgx_if_from_iq", False, {}),
+            (lambda: ctx.decimate(rec, 1, taps, 2, 4), "sgx_if_decimate", True, dict(clipped=100)),
+            (lambda: ctx.resample(rec, taps, 2, 5, 3), "sgx_if_resample", True, dict(clipped=100))):
+        out = run()
+        names, args, records = stage_call()
+        assert names == [fn] + ["sgx_if_length"] * asks and len(out) == (4321 if asks else 1000), fn
+        assert records == [len(args) - 1 - len(counters)], fn            # &record: behind the arguments, before the counters
+        assert dict((k, getattr(out, k)) for k in counters) == counters, fn
+    out = ctx.requantize(rec, np.int16, mult=3, shift=1)
+    assert stage_call()[0] == ["sgx_if_requantize"] and len(out) == 500 and out.clipped == 100
+    out = ctx.condition(rec, np.int16, 1, 256, np.zeros(2, dtype=native.COND_PLAN_DTYPE), 8)
+    assert stage_call()[0] == ["sgx_if_condition"] and len(out) == 500 and (out.blanked, out.clipped) == (100, 101)
+    out = ctx.unpack(rec, 2, [-3, -1, 1, 3])
+    names, args, records = stage_call()
+    assert names == ["sgx_if_unpack", "sgx_if_length"] and len(out) == 4321 and records == [len(args) - 2]
+    assert isinstance(args[-1], ctypes.c_void_p) and out.code_counts.shape == (4,) and out.code_counts.dtype == np.int64

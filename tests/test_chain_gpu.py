@@ -341,3 +341,42 @@ def test_probe_of_a_scene_behind_a_skip(tmp_path, name):
     text = r.stdout.decode(errors="replace")
     assert r.returncode == 0, text[-2000:]
     assert "%d Welch segments" % out["segments"] in text and "Tracking is over" in text, text[-2000:]
+
+
+def test_probe_of_a_record_that_only_the_conditioning_stage_prepares(tmp_path):
+    """main.main asks the table which probe to take, as postProcessing asks it which path to take: with --condition alone
+    the statistics are those of the first ten code periods of the CONDITIONED record behind skipNumberOfBytes - the
+    oracle's on the composed contract's preparation of that slice - not of the file's raw int16 samples; then the same
+    through main.main in a process of its own (full-scale noise: nothing to acquire, the run ends behind the search)."""
+    m = pkg()
+    chain = cases.matrix_chain("cond", "int16", False, False, False)
+    assert (chain.fs, chain.f0) == cases.REAL_FILE
+    offset = step_of(chain)
+    skip_bytes = cases.file_range(chain, offset, 1)[0]
+    p = cases.prepared_settings(chain, skip_bytes)
+    assert p["skipNumberOfBytes"] == offset and skip_bytes > 0
+    n = 10 * p["samplesPerCode"]
+    b = cases.full_scale_file(chain, np.random.default_rng(0xC4A1), cases.file_components(chain, offset + n))
+    assert b.size == skip_bytes + 2 * n
+    path = str(tmp_path / (chain.name + ".bin"))
+    b.tofile(path)
+    s = chain.settings(m, skipNumberOfBytes=skip_bytes, fileName=path)
+    out = pkg("main").probe_iq(s)
+    want = cases.prepare(b, chain, offset, n)
+    check_counts(s, chain, want, (chain.name, "probe"))
+    y = want["record"]
+    assert y.size == n
+    f, pxx, hist = orc.probe_stats(orc.OracleSettings(samplingFreq=want["fs"], IF=want["IF"]), y)
+    assert out["segments"] == (n - 1024) // 15360
+    assert np.array_equal(out["hist"], hist) and np.array_equal(out["f_MHz"], f)
+    assert np.max(np.abs(out["Pxx"] - pxx) / pxx) < PSD_TOL
+    assert np.array_equal(out["timeData"], y[1:p["samplesPerCode"] // 50])
+    r = subprocess.run([sys.executable, "-m", "softgnss-python_amd.main", path, "--fs", repr(chain.fs), "--IF", repr(chain.f0),
+                        "--ms", "10", "--skip", str(skip_bytes), "--condition", "--dtype", "int16"], cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, text[-2000:]
+    assert "%d Welch segments" % out["segments"] in text, text[-2000:]
+    # ... of the conditioned record: its samples' range, which the raw int16 file's (+-32768) is not
+    lo, hi = np.flatnonzero(hist)[[0, -1]] - 128
+    assert abs(lo) < 128 and hi < 127 and "samples within [%d, %d]" % (lo, hi + 1) in text, text[-2000:]

@@ -1,6 +1,6 @@
 """CPU-only checks of the front-end conditioning stage (include/sgx.h: sgx_cond_plan, and the argument refusals of
 sgx_cond_block_stats / sgx_if_condition that need no device) against the numpy contract of tests/cond_spec.py; the exports
-and the struct layouts; the contract's overflow bounds; the Settings surface and main.py's flag."""
+and the struct layouts; the contract's overflow bounds; the Settings surface."""
 import ctypes as C
 import importlib
 import os
@@ -252,7 +252,7 @@ def test_overflow_bounds_of_the_contract():
     assert (st["dc0"][0], st["p_all"][0]) == (-8, B * (16 * 128 - 8) ** 2)
 
 
-# ---- Settings, main.py -----------------------------------------------------------------------------------------------------------
+# ---- Settings --------------------------------------------------------------------------------------------------------------------
 
 def test_settings_surface(built):
     s = built.Settings()
@@ -309,27 +309,3 @@ def test_settings_surface(built):
     s.dataType = 'uint16'
     with pytest.raises(ValueError, match="int8, uint8 and int16"):
         s.postProcessing("/nonexistent/record.bin")
-
-
-def test_main_flag(built, monkeypatch, capsys):
-    main = pkg("main")
-    seen = {}
-
-    def fake_post(self, fileNameStr=None):
-        seen.update(on=self.frontEndConditioning, c=self.condBlankFactor, iq=self.iqRecord, dataType=self.dataType)
-        return None, None, None
-
-    monkeypatch.setattr(built.Settings, "postProcessing", fake_post)
-    assert main.main(["x.bin", "--no-probe", "--iq", "--dtype", "int16", "--condition"]) == 0
-    assert seen == dict(on=True, c=4.0, iq=True, dataType="int16")
-    assert main.main(["x.bin", "--no-probe", "--dtype", "int16", "--condition=3.5"]) == 0
-    assert seen == dict(on=True, c=3.5, iq=False, dataType="int16")
-    assert main.main(["x.bin", "--no-probe", "--condition=0"]) == 0
-    assert seen == dict(on=True, c=0.0, iq=False, dataType="int8")
-    assert main.main(["x.bin", "--no-probe"]) == 0
-    assert seen["on"] is False
-    for bad in (["x.bin", "--condition=0.5"], ["x.bin", "--condition=17"], ["x.bin", "--iq", "--iq-requantize", "--condition"]):
-        with pytest.raises(SystemExit):
-            main.main(bad)
-    capsys.readouterr()
-    assert "--condition" in main.__doc__

@@ -1,6 +1,6 @@
 """CPU-only checks of the decimation stage (include/sgx.h: sgx_decim_design, and the argument refusals of sgx_if_decimate
 that need no record) against the numpy contract of tests/decim_spec.py; the contract's own properties - where a tone comes
-out, what an aliasing zone leaves, the Q-first identity; the Settings surface, the skip arithmetic and main.py's options;
+out, what an aliasing zone leaves, the Q-first identity; the Settings surface and the skip arithmetic;
 and the scenes of tests/decim_cases.py shown to be well conditioned by the contracts plus the oracle alone."""
 import ctypes as C
 import importlib
@@ -472,35 +472,6 @@ def test_skip_arithmetic(built):
         assert s._prepared_settings().skipNumberOfBytes == case.lanes * cases.SKIP_GROUPS
         real = s._prepared_settings()
         assert (real.samplingFreq, real.IF) == case.prepared_rate()
-
-
-def test_main_options(built, monkeypatch, capsys):
-    main = pkg("main")
-    seen = {}
-
-    def fake_post(self, fileNameStr=None):
-        seen.clear()
-        seen.update(D=self.decimation, taps=self.decimTaps, bw=self.decimBandwidth, gain=self.decimGain, iq=self.iqRecord,
-                    fs=self.samplingFreq, IF=self.IF, skip=self.skipNumberOfBytes)
-        return None, None, None
-
-    monkeypatch.setattr(built.Settings, "postProcessing", fake_post)
-    assert main.main(["x.bin", "--no-probe", "--iq", "--fs", "16368000", "--IF", "3200000", "--decimate", "4"]) == 0
-    assert seen == dict(D=4, taps=127, bw=2.046e6, gain=0.0, iq=True, fs=16368000.0, IF=3200000.0, skip=0)
-    out = capsys.readouterr().out
-    assert "8.184000 Msps" in out and "1.154000 MHz" in out
-    assert main.main(["x.bin", "--no-probe", "--decimate", "5:63", "--decimate-bandwidth", "2.4e6", "--skip", "500"]) == 0
-    assert seen == dict(D=5, taps=63, bw=2.4e6, gain=0.0, iq=False, fs=38192000.0, IF=9548000.0, skip=500)
-    assert main.main(["x.bin", "--no-probe"]) == 0
-    assert seen["D"] == 0
-    for bad in (["x.bin", "--decimate", "1"], ["x.bin", "--decimate", "17"], ["x.bin", "--decimate", "5:64"],
-                ["x.bin", "--decimate", "5:513"], ["x.bin", "--decimate", "x"], ["x.bin", "--decimate", "5:63:2"],
-                ["x.bin", "--decimate-bandwidth", "2e6"], ["x.bin", "--decimate", "5", "--decimate-bandwidth", "0"],
-                ["x.bin", "--decimate", "5", "--correlator-bank", "0:1:0.5"]):
-        with pytest.raises(SystemExit):
-            main.main(bad)
-    capsys.readouterr()
-    assert "--decimate" in main.__doc__ and "--decimate-bandwidth" in main.__doc__
 
 
 # ---- the scenes ---------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """CPU-only checks of the requantiser in front of the I/Q converter (include/sgx.h: sgx_requant_gain, and the argument
 refusals of sgx_requant_stats_of / sgx_if_requantize that need no device) against the numpy contract of
-tests/requant_spec.py; the exports and the struct layout; the Settings surface and main.py's flags; and the int16 and
+tests/requant_spec.py; the exports and the struct layout; the Settings surface; and the int16 and
 float32 captures of tests/requant_cases.py shown to be well conditioned by the contracts plus the oracle alone.
 
 Two refusals of the C ABI look at the record itself - N not a multiple of the element width, a window that leaves the
@@ -234,29 +234,6 @@ def test_settings_surface(built):
     s.dataType, s.skipNumberOfBytes = 'int8', 3
     with pytest.raises(ValueError, match="even"):
         s.postProcessing("/nonexistent/record.bin")
-
-
-def test_main_flags(built, monkeypatch, capsys):
-    main = pkg("main")
-    seen = {}
-
-    def fake_post(self, fileNameStr=None):
-        seen.update(iqRecord=self.iqRecord, iqRequantize=self.iqRequantize, iqTargetRms=self.iqTargetRms,
-                    dataType=self.dataType, skip=self.skipNumberOfBytes)
-        return None, None, None
-
-    monkeypatch.setattr(built.Settings, "postProcessing", fake_post)
-    assert main.main(["x.bin", "--no-probe", "--iq", "--dtype", "int16", "--iq-requantize", "--skip", "4000"]) == 0
-    assert seen == dict(iqRecord=True, iqRequantize=True, iqTargetRms=12.0, dataType="int16", skip=4000)
-    assert main.main(["x.bin", "--no-probe", "--iq=qi", "--dtype", "float32", "--iq-requantize=20.5"]) == 0
-    assert seen == dict(iqRecord=True, iqRequantize=True, iqTargetRms=20.5, dataType="float32", skip=0)
-    assert main.main(["x.bin", "--no-probe", "--iq"]) == 0
-    assert seen["iqRequantize"] is False and seen["dataType"] == "int8"
-    for bad in (["x.bin", "--iq-requantize"], ["x.bin", "--iq", "--iq-requantize=0"], ["x.bin", "--iq", "--iq-requantize=128"]):
-        with pytest.raises(SystemExit):
-            main.main(bad)
-    capsys.readouterr()
-    assert "--iq-requantize" in main.__doc__
 
 
 @pytest.mark.parametrize("dtype", ["int16", "float32"])

@@ -1,7 +1,7 @@
 """CPU-only checks of the resampling stage (include/sgx.h: sgx_resamp_design, and the argument refusals of sgx_if_resample
 that need no record) against the numpy contract of tests/resamp_spec.py; the contract's own closed forms and the agreement
 of its two forms; the image rejection of the default design; which tracking kernel and which FFT length a resampled record
-reaches; the Settings surface, the skip arithmetic and main.py's options; and the scenes of tests/resamp_cases.py shown to
+reaches; the Settings surface and the skip arithmetic; and the scenes of tests/resamp_cases.py shown to
 be well conditioned by the contract plus the oracle alone."""
 import ctypes as C
 import importlib
@@ -434,41 +434,6 @@ def test_skip_arithmetic(built):
         real = s._prepared_settings()
         assert real.skipNumberOfBytes == case.skip_out(cases.SKIP_UNITS)
         assert (real.samplingFreq, real.IF) == (case.fs_out, case.scene.f0)
-
-
-def test_main_options(built, monkeypatch, capsys):
-    main = pkg("main")
-    seen = {}
-
-    def fake_post(self, fileNameStr=None):
-        seen.clear()
-        seen.update(L=self.resampleUp, M=self.resampleDown, taps=self.resampTaps, cutoff=self.resampCutoff,
-                    gain=self.resampGain, fs=self.samplingFreq, IF=self.IF, skip=self.skipNumberOfBytes)
-        return None, None, None
-
-    monkeypatch.setattr(built.Settings, "postProcessing", fake_post)
-    assert main.main(["x.bin", "--no-probe", "--fs", "4096000", "--IF", "1000000", "--resample", "10"]) == 0
-    assert seen == dict(L=10, M=1, taps=0, cutoff=0.0, gain=1.0, fs=4096000.0, IF=1000000.0, skip=0)
-    out = capsys.readouterr().out
-    assert "40.960000 Msps" in out and "1.000000 MHz" in out
-    assert main.main(["x.bin", "--no-probe", "--fs", "16368000", "--IF", "4092000", "--resample", "7/3:127",
-                      "--resample-cutoff", "7e6", "--skip", "300"]) == 0
-    assert seen == dict(L=7, M=3, taps=127, cutoff=7e6, gain=1.0, fs=16368000.0, IF=4092000.0, skip=300)
-    assert "38.192000 Msps" in capsys.readouterr().out
-    assert main.main(["x.bin", "--no-probe", "--fs", "4096000", "--IF", "1000000", "--resample", "10:121"]) == 0
-    assert (seen["L"], seen["M"], seen["taps"]) == (10, 1, 121)
-    assert main.main(["x.bin", "--no-probe"]) == 0
-    assert seen["L"] == 0
-    for bad in (["x.bin", "--resample", "1"], ["x.bin", "--resample", "17"], ["x.bin", "--resample", "4/2"],
-                ["x.bin", "--resample", "7/4"], ["x.bin", "--resample", "2/3"], ["x.bin", "--resample", "10:240"],
-                ["x.bin", "--resample", "10:1025"], ["x.bin", "--resample", "x"], ["x.bin", "--resample", "10/1:121:2"],
-                ["x.bin", "--resample", "10/"], ["x.bin", "--resample-cutoff", "2e6"],
-                ["x.bin", "--resample", "10", "--resample-cutoff", "0"],
-                ["x.bin", "--resample", "10", "--correlator-bank", "0:1:0.5"]):
-        with pytest.raises(SystemExit):
-            main.main(bad)
-    capsys.readouterr()
-    assert "--resample" in main.__doc__ and "--resample-cutoff" in main.__doc__
 
 
 # ---- the scenes ---------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """CPU-only checks of the unpacker (include/sgx.h: sgx_unpack_table, and the argument refusals of sgx_if_unpack that need no
 device) against the numpy contract of tests/unpack_spec.py; the contract's own pack / unpack round trips; the exports; the
-Settings surface, the skip arithmetic and main.py's options; and the packed records of tests/unpack_cases.py shown to be
+Settings surface and the skip arithmetic; and the packed records of tests/unpack_cases.py shown to be
 well conditioned by the contracts plus the oracle alone.
 
 One refusal of the C ABI looks at the record itself - fields that do not fill whole frames - and a record exists only on a
@@ -263,39 +263,6 @@ def test_skip_arithmetic(built):
         assert case.file_bytes(cases.SKIP_SAMPLES) % max(1, case.frame * case.bits // 8) == 0
         s = case.settings(built, skipNumberOfBytes=case.file_bytes(cases.SKIP_SAMPLES))
         assert s._prepared_settings().skipNumberOfBytes == cases.SKIP_SAMPLES
-
-
-def test_main_options(built, monkeypatch, capsys):
-    main = pkg("main")
-    seen = {}
-
-    def fake_post(self, fileNameStr=None):
-        seen.clear()
-        seen.update(bits=self.packedBits, enc=self.packedEncoding, lsb=self.packedLsbFirst, frame=self.packedFrame,
-                    first=self.packedFirst, peak=self.packedPeak, iq=self.iqRecord, dataType=self.dataType,
-                    skip=self.skipNumberOfBytes)
-        return None, None, None
-
-    monkeypatch.setattr(built.Settings, "postProcessing", fake_post)
-    assert main.main(["x.bin", "--no-probe", "--packed", "2", "--iq", "--fs", "4096000", "--IF", "0"]) == 0
-    assert seen == dict(bits=2, enc="sign-magnitude", lsb=False, frame=1, first=0, peak=48, iq=True, dataType="int8", skip=0)
-    assert main.main(["x.bin", "--no-probe", "--packed", "4", "--packed-encoding", "twos-complement", "--packed-lsb-first",
-                      "--packed-frame", "4:2", "--packed-peak", "63", "--iq", "--skip", "2000"]) == 0
-    assert seen == dict(bits=4, enc="twos-complement", lsb=True, frame=4, first=2, peak=63, iq=True, dataType="int8", skip=2000)
-    assert main.main(["x.bin", "--no-probe", "--packed", "1", "--packed-frame", "8"]) == 0
-    assert (seen["bits"], seen["frame"], seen["first"], seen["iq"]) == (1, 8, 0, False)
-    assert main.main(["x.bin", "--no-probe"]) == 0
-    assert seen["bits"] == 0
-    for bad in (["x.bin", "--packed", "3"], ["x.bin", "--packed-peak", "48"], ["x.bin", "--packed-lsb-first"],
-                ["x.bin", "--packed", "2", "--packed-frame", "3"], ["x.bin", "--packed", "2", "--packed-frame", "4:4"],
-                ["x.bin", "--packed", "2", "--iq", "--packed-frame", "4:3"], ["x.bin", "--packed", "2", "--packed-frame", "x"],
-                ["x.bin", "--packed", "2", "--packed-peak", "2"], ["x.bin", "--packed", "2", "--packed-peak", "128"],
-                ["x.bin", "--packed", "2", "--packed-encoding", "gray"], ["x.bin", "--packed", "2", "--condition"],
-                ["x.bin", "--packed", "2", "--iq", "--iq-requantize"], ["x.bin", "--packed", "2", "--dtype", "int16"]):
-        with pytest.raises(SystemExit):
-            main.main(bad)
-    capsys.readouterr()
-    assert "--packed" in main.__doc__ and "--packed-frame" in main.__doc__
 
 
 @pytest.mark.parametrize("name", sorted(cases.CASES))
