@@ -24,13 +24,9 @@ def hipcc():
     return "hipcc"
 
 
-def check_trk3_registers(extra=(), cc=None):
-    """Build gate for csrc/sgx_trk3.hip: the filter waves' polls leave loads in flight whose destinations are the PHYSICAL
-    registers v[244:255]; nothing the compiler allocates may touch them.  Compiles the file to assembly (with `extra`
-    flags in front of the build's own) and returns (ok, message): not ok if v244..v255 appear outside an inline-asm
-    statement, or if the kernel spills vector registers or uses AGPRs.  Run by build(), tools/build_variant.sh (through
-    tools/check_trk3_regs.py) and tests/test_cabi_and_host.py."""
-    import re
+def trk3_assembly(extra=(), cc=None):
+    """csrc/sgx_trk3.hip compiled to gfx950 assembly with `extra` flags in front of the build's own: (True, text), or
+    (False, the end of the compiler's messages)."""
     import tempfile
     cc = cc or hipcc()
     with tempfile.TemporaryDirectory() as d:
@@ -40,35 +36,96 @@ def check_trk3_registers(extra=(), cc=None):
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         if r.returncode != 0:
             return False, r.stderr.decode(errors="replace")[-2000:]
-        reserved = re.compile(r"\bv(24[4-9]|25[0-5])\b|\bv\[(\d+):(\d+)\]")
-        in_asm, hits_in, hits_out, spills, agprs = False, 0, [], None, None
-        for line in open(out):
-            t = line.strip()
-            if t.startswith(";;#ASMSTART"):
-                in_asm = True
-            elif t.startswith(";;#ASMEND"):
-                in_asm = False
-            elif t.startswith(".vgpr_spill_count:"):
-                spills = int(t.split(":")[1])
-            elif t.startswith(".agpr_count:"):
-                agprs = int(t.split(":")[1])
+        with open(out) as f:
+            return True, f.read()
+
+
+def trk3_kernels(text):
+    """The kernels of that assembly, one per instantiation of trk3_kernel: {name: {"body": [instruction lines], "meta": {key:
+    value of the kernel's amdhsa.kernels entry}, "args": [{key: value} per kernel argument, in order]}}."""
+    import re
+    kernels, name = {}, None
+    for line in text.splitlines():
+        t = line.strip()
+        m = re.match(r"^(\w*trk3_kernel\w*):", t)
+        if m and name is None:
+            name = m.group(1)
+            kernels[name] = {"body": [], "meta": {}, "args": []}
+        elif name is not None:
+            if t.startswith(".Lfunc_end"):
+                name = None
             elif t and not t.startswith((";", ".")):
-                for mm in reserved.finditer(t):
-                    if mm.group(1) or (int(mm.group(3)) >= 244 and int(mm.group(2)) <= 255):
-                        if in_asm:
-                            hits_in += 1
-                        else:
-                            hits_out.append(t)
-                        break
+                kernels[name]["body"].append(t)
+    # the metadata: a YAML list under "amdhsa.kernels:", an entry per kernel ("  - .key: value"), its ".args:" a list inside
+    entries, cur, arg, in_args = [], None, None, False
+    for line in text[text.find("amdhsa.kernels:"):].splitlines()[1:]:
+        m = re.match(r"^(\s*)(- )?(\.[\w.]+):\s*(.*)$", line)
+        if not m:
+            if line.startswith("amdhsa."):
+                break
+            continue
+        indent, dash, key, val = len(m.group(1)), bool(m.group(2)), m.group(3), m.group(4).strip()
+        if indent == 2 and dash:
+            cur, in_args = {"args": []}, False
+            entries.append(cur)
+        if cur is None:
+            continue
+        if key == ".args":
+            in_args = True
+        elif in_args and indent >= 6:
+            if dash:
+                arg = {}
+                cur["args"].append(arg)
+            arg[key] = val
+        else:
+            in_args = False
+            cur[key] = val
+    for e in entries:
+        if e.get(".name") in kernels:
+            kernels[e[".name"]]["meta"], kernels[e[".name"]]["args"] = e, e["args"]
+    return kernels
+
+
+def check_trk3_registers(extra=(), cc=None):
+    """Build gate for csrc/sgx_trk3.hip: the filter waves' polls leave loads in flight whose destinations are the PHYSICAL
+    registers v[244:255]; nothing the compiler allocates may touch them.  Compiles the file to assembly (with `extra`
+    flags in front of the build's own) and returns (ok, message): not ok if v244..v255 appear outside an inline-asm
+    statement in ANY kernel of the file (the scan is over the whole text), or if ANY of them spills vector registers or uses
+    AGPRs (every kernel's metadata entry is looked at, not the last one's).  Run by build(), tools/build_variant.sh (through
+    tools/check_trk3_regs.py), tests/test_cabi_and_host.py and tests/test_trk3_cases_host.py."""
+    import re
+    ok, text = trk3_assembly(extra, cc)
+    if not ok:
+        return False, text
+    reserved = re.compile(r"\bv(24[4-9]|25[0-5])\b|\bv\[(\d+):(\d+)\]")
+    in_asm, hits_in, hits_out, spills, agprs = False, 0, [], [], []
+    for line in text.splitlines():
+        t = line.strip()
+        if t.startswith(";;#ASMSTART"):
+            in_asm = True
+        elif t.startswith(";;#ASMEND"):
+            in_asm = False
+        elif t.startswith(".vgpr_spill_count:"):
+            spills.append(int(t.split(":")[1]))
+        elif t.startswith(".agpr_count:"):
+            agprs.append(int(t.split(":")[1]))
+        elif t and not t.startswith((";", ".")):
+            for mm in reserved.finditer(t):
+                if mm.group(1) or (int(mm.group(3)) >= 244 and int(mm.group(2)) <= 255):
+                    if in_asm:
+                        hits_in += 1
+                    else:
+                        hits_out.append(t)
+                    break
     if hits_in < 10:
         return False, "the polls' asm statements were not found (%d lines on v[244:255])" % hits_in
     if hits_out:
         return False, "v[244:255] are used outside the polls' asm statements, e.g. '%s' (%d lines)" % (hits_out[0], len(hits_out))
-    if spills != 0:
-        return False, "trk3_kernel spills %s vector registers" % spills
-    if agprs not in (0, None):
+    if not spills or any(spills):
+        return False, "trk3_kernel spills %s vector registers" % (spills or None)
+    if any(agprs):
         return False, "trk3_kernel uses %s AGPRs" % agprs
-    return True, "v[244:255] untouched outside the polls (%d lines inside), no spills" % hits_in
+    return True, "v[244:255] untouched outside the polls (%d lines inside), no spills in %d kernels" % (hits_in, len(spills))
 
 
 def needs_build():

@@ -89,7 +89,7 @@ static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
 
 // The environment a tracking call reads, once at its entry: diagnosis switches and test hooks (sgx_track_plan ignores them)
 struct TrkEnv {
-    bool trace, float_typed, v3_off, fast_xcd, profile, stream, withhold, stall;
+    bool trace, float_typed, v3_off, v3_generic, fast_xcd, profile, stream, withhold, stall, scatter;
     int split, arms, lds_pad;
     char timeout;
 };
@@ -108,6 +108,7 @@ static TrkEnv trk_env() {
     E.split = (split && atoi(split) >= 1) ? atoi(split) : 0;
     E.arms = arms ? (arms[0] == '3' ? 3 : 1) : 0;
     E.v3_off = first("SGX_TRK_V3") == '0';
+    E.v3_generic = first("SGX_TRK3_GENERIC") == '1';       // the speculative kernel's generic text for every case (tests, A/B)
     E.fast_xcd = first("SGX_TRK_FASTX") != '0';            // '0': no same-XCD exchange path
     E.profile = first("SGX_TRK_PROFILE") == '1';           // the kernels' phase cycles on stderr
     E.lds_pad = lds ? atoi(lds) : 90112;                   // dynamic LDS per cooperative workgroup; default: one per CU
@@ -115,6 +116,7 @@ static TrkEnv trk_env() {
     E.withhold = first("SGX_TRK_TEST_WITHHOLD") == '1';    // test hooks: launch without each channel's last member; ...
     E.timeout = first("SGX_TRK_TEST_TIMEOUT");             // ... '1' the first launch times out, '2' the one after a stall;
     E.stall = first("SGX_TRK_TEST_STALL") == '1';          // ... the first launch's stream stalls
+    E.scatter = first("SGX_TRK_TEST_SCATTER") == '1';      // ... the speculative kernel's headline text finds its members scattered
     return E;
 }
 
@@ -182,11 +184,12 @@ static TrkPlan trk_plan(const sgx_settings& S, int kind, int n_ch, long long n_c
     return P;
 }
 
-// What the launches of a call have established: each cause of a repeated launch (at most four launches in all)
+// What the launches of a call have established: each cause of a repeated launch (at most five launches in all)
 struct TrkRepeat {
     bool stream_stalled = false;   // a streaming record's watermark stalled: the launch was repeated on the resident record
     bool one_member = false;       // a member of a cooperative layout timed out: one workgroup per channel from then on
     bool v3_off = false;           // too strong for the speculative kernel's fixed point: the round-3 kernel from then on
+    bool scattered = false;        // a channel's members do not share an XCD: the speculative kernel's generic text from then on
 };
 
 // One launch: the kernel that runs (2, 3, 4, 5 or 6), its layout, and the CUs reserved for it
@@ -425,6 +428,15 @@ static int trk_repeat(TrkCall& T, int launch, const int words[2], bool& again) {
         return SGX_OK;
     }
     h_err &= ~TRK_ERR_SCALE;
+    if ((h_err & TRK_ERR_PLACE) && !R.scattered) {
+        // the speculative kernel's headline text takes every member of a channel to sit on one XCD (its exchange stays in
+        // that L2); the placement check at the kernel's start found otherwise: the generic text asks at run time
+        fprintf(stderr, "[sgx] tracking: a channel's workgroups do not share an XCD; repeating the launch with the "
+                        "speculative kernel's generic text\n");
+        R.scattered = again = true;
+        return SGX_OK;
+    }
+    h_err &= ~TRK_ERR_PLACE;
     if ((h_err & TRK_ERR_RANGE) == 0) h_err &= 0xFFFF;
     if (h_err & TRK_ERR_RANGE) {
         sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
@@ -511,7 +523,10 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
         break;
     case 3: sgx_trk_tp_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
     case 4: sgx_trk_multi_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
-    case 5: sgx_trk3_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.E.lds_pad); break;
+    case 5:
+        sgx_trk3_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.E.lds_pad,
+                        T.E.v3_generic || T.rep.scattered, T.E.scatter);
+        break;
     case 6: sgx_trk_any_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
     }
     hipEventRecord(c->ev[4], st);
@@ -642,8 +657,8 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
     CuGuard reserved{c->device, 0};
     bool again = true;
-    // at most four launches: a repeat has a cause in T.rep (trk_repeat), said on stderr
-    for (int launch = 0; launch < 4 && again; ++launch) {
+    // at most five launches: a repeat has a cause in T.rep (trk_repeat), said on stderr
+    for (int launch = 0; launch < 5 && again; ++launch) {
         rc = trk_launch_once(T, launch, reserved, again);
         if (rc != SGX_OK) return rc;
     }

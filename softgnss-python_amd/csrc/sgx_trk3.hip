@@ -123,6 +123,27 @@ struct T3Shared {
 #endif
 };
 
+// ONE KERNEL TEXT PER CASE.  What a launch is - offset-binary samples (uns), every member of a channel on one XCD (fast), a
+// record that is still streaming in (stream), SGX_TRK_PROFILE=1 (prof) - is the same for every block of it, but a role that
+// tests these values inside its block loop pays for each test there: a lone wave waits 10-20 cycles when it issues an
+// instruction right behind one it depends on through SCC, VCC or EXEC, and the tests sit behind the filter waves' polls and
+// the map waves' publish.  So the roles are templates on a case, and a case that is not `generic` has the four values as
+// constants: its text holds neither the tests nor the branches not taken.  Two kernels are instantiated:
+//   T3Headline  int8, resident, one XCD per channel, no profile: what bench.py and every plain int8 call launch.  Where
+//               the members sit is only known once the kernel runs: if its placement check finds a channel scattered
+//               over XCDs, the channel stops before block 0 with TRK_ERR_PLACE and the host repeats the launch with the
+//               generic text (sgx_trk.hip: trk_repeat).  (The generic roles as a second path INSIDE this kernel were
+//               tried first: the two sets of roles together took 81 scalar registers to spill against 44, and the map
+//               role reached into v[244:255].)
+//   T3Generic   the four values read at run time, as before: uint8, streaming, SGX_TRK_FASTX=0, SGX_TRK_PROFILE=1 and any
+//               combination of them, and the headline case under SGX_TRK3_GENERIC=1 (tests, A/B).  One generic kernel
+//               and not one per combination: a kernel is 31 KB of text, and sixteen of them serve nobody.
+struct T3Case { bool uns, fast, stream, prof, generic; };
+struct T3Headline { static constexpr T3Case is{false, true, false, false, false}; };
+struct T3Generic { static constexpr T3Case is{false, false, false, false, true}; };
+// a case's value: its constant, or for the generic case what the launch says
+#define T3_IS(Case, field, rt) (Case::is.generic ? (rt) : Case::is.field)
+
 // -DTRK_WAVEPROF: how long after the barrier's release each wave of (channel 0, member 0) arrives at the next one
 #ifdef TRK_WAVEPROF
 #define T3_WB_ON(unit, ch) ((unit) == 0 && (ch) == 0)
@@ -247,6 +268,9 @@ __device__ __forceinline__ int t3_carr_mult(int lane, int unit, int head) {
 }
 
 // ================================ MAP (waves 0-1: set 0, waves 2-3: set 1) ================================
+// (The hardware puts wave w on SIMD w % 4: set 0 shares its SIMDs with the PLL wave (4) and the DLL wave (5), set 1 with the
+// record wave (6) and nobody.  set = wave & 1 - one wave of each set beside a filter wave in every block - was measured:
+// 43.52 ms against 42.43, bit-identical series)
 // A lone wave pays ~9 cycles per operation for a compare + select pair through VCC and ~5 for anything else
 // (tools/ubench_fp64.hip), so everything per-lane below is ARITHMETIC: masks from shifts and bit-field extracts, selects
 // on the high dwords of doubles whose low dwords are zero (+-1, +-2, 0, half-integers) by v_bfi, clamps by min / max.
@@ -309,12 +333,14 @@ __device__ __forceinline__ void t3_reduce6(const unsigned long long (&q)[6], uns
     l = ((unsigned long long)l1 << 32) | l0;
 }
 
-template <int SB>
+template <int SB, class Case>
 __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict__ rec, long long rec_alloc, int ms,
                                            long long pos0, int unit, int set, int tid, unsigned long long* __restrict__ xbase,
-                                           bool fast, double step_nom, double spacing, bool uns, bool prof_on,
-                                           bool prof_any, bool wb_on, int* __restrict__ err) {
+                                           bool fast_rt, double step_nom, double spacing, bool uns_rt, bool prof_on,
+                                           bool prof_any_rt, bool wb_on, int* __restrict__ err) {
     static_assert(SB == 1, "one-byte samples");
+    // (constants unless the case is the generic one: every test of them below is then decided when the text is made)
+    const bool uns = T3_IS(Case, uns, uns_rt), fast = T3_IS(Case, fast, fast_rt), prof_any = T3_IS(Case, prof, prof_any_rt);
     const int lane = tid & 63;
     const long long limit = rec_alloc - 16;                  // bytes: the last 16-byte word that may be loaded
     const int g = (tid & (T3_LANES - 1)) + unit * T3_LANES;  // the lane's group inside the block's aligned window
@@ -1069,10 +1095,14 @@ __device__ __forceinline__ int t3_poll2(unsigned long long& x1, unsigned long lo
 // Lane = 32 word + unit polls that unit's granule of I_P (word 0) / Q_P (word 1).  The next block's tables are computed
 // IN FULL for the current rate while the wave waits for the sums; the rate step then turns every entry (W3 by 7.5
 // samples more: the map's moments are taken about the group's centre).
+template <class Case>
 __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const TrkChan& cc, int unit, bool owner, int lane,
                                            int P, int ch, unsigned long long* __restrict__ xbase, int* __restrict__ err,
-                                           bool prof_on, long long* __restrict__ prof, bool wb_on) {
+                                           bool prof_on, long long* __restrict__ prof_rt, bool wb_on) {
     (void)wb_on;
+    // (a case without the profile never looks at the buffer: no test of the pointer behind the poll or in front of the barrier)
+    long long* const prof = T3_IS(Case, prof, true) ? prof_rt : nullptr;
+    const bool uns = T3_IS(Case, uns, K.uns != 0);
     // tracking.py:123-130
     long long acc_map = 0, acc_xch = 0, acc_flt = 0, t_top = 0, t_arr = 0;   // SGX_TRK_PROFILE=1: per-member phase times
     double carrBasis = cc.acquiredFreq;
@@ -1102,7 +1132,7 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
     T2_PIN(ak.c0); T2_PIN(ak.c1); T2_PIN(ak.c2); T2_PIN(ak.c3); T2_PIN(ak.c4); T2_PIN(ak.c5); T2_PIN(ak.c6); T2_PIN(ak.c7); T2_PIN(ak.c8);
     T2_PIN(rk.s0); T2_PIN(rk.s1); T2_PIN(rk.s2); T2_PIN(rk.s3); T2_PIN(rk.s4); T2_PIN(rk.s5);
     T2_PIN(rk.c0); T2_PIN(rk.c1); T2_PIN(rk.c2); T2_PIN(rk.c3); T2_PIN(rk.c4); T2_PIN(rk.c5);
-    double unfix = 1.0 / (K.uns != 0 ? T3_FIX * 0.5 : T3_FIX);
+    double unfix = 1.0 / (uns ? T3_FIX * 0.5 : T3_FIX);
     T2_PIN(unfix);
     const bool w3 = lane >= 48;
     double ctr_fs = w3 ? 7.5 * K.inv_fs : 0.0;   // the map's moments are taken about the group's centre
@@ -1325,12 +1355,16 @@ struct T3DllConst {
     long long rec_len;
 };
 
+template <class Case>
 __device__ __forceinline__ int t3_dll_role(T3Shared& S, const TrkConst& K, const T3DllConst& D, long long pos0, int blk0,
                                            int stop0, bool owner, int lane, int P, int ch,
                                            unsigned long long* __restrict__ xbase, int* __restrict__ err, bool prof_on,
-                                           long long file_off, bool wb_on, long long* __restrict__ prof = nullptr,
+                                           long long file_off, bool wb_on, long long* __restrict__ prof_rt = nullptr,
                                            int unit = -1) {
-    (void)wb_on; (void)prof; (void)unit;
+    (void)wb_on; (void)unit;
+    long long* const prof = T3_IS(Case, prof, true) ? prof_rt : nullptr;
+    (void)prof;
+    const bool uns = T3_IS(Case, uns, K.uns != 0);
     // tracking.py:114-121; block 0's chain part and ramp starts were posted before the loop
     double oldCodeNco = 0.0, oldCodeErr = 0.0;
     double k_a = K.k_code_a, k_b = K.k_code_b, basis = K.code_basis;
@@ -1343,7 +1377,7 @@ __device__ __forceinline__ int t3_dll_role(T3Shared& S, const TrkConst& K, const
     const int l4 = lane & 3;
     const double off = (l4 == 0) ? -D.spacing : ((l4 == 2) ? D.spacing : 0.0);   // rem - spc == rem + (-spc) exactly
     const int lim3 = K.n_units * T3_UNIT - 15;             // the longest block the units of the launch hold
-    double unfix = 1.0 / (K.uns != 0 ? T3_FIX * 0.5 : T3_FIX);
+    double unfix = 1.0 / (uns ? T3_FIX * 0.5 : T3_FIX);
     T2_PIN(unfix);
     const bool mine = (lane & 31) < P;
     unsigned long long* const xabort = xbase + T3_XABORT;
@@ -1588,10 +1622,12 @@ __device__ __forceinline__ void t3_rec_store(T3Shared& S, int k, long long m, in
 // one block ahead and cannot afford more registers in flight; this wave, idle otherwise, touches the unit's cache lines
 // THREE blocks ahead (one dword per 128-byte line, one load instruction per block, result never read), so that the map
 // waves' requests find the lines in L2 and the translation cached.
+template <class Case>
 __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const int8_t* __restrict__ rec, int unit, int ch,
                                            bool owner, int lane, double* __restrict__ o, int* __restrict__ err,
                                            unsigned long long mark_seen, bool wb_on) {
     (void)wb_on;
+    const bool stream = T3_IS(Case, stream, K.mark != nullptr), uns = T3_IS(Case, uns, K.uns != 0);
     const long long m = K.ms;
     const int ms = K.ms;
     const long long span = 2ll * K.n_units * T3_UNIT + 64;   // bytes: a block and the window of the prefetch behind it
@@ -1606,10 +1642,10 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
         if (lane < 20) {
             long long a = ((C.pos + 6ll * C.blk) & ~127ll) + (long long)unit * T3_UNIT + 128ll * (lane - 1);
             a = a < 0 ? 0 : (a > limit ? limit : a);
-            if (K.mark == nullptr || (unsigned long long)(a + 128) <= mark_seen)   // (a streaming record: only what is resident)
+            if (!stream || (unsigned long long)(a + 128) <= mark_seen)   // (a streaming record: only what is resident)
                 asm volatile("global_load_dword %0, %1, off" : "+v"(dummy) : "v"(rec + a) : "memory");
         }
-        if (K.mark != nullptr && K.uns == 0) {
+        if (stream && !uns) {
             // THE SCALE GUARD (see T3_FIX) of a STREAMING int8 record (a resident one has been scanned once by the host,
             // sgx_trk.hip: if_mag_bound): the magnitudes of the unit's 2 048 bytes of THIS block (its aligned window: an
             // L2 hit, the map waves read them two blocks ago) - signed bytes as |(b ^ 0x80) - 0x80| by v_sad_u8, a DPP
@@ -1621,7 +1657,7 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
             long long a = (C.pos & ~15ll) + (long long)unit * T3_UNIT + 32ll * lane;
             const long long top = limit - 16;
             a = a < 0 ? 0 : (a > top ? top : a);
-            if (K.mark == nullptr || (unsigned long long)(a + 32) <= mark_seen) {
+            if ((unsigned long long)(a + 32) <= mark_seen) {
                 const uint4 w0 = *reinterpret_cast<const uint4*>(rec + a);
                 const uint4 w1 = *reinterpret_cast<const uint4*>(rec + a + 16);
                 const unsigned bias = 0x80808080u;
@@ -1646,7 +1682,7 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
             }
         }
         if (owner && it > 0) t3_rec_store(S, it - 1, m, lane, o, err, ch);
-        {   // (a resident record: mark_seen is all ones and this returns at once)
+        if (stream) {   // (a resident record has nothing to wait for)
             const long long need = C.pos + 4 * span;
             wait_mark(K.mark, need < K.rec_len ? need : K.rec_len, mark_seen, err, ch);
         }
@@ -1657,7 +1693,26 @@ __device__ __forceinline__ int t3_rec_role(T3Shared& S, const TrkConst& K, const
     return it;
 }
 
+// A workgroup's wave takes its role for the whole launch
+template <class Case>
+__device__ __forceinline__ int t3_roles(T3Shared& S, const TrkConst& K, const T3DllConst& D, const TrkChan& cc,
+                                        const int8_t* __restrict__ rec, double* __restrict__ o, int unit, int ch, int tid,
+                                        int blk0, int stop0, bool fast, bool prof_on, long long* __restrict__ prof,
+                                        unsigned long long mark_seen, bool wb_on, unsigned long long* __restrict__ xbase,
+                                        int* __restrict__ err) {
+    const int wave = tid >> 6, lane = tid & 63, P = K.split;
+    const bool owner = unit == 0;
+    if (wave < 4)
+        return t3_map_role<1, Case>(S, rec, K.rec_alloc, K.ms, cc.pos0, unit, wave >> 1, tid, xbase, fast, K.code_basis / K.fs,
+                                    K.spacing, K.uns != 0, prof_on, prof != nullptr, wb_on, err);
+    if (wave == 4) return t3_pll_role<Case>(S, K, cc, unit, owner, lane, P, ch, xbase, err, prof_on, prof, wb_on);
+    if (wave == 5)
+        return t3_dll_role<Case>(S, K, D, cc.pos0, blk0, stop0, owner, lane, P, ch, xbase, err, prof_on, K.file_off, wb_on, prof, unit);
+    return t3_rec_role<Case>(S, K, rec, unit, ch, owner, lane, o, err, mark_seen, wb_on);
+}
+
 // A channel has P = K.split = K.n_units members, member = unit.
+template <class Case>
 __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restrict__ rec, const int8_t* __restrict__ codes,
                                                           const TrkChan* __restrict__ chans, double* __restrict__ out,
                                                           int* __restrict__ ms_done, TrkConst K,
@@ -1679,7 +1734,8 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
     }
     unsigned long long* __restrict__ xbase = xch + (long long)ch * T3_XCH_STRIDE;   // granules, abort word, placement granules
     unsigned long long* const xabort = xbase + T3_XABORT;
-    const bool prof_on = (owner && ch == 0 && prof != nullptr && (wave == 0 || wave == 4 || wave == 5));
+    const bool prof_on = (owner && ch == 0 && T3_IS(Case, prof, prof != nullptr) && (wave == 0 || wave == 4 || wave == 5));
+    const bool stream = T3_IS(Case, stream, K.mark != nullptr);
 
     if (tid < 4) {
         S.flag[tid] = 0;
@@ -1727,11 +1783,18 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
         }
         const bool same = __all(lane >= P || (unsigned)(x & 0xF) == me);
         if (lane == 0) {
-            S.flag[0] = (same && !gave_up && K.fast_xcd != 0) ? 1 : 0;
+            const bool one_xcd = same && !gave_up && K.fast_xcd != 0;
+            S.flag[0] = one_xcd ? 1 : 0;
             if (gave_up) {   // a member is not resident: give the channel up at once (the host repeats with split 1)
                 S.flag[1] = 1;
                 atomicCAS(err, 0, 1 + ch);
                 __hip_atomic_store(xabort, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (!Case::is.generic && Case::is.fast && !one_xcd) {
+                // a text made for one XCD per channel, and the members are scattered: the channel stops before block 0
+                // (every member has seen the same placement granules and decides alike) and the host repeats the launch
+                // with the generic text
+                S.flag[1] = 1;
+                atomicOr(err, TRK_ERR_PLACE);
             }
         }
     }
@@ -1773,8 +1836,8 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
         S.carr[0].T[lane] = make_double2(cs, sn);
     }
     // a streaming record: block 0 and the requests made for blocks 1 and 2 must be resident before the first loads
-    unsigned long long mark_seen = K.mark ? 0ull : ~0ull;
-    if (wave == 6 && K.mark) {
+    unsigned long long mark_seen = stream ? 0ull : ~0ull;
+    if (wave == 6 && stream) {
         const long long need = cc.pos0 + 4 * (2ll * K.n_units * T3_UNIT + 64);
         wait_mark(K.mark, need < K.rec_len ? need : K.rec_len, mark_seen, err, ch);
     }
@@ -1783,15 +1846,7 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
     double* __restrict__ o = out + (long long)ch * SGX_NUM_SERIES * K.ms;
     const bool wb_on = T3_WB_ON(unit, ch);
     int done;
-    if (wave < 4)
-        done = t3_map_role<1>(S, rec, K.rec_alloc, K.ms, cc.pos0, unit, wave >> 1, tid, xbase, fast, K.code_basis / K.fs,
-                              K.spacing, K.uns != 0, prof_on, prof != nullptr, wb_on, err);
-    else if (wave == 4)
-        done = t3_pll_role(S, K, cc, unit, owner, lane, P, ch, xbase, err, prof_on, prof, wb_on);
-    else if (wave == 5)
-        done = t3_dll_role(S, K, D, cc.pos0, blk0, stop0, owner, lane, P, ch, xbase, err, prof_on, K.file_off, wb_on, prof, unit);
-    else
-        done = t3_rec_role(S, K, rec, unit, ch, owner, lane, o, err, mark_seen, wb_on);
+    done = t3_roles<Case>(S, K, D, cc, rec, o, unit, ch, tid, blk0, stop0, fast, prof_on, prof, mark_seen, wb_on, xbase, err);
 
 #ifdef T3_TIMELINE
     __syncthreads();
@@ -1808,10 +1863,26 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
 
 // n_blocks = 8-padded channels x K.split workgroups; lds_pad: extra dynamic LDS per workgroup, so that a CU holds ONE
 // workgroup of the launch (members must not share a CU: they would share its issue ports)
+template <class Case>
+static void t3_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans, double* out,
+                      int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err, int lds_pad) {
+    if (lds_pad > 0)
+        (void)hipFuncSetAttribute((const void*)trk3_kernel<Case>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_pad);
+    trk3_kernel<Case><<<n_blocks, T3_THREADS, (size_t)(lds_pad > 0 ? lds_pad : 0), st>>>(rec, codes, chans, out, done, K, prof, xch, err);
+}
+
+// generic: the launch's values are read at run time whatever they are (SGX_TRK3_GENERIC=1, or a launch repeated after
+// TRK_ERR_PLACE); otherwise the headline case gets its own text and every other case the generic one.  test_scatter (a test
+// hook): the headline text is told that its members do not share an XCD.
 void sgx_trk3_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                      double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
-                     int lds_pad) {
-    if (lds_pad > 0)
-        (void)hipFuncSetAttribute((const void*)trk3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_pad);
-    trk3_kernel<<<n_blocks, T3_THREADS, (size_t)(lds_pad > 0 ? lds_pad : 0), st>>>(rec, codes, chans, out, done, K, prof, xch, err);
+                     int lds_pad, bool generic, bool test_scatter) {
+    const bool headline = K.uns == 0 && K.fast_xcd != 0 && K.mark == nullptr && prof == nullptr;
+    if (headline && !generic) {
+        TrkConst Kh = K;
+        if (test_scatter) Kh.fast_xcd = 0;
+        t3_launch<T3Headline>(n_blocks, st, rec, codes, chans, out, done, Kh, prof, xch, err, lds_pad);
+    } else {
+        t3_launch<T3Generic>(n_blocks, st, rec, codes, chans, out, done, K, prof, xch, err, lds_pad);
+    }
 }

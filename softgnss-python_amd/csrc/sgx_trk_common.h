@@ -75,10 +75,11 @@ struct TrkConst {
 void sgx_trk2_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                      double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
                      int sample_bytes, int arms, int lds_pad);
-// sgx_trk3.hip: the speculative latency-mode kernel, one workgroup per unit of 128 groups for all three arms
+// sgx_trk3.hip: the speculative latency-mode kernel, one workgroup per unit of 128 groups for all three arms (generic: the
+// text that reads the launch's case at run time, also where the case has a text of its own; test_scatter: a test hook)
 void sgx_trk3_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                      double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err,
-                     int lds_pad);
+                     int lds_pad, bool generic, bool test_scatter);
 // sgx_trk_tp.hip: the throughput-mode kernel, one workgroup per channel
 void sgx_trk_tp_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                        double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
@@ -292,6 +293,7 @@ __device__ __forceinline__ void granule_store(unsigned long long* p, unsigned lo
 // once per several hundred blocks and not once per block.
 #define TRK_ERR_STREAM 0x40000000   // error word: the watermark of a streaming record did not advance in time
 #define TRK_ERR_RANGE 0x20000000    // error word: a block is longer than the units the launch provides
+#define TRK_ERR_PLACE 0x08000000    // error word: a channel's members do not share an XCD, which the kernel text launched takes for granted (sgx_trk3.hip)
 #define TRK_ERR_SCALE 0x10000000    // error word: samples too strong for the speculative kernel's 2^30 fixed point (sgx_trk3.hip)
 
 __device__ __forceinline__ void wait_mark(const unsigned long long* mark, long long need, unsigned long long& seen,
