@@ -121,6 +121,11 @@ struct T3Shared {
 #ifdef T3_TIMELINE
     unsigned long long tl[6][2][8]; // (diagnosis) sums of the waves' event stamps [wave][block parity][event]
 #endif
+#ifdef T3_MOVED
+    int mv_cls[2];                      // (diagnosis) class of the block of this parity: the set's first map wave -> the PLL wave
+    unsigned long long mv_per[2][4][2]; // [block parity][class]{sum of the release-to-release periods, blocks}
+    unsigned long long mv_pub[4][4][2]; // [map wave][class]{sum of release -> publish issued / handed on, blocks}
+#endif
 };
 
 // ONE KERNEL TEXT PER CASE.  What a launch is - offset-binary samples (uns), every member of a channel on one XCD (fast), a
@@ -206,6 +211,19 @@ struct T3Generic { static constexpr T3Case is{false, false, false, false, true};
 #else
 #define T3_TL(mask, on, wave_, e) do { } while (0)
 #define T3_TL_SET(mask, on, wave_, e, v) do { } while (0)
+#endif
+
+// -DT3_MOVED=1: what a block costs whose final pass finds it somewhere else than its pass put it.  The first map wave of
+// the set leaves the block's class in LDS - 0: the plain route, 1: start or length mispredicted (moved), 2: any other
+// route off the plain one - and the PLL wave of member 0 of EVERY channel adds the release-to-release period of the block
+// to that class (one s_memtime stamp per block at the loop's top, the same for every class: differences between classes
+// are what is read).  -DT3_MOVED=2 also stamps the map waves' final pass - released -> publish issued or handed on, by
+// class - in the members 0, 9 and 18 (the block's first sample, none of its ends, its last sample; the headline text
+// only): two more stamps on the chain, so the periods of that build are longer.  Blocks >= T3_MV_FROM; tools/trk3_moved.py runs the builds.
+#ifdef T3_MOVED
+#ifndef T3_MV_FROM
+#define T3_MV_FROM 200
+#endif
 #endif
 
 // Sum of the 48-bit payloads (two's complement) of the granules of lanes 0..31 / 32..63, as a double, in rows 1 / 3 of the
@@ -606,6 +624,13 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
         // ======== this set's block: the final pass (on the chain) ========
         __builtin_amdgcn_s_setprio(2);
         T3_TL(T3_TL_MAP, tl_on, tid >> 6, 1);   // parameters in registers
+#ifdef T3_MOVED
+        int mv_cls = 0;
+#if T3_MOVED >= 2
+        // (32 bits, a scalar; the headline text only: the generic one has no registers left for it)
+        const unsigned mv_t0 = Case::is.generic ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__builtin_amdgcn_s_memtime());
+#endif
+#endif
         double eps = ep.x;
         double gc, gs;
         bool direct = false;
@@ -639,6 +664,9 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
         T3_TL(T3_TL_MAP, tl_on, tid >> 6, 2);   // test + group phasor
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(!plain) != 0, 0)) {
             unsigned long long me = 0, mb = 0;
+#ifdef T3_MOVED
+            mv_cls = 2;
+#endif
             // The pass ran two blocks back: the block starts `dpos` samples from where it was put and is `blk - cut` samples
             // longer than it was cut (either in a few per cent of the blocks, a sample or two).  The samples' ABSOLUTE
             // positions, code phases and carrier phases do not depend on where the block was taken to start, so the lanes
@@ -652,6 +680,9 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
 #ifdef T3_CHECK
                 chk_moved = true;
                 chk_dpos = dpos;
+#endif
+#ifdef T3_MOVED
+                mv_cls = 1;
 #endif
                 const int i0n = i0 - dpos;
                 int lo_s = -i0, hi_s = cut - i0, lo_f = -i0n, hi_f = blk - i0n;
@@ -670,47 +701,84 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
                 // behind it) or AT its end (half chip 2046: every sample inside lies in front) knows by construction, and
                 // its boundary moved WITH the block - nothing of it crosses.  Any other lane keeps the side the pass saw
                 // unless the sample is one of the two next to the boundary, which the rate step may move across.
-                const bool edge0 = khd < 0.5, edge_e = khd > 2045.5 && khd < 2046.5;
-                const bool st = b1 > a1, en = b2 > a2;
-                const int ca = st ? a1 : a2, cb = st ? b1 : b2;
+                // Everything below as ARITHMETIC on integers and masks (all ones / zero from sign bits; the values are block
+                // indices, byte counts and half-chip numbers, far from 2^31): the && / || chain of it compiled to a nest of
+                // EXEC regions whose lane masks did not fit the scalar file.  khd is an integer (a ceil) in a double.
+                const int khi = (int)khd;
+                const int m_e0 = (khi - 1) >> 31;                                   // edge0: khd < 0.5
+                const int m_ee = ~(((khi - 2046) | (2046 - khi)) >> 31);            // edge_e: khd = 2046
+                const int m_st = (a1 - b1) >> 31, m_en = (a2 - b2) >> 31;           // st: b1 > a1, en: b2 > a2
+                const int m_c0 = -cnt >> 31;                                        // cnt > 0
+                const int ca = (m_st & a1) | (~m_st & a2), cb = (m_st & b1) | (~m_st & b2);
+                // the two bytes the patch may need and their sample phasors (the table the pass ran with), requested HERE,
+                // as soon as their addresses are known: one batch, one wait, in front of the arithmetic that uses them
+                const int bb0 = m_c0 & ca, bb1 = ((1 - cnt) >> 31) & (ca + 1);      // k < cnt ? ca + k : 0
+                int xi0, xi1;
+                t2_v2d Bb0, Bb1;
+                {
+                    const unsigned ra = (unsigned)(unsigned long long)rawb, ta = (unsigned)(unsigned long long)&S.btab[set][0];
+                    asm volatile("ds_read_u8 %0, %1" : "=v"(xi0) : "v"(ra + (unsigned)bb0));
+                    asm volatile("ds_read_u8 %0, %1" : "=v"(xi1) : "v"(ra + (unsigned)bb1));
+                    asm volatile("ds_read_b128 %0, %1" : "=v"(Bb0) : "v"(ta + 16u * (unsigned)bb0));
+                    asm volatile("ds_read_b128 %0, %1" : "=v"(Bb1) : "v"(ta + 16u * (unsigned)bb1));
+                }
                 // (edge0: ... unless the code phase the block starts with is not positive - the reference's own roundings
                 // leave it at -1e-13 while the code NCO rests at its basis - and its first sample lies IN FRONT)
-                const bool hard = cnt > 2 || (st && en) ||
-                                  (cnt > 0 && (khd > 2046.5 || (edge0 && (bsw_s != lo_s || !(rem > 0.0))) ||
-                                               (edge_e && bsw_s < hi_s) ||
-                                               (!edge0 && !edge_e && bsw_s >= ca && bsw_s <= cb)));
-                me = same_win ? __builtin_amdgcn_ballot_w64(hard) : ~0ull;
+                const int m_rp = rem > 0.0 ? -1 : 0;
+                const int m_ne = ((bsw_s - lo_s) | (lo_s - bsw_s)) >> 31;           // bsw_s != lo_s
+                const int m_in = ~((bsw_s - ca) >> 31) & ~((cb - bsw_s) >> 31);     // ca <= bsw_s <= cb
+                const int m_hard = ((2 - cnt) >> 31) | (m_st & m_en) |
+                                   (m_c0 & (((2046 - khi) >> 31) | (m_e0 & (m_ne | ~m_rp)) | (m_ee & ((bsw_s - hi_s) >> 31)) |
+                                            (~m_e0 & ~m_ee & m_in)));
+                me = same_win ? __builtin_amdgcn_ballot_w64(m_hard != 0) : ~0ull;
 #ifdef T3_COUNT
                 n_ev[0] += 1;
                 if (me == 0 && __builtin_amdgcn_ballot_w64(cnt > 0) != 0) n_ev[1] += 1;
 #endif
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xi0), "+v"(xi1), "+v"(Bb0), "+v"(Bb1));
                 if (me == 0) {
                     if (ep.y == 0.0 && __builtin_amdgcn_ballot_w64(cnt > 0) != 0) {
-                        const double sgn = st ? (lo_f < lo_s ? 1.0 : -1.0) : (hi_f > hi_s ? 1.0 : -1.0);
-#pragma unroll 1
-                        for (int k = 0; k < 2; ++k) {
-                            const bool act = k < cnt;
-                            const int bb = act ? ca + k : 0;
-                            const int xi = uns ? (int)reinterpret_cast<const unsigned char*>(rawb)[bb] : (int)rawb[bb];
-                            const double x = act ? sgn * (double)xi : 0.0;
-                            const double2 Bb = S.btab[set][bb];   // the table the pass ran with
-                            const double wgt = (double)bb - 7.5;
-                            const double c0 = x * Bb.x, s0 = x * Bb.y;
+                        // +1.0: the samples enter (the block starts earlier / ends later than the pass had it), -1.0: they leave
+                        const int m_in_ = (m_st & ((lo_f - lo_s) >> 31)) | (~m_st & ((hi_s - hi_f) >> 31));
+                        const double sgn = __hiloint2double((int)(0x3FF00000u | ((unsigned)~m_in_ & 0x80000000u)), 0);
+                        // the side: never in front for edge0, always for edge_e, else where the pass saw the sample
+                        const int m_f0 = ~m_e0 & (m_ee | ((bb0 - bsw_s) >> 31)), m_f1 = ~m_e0 & (m_ee | ((bb1 - bsw_s) >> 31));
+                        // (the samples are small integers: the low dwords of their doubles are zero, a mask on the high one selects)
+                        // (the bytes were read unsigned: an int8 sample's sign by (u ^ 128) - 128, no second text of the reads)
+                        const int sx = uns ? 0 : 128;
+                        const double x0 = __hiloint2double(__double2hiint(sgn * (double)((xi0 ^ sx) - sx)) & m_c0, 0);
+                        const double x1 = __hiloint2double(__double2hiint(sgn * (double)((xi1 ^ sx) - sx)) & ((1 - cnt) >> 31), 0);
+                        const double xf0 = __hiloint2double(__double2hiint(x0) & m_f0, 0), xf1 = __hiloint2double(__double2hiint(x1) & m_f1, 0);
+                        const double wg0 = (double)bb0 - 7.5, wg1 = (double)bb1 - 7.5;
+                        // k = 0, then k = 1: the operations and their order are those of the loop this was (a sample that is
+                        // not in front adds a zero product to the front's moments, which leaves them what they are)
+                        {
+                            const double c0 = x0 * Bb0.x, s0 = x0 * Bb0.y, cf = xf0 * Bb0.x, sf = xf0 * Bb0.y;
                             tc += c0;
                             ts += s0;
-                            t1c = __builtin_fma(c0, wgt, t1c);
-                            t1s = __builtin_fma(s0, wgt, t1s);
-                            if (edge0 ? false : (edge_e ? true : bb < bsw_s)) {
-                                fc += c0;
-                                fs_ += s0;
-                                f1c = __builtin_fma(c0, wgt, f1c);
-                                f1s = __builtin_fma(s0, wgt, f1s);
-                            }
+                            t1c = __builtin_fma(c0, wg0, t1c);
+                            t1s = __builtin_fma(s0, wg0, t1s);
+                            fc += cf;
+                            fs_ += sf;
+                            f1c = __builtin_fma(cf, wg0, f1c);
+                            f1s = __builtin_fma(sf, wg0, f1s);
                         }
-                        if (cnt > 0 && (edge0 || edge_e)) {    // (nothing of this lane crosses: no candidates; the guard stays)
-                            pmc = pms = pm1c = pm1s = 0.0;
-                            ppc = pps = pp1c = pp1s = 0.0;
+                        {
+                            const double c0 = x1 * Bb1.x, s0 = x1 * Bb1.y, cf = xf1 * Bb1.x, sf = xf1 * Bb1.y;
+                            tc += c0;
+                            ts += s0;
+                            t1c = __builtin_fma(c0, wg1, t1c);
+                            t1s = __builtin_fma(s0, wg1, t1s);
+                            fc += cf;
+                            fs_ += sf;
+                            f1c = __builtin_fma(cf, wg1, f1c);
+                            f1s = __builtin_fma(sf, wg1, f1s);
                         }
+                        // (cnt > 0 and edge0 or edge_e: nothing of this lane crosses - no candidates; the guard stays)
+                        const int m_keep = ~(m_c0 & (m_e0 | m_ee));
+                        auto keep = [&](double& v) { v = __hiloint2double(__double2hiint(v) & m_keep, __double2loint(v) & m_keep); };
+                        keep(pmc); keep(pms); keep(pm1c); keep(pm1s);
+                        keep(ppc); keep(pps); keep(pp1c); keep(pp1s);
                     }
                     cut = blk;
                 }
@@ -929,6 +997,15 @@ __device__ __forceinline__ int t3_map_role(T3Shared& S, const int8_t* __restrict
         }
         T2STAMP(prof_on, 5);   // published (or handed to the lanes that publish)
         T3_TL(T3_TL_MAP, tl_on, tid >> 6, 5);
+#ifdef T3_MOVED
+        if ((tid & (T3_LANES - 1)) == 0) S.mv_cls[par] = mv_cls;
+#if T3_MOVED >= 2
+        if (!Case::is.generic && lane == 0 && it >= T3_MV_FROM && (unit == 0 || unit == 9 || unit == 18)) {
+            atomicAdd(&S.mv_pub[tid >> 6][mv_cls][0], (unsigned long long)((unsigned)__builtin_amdgcn_s_memtime() - mv_t0));
+            atomicAdd(&S.mv_pub[tid >> 6][mv_cls][1], 1ull);
+        }
+#endif
+#endif
         __builtin_amdgcn_s_setprio(0);
         if (it + 2 < ms) {
             // ======== part A of the pass of this set's NEXT block, it + 2, with this block's rates (in the shadow of this
@@ -1150,12 +1227,26 @@ __device__ __forceinline__ int t3_pll_role(T3Shared& S, const TrkConst& K, const
     const bool tl_on = ch == 0;
     (void)tl_on;
     (void)prof_on;
+#ifdef T3_MOVED
+    long long mv_t = 0;
+#endif
     __builtin_amdgcn_s_setprio(3);
     int it = 0;
     for (; it < ms; ++it) {
         const int par = it & 1;
         const T3Code& C = S.code[par];
         T3_TL(1, tl_on, 4, 0);   // released (the reference of every other stamp)
+#ifdef T3_MOVED
+        if (owner) {   // the period of block it - 1, by the class its final pass found
+            const long long t_ = (long long)__builtin_amdgcn_s_memtime();
+            if (lane == 0 && it > T3_MV_FROM) {
+                const int c_ = S.mv_cls[par ^ 1];
+                atomicAdd(&S.mv_per[par ^ 1][c_][0], (unsigned long long)(t_ - mv_t));
+                atomicAdd(&S.mv_per[par ^ 1][c_][1], 1ull);
+            }
+            mv_t = t_;
+        }
+#endif
         const int4 hd = *reinterpret_cast<const int4*>(&C.blk);
         const long long pos = C.pos;
         if (owner && it > 0) {
@@ -1746,6 +1837,11 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
 #ifdef T3_TIMELINE
     if (tid < 96) S.tl[tid >> 4][(tid >> 3) & 1][tid & 7] = 0ull;
 #endif
+#ifdef T3_MOVED
+    if (tid < 16) (&S.mv_per[0][0][0])[tid] = 0ull;
+    if (tid < 32) (&S.mv_pub[0][0][0])[tid] = 0ull;
+    if (tid < 2) S.mv_cls[tid] = 0;
+#endif
     if (tid < 2) {
         S.code[tid].xflag = 0;
         S.carr[tid].eps = 0.0;
@@ -1853,6 +1949,20 @@ __global__ __launch_bounds__(T3_THREADS) void trk3_kernel(const int8_t* __restri
     if (ch == 0 && tid < 96 && done > T3_TL_FROM + 2 && S.tl[tid >> 4][(tid >> 3) & 1][tid & 7] != 0ull)
         printf("[t3 tl] unit %d wave %d par %d ev %d mean %.1f\n", unit, tid >> 4, (tid >> 3) & 1, tid & 7,
                (double)S.tl[tid >> 4][(tid >> 3) & 1][tid & 7] / (0.5 * (double)(done - T3_TL_FROM)));
+#endif
+#ifdef T3_MOVED
+    __syncthreads();
+    if (owner && tid < 2)
+        printf("[t3 moved] ch %d set %d: plain %llu blocks, period %.1f | moved %llu blocks, period %.1f | other %llu blocks, period %.1f\n",
+               ch, tid, S.mv_per[tid][0][1], (double)S.mv_per[tid][0][0] / (double)(S.mv_per[tid][0][1] ? S.mv_per[tid][0][1] : 1ull),
+               S.mv_per[tid][1][1], (double)S.mv_per[tid][1][0] / (double)(S.mv_per[tid][1][1] ? S.mv_per[tid][1][1] : 1ull),
+               S.mv_per[tid][2][1], (double)S.mv_per[tid][2][0] / (double)(S.mv_per[tid][2][1] ? S.mv_per[tid][2][1] : 1ull));
+#if T3_MOVED >= 2
+    if (tid < 4 && S.mv_pub[tid][0][1] != 0ull)
+        printf("[t3 moved] ch %d unit %2d wave %d: release -> publish issued, plain %.1f (%llu blocks), moved %.1f (%llu blocks)\n", ch, unit, tid,
+               (double)S.mv_pub[tid][0][0] / (double)S.mv_pub[tid][0][1], S.mv_pub[tid][0][1],
+               (double)S.mv_pub[tid][1][0] / (double)(S.mv_pub[tid][1][1] ? S.mv_pub[tid][1][1] : 1ull), S.mv_pub[tid][1][1]);
+#endif
 #endif
     // a channel that was given up reports the blocks completed before the abort
     const bool aborted = S.code[done & 1].stop == 2;
