@@ -375,6 +375,26 @@ int sgx_stream_rates(sgx_ctx* c, size_t bytes, int reps, double* read_gbs, doubl
 int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, double* f, double* pxx,
                     int64_t* hist, int32_t* n_segments);
 
+/* ---- the record monitor (no reference counterpart: probeData looks at the first 10 code periods only) -----------
+ * Window [offset, offset+n) of an int8 record cut into slices of slice_len samples; slice j covers [offset + j slice_len,
+ * offset + min((j+1) slice_len, n)) and is kept while it holds one whole segment - a trailing piece shorter than nperseg
+ * is dropped.  Segments never cross a slice boundary: slice j has (len_j - noverlap) / (nperseg - noverlap) of them.
+ * Per slice: pxx = the Welch density of sgx_probe_stats at this segment length (exact constant detrend per segment,
+ * periodic Hamming window, one-sided, mean over the segments in segment order; a constant segment gives exactly 0);
+ * moments = count, sum x, sum x^2, sum x^4 and hist = the 256-bin histogram (-128 in bin 0) of ALL samples of the slice,
+ * exact.  hold[k] = max over the slices of pxx[.][k]; f[nperseg/2+1] (MHz) as sgx_probe_stats.  A segment goes from its
+ * int8 samples to its powers inside one compute unit; the sums have one order, so two calls give the same bits.
+ * sgx_waterfall_plan: the number of slices kept, to size the arrays; host code, needs no GPU.
+ * SGX_E_ARG: nperseg not a power of two in 256 .. 16384, noverlap outside [0, nperseg), slice_len below nperseg or above
+ * 2^32 (a slice's sum of x^4 then fits int64), a NULL pointer, a record on another device; SGX_E_RANGE: a window outside
+ * the record, or ("ValueError") shorter than one segment.
+ * sgx_waterfall_timing: HIP-event time of the last sgx_probe_waterfall's kernels on this context. */
+int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, int32_t nperseg,
+                        int32_t noverlap, size_t slice_len, double* f, double* pxx, double* hold, int64_t* moments,
+                        int64_t* hist, int64_t* n_segments, int64_t* n_slices);
+int sgx_waterfall_plan(size_t n, int32_t nperseg, int32_t noverlap, size_t slice_len, int64_t* n_slices);
+int sgx_waterfall_timing(sgx_ctx* c, float* kernel_ms);
+
 /* ---- next row: bit sync + preamble search on the tracking output (postNavigation.py:443-631) ----------------
  * NavigationResult.findPreambles: I_P is [n_ch][ms] float64 (row i = i-th record of the tracking results);
  * firstSubFrame[ch] = ms index of the first verified TLM preamble, 0 = none (then the reference drops the

@@ -158,6 +158,10 @@ _PROTOS = {
                                      C.c_int32, _P, C.c_int64, _P, _P, _P]),
     "sgx_stream_rates": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sgx_probe_stats": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "sgx_probe_waterfall": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, C.c_int32, C.c_int32, C.c_size_t,
+                                      _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sgx_waterfall_plan": (C.c_int, [C.c_size_t, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_int64)]),
+    "sgx_waterfall_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_find_preambles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sgx_nav_parity_check": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "sgx_track_quality": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(LockParams), _P, _P, _P,
@@ -516,6 +520,47 @@ def notch_design(settings, f_mhz, pxx, threshold_db=8.0, width_hz=80e3, n_taps=1
     check(lib().sgx_notch_design(C.byref(st), _ptr(f), _ptr(p), f.size, float(threshold_db), float(width_hz), int(n_taps),
                                  _ptr(taps), C.byref(shift), _ptr(hz), _ptr(wd), C.byref(n)))
     return taps, shift.value, [(float(hz[i]), float(wd[i])) for i in range(n.value)]
+
+
+WATERFALL_MIN_SEGMENT, WATERFALL_MAX_SEGMENT = 256, 16384
+
+
+def waterfall_plan(n, nperseg, noverlap, slice_len):
+    """The number of slices Context.waterfall keeps of a window of n samples (sgx_waterfall_plan; needs no GPU).
+    ValueError for what the monitor refuses: a segment length that is no power of two in 256 .. 16384, an overlap outside
+    [0, nperseg), a slice shorter than a segment or longer than 2^32 samples, a window shorter than one segment."""
+    ns = C.c_int64(0)
+    rc = lib().sgx_waterfall_plan(max(int(n), 0), int(nperseg), int(noverlap), max(int(slice_len), 0), C.byref(ns))
+    if rc in (SGX_E_ARG, SGX_E_RANGE):
+        raise ValueError(last_error())
+    check(rc)
+    return int(ns.value)
+
+
+class Waterfall(object):
+    """What Context.waterfall returns.  f[bins] (MHz), pxx[n_slices, bins], hold[bins] (the maximum over the slices),
+    moments int64[n_slices, 4] (count, sum x, sum x^2, sum x^4), hist int64[n_slices, 256] (-128 in bin 0), n_segments
+    int64[n_slices]; and, in float64 from those integers, per slice: mean, rms, kurtosis (excess, m4 / m2^2 - 3 about the
+    mean; 0 for a constant slice) and clip_share (the share of the samples on -128, -127 or +127)."""
+
+    def __init__(self, f, pxx, hold, moments, hist, n_segments, slice_len):
+        self.f, self.pxx, self.hold, self.moments, self.hist, self.n_segments = f, pxx, hold, moments, hist, n_segments
+        self.slice_len = int(slice_len)
+        n = moments[:, 0].astype(np.float64)
+        v = np.arange(-128, 128, dtype=np.int64)
+        self.mean = moments[:, 1] / n
+        e2, e3, e4 = moments[:, 2] / n, (hist * v ** 3).sum(axis=1) / n, moments[:, 3] / n
+        m2 = e2 - self.mean * self.mean
+        m4 = e4 - 4.0 * self.mean * e3 + 6.0 * self.mean * self.mean * e2 - 3.0 * self.mean ** 4
+        self.rms = np.sqrt(e2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.kurtosis = np.where(m2 > 0, m4 / (m2 * m2) - 3.0, 0.0)
+        self.clip_share = (hist[:, 0] + hist[:, 1] + hist[:, 255]) / n
+
+    def arrays(self):
+        """The arrays by name, as --monitor-out saves them."""
+        return dict((k, getattr(self, k)) for k in ("f", "pxx", "hold", "moments", "hist", "n_segments", "mean", "rms",
+                                                    "kurtosis", "clip_share"))
 
 
 IQ_MAX_TAPS = 255
@@ -925,6 +970,30 @@ class Context(object):
             raise ValueError(last_error())
         check(rc)
         return f, pxx, hist, nseg.value
+
+    def waterfall(self, rec, offset, n, fs_mhz, nperseg=16384, noverlap=1024, slice_len=None):
+        """The record monitor (sgx_probe_waterfall): samples [offset, offset + n) of an int8 record cut into slices of
+        slice_len samples (None: one slice), each slice's Welch spectrum - the density of probe_stats at segment length
+        nperseg - and exact integer statistics.  Returns a Waterfall.  ValueError for what waterfall_plan refuses."""
+        S = int(n) if slice_len is None else int(slice_len)
+        ns = waterfall_plan(n, nperseg, noverlap, S)
+        bins = int(nperseg) // 2 + 1
+        f, pxx, hold = np.zeros(bins), np.zeros((ns, bins)), np.zeros(bins)
+        moments, hist = np.zeros((ns, 4), dtype=np.int64), np.zeros((ns, 256), dtype=np.int64)
+        nseg, got = np.zeros(ns, dtype=np.int64), C.c_int64(0)
+        rc = lib().sgx_probe_waterfall(self._h, rec._h, int(offset), int(n), float(fs_mhz), int(nperseg), int(noverlap), S,
+                                       _ptr(f), _ptr(pxx), _ptr(hold), _ptr(moments), _ptr(hist), _ptr(nseg), C.byref(got))
+        if rc == SGX_E_RANGE:
+            raise ValueError(last_error())
+        check(rc)
+        assert got.value == ns
+        return Waterfall(f, pxx, hold, moments, hist, nseg, S)
+
+    def waterfall_timing(self):
+        """HIP-event time (ms) of the last waterfall()'s kernels."""
+        t = C.c_float(0)
+        check(lib().sgx_waterfall_timing(self._h, C.byref(t)))
+        return t.value
 
     def find_preambles(self, i_p, search_start=0):
         """i_p: float64[n_ch, ms] -> int array firstSubFrame[n_ch] (0 = no verified preamble)."""

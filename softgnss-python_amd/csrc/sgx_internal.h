@@ -87,6 +87,15 @@ struct FftPlan {
     int cus = 0;                        // fine-search length only: compute units of the plan's device
 };
 
+// The twiddle table of the record monitor's segment length (sgx_waterfall.hip): tw[t] = W_n^t, t < n / 2, in ONE device
+// allocation the plan owns, and the sum of the squared window it implies.  prepare() keeps the table of the last length.
+struct WfPlan {
+    int n = 0;
+    DevBuf<cplx> tw;
+    double w2 = 0.0;
+    int prepare(int n_seg);
+};
+
 // sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
 #define SGX_IQ_LP_MAX 136
 
@@ -433,6 +442,12 @@ struct sgx_ctx {
     // (grow-only)
     DevBuf<sgx_cond_stats> d_cond_stats;
     DevBuf<sgx_cond_entry> d_cond_plan;
+    // the record monitor (sgx_waterfall.hip): its plan, the scratch rows of the segments in flight, the results on the
+    // device (grow-only) and the HIP-event time of the last call's kernels
+    WfPlan plan_waterfall;
+    DevBuf<double> d_wf_rows;
+    DevBuf<char> d_wf_out;
+    float waterfall_ms = 0.0f;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

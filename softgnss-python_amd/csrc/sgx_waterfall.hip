@@ -1,0 +1,343 @@
+// The record monitor (no reference counterpart: Settings.probeData looks at the first 10 code periods only): a window of an
+// int8 record cut into slices, each slice's Welch power spectral density - segments of N samples, constant detrend, periodic
+// Hamming window, density scaling, one-sided, mean over the segments, as sgx_probe_stats - and the exact integer statistics
+// of all its samples.  tests/waterfall_spec.py is the contract.
+//
+//   wf_segment_kernel  one workgroup per segment: int8 samples -> exact integer sum -> the packed N/2-point complex
+//                      sequence in LDS (8192 x 16 B = 128 KB at N = 16384, the staged bytes 16 KB behind it) -> in-place transform -> real split -> the
+//                      N/2 + 1 powers to the scratch row of the segment.  The complex spectrum never leaves the CU.
+//   wf_average_kernel  per (slice, bin): the rows of the slice in segment order, * scale (* 2 inside the band), / segments
+//   wf_hold_kernel     per bin: the maximum over the slices, in slice order
+//   wf_stats_kernel    per slice: count, sum x, sum x^2, sum x^4 and the 256-bin histogram of ALL its samples, each
+//                      counted once; LDS histogram per workgroup, 64-bit integer atomics to the slice's row
+// The scratch holds at most WF_CHUNK_SEGMENTS rows (and at most WF_CHUNK_BYTES): a longer window runs chunk by chunk, the
+// running sum of a slice cut by a chunk boundary waits in its row of the result.  No floating-point atomics: every sum has
+// one order, so two runs give the same bits.
+#include <math.h>
+
+#include "sgx_waterfall_core.h"
+
+#define WF_CHUNK_SEGMENTS 4096
+#define WF_CHUNK_BYTES ((size_t)64 << 20)
+#define WF_PIECE 65536             // samples one workgroup of the statistics takes at a time: its LDS counts fit 32 bits
+#define WF_STATS_BLOCKS 2048
+#define WF_MAX_SLICE ((size_t)1 << 32)   // 2^32 samples x 127^4 < 2^63: the sum of x^4 of a slice fits int64
+
+// The twiddle table of one segment length, kept with the context until another length is asked for
+int WfPlan::prepare(int n_seg) {
+    if (n == n_seg && tw.get()) return SGX_OK;
+    const int M = n_seg / 2;
+    std::vector<cplx> h((size_t)M);
+    for (int t = 0; t < M; ++t) {
+        const double a = 2.0 * M_PI * (double)t / (double)n_seg;
+        h[(size_t)t] = make_double2(cos(a), -sin(a));
+    }
+    n = 0;
+    const int rc = tw.ensure(sizeof(cplx) * (size_t)M);
+    if (rc != SGX_OK) return rc;
+    SGX_HIP(hipMemcpy(tw.get(), h.data(), sizeof(cplx) * (size_t)M, hipMemcpyHostToDevice));
+    w2 = 0.0;
+    for (int i = 0; i < n_seg; ++i) {
+        const double w = wf_window(h.data(), M, i);
+        w2 += w * w;
+    }
+    n = n_seg;
+    return SGX_OK;
+}
+
+// Bytes lo <= b < hi of a 16-byte granule kept, the others zeroed, in dword d of it
+__device__ __forceinline__ unsigned wf_keep_bytes(unsigned w, int d, int lo, int hi) {
+    unsigned m = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (4 * d + b >= lo && 4 * d + b < hi) m |= 0xffu << (8 * b);
+    return w & m;
+}
+
+// The segment is read ONCE, as the N / 16 + 1 aligned 16-byte granules that cover it (a segment starts on any byte; the
+// granules reach at most 15 bytes in front of it and 16 behind, inside the record's allocation and its SGX_IF_PAD), and
+// staged in LDS behind the transform's buffer; the bytes outside the segment are left out of the sum.
+__global__ __launch_bounds__(1024) void wf_segment_kernel(const int8_t* __restrict__ x, const cplx* __restrict__ tw,
+                                                          double* __restrict__ rows, WfGeom g, long long seg0) {
+    extern __shared__ __attribute__((aligned(16))) char wf_smem[];
+    cplx* __restrict__ buf = reinterpret_cast<cplx*>(wf_smem);   // [N / 2]
+    __shared__ int s_sum;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int M = g.N / 2;
+    uint4* __restrict__ raw = reinterpret_cast<uint4*>(wf_smem + sizeof(cplx) * (size_t)M);   // [N / 16 + 1]
+    long long slice, start;
+    wf_locate(g, seg0 + blockIdx.x, &slice, &start);
+    const int a = (int)((unsigned long long)(x + start) & 15);
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(x + start - a);
+    if (tid == 0) s_sum = 0;
+    __syncthreads();
+    int part = 0;
+    for (int c = tid; c <= g.N / 16; c += nt) {
+        uint4 v = src[c];
+        raw[c] = v;
+        if (c == 0 || c == g.N / 16) {                           // granule c holds the segment's bytes 16 c - a + (0 .. 15)
+            const int lo = c == 0 ? a : 0, hi = c == 0 ? 16 : a;
+            v.x = wf_keep_bytes(v.x, 0, lo, hi);
+            v.y = wf_keep_bytes(v.y, 1, lo, hi);
+            v.z = wf_keep_bytes(v.z, 2, lo, hi);
+            v.w = wf_keep_bytes(v.w, 3, lo, hi);
+        }
+        part = __builtin_amdgcn_sdot4((int)v.x, 0x01010101, part, false);
+        part = __builtin_amdgcn_sdot4((int)v.y, 0x01010101, part, false);
+        part = __builtin_amdgcn_sdot4((int)v.z, 0x01010101, part, false);
+        part = __builtin_amdgcn_sdot4((int)v.w, 0x01010101, part, false);
+    }
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_down(part, d, 64);
+    if ((tid & 63) == 0) atomicAdd(&s_sum, part);              // integers: any order gives the same sum
+    __syncthreads();
+    const int sum = s_sum;
+    const int8_t* __restrict__ seg = reinterpret_cast<const int8_t*>(raw) + a;
+    for (int m = tid; m < M; m += nt) wf_pack_item(buf, seg, tw, M, g.log2m, sum, m);
+    __syncthreads();
+    for (int s = 0;; ++s) {
+        int log2h = 0;
+        const int radix = wf_step(g.log2m, s, &log2h);
+        if (!radix) break;
+        if (radix == 2)
+            for (int j = tid; j < M / 2; j += nt) wf_radix2_item(buf, j);
+        else if (radix == 4)
+            for (int q = tid; q < M / 4; q += nt) wf_radix4_item(buf, tw, M, 1 << log2h, log2h, q);
+        else
+            for (int q = tid; q < M / 16; q += nt) wf_radix16_item(buf, tw, M, 1 << log2h, log2h, q);
+        __syncthreads();
+    }
+    double* __restrict__ row = rows + (size_t)blockIdx.x * (size_t)g.bins;
+    for (int k = tid; k <= M; k += nt) row[k] = wf_split_item(buf, tw, M, k);
+}
+
+// grid (bins / WF_AVG_THREADS, slices the chunk touches): segments [seg0, seg0 + n_seg) of the window lie in the scratch.
+// One wave per workgroup, so that a chunk of a few slices still spreads over the CUs; eight rows are loaded at a time and
+// added in segment order.
+#define WF_AVG_THREADS 64
+__global__ __launch_bounds__(WF_AVG_THREADS) void wf_average_kernel(const double* __restrict__ rows, double* __restrict__ pxx, WfGeom g,
+                                                         long long seg0, int n_seg, long long slice0, double scale) {
+    const int k = blockIdx.x * WF_AVG_THREADS + threadIdx.x;
+    if (k >= g.bins) return;
+    const long long j = slice0 + blockIdx.y;
+    const long long first = j * g.k_full, end = first + wf_slice_segments(g, j);
+    const long long lo = first > seg0 ? first : seg0, hi = end < seg0 + n_seg ? end : seg0 + n_seg;
+    if (lo >= hi) return;
+    double* __restrict__ out = pxx + (size_t)j * (size_t)g.bins + k;
+    const double two = (k >= 1 && k < g.bins - 1) ? 2.0 : 1.0;
+    double acc = lo == first ? 0.0 : *out;
+    const double* __restrict__ p = rows + (size_t)(lo - seg0) * (size_t)g.bins + k;
+    long long s = lo;
+    for (; s + 8 <= hi; s += 8, p += 8 * (size_t)g.bins) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = p[(size_t)u * (size_t)g.bins];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (v[u] * scale) * two;
+    }
+    for (; s < hi; ++s, p += g.bins) acc += (*p * scale) * two;
+    *out = hi == end ? acc / (double)(end - first) : acc;
+}
+
+__global__ __launch_bounds__(256) void wf_hold_kernel(const double* __restrict__ pxx, double* __restrict__ hold, WfGeom g) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= g.bins) return;
+    double m = pxx[k];
+    for (long long j = 1; j < g.n_slices; ++j) {
+        const double v = pxx[(size_t)j * (size_t)g.bins + k];
+        m = v > m ? v : m;
+    }
+    hold[k] = m;
+}
+
+// Work unit u = (slice, piece of WF_PIECE samples of it); mom: [n_slices][4], hist: [n_slices][256]
+__global__ __launch_bounds__(256) void wf_stats_kernel(const int8_t* __restrict__ x, WfGeom g, long long pieces,
+                                                       long long units, unsigned long long* __restrict__ mom,
+                                                       unsigned long long* __restrict__ hist) {
+    __shared__ unsigned s_h[256];
+    const int tid = threadIdx.x;
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const long long j = u / pieces, p = u - j * pieces;
+        const long long end = (j + 1) * g.S < g.n ? (j + 1) * g.S : g.n;
+        const long long lo = j * g.S + p * WF_PIECE;
+        const long long hi = lo + WF_PIECE < end ? lo + WF_PIECE : end;
+        if (lo >= hi) continue;                                  // (the same for every lane of the workgroup)
+        s_h[tid] = 0;
+        __syncthreads();
+        long long s1 = 0;
+        unsigned long long s2 = 0, s4 = 0;
+        // the piece as the aligned 16-byte granules that cover it (inside the record's allocation and its pad, as the
+        // segments' are); a byte outside [lo, hi) is left out
+        const int a = (int)((unsigned long long)(x + lo) & 15);
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(x + lo - a);
+        const int count = (int)(hi - lo), granules = (a + count + 15) / 16;
+        for (int c = tid; c < granules; c += 256) {
+            const uint4 v = src[c];
+            const int b0 = 16 * c - a;                           // the piece's index of the granule's first byte
+            const bool whole = b0 >= 0 && b0 + 16 <= count;
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const unsigned w = b < 4 ? v.x : b < 8 ? v.y : b < 12 ? v.z : v.w;
+                const int val = (int)(int8_t)(w >> (8 * (b & 3)));
+                if (whole || (b0 + b >= 0 && b0 + b < count)) {
+                    const unsigned q = (unsigned)(val * val);
+                    atomicAdd(&s_h[val + 128], 1u);
+                    s1 += val;
+                    s2 += q;
+                    s4 += (unsigned long long)q * q;
+                }
+            }
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+            s1 += __shfl_down(s1, d, 64);
+            s2 += __shfl_down(s2, d, 64);
+            s4 += __shfl_down(s4, d, 64);
+        }
+        if ((tid & 63) == 0) {
+            atomicAdd(&mom[j * 4 + 1], (unsigned long long)s1);  // (two's complement: the sum of the signed values)
+            atomicAdd(&mom[j * 4 + 2], s2);
+            atomicAdd(&mom[j * 4 + 3], s4);
+        }
+        __syncthreads();
+        if (s_h[tid]) atomicAdd(&hist[j * 256 + tid], (unsigned long long)s_h[tid]);
+        __syncthreads();
+    }
+}
+
+// The geometry of a window, or the refusal: SGX_E_ARG for a segment length, overlap or slice length out of range,
+// SGX_E_RANGE for a window shorter than one segment
+static int wf_geometry(size_t n, int32_t nperseg, int32_t noverlap, size_t slice_len, WfGeom* g) {
+    if (nperseg < WF_MIN_SEGMENT || nperseg > WF_MAX_SEGMENT || (nperseg & (nperseg - 1)) != 0) {
+        sgx_set_error("the monitor's segment length is a power of two in %d .. %d, not %d", WF_MIN_SEGMENT, WF_MAX_SEGMENT,
+                      (int)nperseg);
+        return SGX_E_ARG;
+    }
+    if (noverlap < 0 || noverlap >= nperseg) {
+        sgx_set_error("the monitor's overlap lies in 0 .. segment length - 1 = %d, not %d", (int)nperseg - 1, (int)noverlap);
+        return SGX_E_ARG;
+    }
+    if (slice_len < (size_t)nperseg || slice_len > WF_MAX_SLICE) {
+        // the upper bound: 2^32 samples of 127^4 each keep a slice's sum of x^4 inside int64
+        sgx_set_error("a slice of the monitor holds at least one segment (%d samples) and at most 2^32 samples, not %zu",
+                      (int)nperseg, slice_len);
+        return SGX_E_ARG;
+    }
+    if (n < (size_t)nperseg) {
+        sgx_set_error("ValueError: the monitor needs at least %d samples for one Welch segment, got %zu", (int)nperseg, n);
+        return SGX_E_RANGE;
+    }
+    g->n = (long long)n;
+    g->S = (long long)slice_len;
+    g->N = nperseg;
+    g->noverlap = noverlap;
+    g->step = nperseg - noverlap;
+    g->log2m = 0;
+    while ((2 << g->log2m) < nperseg) ++g->log2m;
+    g->bins = nperseg / 2 + 1;
+    g->pad = 0;
+    g->n_full = g->n / g->S;
+    const long long rem = g->n - g->n_full * g->S;
+    g->k_full = (g->S - noverlap) / g->step;
+    const bool tail = rem >= (long long)nperseg;     // a trailing piece shorter than a segment is dropped
+    g->n_slices = g->n_full + (tail ? 1 : 0);
+    g->k_last = tail ? (rem - noverlap) / g->step : g->k_full;
+    return SGX_OK;
+}
+
+extern "C" int sgx_waterfall_plan(size_t n, int32_t nperseg, int32_t noverlap, size_t slice_len, int64_t* n_slices) {
+    SGX_CHECK_ARG(n_slices);
+    WfGeom g;
+    const int rc = wf_geometry(n, nperseg, noverlap, slice_len, &g);
+    if (rc != SGX_OK) return rc;
+    *n_slices = (int64_t)g.n_slices;
+    return SGX_OK;
+}
+
+extern "C" int sgx_waterfall_timing(sgx_ctx* c, float* kernel_ms) {
+    SGX_CHECK_ARG(c && kernel_ms);
+    *kernel_ms = c->waterfall_ms;
+    return SGX_OK;
+}
+
+extern "C" int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, int32_t nperseg,
+                                   int32_t noverlap, size_t slice_len, double* f, double* pxx, double* hold,
+                                   int64_t* moments, int64_t* hist, int64_t* n_segments, int64_t* n_slices) {
+    SGX_CHECK_ARG(c && rec && f && pxx && hold && moments && hist && n_segments && n_slices && fs_mhz > 0.0);
+    SGX_CHECK_ARG(rec->device == c->device);
+    if (offset > rec->n || n > rec->n - offset) {
+        sgx_set_error("monitor window [%zu, %zu) outside the %zu-sample record", offset, offset + n, rec->n);
+        return SGX_E_RANGE;
+    }
+    WfGeom g;
+    int rc = wf_geometry(n, nperseg, noverlap, slice_len, &g);
+    if (rc != SGX_OK) return rc;
+    rc = sgx_if_require(rec, offset + n);
+    if (rc != SGX_OK) return rc;
+    SGX_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    c->waterfall_ms = 0.0f;
+    rc = c->plan_waterfall.prepare(nperseg);
+    if (rc != SGX_OK) return rc;
+    const double scale = 1.0 / (fs_mhz * c->plan_waterfall.w2);
+
+    const size_t bins = (size_t)g.bins, ns = (size_t)g.n_slices;
+    const long long total = g.n_full * g.k_full + (g.n_slices > g.n_full ? g.k_last : 0);
+    long long chunk = (long long)(WF_CHUNK_BYTES / (sizeof(double) * bins));
+    if (chunk > WF_CHUNK_SEGMENTS) chunk = WF_CHUNK_SEGMENTS;
+    if (chunk > total) chunk = total;
+    rc = c->d_wf_rows.ensure(sizeof(double) * bins * (size_t)chunk);
+    if (rc != SGX_OK) return rc;
+    // the results on the device: pxx[ns][bins] | hold[bins] | moments[ns][4] | hist[ns][256]
+    const size_t pxx_bytes = sizeof(double) * bins * ns, hold_bytes = sizeof(double) * bins;
+    const size_t mom_bytes = sizeof(int64_t) * 4 * ns, hist_bytes = sizeof(int64_t) * 256 * ns;
+    rc = c->d_wf_out.ensure(pxx_bytes + hold_bytes + mom_bytes + hist_bytes);
+    if (rc != SGX_OK) return rc;
+    double* d_pxx = (double*)c->d_wf_out.get();
+    double* d_hold = d_pxx + bins * ns;
+    unsigned long long* d_mom = (unsigned long long*)(d_hold + bins);
+    unsigned long long* d_hist = d_mom + 4 * ns;
+
+    const int8_t* x = rec->d + offset;
+    const int M = nperseg / 2;
+    const int threads = M / 8 >= 1024 ? 1024 : (M / 8 >= 64 ? M / 8 : 64);   // whole waves
+    const size_t lds = sizeof(cplx) * (size_t)M + 16 * ((size_t)nperseg / 16 + 1);   // the buffer and the staged bytes
+    SGX_HIP(hipFuncSetAttribute((const void*)wf_segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(sizeof(cplx) * (WF_MAX_SEGMENT / 2) + 16 * (WF_MAX_SEGMENT / 16 + 1))));
+    SGX_HIP(hipMemsetAsync(d_mom, 0, mom_bytes + hist_bytes, st));
+    hipEventRecord(c->ev[0], st);
+    {
+        const long long pieces = (g.S + WF_PIECE - 1) / WF_PIECE, units = pieces * g.n_slices;
+        wf_stats_kernel<<<(unsigned)(units < WF_STATS_BLOCKS ? units : WF_STATS_BLOCKS), 256, 0, st>>>(x, g, pieces, units,
+                                                                                                      d_mom, d_hist);
+    }
+    for (long long seg0 = 0; seg0 < total; seg0 += chunk) {
+        const int n_seg = (int)(total - seg0 < chunk ? total - seg0 : chunk);
+        wf_segment_kernel<<<n_seg, threads, lds, st>>>(x, c->plan_waterfall.tw.get(), c->d_wf_rows.get(), g, seg0);
+        const long long slice0 = seg0 / g.k_full, slice1 = (seg0 + n_seg - 1) / g.k_full;
+        wf_average_kernel<<<dim3((unsigned)((bins + WF_AVG_THREADS - 1) / WF_AVG_THREADS), (unsigned)(slice1 - slice0 + 1)),
+                            WF_AVG_THREADS, 0, st>>>(
+            c->d_wf_rows.get(), d_pxx, g, seg0, n_seg, slice0, scale);
+    }
+    wf_hold_kernel<<<(unsigned)((bins + 255) / 256), 256, 0, st>>>(d_pxx, d_hold, g);
+    hipEventRecord(c->ev[1], st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(pxx, d_pxx, pxx_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hold, d_hold, hold_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(moments, d_mom, mom_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        sgx_set_error("monitor kernels failed: %s", hipGetErrorString(e));
+        return SGX_E_HIP;
+    }
+    hipEventElapsedTime(&c->waterfall_ms, c->ev[0], c->ev[1]);
+    for (size_t j = 0; j < ns; ++j) {
+        const long long lo = (long long)j * g.S, hi = lo + g.S < g.n ? lo + g.S : g.n;
+        moments[4 * j] = (int64_t)(hi - lo);
+        n_segments[j] = (int64_t)wf_slice_segments(g, (long long)j);
+    }
+    // np.fft.rfftfreq(N, 1 / fs), as sgx_probe_stats
+    const double val = 1.0 / ((double)nperseg * (1.0 / fs_mhz));
+    for (int k = 0; k < g.bins; ++k) f[k] = (double)k * val;
+    *n_slices = (int64_t)g.n_slices;
+    return SGX_OK;
+}

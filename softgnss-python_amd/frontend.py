@@ -343,13 +343,70 @@ _NOTCH_DEFAULTS = (
     ("notchTaps", 1025),                 # filter length (odd, at most 4095)
 )
 
-DEFAULTS = sum((stage.defaults for stage in STAGES), ()) + _NOTCH_DEFAULTS
+# the record monitor (Settings.monitorRecord; INTEGRATION.md, "Monitoring a record"): the spectrum and the sample statistics
+# of the whole prepared record, slice by slice - what the notch is designed from where notchWholeRecord is set
+_MONITOR_DEFAULTS = (
+    ("monitorSliceMs", 100.0),           # slice length: one spectrum and one set of statistics per that many ms
+    ("monitorSegment", 16384),           # Welch segment length, a power of two in 256 .. 16384
+    ("monitorOverlap", 1024),            # samples two consecutive segments share
+    ("monitorMinSlices", 2),             # a line seen in fewer consecutive slices is no event
+    ("notchWholeRecord", False),         # mitigate() designs the notch from the monitor's max-hold spectrum
+)
+MONITOR_PULSED_MADS = 6.0                # a slice is pulsed beyond the median + this many scaled MADs of the record's slices
+
+DEFAULTS = sum((stage.defaults for stage in STAGES), ()) + _NOTCH_DEFAULTS + _MONITOR_DEFAULTS
 # help of main's --dtype: no stage's own option, but which sample types a file may hold is what the stages above read
 DTYPE_HELP = "dataType of the file's samples (numpy name; with --iq: int8 or uint8, with --iq-requantize also int16 or float32)"
 
 
 def _multiple(n):
     return "even" if n == 2 else "a multiple of %d" % n
+
+
+def line_peak_db(f_mhz, pxx, f_hz, width_hz):
+    """How far a line stands above its floor, dB: the largest bin of the band [f_hz - width_hz / 2, f_hz + width_hz / 2]
+    over the median of the 257 bins around it (the baseline notch_design flags against)."""
+    f = np.asarray(f_mhz) * 1e6
+    band = np.flatnonzero(np.abs(f - f_hz) <= width_hz / 2.0)
+    if not band.size:
+        band = np.array([int(np.argmin(np.abs(f - f_hz)))])
+    k = int(band[np.argmax(pxx[band])])
+    floor = float(np.median(pxx[max(0, k - 128):k + 129]))
+    return float(10.0 * np.log10(pxx[k] / floor)) if floor > 0 and pxx[k] > 0 else float("inf")
+
+
+def monitor_events(per_slice, slice_ms, min_slices):
+    """The lines of the slices merged into events.  per_slice[j]: the lines (f_hz, width_hz, peak_db) of slice j in
+    ascending frequency.  A line continues an event seen in slice j - 1 when their bands [f - w / 2, f + w / 2] overlap
+    (the oldest such event), else it opens one.  An event's f_hz and peak_db are those of its strongest slice, its width
+    the widest; first_ms = first slice x slice_ms, last_ms = (last slice + 1) x slice_ms.  Events of fewer than min_slices
+    slices are dropped; the rest come in order of (first_ms, f_hz), each (f_hz, width_hz, first_ms, last_ms, peak_db)."""
+    events = []
+    for j, lines in enumerate(per_slice):
+        for f, w, peak in lines:
+            lo, hi = f - w / 2.0, f + w / 2.0
+            for e in events:
+                if e["last"] == j - 1 and lo <= e["hi"] and e["lo"] <= hi:
+                    if peak > e["peak"]:
+                        e["f"], e["peak"] = f, peak
+                    e.update(w=max(e["w"], w), last=j, lo=lo, hi=hi)
+                    break
+            else:
+                events.append(dict(f=f, w=w, first=j, last=j, peak=peak, lo=lo, hi=hi))
+    kept = [(e["f"], e["w"], e["first"] * slice_ms, (e["last"] + 1) * slice_ms, e["peak"]) for e in events
+            if e["last"] - e["first"] + 1 >= min_slices]
+    return sorted(kept, key=lambda e: (e[2], e[0]))
+
+
+def monitor_pulsed(kurtosis, clip_share, mads=MONITOR_PULSED_MADS):
+    """The slices (indices) whose excess kurtosis or clip share stands out of the record's own slices: above the median
+    of that figure over the slices + mads x 1.4826 x their median absolute deviation."""
+    flagged = np.zeros(len(kurtosis), dtype=bool)
+    for v in (np.asarray(kurtosis, dtype=np.float64), np.asarray(clip_share, dtype=np.float64)):
+        if v.size:
+            med = np.median(v)
+            flagged |= v > med + mads * 1.4826 * np.median(np.abs(v - med))
+    return [int(j) for j in np.flatnonzero(flagged)]
 
 
 class FrontEnd(object):
@@ -429,6 +486,11 @@ class FrontEnd(object):
                 if not lines:
                     say('   No narrowband interference found')
                 self.lastNotchLines = lines
+                if self.notchWholeRecord:
+                    self.lastMonitor = real.lastMonitor
+                    for f_hz, w_hz, first_ms, last_ms, peak_db in self.lastMonitor["events"]:
+                        say('   Seen from %.0f to %.0f ms: a line at %.4f MHz, %.1f dB over the floor'
+                            % (first_ms, last_ms, f_hz / 1e6, peak_db))
             yield rec
         finally:
             if rec is not None:
@@ -439,17 +501,51 @@ class FrontEnd(object):
         periods from sample `offset` (probe_stats, as probeData), its lines by notchThresholdDb / notchWidthHz, a notch of
         notchTaps taps (notch_design) and, if there is a line, the whole record through it (filter_record).  Returns
         (record, lines): a NEW record of the same length - sample n lines up with sample n of the old one - or the SAME
-        record when no line was found; lines is a list of (centre Hz, width Hz).  The caller frees what it gets."""
+        record when no line was found; lines is a list of (centre Hz, width Hz).  The caller frees what it gets.
+        With notchWholeRecord the spectrum is the max-hold over the slices of monitorRecord(record, offset) instead: a line
+        that comes up anywhere in the record is notched, not only one present in its first 10 ms."""
         from . import engine
         if np.dtype(self.dataType) != np.dtype(np.int8):
             raise ValueError("interference excision filters int8 records only, not Settings.dataType %r" % (self.dataType,))
         ctx = record.ctx if device is None else engine.get_context(self, device)
-        n = min(10 * self.samplesPerCode, len(record) - int(offset))
-        f, pxx, _, _ = ctx.probe_stats(record, int(offset), n, self.samplingFreq / 1000000.0)
+        if self.notchWholeRecord:
+            seen = self.monitorRecord(record, offset)["waterfall"]
+            f, pxx = seen.f, seen.hold
+        else:
+            n = min(10 * self.samplesPerCode, len(record) - int(offset))
+            f, pxx, _, _ = ctx.probe_stats(record, int(offset), n, self.samplingFreq / 1000000.0)
         taps, shift, lines = _native.notch_design(self, f, pxx, self.notchThresholdDb, self.notchWidthHz, self.notchTaps)
         if not lines:
             return record, lines
         return ctx.filter_record(record, taps, shift), lines
+
+    def monitorRecord(self, record, offset=0):
+        """The spectrum and the sample statistics of a resident int8 record (a _native.Record) from sample `offset` to its
+        end, slice by slice (Context.waterfall): slices of monitorSliceMs, Welch segments of monitorSegment samples that
+        share monitorOverlap.  Returns info and keeps it as self.lastMonitor: waterfall (a _native.Waterfall: f, pxx, hold,
+        moments, hist, n_segments, mean, rms, kurtosis, clip_share), slice_ms, events and pulsed.
+        events: the lines notch_design finds in each slice's spectrum (notchThresholdDb, notchWidthHz), merged across
+        consecutive slices where their bands overlap (monitor_events), each (f_hz, width_hz, first_ms, last_ms,
+        peak_db_over_floor), ms from `offset`; events shorter than monitorMinSlices slices are dropped.
+        pulsed: the slices whose excess kurtosis or share of samples on -128, -127 or +127 lies above the median of that
+        figure over the record's own slices + 6 x 1.4826 x its median absolute deviation (monitor_pulsed): the threshold
+        comes from the spread of the record, so a steady record of any statistics flags about nothing."""
+        if np.dtype(self.dataType) != np.dtype(np.int8):
+            raise ValueError("the monitor reads int8 records only, not Settings.dataType %r" % (self.dataType,))
+        fs = float(self.samplingFreq)
+        S = int(np.rint(float(self.monitorSliceMs) * 1e-3 * fs))
+        seen = record.ctx.waterfall(record, int(offset), len(record) - int(offset), fs / 1e6, int(self.monitorSegment),
+                                    int(self.monitorOverlap), S)
+        per_slice = []
+        for pxx in seen.pxx:
+            lines = _native.notch_design(self, seen.f, pxx, self.notchThresholdDb, self.notchWidthHz, self.notchTaps)[2]
+            per_slice.append([(f_hz, w_hz, line_peak_db(seen.f, pxx, f_hz, w_hz)) for f_hz, w_hz in lines])
+        slice_ms = 1e3 * S / fs
+        info = dict(waterfall=seen, slice_ms=slice_ms,
+                    events=monitor_events(per_slice, slice_ms, int(self.monitorMinSlices)),
+                    pulsed=monitor_pulsed(seen.kurtosis, seen.clip_share))
+        self.lastMonitor = info
+        return info
 
     def _pack_format(self):
         """(bits, lsb_first, frame, first, take, table) of the unpacker for these settings.  take: a frame of several

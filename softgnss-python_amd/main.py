@@ -11,7 +11,14 @@ ephemerides), the mean position fix.  --correlator-bank=-1:1:0.25 replays the tr
 (chips) and prints each channel's mean correlation envelope per tap, normalised to its maximum.  --notch looks for
 continuous-wave lines in the record's spectrum (8 dB above the local median, or --notch=THRESHOLD_DB), filters them out on
 the GPU before acquisition and tracking, and prints the lines it removed.
-%s"""
+%s
+
+--monitor looks at the whole prepared record before anything else runs: per 100 ms (or --monitor=SLICE_MS) one Welch spectrum
+and the exact statistics of the samples, on the GPU in one pass.  It prints a line per event - a spectral line --notch would
+find, with the time it is first and last seen and how far it stands over the floor - and per slice whose kurtosis or share of
+clipped samples stands out of the record's own slices (pulsed interference); --monitor-out FILE.npz saves the arrays.  With
+--notch, --notch-whole-record designs the notch from the largest value every bin of that spectrum takes anywhere in the record
+instead of from its first 10 ms: a jammer that switches on later is removed too."""
 from __future__ import print_function
 
 import argparse
@@ -40,6 +47,35 @@ def probe_iq(settings):
         return real.probeData(DeviceSignal(rec))
 
 
+def monitor_file(settings, out=None):
+    """--monitor: monitorRecord() of the prepared record postProcessing will read, from skipNumberOfBytes on; a line per
+    event and per flagged slice; the arrays to `out` (.npz) where that is given.  Returns the info."""
+    real = settings._prepared_settings()
+    n, skip = real.samplesPerCode, int(real.skipNumberOfBytes)
+    need = skip + max(real.acquisitionLength(), int(settings.msToProcess) * (n + 2) + 2 * n)
+    if settings.iqRecord:
+        need += need % 2
+    print('Monitoring "%s"...' % settings.fileName)
+    with settings._prepared_record(settings.fileName, 0, need) as rec:
+        info = real.monitorRecord(rec, min(skip, len(rec)))
+    settings.lastMonitor = info
+    seen = info["waterfall"]
+    print('  %d slices of %.1f ms, %d Welch segments each' % (len(seen.n_segments), info["slice_ms"],
+                                                              int(seen.n_segments[0])))
+    for f_hz, w_hz, first_ms, last_ms, peak_db in info["events"]:
+        print('  Line at %.4f MHz (%.1f kHz wide) from %.0f to %.0f ms, %.1f dB over the floor'
+              % (f_hz / 1e6, w_hz / 1e3, first_ms, last_ms, peak_db))
+    for j in info["pulsed"]:
+        print('  Slice at %.0f ms stands out: excess kurtosis %+.3f, %.4f %% of the samples clipped'
+              % (j * info["slice_ms"], seen.kurtosis[j], 100.0 * seen.clip_share[j]))
+    if not info["events"] and not info["pulsed"]:
+        print('  Nothing stands out')
+    if out is not None:
+        np.savez(out, slice_ms=info["slice_ms"], events=np.array(info["events"], dtype=np.float64).reshape(-1, 5),
+                 pulsed=np.array(info["pulsed"], dtype=np.int64), **seen.arrays())
+    return info
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("fileName")
@@ -61,6 +97,12 @@ def main(argv=None):
     ap.add_argument("--notch", nargs="?", type=float, const=-1.0, default=None, metavar="THRESHOLD_DB",
                     help="excise narrowband interference before acquisition: notch out the spectral lines that stand "
                          "THRESHOLD_DB (default: Settings.notchThresholdDb, 8) above the local median")
+    ap.add_argument("--monitor", nargs="?", type=float, const=-1.0, default=None, metavar="SLICE_MS",
+                    help="monitor the whole record first: a spectrum and sample statistics per SLICE_MS ms (default: "
+                         "Settings.monitorSliceMs, 100), a line printed per event and per slice that stands out")
+    ap.add_argument("--monitor-out", default=None, metavar="FILE.npz", help="with --monitor: save the monitor's arrays")
+    ap.add_argument("--notch-whole-record", action="store_true",
+                    help="with --notch: design the notch from the spectrum of the whole record, not of its first 10 ms")
     ap.add_argument("--dtype", default=None, help=DTYPE_HELP)
     dests = [[ap.add_argument(flag, **keywords).dest for flag, keywords in stage.options] for stage in STAGES]
     a = ap.parse_args(argv)
@@ -73,12 +115,20 @@ def main(argv=None):
             taps = None
         if taps is None or not (1 <= taps.size <= 64) or not np.all(np.isfinite(taps)):
             ap.error("--correlator-bank takes LO:HI:STEP in chips with 1 .. 64 taps, e.g. --correlator-bank=-1:1:0.25")
+    if a.notch_whole_record and a.notch is None:
+        ap.error("--notch-whole-record says what --notch designs its filter from: it needs --notch")
+    if a.monitor_out is not None and a.monitor is None:
+        ap.error("--monitor-out saves what --monitor sees: it needs --monitor")
+    if a.monitor is not None and not (a.monitor == -1.0 or (np.isfinite(a.monitor) and a.monitor > 0)):
+        ap.error("--monitor takes the slice length in ms, above 0")
     settings = initialize.Settings()
     asked = dict(fileName=a.fileName, samplingFreq=a.fs, IF=a.IF, msToProcess=a.ms, numberOfChannels=a.channels,
                  skipNumberOfBytes=a.skip, lockDetector=a.lock_detector or None, acqCoherentMs=a.acq_coherent_ms,
                  acqBlocks=a.acq_blocks, acqNonCoherent=a.acq_noncoh or None, dataType=a.dtype,
                  interferenceMitigation=True if a.notch is not None else None,
-                 notchThresholdDb=a.notch if a.notch is not None and a.notch >= 0 else None)
+                 notchThresholdDb=a.notch if a.notch is not None and a.notch >= 0 else None,
+                 notchWholeRecord=a.notch_whole_record or None,
+                 monitorSliceMs=a.monitor if a.monitor is not None and a.monitor > 0 else None)
     for stage, names in zip(STAGES, dests):
         given = [val is not None and val is not False for val in (getattr(a, name) for name in names)]
         if given[0]:
@@ -107,6 +157,8 @@ def main(argv=None):
             print('  %d Welch segments, spectral peak at %.3f MHz, samples within [%d, %d]'
                   % (p["segments"], p["f_MHz"][k], p["hist_edges"][np.flatnonzero(p["hist"])[0]],
                      p["hist_edges"][np.flatnonzero(p["hist"])[-1]] + 1))
+    if a.monitor is not None:
+        monitor_file(settings, a.monitor_out)
     acq, trk, nav = settings.postProcessing()
     if taps is not None and trk is not None and trk.has_results():
         with open(settings.fileName, 'rb') as fid:
