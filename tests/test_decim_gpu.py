@@ -1,13 +1,14 @@
 """The decimation stage on the GPU (sgx_if_decimate, csrc/sgx_decim.hip; Settings.decimateRecord, postProcessing with
 decimation): every factor, both record kinds and the lengths at which plane seams, zero padding, the last partial store
 and the tile seams lie against the numpy contract of tests/decim_spec.py byte for byte with exact clip counts, the
-record's behaviour, the refusals, an input beyond 2^32 bytes, then the scenes of tests/decim_cases.py end to end against
-the contracts' record and the oracle on it.  Run with -m gpu."""
+record's behaviour, the refusals, an input beyond 2^32 bytes whose period hides no wrapped address, then the scenes of
+tests/decim_cases.py end to end against the contracts' record and the oracle on it.  Run with -m gpu."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import big_record as big
 import decim_cases as cases
 import decim_spec as spec
 from conftest import pkg
@@ -273,42 +274,41 @@ def test_refusals_on_the_device(ctx):
 # ---- past 2^32 ----------------------------------------------------------------------------------------------------------
 
 def test_input_beyond_two_to_the_32(ctx, tile):
-    """A real input of 2^32 + 3 tile 16 bytes at D = 16, L = 31, a short pattern over and over: windows at the start,
-    across input byte 2^32 and at the end equal the contract's, and so does the clip count of the whole."""
+    """A real input of 2^32 + 196 944 bytes at D = 16, L = 31: the tiled record of tests/big_record.py, a random block of
+    105 * 2^13 bytes over and over.  That length divides neither 2^31 nor 2^32, so byte p and byte p - 2^32 differ and a load
+    address cut to 32 bits shows (a block of 2^20 bytes would hide it: tests/test_big_record_host.py).  Windows at
+    the start, across input bytes 2^31 and 2^32 and at the end equal the contract's - each held to the wrap rule on the CPU
+    first -, and so does the clip count of the whole."""
     D, L, S = 16, 31, 14
-    rng = np.random.default_rng(162)
-    block = rng.integers(-128, 128, 1 << 20).astype(np.int8)
-    reps = (1 << 32) // block.size
-    tail = 3 * tile * D
-    h = random_taps(rng, L, S)
-    # the contract on block | block | tail: the first block (zeros in front of it), a block between two others, the tail
-    # (zeros behind it)
-    a = spec.sums(np.concatenate([block, block, block[:tail]]), h, 1, D)
-    a = (a + (1 << (S - 1))) >> S
-    over = (a < -127) | (a > 127)
-    want = np.clip(a, -127, 127).astype(np.int8)
-    pb = block.size // D
-    first, mid, last = want[:pb], want[pb:2 * pb], want[2 * pb:]
-    clipped = int(over[:pb].sum()) + (reps - 1) * int(over[pb:2 * pb].sum()) + int(over[2 * pb:].sum())
-    b = np.empty((1 << 32) + tail, dtype=np.int8)
-    b[:1 << 32].reshape(reps, block.size)[:] = block
-    b[1 << 32:] = block[:tail]
-    rec = ctx.upload(b)
+    rec = big.Tiled()
+    stage = big.Decim(D, L, S)
+    assert rec.n > (1 << 32) + 3 * tile * D and stage.width >= 2 * tile and (1 << 32) % rec.P and (1 << 31) % rec.P
+    windows = stage.windows(rec)
+    n_out = -(-rec.n // D)
+    w = stage.width
+    assert windows == [(0, w), ((1 << 31) // D - w // 2, (1 << 31) // D + w // 2),
+                       ((1 << 32) // D - w // 2, (1 << 32) // D + w // 2), (n_out - w, n_out)]
+    wants = [big.wrap_visible(rec.at, stage.contract(rec.n), win) for win in windows]
+    # the contract itself on the head and on the tail of the record, zeros in front and behind
+    head, _ = spec.decimate(rec.at(0, 2 * w * D), stage.h, S, 1, D)
+    assert wants[0].tobytes() == head[:w].tobytes()
+    clipped = stage.counters(rec)["clipped"]
+    b = rec.build()
+    dev = ctx.upload(b)
+    del b
     try:
-        out = ctx.decimate(rec, 1, h, S, D)
+        out = ctx.decimate(dev, 1, stage.h, S, D)
         try:
-            n_out = b.size // D
-            assert len(out) == n_out == reps * pb + last.size and last.size == 3 * tile
-            w = 2 * tile
-            assert out.download(0, w).tobytes() == first[:w].tobytes()
-            # across input byte 2^32 = output byte 2^28
-            assert out.download((1 << 32) // D - tile, w).tobytes() == np.concatenate([mid[-tile:], last[:tile]]).tobytes()
-            assert out.download(n_out - w, w).tobytes() == last[-w:].tobytes()
+            assert len(out) == n_out == rec.n // D
+            for (w0, w1), want in zip(windows, wants):
+                got = out.download(w0, w1 - w0)
+                assert got.tobytes() == want.tobytes(), \
+                    "window [%d, %d): first difference at output byte %d" % (w0, w1, w0 + int(np.flatnonzero(got != want)[0]))
             assert 0 < clipped < n_out and out.clipped == clipped
         finally:
             out.free()
     finally:
-        rec.free()
+        dev.free()
 
 
 # ---- end to end: the scenes ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The cases of the record monitor (include/sgx.h: sgx_probe_waterfall), shared by tests/test_waterfall_host.py (the
 contract against independent ground, sgx_waterfall_plan) and tests/test_waterfall_gpu.py (the kernels against the contract).
 The smallest shapes at which the kernels can go wrong: the shortest and the longest segment, one in the middle and the one
-below the LDS limit, each at no overlap, N/16, N/2 and N - 1; slices of exactly one segment, of one segment and a tail that
+below the LDS limit, each at no overlap, N/16, N/2 and N - 1; the three lengths between them (512, 2048, 4096) once each; slices of exactly one segment, of one segment and a tail that
 counts in the moments only, a last slice that is partial but kept, a last piece that is dropped; more slices than the
 statistics grid has workgroups (2048) and more segments than one scratch chunk holds (4096), with a slice cut by the chunk
 boundary; odd offsets; extreme, constant and alternating contents.  Every record stays under 8 MB.  Test infrastructure."""
@@ -48,6 +48,13 @@ CASES = _grid() + [
     Case("alternating", "alt", 0, 5000, 1024, 0, 2048),
     Case("alternating-16384", "alt", 1, 2 * 16384, 16384, 1024, 16384),
     Case("late-tone", "tone", 0, 8 * 4096, 1024, 64, 4096),
+] + [
+    # the segment lengths the grid leaves out: 512 is the one pure radix-16 length below 8192 and runs with more lanes (64)
+    # than radix-16 items (16), 2048 the one whose first step is the radix-4 step with no radix-2 step in front of it, 4096
+    # the longest below the grid's 8192; each at noverlap = N / 16 with a tail and an odd offset.  Appended, so that the
+    # cases above keep their names, offsets and seeds.
+    Case("length-%d" % N, "gauss", offset, 2 * (2 * N - N // 16 + 7) + N + 5, N, N // 16, 2 * N - N // 16 + 7)
+    for N, offset in ((512, 1), (2048, 3), (4096, 19))
 ]
 BY_NAME = dict((c.name, c) for c in CASES)
 TONE_BIN, TONE_AMPLITUDE = 100, 60
