@@ -37,8 +37,10 @@ extern "C" {
                                out-of-range data (the error text then starts with the exception's name) */
 #define SGX_E_DEFER    -7   /* sgx_track_chained: the queued (deferred) sequence does not apply to this call - no
                                acquisition pending, a kernel other than the cooperative int8 / uint8 ones, a streaming
-                               record, a launch that had to be repeated; the caller runs sgx_acquire_end, preRun and
-                               sgx_track_ex instead (nothing has been lost: the search's results are still pending) */
+                               record, a table preRun could not make (a NaN metric, a failed search, a channel in front
+                               of the record); the caller runs sgx_acquire_end, preRun and sgx_track_ex instead (nothing
+                               has been lost: the search's results are still pending).  A launch that has to be repeated
+                               is repeated on the table the device made, inside the call */
 
 #define SGX_NUM_SERIES 13   /* per-ms tracking series, in this order (tracking.py:255-275):
                                absoluteSample codeFreq carrFreq I_P I_E I_L Q_E Q_P Q_L
@@ -249,7 +251,10 @@ int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, in
  * The reference's caller looks at every stage's result before it starts the next (initialize.py:484-506: acquire, preRun,
  * TrackingResult.track).  A caller that wants the tracking results can queue all three and wait once:
  *   sgx_acquire_begin    sgx_acquire's arguments without the outputs: the search is queued (acquisition.py:27-204), the
- *                        call returns without looking at it.  One acquisition may be pending per context.
+ *                        call returns without looking at it.  One acquisition may be pending per context: any other
+ *                        sgx_acquire* call on the context (this one, sgx_acquire, _f64, _coherent, _coherent_f64,
+ *                        _sharded) drops a pending search, whether or not it succeeds - sgx_track_chained then returns
+ *                        SGX_E_DEFER and sgx_acquire_end SGX_E_ARG ("no acquisition is pending").
  *   sgx_track_chained    preRun (acquisition.py:259-306: stable descending sort of the 32 peak metrics, the first
  *                        min(n_ch, #detected) become channels) runs ON THE DEVICE behind the pending search and the tracking
  *                        kernel (tracking.py:13-295) behind it, reading the channel table where preRun left it; the call

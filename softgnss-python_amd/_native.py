@@ -796,6 +796,7 @@ class Context(object):
         check(lib().sgx_ctx_create_prio(C.byref(self._s), int(device), int(priority), C.byref(self._h)))
         self.device = int(device)
         self._records = weakref.WeakSet()   # live records of this context: freed (loader threads joined) before it
+        self._token = 0                     # searches so far (search_token)
 
     def close(self):
         if self._h:
@@ -870,51 +871,67 @@ class Context(object):
         return Record(self, h, int(n))
 
     # ---- hot path ----
-    def _supersede(self):
-        """Any search supersedes a deferred one nobody has looked at: one search may be pending per context."""
-        self._acq_token = getattr(self, "_acq_token", 0) + 1
-        return self._acq_token
+    def _search(self, fn, n, *args):
+        """The search fn(ctx, *args, outputs of n PRNs ...) as the dict of its five output arrays; n None: a search that is
+        only queued and has no outputs yet.  Any search takes the context's result page, so it supersedes a queued one that
+        nobody has looked at: one search may be pending per context (PendingSearch)."""
+        self._token += 1
+        out, ptrs = _acq_out(n) if n is not None else ((), ())
+        check(getattr(lib(), fn)(self._h, *args, *ptrs))
+        return _acq_dict(out)
+
+    @property
+    def search_token(self):
+        """Counts the searches on this context: a PendingSearch is the context's pending one while it still holds this."""
+        return self._token
 
     def acquire(self, rec, offset, n_samples, prn0, n_blocks=2, noncoh=False):
-        self._supersede()
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        out, ptrs = _acq_out(prn.size)
-        check(lib().sgx_acquire(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
-                                1 if noncoh else 0, *ptrs))
-        return _acq_dict(out)
+        return self._search("sgx_acquire", prn.size, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
+                            1 if noncoh else 0)
+
+    def acquire_f64(self, signal, prn0, n_blocks=2, noncoh=False):
+        """acquire() on a host signal of any real dtype (copied to HBM as fp64)."""
+        sig = np.ascontiguousarray(signal, dtype=np.float64)
+        prn = np.ascontiguousarray(prn0, dtype=np.int32)
+        return self._search("sgx_acquire_f64", prn.size, _ptr(sig), sig.size, _ptr(prn), prn.size, int(n_blocks),
+                            1 if noncoh else 0)
 
     def acquire_coherent(self, rec, offset, n_samples, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
         """acquire() with coherent_ms-ms windows (n_windows of them) on a bin_step_hz grid (None: 500 / coherent_ms)."""
-        self._supersede()
         pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        out, ptrs = _acq_out(prn.size)
-        check(lib().sgx_acquire_coherent(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, C.byref(pa),
-                                         *ptrs))
-        return _acq_dict(out)
+        return self._search("sgx_acquire_coherent", prn.size, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size,
+                            C.byref(pa))
 
     def acquire_coherent_f64(self, signal, prn0, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
         """acquire_coherent() on a host signal of any real dtype (copied to HBM as fp64)."""
-        self._supersede()
         pa = acq_params(coherent_ms, n_windows, noncoh, bin_step_hz)
         sig = np.ascontiguousarray(signal, dtype=np.float64)
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        out, ptrs = _acq_out(prn.size)
-        check(lib().sgx_acquire_coherent_f64(self._h, _ptr(sig), sig.size, _ptr(prn), prn.size, C.byref(pa), *ptrs))
-        return _acq_dict(out)
+        return self._search("sgx_acquire_coherent_f64", prn.size, _ptr(sig), sig.size, _ptr(prn), prn.size, C.byref(pa))
 
     @staticmethod
     def acquire_coherent_plan(settings, coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
         """The module-level acquire_coherent_plan (needs no device)."""
         return acquire_coherent_plan(settings, coherent_ms, n_windows, noncoh, bin_step_hz)
 
+    def acquire_sharded(self, comm, rank, world, rec, offset, n_samples, n_prn_total=32, n_blocks=2, noncoh=False):
+        """This rank's share of the PRN search + the peak gather as ONE library call (sgx_acquire_sharded): packed on the
+        device, one ncclAllGather (comm: a Comm, or None for no collective), one look.  Returns the merged 32-entry arrays."""
+        r = self._search("sgx_acquire_sharded", 32, comm._h if comm is not None else None, int(rank), int(world), rec._h,
+                         int(offset), int(n_samples), int(n_prn_total), int(n_blocks), 1 if noncoh else 0)
+        r["freqBin"], r["fineIdx"] = r["freqBin"].astype(np.int64), r["fineIdx"].astype(np.int64)
+        return r
+
     # ---- the same without host round trips between the stages (include/sgx.h, "round 6") ----
     def acquire_begin(self, rec, offset, n_samples, prn0, n_blocks=2, noncoh=False):
-        """Queue the search of acquire(); nothing is looked at.  acquire_end() returns what acquire() would have."""
+        """Queue the search of acquire(); nothing is looked at.  acquire_end() returns what acquire() would have.  Returns
+        the token of the queued search (PendingSearch) - only a search that was queued takes one."""
         prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        check(lib().sgx_acquire_begin(self._h, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
-                                      1 if noncoh else 0))
-        return self._supersede()   # (only a search that was queued takes the token)
+        self._search("sgx_acquire_begin", None, rec._h, int(offset), int(n_samples), _ptr(prn), prn.size, int(n_blocks),
+                     1 if noncoh else 0)
+        return self._token
 
     def acquire_end(self, n):
         out, ptrs = _acq_out(n)
@@ -937,26 +954,6 @@ class Context(object):
             return None
         check(rc)
         return out, done, prn, freq, cph, n_act.value
-
-    def acquire_sharded(self, comm, rank, world, rec, offset, n_samples, n_prn_total=32, n_blocks=2, noncoh=False):
-        """This rank's share of the PRN search + the peak gather as ONE library call (sgx_acquire_sharded): packed on the
-        device, one ncclAllGather (comm: a Comm, or None for no collective), one look.  Returns the merged 32-entry arrays."""
-        self._supersede()
-        out, ptrs = _acq_out(32)
-        check(lib().sgx_acquire_sharded(self._h, comm._h if comm is not None else None, int(rank), int(world), rec._h,
-                                        int(offset), int(n_samples), int(n_prn_total), int(n_blocks), 1 if noncoh else 0,
-                                        *ptrs))
-        return _acq_dict(out[:3] + (out[3].astype(np.int64), out[4].astype(np.int64)))
-
-    def acquire_f64(self, signal, prn0, n_blocks=2, noncoh=False):
-        """acquire() on a host signal of any real dtype (copied to HBM as fp64)."""
-        self._supersede()
-        sig = np.ascontiguousarray(signal, dtype=np.float64)
-        prn = np.ascontiguousarray(prn0, dtype=np.int32)
-        out, ptrs = _acq_out(prn.size)
-        check(lib().sgx_acquire_f64(self._h, _ptr(sig), sig.size, _ptr(prn), prn.size, int(n_blocks), 1 if noncoh else 0,
-                                    *ptrs))
-        return _acq_dict(out)
 
     def probe_stats(self, rec, offset, n, fs_mhz):
         """(f, Pxx, hist, n_segments) of the record window: Welch PSD and histogram of Settings.probeData."""

@@ -14,6 +14,29 @@ from .initialize import Result
 from .record import DeviceSignal
 
 
+class PendingSearch(object):
+    """A search that Context.acquire_begin queued and nobody has looked at.  One search may be pending per context: any
+    later search on the context takes its result page, and this one then raises instead of decoding the other's."""
+
+    def __init__(self, ctx, prn_indices, token):
+        self.ctx, self.prn_indices, self.token = ctx, prn_indices, token
+
+    def live(self):
+        return self.ctx.search_token == self.token
+
+    def _checked(self):
+        if not self.live():
+            raise RuntimeError("this deferred acquisition was superseded by a later one on the same context before "
+                               "anybody looked at it (one search may be pending per context)")
+        return self.ctx
+
+    def end(self):          # the look: what the eager search would have returned
+        return self._checked().acquire_end(len(self.prn_indices))
+
+    def track_chained(self, rec, n_ch, ms, **kw):   # preRun on the device behind this search, the tracking kernel behind it
+        return self._checked().track_chained(rec, n_ch, ms, **kw)
+
+
 class AcquisitionResult(Result):
     def __init__(self, settings, verbose=False, device=None, deferred=False):
         """deferred (extension; the reference and the default are eager): acquire() of a DeviceSignal only QUEUES the
@@ -26,10 +49,19 @@ class AcquisitionResult(Result):
         self._verbose = verbose
         self._device = device
         self._deferred = bool(deferred)
-        self._pending = None           # (context, PRN indices) of a queued search nobody has looked at
-        self._prerun_pending = False   # preRun() was called while the search was still queued
-        self._merged = None            # arrays of a sharded search (sgx_acquire_sharded) not yet packed into .results
         self._internals = None
+        self._reset_lazy()
+
+    def _reset_lazy(self, pending=None, merged=None):
+        """Every way a search arrives - eager, queued, merged from the shards, assigned to .results - comes through here:
+        whatever was lazy about the search before it is dropped (a queued one is never ended: the newer took its page)."""
+        self._pending = pending        # PendingSearch: a queued search nobody has looked at
+        self._prerun_pending = False   # preRun() was called while the search was still queued
+        self._merged = merged          # arrays of a sharded search (sgx_acquire_sharded) not yet packed into .results
+
+    queued = property(lambda self: self._pending is not None, doc="a queued search nobody has looked at")
+    prerun_queued = property(lambda self: self._prerun_pending, doc="preRun() was asked for while the search was queued")
+    device = property(lambda self: self._device)
 
     @property
     def internals(self):
@@ -41,21 +73,20 @@ class AcquisitionResult(Result):
     def internals(self, value):
         self._internals = value
 
+    @Result.results.setter
+    def results(self, records):
+        Result.results.fset(self, records)
+        self._reset_lazy()
+
     def _materialize(self):
-        merged = self._merged
+        merged, pending, prerun = self._merged, self._pending, self._prerun_pending
+        self._reset_lazy()
         if merged is not None:
-            self._merged = None
             self._results = np.rec.fromarrays([merged["carrFreq"], merged["codePhase"], merged["peakMetric"]],
                                               names='carrFreq,codePhase,peakMetric')
-        if self._pending is not None:
-            ctx, prn_indices, token = self._pending
-            self._pending = None
-            if getattr(ctx, "_acq_token", None) != token:
-                raise RuntimeError("this deferred acquisition was superseded by a later one on the same context before "
-                                   "anybody looked at it (one search may be pending per context)")
-            self._fill(prn_indices, ctx.acquire_end(len(prn_indices)))
-        if self._prerun_pending:
-            self._prerun_pending = False
+        if pending is not None:
+            self._fill(pending.prn_indices, pending.end())
+        if prerun:
             self._prerun_host()
 
     @property
@@ -106,15 +137,13 @@ class AcquisitionResult(Result):
                 if not np.isrealobj(arr):
                     raise TypeError("longSignal must be real-valued")
                 f64 = arr.astype(np.float64)
-        self._prerun_pending = False
-        self._merged = None
+        self._reset_lazy()
         if self._deferred and f64 is None and own is None and not self._verbose and not coherent:
             token = ctx.acquire_begin(rec, off, n, prn_indices, n_blocks=n_blocks, noncoh=noncoh)
-            self._pending = (ctx, prn_indices, token)
+            self._reset_lazy(pending=PendingSearch(ctx, prn_indices, token))
             self._results = None
             self._channels = None
             return
-        self._pending = None
         if self._verbose:
             print('(')
         try:
@@ -132,15 +161,12 @@ class AcquisitionResult(Result):
             if own is not None:
                 own.free()
         self._fill(prn_indices, r)
-        return
 
-    def _fill32(self, r):
-        """The merged 32-entry arrays of a sharded search (sgx_acquire_sharded) as this object's results."""
-        self._pending = None
-        self._prerun_pending = False
+    def take_merged(self, r):
+        """The merged 32-entry arrays of a sharded search (shard.acquire_sharded) as this object's results."""
         self._internals = dict(freqBin=r["freqBin"], fineIdx=r["fineIdx"])
         self._results = None
-        self._merged = r               # the record array (acquisition.py:201-203) is packed on first access
+        self._reset_lazy(merged=r)     # the record array (acquisition.py:201-203) is packed on first access
 
     def _fill(self, prn_indices, r):
         """The reference's three 32-entry result arrays (acquisition.py:201-203) from the library's per-PRN outputs."""
@@ -162,7 +188,6 @@ class AcquisitionResult(Result):
         self._internals = dict(freqBin=freqBin, fineIdx=fineIdx)
         self._results = np.rec.fromarrays([carrFreq, codePhase_, peakMetric],
                                           names='carrFreq,codePhase,peakMetric')
-        return
 
     def plot(self):
         """Bar chart of the acquisition metric per PRN, acquired signals highlighted (reference
@@ -194,14 +219,24 @@ class AcquisitionResult(Result):
             return
         self._prerun_host()
 
-    def _channels_from_table(self, prn, freq, cph, n_active):
-        """The channel table as the device-side preRun left it (sgx_track_chained)."""
-        nch = len(prn)
-        status = ['T' if i < n_active else '-' for i in range(nch)]
+    def track_chained(self, ctx, rec, n_ch, ms, **kw):
+        """TrackingResult's queued step: where this object's search is still queued on ctx and preRun() was asked for,
+        preRun runs on the device behind it and the tracking kernel behind that (Context.track_chained).  Returns
+        (series[n_ch, 13, ms], ms_done[n_ch], n_active, the channel table the device made - now this object's too), or
+        None: not applicable, nothing was tracked and nothing has changed.  The search itself stays queued."""
+        pending = self._pending
+        if pending is None or pending.ctx is not ctx or not self._prerun_pending:
+            return None
+        got = pending.track_chained(rec, n_ch, ms, **kw)
+        if got is None:
+            return None
+        out, done, prn, freq, cph, n_active = got
+        status = ['T' if i < n_active else '-' for i in range(n_ch)]
         self._prerun_pending = False
         self._channels = np.rec.fromarrays([np.asarray(prn, dtype='int64'), np.asarray(freq, dtype=float),
                                             np.asarray(cph, dtype=float), status],
                                            names='PRN,acquiredFreq,codePhase,status')
+        return out, done, n_active, self._channels
 
     def _prerun_host(self):
         assert isinstance(self.results, np.recarray)
@@ -220,7 +255,6 @@ class AcquisitionResult(Result):
             status[ii] = 'T'
         self._channels = np.rec.fromarrays([PRN, acquiredFreq, codePhase, status],
                                            names='PRN,acquiredFreq,codePhase,status')
-        return
 
     def showChannelStatus(self):
         """ASCII channel table (reference acquisition.py:308-336)."""

@@ -2317,8 +2317,15 @@ static int acquire_any(const AcqCall& a, int n_blocks, int noncoh) {
     return acquire_passes(a, n_blocks, noncoh);
 }
 
+// ONE search may be pending per context, and c->acq_pending belongs to the search that ran last: every search's kernels
+// write the result page and d_small->stage, so every entry point drops what an earlier sgx_acquire_begin left before it
+// touches the device.  sgx_track_chained then answers SGX_E_DEFER and sgx_acquire_end SGX_E_ARG, as for "nothing pending".
+static void acq_drop_pending(sgx_ctx* c) { c->acq_pending.mode = 0; }
+
 static int acquire_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0, int32_t n_prn, int32_t n_blocks, int32_t noncoh,
                           const AcqOut& out, const AcqEnv& env) {
+    SGX_CHECK_ARG(c);
+    acq_drop_pending(c);
     SGX_CHECK_ARG(acq_out_non_null(out));
     SgxSig x;
     const int rc = acq_open_source(c, src, prn0, n_prn, n_blocks, &x);
@@ -2356,11 +2363,12 @@ int sgx_prerun_enqueue(sgx_ctx* c, TrkChan* d_ch, int n_ch, long long skip_bytes
 // the same kernels in the same order, and acq_prerun_kernel repeats the host's arithmetic.
 static int acquire_begin(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0, int32_t n_prn,
                          int32_t n_blocks, int32_t noncoh, const AcqEnv& env) {
+    SGX_CHECK_ARG(c);
+    acq_drop_pending(c);
     SgxSig x;
     int rc = acq_open_source(c, AcqSource{r, offset, nullptr, n_samples}, prn0, n_prn, n_blocks, &x);
     if (rc != SGX_OK) return rc;
     AcqPending& P = c->acq_pending;
-    P.mode = 0;
     const AcqCall a = acq_call(c, x, n_samples, prn0, n_prn, P.res.out(), env);
     bool handled = false;
     rc = acquire_four_step(a, n_blocks, noncoh, &handled, true);
@@ -2395,7 +2403,13 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
                                    size_t n_samples, int32_t n_prn_total, int32_t n_blocks, int32_t noncoh, double* carrFreq,
                                    double* codePhase, double* peakMetric, int32_t* freqBin, int32_t* fineIdx) {
     const AcqOut out{carrFreq, codePhase, peakMetric, freqBin, fineIdx};
-    SGX_CHECK_ARG(c && r && acq_out_non_null(out));
+    SGX_CHECK_ARG(c);
+    // (the rank's search is queued by acquire_begin and looked at in here: nothing is pending after ANY return)
+    struct DropPending {
+        sgx_ctx* c;
+        ~DropPending() { acq_drop_pending(c); }
+    } drop{c};
+    SGX_CHECK_ARG(r && acq_out_non_null(out));
     SGX_CHECK_ARG(world >= 1 && rank >= 0 && rank < world && n_prn_total >= 1 && n_prn_total <= 32);
     SGX_CHECK_ARG(!comm || (comm->n_ranks == world && comm->rank == rank && comm->ctx == c));
     const AcqEnv env = acq_env();
@@ -2460,7 +2474,6 @@ extern "C" int sgx_acquire_sharded(sgx_ctx* c, sgx_comm* comm, int32_t rank, int
     const int rl = acq_look_wait(c, &gather->seq, seq, env.spin);   // the one look
     if (rl != SGX_OK) return rl;
     if (queued) {   // (device time of this rank's search; the search's own page is complete: the gather came behind it)
-        c->acq_pending.mode = 0;
         SGX_HIP(hipEventSynchronize(c->ev[2]));
         acq_event_times(c, false);
     }
@@ -2502,7 +2515,9 @@ static int coherent_checks(sgx_ctx* c, size_t n_samples, const int32_t* prn0, in
 
 static int acquire_coherent_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0, int32_t n_prn, const sgx_acq_params* p,
                                    const AcqOut& out) {
-    SGX_CHECK_ARG(c && (src.r || src.signal) && prn0 && p && acq_out_non_null(out));
+    SGX_CHECK_ARG(c);
+    acq_drop_pending(c);
+    SGX_CHECK_ARG((src.r || src.signal) && prn0 && p && acq_out_non_null(out));
     if (src.r) SGX_CHECK_ARG(src.offset <= src.r->n && src.n_samples <= src.r->n - src.offset);
     const AcqEnv env = acq_env();
     CohGrid g;

@@ -18,7 +18,6 @@ class Result(object):
         self._settings = settings
         self._results = None
         self._channels = None
-        self._merged = None
 
     @property
     def settings(self):
@@ -43,7 +42,6 @@ class Result(object):
     @results.setter
     def results(self, records):
         assert isinstance(records, np.recarray)
-        self._merged = None        # (AcquisitionResult: arrays of a sharded search not yet packed)
         self._results = records
 
     def plot(self):

@@ -118,9 +118,9 @@ def acquire_sharded(acq, long_signal, rank, world, gather, n_prn=None, n_blocks=
         # ONE library call: the search queued, the peaks packed on the device, one ncclAllGather on the same stream (or none:
         # a shard run alone), one look, the merge in C (sgx_acquire_sharded) - no Python between the kernels and the gather
         from . import engine
-        ctx = engine.get_context(settings, acq._device)
-        acq._fill32(ctx.acquire_sharded(native(), rank, world, long_signal.record, long_signal.offset, long_signal.length,
-                                        n_prn_total=n_prn, n_blocks=n_blocks, noncoh=noncoh))
+        ctx = engine.get_context(settings, acq.device)
+        acq.take_merged(ctx.acquire_sharded(native(), rank, world, long_signal.record, long_signal.offset, long_signal.length,
+                                            n_prn_total=n_prn, n_blocks=n_blocks, noncoh=noncoh))
         return acq
     if mine:
         acq.acquire(long_signal, n_blocks=n_blocks, noncoh=noncoh, prn_indices=mine)

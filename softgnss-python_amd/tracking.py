@@ -6,6 +6,7 @@ per-millisecond series come back as a record array shaped like the reference's.
 """
 from __future__ import print_function
 
+import contextlib
 import os
 
 import numpy as np
@@ -21,6 +22,9 @@ RESULT_DTYPE = [('status', 'S1'), ('absoluteSample', 'object'), ('codeFreq', 'ob
                 ('PRN', 'int64')]   # reference tracking.py:285-293
 QUALITY_DTYPE = [('PRN', 'int64'), ('CNo', 'object'), ('carrLock', 'object'), ('lockPass', 'object'),
                  ('lostAtMs', 'int64'), ('medianCNo', 'float64')]
+_DT_CODES = {'i1': _native.DT_INT8, 'u1': _native.DT_UINT8, 'i2': _native.DT_INT16, 'u2': _native.DT_UINT16,
+             'i4': _native.DT_INT32, 'u4': _native.DT_UINT32, 'i8': _native.DT_INT64, 'u8': _native.DT_UINT64,
+             'f2': _native.DT_FLOAT16, 'f4': _native.DT_FLOAT32, 'f8': _native.DT_FLOAT64}   # numpy kind + size -> sgx_track_ex
 
 
 class ReplayResult(object):
@@ -58,16 +62,21 @@ class TrackingResult(Result):
         """verbose: print the reference's progress lines (tracking.py:137-143: one per channel and 50 ms) - after the
         kernel has finished; the GPU is never synchronised every 50 ms to print."""
         self._verbose = verbose
-        self._results = None
         self._acq = acqResult
-        # (a deferred acquisition whose preRun is still to run on the device: the table arrives with the tracking results)
-        self._channels = None if getattr(acqResult, "_prerun_pending", False) else acqResult.channels
+        # (a deferred acquisition whose preRun is still to run on the device: the table arrives with the tracking results;
+        # anything with .channels and .settings serves as the acquisition)
+        self._channels = None if getattr(acqResult, "prerun_queued", False) else acqResult.channels
         self._settings = acqResult.settings
         self._device = device
+        self.kernel_ms = None       # HIP-event duration of the tracking kernel
+        self._reset()
+
+    def _reset(self):
+        """Nothing tracked: where __init__ leaves the object and every track() starts."""
+        self._results = None
         self._lazy = None           # (series, active channel numbers): .results is packed on first access
         self.chained = False        # the last track() ran preRun on the device behind a deferred acquisition
         self.series = None          # float64[n_active, 13, ms] in _native.SERIES order
-        self.kernel_ms = None       # HIP-event duration of the tracking kernel
         self._quality = None        # .quality, computed on first access (sgx_track_quality)
         self._lost_rows = ()        # rows of .results the lock detector declared lost inside track() (status '-')
         self._active = []           # channel numbers of the rows of .series
@@ -77,9 +86,14 @@ class TrackingResult(Result):
         """False after the reference's short-read exit (tracking.py:159-163 leaves the results unset) and before track()."""
         return self._results is not None or self._lazy is not None
 
-    def _materialize(self):
-        if self._channels is None and self._acq is not None:
+    def _table(self):
+        """The acquisition's channel table, looked at when first needed (a queued search and its preRun end here)."""
+        if self._channels is None:
             self._channels = self._acq.channels
+        return self._channels
+
+    def _materialize(self):
+        self._table()
         if self._lazy is not None:
             series, active = self._lazy
             self._lazy = None
@@ -95,11 +109,7 @@ class TrackingResult(Result):
                 res[j].status = '-'
             self._results = res
 
-    @property
-    def results(self):
-        return Result.results.fget(self)
-
-    @results.setter
+    @Result.results.setter
     def results(self, records):
         Result.results.fset(self, records)
         self._quality = None
@@ -115,17 +125,37 @@ class TrackingResult(Result):
             self._quality = self._compute_quality()
         return self._quality
 
+    def _tracked(self, names=_native.SERIES, table=True):
+        """What was tracked - from .series, or from an assigned .results (the reference's cache path): (series float64[n,
+        k, ms], the row of axis 1 that holds each of `names` - all 13 of .series, only `names` of .results -, PRN per
+        channel and, with `table`, each channel's (PRN, acquiredFreq, codePhase) from the acquisition's table)."""
+        if self.series is not None and not self._assigned:
+            series, row = self.series, {name: _native.SERIES.index(name) for name in names}
+            active = list(self._active)
+            prn = [int(self._channels[i].PRN) for i in active]
+        else:
+            res = self.results
+            series = np.stack([np.stack([np.asarray(r[name], dtype=np.float64) for name in names]) for r in res]) \
+                if len(res) else np.empty((0, len(names), 0))
+            row = {name: k for k, name in enumerate(names)}
+            prn = [int(p) for p in res.PRN]
+            active = None
+        if not table:
+            return series, row, prn, None
+        channel = self._table()
+        if active is None:
+            active = [i for i in range(len(channel)) if channel[i].PRN != 0][:len(prn)]
+            if [int(channel[i].PRN) for i in active] != prn:
+                raise ValueError("the results' PRNs are not those of the acquisition's channels: replay() needs each "
+                                 "channel's acquiredFreq and codePhase")
+        return series, row, prn, [(int(channel[i].PRN), float(channel[i].acquiredFreq), float(channel[i].codePhase))
+                                  for i in active]
+
     def _compute_quality(self):
         settings = self._settings
         params = _native.lock_params(settings)
-        if self.series is not None and not self._assigned:
-            i_p, q_p = self.series[:, 3], self.series[:, 7]      # rows of the [n, 13, ms] array, passed as they lie
-            prn = [int(self._channels[i].PRN) for i in self._active]
-        else:
-            res = self.results
-            i_p = np.stack([np.asarray(r, dtype=np.float64) for r in res.I_P]) if len(res) else np.empty((0, 0))
-            q_p = np.stack([np.asarray(r, dtype=np.float64) for r in res.Q_P]) if len(res) else np.empty((0, 0))
-            prn = [int(p) for p in res.PRN]
+        series, row, prn, _ = self._tracked(("I_P", "Q_P"), table=False)
+        i_p, q_p = series[:, row["I_P"]], series[:, row["Q_P"]]   # rows of the [n, k, ms] array, passed as they lie
         q = np.recarray((len(prn),), dtype=QUALITY_DTYPE)
         if not len(prn):
             return q
@@ -151,40 +181,15 @@ class TrackingResult(Result):
         assigned from a cache.  Returns a ReplayResult (.taps, .PRN, .I, .Q, .envelope())."""
         settings = self._settings
         taps = np.atleast_1d(np.asarray(taps, dtype=np.float64))
-        if self._channels is None and self._acq is not None:
-            self._channels = self._acq.channels
-        channel = self._channels
-        if self.series is not None and not self._assigned:
-            series = self.series
-            active = list(self._active)
-        else:
-            res = self.results
-            series = np.stack([np.stack([np.asarray(r[name], dtype=np.float64) for name in _native.SERIES]) for r in res]) \
-                if len(res) else np.empty((0, _native.NUM_SERIES, 0))
-            active = [i for i in range(len(channel)) if channel[i].PRN != 0][:len(res)]
-            if len(active) != len(res) or [int(channel[i].PRN) for i in active] != [int(p) for p in res.PRN]:
-                raise ValueError("the results' PRNs are not those of the acquisition's channels: replay() needs each "
-                                 "channel's acquiredFreq and codePhase")
-        prn = [int(channel[i].PRN) for i in active]
-        if not active:
+        series, _, prn, chans = self._tracked()
+        if not chans:
             return ReplayResult(taps, prn, np.zeros((0, taps.size, 2, series.shape[2])))
-        chans = [(int(channel[i].PRN), float(channel[i].acquiredFreq), float(channel[i].codePhase)) for i in active]
         ctx = engine.get_context(settings, self._device)
         dtype_code, isz = self._data_type()
-        own = None
-        if isinstance(fid, DeviceFile):
-            rec, file_off = fid.record, fid.file_offset
-        else:
-            first = (int(settings.skipNumberOfBytes + min(c[2] for c in chans)) // 4096) * 4096
-            last = int(series[:, 0, :].max())
-            own = rec = self._window(fid, first, last - first)
-            file_off = first
-        try:
+        first = int(settings.skipNumberOfBytes + min(c[2] for c in chans))
+        with self._record(fid, first, lambda: int(series[:, 0, :].max()) - first) as (rec, file_off):
             out = ctx.track_replay(rec, chans, series, taps, rec_file_offset=file_off, data_type=dtype_code)
             kernel_ms = ctx.replay_timing()[0]
-        finally:
-            if own is not None:
-                own.free()
         return ReplayResult(taps, prn, out, kernel_ms)
 
     def showTrackingQuality(self):
@@ -213,15 +218,12 @@ class TrackingResult(Result):
         """Settings.dataType -> (sgx_track_ex data_type, bytes per sample).  The reference reads np.fromfile(fid,
         dataType, blksize) (tracking.py:154) but seeks and tells in BYTES (tracking.py:107, 255): both are kept."""
         dt = np.dtype(self._settings.dataType)
-        codes = {'i1': _native.DT_INT8, 'u1': _native.DT_UINT8, 'i2': _native.DT_INT16, 'u2': _native.DT_UINT16,
-                 'i4': _native.DT_INT32, 'u4': _native.DT_UINT32, 'i8': _native.DT_INT64, 'u8': _native.DT_UINT64,
-                 'f2': _native.DT_FLOAT16, 'f4': _native.DT_FLOAT32, 'f8': _native.DT_FLOAT64}
         key = dt.kind + str(dt.itemsize)
         # int8 / uint8 / int16 have their own kernels; float32 records of integers times one power of two are narrowed
         # to them exactly; every other real type is read sample by sample where it lies (include/sgx.h, sgx_track_ex)
         little = dt.byteorder in ('<', '|') or (dt.byteorder == '=' and np.little_endian)
-        if key in codes and little:
-            return codes[key], dt.itemsize
+        if key in _DT_CODES and little:
+            return _DT_CODES[key], dt.itemsize
         raise TypeError("the GPU path tracks little-endian real IF samples - int8 ... uint64, float16 / 32 / 64 - not "
                         "Settings.dataType %r" % (self._settings.dataType,))
 
@@ -244,6 +246,45 @@ class TrackingResult(Result):
             data = np.frombuffer(fid.read(need), dtype=np.int8)
         return ctx.upload(data)
 
+    @contextlib.contextmanager
+    def _record(self, fid, first, need):
+        """(the record a launch runs on, the file offset of its first byte): a DeviceFile's resident record, or bytes
+        [first, first + need()) of the reference's file in a record of this call's own, freed on the way out."""
+        if isinstance(fid, DeviceFile):
+            yield fid.record, fid.file_offset
+            return
+        # the window starts on a 4 KiB boundary of the FILE: page-aligned reads, and every sample keeps the place
+        # inside its 16-byte group that it has in a record resident from file offset 0 - the kernel's lanes then
+        # add the same samples in the same order, and the series are bit-identical to the resident run's
+        start = (first // 4096) * 4096
+        rec = self._window(fid, start, first - start + need())
+        try:
+            yield rec, start
+        finally:
+            rec.free()
+
+    def _finish(self, fid, series, active, done, ms):
+        """The tail of a launch, eager or chained.  series: float64[len(active), 13, ms], done: ms completed per row."""
+        if not active:
+            self._results = np.recarray((0,), dtype=RESULT_DTYPE)
+            self.series = np.empty((0, _native.NUM_SERIES, ms))
+            return
+        if np.any(done != ms):
+            print('Not able to read the specified number of samples for tracking, exiting!')
+            fid.close()
+            return
+        if self._verbose:
+            channel, nch = self._channels, int(self._settings.numberOfChannels)
+            for i in active:
+                for k in range(0, ms, 50):
+                    print('Tracking: Ch %d' % (i + 1) + ' of %d' % nch + '; PRN#%02d' % int(channel[i].PRN) +
+                          '; Completed %d' % k + ' of %d' % ms + ' msec')
+        fid.seek(int(series[-1, 0, ms - 1]), 0)    # where the reference's last read left the file
+        self.series = series
+        self._lazy = (series, active)              # the record array of object fields is packed on first access of .results
+        self._active = active
+        self._detect_locks()
+
     def track(self, fid):
         """Code and carrier tracking of all channels (reference tracking.py:13-295).
 
@@ -257,99 +298,44 @@ class TrackingResult(Result):
         ctx = engine.get_context(settings, self._device)
         ms = int(settings.msToProcess)            # float in the reference (Q9)
         nch = int(settings.numberOfChannels)
-        self._lazy = None
-        self._results = None
-        self.series = None
-        self.chained = False
-        self._quality = None
-        self._lost_rows = ()
-        self._assigned = False
-        self._active = []
+        self._reset()
         if self._channels is None and self._try_chained(fid, ctx, nch, ms):
-            self._detect_locks()
             return
-        if self._channels is None:
-            self._channels = self._acq.channels   # (the queued sequence did not apply: the search is looked at, preRun runs here)
-        channel = self._channels
+        channel = self._table()   # (where the queued sequence did not apply: the search is looked at, preRun runs here)
         active = [i for i in range(nch) if channel[i].PRN != 0]
         if not active:
-            self._results = np.recarray((0,), dtype=RESULT_DTYPE)
-            self.series = np.empty((0, _native.NUM_SERIES, ms))
-            return
+            return self._finish(fid, None, active, None, ms)
         chans = [(int(channel[i].PRN), float(channel[i].acquiredFreq), float(channel[i].codePhase))
                  for i in active]
         dtype_code, isz = self._data_type()
-        own = None
-        if isinstance(fid, DeviceFile):
-            rec, file_off = fid.record, fid.file_offset
-        else:
+        first = int(settings.skipNumberOfBytes + min(c[2] for c in chans))
+        last = int(settings.skipNumberOfBytes + max(c[2] for c in chans))
+
+        def need():
             n = settings.samplesPerCode
-            first = int(settings.skipNumberOfBytes + min(c[2] for c in chans))
-            last = int(settings.skipNumberOfBytes + max(c[2] for c in chans))
-            # the window starts on a 4 KiB boundary of the FILE: page-aligned reads, and every sample keeps the place
-            # inside its 16-byte group that it has in a record resident from file offset 0 - the kernel's lanes then
-            # add the same samples in the same order, and the series are bit-identical to the resident run's
-            first_al = (first // 4096) * 4096
-            need = (last - first_al) + (ms * (n + 2) + n) * isz   # a block is at most samplesPerCode + 1 long
-            first = first_al
-            own = rec = self._window(fid, first, need)
-            file_off = first
-        try:
+            return last - first + (ms * (n + 2) + n) * isz   # a block is at most samplesPerCode + 1 long
+        with self._record(fid, first, need) as (rec, file_off):
             series, done = ctx.track(rec, chans, ms, rec_file_offset=file_off, data_type=dtype_code)
             self.kernel_ms = ctx.timing()["track_ms"]
-        finally:
-            if own is not None:
-                own.free()
-        if np.any(done != ms):
-            print('Not able to read the specified number of samples for tracking, exiting!')
-            fid.close()
-            return None
-        if self._verbose:
-            for j, i in enumerate(active):
-                for k in range(0, ms, 50):
-                    print('Tracking: Ch %d' % (i + 1) + ' of %d' % nch + '; PRN#%02d' % int(channel[i].PRN) +
-                          '; Completed %d' % k + ' of %d' % ms + ' msec')
-        fid.seek(int(series[-1, 0, ms - 1]), 0)    # where the reference's last read left the file
-        self.series = series
-        self._lazy = (series, active)              # the record array of object fields is packed on first access of .results
-        self._active = active
-        self._detect_locks()
-        return
+        self._finish(fid, series, active, done, ms)
 
     def _try_chained(self, fid, ctx, nch, ms):
-        """A deferred acquisition + preRun are pending on this context and the record is resident: preRun runs on the
-        device, the tracking kernel behind it, and the host waits once (sgx_track_chained).  False: not applicable -
-        the eager sequence follows."""
-        acq = self._acq
-        pend = getattr(acq, "_pending", None)
-        if not (isinstance(fid, DeviceFile) and pend is not None and pend[0] is ctx and getattr(acq, "_prerun_pending", False)
-                and getattr(ctx, "_acq_token", None) == pend[2] and not self._verbose and 1 <= nch <= 32):
+        """The record is resident, and the acquisition's search and its preRun are still queued on this context: preRun
+        runs on the device, the tracking kernel behind it, and the host waits once (AcquisitionResult.track_chained).
+        False: not applicable - the eager sequence follows."""
+        if not (isinstance(fid, DeviceFile) and not self._verbose and 1 <= nch <= 32):
             return False
         try:
             dtype_code, isz = self._data_type()
         except TypeError:
             return False
-        got = ctx.track_chained(fid.record, nch, ms, rec_file_offset=fid.file_offset, data_type=dtype_code)
+        got = self._acq.track_chained(ctx, fid.record, nch, ms, rec_file_offset=fid.file_offset, data_type=dtype_code)
         if got is None:
             return False
-        out, done, prn, freq, cph, n_act = got
+        out, done, n_act, self._channels = got           # (the table: what preRun made, on the device)
         self.chained = True
         self.kernel_ms = ctx.timing()["track_ms"]
-        acq._channels_from_table(prn, freq, cph, n_act)   # what preRun made, on the device
-        self._channels = acq._channels
-        if n_act == 0:
-            self._results = np.recarray((0,), dtype=RESULT_DTYPE)
-            self.series = np.empty((0, _native.NUM_SERIES, ms))
-            return True
-        if np.any(done[:n_act] != ms):
-            print('Not able to read the specified number of samples for tracking, exiting!')
-            fid.close()
-            return True
-        series = out[:n_act]
-        fid.seek(int(series[-1, 0, ms - 1]), 0)
-        self.series = series
-        self._lazy = (series, list(range(n_act)))
-        self._active = list(range(n_act))
+        self._finish(fid, out[:n_act], list(range(n_act)), done[:n_act], ms)
         return True
 
     def plot(self):

@@ -1964,12 +1964,12 @@ def test_deferred_step_equals_the_eager_one(default_record):
         ae, te, fe = _step(m, s, rec, ms, False)
         ad, td, fd = _step(m, s, rec, ms, True)
         assert td.chained == chained and not te.chained
-        assert (ad._pending is not None) == chained   # chained: tracking is done and nobody has looked at the search yet
+        assert ad.queued == chained   # chained: tracking is done and nobody has looked at the search yet
         assert np.array_equal(td.series, te.series)
         assert fd.tell() == fe.tell()
         for f in ("carrFreq", "codePhase", "peakMetric"):
             assert np.array_equal(ad.results[f], ae.results[f]), f
-        assert ad._pending is None
+        assert not ad.queued
         for f in ("freqBin", "fineIdx"):
             assert np.array_equal(ad.internals[f], ae.internals[f]), f
         for f in ("PRN", "acquiredFreq", "codePhase", "status"):
@@ -1995,7 +1995,7 @@ def test_deferred_results_looked_at_early_and_superseded(default_record):
     want.preRun()
     a = m.AcquisitionResult(s, device=0, deferred=True)
     a.acquire(m.DeviceSignal(rec, 0, 11 * n))
-    assert np.array_equal(a.peakMetric, want.peakMetric) and a._pending is None     # the look
+    assert np.array_equal(a.peakMetric, want.peakMetric) and not a.queued     # the look
     a.preRun()
     assert np.array_equal(a.channels.PRN, want.channels.PRN)
     t = m.TrackingResult(a, device=0)
@@ -2005,8 +2005,8 @@ def test_deferred_results_looked_at_early_and_superseded(default_record):
     b = m.AcquisitionResult(s, device=0, deferred=True)
     b.acquire(m.DeviceSignal(rec, 0, 11 * n))
     b.preRun()
-    assert b._prerun_pending
-    assert np.array_equal(b.channels.acquiredFreq, want.channels.acquiredFreq) and not b._prerun_pending
+    assert b.prerun_queued
+    assert np.array_equal(b.channels.acquiredFreq, want.channels.acquiredFreq) and not b.prerun_queued
     # two deferred searches on one context: the first one's owner is told
     c1 = m.AcquisitionResult(s, device=0, deferred=True)
     c1.acquire(m.DeviceSignal(rec, 0, 11 * n))
@@ -2171,3 +2171,32 @@ def test_a_sharded_search_packed_on_the_host_equals_the_eager_call(unqueued_sear
         ref = want[k].astype(np.int64) if reset == -1 else want[k]
         assert got[k].shape == (32,) and got[k].dtype == ref.dtype, k
         assert np.array_equal(got[k][:3], ref) and np.all(got[k][3:] == reset), k
+
+
+def test_an_eager_search_drops_the_search_queued_before_it():
+    """One search may be pending per context (include/sgx.h): an eager search takes the result page of a queued one, so the
+    queued one is dropped - sgx_track_chained then answers "does not apply" and sgx_acquire_end "no acquisition is
+    pending" - and the eager search returns what it returns on a fresh context.  Before, the coherent paths
+    (acquire_coherent_shift, acquire_passes) never wrote the context's pending state, so sgx_track_chained would have built
+    a channel table from the half-overwritten page: that is read from the code, it has not been run on a GPU."""
+    m = pkg()
+    s = m.Settings()
+    n = s.samplesPerCode
+    scene = m.synth.Scene.make(0xD0B5, s.samplingFreq, s.IF, [1, 3], [1750.0, -3300.0], [n // 3, n - 5], [9, 8])
+    idx, kw = [0, 1, 2, 3], dict(coherent_ms=2, n_windows=2)
+    fresh = m._native.Context(s, 0)
+    try:
+        want = fresh.acquire_coherent(fresh.synth(scene, 11 * n), 0, 11 * n, idx, **kw)
+    finally:
+        fresh.close()
+    assert list(want["carrFreq"] > 0) == [True, False, True, False]
+    ctx = m.engine.get_context(s, 0)
+    rec = ctx.synth(scene, 11 * n)
+    ctx.acquire_begin(rec, 0, 11 * n, idx)
+    got = ctx.acquire_coherent(rec, 0, 11 * n, idx, **kw)
+    assert ctx.track_chained(rec, 4, 20) is None
+    with pytest.raises(m._native.SgxError, match="no acquisition is pending"):
+        ctx.acquire_end(4)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+    rec.free()
