@@ -161,6 +161,14 @@ def test_acquire_device_signal_equals_host_signal(default_record):
     assert np.array_equal(a.codePhase, g["codePhase"]) and np.array_equal(a.carrFreq, g["carrFreq"])
 
 
+# The implementation switches of the acquisition call path, as test_acquire_variants_agree describes them
+ACQ_VARIANTS = ({"SGX_ACQ_SPIN": "0"}, {"SGX_ACQ_FINE_V1": "1"}, {"SGX_ACQ_V1": "1"}, {"SGX_ACQ_DEVICE_LED": "0"},
+                {"SGX_ACQ_FRONT": "0"}, {"SGX_ACQ_DEVICE_LED": "0", "SGX_ACQ_SPIN": "0"}, {"SGX_ACQ_TOP2": "0"},
+                {"SGX_ACQ_TOP2": "0", "SGX_ACQ_DEVICE_LED": "0"}, {"SGX_ACQ_STREAMS": "1"})
+# ... and those that leave the coarse search's arithmetic alone: peakMetric bit for bit
+ACQ_VARIANTS_EXACT = ("SGX_ACQ_DEVICE_LED", "SGX_ACQ_FRONT", "SGX_ACQ_TOP2", "SGX_ACQ_STREAMS")
+
+
 def test_acquire_variants_agree(default_record):
     """The knobs that pick another implementation of a stage: the coarse outcome fetched by a stream synchronisation
     instead of the spin on the pinned page (SGX_ACQ_SPIN=0), the fine search on the pass-per-radix transform
@@ -177,9 +185,7 @@ def test_acquire_variants_agree(default_record):
     ref = m.AcquisitionResult(s, device=0)
     ref.acquire(x)
     assert np.array_equal(ref.codePhase, g["codePhase"]) and np.array_equal(ref.carrFreq, g["carrFreq"])
-    for env in ({"SGX_ACQ_SPIN": "0"}, {"SGX_ACQ_FINE_V1": "1"}, {"SGX_ACQ_V1": "1"}, {"SGX_ACQ_DEVICE_LED": "0"},
-                {"SGX_ACQ_FRONT": "0"}, {"SGX_ACQ_DEVICE_LED": "0", "SGX_ACQ_SPIN": "0"}, {"SGX_ACQ_TOP2": "0"},
-                {"SGX_ACQ_TOP2": "0", "SGX_ACQ_DEVICE_LED": "0"}, {"SGX_ACQ_STREAMS": "1"}):
+    for env in ACQ_VARIANTS:
         os.environ.update(env)
         try:
             a = m.AcquisitionResult(s, device=0)
@@ -190,8 +196,56 @@ def test_acquire_variants_agree(default_record):
         assert np.array_equal(a.codePhase, ref.codePhase) and np.array_equal(a.carrFreq, ref.carrFreq), env
         assert np.array_equal(a.internals["freqBin"], ref.internals["freqBin"]), env
         assert np.allclose(a.peakMetric, ref.peakMetric, rtol=1e-9, atol=0), env
-        if "SGX_ACQ_DEVICE_LED" in env or "SGX_ACQ_FRONT" in env or "SGX_ACQ_TOP2" in env or "SGX_ACQ_STREAMS" in env:
+        if any(k in env for k in ACQ_VARIANTS_EXACT):
             assert np.array_equal(a.peakMetric, ref.peakMetric), env
+
+
+def test_acquire_variants_agree_on_every_rule_and_source(default_record):
+    """test_acquire_variants_agree's switches on the branches it does not reach: three PRNs (two in the scene, one
+    absent; chunks on two queues), the reference rule (2 blocks) and the non-coherent sum of 10 blocks (290 rows per PRN:
+    runs of bins on two queues, the round-4 sequence with n_prn x n_blocks rows), an int8 record and the same samples as
+    float64 (the four-launch front).  Every combination under every switch against its own default: same indices, same
+    frequencies, peak metrics to rounding - and bit for bit where the switch leaves the coarse arithmetic alone (every PRN
+    of every rule and source held that before the call path was restructured around shared stages: none is excepted).  The two
+    sources agree on indices and frequencies."""
+    m, s, ctx = _ctx()
+    n = 11 * 38192
+    x = np.ascontiguousarray(default_record[:n])
+    x64 = x.astype(np.float64)
+    rec = ctx.upload(x)
+    prns = [0, 1, 6]
+    exact = ("codePhase", "carrFreq", "freqBin", "fineIdx")
+
+    def search(source, nb, nc):
+        if source == "int8":
+            return ctx.acquire(rec, 0, n, prns, n_blocks=nb, noncoh=nc)
+        return ctx.acquire_f64(x64, prns, n_blocks=nb, noncoh=nc)
+
+    try:
+        for nb, nc in ((2, False), (10, True)):
+            refs = {}
+            for source in ("int8", "float64"):
+                ref = refs[source] = search(source, nb, nc)
+                assert ref["carrFreq"][0] > 0 and ref["carrFreq"][2] > 0 and ref["carrFreq"][1] == 0, (nb, nc, source)
+                for env in ACQ_VARIANTS:
+                    os.environ.update(env)
+                    try:
+                        a = search(source, nb, nc)
+                    finally:
+                        for k in env:
+                            os.environ.pop(k, None)
+                    what = (nb, nc, source, env)
+                    print(what, "bit-equal" if np.array_equal(a["peakMetric"], ref["peakMetric"]) else "rel %.3g" % np.max(
+                        np.abs(a["peakMetric"] / ref["peakMetric"] - 1)))
+                    for f in exact:
+                        assert np.array_equal(a[f], ref[f]), (f, what)
+                    assert np.allclose(a["peakMetric"], ref["peakMetric"], rtol=1e-9, atol=0), what
+                    if any(k in env for k in ACQ_VARIANTS_EXACT):
+                        assert np.array_equal(a["peakMetric"], ref["peakMetric"]), what
+            for f in exact:
+                assert np.array_equal(refs["int8"][f], refs["float64"][f]), (f, nb, nc)
+    finally:
+        rec.free()
 
 
 def _golden_tracker(m, g, ms=None, nch=4):
