@@ -815,6 +815,80 @@ int sgx_if_resample(sgx_ctx* c, const sgx_if* rec, const int16_t* taps, int32_t 
 int sgx_resamp_timing(sgx_ctx* c, float* kernel_ms);
 int sgx_resamp_tile(int32_t* tile_bytes);
 
+/* ---- multi-antenna records: a space-time combiner with power-inversion weights (no reference counterpart; directly behind
+ * the unpacker, in front of every other stage) ---------------------------------------------------------------------------
+ * Opt-in.  A resident int8 record of N bytes holds F = N / (A lanes) frames of A antennas: byte (f A + a) lanes + l is
+ * component l of antenna a at frame f; lanes = 1 a real record x_a[f], lanes = 2 interleaved I/Q, z_a[f] = I + j Q.
+ * SGX_ARRAY_OFFSET_BINARY first turns every byte into byte - 128 (XOR 0x80 read as int8).  A = 2 .. SGX_ARRAY_MAX_ANTENNAS,
+ * K odd, 1 .. SGX_ARRAY_MAX_TAPS, A K <= SGX_ARRAY_MAX_WEIGHTS, N a multiple of A lanes; x = 0 outside the record.  The
+ * exact integer statistics of the streams are taken on the GPU (sgx_array_stats), weights that minimise the output power
+ * while one tap of one antenna is held at 1 are designed from them on the host (sgx_array_design: power inversion, which
+ * needs no array geometry, calibration or satellite direction - the GNSS signals lie below the noise, so only what stands
+ * above it is cancelled), and the A streams go through one integer FIR each and are summed into ONE int8 record
+ * (sgx_if_combine) that every later stage reads as before.  tests/array_spec.py restates all of it in numpy.
+ *
+ * sgx_array_stats: the lag statistics of the whole record, int64 rho[A][A][K][lanes]:
+ *   lanes = 1   rho[a][b][d]    = sum_{f = 0}^{F-1-d} x_a[f + d] x_b[f]
+ *   lanes = 2   rho[a][b][d][.] = sum_{f = 0}^{F-1-d} z_a[f + d] conj(z_b[f]),  the real part, then the imaginary part
+ * Exact integers: a workgroup sums a tile of sgx_array_stats_tile frames in 32 bits (at most 2^27 in magnitude) and adds
+ * the tile's sums into 64 bits, so no partial sum wraps; the result does not depend on the order and two calls are
+ * bit-identical.  A record that is still streaming in is waited for; N = 0 gives zeros and launches nothing.
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: lanes not 1 or 2, A or K outside the limits
+ * above, an unknown flag bit, a NULL pointer, N no multiple of A lanes, a record on another device than the context's.
+ *
+ * sgx_array_design: exact host code, needs no GPU.  frames = F.  n = A K, c = (K - 1) / 2, the stacked index (a, k) = a K + k
+ * stands for x_a[f + c - k].  In doubles, in this order (every sum from its first index up, starting from the first term):
+ *   1. R[(a,k)][(b,l)] = rho_ab[l - k] / frames, rho_ab[-d] = conj(rho_ba[d]) (int64 -> double, then the division)
+ *   2. tr = sum_i R[i][i];  ld = (loading tr) / n;  RL = R with ld added to every diagonal entry
+ *   3. M = RL (lanes = 1, m = n) or the real symmetric embedding [[P, -Q], [Q, P]] of RL = P + j Q (lanes = 2, m = 2 n);
+ *      Cholesky M = L L^T, for j = 0 .. m-1, for i = j .. m-1:  s = M[i][j] - L[i][0] L[j][0] - .. - L[i][j-1] L[j][j-1]
+ *      (one subtraction after the other); i = j: s > 0 or the matrix is refused, L[j][j] = sqrt(s); else L[i][j] = s / L[j][j].
+ *      b = unit vector at (ref, c).  Forward: y[i] = (b[i] - L[i][0] y[0] - .. - L[i][i-1] y[i-1]) / L[i][i], i upwards;
+ *      back: g[i] = (y[i] - L[i+1][i] g[i+1] - .. - L[m-1][i] g[m-1]) / L[i][i], i downwards.  lanes = 2: g = g[0..n) + j g[n..2n)
+ *   4. g <- g / Re g[(ref,c)] (each component divided);  h = conj(g)
+ *   5. p_out = g^H R g with the UNLOADED R: t_i = sum_j R[i][j] g[j] (lanes = 2: re = P gr - Q gi, im = P gi + Q gr, each
+ *      product added or subtracted in this order per j), p_out = sum_i (gr_i tr_i [+ gi_i ti_i])
+ *   6. *gain = target_rms / sqrt(p_out / lanes)
+ *   7. taps[(a K + k) lanes + l] = rint((2^SGX_ARRAY_SHIFT gain) h) (half to even), re then im;  *shift = SGX_ARRAY_SHIFT
+ *   8. *suppression_db = 10 log10(R[(ref,c)][(ref,c)] / p_out)
+ *   9. weights[(a K + k) lanes + l] = h before the gain
+ * The output w[f] = sum_a sum_k h_a[k] z_a[f + c - k] = g^H u[f] then has the least power among all weights with
+ * h_ref[c] = 1, and power target_rms^2 per component behind the gain.
+ * SGX_E_ARG with a text that names the cause: a matrix that is not positive definite (an all-zero record), a tap beyond
+ * 32 512 in magnitude, 128 sum(|re| + |im|) >= 2^31, ref outside 0 .. A - 1, loading < 0 or not finite, target_rms outside
+ * (0, 127], frames < 1, the limits above, a NULL pointer (weights, gain and suppression_db may be NULL).
+ *
+ * sgx_if_combine: a NEW int8 record of F lanes bytes; taps int16 [A][K] (lanes = 2: COMPLEX, [A][K][2], re and im
+ * interleaved), c = (K - 1) / 2, rnd = shift ? 2^(shift-1) : 0, q(a) = clip((a + rnd) >> shift, -127, 127) with an
+ * arithmetic (floor) shift, exactly as sgx_if_decimate:
+ *   lanes = 1   y[f] = q(sum_a sum_k h_a[k] x_a[f + c - k])
+ *   lanes = 2   w[f] = sum_a sum_k h_a[k] z_a[f + c - k],  output bytes q(Re w[f]), q(Im w[f])
+ * Output frame f is the instant of input frame f.  The sums are exact in int32 under the bound on sum|h|, so the output is
+ * the contract's byte for byte.  *clipped (may be NULL): the exact count of output bytes whose value before the clip lay
+ * outside [-127, 127].  The input is left alone; a record that is still streaming in is waited for; *out is an ordinary
+ * record (sgx_if_free); N = 0 gives an empty record and launches nothing.
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: lanes not 1 or 2, A or K outside the limits
+ * above, shift outside 0 .. 30, a tap component beyond 32 512 in magnitude, 128 sum(|re| + |im|) over all antennas >= 2^31,
+ * an unknown flag bit, a NULL pointer, N no multiple of A lanes, a record on another device than the context's, a record
+ * beyond one launch.
+ * sgx_array_stats_timing, sgx_combine_timing: HIP-event time of the last call's kernel on this context.
+ * sgx_array_stats_tile: the frames one workgroup sums at a time; sgx_combine_tile: the output bytes one workgroup makes. */
+#define SGX_ARRAY_MAX_ANTENNAS 8
+#define SGX_ARRAY_MAX_TAPS 15
+#define SGX_ARRAY_MAX_WEIGHTS 64
+#define SGX_ARRAY_SHIFT 12
+#define SGX_ARRAY_OFFSET_BINARY 1
+int sgx_array_stats(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, int32_t K, int32_t flags, int64_t* rho);
+int sgx_array_stats_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_array_stats_tile(int32_t* tile_frames);
+int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lanes, int32_t A, int32_t K, int32_t ref, double loading,
+                     double target_rms, int16_t* taps, int32_t* shift, double* weights, double* gain,
+                     double* suppression_db);
+int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, const int16_t* taps, int32_t K, int32_t shift,
+                   int32_t flags, sgx_if** out, int64_t* clipped);
+int sgx_combine_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_combine_tile(int32_t* tile_bytes);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -208,6 +208,15 @@ _PROTOS = {
                                   C.POINTER(C.c_int64)]),
     "sgx_resamp_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_resamp_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_array_stats": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "sgx_array_stats_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_array_stats_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_array_design": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
+                                   C.POINTER(C.c_int32), _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "sgx_if_combine": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P),
+                                 C.POINTER(C.c_int64)]),
+    "sgx_combine_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_combine_tile": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -722,6 +731,45 @@ def resamp_tile():
     return _tile("sgx_resamp_tile")
 
 
+ARRAY_MAX_ANTENNAS = 8
+ARRAY_MAX_TAPS = 15
+ARRAY_MAX_WEIGHTS = 64
+ARRAY_SHIFT = 12
+ARRAY_OFFSET_BINARY = 1
+
+
+def array_design(rho, frames, lanes, ref=0, loading=1e-3, target_rms=12.0):
+    """The power-inversion weights of the multi-antenna combiner (sgx_array_design; exact host code, needs no GPU) from the
+    lag statistics rho, int64[A, A, K, lanes] of `frames` frames (Context.array_stats): the weights that minimise the output
+    power while tap (K - 1) / 2 of antenna `ref` is held at 1, with `loading` x the mean diagonal added to the diagonal,
+    scaled so that the output's rms per component is target_rms.  Returns (taps, shift, info): taps int16[A, K] - for
+    lanes 2 int16[A, K, 2], re and im - and info = dict(weights float64[A, K] or complex128[A, K] before the gain, gain,
+    suppression_db: the reference antenna's power over the output's before the gain)."""
+    r = np.ascontiguousarray(rho, dtype=np.int64)
+    la = int(lanes)
+    if r.ndim != 4 or r.shape[0] != r.shape[1] or r.shape[3] != la:
+        raise ValueError("rho has shape %r, expected (A, A, K, %d)" % (r.shape, la))
+    A, K = r.shape[0], r.shape[2]
+    taps = np.zeros((A, K, la), dtype=np.int16)
+    w = np.zeros((A, K, la))
+    shift, gain, supp = C.c_int32(0), C.c_double(0), C.c_double(0)
+    check(lib().sgx_array_design(_ptr(r), int(frames), la, A, K, int(ref), float(loading), float(target_rms), _ptr(taps),
+                                 C.byref(shift), _ptr(w), C.byref(gain), C.byref(supp)))
+    weights = w[:, :, 0] + 1j * w[:, :, 1] if la == 2 else w[:, :, 0].copy()
+    return (taps if la == 2 else taps[:, :, 0].copy()), shift.value, dict(weights=weights, gain=gain.value,
+                                                                         suppression_db=supp.value)
+
+
+def array_stats_tile():
+    """Frames one workgroup of the array statistics kernel sums at a time: its tile seams lie at the multiples."""
+    return _tile("sgx_array_stats_tile")
+
+
+def combine_tile():
+    """Output bytes one workgroup of the combiner makes: its tile seams lie at the multiples."""
+    return _tile("sgx_combine_tile")
+
+
 def _int16_taps(taps):
     a = np.asarray(taps)
     if a.dtype.kind not in "iu" or a.size and (a.min() < -32768 or a.max() > 32767):
@@ -1189,6 +1237,41 @@ class Context(object):
     def resamp_timing(self):
         """Kernel ms of the last resample on this context, from HIP events on its stream."""
         return self._timing("sgx_resamp_timing", 1)[0]
+
+    def array_stats(self, rec, lanes, A, K, offset_binary=False):
+        """The exact lag statistics of `rec`, an int8 record of frames of A antennas (byte (f A + a) lanes + l: component l
+        of antenna a at frame f; lanes 2: interleaved I/Q), as int64[A, A, K, lanes] (sgx_array_stats):
+        rho[a, b, d] = sum_f x_a[f + d] conj(x_b[f]), real part then imaginary part.  K odd, 1 .. 15, A 2 .. 8, A K <= 64.
+        offset_binary: the input bytes are uint8 around 128."""
+        rho = np.zeros((max(int(A), 0), max(int(A), 0), max(int(K), 0), 2 if int(lanes) == 2 else 1), dtype=np.int64)
+        buf = np.zeros(max(rho.size, 1), dtype=np.int64)
+        check(lib().sgx_array_stats(self._h, rec._h, int(lanes), int(A), int(K), ARRAY_OFFSET_BINARY if offset_binary else 0,
+                                    _ptr(buf)))
+        rho[...] = buf[:rho.size].reshape(rho.shape)
+        return rho
+
+    def array_stats_timing(self):
+        """Kernel ms of the last array_stats on this context, from HIP events on its stream."""
+        return self._timing("sgx_array_stats_timing", 1)[0]
+
+    def combine(self, rec, lanes, A, taps, shift, offset_binary=False):
+        """A new int8 record of one frame per frame of `rec` (frames of A antennas, as array_stats reads them): every antenna
+        through its own integer FIR and all of them summed (sgx_if_combine).  taps int16[A, K], for lanes 2 COMPLEX as
+        int16[A, K, 2]; K odd, at most 15; array_design makes the usual ones.  Output frame f is the instant of input frame
+        f.  The exact count of outputs whose value before the clip lay outside [-127, 127] is left in the new record's
+        `clipped`."""
+        a = np.asarray(taps)
+        la, n_a = int(lanes), int(A)
+        h16 = _int16_taps(a)
+        per = n_a * la
+        if per <= 0 or h16.size % per:
+            raise ValueError("the taps of %d antennas (lanes %d) are %d values per tap, %d values are not" % (n_a, la, per, h16.size))
+        return self._stage("sgx_if_combine", (rec._h, la, n_a, _ptr(h16), h16.size // per, int(shift),
+                                              ARRAY_OFFSET_BINARY if offset_binary else 0), counters=("clipped",))
+
+    def combine_timing(self):
+        """Kernel ms of the last combine on this context, from HIP events on its stream."""
+        return self._timing("sgx_combine_timing", 1)[0]
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

@@ -1,0 +1,470 @@
+// Multi-antenna records (include/sgx.h: sgx_array_stats, sgx_if_combine; contract: tests/array_spec.py): the exact lag
+// statistics of the A streams of a resident int8 record, and the A streams through one integer FIR each, summed into one
+// int8 record.  The fourth user of the dot4 FIR core (sgx_fir_dot4.h); the int8 matrix cores are left aside for the reason
+// DESIGN.md section 4.11 gives.
+//
+// Both kernels are templated on (LANES, A) and start the same way: the record's bytes are one stream of P = A LANES planes,
+// plane a LANES + l holding component l of antenna a.  ar_load_planes brings a run of frames from the interleaved bytes
+// into per-plane runs in LDS: a lane loads the P dwords that hold 4 consecutive frames (guarded per dword: bytes outside
+// [0, N) are zero and never read; XOR 0x80 for offset binary), picks the 4 bytes of each plane out of them - three
+// v_perm_b32 with selectors that are constants once P is fixed, as the decimator's transpose - and writes one dword per
+// plane.  Lanes write consecutive dwords of a plane and, afterwards, read consecutive dwords: no bank conflict.
+//
+// array_stats_kernel.  A workgroup takes tiles of AR_TILE frames plus 16 frames behind them (the lags reach K - 1 <= 14
+// frames ahead), tile blockIdx.x, + gridDim.x, ..: frame f of the tile is the x_b[f] of its products, x_a[f + d] comes from
+// the same image, and frames past the record are zero, so every product of the contract is formed once.  The A^2 pairs
+// (a, b) are dealt to the four waves; a lane takes 4 frames per step - one dword of x_b, five of x_a, the K byte-shifted
+// windows of x_a by v_alignbyte_b32 - and one v_dot4_i32_i8 per lag (four per lag for I/Q: II + QQ, QI, IQ).  Per tile a
+// lane adds at most 8 x 2 x 2^16 into an int32 and the wave's sum stays below 2^27; it is folded over the wave by shuffles
+// and added into the workgroup's int64 sums in LDS, each owned by one wave.  At the end the workgroup adds its sums into
+// one of AR_SUM_SLOTS copies of rho in the context's small area, one integer atomic per value.
+//
+// combine_kernel.  A workgroup makes FIR_TILE output bytes, 16 per lane, from plane images of FIR_TILE / LANES + 16 frames
+// that start AR_CQ = 8 frames in front of the tile: fir_steps<W> as it stands, per antenna one image and one tap image
+// G_a[j] = h_a[c + AR_CQ - j] (I/Q: re, im, -im), the partial sums added modulo 2^32 (the contract bounds the true sum
+// inside int32), the decimator's epilogue and its clip counters.
+#include "sgx_fir_dot4.h"
+
+#define AR_TILE 2048                      // frames a workgroup of the statistics kernel sums at a time
+#define AR_HALO 16                        // frames behind a tile that its lags may reach into
+#define AR_MAX_GRID 2048                  // workgroups of the statistics kernel
+#define AR_CQ 8                           // frames in front of a combiner tile: >= (SGX_ARRAY_MAX_TAPS - 1) / 2, a multiple of 4
+#define AR_LQ 16                          // length of a tap image: AR_CQ + c + 1 <= 16
+static_assert(SGX_ARRAY_MAX_TAPS - 1 < AR_HALO && AR_CQ + (SGX_ARRAY_MAX_TAPS - 1) / 2 + 1 <= AR_LQ, "the lags fit the halo");
+static_assert(AR_SUM_VALUES >= SGX_ARRAY_MAX_ANTENNAS * SGX_ARRAY_MAX_WEIGHTS * 2, "a copy of rho holds the largest case");
+static_assert((size_t)SGX_ARRAY_MAX_ANTENNAS * 3 * (AR_LQ / 4) * sizeof(uint2) <= sizeof(SgxSmall::fir_taps),
+              "the tap images of eight antennas fit the tap staging");
+
+// Record bytes [a, a + 4) XOR flip, a a multiple of 4: zero outside [0, n)
+__device__ __forceinline__ unsigned ar_load_dword(const int8_t* __restrict__ x, long long a, unsigned long long n,
+                                                  unsigned flip) {
+    unsigned v = 0u;
+    if (a >= 0 && (unsigned long long)a + 4 <= n) {
+        v = *reinterpret_cast<const unsigned*>(x + a) ^ flip;
+    } else if (a >= 0 && (unsigned long long)a < n) {
+        const int left = (int)(n - (unsigned long long)a);   // 1 .. 3
+        for (int b = 0; b < left; ++b) v |= (((unsigned)(uint8_t)x[a + b]) ^ (flip & 0xFFu)) << (b * 8);
+    }
+    return v;
+}
+
+// Frames [frame0, frame0 + 4 units) of the record into P plane images of `pitch` dwords each; frame0 is a multiple of 4
+// (or negative and one), so every dword it loads is aligned
+template <int P>
+__device__ __forceinline__ void ar_load_planes(const int8_t* __restrict__ x, unsigned long long n, unsigned flip,
+                                               long long frame0, int units, int pitch, unsigned* __restrict__ s_pl) {
+    for (int u = threadIdx.x; u < units; u += FIR_THREADS) {
+        const long long at = (frame0 + 4ll * u) * P;
+        unsigned raw[P];
+#pragma unroll
+        for (int i = 0; i < P; ++i) raw[i] = ar_load_dword(x, at + 4 * i, n, flip);
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const unsigned lo = fir_pick2(raw, p, P + p), hi = fir_pick2(raw, 2 * P + p, 3 * P + p);
+            s_pl[p * pitch + u] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+        }
+    }
+}
+
+__device__ __forceinline__ int ar_wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+template <int LANES, int A>
+__global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* __restrict__ x, unsigned long long n,
+                                                                  unsigned long long tiles, int K, unsigned flip,
+                                                                  unsigned long long* __restrict__ sums) {
+    constexpr int P = LANES * A;
+    constexpr int PITCH = (AR_TILE + AR_HALO) / 4;     // dwords of a plane image
+    constexpr int KM = SGX_ARRAY_MAX_TAPS;
+    __shared__ unsigned s_pl[P * PITCH];
+    __shared__ long long s_sum[A * A * KM * LANES];    // [pair][d][lane component], K of the KM used
+
+    const int n_val = A * A * K * LANES;
+    for (int i = threadIdx.x; i < n_val; i += FIR_THREADS) s_sum[i] = 0;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+
+    for (unsigned long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        __syncthreads();                               // (the image of the tile before is read no more; s_sum is cleared)
+        ar_load_planes<P>(x, n, flip, (long long)(tile * AR_TILE), PITCH, PITCH, s_pl);
+        __syncthreads();
+        for (int pr = wave; pr < A * A; pr += FIR_THREADS / 64) {
+            const int a = pr / A, b = pr % A;
+            if constexpr (LANES == 1) {
+                const unsigned* pa = s_pl + a * PITCH;
+                const unsigned* pb = s_pl + b * PITCH;
+                int acc[KM];
+#pragma unroll
+                for (int d = 0; d < KM; ++d) acc[d] = 0;
+                for (int u = lane; u < AR_TILE / 4; u += 64) {
+                    const int xb = (int)pb[u];
+                    unsigned w[5];
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) w[i] = pa[u + i];
+#pragma unroll
+                    for (int d = 0; d < KM; ++d) {
+                        if (d < K) {
+                            const unsigned xa = (d & 3) ? __builtin_amdgcn_alignbyte(w[(d >> 2) + 1], w[d >> 2], d & 3) : w[d >> 2];
+                            acc[d] = __builtin_amdgcn_sdot4((int)xa, xb, acc[d], false);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < KM; ++d) {
+                    if (d < K) {
+                        const int t = ar_wave_sum(acc[d]);
+                        if (lane == 0) s_sum[pr * K + d] += (long long)t;
+                    }
+                }
+            } else {
+                const unsigned* pai = s_pl + (2 * a) * PITCH;
+                const unsigned* paq = pai + PITCH;
+                const unsigned* pbi = s_pl + (2 * b) * PITCH;
+                const unsigned* pbq = pbi + PITCH;
+                int acc_re[KM], acc_p[KM], acc_m[KM];   // II + QQ;  Q_a I_b;  I_a Q_b
+#pragma unroll
+                for (int d = 0; d < KM; ++d) acc_re[d] = acc_p[d] = acc_m[d] = 0;
+                for (int u = lane; u < AR_TILE / 4; u += 64) {
+                    const int bi = (int)pbi[u], bq = (int)pbq[u];
+                    unsigned wi[5], wq[5];
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) wi[i] = pai[u + i], wq[i] = paq[u + i];
+#pragma unroll
+                    for (int d = 0; d < KM; ++d) {
+                        if (d < K) {
+                            const unsigned ai = (d & 3) ? __builtin_amdgcn_alignbyte(wi[(d >> 2) + 1], wi[d >> 2], d & 3) : wi[d >> 2];
+                            const unsigned aq = (d & 3) ? __builtin_amdgcn_alignbyte(wq[(d >> 2) + 1], wq[d >> 2], d & 3) : wq[d >> 2];
+                            acc_re[d] = __builtin_amdgcn_sdot4((int)ai, bi, acc_re[d], false);
+                            acc_re[d] = __builtin_amdgcn_sdot4((int)aq, bq, acc_re[d], false);
+                            acc_p[d] = __builtin_amdgcn_sdot4((int)aq, bi, acc_p[d], false);
+                            acc_m[d] = __builtin_amdgcn_sdot4((int)ai, bq, acc_m[d], false);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < KM; ++d) {
+                    if (d < K) {
+                        const int t_re = ar_wave_sum(acc_re[d]), t_im = ar_wave_sum(acc_p[d] - acc_m[d]);
+                        if (lane == 0) {
+                            s_sum[(pr * K + d) * 2] += (long long)t_re;
+                            s_sum[(pr * K + d) * 2 + 1] += (long long)t_im;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* mine = sums + (size_t)(blockIdx.x % AR_SUM_SLOTS) * AR_SUM_VALUES;
+    for (int i = threadIdx.x; i < n_val; i += FIR_THREADS) {
+        const long long v = s_sum[i];
+        if (v) atomicAdd(&mine[i], (unsigned long long)v);
+    }
+}
+
+template <int LANES, int A>
+__global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
+                                                              unsigned long long n, unsigned long long n_out,
+                                                              const uint2* __restrict__ taps, int q_lo, int q_hi, int shift,
+                                                              unsigned flip, unsigned long long* __restrict__ counts) {
+    constexpr int W = 16 / LANES;              // bytes of a slot = outputs of a lane per plane image
+    constexpr int P = LANES * A;               // planes
+    constexpr int TF = FIR_TILE / LANES;       // frames of a tile
+    constexpr int NS = (TF + AR_LQ) / W;       // slots of a plane image: frames m0 - AR_CQ .. m0 + TF + AR_LQ - AR_CQ
+    constexpr int IMG = AR_LQ / 4;             // pairs of a tap image
+    typedef typename FirSlot<W>::type slot_t;
+    __shared__ slot_t s_img[P * NS];
+    __shared__ unsigned s_cnt[FIR_THREADS / 64];
+
+    ar_load_planes<P>(x, n, flip, (long long)blockIdx.x * TF - AR_CQ, (TF + AR_LQ) / 4, NS * (W / 4),
+                      reinterpret_cast<unsigned*>(s_img));
+    __syncthreads();
+
+    const long long rnd = shift ? (1ll << (shift - 1)) : 0ll;
+    const unsigned long long o0 = (unsigned long long)blockIdx.x * FIR_TILE + 16ull * threadIdx.x;
+    unsigned out[4] = {0u, 0u, 0u, 0u};
+    unsigned clipped = 0;
+    if constexpr (LANES == 1) {
+        int tot[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tot[r] = 0;
+#pragma unroll 1
+        for (int a = 0; a < A; ++a) {
+            int sum[16];
+            fir_steps<16>(s_img + a * NS, taps + a * IMG, q_lo, q_hi, sum);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tot[r] = (int)((unsigned)tot[r] + (unsigned)sum[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long long v = ((long long)tot[r] + rnd) >> shift;
+            clipped += (o0 + r < n_out && (v < -127 || v > 127)) ? 1u : 0u;
+            out[r >> 2] |= fir_round_clip(tot[r], false, rnd, shift) << ((r & 3) * 8);
+        }
+    } else {
+        int tot_i[8], tot_q[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) tot_i[r] = tot_q[r] = 0;
+#pragma unroll 1
+        for (int a = 0; a < A; ++a) {
+            const slot_t* s_i = s_img + (2 * a) * NS;
+            const slot_t* s_q = s_img + (2 * a + 1) * NS;
+            const uint2* g_re = taps + (3 * a) * IMG;
+            const uint2* g_im = g_re + IMG;
+            const uint2* g_nim = g_im + IMG;
+            int u[8], v[8];
+            fir_steps<8>(s_i, g_re, q_lo, q_hi, u);
+            fir_steps<8>(s_q, g_nim, q_lo, q_hi, v);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) tot_i[r] = (int)((unsigned)tot_i[r] + (unsigned)u[r] + (unsigned)v[r]);
+            fir_steps<8>(s_q, g_re, q_lo, q_hi, u);
+            fir_steps<8>(s_i, g_im, q_lo, q_hi, v);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) tot_q[r] = (int)((unsigned)tot_q[r] + (unsigned)u[r] + (unsigned)v[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const long long vi = ((long long)tot_i[r] + rnd) >> shift, vq = ((long long)tot_q[r] + rnd) >> shift;
+            // (n_out is even: a pair exists whole or not at all)
+            if (o0 + 2 * r < n_out) clipped += ((vi < -127 || vi > 127) ? 1u : 0u) + ((vq < -127 || vq > 127) ? 1u : 0u);
+            const unsigned e = fir_round_clip(tot_i[r], false, rnd, shift), o = fir_round_clip(tot_q[r], false, rnd, shift);
+            out[r >> 1] |= (e | (o << 8)) << ((r & 1) * 16);
+        }
+    }
+    if (o0 + 16 <= n_out) {
+        *reinterpret_cast<uint4*>(y + o0) = make_uint4(out[0], out[1], out[2], out[3]);
+    } else {
+        for (int r = 0; r < 16 && o0 + r < n_out; ++r) y[o0 + r] = (int8_t)((out[r >> 2] >> ((r & 3) * 8)) & 0xFF);
+    }
+
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) clipped += __shfl_down(clipped, d, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = clipped;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (int w = 0; w < FIR_THREADS / 64; ++w) t += s_cnt[w];
+        if (t) atomicAdd(&counts[(size_t)(blockIdx.x % DC_COUNT_SLOTS) * DC_COUNT_STRIDE], (unsigned long long)t);
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+struct ArStats {
+    hipStream_t st;
+    unsigned grid;
+    const int8_t* x;
+    unsigned long long n, tiles;
+    int K;
+    unsigned flip;
+    unsigned long long* sums;
+};
+
+struct ArCombine {
+    hipStream_t st;
+    unsigned grid;
+    const int8_t* x;
+    int8_t* y;
+    unsigned long long n, n_out;
+    const uint2* taps;
+    int q_lo, q_hi, shift;
+    unsigned flip;
+    unsigned long long* counts;
+};
+
+template <int LANES, int A> static void ar_launch(const ArStats& l) {
+    array_stats_kernel<LANES, A><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums);
+}
+template <int LANES, int A> static void ar_launch(const ArCombine& l) {
+    combine_kernel<LANES, A><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift, l.flip,
+                                                              l.counts);
+}
+template <int LANES, typename Launch> static void ar_launch_l(int A, const Launch& l) {
+    switch (A) {
+        case 2: return ar_launch<LANES, 2>(l);
+        case 3: return ar_launch<LANES, 3>(l);
+        case 4: return ar_launch<LANES, 4>(l);
+        case 5: return ar_launch<LANES, 5>(l);
+        case 6: return ar_launch<LANES, 6>(l);
+        case 7: return ar_launch<LANES, 7>(l);
+        default: return ar_launch<LANES, 8>(l);
+    }
+}
+
+// The refusals of the shape that both entry points share; each names its argument
+static int ar_check_shape(int32_t lanes, int32_t A, int32_t K, int32_t flags) {
+    if (lanes != 1 && lanes != 2) {
+        sgx_set_error("bad argument: lanes %d is not 1 (real records) or 2 (interleaved I/Q)", (int)lanes);
+        return SGX_E_ARG;
+    }
+    if (A < 2 || A > SGX_ARRAY_MAX_ANTENNAS) {
+        sgx_set_error("bad argument: A = %d antennas lie outside 2 .. %d", (int)A, SGX_ARRAY_MAX_ANTENNAS);
+        return SGX_E_ARG;
+    }
+    if (K < 1 || K > SGX_ARRAY_MAX_TAPS || (K & 1) == 0) {
+        sgx_set_error("bad argument: K = %d is not an odd number in 1 .. %d", (int)K, SGX_ARRAY_MAX_TAPS);
+        return SGX_E_ARG;
+    }
+    if (A * K > SGX_ARRAY_MAX_WEIGHTS) {
+        sgx_set_error("bad argument: A K = %d weights are more than %d", (int)(A * K), SGX_ARRAY_MAX_WEIGHTS);
+        return SGX_E_ARG;
+    }
+    if (flags & ~SGX_ARRAY_OFFSET_BINARY) {
+        sgx_set_error("bad argument: flags 0x%x holds a bit other than SGX_ARRAY_OFFSET_BINARY", (unsigned)flags);
+        return SGX_E_ARG;
+    }
+    return SGX_OK;
+}
+
+static int ar_check_record(const sgx_if* rec, int32_t lanes, int32_t A) {
+    if (rec->n % (size_t)(A * lanes)) {
+        sgx_set_error("bad argument: a record of %d antennas (lanes %d) holds whole frames of %d bytes, not %zu bytes", (int)A,
+                      (int)lanes, (int)(A * lanes), rec->n);
+        return SGX_E_ARG;
+    }
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_stats_tile(int32_t* tile_frames) {
+    SGX_CHECK_ARG(tile_frames);
+    *tile_frames = AR_TILE;
+    return SGX_OK;
+}
+
+extern "C" int sgx_combine_tile(int32_t* tile_bytes) {
+    SGX_CHECK_ARG(tile_bytes);
+    *tile_bytes = FIR_TILE;
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_stats_timing(sgx_ctx* c, float* kernel_ms) {
+    SGX_CHECK_ARG(c && kernel_ms);
+    *kernel_ms = c->stage_ms[SGX_STAGE_ARRAY_STATS];
+    return SGX_OK;
+}
+
+extern "C" int sgx_combine_timing(sgx_ctx* c, float* kernel_ms) {
+    SGX_CHECK_ARG(c && kernel_ms);
+    *kernel_ms = c->stage_ms[SGX_STAGE_COMBINE];
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_stats(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, int32_t K, int32_t flags,
+                               int64_t* rho) {
+    int rc = ar_check_shape(lanes, A, K, flags);
+    if (rc != SGX_OK) return rc;
+    SGX_CHECK_ARG(c && rec && rho);
+    SGX_CHECK_ARG(rec->device == c->device);
+    rc = ar_check_record(rec, lanes, A);
+    if (rc != SGX_OK) return rc;
+    rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
+
+    const unsigned long long frames = rec->n / (size_t)(A * lanes);
+    ArStats l;
+    l.st = c->stream;
+    l.tiles = (frames + AR_TILE - 1) / AR_TILE;
+    l.grid = (unsigned)(l.tiles < AR_MAX_GRID ? l.tiles : AR_MAX_GRID);
+    l.x = rec->d;
+    l.n = (unsigned long long)rec->n;
+    l.K = K;
+    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
+    l.sums = c->d_small->array_sum;
+    unsigned long long* h_sum = c->h_small->array_sum;
+    SgxStage st(SGX_STAGE_ARRAY_STATS, l.grid, "array statistics kernel failed: %s");
+    st.count_into(h_sum, l.sums, sizeof(SgxSmall::array_sum));
+    rc = sgx_stage_run(c, st, [&](sgx_if*) {
+        if (lanes == 1) {
+            ar_launch_l<1>(A, l);
+        } else {
+            ar_launch_l<2>(A, l);
+        }
+    });
+    if (rc != SGX_OK) return rc;
+    const int n_val = A * A * K * lanes;
+    for (int i = 0; i < n_val; ++i) {
+        unsigned long long t = 0;   // (two's complement: the copies add up modulo 2^64)
+        for (int s = 0; s < AR_SUM_SLOTS; ++s) t += h_sum[(size_t)s * AR_SUM_VALUES + i];
+        rho[i] = (int64_t)t;
+    }
+    return SGX_OK;
+}
+
+extern "C" int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, const int16_t* taps, int32_t K,
+                              int32_t shift, int32_t flags, sgx_if** out, int64_t* clipped) {
+    // the shape and the taps first: these refusals need no device
+    int rc = ar_check_shape(lanes, A, K, flags);
+    if (rc != SGX_OK) return rc;
+    if (shift < 0 || shift > 30) {
+        sgx_set_error("bad argument: shift %d lies outside 0 .. 30", (int)shift);
+        return SGX_E_ARG;
+    }
+    SGX_CHECK_ARG(taps);
+    // (all antennas add into one sum, so the bound is on the sum over all of them; lanes = 2: of |re| + |im|)
+    rc = fir_check_taps(taps, lanes * A * K);
+    if (rc != SGX_OK) return rc;
+    SGX_CHECK_ARG(c && rec && out);
+    SGX_CHECK_ARG(rec->device == c->device);
+    rc = ar_check_record(rec, lanes, A);
+    if (rc != SGX_OK) return rc;
+    const size_t n_out = rec->n / (size_t)A;
+    const unsigned long long tiles = ((unsigned long long)n_out + FIR_TILE - 1) / FIR_TILE;
+    rc = sgx_stage_one_launch(tiles, "bad argument: a record of %zu output bytes is beyond one launch of the combiner", n_out);
+    if (rc != SGX_OK) return rc;
+    rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
+
+    // G_a[j] = the tap at frame offset j - AR_CQ: h_a[cc - (j - AR_CQ)]
+    const int cc = (K - 1) / 2, W = 16 / lanes, img = AR_LQ / 4, per_antenna = lanes == 2 ? 3 : 1;
+    const int pairs = A * per_antenna * img;
+    uint2* g = fir_tap_image(c, pairs);
+    int q_lo = AR_LQ / W, q_hi = 0;
+    for (int a = 0; a < A; ++a) {
+        uint2* ga = g + (size_t)a * per_antenna * img;
+        for (int j = 0; j < AR_LQ; ++j) {
+            const int k = cc - (j - AR_CQ);
+            if (k < 0 || k >= K) continue;
+            bool any;
+            if (lanes == 1) {
+                const int h = taps[a * K + k];
+                any = h != 0;
+                if (any) fir_pack_tap(ga, j, h);
+            } else {
+                const int re = taps[2 * (a * K + k)], im = taps[2 * (a * K + k) + 1];
+                any = re != 0 || im != 0;
+                if (re) fir_pack_tap(ga, j, re);
+                if (im) fir_pack_tap(ga + img, j, im), fir_pack_tap(ga + 2 * img, j, -im);
+            }
+            if (!any) continue;
+            if (j / W < q_lo) q_lo = j / W;
+            if (j / W + 1 > q_hi) q_hi = j / W + 1;
+        }
+    }
+    if (q_hi == 0) q_lo = 0;   // no tap at all: no step
+
+    ArCombine l;
+    l.st = c->stream;
+    l.grid = (unsigned)tiles;
+    l.x = rec->d;
+    l.n = (unsigned long long)rec->n, l.n_out = (unsigned long long)n_out;
+    l.taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
+    l.q_lo = q_lo, l.q_hi = q_hi, l.shift = shift;
+    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
+    l.counts = c->d_small->array_clip;
+    unsigned long long* h_count = c->h_small->array_clip;
+    SgxStage st(SGX_STAGE_COMBINE, l.grid, "combine kernel failed: %s", out, n_out);
+    st.up = {c->d_small->fir_taps, g, (size_t)pairs * sizeof(uint2)};
+    st.count_into(h_count, l.counts, sizeof(SgxSmall::array_clip));
+    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
+        l.y = r->d;
+        if (lanes == 1) {
+            ar_launch_l<1>(A, l);
+        } else {
+            ar_launch_l<2>(A, l);
+        }
+    });
+    if (rc != SGX_OK) return rc;
+    if (clipped) *clipped = sgx_sum_slots(h_count, DC_COUNT_SLOTS, DC_COUNT_STRIDE);
+    return SGX_OK;
+}

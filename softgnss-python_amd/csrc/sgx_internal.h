@@ -120,11 +120,17 @@ struct WfPlan {
 #define DC_COUNT_SLOTS 256
 #define DC_COUNT_STRIDE 16   // 64-bit words between two slots
 
+// sgx_array.hip: the copies of rho the statistics kernel spreads its per-workgroup sums over, each of AR_SUM_VALUES int64
+// values (A^2 K lanes <= 8 x 64 x 2 of them used)
+#define AR_SUM_SLOTS 8
+#define AR_SUM_VALUES 1024
+
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
 // sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
-// sgx_if_resample
+// sgx_if_resample, sgx_array_stats, sgx_if_combine
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
-                    SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_ARRAY_STATS,
+                    SGX_STAGE_COMBINE, SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -338,6 +344,10 @@ struct SgxSmall {
     alignas(256) unsigned long long decim_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
     // sgx_resamp.hip: the resampler's counters of clipped outputs, in the decimator's layout
     alignas(256) unsigned long long resamp_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
+    // sgx_array.hip: the statistics kernel's copies of rho (int64 values, added modulo 2^64), and the combiner's counters
+    // of clipped outputs, in the decimator's layout
+    alignas(256) unsigned long long array_sum[AR_SUM_SLOTS * AR_SUM_VALUES];
+    alignas(256) unsigned long long array_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");

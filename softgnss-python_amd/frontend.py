@@ -1,6 +1,6 @@
 """The record front end of Settings: the stages that stand between a record file and acquisition.
 
-STAGES is the one ordered table: unpack | condition | requantise -> decimate -> convert -> resample (the notch follows them
+STAGES is the one ordered table: unpack -> combine | condition | requantise -> decimate -> convert -> resample (the notch follows them
 and changes no position); what an entry says of its stage is listed at _Stage.  FrontEnd._walk folds the table forwards over
 the file's settings, _file_range walks the same pairs backwards and _prepared_record runs the stages in one loop: the shape
 of the composed contract, tests/chain_cases.py.  main.py builds its command line and its banner from the same table.
@@ -107,6 +107,60 @@ the results are samples of the unpacked record.  Not with --iq-requantize or --c
         rec, info = s.unpackRecord(raw)
         say('   %d samples; levels %s' % (info["samples"], ", ".join(
             "%+d: %.2f %%" % (int(lv), 100.0 * sh) for lv, sh in sorted(zip(info["table"], info["shares"])))))
+        return rec, info
+
+
+# multi-antenna records (Settings.combineAntennas; INTEGRATION.md, "Multi-antenna records"): the streams of several antennas go
+# through a space-time combiner whose power-inversion weights cancel what stands above the noise - a broadband jammer - and
+# come out as one int8 record, directly behind the unpacker
+class _Combine(_Stage):
+    name, flag, last = "combine", "antennas", "lastCombining"
+    reads, makes = "a frame of all antennas", "a frame"
+    defaults = (
+        ("antennas", 0),                     # A: the file interleaves that many streams, 2 .. 8; 0: the stage is off
+        ("arrayTaps", 0),                    # K: taps per antenna (odd, at most 15, A K <= 64); 0: 1 for iqRecord, 5 for a real record
+        ("arrayReference", 0),               # the antenna whose centre tap is held at 1
+        ("arrayLoading", 1e-3),              # diagonal loading, in units of the mean power of the streams
+        ("arrayTargetRms", 12.0),            # rms of the int8 record it makes, LSB, in (0, 127]
+    )
+    options = (("--antennas", dict(default=None, metavar="A[:REF]",
+                    help="the file interleaves the streams of A antennas (2 .. 8), frame by frame: combine them on the GPU "
+                         "into one record with power-inversion weights that null a jammer, antenna REF (default 0) held at 1")),
+               ("--array-taps", dict(type=int, default=None, metavar="K",
+                    help="with --antennas: taps per antenna (odd, 1 .. 15, A x K <= 64; default: 1 with --iq, else 5)")))
+    needs = "--array-taps is the filter length of the antenna combiner: it needs --antennas"
+    replays_file, verb = False, "combines"
+    usage = """--antennas A[:REF] (A = 2 .. 8; int8 or uint8 files, real or with --iq, or the A streams of a --packed file) reads a
+file that interleaves the streams of A antennas frame by frame: the GPU takes the exact cross-correlations of the streams,
+the host designs power-inversion weights from them - least output power with antenna REF (0) held at 1, which nulls a
+broadband jammer and needs no array geometry - and the GPU runs every stream through a --array-taps K tap integer FIR (1 with
+--iq, else 5) and sums them into one int8 record at 12 LSB rms, in front of every other stage.  The suppression of the
+reference antenna's power, the largest weight and the share of clipped samples are printed.  --skip stays a byte of the file,
+on a frame of all antennas; positions in the results are samples of the combined record.  Not with --condition or
+--iq-requantize."""
+
+    def settings_from(self, args, fail):
+        A, ref = _numbers(args.antennas, ":") or (0, None)
+        if not A:                            # (A = 0 is Settings.antennas' word for "the stage is off")
+            fail("--antennas takes A[:REF] with A in 2 .. 8 and REF one of the antennas 0 .. A - 1")
+        if args.array_taps is not None and args.array_taps <= 0:     # (0 is Settings' word for "the default length")
+            fail("--array-taps takes the taps per antenna, odd, 1 .. 15")
+        return dict(antennas=A, arrayReference=ref, arrayTaps=args.array_taps)
+
+    def announce(self, file):
+        return 'Combined %d antennas' % file.antennas
+
+    def step(self, s):
+        lanes, A = s._array_format()[:2]
+        return A * lanes, lanes, _with(s, antennas=0, dataType='int8')
+
+    def run(self, s, raw, say, prepared):
+        lanes, A, K = s._array_format()[:3]
+        say('   Combining %d antennas through %d tap%s each...' % (A, K, "" if K == 1 else "s"))
+        rec, info = s.combineAntennas(raw)
+        say('   %d samples: reference antenna suppressed by %.2f dB, largest |weight| %.3f, gain %+.2f dB, %.4f %% of the '
+            'samples clipped' % (info["samples"], info["suppression_db"], float(np.max(np.abs(info["weights"]))),
+                                 info["gain_db"], 100.0 * info["clipped"]))
         return rec, info
 
 
@@ -332,7 +386,7 @@ positions in the results are samples of the resampled record."""
         return rec, info
 
 
-STAGES = (_Unpack(), _Condition(), _Requantise(), _Decimate(), _Convert(), _Resample())     # the order: written here only
+STAGES = (_Unpack(), _Combine(), _Condition(), _Requantise(), _Decimate(), _Convert(), _Resample())     # the order: written here only
 
 # narrowband interference excision (Settings.mitigate; INTEGRATION.md, "Interference excision"): continuous-wave lines found
 # in the Welch spectrum of probeData are notched out of the prepared record by a zero-phase integer FIR, behind all stages
@@ -550,7 +604,8 @@ class FrontEnd(object):
     def _pack_format(self):
         """(bits, lsb_first, frame, first, take, table) of the unpacker for these settings.  take: a frame of several
         fields (packedFrame > 1) gives its I/Q pair with iqRecord, else one field; with packedFrame = 1 every field is
-        taken (I and Q simply alternate, the converter sorts them out)."""
+        taken (I and Q simply alternate, the converter sorts them out).  With Settings.antennas a frame of several fields
+        gives that many times as many: the streams of all antennas from `first` on, for the combiner behind the unpacker."""
         b = int(self.packedBits)
         if b not in (1, 2, 4):
             raise ValueError("Settings.packedBits = %r: packed records hold 1-, 2- or 4-bit samples (0: not packed)"
@@ -568,6 +623,8 @@ class FrontEnd(object):
         if F not in (1, 2, 4, 8, 16):
             raise ValueError("Settings.packedFrame = %r: a frame holds 1, 2, 4, 8 or 16 fields" % (self.packedFrame,))
         take = 2 if (self.iqRecord and F > 1) else 1
+        if self.antennas and F > 1:          # (the streams of all antennas, for the combiner behind the unpacker)
+            take = self._array_format()[1] * take
         if first < 0 or first + take > F:
             raise ValueError("Settings.packedFirst = %d: %d field%s from there on do not lie inside a frame of %d"
                              % (first, take, "s" if take > 1 else "", F))
@@ -608,6 +665,73 @@ class FrontEnd(object):
         info = dict(samples=len(rec8), bits=b, table=table.copy(), code_counts=counts.copy(),
                     shares=counts / float(len(rec8)) if len(rec8) else np.zeros(counts.size))
         self.lastUnpack = info
+        return rec8, info
+
+    def _array_format(self):
+        """(lanes, A, K, reference, offset_binary) of the antenna combiner for these settings."""
+        if self.frontEndConditioning or self.iqRequantize:
+            raise ValueError("Settings.antennas with Settings.%s: a gain of its own per stream would destroy the coherence "
+                             "of the streams that the combiner's null rests on"
+                             % ("frontEndConditioning" if self.frontEndConditioning else "iqRequantize"))
+        try:
+            A, K, ref = int(self.antennas), int(self.arrayTaps), int(self.arrayReference)
+            ok = A == self.antennas and 2 <= A <= _native.ARRAY_MAX_ANTENNAS
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.antennas = %r: the number of antennas is an integer in 2 .. %d (0: the stage is off)"
+                             % (self.antennas, _native.ARRAY_MAX_ANTENNAS))
+        dt = np.dtype(self.dataType)
+        if dt not in (np.dtype(np.int8), np.dtype(np.uint8)):
+            raise ValueError("a multi-antenna record (Settings.antennas) holds int8 samples, or uint8 for offset binary, not "
+                             "Settings.dataType %r: int16 and float multi-antenna files are out of scope" % (self.dataType,))
+        if K == 0:
+            K = 1 if self.iqRecord else 5
+        if K != (self.arrayTaps or K) or not (1 <= K <= _native.ARRAY_MAX_TAPS and K % 2 == 1):
+            raise ValueError("Settings.arrayTaps = %r: the taps per antenna are odd, 1 .. %d (0: 1 for an I/Q record, else 5)"
+                             % (self.arrayTaps, _native.ARRAY_MAX_TAPS))
+        if A * K > _native.ARRAY_MAX_WEIGHTS:
+            raise ValueError("Settings.antennas x Settings.arrayTaps = %d x %d: more than %d weights"
+                             % (A, K, _native.ARRAY_MAX_WEIGHTS))
+        if ref != self.arrayReference or not (0 <= ref < A):
+            raise ValueError("Settings.arrayReference = %r is none of the antennas 0 .. %d" % (self.arrayReference, A - 1))
+        loading, target = float(self.arrayLoading), float(self.arrayTargetRms)
+        if not (np.isfinite(loading) and loading >= 0):
+            raise ValueError("Settings.arrayLoading = %r: the diagonal loading is finite and not negative" % (self.arrayLoading,))
+        if not (0 < target <= 127.0):
+            raise ValueError("Settings.arrayTargetRms = %r lies outside (0, 127]" % (self.arrayTargetRms,))
+        return 2 if self.iqRecord else 1, A, K, ref, dt == np.dtype(np.uint8)
+
+    def combineAntennas(self, record):
+        """A resident int8 record that interleaves the streams of Settings.antennas antennas frame by frame (a
+        _native.Record; with iqRecord every stream is interleaved I/Q, uint8 is read as offset binary) as a NEW int8
+        record of one stream: the exact lag statistics of the streams (Context.array_stats), the power-inversion weights
+        of arrayTaps taps per antenna with antenna arrayReference held at 1 (_native.array_design; arrayLoading,
+        arrayTargetRms), every stream through its taps and all of them summed (Context.combine).  Output frame f is the
+        instant of input frame f.  Returns (record8, info) and keeps info as self.lastCombining: samples, antennas, taps
+        (per antenna), reference, weights (antennas x taps, complex for I/Q, before the gain), gain_db, suppression_db (the
+        reference antenna's power over the output's), input_rms (per antenna and component, LSB) and clipped (share of the
+        samples that left the int8 range).  The caller frees both."""
+        if not self.antennas:
+            raise ValueError("Settings.antennas is 0: the stage is off")
+        lanes, A, K, ref, offset_binary = self._array_format()
+        if len(record) % (A * lanes):
+            raise ValueError("a record of %d antennas holds whole frames of %d bytes, not %d bytes" % (A, A * lanes, len(record)))
+        ctx = record.ctx
+        frames = len(record) // (A * lanes)
+        rho = ctx.array_stats(record, lanes, A, K, offset_binary=offset_binary)
+        try:
+            taps, shift, out = _native.array_design(rho, frames, lanes, ref, self.arrayLoading, self.arrayTargetRms)
+        except _native.SgxError as e:
+            raise ValueError("Settings.antennas = %d, arrayTaps = %d, arrayReference = %d, arrayLoading = %r, arrayTargetRms = %r "
+                             "on a record of %d frames: %s" % (A, K, ref, self.arrayLoading, self.arrayTargetRms, frames, e))
+        rec8 = ctx.combine(record, lanes, A, taps, shift, offset_binary=offset_binary)
+        power = np.array([float(rho[a, a, 0, 0]) for a in range(A)])
+        info = dict(samples=len(rec8), antennas=A, taps=K, reference=ref, weights=out["weights"],
+                    gain_db=20.0 * float(np.log10(out["gain"])), suppression_db=out["suppression_db"],
+                    input_rms=np.sqrt(power / (float(frames) * lanes)),
+                    clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0)
+        self.lastCombining = info
         return rec8, info
 
     def _cond_format(self):

@@ -1,0 +1,79 @@
+"""Times of the two kernels of the multi-antenna combiner (csrc/sgx_array.hip: sgx_array_stats, sgx_if_combine) on one GPU
+beside a copy of the same bytes:
+
+    python tools/array_probe.py [--ms 37000] [--antennas 4] [--calls 10]
+
+The input is the default scene's bytes, --antennas times the record of --ms code periods (37 000: the OUTPUT is the 1.4 GB
+record of the benchmark; less where the memory does not hold it), read as that many interleaved real streams with K = 5 taps
+each and as interleaved I/Q streams with K = 1.  One warm-up call, then --calls timed calls; HIP events on the context's
+stream around the kernel.  Prints one JSON line with the read and copy rates sgx_stream_rates measures in the same job, then
+one line per (kernel, lanes, K): min and median in ms, the time of the bytes it reads and writes at the copy rate (the
+statistics kernel only reads: at the read rate), the dot4 instructions per input byte, and the share of the memory bound it
+reaches."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ms", type=int, default=37000)
+    ap.add_argument("--antennas", type=int, default=4)
+    ap.add_argument("--calls", type=int, default=10)
+    a = ap.parse_args()
+    m = importlib.import_module("softgnss-python_amd")
+    n = m._native
+    s = m.Settings()
+    ctx = m.engine.get_context(s, 0)
+    A = a.antennas
+    n_out = m.synth.record_length(s.samplesPerCode, a.ms)
+    n_out -= n_out % 64
+    rec = None
+    while rec is None:
+        try:
+            rec = ctx.synth(m.synth.Scene.default(), n_out * A)
+        except n.SgxError:                                 # as large as the memory allows
+            n_out = n_out // 2 // 64 * 64
+            if n_out < 1 << 20:
+                raise
+    n_in = n_out * A
+    read_gbs, copy_gbs = ctx.stream_rates()
+    print(json.dumps(dict(antennas=A, in_bytes=n_in, out_bytes=n_out, read_GBps=round(read_gbs, 1),
+                          copy_GBps=round(copy_gbs, 1))), flush=True)
+    for lanes, K in ((1, 5), (2, 1)):
+        frames = n_in // (A * lanes)
+        ms = []
+        for i in range(a.calls + 1):
+            rho = ctx.array_stats(rec, lanes, A, K)
+            if i:
+                ms.append(ctx.array_stats_timing())
+        read_ms = n_in / read_gbs / 1e6
+        print(json.dumps(dict(kernel="array_stats_kernel", lanes=lanes, antennas=A, taps=K, calls=a.calls,
+                              kernel_ms_min=round(min(ms), 3), kernel_ms_median=round(float(np.median(ms)), 3),
+                              read_ms=round(read_ms, 3), dot4_per_byte=round(A * K * lanes / 4.0, 2),
+                              share_of_bound=round(read_ms / min(ms), 3))), flush=True)
+        taps, shift, info = n.array_design(rho, frames, lanes)
+        ms = []
+        for i in range(a.calls + 1):
+            out = ctx.combine(rec, lanes, A, taps, shift)
+            clipped = out.clipped / float(len(out))
+            out.free()
+            if i:
+                ms.append(ctx.combine_timing())
+        copy_ms = (n_in + n_out) / copy_gbs / 1e6            # (bytes read + written, as tools/decim_probe.py counts them)
+        print(json.dumps(dict(kernel="combine_kernel", lanes=lanes, antennas=A, taps=K, calls=a.calls,
+                              kernel_ms_min=round(min(ms), 3), kernel_ms_median=round(float(np.median(ms)), 3),
+                              copy_ms=round(copy_ms, 3), suppression_db=round(info["suppression_db"], 2),
+                              clipped=clipped, share_of_bound=round(copy_ms / min(ms), 3))), flush=True)
+    rec.free()
+
+
+if __name__ == "__main__":
+    main()
