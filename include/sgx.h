@@ -889,6 +889,51 @@ int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, cons
 int sgx_combine_timing(sgx_ctx* c, float* kernel_ms);
 int sgx_combine_tile(int32_t* tile_bytes);
 
+/* ---- weights that change along the record: the same three steps block by block (opt-in; tests/array_block_spec.py) -------
+ * The record layout, lanes, A, K, flags, c = (K - 1) / 2 and q() are those above.  A block is B frames, B a positive multiple
+ * of SGX_ARRAY_BLOCK_UNIT = 4096: the combiner's tile of a real record, two of its tiles for I/Q and two tiles of the
+ * statistics kernel, so that no workgroup of either kernel straddles a seam.  n_blocks = ceil(F / B), the last block may be
+ * short; n_blocks <= SGX_ARRAY_MAX_BLOCKS = 2^20 (the statistics launch one workgroup or more per block, the table of
+ * statistics holds A A K lanes int64 per block and the tap table up to 768 bytes per block; 2^20 blocks of 4096 frames are
+ * 17 minutes at 4.092 Msps).
+ *
+ * sgx_array_block_stats: int64 rho_blocks[n_blocks][A][A][K][lanes].  Block j holds the terms of the sums above whose x_b
+ * frame f lies in [j B, min((j + 1) B, F)); the x_a[f + d] factor may lie in the next block, frames beyond F are zero.  Exact
+ * integers that do not depend on the order, two calls are bit-identical, and sum_j rho_blocks[j] is what sgx_array_stats
+ * gives.  F = 0 launches nothing and writes nothing.  SGX_E_ARG as sgx_array_stats, and for a B that is no positive multiple
+ * of the unit, more than SGX_ARRAY_MAX_BLOCKS blocks, a NULL pointer.
+ *
+ * sgx_array_design_blocks: exact host code, needs no GPU.  W odd, 1 .. SGX_ARRAY_MAX_WINDOW, h = (W - 1) / 2.  Block j is
+ * designed from the window lo = max(0, j - h) .. hi = min(n_blocks, j + h + 1): rho = the exact int64 sum of the window's
+ * blocks, frames = min(hi B, F) - lo B, then steps 1 to 9 of sgx_array_design on that pair - the same code.  Per block:
+ * taps int16 [n_blocks][A][K][lanes], gain, suppression_db, weights (doubles, [n_blocks][A][K][lanes]) and status; the last
+ * four may be NULL.  A window whose matrix the design refuses as not positive definite (an all-zero stretch) does not fail
+ * the call: the block takes taps, weights, gain and suppression of the nearest designed block before it, a leading block
+ * those of the first designed block, and status[j] = 1 (else 0).  If no block can be designed: SGX_E_ARG with
+ * sgx_array_design's text.  A tap beyond 32 512 or 128 sum(|re| + |im|) >= 2^31 in any block: SGX_E_ARG, the text names the
+ * block.  Otherwise the refusals of sgx_array_design, and: B no positive multiple of the unit, W not odd or outside its
+ * range, F < 1, n_blocks not ceil(F / B) or beyond the limit.
+ *
+ * sgx_if_combine_blocks: taps int16 [n_blocks][A][K][lanes].  OUTPUT frame f is made with tap set j = f / B and is otherwise
+ * exactly sgx_if_combine's formula: the inputs f + c - k of a frame next to a seam come from the neighbouring block, the
+ * taps are block j's.  The same kind and length of record, *clipped the exact count; a record that is still streaming in,
+ * N = 0 (n_blocks = 0 then), another device and a record beyond one launch as sgx_if_combine.  The bounds on the taps are
+ * checked for every block before anything is launched; the text names the block.  SGX_E_ARG also for a B off the unit and
+ * an n_blocks that is not ceil(F / B) or beyond the limit.
+ * sgx_array_block_stats_timing, sgx_combine_blocks_timing: HIP-event time of the last call's kernel on this context. */
+#define SGX_ARRAY_BLOCK_UNIT 4096
+#define SGX_ARRAY_MAX_BLOCKS (1 << 20)
+#define SGX_ARRAY_MAX_WINDOW 63
+int sgx_array_block_stats(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, int32_t K, int32_t flags, int64_t B,
+                          int64_t* rho_blocks);
+int sgx_array_block_stats_timing(sgx_ctx* c, float* kernel_ms);
+int sgx_array_design_blocks(const int64_t* rho_blocks, int64_t n_blocks, int64_t F, int64_t B, int32_t W, int32_t lanes,
+                            int32_t A, int32_t K, int32_t ref, double loading, double target_rms, int16_t* taps,
+                            int32_t* shift, double* weights, double* gain, double* suppression_db, uint8_t* status);
+int sgx_if_combine_blocks(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, const int16_t* taps, int64_t n_blocks,
+                          int64_t B, int32_t K, int32_t shift, int32_t flags, sgx_if** out, int64_t* clipped);
+int sgx_combine_blocks_timing(sgx_ctx* c, float* kernel_ms);
+
 /* The bit integration at the head of postNavigate (postNavigation.py:125-138): I_P[start-20 : start+30000] of one
  * channel summed in 20-ms columns (numpy's summation order), bit = sum > 0.  bits must hold 1501 entries;
  * *n_bits = 1501 for a full slice, fewer where Python's slice is clipped; SGX_E_RANGE ("ValueError") when the

@@ -217,6 +217,13 @@ _PROTOS = {
                                  C.POINTER(C.c_int64)]),
     "sgx_combine_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_combine_tile": (C.c_int, [C.POINTER(C.c_int32)]),
+    "sgx_array_block_stats": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P]),
+    "sgx_array_block_stats_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_array_design_blocks": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_double, C.c_double, _P, C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "sgx_if_combine_blocks": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "sgx_combine_blocks_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_check_t": (C.c_int, [C.c_double, _P]),
     "sgx_e_r_corr": (C.c_int, [C.c_double, _P, _P]),
     "sgx_togeod": (C.c_int, [C.c_double] * 5 + [_P, _P, _P]),
@@ -736,6 +743,9 @@ ARRAY_MAX_TAPS = 15
 ARRAY_MAX_WEIGHTS = 64
 ARRAY_SHIFT = 12
 ARRAY_OFFSET_BINARY = 1
+ARRAY_BLOCK_UNIT = 4096
+ARRAY_MAX_BLOCKS = 1 << 20
+ARRAY_MAX_WINDOW = 63
 
 
 def array_design(rho, frames, lanes, ref=0, loading=1e-3, target_rms=12.0):
@@ -758,6 +768,37 @@ def array_design(rho, frames, lanes, ref=0, loading=1e-3, target_rms=12.0):
     weights = w[:, :, 0] + 1j * w[:, :, 1] if la == 2 else w[:, :, 0].copy()
     return (taps if la == 2 else taps[:, :, 0].copy()), shift.value, dict(weights=weights, gain=gain.value,
                                                                          suppression_db=supp.value)
+
+
+def array_blocks(frames, block_frames):
+    """The blocks of block_frames frames that `frames` frames make: the last one may be short."""
+    return -(-int(frames) // int(block_frames)) if int(block_frames) > 0 else 0
+
+
+def array_design_blocks(rho_blocks, frames, block_frames, window, lanes, ref=0, loading=1e-3, target_rms=12.0):
+    """The power-inversion weights of every block of a record of `frames` frames (sgx_array_design_blocks; exact host code,
+    needs no GPU) from its block statistics rho_blocks, int64[blocks, A, A, K, lanes] (Context.array_block_stats): block j
+    is designed as array_design designs a record, from the summed statistics of the `window` blocks around it (odd,
+    1 .. 63; fewer at the ends of the record).  A block whose window the design refuses as not positive definite - an
+    all-zero stretch - holds the taps of the nearest designed block before it (a leading one: behind it).  Returns (taps,
+    shift, info): taps int16[blocks, A, K] - for lanes 2 int16[blocks, A, K, 2] - and info = dict(weights float64 or
+    complex128 [blocks, A, K] before the gain, gain and suppression_db float64[blocks], status uint8[blocks]: 1 for a
+    block that holds another's taps)."""
+    r = np.ascontiguousarray(rho_blocks, dtype=np.int64)
+    la = int(lanes)
+    if r.ndim != 5 or r.shape[1] != r.shape[2] or r.shape[4] != la:
+        raise ValueError("rho_blocks has shape %r, expected (blocks, A, A, K, %d)" % (r.shape, la))
+    nb, A, K = r.shape[0], r.shape[1], r.shape[3]
+    taps = np.zeros((nb, A, K, la), dtype=np.int16)
+    w = np.zeros((nb, A, K, la))
+    gain, supp, status = np.zeros(nb), np.zeros(nb), np.zeros(nb, dtype=np.uint8)
+    shift = C.c_int32(0)
+    check(lib().sgx_array_design_blocks(_ptr(r), nb, int(frames), int(block_frames), int(window), la, A, K, int(ref),
+                                        float(loading), float(target_rms), _ptr(taps), C.byref(shift), _ptr(w), _ptr(gain),
+                                        _ptr(supp), _ptr(status)))
+    weights = w[..., 0] + 1j * w[..., 1] if la == 2 else w[..., 0].copy()
+    return (taps if la == 2 else taps[..., 0].copy()), shift.value, dict(weights=weights, gain=gain, suppression_db=supp,
+                                                                        status=status)
 
 
 def array_stats_tile():
@@ -1272,6 +1313,44 @@ class Context(object):
     def combine_timing(self):
         """Kernel ms of the last combine on this context, from HIP events on its stream."""
         return self._timing("sgx_combine_timing", 1)[0]
+
+    def array_block_stats(self, rec, lanes, A, K, block_frames, offset_binary=False):
+        """The exact lag statistics of `rec` as array_stats takes them, block by block (sgx_array_block_stats):
+        int64[blocks, A, A, K, lanes], block j holding the terms whose x_b frame lies in [j block_frames, (j + 1)
+        block_frames) - the x_a frame may lie in the next block.  block_frames is a multiple of ARRAY_BLOCK_UNIT; the sum
+        over the blocks is array_stats' result."""
+        la, n_a, k = (2 if int(lanes) == 2 else 1), max(int(A), 0), max(int(K), 0)
+        frames = len(rec) // (n_a * la) if n_a else 0
+        rho = np.zeros((array_blocks(frames, block_frames), n_a, n_a, k, la), dtype=np.int64)
+        buf = rho.reshape(-1) if rho.size else np.zeros(1, dtype=np.int64)
+        check(lib().sgx_array_block_stats(self._h, rec._h, int(lanes), int(A), int(K),
+                                          ARRAY_OFFSET_BINARY if offset_binary else 0, int(block_frames), _ptr(buf)))
+        return rho
+
+    def array_block_stats_timing(self):
+        """Kernel ms of the last array_block_stats on this context, from HIP events on its stream."""
+        return self._timing("sgx_array_block_stats_timing", 1)[0]
+
+    def combine_blocks(self, rec, lanes, A, taps, block_frames, shift, offset_binary=False):
+        """combine() with a set of taps per block of block_frames frames (sgx_if_combine_blocks): OUTPUT frame f is made with
+        set f // block_frames, from input frames that may lie in the neighbouring block.  taps int16[blocks, A, K], for
+        lanes 2 int16[blocks, A, K, 2]; array_design_blocks makes the usual ones.  The exact count of outputs whose value
+        before the clip lay outside [-127, 127] is left in the new record's `clipped`."""
+        a = np.asarray(taps)
+        la, n_a = int(lanes), int(A)
+        if a.ndim != (4 if la == 2 else 3) or a.shape[1] != n_a or (la == 2 and a.shape[3] != 2):
+            raise ValueError("the taps of the blocks have shape %r, expected (blocks, %d, K%s)"
+                             % (a.shape, n_a, ", 2" if la == 2 else ""))
+        h16 = _int16_taps(a)
+        if not h16.size:
+            h16 = np.zeros(1, dtype=np.int16)
+        return self._stage("sgx_if_combine_blocks", (rec._h, la, n_a, _ptr(h16), a.shape[0], int(block_frames), a.shape[2],
+                                                     int(shift), ARRAY_OFFSET_BINARY if offset_binary else 0),
+                           counters=("clipped",))
+
+    def combine_blocks_timing(self):
+        """Kernel ms of the last combine_blocks on this context, from HIP events on its stream."""
+        return self._timing("sgx_combine_blocks_timing", 1)[0]
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).

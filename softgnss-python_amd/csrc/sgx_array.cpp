@@ -1,16 +1,18 @@
 // Host side of the multi-antenna combiner: the power-inversion weights from the record's lag statistics (include/sgx.h:
-// sgx_array_design).  No device.  The operations run in the order the header and tests/array_spec.py state them
-// (-ffp-contract=off), so taps, gain, suppression and weights are the contract's to the bit.
+// sgx_array_design, and sgx_array_design_blocks, which runs the same steps on the statistics of a window of blocks).  No
+// device.  The operations run in the order the header and tests/array_spec.py state them (-ffp-contract=off), so taps, gain,
+// suppression and weights are the contract's to the bit.
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
 #include "sgx_check.h"
 
-extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lanes, int32_t A, int32_t K, int32_t ref,
-                                double loading, double target_rms, int16_t* taps, int32_t* shift, double* weights,
-                                double* gain, double* suppression_db) {
+// The refusals of the arguments that both entry points share, in sgx_array_design's order
+static int ar_design_args(int32_t lanes, int32_t A, int32_t K, int32_t ref, double loading, double target_rms) {
     if (lanes != 1 && lanes != 2) {
         sgx_set_error("array design: lanes %d is not 1 (real records) or 2 (interleaved I/Q)", (int)lanes);
         return SGX_E_ARG;
@@ -39,12 +41,16 @@ extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lane
         sgx_set_error("array design: target_rms = %g lies outside (0, 127]", target_rms);
         return SGX_E_ARG;
     }
-    if (frames < 1) {
-        sgx_set_error("array design: frames = %lld: the statistics of no frame at all", (long long)frames);
-        return SGX_E_ARG;
-    }
-    SGX_CHECK_ARG(rho && taps && shift);
+    return SGX_OK;
+}
 
+// Steps 1 to 9 on one pair (rho, frames) whose arguments have passed.  where: the head of a refusal of the TAPS it makes,
+// "array design" or that with the block's number.  *matrix_refused (never null): the matrix is what was refused - not
+// positive definite -, which sgx_array_design_blocks answers by holding a neighbour's taps; nothing has been written then.
+static int ar_design_solve(const char* where, const int64_t* rho, int64_t frames, int32_t lanes, int32_t A, int32_t K,
+                           int32_t ref, double loading, double target_rms, int16_t* taps, double* weights, double* gain,
+                           double* suppression_db, bool* matrix_refused) {
+    *matrix_refused = true;
     const int n = A * K, c = (K - 1) / 2, m = lanes * n, at = ref * K + c;
     // 1. R = P + j Q
     std::vector<double> P((size_t)n * n), Q((size_t)n * n, 0.0);
@@ -130,6 +136,7 @@ extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lane
         sgx_set_error("array design: the covariance matrix is not positive definite (output power %g)", p_out);
         return SGX_E_ARG;
     }
+    *matrix_refused = false;
     // 6. .. 9.
     const double gn = target_rms / sqrt(p_out / (double)lanes);
     const double scale = (double)(1 << SGX_ARRAY_SHIFT) * gn;
@@ -139,8 +146,8 @@ extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lane
             const double h = l == 0 ? gr[i] : -gi[i];
             const double r = nearbyint(scale * h);   // round half to even (the default rounding mode)
             if (!(fabs(r) <= 32512.0)) {
-                sgx_set_error("array design: tap %d of antenna %d = %.1f leaves the +-32512 the combiner takes (the gain %g is "
-                              "too large: a lower target_rms, or more loading)", i % K, i / K, r, gn);
+                sgx_set_error("%s: tap %d of antenna %d = %.1f leaves the +-32512 the combiner takes (the gain %g is "
+                              "too large: a lower target_rms, or more loading)", where, i % K, i / K, r, gn);
                 return SGX_E_ARG;
             }
             taps[i * lanes + l] = (int16_t)r;
@@ -148,11 +155,93 @@ extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lane
             if (weights) weights[i * lanes + l] = h;
         }
     if (128 * sum_abs >= (1ll << 31)) {
-        sgx_set_error("array design: 128 sum(|re| + |im|) = %lld does not fit the combiner's int32 accumulator", 128 * sum_abs);
+        sgx_set_error("%s: 128 sum(|re| + |im|) = %lld does not fit the combiner's int32 accumulator", where, 128 * sum_abs);
         return SGX_E_ARG;
     }
-    *shift = SGX_ARRAY_SHIFT;
     if (gain) *gain = gn;
     if (suppression_db) *suppression_db = 10.0 * log10(P[(size_t)at * n + at] / p_out);
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_design(const int64_t* rho, int64_t frames, int32_t lanes, int32_t A, int32_t K, int32_t ref,
+                                double loading, double target_rms, int16_t* taps, int32_t* shift, double* weights,
+                                double* gain, double* suppression_db) {
+    const int rc = ar_design_args(lanes, A, K, ref, loading, target_rms);
+    if (rc != SGX_OK) return rc;
+    if (frames < 1) {
+        sgx_set_error("array design: frames = %lld: the statistics of no frame at all", (long long)frames);
+        return SGX_E_ARG;
+    }
+    SGX_CHECK_ARG(rho && taps && shift);
+    bool matrix_refused;
+    const int rs = ar_design_solve("array design", rho, frames, lanes, A, K, ref, loading, target_rms, taps, weights, gain,
+                                   suppression_db, &matrix_refused);
+    if (rs != SGX_OK) return rs;
+    *shift = SGX_ARRAY_SHIFT;
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_design_blocks(const int64_t* rho_blocks, int64_t n_blocks, int64_t F, int64_t B, int32_t W,
+                                       int32_t lanes, int32_t A, int32_t K, int32_t ref, double loading, double target_rms,
+                                       int16_t* taps, int32_t* shift, double* weights, double* gain, double* suppression_db,
+                                       uint8_t* status) {
+    const int rc = ar_design_args(lanes, A, K, ref, loading, target_rms);
+    if (rc != SGX_OK) return rc;
+    if (B < 1 || B % SGX_ARRAY_BLOCK_UNIT) {
+        sgx_set_error("array design: B = %lld frames is no positive multiple of %d", (long long)B, SGX_ARRAY_BLOCK_UNIT);
+        return SGX_E_ARG;
+    }
+    if (W < 1 || W > SGX_ARRAY_MAX_WINDOW || (W & 1) == 0) {
+        sgx_set_error("array design: W = %d is not an odd number of blocks in 1 .. %d", (int)W, SGX_ARRAY_MAX_WINDOW);
+        return SGX_E_ARG;
+    }
+    if (F < 1) {
+        sgx_set_error("array design: F = %lld frames: the statistics of no frame at all", (long long)F);
+        return SGX_E_ARG;
+    }
+    if (n_blocks < 1 || n_blocks > SGX_ARRAY_MAX_BLOCKS || n_blocks != (F + B - 1) / B) {
+        sgx_set_error("array design: n_blocks = %lld is not the ceil(F / B) = %lld blocks of F = %lld frames, or more than %d",
+                      (long long)n_blocks, (long long)((F + B - 1) / B), (long long)F, SGX_ARRAY_MAX_BLOCKS);
+        return SGX_E_ARG;
+    }
+    SGX_CHECK_ARG(rho_blocks && taps && shift);
+
+    const size_t n_val = (size_t)A * A * K * lanes, n_tap = (size_t)A * K * lanes;
+    const int64_t h = (W - 1) / 2;
+    std::vector<int64_t> rho(n_val);
+    std::vector<uint8_t> held((size_t)n_blocks);
+    int64_t first = -1;      // the first block that was designed
+    char where[64];
+    for (int64_t j = 0; j < n_blocks; ++j) {
+        const int64_t lo = j - h > 0 ? j - h : 0, hi = j + h + 1 < n_blocks ? j + h + 1 : n_blocks;
+        memcpy(rho.data(), rho_blocks + (size_t)lo * n_val, n_val * sizeof(int64_t));
+        for (int64_t w = lo + 1; w < hi; ++w) {
+            const int64_t* r = rho_blocks + (size_t)w * n_val;
+            for (size_t i = 0; i < n_val; ++i) rho[i] += r[i];
+        }
+        const int64_t frames = (hi * B < F ? hi * B : F) - lo * B;
+        snprintf(where, sizeof where, "array design, block %lld", (long long)j);
+        bool matrix_refused;
+        const int rs = ar_design_solve(where, rho.data(), frames, lanes, A, K, ref, loading, target_rms, taps + (size_t)j * n_tap,
+                                       weights ? weights + (size_t)j * n_tap : nullptr, gain ? gain + j : nullptr,
+                                       suppression_db ? suppression_db + j : nullptr, &matrix_refused);
+        if (rs != SGX_OK && !matrix_refused) return rs;
+        held[(size_t)j] = rs != SGX_OK;
+        if (rs == SGX_OK && first < 0) first = j;
+    }
+    if (first < 0) return SGX_E_ARG;   // (no block has a matrix the design takes: the last one's refusal is the text)
+    // a held block takes what the nearest designed block before it got, the leading ones what the first designed block got
+    for (int64_t j = 0, from = first; j < n_blocks; ++j) {
+        if (!held[(size_t)j]) {
+            from = j;
+            continue;
+        }
+        memcpy(taps + (size_t)j * n_tap, taps + (size_t)from * n_tap, n_tap * sizeof(int16_t));
+        if (weights) memcpy(weights + (size_t)j * n_tap, weights + (size_t)from * n_tap, n_tap * sizeof(double));
+        if (gain) gain[j] = gain[from];
+        if (suppression_db) suppression_db[j] = suppression_db[from];
+    }
+    if (status) memcpy(status, held.data(), (size_t)n_blocks);
+    *shift = SGX_ARRAY_SHIFT;
     return SGX_OK;
 }

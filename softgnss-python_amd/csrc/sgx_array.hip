@@ -23,6 +23,12 @@
 // that start AR_CQ = 8 frames in front of the tile: fir_steps<W> as it stands, per antenna one image and one tap image
 // G_a[j] = h_a[c + AR_CQ - j] (I/Q: re, im, -im), the partial sums added modulo 2^32 (the contract bounds the true sum
 // inside int32), the decimator's epilogue and its clip counters.
+//
+// Weights per block (sgx_array_block_stats, sgx_if_combine_blocks; contract: tests/array_block_spec.py): the same two kernels
+// with BLOCKS set.  A block is a whole number of tiles of either kernel (SGX_ARRAY_BLOCK_UNIT), so no workgroup straddles a
+// seam: the statistics kernel walks the tiles of ONE block and adds into that block's slot of a table (sgx_ctx::
+// d_array_blocks) - what reaches across a seam is the halo behind a tile -, the combiner reads the tap images of the block
+// its tile lies in from a table of them (sgx_ctx::d_array_taps).  BLOCKS = false is what it was before the flag.
 #include "sgx_fir_dot4.h"
 
 #define AR_TILE 2048                      // frames a workgroup of the statistics kernel sums at a time
@@ -31,6 +37,7 @@
 #define AR_CQ 8                           // frames in front of a combiner tile: >= (SGX_ARRAY_MAX_TAPS - 1) / 2, a multiple of 4
 #define AR_LQ 16                          // length of a tap image: AR_CQ + c + 1 <= 16
 static_assert(SGX_ARRAY_MAX_TAPS - 1 < AR_HALO && AR_CQ + (SGX_ARRAY_MAX_TAPS - 1) / 2 + 1 <= AR_LQ, "the lags fit the halo");
+static_assert(SGX_ARRAY_BLOCK_UNIT % AR_TILE == 0 && SGX_ARRAY_BLOCK_UNIT % FIR_TILE == 0, "a block is whole tiles of both kernels");
 static_assert(AR_SUM_VALUES >= SGX_ARRAY_MAX_ANTENNAS * SGX_ARRAY_MAX_WEIGHTS * 2, "a copy of rho holds the largest case");
 static_assert((size_t)SGX_ARRAY_MAX_ANTENNAS * 3 * (AR_LQ / 4) * sizeof(uint2) <= sizeof(SgxSmall::fir_taps),
               "the tap images of eight antennas fit the tap staging");
@@ -72,10 +79,13 @@ __device__ __forceinline__ int ar_wave_sum(int v) {
     return v;
 }
 
-template <int LANES, int A>
+// BLOCKS: workgroup blockIdx.x takes part blockIdx.x % parts of block blockIdx.x / parts - tiles part, part + parts, .. of the
+// block's tpb tiles, as far as the record has them - and adds into the block's own slot of the table `sums`
+template <int LANES, int A, bool BLOCKS>
 __global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* __restrict__ x, unsigned long long n,
                                                                   unsigned long long tiles, int K, unsigned flip,
-                                                                  unsigned long long* __restrict__ sums) {
+                                                                  unsigned long long* __restrict__ sums, unsigned tpb,
+                                                                  unsigned parts) {
     constexpr int P = LANES * A;
     constexpr int PITCH = (AR_TILE + AR_HALO) / 4;     // dwords of a plane image
     constexpr int KM = SGX_ARRAY_MAX_TAPS;
@@ -86,7 +96,13 @@ __global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* 
     for (int i = threadIdx.x; i < n_val; i += FIR_THREADS) s_sum[i] = 0;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 
-    for (unsigned long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    unsigned long long tile = blockIdx.x, tile_end = tiles, step = gridDim.x;
+    if constexpr (BLOCKS) {
+        const unsigned long long first = (unsigned long long)(blockIdx.x / parts) * tpb;
+        tile = first + blockIdx.x % parts, step = parts;
+        if (first + tpb < tiles) tile_end = first + tpb;
+    }
+    for (; tile < tile_end; tile += step) {
         __syncthreads();                               // (the image of the tile before is read no more; s_sum is cleared)
         ar_load_planes<P>(x, n, flip, (long long)(tile * AR_TILE), PITCH, PITCH, s_pl);
         __syncthreads();
@@ -157,18 +173,21 @@ __global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* 
         }
     }
     __syncthreads();
-    unsigned long long* mine = sums + (size_t)(blockIdx.x % AR_SUM_SLOTS) * AR_SUM_VALUES;
+    unsigned long long* mine = BLOCKS ? sums + (size_t)(blockIdx.x / parts) * n_val
+                                      : sums + (size_t)(blockIdx.x % AR_SUM_SLOTS) * AR_SUM_VALUES;
     for (int i = threadIdx.x; i < n_val; i += FIR_THREADS) {
         const long long v = s_sum[i];
         if (v) atomicAdd(&mine[i], (unsigned long long)v);
     }
 }
 
-template <int LANES, int A>
+// BLOCKS: `taps` is a table of tap images, one set per block of tpb tiles; a workgroup reads the set of its own block
+template <int LANES, int A, bool BLOCKS>
 __global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
                                                               unsigned long long n, unsigned long long n_out,
                                                               const uint2* __restrict__ taps, int q_lo, int q_hi, int shift,
-                                                              unsigned flip, unsigned long long* __restrict__ counts) {
+                                                              unsigned flip, unsigned long long* __restrict__ counts,
+                                                              unsigned tpb) {
     constexpr int W = 16 / LANES;              // bytes of a slot = outputs of a lane per plane image
     constexpr int P = LANES * A;               // planes
     constexpr int TF = FIR_TILE / LANES;       // frames of a tile
@@ -178,6 +197,7 @@ __global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __re
     __shared__ slot_t s_img[P * NS];
     __shared__ unsigned s_cnt[FIR_THREADS / 64];
 
+    if constexpr (BLOCKS) taps += (size_t)(blockIdx.x / tpb) * ((LANES == 2 ? 3 : 1) * A * IMG);
     ar_load_planes<P>(x, n, flip, (long long)blockIdx.x * TF - AR_CQ, (TF + AR_LQ) / 4, NS * (W / 4),
                       reinterpret_cast<unsigned*>(s_img));
     __syncthreads();
@@ -259,6 +279,7 @@ struct ArStats {
     int K;
     unsigned flip;
     unsigned long long* sums;
+    unsigned tpb = 0, parts = 0;   // block statistics: tiles of a block and the workgroups that share them; parts 0: the whole record
 };
 
 struct ArCombine {
@@ -271,14 +292,24 @@ struct ArCombine {
     int q_lo, q_hi, shift;
     unsigned flip;
     unsigned long long* counts;
+    unsigned tpb = 0;              // block combiner: tiles of a block; 0: one set of taps
 };
 
 template <int LANES, int A> static void ar_launch(const ArStats& l) {
-    array_stats_kernel<LANES, A><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums);
+    if (l.parts) {
+        array_stats_kernel<LANES, A, true><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums, l.tpb, l.parts);
+    } else {
+        array_stats_kernel<LANES, A, false><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums, 0u, 0u);
+    }
 }
 template <int LANES, int A> static void ar_launch(const ArCombine& l) {
-    combine_kernel<LANES, A><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift, l.flip,
-                                                              l.counts);
+    if (l.tpb) {
+        combine_kernel<LANES, A, true><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift,
+                                                                        l.flip, l.counts, l.tpb);
+    } else {
+        combine_kernel<LANES, A, false><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift,
+                                                                         l.flip, l.counts, 0u);
+    }
 }
 template <int LANES, typename Launch> static void ar_launch_l(int A, const Launch& l) {
     switch (A) {
@@ -321,6 +352,54 @@ static int ar_check_record(const sgx_if* rec, int32_t lanes, int32_t A) {
     if (rec->n % (size_t)(A * lanes)) {
         sgx_set_error("bad argument: a record of %d antennas (lanes %d) holds whole frames of %d bytes, not %zu bytes", (int)A,
                       (int)lanes, (int)(A * lanes), rec->n);
+        return SGX_E_ARG;
+    }
+    return SGX_OK;
+}
+
+// The tap images of one set of taps, into g, which is zero: G_a[j] = the tap at frame offset j - AR_CQ, h_a[cc - (j - AR_CQ)]
+// (I/Q: re, im, -im per antenna).  [*q_lo, *q_hi) grows to the steps that hold a tap other than zero.
+static int ar_tap_pairs(int32_t lanes, int32_t A) { return A * (lanes == 2 ? 3 : 1) * (AR_LQ / 4); }
+static void ar_pack_taps(const int16_t* taps, int32_t lanes, int32_t A, int32_t K, uint2* g, int* q_lo, int* q_hi) {
+    const int cc = (K - 1) / 2, W = 16 / lanes, img = AR_LQ / 4, per_antenna = lanes == 2 ? 3 : 1;
+    for (int a = 0; a < A; ++a) {
+        uint2* ga = g + (size_t)a * per_antenna * img;
+        for (int j = 0; j < AR_LQ; ++j) {
+            const int k = cc - (j - AR_CQ);
+            if (k < 0 || k >= K) continue;
+            bool any;
+            if (lanes == 1) {
+                const int h = taps[a * K + k];
+                any = h != 0;
+                if (any) fir_pack_tap(ga, j, h);
+            } else {
+                const int re = taps[2 * (a * K + k)], im = taps[2 * (a * K + k) + 1];
+                any = re != 0 || im != 0;
+                if (re) fir_pack_tap(ga, j, re);
+                if (im) fir_pack_tap(ga + img, j, im), fir_pack_tap(ga + 2 * img, j, -im);
+            }
+            if (!any) continue;
+            if (j / W < *q_lo) *q_lo = j / W;
+            if (j / W + 1 > *q_hi) *q_hi = j / W + 1;
+        }
+    }
+}
+
+// The refusals of the blocks that the two block entry points share: B (no device needed), and the number of blocks that
+// `frames` frames make
+static int ar_check_block_length(int64_t B) {
+    if (B < 1 || B % SGX_ARRAY_BLOCK_UNIT) {
+        sgx_set_error("bad argument: B = %lld frames is no positive multiple of SGX_ARRAY_BLOCK_UNIT = %d", (long long)B,
+                      SGX_ARRAY_BLOCK_UNIT);
+        return SGX_E_ARG;
+    }
+    return SGX_OK;
+}
+static int ar_check_blocks(int64_t B, unsigned long long frames, unsigned long long* n_blocks) {
+    *n_blocks = (frames + (unsigned long long)B - 1) / (unsigned long long)B;
+    if (*n_blocks > SGX_ARRAY_MAX_BLOCKS) {
+        sgx_set_error("bad argument: %llu blocks of B = %lld frames are more than SGX_ARRAY_MAX_BLOCKS = %d", *n_blocks,
+                      (long long)B, SGX_ARRAY_MAX_BLOCKS);
         return SGX_E_ARG;
     }
     return SGX_OK;
@@ -415,32 +494,10 @@ extern "C" int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int3
     rc = sgx_stage_open(c, rec, rec->n);
     if (rc != SGX_OK) return rc;
 
-    // G_a[j] = the tap at frame offset j - AR_CQ: h_a[cc - (j - AR_CQ)]
-    const int cc = (K - 1) / 2, W = 16 / lanes, img = AR_LQ / 4, per_antenna = lanes == 2 ? 3 : 1;
-    const int pairs = A * per_antenna * img;
+    const int pairs = ar_tap_pairs(lanes, A);
     uint2* g = fir_tap_image(c, pairs);
-    int q_lo = AR_LQ / W, q_hi = 0;
-    for (int a = 0; a < A; ++a) {
-        uint2* ga = g + (size_t)a * per_antenna * img;
-        for (int j = 0; j < AR_LQ; ++j) {
-            const int k = cc - (j - AR_CQ);
-            if (k < 0 || k >= K) continue;
-            bool any;
-            if (lanes == 1) {
-                const int h = taps[a * K + k];
-                any = h != 0;
-                if (any) fir_pack_tap(ga, j, h);
-            } else {
-                const int re = taps[2 * (a * K + k)], im = taps[2 * (a * K + k) + 1];
-                any = re != 0 || im != 0;
-                if (re) fir_pack_tap(ga, j, re);
-                if (im) fir_pack_tap(ga + img, j, im), fir_pack_tap(ga + 2 * img, j, -im);
-            }
-            if (!any) continue;
-            if (j / W < q_lo) q_lo = j / W;
-            if (j / W + 1 > q_hi) q_hi = j / W + 1;
-        }
-    }
+    int q_lo = AR_LQ / (16 / lanes), q_hi = 0;
+    ar_pack_taps(taps, lanes, A, K, g, &q_lo, &q_hi);
     if (q_hi == 0) q_lo = 0;   // no tap at all: no step
 
     ArCombine l;
@@ -455,6 +512,150 @@ extern "C" int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int3
     unsigned long long* h_count = c->h_small->array_clip;
     SgxStage st(SGX_STAGE_COMBINE, l.grid, "combine kernel failed: %s", out, n_out);
     st.up = {c->d_small->fir_taps, g, (size_t)pairs * sizeof(uint2)};
+    st.count_into(h_count, l.counts, sizeof(SgxSmall::array_clip));
+    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
+        l.y = r->d;
+        if (lanes == 1) {
+            ar_launch_l<1>(A, l);
+        } else {
+            ar_launch_l<2>(A, l);
+        }
+    });
+    if (rc != SGX_OK) return rc;
+    if (clipped) *clipped = sgx_sum_slots(h_count, DC_COUNT_SLOTS, DC_COUNT_STRIDE);
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_block_stats_timing(sgx_ctx* c, float* kernel_ms) {
+    SGX_CHECK_ARG(c && kernel_ms);
+    *kernel_ms = c->stage_ms[SGX_STAGE_ARRAY_BLOCK_STATS];
+    return SGX_OK;
+}
+
+extern "C" int sgx_combine_blocks_timing(sgx_ctx* c, float* kernel_ms) {
+    SGX_CHECK_ARG(c && kernel_ms);
+    *kernel_ms = c->stage_ms[SGX_STAGE_COMBINE_BLOCKS];
+    return SGX_OK;
+}
+
+extern "C" int sgx_array_block_stats(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, int32_t K, int32_t flags,
+                                     int64_t B, int64_t* rho_blocks) {
+    int rc = ar_check_shape(lanes, A, K, flags);
+    if (rc == SGX_OK) rc = ar_check_block_length(B);
+    if (rc != SGX_OK) return rc;
+    SGX_CHECK_ARG(c && rec && rho_blocks);
+    SGX_CHECK_ARG(rec->device == c->device);
+    rc = ar_check_record(rec, lanes, A);
+    if (rc != SGX_OK) return rc;
+    const unsigned long long frames = rec->n / (size_t)(A * lanes);
+    unsigned long long n_blocks;
+    rc = ar_check_blocks(B, frames, &n_blocks);
+    if (rc != SGX_OK) return rc;
+    rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
+    const size_t bytes = (size_t)n_blocks * (size_t)(A * A * K * lanes) * sizeof(unsigned long long);
+    if (bytes) rc = c->d_array_blocks.ensure(bytes);
+    if (rc != SGX_OK) return rc;
+
+    ArStats l;
+    l.st = c->stream;
+    l.tiles = (frames + AR_TILE - 1) / AR_TILE;
+    // a block's tiles go to one workgroup, or - few blocks - to as many as fill the grid the whole-record kernel runs on
+    const unsigned long long tpb = (unsigned long long)B / AR_TILE;
+    l.tpb = (unsigned)(tpb < l.tiles ? tpb : l.tiles);
+    l.parts = 1;
+    if (n_blocks) {
+        const unsigned long long want = (AR_MAX_GRID + n_blocks - 1) / n_blocks;
+        l.parts = (unsigned)(want < l.tpb ? want : l.tpb);
+    }
+    l.grid = (unsigned)(n_blocks * l.parts);
+    l.x = rec->d;
+    l.n = (unsigned long long)rec->n;
+    l.K = K;
+    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
+    l.sums = c->d_array_blocks;
+    SgxStage st(SGX_STAGE_ARRAY_BLOCK_STATS, l.grid, "array block statistics kernel failed: %s");
+    st.count_into(rho_blocks, l.sums, bytes);   // (the table is the counters: cleared, added into, copied down)
+    return sgx_stage_run(c, st, [&](sgx_if*) {
+        if (lanes == 1) {
+            ar_launch_l<1>(A, l);
+        } else {
+            ar_launch_l<2>(A, l);
+        }
+    });
+}
+
+extern "C" int sgx_if_combine_blocks(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, const int16_t* taps,
+                                     int64_t n_blocks, int64_t B, int32_t K, int32_t shift, int32_t flags, sgx_if** out,
+                                     int64_t* clipped) {
+    // the shape and the taps of every block first: these refusals need no device
+    int rc = ar_check_shape(lanes, A, K, flags);
+    if (rc != SGX_OK) return rc;
+    if (shift < 0 || shift > 30) {
+        sgx_set_error("bad argument: shift %d lies outside 0 .. 30", (int)shift);
+        return SGX_E_ARG;
+    }
+    SGX_CHECK_ARG(taps);
+    rc = ar_check_block_length(B);
+    if (rc != SGX_OK) return rc;
+    if (n_blocks < 0 || n_blocks > SGX_ARRAY_MAX_BLOCKS) {
+        sgx_set_error("bad argument: n_blocks = %lld lies outside 0 .. SGX_ARRAY_MAX_BLOCKS = %d", (long long)n_blocks,
+                      SGX_ARRAY_MAX_BLOCKS);
+        return SGX_E_ARG;
+    }
+    const int per_block = lanes * A * K;
+    for (int64_t j = 0; j < n_blocks; ++j) {
+        if (fir_check_taps(taps + (size_t)j * per_block, per_block) == SGX_OK) continue;
+        char why[256];
+        sgx_last_error(why, sizeof why);
+        sgx_set_error("%s, in the taps of block %lld", why, (long long)j);
+        return SGX_E_ARG;
+    }
+    SGX_CHECK_ARG(c && rec && out);
+    SGX_CHECK_ARG(rec->device == c->device);
+    rc = ar_check_record(rec, lanes, A);
+    if (rc != SGX_OK) return rc;
+    const size_t n_out = rec->n / (size_t)A;
+    unsigned long long blocks_of_record;
+    rc = ar_check_blocks(B, (unsigned long long)(n_out / (size_t)lanes), &blocks_of_record);
+    if (rc != SGX_OK) return rc;
+    if (blocks_of_record != (unsigned long long)n_blocks) {
+        sgx_set_error("bad argument: n_blocks = %lld sets of taps for a record of %llu blocks of B = %lld frames",
+                      (long long)n_blocks, blocks_of_record, (long long)B);
+        return SGX_E_ARG;
+    }
+    const unsigned long long tiles = ((unsigned long long)n_out + FIR_TILE - 1) / FIR_TILE;
+    rc = sgx_stage_one_launch(tiles, "bad argument: a record of %zu output bytes is beyond one launch of the combiner", n_out);
+    if (rc != SGX_OK) return rc;
+    rc = sgx_stage_open(c, rec, rec->n);
+    if (rc != SGX_OK) return rc;
+
+    // every block's tap images, one table; the steps are those that hold a tap other than zero in ANY block (a zero tap adds
+    // nothing, so each block's bytes are what its own steps would give)
+    const int pairs = ar_tap_pairs(lanes, A);
+    std::vector<uint2> g((size_t)n_blocks * pairs, make_uint2(0u, 0u));
+    int q_lo = AR_LQ / (16 / lanes), q_hi = 0;
+    for (int64_t j = 0; j < n_blocks; ++j)
+        ar_pack_taps(taps + (size_t)j * per_block, lanes, A, K, g.data() + (size_t)j * pairs, &q_lo, &q_hi);
+    if (q_hi == 0) q_lo = 0;   // no tap at all: no step
+    if (!g.empty()) rc = c->d_array_taps.ensure(g.size() * sizeof(uint2));
+    if (rc != SGX_OK) return rc;
+
+    ArCombine l;
+    l.st = c->stream;
+    l.grid = (unsigned)tiles;
+    l.x = rec->d;
+    l.n = (unsigned long long)rec->n, l.n_out = (unsigned long long)n_out;
+    l.taps = c->d_array_taps;
+    l.q_lo = q_lo, l.q_hi = q_hi, l.shift = shift;
+    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
+    l.counts = c->d_small->array_clip;
+    // (a block is a whole number of tiles; a single block longer than the record's tiles is all of them)
+    const unsigned long long tpb = (unsigned long long)B * lanes / FIR_TILE;
+    l.tpb = (unsigned)(tpb < tiles ? tpb : (tiles ? tiles : 1));
+    unsigned long long* h_count = c->h_small->array_clip;
+    SgxStage st(SGX_STAGE_COMBINE_BLOCKS, l.grid, "block combine kernel failed: %s", out, n_out);
+    st.up = {c->d_array_taps.get(), g.data(), g.size() * sizeof(uint2)};
     st.count_into(h_count, l.counts, sizeof(SgxSmall::array_clip));
     rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         l.y = r->d;

@@ -127,10 +127,10 @@ struct WfPlan {
 
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
 // sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
-// sgx_if_resample, sgx_array_stats, sgx_if_combine
+// sgx_if_resample, sgx_array_stats, sgx_if_combine, sgx_array_block_stats, sgx_if_combine_blocks
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
                     SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_ARRAY_STATS,
-                    SGX_STAGE_COMBINE, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COMBINE, SGX_STAGE_ARRAY_BLOCK_STATS, SGX_STAGE_COMBINE_BLOCKS, SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -458,6 +458,10 @@ struct sgx_ctx {
     DevBuf<double> d_wf_rows;
     DevBuf<char> d_wf_out;
     float waterfall_ms = 0.0f;
+    // block-adaptive antenna combining (sgx_array.hip): the statistics of every block as the kernel adds them up, int64
+    // [n_blocks][A][A][K][lanes], and the tap images of every block as the combiner reads them (grow-only)
+    DevBuf<unsigned long long> d_array_blocks;
+    DevBuf<uint2> d_array_taps;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

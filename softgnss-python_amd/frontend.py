@@ -122,22 +122,30 @@ class _Combine(_Stage):
         ("arrayReference", 0),               # the antenna whose centre tap is held at 1
         ("arrayLoading", 1e-3),              # diagonal loading, in units of the mean power of the streams
         ("arrayTargetRms", 12.0),            # rms of the int8 record it makes, LSB, in (0, 127]
+        ("arrayBlockMs", 0),                 # weights per block of about that many ms (whole multiples of 4096 frames); 0: one set per record
+        ("arrayWindowBlocks", 3),            # a block's weights come from the statistics of that many blocks around it (odd, 1 .. 63)
     )
     options = (("--antennas", dict(default=None, metavar="A[:REF]",
                     help="the file interleaves the streams of A antennas (2 .. 8), frame by frame: combine them on the GPU "
                          "into one record with power-inversion weights that null a jammer, antenna REF (default 0) held at 1")),
                ("--array-taps", dict(type=int, default=None, metavar="K",
-                    help="with --antennas: taps per antenna (odd, 1 .. 15, A x K <= 64; default: 1 with --iq, else 5)")))
-    needs = "--array-taps is the filter length of the antenna combiner: it needs --antennas"
+                    help="with --antennas: taps per antenna (odd, 1 .. 15, A x K <= 64; default: 1 with --iq, else 5)")),
+               ("--array-block", dict(default=None, metavar="MS[:WINDOW]",
+                    help="with --antennas: new weights every MS ms (to a whole multiple of 4096 frames), each set from the "
+                         "statistics of WINDOW blocks around its own (odd, 1 .. 63; default 3): follows a jammer or an "
+                         "antenna that moves")))
+    needs = "--array-taps and --array-block describe the antenna combiner: they need --antennas"
     replays_file, verb = False, "combines"
     usage = """--antennas A[:REF] (A = 2 .. 8; int8 or uint8 files, real or with --iq, or the A streams of a --packed file) reads a
 file that interleaves the streams of A antennas frame by frame: the GPU takes the exact cross-correlations of the streams,
 the host designs power-inversion weights from them - least output power with antenna REF (0) held at 1, which nulls a
 broadband jammer and needs no array geometry - and the GPU runs every stream through a --array-taps K tap integer FIR (1 with
 --iq, else 5) and sums them into one int8 record at 12 LSB rms, in front of every other stage.  The suppression of the
-reference antenna's power, the largest weight and the share of clipped samples are printed.  --skip stays a byte of the file,
-on a frame of all antennas; positions in the results are samples of the combined record.  Not with --condition or
---iq-requantize."""
+reference antenna's power, the largest weight and the share of clipped samples are printed.  --array-block MS[:WINDOW]
+designs new weights for every block of MS ms (a whole multiple of 4096 frames) from the statistics of WINDOW blocks around it
+(3), for a jammer or an antenna that moves; the least and the median suppression over the blocks are printed.  --skip stays a
+byte of the file, on a frame of all antennas; positions in the results are samples of the combined record.  Not with
+--condition or --iq-requantize."""
 
     def settings_from(self, args, fail):
         A, ref = _numbers(args.antennas, ":") or (0, None)
@@ -145,7 +153,16 @@ on a frame of all antennas; positions in the results are samples of the combined
             fail("--antennas takes A[:REF] with A in 2 .. 8 and REF one of the antennas 0 .. A - 1")
         if args.array_taps is not None and args.array_taps <= 0:     # (0 is Settings' word for "the default length")
             fail("--array-taps takes the taps per antenna, odd, 1 .. 15")
-        return dict(antennas=A, arrayReference=ref, arrayTaps=args.array_taps)
+        block_ms = window = None
+        if args.array_block is not None:
+            ms, found, tail = args.array_block.partition(":")
+            try:
+                block_ms, window = float(ms), int(tail) if found else None
+            except ValueError:
+                block_ms = None
+            if block_ms is None or not (np.isfinite(block_ms) and block_ms > 0):     # (0 is Settings' word for "one set per record")
+                fail("--array-block takes MS[:WINDOW] with the block length MS in ms, above 0, and WINDOW blocks, odd, 1 .. 63")
+        return dict(antennas=A, arrayReference=ref, arrayTaps=args.array_taps, arrayBlockMs=block_ms, arrayWindowBlocks=window)
 
     def announce(self, file):
         return 'Combined %d antennas' % file.antennas
@@ -158,6 +175,12 @@ on a frame of all antennas; positions in the results are samples of the combined
         lanes, A, K = s._array_format()[:3]
         say('   Combining %d antennas through %d tap%s each...' % (A, K, "" if K == 1 else "s"))
         rec, info = s.combineAntennas(raw)
+        if "blocks" in info:
+            say('   %d samples in %d blocks of %d frames (%d held): reference antenna suppressed by %.2f dB at the least, %.2f dB '
+                'in the median, largest |weight| %.3f, median gain %+.2f dB, %.4f %% of the samples clipped'
+                % (info["samples"], info["blocks"], info["block_frames"], info["held_blocks"], info["suppression_db_min"],
+                   info["suppression_db"], float(np.max(np.abs(info["weights"]))), info["gain_db"], 100.0 * info["clipped"]))
+            return rec, info
         say('   %d samples: reference antenna suppressed by %.2f dB, largest |weight| %.3f, gain %+.2f dB, %.4f %% of the '
             'samples clipped' % (info["samples"], info["suppression_db"], float(np.max(np.abs(info["weights"]))),
                                  info["gain_db"], 100.0 * info["clipped"]))
@@ -700,7 +723,32 @@ class FrontEnd(object):
             raise ValueError("Settings.arrayLoading = %r: the diagonal loading is finite and not negative" % (self.arrayLoading,))
         if not (0 < target <= 127.0):
             raise ValueError("Settings.arrayTargetRms = %r lies outside (0, 127]" % (self.arrayTargetRms,))
+        self._array_block_format()
         return 2 if self.iqRecord else 1, A, K, ref, dt == np.dtype(np.uint8)
+
+    def _array_block_format(self):
+        """(block length in frames, window in blocks) of the block-adaptive combiner for these settings, or None where
+        arrayBlockMs is 0: one set of weights per record."""
+        try:
+            ms = float(self.arrayBlockMs)
+            ok = np.isfinite(ms) and ms >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.arrayBlockMs = %r: the block length in ms is finite and not negative (0: one set of "
+                             "weights per record)" % (self.arrayBlockMs,))
+        try:
+            W = int(self.arrayWindowBlocks)
+            ok = W == self.arrayWindowBlocks and 1 <= W <= _native.ARRAY_MAX_WINDOW and W % 2 == 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Settings.arrayWindowBlocks = %r: the window is an odd number of blocks in 1 .. %d"
+                             % (self.arrayWindowBlocks, _native.ARRAY_MAX_WINDOW))
+        if ms == 0:
+            return None
+        unit = _native.ARRAY_BLOCK_UNIT                # (the rate of frames is samplingFreq for a real and an I/Q record alike)
+        return max(1, int(round(ms * float(self.samplingFreq) / 1000.0 / unit))) * unit, W
 
     def combineAntennas(self, record):
         """A resident int8 record that interleaves the streams of Settings.antennas antennas frame by frame (a
@@ -711,7 +759,8 @@ class FrontEnd(object):
         instant of input frame f.  Returns (record8, info) and keeps info as self.lastCombining: samples, antennas, taps
         (per antenna), reference, weights (antennas x taps, complex for I/Q, before the gain), gain_db, suppression_db (the
         reference antenna's power over the output's), input_rms (per antenna and component, LSB) and clipped (share of the
-        samples that left the int8 range).  The caller frees both."""
+        samples that left the int8 range).  With arrayBlockMs the weights change along the record, block by block
+        (_combine_blocks says what the info holds then).  The caller frees both."""
         if not self.antennas:
             raise ValueError("Settings.antennas is 0: the stage is off")
         lanes, A, K, ref, offset_binary = self._array_format()
@@ -719,6 +768,9 @@ class FrontEnd(object):
             raise ValueError("a record of %d antennas holds whole frames of %d bytes, not %d bytes" % (A, A * lanes, len(record)))
         ctx = record.ctx
         frames = len(record) // (A * lanes)
+        blocks = self._array_block_format()
+        if blocks is not None:
+            return self._combine_blocks(record, frames, *blocks)
         rho = ctx.array_stats(record, lanes, A, K, offset_binary=offset_binary)
         try:
             taps, shift, out = _native.array_design(rho, frames, lanes, ref, self.arrayLoading, self.arrayTargetRms)
@@ -731,6 +783,36 @@ class FrontEnd(object):
                     gain_db=20.0 * float(np.log10(out["gain"])), suppression_db=out["suppression_db"],
                     input_rms=np.sqrt(power / (float(frames) * lanes)),
                     clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0)
+        self.lastCombining = info
+        return rec8, info
+
+    def _combine_blocks(self, record, frames, B, W):
+        """combineAntennas with arrayBlockMs: the statistics of every block of B frames (Context.array_block_stats), a set
+        of weights per block from the statistics of the W blocks around it (_native.array_design_blocks) and every output
+        frame through the set of its block (Context.combine_blocks).  Blocks count from the first frame of `record`.
+        lastCombining keeps its keys, with weights (blocks x antennas x taps) and suppression_db and gain_db the medians
+        over the designed blocks, and gains block_frames, blocks, window_blocks, block_suppression_db, block_gain_db,
+        held_blocks (blocks that hold a neighbour's weights: their own window is all zero) and suppression_db_min."""
+        lanes, A, K, ref, offset_binary = self._array_format()
+        ctx = record.ctx
+        rho = ctx.array_block_stats(record, lanes, A, K, B, offset_binary=offset_binary)
+        try:
+            taps, shift, out = _native.array_design_blocks(rho, frames, B, W, lanes, ref, self.arrayLoading, self.arrayTargetRms)
+        except _native.SgxError as e:
+            raise ValueError("Settings.antennas = %d, arrayTaps = %d, arrayReference = %d, arrayLoading = %r, arrayTargetRms = %r, "
+                             "arrayBlockMs = %r (%d frames), arrayWindowBlocks = %d on a record of %d frames: %s"
+                             % (A, K, ref, self.arrayLoading, self.arrayTargetRms, self.arrayBlockMs, B, W, frames, e))
+        rec8 = ctx.combine_blocks(record, lanes, A, taps, B, shift, offset_binary=offset_binary)
+        power = np.array([float(rho[:, a, a, 0, 0].sum()) for a in range(A)])
+        designed = out["status"] == 0
+        gain_db = 20.0 * np.log10(out["gain"])
+        info = dict(samples=len(rec8), antennas=A, taps=K, reference=ref, weights=out["weights"],
+                    gain_db=float(np.median(gain_db[designed])), suppression_db=float(np.median(out["suppression_db"][designed])),
+                    suppression_db_min=float(np.min(out["suppression_db"][designed])),
+                    input_rms=np.sqrt(power / (float(frames) * lanes)),
+                    clipped=float(rec8.clipped) / len(rec8) if len(rec8) else 0.0,
+                    block_frames=B, blocks=int(rho.shape[0]), window_blocks=W, block_suppression_db=out["suppression_db"],
+                    block_gain_db=gain_db, held_blocks=int(np.count_nonzero(out["status"])))
         self.lastCombining = info
         return rec8, info
 

@@ -1,5 +1,5 @@
-"""Times of the two kernels of the multi-antenna combiner (csrc/sgx_array.hip: sgx_array_stats, sgx_if_combine) on one GPU
-beside a copy of the same bytes:
+"""Times of the kernels of the multi-antenna combiner (csrc/sgx_array.hip: sgx_array_stats, sgx_if_combine and their
+block-wise siblings sgx_array_block_stats, sgx_if_combine_blocks) on one GPU beside a copy of the same bytes:
 
     python tools/array_probe.py [--ms 37000] [--antennas 4] [--calls 10]
 
@@ -9,12 +9,15 @@ each and as interleaved I/Q streams with K = 1.  One warm-up call, then --calls 
 stream around the kernel.  Prints one JSON line with the read and copy rates sgx_stream_rates measures in the same job, then
 one line per (kernel, lanes, K): min and median in ms, the time of the bytes it reads and writes at the copy rate (the
 statistics kernel only reads: at the read rate), the dot4 instructions per input byte, and the share of the memory bound it
-reaches."""
+reaches.  Then, per (lanes, K) and block length of 1 ms and 10 ms of frames (--block-ms), the block kernels in the same
+job with their ratio to the whole-record sibling, and for the longest block the wall-clock time of the whole block stage:
+statistics, download, host design, table upload and combine."""
 import argparse
 import importlib
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--ms", type=int, default=37000)
     ap.add_argument("--antennas", type=int, default=4)
     ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--block-ms", type=float, nargs="*", default=[1.0, 10.0])
     a = ap.parse_args()
     m = importlib.import_module("softgnss-python_amd")
     n = m._native
@@ -54,10 +58,11 @@ def main():
             rho = ctx.array_stats(rec, lanes, A, K)
             if i:
                 ms.append(ctx.array_stats_timing())
+        stats_ms = ms
         read_ms = n_in / read_gbs / 1e6
         print(json.dumps(dict(kernel="array_stats_kernel", lanes=lanes, antennas=A, taps=K, calls=a.calls,
                               kernel_ms_min=round(min(ms), 3), kernel_ms_median=round(float(np.median(ms)), 3),
-                              read_ms=round(read_ms, 3), dot4_per_byte=round(A * K * lanes / 4.0, 2),
+                              spread_ms=round(max(ms) - min(ms), 3), read_ms=round(read_ms, 3), dot4_per_byte=round(A * K * lanes / 4.0, 2),
                               share_of_bound=round(read_ms / min(ms), 3))), flush=True)
         taps, shift, info = n.array_design(rho, frames, lanes)
         ms = []
@@ -70,8 +75,52 @@ def main():
         copy_ms = (n_in + n_out) / copy_gbs / 1e6            # (bytes read + written, as tools/decim_probe.py counts them)
         print(json.dumps(dict(kernel="combine_kernel", lanes=lanes, antennas=A, taps=K, calls=a.calls,
                               kernel_ms_min=round(min(ms), 3), kernel_ms_median=round(float(np.median(ms)), 3),
-                              copy_ms=round(copy_ms, 3), suppression_db=round(info["suppression_db"], 2),
+                              spread_ms=round(max(ms) - min(ms), 3), copy_ms=round(copy_ms, 3), suppression_db=round(info["suppression_db"], 2),
                               clipped=clipped, share_of_bound=round(copy_ms / min(ms), 3))), flush=True)
+        whole = dict(stats=min(stats_ms), combine=min(ms))
+        for block_ms in a.block_ms:
+            B = max(1, int(round(block_ms * s.samplesPerCode / n.ARRAY_BLOCK_UNIT))) * n.ARRAY_BLOCK_UNIT
+            common = dict(lanes=lanes, antennas=A, taps=K, calls=a.calls, block_ms=block_ms, block_frames=B,
+                          blocks=n.array_blocks(frames, B))
+            ms = []
+            for i in range(a.calls + 1):
+                rho_b = ctx.array_block_stats(rec, lanes, A, K, B)
+                if i:
+                    ms.append(ctx.array_block_stats_timing())
+            assert np.array_equal(rho_b.sum(axis=0), rho)
+            print(json.dumps(dict(kernel="array_stats_kernel, blocks", kernel_ms_min=round(min(ms), 3),
+                                  kernel_ms_median=round(float(np.median(ms)), 3), spread_ms=round(max(ms) - min(ms), 3),
+                                  ratio_to_whole=round(min(ms) / whole["stats"], 3), **common)), flush=True)
+            taps_b, shift_b, info_b = n.array_design_blocks(rho_b, frames, B, 3, lanes)
+            ms = []
+            for i in range(a.calls + 1):
+                out = ctx.combine_blocks(rec, lanes, A, taps_b, B, shift_b)
+                out.free()
+                if i:
+                    ms.append(ctx.combine_blocks_timing())
+            print(json.dumps(dict(kernel="combine_kernel, blocks", kernel_ms_min=round(min(ms), 3),
+                                  kernel_ms_median=round(float(np.median(ms)), 3), spread_ms=round(max(ms) - min(ms), 3),
+                                  ratio_to_whole=round(min(ms) / whole["combine"], 3),
+                                  suppression_db_min=round(float(info_b["suppression_db"].min()), 2), **common)), flush=True)
+        # the whole block stage at the last block length, as Settings.combineAntennas runs it
+        parts = []
+        for i in range(a.calls + 1):
+            t = [time.perf_counter()]
+            rho_b = ctx.array_block_stats(rec, lanes, A, K, B)
+            t.append(time.perf_counter())
+            taps_b, shift_b, info_b = n.array_design_blocks(rho_b, frames, B, 3, lanes)
+            t.append(time.perf_counter())
+            ctx.combine_blocks(rec, lanes, A, taps_b, B, shift_b).free()
+            t.append(time.perf_counter())
+            if i:
+                parts.append(np.diff(t) * 1e3)
+        parts = np.array(parts)
+        total = parts.sum(axis=1)
+        print(json.dumps(dict(stage="block stage, wall clock", stage_ms_min=round(float(total.min()), 3),
+                              stage_ms_median=round(float(np.median(total)), 3),
+                              statistics_and_download_ms=round(float(np.median(parts[:, 0])), 3),
+                              host_design_ms=round(float(np.median(parts[:, 1])), 3),
+                              upload_and_combine_ms=round(float(np.median(parts[:, 2])), 3), **common)), flush=True)
     rec.free()
 
 
