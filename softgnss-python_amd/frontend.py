@@ -99,7 +99,18 @@ the results are samples of the unpacked record.  Not with --iq-requantize or --c
         unit, samples = s._pack_units()
         return unit, samples, _with(s, packedBits=0)
 
+    def whole(self, file, n_in, n_out):
+        """(bytes of the file, samples of the unpacked record) of the least run that holds whole frames of the packed file
+        and, with Settings.antennas, whole frames of all antennas: where the samples of a byte are not whole antenna
+        frames (packedFrame = 1: 2-bit samples of 3 antennas) the least common multiple of the two."""
+        if not _Combine().on(file):
+            return n_in, n_out
+        lanes, A = file._array_format()[:2]
+        k = int(np.lcm(n_out, A * lanes)) // n_out
+        return k * n_in, k * n_out
+
     def count_in(self, file, count, n_in, n_out):
+        n_in, n_out = self.whole(file, n_in, n_out)
         return -(-count // n_out) * n_in             # whole frames (with iqRecord n_out is even: whole pairs)
 
     def run(self, s, raw, say, prepared):
@@ -540,7 +551,7 @@ class FrontEnd(object):
         steps, real = self._walk()
         first, n_bytes = self._file_range(offset, count)
         if steps and isinstance(steps[0][0], _Unpack):      # (a packed file that ends inside a frame: the frame is left)
-            unit = steps[0][2]
+            unit = steps[0][0].whole(self, steps[0][2], steps[0][3])[0]     # (... with antennas, of all antennas)
             n_bytes = min(n_bytes, max(0, os.path.getsize(name) - first) // unit * unit)
         rec = engine.get_context(real, None).upload_file(name, first, n_bytes)
         try:

@@ -59,6 +59,23 @@ def check_counts(s, chain, want, what):
         assert np.array_equal(info["code_counts"], c["code_counts"][:info["code_counts"].size]), what
         assert int(c["code_counts"][info["code_counts"].size:].sum()) == 0
         assert np.array_equal(info["table"], c["table"]), what
+    if chain.antennas:
+        info, c = s.lastCombining, want["combine"]
+        A, K, ref, B, W = cases.array_of(chain)
+        assert (info["samples"], info["antennas"], info["taps"], info["reference"]) == (c["samples"], A, K, ref), what
+        assert np.array_equal(info["weights"], c["weights"]), what
+        assert info["clipped"] == c["clipped"] / float(c["samples"]), (what, info["clipped"], c["clipped"])
+        if not B:
+            assert info["suppression_db"] == c["suppression_db"] and info["gain_db"] == 20.0 * float(np.log10(c["gain"])), what
+        else:
+            designed = c["status"] == 0
+            assert (info["blocks"], info["block_frames"], info["window_blocks"], info["held_blocks"]) == \
+                (c["blocks"], B, W, c["held"]), what
+            assert np.array_equal(info["block_suppression_db"], c["suppression_db"]), what
+            assert np.array_equal(info["block_gain_db"], 20.0 * np.log10(c["gain"])), what
+            assert info["suppression_db"] == float(np.median(c["suppression_db"][designed])), what
+            assert info["suppression_db_min"] == float(np.min(c["suppression_db"][designed])), what
+            assert info["gain_db"] == float(np.median(20.0 * np.log10(c["gain"])[designed])), what
     if chain.first == "cond":
         info, c = s.lastConditioning, want["cond"]
         frames = c["samples"] // chain.lanes
@@ -97,7 +114,7 @@ def contract_for(s, chain, b, offset, count):
 
 
 def forget(s):
-    for k in ("lastUnpack", "lastConditioning", "lastRequant", "lastDecimation", "lastResampling", "lastNotchLines"):
+    for k in ("lastUnpack", "lastCombining", "lastConditioning", "lastRequant", "lastDecimation", "lastResampling", "lastNotchLines"):
         if hasattr(s, k):
             delattr(s, k)
 
@@ -148,7 +165,7 @@ def rounding_count(chain, most):
             if frames and per_unit > 1 and (n * (chain.D or 1)) % per_unit == 0:
                 continue
             return count
-        assert per_unit > 1 and chain.iq and chain.D, chain.name
+        assert per_unit > 1 and chain.iq and (chain.lanes * (chain.D or 1)) % per_unit == 0, chain.name
     raise AssertionError(chain.name)
 
 
