@@ -1,6 +1,6 @@
 // Multi-antenna records (include/sgx.h: sgx_array_stats, sgx_if_combine; contract: tests/array_spec.py): the exact lag
 // statistics of the A streams of a resident int8 record, and the A streams through one integer FIR each, summed into one
-// int8 record.  The fourth user of the dot4 FIR core (sgx_fir_dot4.h); the int8 matrix cores are left aside for the reason
+// int8 record.  The fifth user of the dot4 FIR core (sgx_fir_dot4.h); the int8 matrix cores are left aside for the reason
 // DESIGN.md section 4.11 gives.
 //
 // Both kernels are templated on (LANES, A) and start the same way: the record's bytes are one stream of P = A LANES planes,
@@ -20,9 +20,9 @@
 // one of AR_SUM_SLOTS copies of rho in the context's small area, one integer atomic per value.
 //
 // combine_kernel.  A workgroup makes FIR_TILE output bytes, 16 per lane, from plane images of FIR_TILE / LANES + 16 frames
-// that start AR_CQ = 8 frames in front of the tile: fir_steps<W> as it stands, per antenna one image and one tap image
-// G_a[j] = h_a[c + AR_CQ - j] (I/Q: re, im, -im), the partial sums added modulo 2^32 (the contract bounds the true sum
-// inside int32), the decimator's epilogue and its clip counters.
+// that start AR_CQ = 8 frames in front of the tile, per antenna one image and one tap image G_a[j] = h_a[c + AR_CQ - j]
+// (I/Q: re, im, -im).  The sum over the antennas, the rounding, the clip count and its fold are the header's
+// (fir_plane_sums, fir_count_fold).
 //
 // Weights per block (sgx_array_block_stats, sgx_if_combine_blocks; contract: tests/array_block_spec.py): the same two kernels
 // with BLOCKS set.  A block is a whole number of tiles of either kernel (SGX_ARRAY_BLOCK_UNIT), so no workgroup straddles a
@@ -56,7 +56,8 @@ __device__ __forceinline__ unsigned ar_load_dword(const int8_t* __restrict__ x, 
 }
 
 // Frames [frame0, frame0 + 4 units) of the record into P plane images of `pitch` dwords each; frame0 is a multiple of 4
-// (or negative and one), so every dword it loads is aligned
+// (or negative and one), so every dword it loads is aligned.  (Not the header's fir_split_planes: dwords of 4 frames, not
+// chunks of a slot, under this alignment rule, and the statistics kernel shares it.)
 template <int P>
 __device__ __forceinline__ void ar_load_planes(const int8_t* __restrict__ x, unsigned long long n, unsigned flip,
                                                long long frame0, int units, int pitch, unsigned* __restrict__ s_pl) {
@@ -202,72 +203,16 @@ __global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __re
                       reinterpret_cast<unsigned*>(s_img));
     __syncthreads();
 
-    const long long rnd = shift ? (1ll << (shift - 1)) : 0ll;
     const unsigned long long o0 = (unsigned long long)blockIdx.x * FIR_TILE + 16ull * threadIdx.x;
     unsigned out[4] = {0u, 0u, 0u, 0u};
     unsigned clipped = 0;
-    if constexpr (LANES == 1) {
-        int tot[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[r] = 0;
-#pragma unroll 1
-        for (int a = 0; a < A; ++a) {
-            int sum[16];
-            fir_steps<16>(s_img + a * NS, taps + a * IMG, q_lo, q_hi, sum);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tot[r] = (int)((unsigned)tot[r] + (unsigned)sum[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long long v = ((long long)tot[r] + rnd) >> shift;
-            clipped += (o0 + r < n_out && (v < -127 || v > 127)) ? 1u : 0u;
-            out[r >> 2] |= fir_round_clip(tot[r], false, rnd, shift) << ((r & 3) * 8);
-        }
-    } else {
-        int tot_i[8], tot_q[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) tot_i[r] = tot_q[r] = 0;
-#pragma unroll 1
-        for (int a = 0; a < A; ++a) {
-            const slot_t* s_i = s_img + (2 * a) * NS;
-            const slot_t* s_q = s_img + (2 * a + 1) * NS;
-            const uint2* g_re = taps + (3 * a) * IMG;
-            const uint2* g_im = g_re + IMG;
-            const uint2* g_nim = g_im + IMG;
-            int u[8], v[8];
-            fir_steps<8>(s_i, g_re, q_lo, q_hi, u);
-            fir_steps<8>(s_q, g_nim, q_lo, q_hi, v);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) tot_i[r] = (int)((unsigned)tot_i[r] + (unsigned)u[r] + (unsigned)v[r]);
-            fir_steps<8>(s_q, g_re, q_lo, q_hi, u);
-            fir_steps<8>(s_i, g_im, q_lo, q_hi, v);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) tot_q[r] = (int)((unsigned)tot_q[r] + (unsigned)u[r] + (unsigned)v[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const long long vi = ((long long)tot_i[r] + rnd) >> shift, vq = ((long long)tot_q[r] + rnd) >> shift;
-            // (n_out is even: a pair exists whole or not at all)
-            if (o0 + 2 * r < n_out) clipped += ((vi < -127 || vi > 127) ? 1u : 0u) + ((vq < -127 || vq > 127) ? 1u : 0u);
-            const unsigned e = fir_round_clip(tot_i[r], false, rnd, shift), o = fir_round_clip(tot_q[r], false, rnd, shift);
-            out[r >> 1] |= (e | (o << 8)) << ((r & 1) * 16);
-        }
-    }
+    fir_plane_sums<LANES, A>(s_img, NS, taps, IMG, q_lo, q_hi, shift, o0, n_out, out, clipped);
     if (o0 + 16 <= n_out) {
         *reinterpret_cast<uint4*>(y + o0) = make_uint4(out[0], out[1], out[2], out[3]);
     } else {
         for (int r = 0; r < 16 && o0 + r < n_out; ++r) y[o0 + r] = (int8_t)((out[r >> 2] >> ((r & 3) * 8)) & 0xFF);
     }
-
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) clipped += __shfl_down(clipped, d, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < FIR_THREADS / 64; ++w) t += s_cnt[w];
-        if (t) atomicAdd(&counts[(size_t)(blockIdx.x % DC_COUNT_SLOTS) * DC_COUNT_STRIDE], (unsigned long long)t);
-    }
+    fir_count_fold(clipped, s_cnt, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -282,45 +227,27 @@ struct ArStats {
     unsigned tpb = 0, parts = 0;   // block statistics: tiles of a block and the workgroups that share them; parts 0: the whole record
 };
 
-struct ArCombine {
-    hipStream_t st;
-    unsigned grid;
-    const int8_t* x;
-    int8_t* y;
-    unsigned long long n, n_out;
-    const uint2* taps;
-    int q_lo, q_hi, shift;
-    unsigned flip;
-    unsigned long long* counts;
-    unsigned tpb = 0;              // block combiner: tiles of a block; 0: one set of taps
-};
-
-template <int LANES, int A> static void ar_launch(const ArStats& l) {
+// The kernel of a launch's shape: the statistics kernel of an ArStats, the combiner of a FirLaunch
+template <int LANES, int A> static void ar_launch_la(const ArStats& l) {
     if (l.parts) {
         array_stats_kernel<LANES, A, true><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums, l.tpb, l.parts);
     } else {
         array_stats_kernel<LANES, A, false><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.n, l.tiles, l.K, l.flip, l.sums, 0u, 0u);
     }
 }
-template <int LANES, int A> static void ar_launch(const ArCombine& l) {
+template <int LANES, int A> static void ar_launch_la(const FirLaunch& l) {
     if (l.tpb) {
-        combine_kernel<LANES, A, true><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift,
-                                                                        l.flip, l.counts, l.tpb);
+        combine_kernel<LANES, A, true><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.steps.lo, l.steps.hi,
+                                                                        l.shift, l.flip, l.counts, l.tpb);
     } else {
-        combine_kernel<LANES, A, false><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.q_lo, l.q_hi, l.shift,
-                                                                         l.flip, l.counts, 0u);
+        combine_kernel<LANES, A, false><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.steps.lo, l.steps.hi,
+                                                                         l.shift, l.flip, l.counts, 0u);
     }
 }
-template <int LANES, typename Launch> static void ar_launch_l(int A, const Launch& l) {
-    switch (A) {
-        case 2: return ar_launch<LANES, 2>(l);
-        case 3: return ar_launch<LANES, 3>(l);
-        case 4: return ar_launch<LANES, 4>(l);
-        case 5: return ar_launch<LANES, 5>(l);
-        case 6: return ar_launch<LANES, 6>(l);
-        case 7: return ar_launch<LANES, 7>(l);
-        default: return ar_launch<LANES, 8>(l);
-    }
+template <typename Launch> static void ar_launch(int lanes, int A, const Launch& l) {
+    fir_dispatch<1, 2>(lanes, [&](auto la) {
+        fir_dispatch<2, SGX_ARRAY_MAX_ANTENNAS>(A, [&](auto a) { ar_launch_la<decltype(la)::value, decltype(a)::value>(l); });
+    });
 }
 
 // The refusals of the shape that both entry points share; each names its argument
@@ -358,31 +285,14 @@ static int ar_check_record(const sgx_if* rec, int32_t lanes, int32_t A) {
 }
 
 // The tap images of one set of taps, into g, which is zero: G_a[j] = the tap at frame offset j - AR_CQ, h_a[cc - (j - AR_CQ)]
-// (I/Q: re, im, -im per antenna).  [*q_lo, *q_hi) grows to the steps that hold a tap other than zero.
+// (I/Q: re, im, -im per antenna).  Returns `steps` grown to the steps that hold a tap other than zero.
 static int ar_tap_pairs(int32_t lanes, int32_t A) { return A * (lanes == 2 ? 3 : 1) * (AR_LQ / 4); }
-static void ar_pack_taps(const int16_t* taps, int32_t lanes, int32_t A, int32_t K, uint2* g, int* q_lo, int* q_hi) {
-    const int cc = (K - 1) / 2, W = 16 / lanes, img = AR_LQ / 4, per_antenna = lanes == 2 ? 3 : 1;
-    for (int a = 0; a < A; ++a) {
-        uint2* ga = g + (size_t)a * per_antenna * img;
-        for (int j = 0; j < AR_LQ; ++j) {
-            const int k = cc - (j - AR_CQ);
-            if (k < 0 || k >= K) continue;
-            bool any;
-            if (lanes == 1) {
-                const int h = taps[a * K + k];
-                any = h != 0;
-                if (any) fir_pack_tap(ga, j, h);
-            } else {
-                const int re = taps[2 * (a * K + k)], im = taps[2 * (a * K + k) + 1];
-                any = re != 0 || im != 0;
-                if (re) fir_pack_tap(ga, j, re);
-                if (im) fir_pack_tap(ga + img, j, im), fir_pack_tap(ga + 2 * img, j, -im);
-            }
-            if (!any) continue;
-            if (j / W < *q_lo) *q_lo = j / W;
-            if (j / W + 1 > *q_hi) *q_hi = j / W + 1;
-        }
-    }
+static FirSteps ar_pack_taps(const int16_t* taps, int32_t lanes, int32_t A, int32_t K, uint2* g, FirSteps steps) {
+    const int cc = (K - 1) / 2, per_antenna = ar_tap_pairs(lanes, 1);
+    for (int a = 0; a < A; ++a)
+        steps = fir_pack_image(taps + (size_t)a * K * lanes, K, lanes, 16 / lanes, g + (size_t)a * per_antenna, AR_LQ / 4,
+                               [&](int j) { return cc - (j - AR_CQ); }, steps);
+    return steps;
 }
 
 // The refusals of the blocks that the two block entry points share: B (no device needed), and the number of blocks that
@@ -453,13 +363,7 @@ extern "C" int sgx_array_stats(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int
     unsigned long long* h_sum = c->h_small->array_sum;
     SgxStage st(SGX_STAGE_ARRAY_STATS, l.grid, "array statistics kernel failed: %s");
     st.count_into(h_sum, l.sums, sizeof(SgxSmall::array_sum));
-    rc = sgx_stage_run(c, st, [&](sgx_if*) {
-        if (lanes == 1) {
-            ar_launch_l<1>(A, l);
-        } else {
-            ar_launch_l<2>(A, l);
-        }
-    });
+    rc = sgx_stage_run(c, st, [&](sgx_if*) { ar_launch(lanes, A, l); });
     if (rc != SGX_OK) return rc;
     const int n_val = A * A * K * lanes;
     for (int i = 0; i < n_val; ++i) {
@@ -475,10 +379,8 @@ extern "C" int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int3
     // the shape and the taps first: these refusals need no device
     int rc = ar_check_shape(lanes, A, K, flags);
     if (rc != SGX_OK) return rc;
-    if (shift < 0 || shift > 30) {
-        sgx_set_error("bad argument: shift %d lies outside 0 .. 30", (int)shift);
-        return SGX_E_ARG;
-    }
+    rc = fir_check_shift(shift);
+    if (rc != SGX_OK) return rc;
     SGX_CHECK_ARG(taps);
     // (all antennas add into one sum, so the bound is on the sum over all of them; lanes = 2: of |re| + |im|)
     rc = fir_check_taps(taps, lanes * A * K);
@@ -496,34 +398,11 @@ extern "C" int sgx_if_combine(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int3
 
     const int pairs = ar_tap_pairs(lanes, A);
     uint2* g = fir_tap_image(c, pairs);
-    int q_lo = AR_LQ / (16 / lanes), q_hi = 0;
-    ar_pack_taps(taps, lanes, A, K, g, &q_lo, &q_hi);
-    if (q_hi == 0) q_lo = 0;   // no tap at all: no step
-
-    ArCombine l;
-    l.st = c->stream;
-    l.grid = (unsigned)tiles;
-    l.x = rec->d;
-    l.n = (unsigned long long)rec->n, l.n_out = (unsigned long long)n_out;
-    l.taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
-    l.q_lo = q_lo, l.q_hi = q_hi, l.shift = shift;
-    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
-    l.counts = c->d_small->array_clip;
-    unsigned long long* h_count = c->h_small->array_clip;
+    FirLaunch l(c, rec, tiles, n_out, shift, (flags & SGX_ARRAY_OFFSET_BINARY) != 0);
+    l.steps = ar_pack_taps(taps, lanes, A, K, g, l.steps);
     SgxStage st(SGX_STAGE_COMBINE, l.grid, "combine kernel failed: %s", out, n_out);
     st.up = {c->d_small->fir_taps, g, (size_t)pairs * sizeof(uint2)};
-    st.count_into(h_count, l.counts, sizeof(SgxSmall::array_clip));
-    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
-        l.y = r->d;
-        if (lanes == 1) {
-            ar_launch_l<1>(A, l);
-        } else {
-            ar_launch_l<2>(A, l);
-        }
-    });
-    if (rc != SGX_OK) return rc;
-    if (clipped) *clipped = sgx_sum_slots(h_count, DC_COUNT_SLOTS, DC_COUNT_STRIDE);
-    return SGX_OK;
+    return fir_run_counted(c, st, l, clipped, [&] { ar_launch(lanes, A, l); });
 }
 
 extern "C" int sgx_array_block_stats_timing(sgx_ctx* c, float* kernel_ms) {
@@ -576,13 +455,7 @@ extern "C" int sgx_array_block_stats(sgx_ctx* c, const sgx_if* rec, int32_t lane
     l.sums = c->d_array_blocks;
     SgxStage st(SGX_STAGE_ARRAY_BLOCK_STATS, l.grid, "array block statistics kernel failed: %s");
     st.count_into(rho_blocks, l.sums, bytes);   // (the table is the counters: cleared, added into, copied down)
-    return sgx_stage_run(c, st, [&](sgx_if*) {
-        if (lanes == 1) {
-            ar_launch_l<1>(A, l);
-        } else {
-            ar_launch_l<2>(A, l);
-        }
-    });
+    return sgx_stage_run(c, st, [&](sgx_if*) { ar_launch(lanes, A, l); });
 }
 
 extern "C" int sgx_if_combine_blocks(sgx_ctx* c, const sgx_if* rec, int32_t lanes, int32_t A, const int16_t* taps,
@@ -591,10 +464,8 @@ extern "C" int sgx_if_combine_blocks(sgx_ctx* c, const sgx_if* rec, int32_t lane
     // the shape and the taps of every block first: these refusals need no device
     int rc = ar_check_shape(lanes, A, K, flags);
     if (rc != SGX_OK) return rc;
-    if (shift < 0 || shift > 30) {
-        sgx_set_error("bad argument: shift %d lies outside 0 .. 30", (int)shift);
-        return SGX_E_ARG;
-    }
+    rc = fir_check_shift(shift);
+    if (rc != SGX_OK) return rc;
     SGX_CHECK_ARG(taps);
     rc = ar_check_block_length(B);
     if (rc != SGX_OK) return rc;
@@ -634,38 +505,16 @@ extern "C" int sgx_if_combine_blocks(sgx_ctx* c, const sgx_if* rec, int32_t lane
     // nothing, so each block's bytes are what its own steps would give)
     const int pairs = ar_tap_pairs(lanes, A);
     std::vector<uint2> g((size_t)n_blocks * pairs, make_uint2(0u, 0u));
-    int q_lo = AR_LQ / (16 / lanes), q_hi = 0;
+    FirLaunch l(c, rec, tiles, n_out, shift, (flags & SGX_ARRAY_OFFSET_BINARY) != 0);
     for (int64_t j = 0; j < n_blocks; ++j)
-        ar_pack_taps(taps + (size_t)j * per_block, lanes, A, K, g.data() + (size_t)j * pairs, &q_lo, &q_hi);
-    if (q_hi == 0) q_lo = 0;   // no tap at all: no step
+        l.steps = ar_pack_taps(taps + (size_t)j * per_block, lanes, A, K, g.data() + (size_t)j * pairs, l.steps);
     if (!g.empty()) rc = c->d_array_taps.ensure(g.size() * sizeof(uint2));
     if (rc != SGX_OK) return rc;
-
-    ArCombine l;
-    l.st = c->stream;
-    l.grid = (unsigned)tiles;
-    l.x = rec->d;
-    l.n = (unsigned long long)rec->n, l.n_out = (unsigned long long)n_out;
     l.taps = c->d_array_taps;
-    l.q_lo = q_lo, l.q_hi = q_hi, l.shift = shift;
-    l.flip = (flags & SGX_ARRAY_OFFSET_BINARY) ? 0x80808080u : 0u;
-    l.counts = c->d_small->array_clip;
     // (a block is a whole number of tiles; a single block longer than the record's tiles is all of them)
     const unsigned long long tpb = (unsigned long long)B * lanes / FIR_TILE;
     l.tpb = (unsigned)(tpb < tiles ? tpb : (tiles ? tiles : 1));
-    unsigned long long* h_count = c->h_small->array_clip;
     SgxStage st(SGX_STAGE_COMBINE_BLOCKS, l.grid, "block combine kernel failed: %s", out, n_out);
     st.up = {c->d_array_taps.get(), g.data(), g.size() * sizeof(uint2)};
-    st.count_into(h_count, l.counts, sizeof(SgxSmall::array_clip));
-    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
-        l.y = r->d;
-        if (lanes == 1) {
-            ar_launch_l<1>(A, l);
-        } else {
-            ar_launch_l<2>(A, l);
-        }
-    });
-    if (rc != SGX_OK) return rc;
-    if (clipped) *clipped = sgx_sum_slots(h_count, DC_COUNT_SLOTS, DC_COUNT_STRIDE);
-    return SGX_OK;
+    return fir_run_counted(c, st, l, clipped, [&] { ar_launch(lanes, A, l); });
 }

@@ -116,9 +116,10 @@ struct WfPlan {
 #define UP_COUNT_SLOTS 256
 #define UP_COUNT_STRIDE 16   // 64-bit words between two slots
 
-// sgx_decim.hip: the slots the decimator spreads its per-workgroup counts of clipped outputs over, one 128-byte line each
-#define DC_COUNT_SLOTS 256
-#define DC_COUNT_STRIDE 16   // 64-bit words between two slots
+// sgx_fir_dot4.h: the slots the decimator, the resampler and the combiner spread their per-workgroup counts of clipped
+// outputs over, one 128-byte line each
+#define FIR_COUNT_SLOTS 256
+#define FIR_COUNT_STRIDE 16   // 64-bit words between two slots
 
 // sgx_array.hip: the copies of rho the statistics kernel spreads its per-workgroup sums over, each of AR_SUM_VALUES int64
 // values (A^2 K lanes <= 8 x 64 x 2 of them used)
@@ -330,7 +331,8 @@ struct SgxSmall {
     uint8_t nav_bits[SGX_MAX_SATS][256];    // sgx_synth.hip: the scene's navigation bits
     // The record front-end stages: what sgx_stage_run (sgx_stage.h) copies up in front of a stage's kernel or down behind
     // it.  Every stage waits before it returns, so one call owns a slot at a time; both.
-    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter, sgx_if_from_iq, sgx_if_decimate or sgx_if_resample call
+    // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter, sgx_if_from_iq, sgx_if_decimate, sgx_if_resample or
+    // sgx_if_combine call
     alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
     // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass, and
     // the quantiser's counters of outputs on +-127
@@ -340,14 +342,10 @@ struct SgxSmall {
     alignas(256) unsigned long long cond_count[CD_COUNT_SLOTS * CD_COUNT_STRIDE];
     // sgx_unpack.hip: the unpacker's code counters
     alignas(256) unsigned long long unpack_count[UP_COUNT_SLOTS * UP_COUNT_STRIDE];
-    // sgx_decim.hip: the decimator's counters of clipped outputs
-    alignas(256) unsigned long long decim_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
-    // sgx_resamp.hip: the resampler's counters of clipped outputs, in the decimator's layout
-    alignas(256) unsigned long long resamp_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
-    // sgx_array.hip: the statistics kernel's copies of rho (int64 values, added modulo 2^64), and the combiner's counters
-    // of clipped outputs, in the decimator's layout
+    // sgx_fir_dot4.h: the counters of clipped outputs of the decimator, the resampler or the combiner
+    alignas(256) unsigned long long fir_clip[FIR_COUNT_SLOTS * FIR_COUNT_STRIDE];
+    // sgx_array.hip: the statistics kernel's copies of rho (int64 values, added modulo 2^64)
     alignas(256) unsigned long long array_sum[AR_SUM_SLOTS * AR_SUM_VALUES];
-    alignas(256) unsigned long long array_clip[DC_COUNT_SLOTS * DC_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");

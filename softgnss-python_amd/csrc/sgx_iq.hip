@@ -124,19 +124,10 @@ extern "C" int sgx_if_from_iq(sgx_ctx* c, const sgx_if* iq_bytes, const int16_t*
     const int cp = ((cc / 2 + 7) / 8) * 8;
     const int lp = ((cp + (cc + 1) / 2 + 1 + 7) / 8) * 8;
     uint2* g = fir_tap_image(c, 2 * lp / 4);
-    int4 steps = make_int4(lp / 8, 0, lp / 8, 0);
-    for (int br = 0; br < 2; ++br) {
-        int* lo_step = br ? &steps.z : &steps.x;
-        int* end_step = br ? &steps.w : &steps.y;
-        for (int j = 0; j < lp; ++j) {
-            const int k = cc + br - 2 * (j - cp);
-            if (k < 0 || k >= L || taps[k] == 0) continue;
-            fir_pack_tap(g + br * (lp / 4), j, taps[k]);
-            if (j / 8 < *lo_step) *lo_step = j / 8;
-            if (j / 8 + 1 > *end_step) *end_step = j / 8 + 1;
-        }
-        if (*end_step == 0) *lo_step = 0;   // a branch without a tap: no step
-    }
+    FirSteps br[2];   // (a branch without a tap: no step)
+    for (int b = 0; b < 2; ++b)
+        br[b] = fir_pack_image(taps, L, 1, 8, g + b * (lp / 4), lp / 4, [&](int j) { return cc + b - 2 * (j - cp); });
+    const int4 steps = make_int4(br[0].lo, br[0].hi, br[1].lo, br[1].hi);
     const uint2* d_taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
     SgxStage st(SGX_STAGE_IQ, (unsigned)blocks, "I/Q conversion kernel failed: %s", out, iq_bytes->n);
     st.up = {c->d_small->fir_taps, g, (size_t)(2 * lp / 4) * sizeof(uint2)};

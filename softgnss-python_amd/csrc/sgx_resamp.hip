@@ -18,13 +18,12 @@
 //   * The sub-filter images share one origin: G_rp sits at j = e + cq, cq the reach to the left in plane samples rounded up
 //     so that cq M is a multiple of 16 (rs_cq); lq (a multiple of 16) covers all of them.  The first byte a workgroup
 //     needs, (i0 - cq) M, is then a multiple of 16: chunk loads are aligned, guarded per chunk (zero outside [0, N)).
-//   * M = 1: all L streams read ONE image of the input, filled by plain 16-byte copies.  M = 2, 3: a lane loads the M
-//     chunks that hold slot s of every plane and de-interleaves them in registers, as decim_kernel does for D = M.  Lanes
-//     write and read consecutive slots: no bank conflict.
+//   * M = 1: all L streams read ONE image of the input, filled by plain 16-byte copies.  M = 2, 3: fir_split_planes<M, 16>
+//     (sgx_fir_dot4.h), M chunks per slot of every plane.  Lanes write and read consecutive slots: no bank conflict.
 //   * Taps are wave-uniform: scalar loads from d_small->fir_taps, [L][M][lq / 4] pairs.  All streams run over one range of
 //     steps, the union of the steps that hold a tap; a step is 16 taps, so the default 24 taps per stream (M = 1) cost 32.
-//   * Clipped outputs: counted per lane on the value before the clip, folded over the wave by shuffles and over the
-//     workgroup through LDS, one integer atomic per workgroup into one of DC_COUNT_SLOTS padded slots.
+//   * Clipped outputs: counted per lane on the value before the clip (in 32 bits, see the kernel) and folded by the header's
+//     fir_count_fold.
 //
 // What bounds it: vector-ALU issue, not HBM.  Per output byte the kernel reads 1 / L input byte and writes one, 0.33 ms at
 // the copy rate for 1.4 GB of output at L = 10; it takes 1.3 ms there.  A step is 16 taps, so the default 24 taps of a stream
@@ -66,31 +65,6 @@ static constexpr int rs_img_slots(int l) {
     return most;
 }
 
-// Slots [0, ns) of the MM plane images from the record's bytes [base, base + 16 MM ns)
-template <int MM>
-__device__ __forceinline__ void rs_split(const int8_t* __restrict__ x, long long base, unsigned long long n, uint4* s_img,
-                                         int ns) {
-    for (int s = threadIdx.x; s < ns; s += FIR_THREADS) {
-        unsigned raw[4 * MM];
-#pragma unroll
-        for (int d = 0; d < MM; ++d) {
-            const uint4 v = fir_load_chunk(x, base + (long long)s * (16 * MM) + 16 * d, n, 0u);
-            raw[4 * d] = v.x, raw[4 * d + 1] = v.y, raw[4 * d + 2] = v.z, raw[4 * d + 3] = v.w;
-        }
-#pragma unroll
-        for (int pp = 0; pp < MM; ++pp) {
-            unsigned o[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const unsigned lo = fir_pick2(raw, (4 * g) * MM + pp, (4 * g + 1) * MM + pp);
-                const unsigned hi = fir_pick2(raw, (4 * g + 2) * MM + pp, (4 * g + 3) * MM + pp);
-                o[g] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-            }
-            s_img[pp * ns + s] = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-    }
-}
-
 template <int L>
 __global__ __launch_bounds__(FIR_THREADS) void resamp_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
                                                              unsigned long long n, unsigned long long n_out,
@@ -104,9 +78,9 @@ __global__ __launch_bounds__(FIR_THREADS) void resamp_kernel(const int8_t* __res
     if (M == 1) {
         for (int s = threadIdx.x; s < ns; s += FIR_THREADS) s_img[s] = fir_load_chunk(x, base + 16ll * s, n, 0u);
     } else if (M == 2) {
-        rs_split<2>(x, base, n, s_img, ns);
+        fir_split_planes<2, 16>(x, base, n, 0u, s_img, ns);
     } else {
-        rs_split<3>(x, base, n, s_img, ns);
+        fir_split_planes<3, 16>(x, base, n, 0u, s_img, ns);
     }
     __syncthreads();
 
@@ -162,54 +136,10 @@ __global__ __launch_bounds__(FIR_THREADS) void resamp_kernel(const int8_t* __res
             for (int b = 0; b < 16 && 16 * s + b < left; ++b) at[b] = (int8_t)((o[b >> 2] >> ((b & 3) * 8)) & 0xFF);
         }
     }
-
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) clipped += __shfl_down(clipped, d, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < FIR_THREADS / 64; ++w) t += s_cnt[w];
-        if (t) atomicAdd(&counts[(size_t)(blockIdx.x % DC_COUNT_SLOTS) * DC_COUNT_STRIDE], (unsigned long long)t);
-    }
+    fir_count_fold(clipped, s_cnt, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-struct RsLaunch {
-    hipStream_t st;
-    unsigned grid;
-    const int8_t* x;
-    int8_t* y;
-    unsigned long long n, n_out;
-    const uint2* taps;
-    int M, lq, cq, q_lo, q_hi, shift;
-    unsigned long long* counts;
-};
-
-template <int L> static void rs_launch_l(const RsLaunch& l) {
-    resamp_kernel<L><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.M, l.lq, l.cq, l.q_lo, l.q_hi, l.shift,
-                                                       l.counts);
-}
-static void rs_launch(int L, const RsLaunch& l) {
-    switch (L) {
-        case 2: return rs_launch_l<2>(l);
-        case 3: return rs_launch_l<3>(l);
-        case 4: return rs_launch_l<4>(l);
-        case 5: return rs_launch_l<5>(l);
-        case 6: return rs_launch_l<6>(l);
-        case 7: return rs_launch_l<7>(l);
-        case 8: return rs_launch_l<8>(l);
-        case 9: return rs_launch_l<9>(l);
-        case 10: return rs_launch_l<10>(l);
-        case 11: return rs_launch_l<11>(l);
-        case 12: return rs_launch_l<12>(l);
-        case 13: return rs_launch_l<13>(l);
-        case 14: return rs_launch_l<14>(l);
-        case 15: return rs_launch_l<15>(l);
-        default: return rs_launch_l<16>(l);
-    }
-}
-
 extern "C" int sgx_resamp_tile(int32_t* tile_bytes) {
     SGX_CHECK_ARG(tile_bytes);
     *tile_bytes = FIR_TILE * 16;
@@ -234,59 +164,38 @@ extern "C" int sgx_if_resample(sgx_ctx* c, const sgx_if* rec, const int16_t* tap
         sgx_set_error("bad argument: n_taps = %d is not an odd number in 1 .. %d", (int)n_taps, SGX_RESAMP_MAX_TAPS);
         return SGX_E_ARG;
     }
-    if (shift < 0 || shift > 30) {
-        sgx_set_error("bad argument: shift %d lies outside 0 .. 30", (int)shift);
-        return SGX_E_ARG;
-    }
+    int rc = fir_check_shift(shift);
+    if (rc != SGX_OK) return rc;
     SGX_CHECK_ARG(taps);
-    const int bad = fir_check_taps(taps, n_taps);
-    if (bad != SGX_OK) return bad;
+    rc = fir_check_taps(taps, n_taps);
+    if (rc != SGX_OK) return rc;
     SGX_CHECK_ARG(c && rec && out);
     SGX_CHECK_ARG(rec->device == c->device);
     const unsigned long long n_out = ((unsigned long long)rec->n * (unsigned)L + (unsigned)M - 1) / (unsigned)M;
     const unsigned long long per_stream = (n_out + (unsigned)L - 1) / (unsigned)L;
     const unsigned long long tiles = (per_stream + FIR_TILE - 1) / FIR_TILE;
-    int rc = sgx_stage_one_launch(tiles, "bad argument: a record of %zu output bytes is beyond one launch of the resampler",
-                                  (size_t)n_out);
+    rc = sgx_stage_one_launch(tiles, "bad argument: a record of %zu output bytes is beyond one launch of the resampler",
+                              (size_t)n_out);
     if (rc != SGX_OK) return rc;
     rc = sgx_stage_open(c, rec, rec->n);
     if (rc != SGX_OK) return rc;
 
     // G_rp[j] = the tap of stream r on plane p at e = j - cq: h[r M + cc - (e M + p) L]
-    const int cc = (n_taps - 1) / 2;
-    const int cq = rs_cq(L, M, cc), lq = rs_lq(L, M, cc), img = lq / 4;
-    uint2* g = fir_tap_image(c, rs_tap_pairs(L, M, cc));
-    int q_lo = lq / 16, q_hi = 0;
-    for (int r = 0; r < L; ++r) {
-        for (int p = 0; p < M; ++p) {
-            for (int j = 0; j < lq; ++j) {
-                const int k = r * M + cc - ((j - cq) * M + p) * L;
-                if (k < 0 || k >= n_taps || taps[k] == 0) continue;
-                fir_pack_tap(g + (size_t)(r * M + p) * img, j, taps[k]);
-                if (j / 16 < q_lo) q_lo = j / 16;
-                if (j / 16 + 1 > q_hi) q_hi = j / 16 + 1;
-            }
-        }
-    }
-    if (q_hi == 0) q_lo = 0;   // no tap at all: no step
+    const int cc = (n_taps - 1) / 2, cq = rs_cq(L, M, cc), lq = rs_lq(L, M, cc), pairs = rs_tap_pairs(L, M, cc);
+    uint2* g = fir_tap_image(c, pairs);
+    FirLaunch l(c, rec, tiles, n_out, shift, false);
+    l.M = M, l.lq = lq, l.cq = cq;
+    for (int r = 0; r < L; ++r)
+        for (int p = 0; p < M; ++p)
+            l.steps = fir_pack_image(taps, n_taps, 1, 16, g + (size_t)(r * M + p) * (lq / 4), lq / 4,
+                                     [&](int j) { return r * M + cc - ((j - cq) * M + p) * L; }, l.steps);
 
-    RsLaunch l;
-    l.st = c->stream;
-    l.grid = (unsigned)tiles;
-    l.x = rec->d;
-    l.n = (unsigned long long)rec->n, l.n_out = n_out;
-    l.taps = reinterpret_cast<const uint2*>(c->d_small->fir_taps);
-    l.M = M, l.lq = lq, l.cq = cq, l.q_lo = q_lo, l.q_hi = q_hi, l.shift = shift;
-    l.counts = c->d_small->resamp_clip;
-    unsigned long long* h_count = c->h_small->resamp_clip;
     SgxStage st(SGX_STAGE_RESAMP, l.grid, "resampling kernel failed: %s", out, (size_t)n_out);
-    st.up = {c->d_small->fir_taps, g, (size_t)rs_tap_pairs(L, M, cc) * sizeof(uint2)};
-    st.count_into(h_count, l.counts, sizeof(SgxSmall::resamp_clip));
-    rc = sgx_stage_run(c, st, [&](sgx_if* r) {
-        l.y = r->d;
-        rs_launch(L, l);
+    st.up = {c->d_small->fir_taps, g, (size_t)pairs * sizeof(uint2)};
+    return fir_run_counted(c, st, l, clipped, [&] {
+        fir_dispatch<2, 16>(L, [&](auto up) {
+            resamp_kernel<decltype(up)::value><<<l.grid, FIR_THREADS, 0, l.st>>>(l.x, l.y, l.n, l.n_out, l.taps, l.M, l.lq, l.cq,
+                                                                                 l.steps.lo, l.steps.hi, l.shift, l.counts);
+        });
     });
-    if (rc != SGX_OK) return rc;
-    if (clipped) *clipped = sgx_sum_slots(h_count, DC_COUNT_SLOTS, DC_COUNT_STRIDE);
-    return SGX_OK;
 }

@@ -5,10 +5,17 @@ other, a record without work leaves a zero slot and zero counters and still make
 carry over into the next one.  What the stages compute is the business of their own test files.
 
 Records are two tiles plus five bytes (elements, frames) of the stage, as its *_tile() reports it; the notch has the
-converter's tile, and the converter takes one byte more, because an I/Q record holds whole pairs.  Run with -m gpu."""
+converter's tile, and the converter takes one byte more, because an I/Q record holds whole pairs.
+
+The decimator, the resampler and the combiner count their clipped outputs in ONE area of the context (csrc/sgx_fir_dot4.h:
+fir_run_counted), so the last test runs them one after the other on one context and holds every count and every byte
+against the stage's spec.  Run with -m gpu."""
 import numpy as np
 import pytest
 
+import array_spec
+import decim_spec
+import resamp_spec
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -149,3 +156,44 @@ def test_counters_start_from_zero_on_every_call(ctx, stage):
     finally:
         loud.free()
         quiet.free()
+
+
+def clip_area_cases():
+    """(name, input bytes, call on a context and a record, (spec bytes, spec count)) of the stages that share the clip area:
+    a decimation (D = 3, I/Q) and a combine (A = 3, I/Q) of loud records through taps that must clip, and a resampling (L / M
+    = 3 / 2) of a quiet record through small taps that cannot: at most 9 taps of a stream meet a sample, 9 x 64 x 20 >> 8 is
+    45.  Outputs are three tiles of the stage plus 17 bytes - a workgroup with a whole tile, a seam, a whole 16-byte store
+    and byte stores behind the last tile, four counter slots -, and one byte more where the record is I/Q, whose outputs
+    are whole pairs."""
+    n = pkg()._native
+    rng = np.random.default_rng(11)
+    n_dec, n_res, n_com = 3 * n.decim_tile() + 18, 3 * n.resamp_tile() + 17, 3 * n.combine_tile() + 18
+    x_dec = rng.integers(-100, 101, 2 * (3 * (n_dec // 2) - 1)).astype(np.int8)      # ceil(frames / 3) = n_dec / 2
+    h_dec = rng.integers(-2000, 2001, 2 * 9).astype(np.int16)
+    x_res = rng.integers(-20, 21, (2 * n_res) // 3).astype(np.int8)                   # ceil(3 N / 2) = n_res
+    h_res = np.full(25, 64, dtype=np.int16)
+    x_com = rng.integers(-100, 101, 3 * n_com).astype(np.int8)
+    h_com = rng.integers(-3000, 3001, (3, 3, 2)).astype(np.int16)
+    cases = [("decimate", x_dec, lambda c, r: c.decimate(r, 2, h_dec, 6, 3), decim_spec.decimate(x_dec, h_dec, 6, 2, 3)),
+             ("resample", x_res, lambda c, r: c.resample(r, h_res, 8, 3, 2), resamp_spec.resample(x_res, h_res, 8, 3, 2)),
+             ("combine", x_com, lambda c, r: c.combine(r, 2, 3, h_com, 6), array_spec.combine(x_com, h_com, 6, 2, 3))]
+    for (name, _, _, (y, count)), size in zip(cases, (n_dec, n_res, n_com)):
+        assert y.size == size, (name, y.size, size)
+        assert (count == 0) == (name == "resample"), (name, count)       # the specs alone: (a) and (c) clip, (b) never does
+    return cases
+
+
+def test_the_fir_stages_share_one_clip_area_and_each_count_is_its_own(ctx):
+    dec, res, com = clip_area_cases()
+    for name, x, call, (want, count) in (dec, res, com, res):
+        rec = ctx.upload(x)
+        try:
+            out = call(ctx, rec)
+        finally:
+            rec.free()
+        try:
+            print(name, "clipped", out.clipped, "spec", count)
+            assert out.clipped == count, (name, out.clipped, count)
+            assert out.download().tobytes() == want.tobytes(), name
+        finally:
+            out.free()
