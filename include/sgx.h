@@ -400,6 +400,34 @@ int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, 
 int sgx_waterfall_plan(size_t n, int32_t nperseg, int32_t noverlap, size_t slice_len, int64_t* n_slices);
 int sgx_waterfall_timing(sgx_ctx* c, float* kernel_ms);
 
+/* ---- swept (chirp) interference excision (no reference counterpart; behind every preparing stage, in front of
+ * sgx_if_filter) --------------------------------------------------------------------------------------------------
+ * A real int8 record of n >= 1 samples through a short-time Fourier transform and back.  Segment j = 0 .. J - 1,
+ * J = ceil(n / H) + 1, H = N / 2, covers samples [(j - 1) H, (j + 1) H), zero outside the record, under the periodic
+ * root-Hann window w[i] = sin(pi i / N).  Of its bins k = 1 .. N/2 - 1 (DC and Nyquist are never cut) those are zeroed that
+ * stand above threshold x m, m the mean power of the kept bins, found in `passes` rounds that start from all of them; the
+ * segment goes back through the inverse transform and the same window into an overlap-add, and
+ * y = clip(floor(o + 1/2), -127, 127).  fp64 throughout.  A NEW record of the same length (sgx_if_free); sample n lines up
+ * with sample n of the input.  info: the segments J, the bins cut, the segments with a cut bin, and the outputs that lay
+ * outside [-127, 127] in front of the clip; cut_per_segment (may be NULL): the bins cut in each of the J segments.  No sum
+ * crosses a workgroup and every sum has one order: two calls give the same bytes.
+ * SGX_E_ARG, before anything is launched, with a text that names the argument: N not a power of two in 64 .. 1024, a
+ * threshold below 1 or not finite, passes outside 1 .. 8, an empty record, a record beyond one launch, a NULL pointer, a
+ * record on another device.
+ * sgx_excise_plan: J and the segments one workgroup holds, 8192 / N (a tile owns the hops between them; its last segment is
+ * the next tile's first); host code, needs no GPU.
+ * sgx_excise_host: the same arithmetic, item by item, in a host loop - what the kernel is tested against; needs no GPU.
+ * sgx_excise_host_spectra: the J x (N/2 + 1) complex bins (re, im) of the windowed segments as that loop computes them.
+ * sgx_excise_timing: HIP-event time of the last sgx_if_excise's kernel on this context, 0 where it had no work. */
+typedef struct { int64_t segments, bins_cut, segments_cut, clipped; } sgx_excise_info;
+int sgx_excise_plan(size_t n, int32_t N, int64_t* n_segments, int32_t* tile_segments);
+int sgx_if_excise(sgx_ctx* c, const sgx_if* rec, int32_t N, double threshold, int32_t passes, sgx_if** out,
+                  sgx_excise_info* info, uint16_t* cut_per_segment);
+int sgx_excise_host(const int8_t* x, size_t n, int32_t N, double threshold, int32_t passes, int8_t* y,
+                    sgx_excise_info* info, uint16_t* cut_per_segment);
+int sgx_excise_host_spectra(const int8_t* x, size_t n, int32_t N, double* spectra);
+int sgx_excise_timing(sgx_ctx* c, float* kernel_ms);
+
 /* ---- next row: bit sync + preamble search on the tracking output (postNavigation.py:443-631) ----------------
  * NavigationResult.findPreambles: I_P is [n_ch][ms] float64 (row i = i-th record of the tracking results);
  * firstSubFrame[ch] = ms index of the first verified TLM preamble, 0 = none (then the reference drops the

@@ -106,6 +106,11 @@ REPLAY_MAX_TAPS = 64
 REPLAY_STATE_DTYPE = np.dtype([("start", "<i8"), ("rem_code", "<f8"), ("rem_carr", "<f8"), ("step", "<f8"),
                                ("carr_freq", "<f8"), ("blk", "<i4"), ("reserved", "<i4")])
 
+class ExciseInfo(C.Structure):
+    """sgx_excise_info: what sgx_if_excise and sgx_excise_host count."""
+    _fields_ = [(k, C.c_int64) for k in ("segments", "bins_cut", "segments_cut", "clipped")]
+
+
 # every symbol include/sgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PROTOS = {
@@ -162,6 +167,11 @@ _PROTOS = {
                                       _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sgx_waterfall_plan": (C.c_int, [C.c_size_t, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_int64)]),
     "sgx_waterfall_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "sgx_excise_plan": (C.c_int, [C.c_size_t, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "sgx_if_excise": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_int32, C.POINTER(_P), C.POINTER(ExciseInfo), _P]),
+    "sgx_excise_host": (C.c_int, [_P, C.c_size_t, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(ExciseInfo), _P]),
+    "sgx_excise_host_spectra": (C.c_int, [_P, C.c_size_t, C.c_int32, _P]),
+    "sgx_excise_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_find_preambles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sgx_nav_parity_check": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "sgx_track_quality": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(LockParams), _P, _P, _P,
@@ -551,6 +561,46 @@ def waterfall_plan(n, nperseg, noverlap, slice_len):
         raise ValueError(last_error())
     check(rc)
     return int(ns.value)
+
+
+EXCISE_MIN_SEGMENT, EXCISE_MAX_SEGMENT, EXCISE_MAX_PASSES = 64, 1024, 8
+
+
+def excise_plan(n, N):
+    """(segments J, segments of one tile) of the excision of a record of n samples at segment length N (sgx_excise_plan;
+    needs no GPU).  ValueError for an N that is no power of two in 64 .. 1024 and for an empty record."""
+    J, S = C.c_int64(0), C.c_int32(0)
+    rc = lib().sgx_excise_plan(max(int(n), 0), int(N), C.byref(J), C.byref(S))
+    if rc == SGX_E_ARG:
+        raise ValueError(last_error())
+    check(rc)
+    return int(J.value), int(S.value)
+
+
+def _excise_info(info, per_segment):
+    return dict(segments=int(info.segments), bins_cut=int(info.bins_cut), segments_cut=int(info.segments_cut),
+                clipped=int(info.clipped), cut_per_segment=per_segment)
+
+
+def excise_host(x, N=256, threshold=8.0, passes=3):
+    """(y int8, info) of sgx_excise_host: the excision kernel's work items in a host loop; test infrastructure, needs no
+    GPU.  info as Context.excise_record's.  SgxError for what the library refuses."""
+    a = np.ascontiguousarray(x, dtype=np.int8).ravel()
+    y = np.zeros(a.size, dtype=np.int8)
+    ok = EXCISE_MIN_SEGMENT <= int(N) <= EXCISE_MAX_SEGMENT      # (what is out of range is the library's to refuse)
+    per = np.zeros(-(-a.size // (int(N) // 2)) + 1 if ok else 1, dtype=np.uint16)
+    info = ExciseInfo()
+    check(lib().sgx_excise_host(_ptr(a), a.size, int(N), float(threshold), int(passes), _ptr(y), C.byref(info), _ptr(per)))
+    return y, _excise_info(info, per[:info.segments])
+
+
+def excise_host_spectra(x, N=256):
+    """complex128[J, N/2 + 1]: the bins of the windowed segments as the host items compute them (sgx_excise_host_spectra)."""
+    a = np.ascontiguousarray(x, dtype=np.int8).ravel()
+    J = excise_plan(a.size, N)[0]
+    out = np.zeros((J, int(N) // 2 + 1), dtype=np.complex128)
+    check(lib().sgx_excise_host_spectra(_ptr(a), a.size, int(N), _ptr(out)))
+    return out
 
 
 class Waterfall(object):
@@ -1161,6 +1211,22 @@ class Context(object):
     def filter_timing(self):
         """Kernel ms of the last filter_record on this context, from HIP events on its stream."""
         return self._timing("sgx_filter_timing", 1)[0]
+
+    def excise_record(self, rec, N=256, threshold=8.0, passes=3):
+        """A new int8 record of the same length: `rec` cleared of swept interference (sgx_if_excise: segments of N samples at
+        hop N / 2 under the root-Hann window, in each the bins above threshold x the mean of the kept bins zeroed, `passes`
+        rounds, windowed overlap-add back).  Returns (record, info): segments, bins_cut, segments_cut, clipped and
+        cut_per_segment (uint16 per segment)."""
+        ok = EXCISE_MIN_SEGMENT <= int(N) <= EXCISE_MAX_SEGMENT      # (what is out of range is the library's to refuse)
+        J = -(-len(rec) // (int(N) // 2)) + 1 if ok else 1
+        per, info = np.zeros(J, dtype=np.uint16), ExciseInfo()
+        out = self._stage("sgx_if_excise", (rec._h, int(N), float(threshold), int(passes)), len(rec),
+                          tail=(C.byref(info), _ptr(per)))
+        return out, _excise_info(info, per)
+
+    def excise_timing(self):
+        """Kernel ms of the last excise_record on this context, from HIP events on its stream."""
+        return self._timing("sgx_excise_timing", 1)[0]
 
     def iq_to_if(self, rec, taps, shift, q_first=False, offset_binary=False):
         """A new int8 record of the same length: `rec`, the raw bytes of an interleaved 8-bit I/Q file at complex rate fs_c,

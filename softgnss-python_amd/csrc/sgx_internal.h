@@ -96,6 +96,16 @@ struct WfPlan {
     int prepare(int n_seg);
 };
 
+// The tables of the excision stage's segment length (sgx_excise.hip): tw[t] = W_n^t, t < n / 2, then win[i] = sin(pi i / n),
+// i < n, both computed on the host (ex_tables), in ONE device allocation the plan owns.  prepare() keeps those of the last
+// length.
+struct ExPlan {
+    int n = 0;
+    DevBuf<double> tables;
+    int prepare(int n_seg);
+};
+void ex_tables(int n_seg, cplx* tw, double* win);
+
 // sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
 #define SGX_IQ_LP_MAX 136
 
@@ -126,12 +136,17 @@ struct WfPlan {
 #define AR_SUM_SLOTS 8
 #define AR_SUM_VALUES 1024
 
+// sgx_excise.hip: the slots the excision kernel spreads its counts over; a slot is one 128-byte line that holds the bins
+// cut (word 0), the segments with a cut bin (word 1) and the clipped outputs (word 2)
+#define EX_COUNT_SLOTS 256
+#define EX_COUNT_STRIDE 16   // 64-bit words between two slots
+
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
 // sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
-// sgx_if_resample, sgx_array_stats, sgx_if_combine, sgx_array_block_stats, sgx_if_combine_blocks
+// sgx_if_resample, sgx_array_stats, sgx_if_combine, sgx_array_block_stats, sgx_if_combine_blocks, sgx_if_excise
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
                     SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_ARRAY_STATS,
-                    SGX_STAGE_COMBINE, SGX_STAGE_ARRAY_BLOCK_STATS, SGX_STAGE_COMBINE_BLOCKS, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COMBINE, SGX_STAGE_ARRAY_BLOCK_STATS, SGX_STAGE_COMBINE_BLOCKS, SGX_STAGE_EXCISE, SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -346,6 +361,8 @@ struct SgxSmall {
     alignas(256) unsigned long long fir_clip[FIR_COUNT_SLOTS * FIR_COUNT_STRIDE];
     // sgx_array.hip: the statistics kernel's copies of rho (int64 values, added modulo 2^64)
     alignas(256) unsigned long long array_sum[AR_SUM_SLOTS * AR_SUM_VALUES];
+    // sgx_excise.hip: the excision kernel's counters
+    alignas(256) unsigned long long excise_count[EX_COUNT_SLOTS * EX_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");
@@ -460,6 +477,10 @@ struct sgx_ctx {
     // [n_blocks][A][A][K][lanes], and the tap images of every block as the combiner reads them (grow-only)
     DevBuf<unsigned long long> d_array_blocks;
     DevBuf<uint2> d_array_taps;
+    // swept-interference excision (sgx_excise.hip): its plan and the cut bins of every segment as the kernel leaves them
+    // (grow-only)
+    ExPlan plan_excise;
+    DevBuf<uint16_t> d_excise_cut;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

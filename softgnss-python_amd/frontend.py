@@ -1,7 +1,7 @@
 """The record front end of Settings: the stages that stand between a record file and acquisition.
 
-STAGES is the one ordered table: unpack -> combine | condition | requantise -> decimate -> convert -> resample (the notch follows them
-and changes no position); what an entry says of its stage is listed at _Stage.  FrontEnd._walk folds the table forwards over
+STAGES is the one ordered table: unpack -> combine | condition | requantise -> decimate -> convert -> resample (the swept-interference
+excision and the notch follow them and change no position); what an entry says of its stage is listed at _Stage.  FrontEnd._walk folds the table forwards over
 the file's settings, _file_range walks the same pairs backwards and _prepared_record runs the stages in one loop: the shape
 of the composed contract, tests/chain_cases.py.  main.py builds its command line and its banner from the same table.
 """
@@ -431,6 +431,15 @@ _NOTCH_DEFAULTS = (
     ("notchTaps", 1025),                 # filter length (odd, at most 4095)
 )
 
+# swept (chirp) interference excision (Settings.excise; INTEGRATION.md, "Swept interference"): every short segment of the
+# prepared record loses the bins that stand out of its own spectrum, directly in front of the notch
+_EXCISE_DEFAULTS = (
+    ("sweptMitigation", False),          # postProcessing() excises the record before the notch, acquisition and tracking
+    ("exciseSegment", 256),              # segment length, a power of two in 64 .. 1024; the hop is half of it
+    ("exciseThreshold", 8.0),            # a bin this many times the mean of the segment's kept bins is cut (at least 1)
+    ("excisePasses", 3),                 # rounds of mean and cut, 1 .. 8
+)
+
 # the record monitor (Settings.monitorRecord; INTEGRATION.md, "Monitoring a record"): the spectrum and the sample statistics
 # of the whole prepared record, slice by slice - what the notch is designed from where notchWholeRecord is set
 _MONITOR_DEFAULTS = (
@@ -442,7 +451,7 @@ _MONITOR_DEFAULTS = (
 )
 MONITOR_PULSED_MADS = 6.0                # a slice is pulsed beyond the median + this many scaled MADs of the record's slices
 
-DEFAULTS = sum((stage.defaults for stage in STAGES), ()) + _NOTCH_DEFAULTS + _MONITOR_DEFAULTS
+DEFAULTS = sum((stage.defaults for stage in STAGES), ()) + _EXCISE_DEFAULTS + _NOTCH_DEFAULTS + _MONITOR_DEFAULTS
 # help of main's --dtype: no stage's own option, but which sample types a file may hold is what the stages above read
 DTYPE_HELP = "dataType of the file's samples (numpy name; with --iq: int8 or uint8, with --iq-requantize also int16 or float32)"
 
@@ -544,8 +553,10 @@ class FrontEnd(object):
         GPU, for the length of the block: the bytes _file_range(offset, count) of the file - offset and count are in BYTES
         OF THE PREPARED RECORD - through every stage of STAGES that is on, each intermediate record freed as soon as the
         next one exists, then with mitigate_at (a sample of the prepared record; None: no mitigation) cleared of the
-        narrowband lines in the spectrum from there on - the notch is designed at the prepared rate.  Yields the prepared
-        record, to be read under _prepared_settings(), and frees it afterwards."""
+        narrowband lines in the spectrum from there on - the notch is designed at the prepared rate.  With
+        sweptMitigation the record first goes through excise(), so the notch's spectrum is the excised record's; the notch
+        then runs only where interferenceMitigation asks for it too.  Yields the prepared record, to be read under
+        _prepared_settings(), and frees it afterwards."""
         from . import engine
         say = print if verbose else (lambda *args: None)
         steps, real = self._walk()
@@ -563,7 +574,17 @@ class FrontEnd(object):
                     raw.free()
                 if stage.last:
                     setattr(self, stage.last, info)
-            if mitigate_at is not None:
+            if mitigate_at is not None and self.sweptMitigation:
+                say('   Excising swept interference (segments of %d samples)...' % int(self.exciseSegment))
+                raw, rec = rec, None
+                try:
+                    rec, info = real.excise(raw)
+                finally:
+                    raw.free()
+                say('   %.4f %% of the time-frequency cells cut, %d samples clipped'
+                    % (100.0 * info["cells_cut"], info["clipped"]))
+                self.lastExcision = info
+            if mitigate_at is not None and (self.interferenceMitigation or not self.sweptMitigation):
                 say('   Looking for narrowband interference...')
                 raw = rec
                 rec, lines = real.mitigate(raw, offset=min(mitigate_at, len(raw)))
@@ -583,6 +604,21 @@ class FrontEnd(object):
         finally:
             if rec is not None:
                 rec.free()
+
+    def excise(self, record):
+        """Swept (chirp) interference excision of a resident int8 record (a _native.Record; Context.excise_record): segments
+        of exciseSegment samples at half that hop under a root-Hann window, in each the bins above exciseThreshold x the
+        mean of its kept bins zeroed (excisePasses rounds), overlap-add back.  Returns (record, info): a NEW record of the
+        same length - sample n lines up with sample n of the old one - and info, kept as self.lastExcision: segments,
+        bins_cut, segments_cut, clipped, cells_cut (the share of the segments x (exciseSegment / 2 - 1) time-frequency
+        cells that were cut) and cut_per_segment (uint16 per segment).  The caller frees both records."""
+        if np.dtype(self.dataType) != np.dtype(np.int8):
+            raise ValueError("swept-interference excision reads int8 records only, not Settings.dataType %r" % (self.dataType,))
+        N = int(self.exciseSegment)
+        new, info = record.ctx.excise_record(record, N, float(self.exciseThreshold), int(self.excisePasses))
+        info["cells_cut"] = info["bins_cut"] / float(info["segments"] * (N // 2 - 1))
+        self.lastExcision = info
+        return new, info
 
     def mitigate(self, record, offset=0, device=None):
         """Narrowband interference excision of a resident int8 record (a _native.Record): the Welch spectrum of the 10 code

@@ -241,7 +241,8 @@ class Settings(frontend.FrontEnd):
         need = skip + max(real.acquisitionLength(), int(self.msToProcess) * (n + 2) + 2 * n)
         if self.iqRecord:
             need += need % 2                         # (whole pairs; with decimation: whole groups of D pairs)
-        with self._prepared_record(name, 0, need, skip if self.interferenceMitigation else None, verbose=True) as rec:
+        mitigating = self.interferenceMitigation or self.sweptMitigation
+        with self._prepared_record(name, 0, need, skip if mitigating else None, verbose=True) as rec:
             window = DeviceSignal(rec, skip, min(real.acquisitionLength(), max(0, len(rec) - skip)))
             return self._acquire_and_track(real, window, DeviceFile(rec))
 
@@ -263,7 +264,7 @@ class Settings(frontend.FrontEnd):
             # (the reference then reads acqResults before anything assigned it: NameError, initialize.py:476,490)
             raise ValueError('skipAcquisition is set, but there are no acquisition results to reuse: '
                              'postProcessing() always acquires (initialize.py:476-490)')
-        if self.interferenceMitigation or any(stage.on(self) for stage in frontend.STAGES):
+        if self.interferenceMitigation or self.sweptMitigation or any(stage.on(self) for stage in frontend.STAGES):
             acqResults, trackResults = self._resident_processing(name)
             if trackResults is None:
                 return acqResults, None, None

@@ -3,6 +3,7 @@
     python -m softgnss-python_amd.main record.bin [--fs 38192000 --IF 9548000 --ms 37000 --channels 8 --skip 0]
                                                   [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]] [--dtype int8]
+                                                  [--excise[=THRESHOLD] --excise-segment N]
 %s
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
@@ -10,7 +11,10 @@ was lost, lost channels leaving the navigation) and, when the record is long eno
 ephemerides), the mean position fix.  --correlator-bank=-1:1:0.25 replays the tracked channels at those code offsets
 (chips) and prints each channel's mean correlation envelope per tap, normalised to its maximum.  --notch looks for
 continuous-wave lines in the record's spectrum (8 dB above the local median, or --notch=THRESHOLD_DB), filters them out on
-the GPU before acquisition and tracking, and prints the lines it removed.
+the GPU before acquisition and tracking, and prints the lines it removed.  --excise removes swept (chirp) interference in
+front of that: every segment of 256 samples (or --excise-segment N, a power of two in 64 .. 1024) loses the bins of its
+spectrum that stand 8 times (or --excise=THRESHOLD times) above the mean of its other bins; it prints the share of the
+time-frequency cells it cut and the samples it clipped.
 %s
 
 --monitor looks at the whole prepared record before anything else runs: per 100 ms (or --monitor=SLICE_MS) one Welch spectrum
@@ -97,6 +101,13 @@ def main(argv=None):
     ap.add_argument("--notch", nargs="?", type=float, const=-1.0, default=None, metavar="THRESHOLD_DB",
                     help="excise narrowband interference before acquisition: notch out the spectral lines that stand "
                          "THRESHOLD_DB (default: Settings.notchThresholdDb, 8) above the local median")
+    ap.add_argument("--excise", nargs="?", type=float, const=-1.0, default=None, metavar="THRESHOLD",
+                    help="excise swept (chirp) interference before the notch and acquisition: cut the bins of every short "
+                         "segment that stand THRESHOLD times (default: Settings.exciseThreshold, 8) above the mean of its "
+                         "other bins")
+    ap.add_argument("--excise-segment", type=int, default=None, metavar="N",
+                    help="with --excise: the segment length, a power of two in 64 .. 1024 (default: Settings.exciseSegment, "
+                         "256)")
     ap.add_argument("--monitor", nargs="?", type=float, const=-1.0, default=None, metavar="SLICE_MS",
                     help="monitor the whole record first: a spectrum and sample statistics per SLICE_MS ms (default: "
                          "Settings.monitorSliceMs, 100), a line printed per event and per slice that stands out")
@@ -117,6 +128,12 @@ def main(argv=None):
             ap.error("--correlator-bank takes LO:HI:STEP in chips with 1 .. 64 taps, e.g. --correlator-bank=-1:1:0.25")
     if a.notch_whole_record and a.notch is None:
         ap.error("--notch-whole-record says what --notch designs its filter from: it needs --notch")
+    if a.excise_segment is not None and a.excise is None:
+        ap.error("--excise-segment says how --excise cuts the record: it needs --excise")
+    if a.excise is not None and not (a.excise == -1.0 or (np.isfinite(a.excise) and a.excise >= 1.0)):
+        ap.error("--excise takes the threshold, a factor of at least 1")
+    if a.excise_segment is not None and not (64 <= a.excise_segment <= 1024 and a.excise_segment & (a.excise_segment - 1) == 0):
+        ap.error("--excise-segment takes a power of two in 64 .. 1024")
     if a.monitor_out is not None and a.monitor is None:
         ap.error("--monitor-out saves what --monitor sees: it needs --monitor")
     if a.monitor is not None and not (a.monitor == -1.0 or (np.isfinite(a.monitor) and a.monitor > 0)):
@@ -128,6 +145,9 @@ def main(argv=None):
                  interferenceMitigation=True if a.notch is not None else None,
                  notchThresholdDb=a.notch if a.notch is not None and a.notch >= 0 else None,
                  notchWholeRecord=a.notch_whole_record or None,
+                 sweptMitigation=True if a.excise is not None else None,
+                 exciseThreshold=a.excise if a.excise is not None and a.excise >= 1.0 else None,
+                 exciseSegment=a.excise_segment,
                  monitorSliceMs=a.monitor if a.monitor is not None and a.monitor > 0 else None)
     for stage, names in zip(STAGES, dests):
         given = [val is not None and val is not False for val in (getattr(a, name) for name in names)]
