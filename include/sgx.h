@@ -374,7 +374,9 @@ int sgx_stream_rates(sgx_ctx* c, size_t bytes, int reps, double* read_gbs, doubl
  * initialize.py:369-371).  f[8193] (MHz) and pxx[8193] = welch(data - mean(data), fs_mhz, hamming(16384, False),
  * 16384, 1024, 16384) (initialize.py:389-394); hist[255] = np.histogram(data, arange(-128, 128))[0]
  * (initialize.py:400, last bin closed); *n_segments = Welch segments averaged.  SGX_E_RANGE ("ValueError") for
- * fewer than 16384 samples. */
+ * fewer than 16384 samples.  The call is the record monitor below at nperseg 16384, noverlap 1024 and one slice of n
+ * samples, so a window longer than the monitor's longest slice, 2^32 samples, is refused as the monitor refuses it
+ * (SGX_E_ARG, the monitor's message).  It leaves sgx_waterfall_timing as it was. */
 #define SGX_PROBE_BINS 8193
 #define SGX_PROBE_HIST 255
 int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, double* f, double* pxx,
@@ -393,11 +395,15 @@ int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, doub
  * SGX_E_ARG: nperseg not a power of two in 256 .. 16384, noverlap outside [0, nperseg), slice_len below nperseg or above
  * 2^32 (a slice's sum of x^4 then fits int64), a NULL pointer, a record on another device; SGX_E_RANGE: a window outside
  * the record, or ("ValueError") shorter than one segment.
+ * sgx_waterfall_host: pxx[n_slices][nperseg/2+1] and n_segments[n_slices] of the window x[n] by the kernels' own work
+ * items and order of additions in a host loop - what the kernels are tested against, bit for bit; needs no GPU.
  * sgx_waterfall_timing: HIP-event time of the last sgx_probe_waterfall's kernels on this context. */
 int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, int32_t nperseg,
                         int32_t noverlap, size_t slice_len, double* f, double* pxx, double* hold, int64_t* moments,
                         int64_t* hist, int64_t* n_segments, int64_t* n_slices);
 int sgx_waterfall_plan(size_t n, int32_t nperseg, int32_t noverlap, size_t slice_len, int64_t* n_slices);
+int sgx_waterfall_host(const int8_t* x, size_t n, double fs_mhz, int32_t nperseg, int32_t noverlap, size_t slice_len,
+                       double* pxx, int64_t* n_segments);
 int sgx_waterfall_timing(sgx_ctx* c, float* kernel_ms);
 
 /* ---- swept (chirp) interference excision (no reference counterpart; behind every preparing stage, in front of

@@ -166,6 +166,7 @@ _PROTOS = {
     "sgx_probe_waterfall": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_double, C.c_int32, C.c_int32, C.c_size_t,
                                       _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sgx_waterfall_plan": (C.c_int, [C.c_size_t, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_int64)]),
+    "sgx_waterfall_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_int32, C.c_int32, C.c_size_t, _P, _P]),
     "sgx_waterfall_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_excise_plan": (C.c_int, [C.c_size_t, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sgx_if_excise": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_int32, C.POINTER(_P), C.POINTER(ExciseInfo), _P]),
@@ -561,6 +562,17 @@ def waterfall_plan(n, nperseg, noverlap, slice_len):
         raise ValueError(last_error())
     check(rc)
     return int(ns.value)
+
+
+def waterfall_host(x, fs_mhz, nperseg=16384, noverlap=1024, slice_len=None):
+    """(pxx float64[n_slices, bins], n_segments int64[n_slices]) of sgx_waterfall_host: the monitor's spectra of the window x
+    by the kernels' work items in a host loop; test infrastructure, needs no GPU.  ValueError as waterfall_plan."""
+    a = np.ascontiguousarray(x, dtype=np.int8).ravel()
+    S = a.size if slice_len is None else int(slice_len)
+    ns = waterfall_plan(a.size, nperseg, noverlap, S)
+    pxx, nseg = np.zeros((ns, int(nperseg) // 2 + 1)), np.zeros(ns, dtype=np.int64)
+    check(lib().sgx_waterfall_host(_ptr(a), a.size, float(fs_mhz), int(nperseg), int(noverlap), S, _ptr(pxx), _ptr(nseg)))
+    return pxx, nseg
 
 
 EXCISE_MIN_SEGMENT, EXCISE_MAX_SEGMENT, EXCISE_MAX_PASSES = 64, 1024, 8

@@ -1,7 +1,7 @@
 // Swept-interference excision (no reference counterpart): a real int8 record through a short-time Fourier transform -
 // segments of N samples at hop N / 2 under the root-Hann window - in which every segment loses the bins that stand above
 // threshold x the mean of its other bins, and back by windowed overlap-add.  tests/excise_spec.py is the contract,
-// sgx_excise_core.h the arithmetic, DESIGN.md section 4.22 the account.
+// sgx_excise_core.h the arithmetic around the transform of sgx_seg_fft.h, DESIGN.md section 4.22 the account.
 //
 //   excise_kernel  one workgroup per tile of S = 8192 / N consecutive segments, all of them in LDS (64 KB) from the staged
 //                  bytes to the output: every step of the transforms is one barrier for the whole tile.  The tile writes the
@@ -21,55 +21,22 @@
 #define EX_RAW_BYTES(S, M) ((size_t)((S) + 1) * (size_t)(M) + 32)
 #define EX_LDS_BYTES(S, M) (sizeof(cplx) * EX_TILE_POINTS + EX_RAW_BYTES(S, M))
 
-// The tables of one segment length, kept with the context until another length is asked for: tw[N / 2] | win[N]
-int ExPlan::prepare(int n_seg) {
-    if (n == n_seg && tables.get()) return SGX_OK;
-    const int M = n_seg / 2;
-    std::vector<double> h((size_t)2 * M + n_seg);
-    ex_tables(n_seg, reinterpret_cast<cplx*>(h.data()), h.data() + 2 * M);
-    n = 0;
-    const int rc = tables.ensure(sizeof(double) * h.size());
-    if (rc != SGX_OK) return rc;
-    SGX_HIP(hipMemcpy(tables.get(), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    n = n_seg;
-    return SGX_OK;
-}
-
+// The tables of segment length n_seg on the host: tw[n_seg / 2], win[n_seg]
 void ex_tables(int n_seg, cplx* tw, double* win) {
-    const int M = n_seg / 2;
-    for (int t = 0; t < M; ++t) {
-        const double a = 2.0 * M_PI * (double)t / (double)n_seg;
-        tw[t] = make_double2(cos(a), -sin(a));
-    }
+    seg_twiddles(n_seg, tw);
     for (int i = 0; i < n_seg; ++i) win[i] = sin(M_PI * (double)i / (double)n_seg);
 }
 
-// The forward steps on every segment of the tile; item q of a step belongs to segment q / (items per segment)
-#define EX_FORWARD(FOR_ITEMS)                                                                               \
-    for (int st = 0;; ++st) {                                                                               \
-        int log2h = 0;                                                                                      \
-        const int radix = wf_step(g.log2m, st, &log2h);                                                     \
-        if (!radix) break;                                                                                  \
-        if (radix == 2) {                                                                                   \
-            FOR_ITEMS(q, EX_TILE_POINTS / 2) wf_radix2_item(buf, q);                                        \
-        } else if (radix == 4) {                                                                            \
-            FOR_ITEMS(q, EX_TILE_POINTS / 4)                                                                \
-                wf_radix4_item(buf + ((q >> (g.log2m - 2)) << g.log2m), tw, M, 1 << log2h, log2h, q & (M / 4 - 1)); \
-        } else {                                                                                            \
-            FOR_ITEMS(q, EX_TILE_POINTS / 16)                                                               \
-                wf_radix16_item(buf + ((q >> (g.log2m - 4)) << g.log2m), tw, M, 1 << log2h, log2h, q & (M / 16 - 1)); \
-        }                                                                                                   \
-        EX_BARRIER;                                                                                         \
-    }
-
-// Byte b of dword d of the granule that starts at sample gs kept where the sample lies inside the record
-__device__ __forceinline__ unsigned ex_keep_bytes(unsigned w, int d, long long gs, long long n) {
-    unsigned m = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (gs + 4 * d + b >= 0 && gs + 4 * d + b < n) m |= 0xffu << (8 * b);
-    return w & m;
+// The excision's plan of segment length n_seg: tw[n_seg / 2] | win[n_seg] on the device
+static int ex_prepare(SegPlan* plan, int n_seg) {
+    if (plan->holds(n_seg)) return SGX_OK;
+    std::vector<double> h((size_t)2 * n_seg);
+    ex_tables(n_seg, reinterpret_cast<cplx*>(h.data()), h.data() + n_seg);
+    return plan->upload(n_seg, h.data(), h.size());
 }
+
+// The forward steps on every segment of the tile (EX_BARRIER: the caller's)
+#define EX_FORWARD(FOR_ITEMS) SEG_FORWARD(FOR_ITEMS, EX_BARRIER, buf, tw, M, g.log2m, EX_TILE_POINTS)
 
 // counts: EX_COUNT_SLOTS slots of (bins cut, segments cut, clipped outputs); cut_seg: per segment, or null
 __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
@@ -88,29 +55,9 @@ __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __rest
 #define EX_BARRIER __syncthreads()
 #define EX_LANES(q, count) for (int q = tid; q < (count); q += EX_THREADS)
 
-    // the bytes of the tile, samples [p0, p0 + (S + 1) M), read ONCE as the aligned 16-byte granules that cover them; a
-    // granule is loaded where it holds a sample of the record - it then lies inside the record's allocation and its
-    // SGX_IF_PAD, the record starting on a granule - and the bytes outside the record are zeroed
-    const long long p0 = (j0 - 1) * M;
-    const int a = (int)(((long long)(size_t)x + p0) & 15);
-    {
-        uint4* __restrict__ stage = reinterpret_cast<uint4*>(raw);
-        const int granules = (S + 1) * M / 16 + 1;
-        EX_LANES(c, granules) {
-            const long long gs = p0 - a + 16ll * c;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (gs >= 0 && gs < g.n) {
-                v = *reinterpret_cast<const uint4*>(x + gs);
-                if (gs + 16 > g.n) {
-                    v.x = ex_keep_bytes(v.x, 0, gs, g.n);
-                    v.y = ex_keep_bytes(v.y, 1, gs, g.n);
-                    v.z = ex_keep_bytes(v.z, 2, gs, g.n);
-                    v.w = ex_keep_bytes(v.w, 3, gs, g.n);
-                }
-            }
-            stage[c] = v;
-        }
-    }
+    // the bytes of the tile, samples [p0, p0 + (S + 1) M), zero outside the record
+    const int a = seg_stage(reinterpret_cast<uint4*>(raw), x, g.n, (j0 - 1) * M, (S + 1) * M, tid, EX_THREADS,
+                            [](int, uint4) {});
     EX_BARRIER;
     const int8_t* __restrict__ bytes = reinterpret_cast<const int8_t*>(raw) + a;
     EX_LANES(q, EX_TILE_POINTS) {
@@ -356,15 +303,15 @@ extern "C" int sgx_if_excise(sgx_ctx* c, const sgx_if* rec, int32_t N, double th
     rc = sgx_stage_one_launch((unsigned long long)g.tiles,
                               "bad argument: a record of %zu samples is beyond one launch of the excision kernel", rec->n);
     if (rc == SGX_OK) rc = sgx_stage_open(c, rec, rec->n);
-    if (rc == SGX_OK) rc = c->plan_excise.prepare(N);
+    if (rc == SGX_OK) rc = ex_prepare(&c->plan_excise, N);
     if (rc == SGX_OK && cut_per_segment) rc = c->d_excise_cut.ensure(sizeof(uint16_t) * (size_t)g.J);
     if (rc != SGX_OK) return rc;
     SGX_CHECK_ARG(((size_t)rec->d & 15) == 0);               // (every record starts on a granule: hipMalloc's alignment)
     const size_t lds = EX_LDS_BYTES(g.S, g.M);
     SGX_HIP(hipFuncSetAttribute((const void*)excise_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)EX_LDS_BYTES(EX_TILE_POINTS / (EX_MAX_SEGMENT / 2), EX_MAX_SEGMENT / 2)));
-    const cplx* d_tw = reinterpret_cast<const cplx*>(c->plan_excise.tables.get());
-    const double* d_win = reinterpret_cast<const double*>(d_tw + g.M);
+    const cplx* d_tw = c->plan_excise.tw();
+    const double* d_win = c->plan_excise.extra();
     uint16_t* d_cut = cut_per_segment ? c->d_excise_cut.get() : nullptr;
     unsigned long long* d_cnt = c->d_small->excise_count;
     unsigned long long* h_cnt = c->h_small->excise_count;

@@ -67,7 +67,6 @@ extern "C" int sgx_ctx_create_prio(const sgx_settings* s, int device, int priori
 sgx_ctx::~sgx_ctx() {
     sgx_fft_plan_destroy(&plan_code);
     sgx_fft_plan_destroy(&plan_fine);
-    sgx_fft_plan_destroy(&plan_probe);
     for (int i = 0; i < 2; ++i)
         if (stage[i]) hipHostFree(stage[i]);
     if (d_codes) hipFree(d_codes);

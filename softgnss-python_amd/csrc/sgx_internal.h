@@ -87,22 +87,25 @@ struct FftPlan {
     int cus = 0;                        // fine-search length only: compute units of the plan's device
 };
 
-// The twiddle table of the record monitor's segment length (sgx_waterfall.hip): tw[t] = W_n^t, t < n / 2, in ONE device
-// allocation the plan owns, and the sum of the squared window it implies.  prepare() keeps the table of the last length.
-struct WfPlan {
-    int n = 0;
-    DevBuf<cplx> tw;
-    double w2 = 0.0;
-    int prepare(int n_seg);
-};
-
-// The tables of the excision stage's segment length (sgx_excise.hip): tw[t] = W_n^t, t < n / 2, then win[i] = sin(pi i / n),
-// i < n, both computed on the host (ex_tables), in ONE device allocation the plan owns.  prepare() keeps those of the last
-// length.
-struct ExPlan {
+// The tables of one segment length of a short-time-transform stage (sgx_seg_fft.h), in ONE device allocation the plan owns
+// and kept with the context until another length is asked for: tw[t] = W_n^t, t < n / 2 (seg_twiddles), then what the stage
+// adds - the excision its root-Hann window win[n] (ex_tables), the monitor nothing on the device (the sum of its squared
+// window, which the table implies, stays beside its plan in the context).
+struct SegPlan {
     int n = 0;
     DevBuf<double> tables;
-    int prepare(int n_seg);
+    bool holds(int n_seg) const { return n == n_seg && tables.get(); }
+    // The tables of length n_seg as the stage computed them on the host: `count` doubles
+    int upload(int n_seg, const double* h, size_t count) {
+        n = 0;
+        const int rc = tables.ensure(sizeof(double) * count);
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipMemcpy(tables.get(), h, sizeof(double) * count, hipMemcpyHostToDevice));
+        n = n_seg;
+        return SGX_OK;
+    }
+    const cplx* tw() const { return reinterpret_cast<const cplx*>(tables.get()); }
+    const double* extra() const { return tables.get() + n; }     // behind the n / 2 complex twiddles
 };
 void ex_tables(int n_seg, cplx* tw, double* win);
 
@@ -436,7 +439,6 @@ struct sgx_ctx {
     // acquisition scratch (lazily sized)
     FftPlan plan_code;           // length samplesPerCode
     FftPlan plan_fine;           // length 8 * 2^ceil(log2(10 N))
-    FftPlan plan_probe;          // length 16384 (Welch segments of sgx_probe_stats)
     DevBuf<cplx> d_fwd;          // [n_blocks][n_bins][N] mixed-signal spectra
     DevBuf<cplx> d_codefd;       // [32][N] code spectra
     DevBuf<cplx> d_work[2];      // ping-pong [rows][N]
@@ -467,9 +469,11 @@ struct sgx_ctx {
     // (grow-only)
     DevBuf<sgx_cond_stats> d_cond_stats;
     DevBuf<sgx_cond_entry> d_cond_plan;
-    // the record monitor (sgx_waterfall.hip): its plan, the scratch rows of the segments in flight, the results on the
-    // device (grow-only) and the HIP-event time of the last call's kernels
-    WfPlan plan_waterfall;
+    // the record monitor (sgx_waterfall.hip; sgx_probe_stats runs it too): its plan and the sum of the squared window of
+    // the plan's length, the scratch rows of the segments in flight, the results on the device (grow-only) and the
+    // HIP-event time of the kernels of the last sgx_probe_waterfall
+    SegPlan plan_waterfall;
+    double waterfall_w2 = 0.0;
     DevBuf<double> d_wf_rows;
     DevBuf<char> d_wf_out;
     float waterfall_ms = 0.0f;
@@ -479,7 +483,7 @@ struct sgx_ctx {
     DevBuf<uint2> d_array_taps;
     // swept-interference excision (sgx_excise.hip): its plan and the cut bins of every segment as the kernel leaves them
     // (grow-only)
-    ExPlan plan_excise;
+    SegPlan plan_excise;
     DevBuf<uint16_t> d_excise_cut;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();

@@ -1,7 +1,9 @@
 // The record monitor (no reference counterpart: Settings.probeData looks at the first 10 code periods only): a window of an
 // int8 record cut into slices, each slice's Welch power spectral density - segments of N samples, constant detrend, periodic
 // Hamming window, density scaling, one-sided, mean over the segments, as sgx_probe_stats - and the exact integer statistics
-// of all its samples.  tests/waterfall_spec.py is the contract.
+// of all its samples.  tests/waterfall_spec.py is the contract; the transform, its step loop, the twiddle table and the
+// staging of the bytes are sgx_seg_fft.h's, shared with the excision stage.  sgx_probe_stats (Settings.probeData, reference
+// initialize.py:330-417) is the monitor at N = 16384, overlap 1024 and one slice, and lives at the end of this file.
 //
 //   wf_segment_kernel  one workgroup per segment: int8 samples -> exact integer sum -> the packed N/2-point complex
 //                      sequence in LDS (8192 x 16 B = 128 KB at N = 16384, the staged bytes 16 KB behind it) -> in-place transform -> real split -> the
@@ -13,6 +15,7 @@
 // The scratch holds at most WF_CHUNK_SEGMENTS rows (and at most WF_CHUNK_BYTES): a longer window runs chunk by chunk, the
 // running sum of a slice cut by a chunk boundary waits in its row of the result.  No floating-point atomics: every sum has
 // one order, so two runs give the same bits.
+//   sgx_waterfall_host  the segments' items and the averaging in a host loop: what the kernels are held to, bit for bit
 #include <math.h>
 
 #include "sgx_waterfall_core.h"
@@ -23,91 +26,66 @@
 #define WF_STATS_BLOCKS 2048
 #define WF_MAX_SLICE ((size_t)1 << 32)   // 2^32 samples x 127^4 < 2^63: the sum of x^4 of a slice fits int64
 
-// The twiddle table of one segment length, kept with the context until another length is asked for
-int WfPlan::prepare(int n_seg) {
-    if (n == n_seg && tw.get()) return SGX_OK;
-    const int M = n_seg / 2;
-    std::vector<cplx> h((size_t)M);
-    for (int t = 0; t < M; ++t) {
-        const double a = 2.0 * M_PI * (double)t / (double)n_seg;
-        h[(size_t)t] = make_double2(cos(a), -sin(a));
-    }
-    n = 0;
-    const int rc = tw.ensure(sizeof(cplx) * (size_t)M);
-    if (rc != SGX_OK) return rc;
-    SGX_HIP(hipMemcpy(tw.get(), h.data(), sizeof(cplx) * (size_t)M, hipMemcpyHostToDevice));
-    w2 = 0.0;
+// The twiddles of segment length n_seg on the host; returned: the sum of the squared window they imply
+static double wf_tables(int n_seg, cplx* tw) {
+    seg_twiddles(n_seg, tw);
+    double w2 = 0.0;
     for (int i = 0; i < n_seg; ++i) {
-        const double w = wf_window(h.data(), M, i);
+        const double w = wf_window(tw, n_seg / 2, i);
         w2 += w * w;
     }
-    n = n_seg;
-    return SGX_OK;
+    return w2;
 }
 
-// Bytes lo <= b < hi of a 16-byte granule kept, the others zeroed, in dword d of it
-__device__ __forceinline__ unsigned wf_keep_bytes(unsigned w, int d, int lo, int hi) {
-    unsigned m = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (4 * d + b >= lo && 4 * d + b < hi) m |= 0xffu << (8 * b);
-    return w & m;
+// The monitor's plan of segment length n_seg: the twiddles alone on the device, *w2 beside it
+static int wf_prepare(SegPlan* plan, double* w2, int n_seg) {
+    if (plan->holds(n_seg)) return SGX_OK;
+    std::vector<cplx> h((size_t)n_seg / 2);
+    *w2 = wf_tables(n_seg, h.data());
+    return plan->upload(n_seg, reinterpret_cast<const double*>(h.data()), (size_t)n_seg);
 }
 
-// The segment is read ONCE, as the N / 16 + 1 aligned 16-byte granules that cover it (a segment starts on any byte; the
-// granules reach at most 15 bytes in front of it and 16 behind, inside the record's allocation and its SGX_IF_PAD), and
-// staged in LDS behind the transform's buffer; the bytes outside the segment are left out of the sum.
-__global__ __launch_bounds__(1024) void wf_segment_kernel(const int8_t* __restrict__ x, const cplx* __restrict__ tw,
-                                                          double* __restrict__ rows, WfGeom g, long long seg0) {
+#define WF_STAGE_BYTES(N) (16 * ((size_t)(N) / 16 + 1))
+#define WF_LDS_BYTES(N) (sizeof(cplx) * ((size_t)(N) / 2) + WF_STAGE_BYTES(N))
+
+// One workgroup per segment.  x: the record (on a granule), n_rec samples long; the window starts at sample `offset` of
+// it.  The segment is staged in LDS behind the transform's buffer (seg_stage); the granules reach at most 15 bytes in
+// front of it and 15 behind, and their bytes outside the segment are left out of the sum.
+__global__ __launch_bounds__(1024) void wf_segment_kernel(const int8_t* __restrict__ x, long long n_rec, long long offset,
+                                                          const cplx* __restrict__ tw, double* __restrict__ rows, WfGeom g,
+                                                          long long seg0) {
     extern __shared__ __attribute__((aligned(16))) char wf_smem[];
     cplx* __restrict__ buf = reinterpret_cast<cplx*>(wf_smem);   // [N / 2]
     __shared__ int s_sum;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int M = g.N / 2;
     uint4* __restrict__ raw = reinterpret_cast<uint4*>(wf_smem + sizeof(cplx) * (size_t)M);   // [N / 16 + 1]
+#define WF_LANES(q, count) for (int q = tid; q < (count); q += nt)
     long long slice, start;
     wf_locate(g, seg0 + blockIdx.x, &slice, &start);
-    const int a = (int)((unsigned long long)(x + start) & 15);
-    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(x + start - a);
     if (tid == 0) s_sum = 0;
-    __syncthreads();
     int part = 0;
-    for (int c = tid; c <= g.N / 16; c += nt) {
-        uint4 v = src[c];
-        raw[c] = v;
-        if (c == 0 || c == g.N / 16) {                           // granule c holds the segment's bytes 16 c - a + (0 .. 15)
-            const int lo = c == 0 ? a : 0, hi = c == 0 ? 16 : a;
-            v.x = wf_keep_bytes(v.x, 0, lo, hi);
-            v.y = wf_keep_bytes(v.y, 1, lo, hi);
-            v.z = wf_keep_bytes(v.z, 2, lo, hi);
-            v.w = wf_keep_bytes(v.w, 3, lo, hi);
-        }
+    const int a = (int)((offset + start) & 15), last = (a + g.N - 1) / 16;
+    seg_stage(raw, x, n_rec, offset + start, g.N, tid, nt, [&](int c, uint4 v) {
+        // granule c holds the segment's bytes 16 c - a + (0 .. 15): the exact integer sum of the segment
+        if (c == 0 || c == last) v = seg_keep_bytes(v, a - 16 * c, a + g.N - 16 * c);
         part = __builtin_amdgcn_sdot4((int)v.x, 0x01010101, part, false);
         part = __builtin_amdgcn_sdot4((int)v.y, 0x01010101, part, false);
         part = __builtin_amdgcn_sdot4((int)v.z, 0x01010101, part, false);
         part = __builtin_amdgcn_sdot4((int)v.w, 0x01010101, part, false);
-    }
+    });
+    __syncthreads();
     for (int d = 32; d > 0; d >>= 1) part += __shfl_down(part, d, 64);
     if ((tid & 63) == 0) atomicAdd(&s_sum, part);              // integers: any order gives the same sum
     __syncthreads();
     const int sum = s_sum;
     const int8_t* __restrict__ seg = reinterpret_cast<const int8_t*>(raw) + a;
-    for (int m = tid; m < M; m += nt) wf_pack_item(buf, seg, tw, M, g.log2m, sum, m);
+    WF_LANES(m, M) wf_pack_item(buf, seg, tw, M, g.log2m, sum, m);
     __syncthreads();
-    for (int s = 0;; ++s) {
-        int log2h = 0;
-        const int radix = wf_step(g.log2m, s, &log2h);
-        if (!radix) break;
-        if (radix == 2)
-            for (int j = tid; j < M / 2; j += nt) wf_radix2_item(buf, j);
-        else if (radix == 4)
-            for (int q = tid; q < M / 4; q += nt) wf_radix4_item(buf, tw, M, 1 << log2h, log2h, q);
-        else
-            for (int q = tid; q < M / 16; q += nt) wf_radix16_item(buf, tw, M, 1 << log2h, log2h, q);
-        __syncthreads();
-    }
+    SEG_FORWARD(WF_LANES, __syncthreads(), buf, tw, M, g.log2m, M)
     double* __restrict__ row = rows + (size_t)blockIdx.x * (size_t)g.bins;
-    for (int k = tid; k <= M; k += nt) row[k] = wf_split_item(buf, tw, M, k);
+    WF_LANES(k, M + 1) row[k] = wf_split_item(buf, tw, M, k);
+#undef WF_LANES
 }
 
 // grid (bins / WF_AVG_THREADS, slices the chunk touches): segments [seg0, seg0 + n_seg) of the window lie in the scratch.
@@ -258,26 +236,19 @@ extern "C" int sgx_waterfall_timing(sgx_ctx* c, float* kernel_ms) {
     return SGX_OK;
 }
 
-extern "C" int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, int32_t nperseg,
-                                   int32_t noverlap, size_t slice_len, double* f, double* pxx, double* hold,
-                                   int64_t* moments, int64_t* hist, int64_t* n_segments, int64_t* n_slices) {
-    SGX_CHECK_ARG(c && rec && f && pxx && hold && moments && hist && n_segments && n_slices && fs_mhz > 0.0);
-    SGX_CHECK_ARG(rec->device == c->device);
-    if (offset > rec->n || n > rec->n - offset) {
-        sgx_set_error("monitor window [%zu, %zu) outside the %zu-sample record", offset, offset + n, rec->n);
-        return SGX_E_RANGE;
-    }
-    WfGeom g;
-    int rc = wf_geometry(n, nperseg, noverlap, slice_len, &g);
-    if (rc != SGX_OK) return rc;
-    rc = sgx_if_require(rec, offset + n);
+// The monitor on a window the caller has checked (inside the record, geometry g): the kernels, the results to the caller's
+// arrays, *kernel_ms = the HIP-event time of the kernels
+static int wf_run(sgx_ctx* c, const sgx_if* rec, size_t offset, const WfGeom& g, double fs_mhz, double* f, double* pxx,
+                  double* hold, int64_t* moments, int64_t* hist, int64_t* n_segments, float* kernel_ms) {
+    int rc = sgx_if_require(rec, offset + (size_t)g.n);
     if (rc != SGX_OK) return rc;
     SGX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    c->waterfall_ms = 0.0f;
-    rc = c->plan_waterfall.prepare(nperseg);
+    *kernel_ms = 0.0f;
+    rc = wf_prepare(&c->plan_waterfall, &c->waterfall_w2, g.N);
     if (rc != SGX_OK) return rc;
-    const double scale = 1.0 / (fs_mhz * c->plan_waterfall.w2);
+    SGX_CHECK_ARG(((size_t)rec->d & 15) == 0);               // (every record starts on a granule: hipMalloc's alignment)
+    const double scale = 1.0 / (fs_mhz * c->waterfall_w2);
 
     const size_t bins = (size_t)g.bins, ns = (size_t)g.n_slices;
     const long long total = g.n_full * g.k_full + (g.n_slices > g.n_full ? g.k_last : 0);
@@ -296,22 +267,21 @@ extern "C" int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset,
     unsigned long long* d_mom = (unsigned long long*)(d_hold + bins);
     unsigned long long* d_hist = d_mom + 4 * ns;
 
-    const int8_t* x = rec->d + offset;
-    const int M = nperseg / 2;
+    const int M = g.N / 2;
     const int threads = M / 8 >= 1024 ? 1024 : (M / 8 >= 64 ? M / 8 : 64);   // whole waves
-    const size_t lds = sizeof(cplx) * (size_t)M + 16 * ((size_t)nperseg / 16 + 1);   // the buffer and the staged bytes
     SGX_HIP(hipFuncSetAttribute((const void*)wf_segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(sizeof(cplx) * (WF_MAX_SEGMENT / 2) + 16 * (WF_MAX_SEGMENT / 16 + 1))));
+                                (int)WF_LDS_BYTES(WF_MAX_SEGMENT)));
     SGX_HIP(hipMemsetAsync(d_mom, 0, mom_bytes + hist_bytes, st));
     hipEventRecord(c->ev[0], st);
     {
         const long long pieces = (g.S + WF_PIECE - 1) / WF_PIECE, units = pieces * g.n_slices;
-        wf_stats_kernel<<<(unsigned)(units < WF_STATS_BLOCKS ? units : WF_STATS_BLOCKS), 256, 0, st>>>(x, g, pieces, units,
-                                                                                                      d_mom, d_hist);
+        wf_stats_kernel<<<(unsigned)(units < WF_STATS_BLOCKS ? units : WF_STATS_BLOCKS), 256, 0, st>>>(
+            rec->d + offset, g, pieces, units, d_mom, d_hist);
     }
     for (long long seg0 = 0; seg0 < total; seg0 += chunk) {
         const int n_seg = (int)(total - seg0 < chunk ? total - seg0 : chunk);
-        wf_segment_kernel<<<n_seg, threads, lds, st>>>(x, c->plan_waterfall.tw.get(), c->d_wf_rows.get(), g, seg0);
+        wf_segment_kernel<<<n_seg, threads, WF_LDS_BYTES(g.N), st>>>(rec->d, (long long)rec->n, (long long)offset,
+                                                                     c->plan_waterfall.tw(), c->d_wf_rows.get(), g, seg0);
         const long long slice0 = seg0 / g.k_full, slice1 = (seg0 + n_seg - 1) / g.k_full;
         wf_average_kernel<<<dim3((unsigned)((bins + WF_AVG_THREADS - 1) / WF_AVG_THREADS), (unsigned)(slice1 - slice0 + 1)),
                             WF_AVG_THREADS, 0, st>>>(
@@ -329,15 +299,103 @@ extern "C" int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset,
         sgx_set_error("monitor kernels failed: %s", hipGetErrorString(e));
         return SGX_E_HIP;
     }
-    hipEventElapsedTime(&c->waterfall_ms, c->ev[0], c->ev[1]);
+    hipEventElapsedTime(kernel_ms, c->ev[0], c->ev[1]);
     for (size_t j = 0; j < ns; ++j) {
         const long long lo = (long long)j * g.S, hi = lo + g.S < g.n ? lo + g.S : g.n;
         moments[4 * j] = (int64_t)(hi - lo);
         n_segments[j] = (int64_t)wf_slice_segments(g, (long long)j);
     }
-    // np.fft.rfftfreq(N, 1 / fs), as sgx_probe_stats
-    const double val = 1.0 / ((double)nperseg * (1.0 / fs_mhz));
+    // np.fft.rfftfreq(N, 1 / fs): val = 1 / (n d); f = arange(n / 2 + 1) * val
+    const double val = 1.0 / ((double)g.N * (1.0 / fs_mhz));
     for (int k = 0; k < g.bins; ++k) f[k] = (double)k * val;
-    *n_slices = (int64_t)g.n_slices;
+    return SGX_OK;
+}
+
+extern "C" int sgx_probe_waterfall(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, int32_t nperseg,
+                                   int32_t noverlap, size_t slice_len, double* f, double* pxx, double* hold,
+                                   int64_t* moments, int64_t* hist, int64_t* n_segments, int64_t* n_slices) {
+    SGX_CHECK_ARG(c && rec && f && pxx && hold && moments && hist && n_segments && n_slices && fs_mhz > 0.0);
+    SGX_CHECK_ARG(rec->device == c->device);
+    if (offset > rec->n || n > rec->n - offset) {
+        sgx_set_error("monitor window [%zu, %zu) outside the %zu-sample record", offset, offset + n, rec->n);
+        return SGX_E_RANGE;
+    }
+    WfGeom g;
+    int rc = wf_geometry(n, nperseg, noverlap, slice_len, &g);
+    if (rc == SGX_OK) rc = wf_run(c, rec, offset, g, fs_mhz, f, pxx, hold, moments, hist, n_segments, &c->waterfall_ms);
+    if (rc == SGX_OK) *n_slices = (int64_t)g.n_slices;
+    return rc;
+}
+
+// The monitor's spectra without a GPU: the segments' items in a host loop, SEG_FORWARD between them, and the additions of
+// wf_average_kernel in its order - acc += (p * scale) * two in segment order, then / count.  x: the window.
+extern "C" int sgx_waterfall_host(const int8_t* x, size_t n, double fs_mhz, int32_t nperseg, int32_t noverlap,
+                                  size_t slice_len, double* pxx, int64_t* n_segments) {
+    SGX_CHECK_ARG(x && pxx && n_segments && fs_mhz > 0.0);
+    WfGeom g;
+    const int rc = wf_geometry(n, nperseg, noverlap, slice_len, &g);
+    if (rc != SGX_OK) return rc;
+    const int M = g.N / 2;
+    std::vector<cplx> tw((size_t)M), buf((size_t)M);
+    const double scale = 1.0 / (fs_mhz * wf_tables(g.N, tw.data()));
+#define WF_ALL(q, count) for (int q = 0; q < (count); ++q)
+    for (long long j = 0; j < g.n_slices; ++j) {
+        const long long count = wf_slice_segments(g, j);
+        double* out = pxx + (size_t)j * (size_t)g.bins;
+        for (int k = 0; k < g.bins; ++k) out[k] = 0.0;
+        for (long long s = 0; s < count; ++s) {
+            long long slice, start;
+            wf_locate(g, j * g.k_full + s, &slice, &start);
+            const int8_t* seg = x + start;
+            int sum = 0;
+            WF_ALL(i, g.N) sum += seg[i];
+            WF_ALL(m, M) wf_pack_item(buf.data(), seg, tw.data(), M, g.log2m, sum, m);
+            SEG_FORWARD(WF_ALL, (void)0, buf.data(), tw.data(), M, g.log2m, M)
+            WF_ALL(k, g.bins) {
+                const double two = (k >= 1 && k < g.bins - 1) ? 2.0 : 1.0;
+                out[k] += (wf_split_item(buf.data(), tw.data(), M, k) * scale) * two;
+            }
+        }
+        WF_ALL(k, g.bins) out[k] /= (double)count;
+        n_segments[j] = (int64_t)count;
+    }
+#undef WF_ALL
+    return SGX_OK;
+}
+
+// ---- Settings.probeData ----------------------------------------------------------------------------------------------------
+// Raw-data statistics of Settings.probeData (reference initialize.py:330-417), the step before
+// acquisition: the Welch power spectral density of the first 10 code periods,
+//   welch(data - mean(data), fs/1e6, hamming(16384, sym=False), nperseg 16384, noverlap 1024, nfft 16384)
+// (scipy defaults: constant detrend per segment, density scaling, one-sided, mean over segments), and the histogram
+// np.histogram(data, arange(-128, 128)).  That is the monitor with one slice: removing the window's mean first changes
+// nothing behind a per-segment detrend, which the monitor does in exact integers.
+#define PROBE_NSEG 16384
+#define PROBE_NOVERLAP 1024
+
+extern "C" int sgx_probe_stats(sgx_ctx* c, const sgx_if* rec, size_t offset, size_t n, double fs_mhz, double* f,
+                               double* pxx, int64_t* hist, int32_t* n_segments) {
+    SGX_CHECK_ARG(c && rec && f && pxx && hist && n_segments && fs_mhz > 0.0);
+    SGX_CHECK_ARG(rec->device == c->device);
+    if (offset > rec->n || n > rec->n - offset) {
+        sgx_set_error("probe window [%zu, %zu) outside the %zu-sample record", offset, offset + n, rec->n);
+        return SGX_E_RANGE;
+    }
+    if (n < (size_t)PROBE_NSEG) {
+        // scipy falls back to nperseg = len(x) with a warning and then rejects the 16384-point window
+        sgx_set_error("ValueError: probeData needs at least %d samples for one Welch segment, got %zu", PROBE_NSEG, n);
+        return SGX_E_RANGE;
+    }
+    WfGeom g;
+    int rc = wf_geometry(n, PROBE_NSEG, PROBE_NOVERLAP, n, &g);   // (refuses a window beyond the monitor's longest slice)
+    if (rc != SGX_OK) return rc;
+    std::vector<double> hold((size_t)g.bins);
+    int64_t moments[4], h[256], segments = 0;
+    float ms = 0.0f;                                              // (waterfall_ms stays the last sgx_probe_waterfall's)
+    rc = wf_run(c, rec, offset, g, fs_mhz, f, pxx, hold.data(), moments, h, &segments, &ms);
+    if (rc != SGX_OK) return rc;
+    for (int b = 0; b < 255; ++b) hist[b] = h[b];
+    hist[254] += h[255];                                          // np.histogram's last bin [126, 127] is closed
+    *n_segments = (int32_t)segments;
     return SGX_OK;
 }

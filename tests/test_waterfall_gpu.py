@@ -1,7 +1,8 @@
 """The record monitor on the GPU (sgx_probe_waterfall, csrc/sgx_waterfall.hip; Settings.monitorRecord, mitigate with
 notchWholeRecord): the kernels against the numpy contract of tests/waterfall_spec.py on every case of tests/waterfall_cases.py -
-the integers exactly, the spectra to the bar of the probeData parity test taken relative to the slice's largest bin - then
-against sgx_probe_stats on the same window, on a streaming record, and end to end on a scene whose jammer switches on late."""
+the integers exactly, the spectra to the bar of the probeData parity test taken relative to the slice's largest bin - and
+against the host run of the same work items (sgx_waterfall_host) bit for bit; then sgx_probe_stats, which is the monitor at
+its own parameters, on the same window, a streaming record, and end to end a scene whose jammer switches on late."""
 import tempfile
 
 import numpy as np
@@ -64,6 +65,15 @@ def test_case_equals_the_contract(ctx, c):
     assert np.array_equal(got.hold, got.pxx.max(axis=0))
 
 
+@pytest.mark.parametrize("c", cases.CASES, ids=[c.name for c in cases.CASES])
+def test_case_equals_the_host_items_bit_for_bit(ctx, c):
+    got = run(ctx, c)
+    pxx, nseg = pkg()._native.waterfall_host(cases.record(c)[c.offset:c.offset + c.n], cases.FS_MHZ, c.N, c.noverlap, c.S)
+    assert np.array_equal(got.n_segments, nseg)
+    assert got.pxx.tobytes() == pxx.tobytes()
+    assert got.hold.tobytes() == pxx.max(axis=0).tobytes()
+
+
 @pytest.mark.parametrize("name", ["constant", "constant-16384", "all-min", "all-max"])
 def test_a_constant_record_gives_exactly_zero(ctx, name):
     got = run(ctx, cases.BY_NAME[name])
@@ -99,8 +109,7 @@ def test_two_calls_are_bit_identical(ctx, name):
 
 
 def test_slice_0_at_the_probe_s_parameters_is_probe_stats(ctx):
-    """One slice of 10 code periods at N = 16384, noverlap = 1024 is sgx_probe_stats' spectrum of the window: removing the
-    record mean first changes nothing behind a per-segment detrend."""
+    """sgx_probe_stats is the monitor with one slice of the window at N = 16384, noverlap = 1024: the same bits."""
     n = 10 * 38192
     x = np.clip(np.rint(np.random.default_rng(5).normal(3.0, 12.0, n + 7)), -127, 127).astype(np.int8)
     rec = ctx.upload(x)
@@ -109,8 +118,18 @@ def test_slice_0_at_the_probe_s_parameters_is_probe_stats(ctx):
     rec.free()
     assert got.pxx.shape == (1, 8193) and int(got.n_segments[0]) == nseg == 24
     assert np.array_equal(got.f, f)
-    assert np.abs(got.pxx[0] - pxx).max() / pxx.max() < PSD_TOL
+    assert np.array_equal(got.pxx[0], pxx)
     assert np.array_equal(got.hist[0, :254], hist[:254]) and got.hist[0, 254] + got.hist[0, 255] == hist[254]
+
+
+def test_probe_stats_leaves_the_monitor_s_timing(ctx):
+    c = cases.BY_NAME["grid-16384-1024"]
+    rec = ctx.upload(cases.record(c))
+    run(ctx, c, rec)
+    before = ctx.waterfall_timing()
+    ctx.probe_stats(rec, c.offset, c.n, cases.FS_MHZ)
+    assert before > 0.0 and ctx.waterfall_timing() == before
+    rec.free()
 
 
 def test_a_streaming_record_gives_the_same_arrays(ctx):

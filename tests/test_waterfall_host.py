@@ -1,7 +1,9 @@
 """The record monitor without a GPU: the numpy contract of tests/waterfall_spec.py against independent ground - scipy's welch
 per slice, the reference's own probeData spectrum, np.histogram and Python's big integers - then sgx_waterfall_plan against
 the contract's slice counts, the event merging and the pulsed rule of frontend.py on hand-built arrays, every refusal, and
-the false-alarm condition: the max-hold of the default scene without an interferer gives notch_design no line.
+the false-alarm condition: the max-hold of the default scene without an interferer gives notch_design no line; and the
+kernels' own work items in a host loop (sgx_waterfall_host) against the contract on every case and, at the probe's
+parameters, against the oracle's probeData spectrum per bin.
 Run with -m "not gpu"."""
 import ctypes
 import importlib
@@ -17,6 +19,7 @@ except ImportError:              # the restatement below stands in
 import waterfall_cases as cases
 import waterfall_spec as spec
 from conftest import load_golden, pkg, scene_from_json
+from oracle import softgnss_oracle as orc
 
 PSD_TOL = 1e-9     # tests/test_gpu_parity.py: relative, per bin
 
@@ -173,6 +176,43 @@ def test_the_options_reach_the_settings(built, monkeypatch, capsys):
     assert seen["monitored"] and seen["out"] == "a.npz"
     for option in ("--monitor", "--monitor-out", "--notch-whole-record"):
         assert option in pkg("main").__doc__
+
+
+# ---- the kernels' work items in a host loop -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c", cases.CASES, ids=[c.name for c in cases.CASES])
+def test_the_host_items_equal_the_contract(built, c):
+    """Every segment length 256 .. 16384 and every step pattern of the transform (2.4.16^n, 16^n, 4.16^n, 2.16^n) without a
+    GPU: the bar of tests/test_waterfall_gpu.py, PSD_TOL of the slice's largest bin; a slice that must be zero is +0.0."""
+    want = cases.want(c)
+    pxx, nseg = built._native.waterfall_host(cases.record(c)[c.offset:c.offset + c.n], cases.FS_MHZ, c.N, c.noverlap, c.S)
+    assert pxx.shape == want["pxx"].shape and np.array_equal(nseg, want["n_segments"])
+    worst = 0.0
+    for g, w in zip(pxx, want["pxx"]):
+        if w.max() == 0.0:
+            assert not g.any() and not np.signbit(g).any()
+        else:
+            worst = max(worst, float(np.abs(g - w).max() / w.max()))
+    print("%s: spectrum error %.3g of the slice's largest bin" % (c.name, worst))
+    assert worst < PSD_TOL
+
+
+def test_the_host_items_at_the_probe_s_parameters_are_the_oracle_s_probe_stats(built):
+    """sgx_probe_stats is the monitor at N = 16384, overlap 1024, one slice: its arithmetic on the windows of
+    tests/test_gpu_parity.py::test_probe_statistics_golden, held to the oracle per bin as that test holds the GPU."""
+    rng = np.random.default_rng(21)
+    x = rng.integers(-128, 128, size=500000, dtype=np.int8)
+    x[1000:1200] = -128
+    x[5000:5100] = 127
+    s2 = orc.OracleSettings()
+    s2.samplingFreq = 16367600.0
+    for off, n in ((0, 381920), (12345, 300001), (7, 16384), (99, 16385 + 15359)):
+        pxx, nseg = built._native.waterfall_host(x[off:off + n], 16.3676, 16384, 1024, n)
+        fo, po, ho = orc.probe_stats(s2, x[off:off + n])
+        assert pxx.shape == (1, 8193) and int(nseg[0]) == (n - 1024) // 15360
+        worst = float(np.max(np.abs(pxx[0] - po) / po))
+        print("window (%d, %d): PSD error %.3g per bin" % (off, n, worst))
+        assert worst < PSD_TOL
 
 
 # ---- events and pulsed slices ---------------------------------------------------------------------------------------------

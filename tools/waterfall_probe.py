@@ -6,9 +6,10 @@ The input is the default scene's record of --ms code periods (37 000: the 1.4 GB
 defaults (100 ms slices, segments of 16384 that share 1024).  One warm-up call, then --calls timed calls; HIP events on the
 context's stream around the kernels.  Prints one JSON line with the read and copy rates sgx_stream_rates measures in the same
 job and the read floor (the record's bytes at the read rate); one line with the monitor's kernel time, min and median; one
-line with the same analysis done the old way - sgx_probe_stats called once per slice, wall clock around the loop, which
-synchronises twice per call, writes every windowed segment to HBM as complex doubles and runs the FFT as global-memory
-passes - and the largest difference between the two spectra relative to each slice's largest bin."""
+line with the same analysis done slice by slice - sgx_probe_stats called once per slice, wall clock around the loop.
+sgx_probe_stats is the monitor at one slice, so the loop now measures what a call costs around the same kernels (the
+launches, a synchronisation and the copies back per slice), and the largest difference between the two spectra relative
+to each slice's largest bin is 0."""
 import argparse
 import importlib
 import json
