@@ -22,7 +22,7 @@
 // combine_kernel.  A workgroup makes FIR_TILE output bytes, 16 per lane, from plane images of FIR_TILE / LANES + 16 frames
 // that start AR_CQ = 8 frames in front of the tile, per antenna one image and one tap image G_a[j] = h_a[c + AR_CQ - j]
 // (I/Q: re, im, -im).  The sum over the antennas, the rounding, the clip count and its fold are the header's
-// (fir_plane_sums, fir_count_fold).
+// (fir_plane_sums) and the stage counters' (sgx_count.h).
 //
 // Weights per block (sgx_array_block_stats, sgx_if_combine_blocks; contract: tests/array_block_spec.py): the same two kernels
 // with BLOCKS set.  A block is a whole number of tiles of either kernel (SGX_ARRAY_BLOCK_UNIT), so no workgroup straddles a
@@ -72,12 +72,6 @@ __device__ __forceinline__ void ar_load_planes(const int8_t* __restrict__ x, uns
             s_pl[p * pitch + u] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
         }
     }
-}
-
-__device__ __forceinline__ int ar_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // BLOCKS: workgroup blockIdx.x takes part blockIdx.x % parts of block blockIdx.x / parts - tiles part, part + parts, .. of the
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* 
 #pragma unroll
                 for (int d = 0; d < KM; ++d) {
                     if (d < K) {
-                        const int t = ar_wave_sum(acc[d]);
+                        const int t = sgx_wave_sum(acc[d]);
                         if (lane == 0) s_sum[pr * K + d] += (long long)t;
                     }
                 }
@@ -163,7 +157,7 @@ __global__ __launch_bounds__(FIR_THREADS) void array_stats_kernel(const int8_t* 
 #pragma unroll
                 for (int d = 0; d < KM; ++d) {
                     if (d < K) {
-                        const int t_re = ar_wave_sum(acc_re[d]), t_im = ar_wave_sum(acc_p[d] - acc_m[d]);
+                        const int t_re = sgx_wave_sum(acc_re[d]), t_im = sgx_wave_sum(acc_p[d] - acc_m[d]);
                         if (lane == 0) {
                             s_sum[(pr * K + d) * 2] += (long long)t_re;
                             s_sum[(pr * K + d) * 2 + 1] += (long long)t_im;
@@ -196,7 +190,6 @@ __global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __re
     constexpr int IMG = AR_LQ / 4;             // pairs of a tap image
     typedef typename FirSlot<W>::type slot_t;
     __shared__ slot_t s_img[P * NS];
-    __shared__ unsigned s_cnt[FIR_THREADS / 64];
 
     if constexpr (BLOCKS) taps += (size_t)(blockIdx.x / tpb) * ((LANES == 2 ? 3 : 1) * A * IMG);
     ar_load_planes<P>(x, n, flip, (long long)blockIdx.x * TF - AR_CQ, (TF + AR_LQ) / 4, NS * (W / 4),
@@ -212,7 +205,8 @@ __global__ __launch_bounds__(FIR_THREADS) void combine_kernel(const int8_t* __re
     } else {
         for (int r = 0; r < 16 && o0 + r < n_out; ++r) y[o0 + r] = (int8_t)((out[r >> 2] >> ((r & 3) * 8)) & 0xFF);
     }
-    fir_count_fold(clipped, s_cnt, counts);
+    const unsigned count[1] = {clipped};
+    sgx_count_publish<1, FIR_THREADS / 64>(count, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------

@@ -18,8 +18,8 @@
 //                      16 frames in LDS, the first 2 CD_HALO lanes also those of the CD_HALO groups either side of the tile
 //                      (read again from the record, cut at its ends); the dilation is a windowed OR over the 9 masks
 //                      around a lane's own.  The group that holds the record's end loads and stores byte by byte.  Blanked
-//                      frames and outputs on +-127 are folded over the workgroup and added once, to one of CD_COUNT_SLOTS
-//                      lines.
+//                      frames and outputs on +-127 are counters 0 and 1 of the stage counters (sgx_count.h), one integer
+//                      atomic per workgroup each.
 #include <limits.h>
 
 #include <type_traits>
@@ -40,7 +40,6 @@ static_assert(CD_HALO * CD_GROUP >= CD_GUARD_MAX, "the halo covers the guard");
 static_assert((CD_BLOCK_MIN - 1 + CD_TILE + 2 * CD_HALO * CD_GROUP) / CD_BLOCK_MIN + 1 <= CD_PLAN_MAX, "the staged entries");
 static_assert(CD_BLOCK_MAX * 4 <= 4 * 1024 * 16, "the largest block fits 4 chunks in each of 1024 lanes");
 static_assert(sizeof(sgx_cond_stats) == 64 && sizeof(sgx_cond_entry) == 24, "include/sgx.h");
-static_assert(sizeof(SgxSmall::cond_count) == CD_COUNT_SLOTS * CD_COUNT_STRIDE * sizeof(unsigned long long), "one line per slot");
 
 // element i (a compile-time index after unrolling) of the words w of W-byte elements; offset binary was undone on loading
 template <int W> __device__ __forceinline__ int cd_elem(const unsigned* w, int i) {
@@ -68,26 +67,12 @@ template <int NW> __device__ __forceinline__ void cd_load_bytes(const int8_t* p,
         if (b < nb) w[b >> 2] |= (unsigned)(unsigned char)p[b] << (8 * (b & 3));
 }
 
-__device__ __forceinline__ long long cd_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ long long cd_wave_max(long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const long long o = __shfl_down(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // ---- statistics ----------------------------------------------------------------------------------------------------------
 // Two values per lane -> the same two totals in every lane.  s: this reduction's own [WAVES][2] slots (each of the four
 // reductions has its own, so one barrier per reduction is enough).  MAX1: the second value is a maximum, else a sum.
 template <bool MAX1, int WAVES> __device__ __forceinline__ void cd_reduce2(long long& a, long long& b, long long (*s)[2]) {
-    a = cd_wave_sum(a);
-    b = MAX1 ? cd_wave_max(b) : cd_wave_sum(b);
+    a = sgx_wave_sum(a);
+    b = MAX1 ? sgx_wave_max(b) : sgx_wave_sum(b);
     if ((threadIdx.x & 63) == 0) {
         s[threadIdx.x >> 6][0] = a;
         s[threadIdx.x >> 6][1] = b;
@@ -242,8 +227,8 @@ __device__ __forceinline__ unsigned cd_hits(const unsigned* w, int nv, const sgx
     return m;
 }
 
-// plan[n_plan]: one entry per block.  count: zeroed; slot i holds the blanked frames in word i * CD_COUNT_STRIDE and the
-// outputs on +-127 in the next.
+// plan[n_plan]: one entry per block.  count: the stage counters, zeroed; counter 0 takes the blanked frames, counter 1 the
+// outputs on +-127.
 template <int W, int L>
 __global__ __launch_bounds__(CD_THREADS) void cond_apply_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
                                                                 unsigned long long n_frames, int block,
@@ -253,7 +238,6 @@ __global__ __launch_bounds__(CD_THREADS) void cond_apply_kernel(const int8_t* __
     constexpr int FB = W * L;
     __shared__ sgx_cond_entry s_plan[CD_PLAN_MAX];
     __shared__ unsigned short s_hit[CD_THREADS + 2 * CD_HALO];
-    __shared__ unsigned s_cnt[CD_WAVES][2];
     const int t = (int)threadIdx.x;
     const unsigned long long tile_f0 = (unsigned long long)blockIdx.x * CD_TILE;
     // the blocks of the tile and its halo: kfirst .. kfirst + n_ent - 1; base_f = the first frame of block kfirst
@@ -313,7 +297,8 @@ __global__ __launch_bounds__(CD_THREADS) void cond_apply_kernel(const int8_t* __
         blank |= b ? 1u << i : 0u;
     }
     const unsigned valid = nv == CD_GROUP ? 0xFFFFu : (1u << nv) - 1u;
-    unsigned n_blank = __popc(blank & valid), rails = 0;
+    const unsigned n_blank = __popc(blank & valid);
+    unsigned rails = 0;
     // the outputs
     if (nv > 0) {
         unsigned o[4 * L];
@@ -342,28 +327,8 @@ __global__ __launch_bounds__(CD_THREADS) void cond_apply_kernel(const int8_t* __
                 if (b < nv * L) dst[b] = (int8_t)((o[b >> 2] >> (8 * (b & 3))) & 0xFFu);
         }
     }
-    // one count per workgroup: lanes by shuffles, waves through LDS, then one integer atomic per counter on a line of the
-    // slot's own
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        n_blank += __shfl_down(n_blank, d, 64);
-        rails += __shfl_down(rails, d, 64);
-    }
-    if ((t & 63) == 0) {
-        s_cnt[t >> 6][0] = n_blank;
-        s_cnt[t >> 6][1] = rails;
-    }
-    __syncthreads();
-    if (t == 0) {
-        unsigned a = 0, b = 0;
-        for (int wv = 0; wv < CD_WAVES; ++wv) {
-            a += s_cnt[wv][0];
-            b += s_cnt[wv][1];
-        }
-        unsigned long long* slot = count + (size_t)(blockIdx.x % CD_COUNT_SLOTS) * CD_COUNT_STRIDE;
-        if (a) atomicAdd(slot, (unsigned long long)a);
-        if (b) atomicAdd(slot + 1, (unsigned long long)b);
-    }
+    const unsigned counts[2] = {n_blank, rails};
+    sgx_count_publish<2, CD_WAVES>(counts, count);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -498,11 +463,9 @@ extern "C" int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type
     if (rc == SGX_OK && n_plan) rc = c->d_cond_plan.ensure(n_plan * sizeof(sgx_cond_entry));
     if (rc != SGX_OK) return rc;
     sgx_cond_entry* d_plan = c->d_cond_plan;
-    unsigned long long* d_cnt = c->d_small->cond_count;
-    unsigned long long* h_cnt = c->h_small->cond_count;
     SgxStage st(SGX_STAGE_COND_APPLY, (unsigned)tiles, "conditioning kernel failed: %s", out, sh.frames * (size_t)lanes);
     st.up = {d_plan, plan, n_plan * sizeof(sgx_cond_entry)};
-    st.count_into(h_cnt, d_cnt, sizeof(SgxSmall::cond_count));
+    unsigned long long* d_cnt = st.count(c);
     rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         cd_dispatch(sh.w, lanes, [&](auto W, auto L) {
             cond_apply_kernel<decltype(W)::value, decltype(L)::value><<<st.grid, CD_THREADS, 0, c->stream>>>(
@@ -510,7 +473,7 @@ extern "C" int sgx_if_condition(sgx_ctx* c, const sgx_if* rec, int32_t data_type
         });
     });
     if (rc != SGX_OK) return rc;
-    if (blanked_frames) *blanked_frames = sgx_sum_slots(h_cnt, CD_COUNT_SLOTS, CD_COUNT_STRIDE);
-    if (clipped) *clipped = sgx_sum_slots(h_cnt + 1, CD_COUNT_SLOTS, CD_COUNT_STRIDE);
+    if (blanked_frames) *blanked_frames = sgx_stage_count(c, 0);
+    if (clipped) *clipped = sgx_stage_count(c, 1);
     return SGX_OK;
 }

@@ -19,7 +19,8 @@
 //     side.  The kernel is templated on (LANES, D), every D from 2 to 16.
 //   * Taps are wave-uniform: scalar loads from d_small->fir_taps, [D][Lq / 4] pairs for a real record, [D][3][Lq / 4] for
 //     I/Q (re, im, -im).  All phases run over one range of steps, the union of the steps that hold a tap.
-//   * The sum over the phases, the rounding, the clip count and its fold are the header's (fir_plane_sums, fir_count_fold).
+//   * The sum over the phases, the rounding and the clip count are the header's (fir_plane_sums), the count's fold the stage
+//     counters' (sgx_count.h).
 #include "sgx_fir_dot4.h"
 
 #define DC_MAX_C ((SGX_DECIM_MAX_TAPS - 1) / 2)
@@ -59,7 +60,6 @@ __global__ __launch_bounds__(FIR_THREADS) void decim_kernel(const int8_t* __rest
     constexpr int NS_MAX = (TF + dc_lq(LANES, D, DC_MAX_C)) / W;
     typedef typename FirSlot<W>::type slot_t;
     __shared__ slot_t s_img[P * NS_MAX];
-    __shared__ unsigned s_cnt[FIR_THREADS / 64];
 
     const int ns = (TF + lq) / W;              // slots of a plane image: frames m0 - cq .. m0 + TF + lq - cq
     const long long base = ((long long)blockIdx.x * TF - cq) * P;   // its first byte in the record, a multiple of 16
@@ -75,7 +75,8 @@ __global__ __launch_bounds__(FIR_THREADS) void decim_kernel(const int8_t* __rest
     } else {
         for (int r = 0; r < 16 && o0 + r < n_out; ++r) y[o0 + r] = (int8_t)((out[r >> 2] >> ((r & 3) * 8)) & 0xFF);
     }
-    fir_count_fold(clipped, s_cnt, counts);
+    const unsigned count[1] = {clipped};
+    sgx_count_publish<1, FIR_THREADS / 64>(count, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,8 @@ static int ex_prepare(SegPlan* plan, int n_seg) {
 // The forward steps on every segment of the tile (EX_BARRIER: the caller's)
 #define EX_FORWARD(FOR_ITEMS) SEG_FORWARD(FOR_ITEMS, EX_BARRIER, buf, tw, M, g.log2m, EX_TILE_POINTS)
 
-// counts: EX_COUNT_SLOTS slots of (bins cut, segments cut, clipped outputs); cut_seg: per segment, or null
+// counts: the stage counters (sgx_count.h), zeroed: counters 0, 1, 2 take the bins cut, the segments cut and the clipped
+// outputs; cut_seg: per segment, or null
 __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
                                                             const cplx* __restrict__ tw, const double* __restrict__ win,
                                                             ExGeom g, unsigned long long* __restrict__ counts,
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __rest
     EX_LANES(q, EX_TILE_POINTS) ex_swap_item(buf + ((q >> g.log2m) << g.log2m), g.log2m, q & (M - 1));
     // the counters of the segments this tile owns: lanes by shuffles, one integer atomic per wave and counter on a line of
     // the slot's own (S <= 128: the first two waves)
-    unsigned long long* __restrict__ slot = counts + (size_t)(blockIdx.x % EX_COUNT_SLOTS) * EX_COUNT_STRIDE;
+    unsigned long long* __restrict__ slot = sgx_count_slot(counts);
     if (tid < EX_MAX_TILE_SEGMENTS) {
         unsigned bins = 0, segs = 0;
         if (tid < S && ex_owns(g, t, tid)) {
@@ -101,10 +102,8 @@ __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __rest
             segs = bins ? 1u : 0u;
             if (cut_seg) cut_seg[j0 + tid] = (uint16_t)bins;
         }
-        for (int d = 32; d > 0; d >>= 1) {
-            bins += __shfl_down(bins, d, 64);
-            segs += __shfl_down(segs, d, 64);
-        }
+        bins = sgx_wave_sum(bins);
+        segs = sgx_wave_sum(segs);
         if ((tid & 63) == 0 && bins) {
             atomicAdd(slot, (unsigned long long)bins);
             atomicAdd(slot + 1, (unsigned long long)segs);
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(EX_THREADS) void excise_kernel(const int8_t* __rest
                 if (pos + e < g.n) y[pos + e] = (int8_t)((o[e >> 2] >> (8 * (e & 3))) & 0xFFu);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) clipped += __shfl_down(clipped, d, 64);
+    clipped = sgx_wave_sum(clipped);
     if ((tid & 63) == 0 && clipped) atomicAdd(slot + 2, (unsigned long long)clipped);
 #undef EX_BARRIER
 #undef EX_LANES
@@ -313,10 +312,8 @@ extern "C" int sgx_if_excise(sgx_ctx* c, const sgx_if* rec, int32_t N, double th
     const cplx* d_tw = c->plan_excise.tw();
     const double* d_win = c->plan_excise.extra();
     uint16_t* d_cut = cut_per_segment ? c->d_excise_cut.get() : nullptr;
-    unsigned long long* d_cnt = c->d_small->excise_count;
-    unsigned long long* h_cnt = c->h_small->excise_count;
     SgxStage st(SGX_STAGE_EXCISE, (unsigned)g.tiles, "excision kernel failed: %s", out, rec->n);
-    st.count_into(h_cnt, d_cnt, sizeof(SgxSmall::excise_count));
+    unsigned long long* d_cnt = st.count(c);
     rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         excise_kernel<<<st.grid, EX_THREADS, lds, c->stream>>>(rec->d, r->d, d_tw, d_win, g, d_cnt, d_cut);
     });
@@ -330,8 +327,6 @@ extern "C" int sgx_if_excise(sgx_ctx* c, const sgx_if* rec, int32_t N, double th
             return SGX_E_HIP;
         }
     }
-    *info = sgx_excise_info{(int64_t)g.J, sgx_sum_slots(h_cnt, EX_COUNT_SLOTS, EX_COUNT_STRIDE),
-                            sgx_sum_slots(h_cnt + 1, EX_COUNT_SLOTS, EX_COUNT_STRIDE),
-                            sgx_sum_slots(h_cnt + 2, EX_COUNT_SLOTS, EX_COUNT_STRIDE)};
+    *info = sgx_excise_info{(int64_t)g.J, sgx_stage_count(c, 0), sgx_stage_count(c, 1), sgx_stage_count(c, 2)};
     return SGX_OK;
 }

@@ -4,7 +4,7 @@
 //   the chunk load, fir_steps, fir_round_clip, the tap checks and the tap-image packer      all five
 //   fir_split_planes (the register de-interleave into plane images)                          decimator, resampler
 //   fir_plane_sums (the sum over planes, the rounding, the clip count, the packing)          decimator, combiner
-//   fir_count_fold, FirLaunch, fir_dispatch, fir_check_shift, fir_run_counted (the clip area) decimator, resampler, combiner
+//   FirLaunch, fir_dispatch, fir_check_shift, fir_run_counted (the clip count of a launch)   decimator, resampler, combiner
 //
 // Formulation: v_dot4_i32_i8 on byte windows (DESIGN.md section 4.11 says why not the int8 matrix cores).  Each int16 tap
 // is two signed bytes, h = 256 hi + lo; the two byte filters accumulate separately and are combined as 256 acc_hi + acc_lo.
@@ -15,13 +15,14 @@
 // lane (a 16-byte store only when all 16 outputs exist, byte stores on the record's last partial group).  The store is
 // written out in each kernel: behind a helper the compiler packs the bytes before the branch and unpacks them again for
 // the byte stores, a different epilogue from the one the kernels have always had.
-// Clipped outputs: counted per lane on the value before the clip, folded over the wave by shuffles and over the workgroup
-// through LDS, one integer atomic per workgroup into one of FIR_COUNT_SLOTS padded slots of SgxSmall::fir_clip.
+// Clipped outputs: counted per lane on the value before the clip; the kernel hands its lanes' counts to sgx_count_publish
+// (sgx_count.h), counter 0 of the stage counters.
 #pragma once
 #include <limits.h>
 
 #include <type_traits>
 
+#include "sgx_count.h"
 #include "sgx_stage.h"
 
 #define FIR_THREADS 256
@@ -207,19 +208,6 @@ __device__ __forceinline__ void fir_plane_sums(const typename FirSlot<16 / LANES
     }
 }
 
-// The lanes' counts of clipped outputs into the workgroup's slot of `counts`; s_cnt: FIR_THREADS / 64 words of LDS
-__device__ __forceinline__ void fir_count_fold(unsigned clipped, unsigned* s_cnt, unsigned long long* __restrict__ counts) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) clipped += __shfl_down(clipped, d, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = clipped;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < FIR_THREADS / 64; ++w) t += s_cnt[w];
-        if (t) atomicAdd(&counts[(size_t)(blockIdx.x % FIR_COUNT_SLOTS) * FIR_COUNT_STRIDE], (unsigned long long)t);
-    }
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------
 // The refusals of the taps' magnitudes (no device needed): every tap splits into two signed bytes, and the sum stays in int32
 static inline int fir_check_taps(const int16_t* taps, int32_t n_taps) {
@@ -317,17 +305,15 @@ static inline void fir_dispatch(int value, F&& f) {
     f(std::integral_constant<int, LO>());
 }
 
-// sgx_stage_run of a stage whose kernel counts its clipped outputs: the one clip area of the context (a stage waits before
-// it returns, so one call owns it at a time) is the stage's counters, launch() runs with l.y and l.counts set, and the
-// total goes to *clipped (may be null)
+// sgx_stage_run of a stage whose kernel counts its clipped outputs, counter 0 of the stage counters: launch() runs with l.y
+// and l.counts set, and the total goes to *clipped (may be null)
 template <typename Launch>
 static int fir_run_counted(sgx_ctx* c, SgxStage& st, FirLaunch& l, int64_t* clipped, Launch launch) {
-    l.counts = c->d_small->fir_clip;
-    st.count_into(c->h_small->fir_clip, l.counts, sizeof(SgxSmall::fir_clip));
+    l.counts = st.count(c);
     const int rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         l.y = r->d;
         launch();
     });
-    if (rc == SGX_OK && clipped) *clipped = sgx_sum_slots(c->h_small->fir_clip, FIR_COUNT_SLOTS, FIR_COUNT_STRIDE);
+    if (rc == SGX_OK && clipped) *clipped = sgx_stage_count(c, 0);
     return rc;
 }

@@ -15,6 +15,7 @@
 
 #include "sgx.h"
 #include "sgx_check.h"   // sgx_set_error, SGX_CHECK_ARG, SGX_VERSION_STR: all that the HIP-free host files need
+#include "sgx_count.h"   // SGX_COUNT_SLOTS, SGX_COUNT_STRIDE: the layout of SgxSmall::stage_count
 
 #define SGX_HIP(call)                                                                          \
     do {                                                                                       \
@@ -112,37 +113,15 @@ void ex_tables(int n_seg, cplx* tw, double* win);
 // sgx_iq.hip: the padded length of one polyphase branch of the longest filter (cp = 64, d up to 64, rounded up to 8)
 #define SGX_IQ_LP_MAX 136
 
-// sgx_requant.hip: the fixed grid of the statistics pass (the float sums are reproducible because it is fixed), its loads
-// in flight per lane, and the counters the quantiser spreads its per-wave counts of clipped outputs over
+// sgx_requant.hip: the fixed grid of the statistics pass (the float sums are reproducible because it is fixed) and its loads
+// in flight per lane
 #define RQ_STATS_BLOCKS 2048
 #define RQ_STATS_UNROLL 4
-#define RQ_CLIP_SLOTS 256
-#define RQ_CLIP_STRIDE 32    // words between two counters: one 128-byte line each
-
-// sgx_cond.hip: the slots the apply kernel spreads its per-workgroup counts over; a slot is one 128-byte line that holds
-// the blanked frames (word 0) and the elements on +-127 (word 1)
-#define CD_COUNT_SLOTS 256
-#define CD_COUNT_STRIDE 16   // 64-bit words between two slots
-
-// sgx_unpack.hip: the slots the unpacker spreads its per-workgroup code counts over; a slot is one 128-byte line that holds
-// the 16 counters
-#define UP_COUNT_SLOTS 256
-#define UP_COUNT_STRIDE 16   // 64-bit words between two slots
-
-// sgx_fir_dot4.h: the slots the decimator, the resampler and the combiner spread their per-workgroup counts of clipped
-// outputs over, one 128-byte line each
-#define FIR_COUNT_SLOTS 256
-#define FIR_COUNT_STRIDE 16   // 64-bit words between two slots
 
 // sgx_array.hip: the copies of rho the statistics kernel spreads its per-workgroup sums over, each of AR_SUM_VALUES int64
 // values (A^2 K lanes <= 8 x 64 x 2 of them used)
 #define AR_SUM_SLOTS 8
 #define AR_SUM_VALUES 1024
-
-// sgx_excise.hip: the slots the excision kernel spreads its counts over; a slot is one 128-byte line that holds the bins
-// cut (word 0), the segments with a cut bin (word 1) and the clipped outputs (word 2)
-#define EX_COUNT_SLOTS 256
-#define EX_COUNT_STRIDE 16   // 64-bit words between two slots
 
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
 // sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
@@ -352,20 +331,12 @@ struct SgxSmall {
     // sgx_fir_dot4.h: (hi, lo) tap dwords of one sgx_if_filter, sgx_if_from_iq, sgx_if_decimate, sgx_if_resample or
     // sgx_if_combine call
     alignas(16) unsigned fir_taps[2 * ((SGX_FILTER_MAX_TAPS + 30) / 16) * 4];
-    // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass, and
-    // the quantiser's counters of outputs on +-127
+    // sgx_requant.hip: one partial (sum, sum of squares, non-finite count, max) per workgroup of the statistics pass
     alignas(256) unsigned long long requant_part[RQ_STATS_BLOCKS * 4];
-    alignas(256) unsigned requant_clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE];
-    // sgx_cond.hip: the apply kernel's counters
-    alignas(256) unsigned long long cond_count[CD_COUNT_SLOTS * CD_COUNT_STRIDE];
-    // sgx_unpack.hip: the unpacker's code counters
-    alignas(256) unsigned long long unpack_count[UP_COUNT_SLOTS * UP_COUNT_STRIDE];
-    // sgx_fir_dot4.h: the counters of clipped outputs of the decimator, the resampler or the combiner
-    alignas(256) unsigned long long fir_clip[FIR_COUNT_SLOTS * FIR_COUNT_STRIDE];
+    // sgx_count.h: the counters of the stage that runs - outputs on the rails, blanked frames, codes, cut bins
+    alignas(256) unsigned long long stage_count[SGX_COUNT_SLOTS * SGX_COUNT_STRIDE];
     // sgx_array.hip: the statistics kernel's copies of rho (int64 values, added modulo 2^64)
     alignas(256) unsigned long long array_sum[AR_SUM_SLOTS * AR_SUM_VALUES];
-    // sgx_excise.hip: the excision kernel's counters
-    alignas(256) unsigned long long excise_count[EX_COUNT_SLOTS * EX_COUNT_STRIDE];
 };
 static_assert(2 * 2 * (SGX_IQ_LP_MAX / 4) <= sizeof(SgxSmall::fir_taps) / sizeof(unsigned),
               "the two branches of sgx_iq.hip fit the tap staging too");

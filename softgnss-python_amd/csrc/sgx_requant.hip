@@ -16,8 +16,8 @@
 //                         pattern, so they do not depend on the denormal mode.
 //   requant_kernel        a lane makes 16 output bytes from 2 (int16) or 4 (float32) 16-byte loads, packs them in registers
 //                         and issues one 16-byte store; the lane that holds the record's last partial group loads and stores
-//                         element by element.  Nothing outside the record is read.  Outputs on +-127 are counted: folded
-//                         over the workgroup, one integer atomic per workgroup into one of RQ_CLIP_SLOTS counters.
+//                         element by element.  Nothing outside the record is read.  Outputs on +-127 are counted: counter 0
+//                         of the stage counters (sgx_count.h), one integer atomic per workgroup.
 #include <math.h>
 
 #include "sgx_stage.h"
@@ -187,11 +187,11 @@ __device__ __forceinline__ unsigned rq_on_rails(unsigned w) {
     return n;
 }
 
-// n: elements of the record = bytes of y.  clip[RQ_CLIP_SLOTS * RQ_CLIP_STRIDE]: zeroed; counter i of the outputs on +-127
-// is word i * RQ_CLIP_STRIDE.
+// n: elements of the record = bytes of y.  clip: the stage counters, zeroed; counter 0 takes the outputs on +-127.
 template <int DT>
 __global__ __launch_bounds__(RQ_THREADS) void requant_kernel(const int8_t* __restrict__ x, int8_t* __restrict__ y,
-                                                             unsigned long long n, RqGain g, unsigned* __restrict__ clip) {
+                                                             unsigned long long n, RqGain g,
+                                                             unsigned long long* __restrict__ clip) {
     constexpr int W = RqType<DT>::W;
     const unsigned long long e0 = ((unsigned long long)blockIdx.x * RQ_THREADS + threadIdx.x) * 16;
     unsigned rails = 0;
@@ -231,18 +231,8 @@ __global__ __launch_bounds__(RQ_THREADS) void requant_kernel(const int8_t* __res
             }
         }
     }
-    // one count per workgroup: lanes by shuffles, waves through LDS, then one integer atomic on a counter with a 128-byte
-    // line to itself (per-wave atomics on adjacent words serialised on their lines and bound the kernel)
-    __shared__ unsigned s_rails[RQ_THREADS / 64];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) rails += __shfl_down(rails, d, 64);
-    if ((threadIdx.x & 63) == 0) s_rails[threadIdx.x >> 6] = rails;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-        for (int w = 0; w < RQ_THREADS / 64; ++w) t += s_rails[w];
-        if (t) atomicAdd(&clip[(blockIdx.x % RQ_CLIP_SLOTS) * RQ_CLIP_STRIDE], t);
-    }
+    const unsigned count[1] = {rails};
+    sgx_count_publish<1, RQ_THREADS / 64>(count, clip);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -386,11 +376,9 @@ extern "C" int sgx_if_requantize(sgx_ctx* c, const sgx_if* rec, int32_t data_typ
     const unsigned long long blocks = ((unsigned long long)n + RQ_TILE - 1) / RQ_TILE;
     rc = sgx_stage_one_launch(blocks, "bad argument: a record of %zu elements is beyond one launch of the requantiser", n);
     if (rc != SGX_OK) return rc;
-    unsigned* d_clip = c->d_small->requant_clip;
-    unsigned* h_clip = c->h_small->requant_clip;
     const RqGain g = {mult, (1 << shift) >> 1, shift, scale};
     SgxStage st(SGX_STAGE_REQUANT, (unsigned)blocks, "requantiser kernel failed: %s", out, n);
-    st.count_into(h_clip, d_clip, sizeof(SgxSmall::requant_clip));
+    unsigned long long* d_clip = st.count(c);
     rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         if (data_type == SGX_DT_INT16) {
             requant_kernel<SGX_DT_INT16><<<st.grid, RQ_THREADS, 0, c->stream>>>(rec->d, r->d, n, g, d_clip);
@@ -399,6 +387,6 @@ extern "C" int sgx_if_requantize(sgx_ctx* c, const sgx_if* rec, int32_t data_typ
         }
     });
     if (rc != SGX_OK) return rc;
-    if (n_clipped) *n_clipped = sgx_sum_slots(h_clip, RQ_CLIP_SLOTS, RQ_CLIP_STRIDE);
+    if (n_clipped) *n_clipped = sgx_stage_count(c, 0);
     return SGX_OK;
 }

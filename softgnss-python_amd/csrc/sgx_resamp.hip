@@ -22,8 +22,8 @@
 //     (sgx_fir_dot4.h), M chunks per slot of every plane.  Lanes write and read consecutive slots: no bank conflict.
 //   * Taps are wave-uniform: scalar loads from d_small->fir_taps, [L][M][lq / 4] pairs.  All streams run over one range of
 //     steps, the union of the steps that hold a tap; a step is 16 taps, so the default 24 taps per stream (M = 1) cost 32.
-//   * Clipped outputs: counted per lane on the value before the clip (in 32 bits, see the kernel) and folded by the header's
-//     fir_count_fold.
+//   * Clipped outputs: counted per lane on the value before the clip (in 32 bits, see the kernel), counter 0 of the stage
+//     counters (sgx_count.h).
 //
 // What bounds it: vector-ALU issue, not HBM.  Per output byte the kernel reads 1 / L input byte and writes one, 0.33 ms at
 // the copy rate for 1.4 GB of output at L = 10; it takes 1.3 ms there.  A step is 16 taps, so the default 24 taps of a stream
@@ -71,7 +71,6 @@ __global__ __launch_bounds__(FIR_THREADS) void resamp_kernel(const int8_t* __res
                                                              const uint2* __restrict__ taps, int M, int lq, int cq, int q_lo,
                                                              int q_hi, int shift, unsigned long long* __restrict__ counts) {
     __shared__ uint4 s_img[rs_img_slots(L)];
-    __shared__ unsigned s_cnt[FIR_THREADS / 64];
 
     const int ns = (FIR_TILE + lq) / 16;       // slots of a plane image: plane samples i0 - cq .. i0 + FIR_TILE + lq - cq
     const long long base = ((long long)blockIdx.x * FIR_TILE - cq) * M;   // its first byte in the record, a multiple of 16
@@ -136,7 +135,8 @@ __global__ __launch_bounds__(FIR_THREADS) void resamp_kernel(const int8_t* __res
             for (int b = 0; b < 16 && 16 * s + b < left; ++b) at[b] = (int8_t)((o[b >> 2] >> ((b & 3) * 8)) & 0xFF);
         }
     }
-    fir_count_fold(clipped, s_cnt, counts);
+    const unsigned count[1] = {clipped};
+    sgx_count_publish<1, FIR_THREADS / 64>(count, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------

@@ -3,9 +3,11 @@
 // (sgx_decim.hip), the resampler (sgx_resamp.hip), the multi-antenna combiner (sgx_array.hip) and the swept-interference
 // excision (sgx_excise.hip; what its kernel shares with the record monitor's is in sgx_seg_fft.h, not here).  Each of their
 // fourteen entry points keeps its own argument checks, in its own order and with its own messages, and its launch; what
-// comes around the launch is here once
+// comes around the launch is here once, and so is the host side of the one counter area that the eight counting entry
+// points share (SgxStage::count, sgx_stage_count; the device side is sgx_count.h)
 // ("The stage tail").
 #pragma once
+#include "sgx_count.h"
 #include "sgx_internal.h"
 
 // Opening the input, once the stage's own checks of its shape have passed: wait until the first `bytes` of a record that
@@ -47,6 +49,12 @@ struct SgxStage {
         down = {mirror, device, bytes};
         counters = device;
     }
+    // The stage's kernel counts (sgx_count.h): the context's one counter area is the stage's counters.  A stage waits
+    // before it returns, so one call owns the area at a time.  Returns the device side, for the kernel.
+    unsigned long long* count(sgx_ctx* c) {
+        count_into(c->h_small->stage_count, c->d_small->stage_count, sizeof(SgxSmall::stage_count));
+        return c->d_small->stage_count;
+    }
 };
 
 // The tail of an entry point, on the context's stream: the output record is allocated, the stage's timing slot and the
@@ -87,10 +95,9 @@ static int sgx_stage_run(sgx_ctx* c, const SgxStage& s, Launch launch) {
     return SGX_OK;
 }
 
-// The total of `count` counters that lie `stride` words apart (the padded slots a kernel spreads its atomics over)
-template <typename T>
-static inline int64_t sgx_sum_slots(const T* h, int count, int stride) {
+// Counter k of the stage that has just run (SgxStage::count): the total over the slots of the mirror
+static inline int64_t sgx_stage_count(const sgx_ctx* c, int k) {
     int64_t total = 0;
-    for (int i = 0; i < count; ++i) total += (int64_t)h[(size_t)i * stride];
+    for (int i = 0; i < SGX_COUNT_SLOTS; ++i) total += (int64_t)c->h_small->stage_count[(size_t)i * SGX_COUNT_STRIDE + k];
     return total;
 }

@@ -19,8 +19,8 @@
 //
 // Code counts: a lane adds 1 << 4 code into a nibble-packed word for 8 outputs at a time, spreads the nibbles into two
 // byte-packed 64-bit accumulators (even and odd codes; at most 16 UP_ITERS = 64 per byte) and keeps those over its rounds.
-// At the end the 2^b counts are folded over the wave by shuffles, over the workgroup through LDS, and 2^b lanes add them
-// into one of UP_COUNT_SLOTS slots of one 128-byte line each: 2^b integer atomics per UP_TILE output bytes.
+// At the end the 2^b counts are counters 0 .. 2^b - 1 of the stage counters (sgx_count.h): 2^b integer atomics per UP_TILE
+// output bytes.
 #include <type_traits>
 
 #include "sgx_stage.h"
@@ -29,7 +29,6 @@
 #define UP_ITERS 4
 #define UP_TILE (UP_THREADS * 16 * UP_ITERS)   // output bytes per workgroup
 static_assert(16 * UP_ITERS < 256, "a lane's count of one code fits a byte");
-static_assert(UP_COUNT_STRIDE >= 16, "a slot holds the 16 counters");
 
 typedef unsigned long long up_u64;
 
@@ -89,23 +88,13 @@ __device__ __forceinline__ void up_slow_chunk(const uint8_t* __restrict__ x, uin
     }
 }
 
-// counts[UP_COUNT_SLOTS * UP_COUNT_STRIDE]: zeroed; counter c of slot i is word i * UP_COUNT_STRIDE + c
+// counts: the stage counters, zeroed; counter c takes the lanes' counts of code c, bytes of E and O
 template <int NC>
-__device__ __forceinline__ void up_publish(up_u64 E, up_u64 O, up_u64* __restrict__ counts) {
-    __shared__ unsigned s_cnt[UP_THREADS / 64][NC];
+__device__ __forceinline__ void up_count_codes(up_u64 E, up_u64 O, up_u64* __restrict__ counts) {
+    unsigned v[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        unsigned v = (unsigned)(((c & 1) ? O : E) >> (8 * (c >> 1))) & 0xFFu;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NC) {
-        unsigned t = 0;
-        for (int w = 0; w < UP_THREADS / 64; ++w) t += s_cnt[w][threadIdx.x];
-        if (t) atomicAdd(&counts[(size_t)(blockIdx.x % UP_COUNT_SLOTS) * UP_COUNT_STRIDE + threadIdx.x], (up_u64)t);
-    }
+    for (int c = 0; c < NC; ++c) v[c] = (unsigned)(((c & 1) ? O : E) >> (8 * (c >> 1))) & 0xFFu;
+    sgx_count_publish<NC, UP_THREADS / 64>(v, counts);
 }
 
 template <int B, int W, int K>
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(UP_THREADS) void unpack_kernel(const uint8_t* __res
             up_slow_chunk(x, y, o0, n_out, a, E, O);    // the record's last partial group
         }
     }
-    up_publish<(1 << B)>(E, O, counts);
+    up_count_codes<(1 << B)>(E, O, counts);
 }
 
 __global__ __launch_bounds__(UP_THREADS) void unpack_any_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ y,
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(UP_THREADS) void unpack_any_kernel(const uint8_t* _
         const up_u64 o0 = 16 * (chunk0 + (up_u64)it * UP_THREADS);
         if (o0 < n_out) up_slow_chunk(x, y, o0, n_out, a, E, O);
     }
-    up_publish<16>(E, O, counts);
+    up_count_codes<16>(E, O, counts);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -311,7 +300,6 @@ extern "C" int sgx_if_unpack(sgx_ctx* c, const sgx_if* rec, int32_t bits, int32_
     l.grid = (unsigned)tiles;
     l.x = reinterpret_cast<const uint8_t*>(rec->d);
     l.n_out = n_out;
-    l.counts = c->d_small->unpack_count;
     memset(&l.a, 0, sizeof(l.a));
     memcpy(l.a.tab, table, (size_t)1 << bits);
     l.a.W = W, l.a.K = K, l.a.mask = (1u << bits) - 1u;
@@ -324,15 +312,14 @@ extern "C" int sgx_if_unpack(sgx_ctx* c, const sgx_if* rec, int32_t bits, int32_
             l.a.sh[k >> 3] |= (up_u64)s << (8 * (k & 7));
         }
     }
-    up_u64* h_count = c->h_small->unpack_count;
     SgxStage st(SGX_STAGE_UNPACK, l.grid, "unpacker kernel failed: %s", out, n_out);
-    st.count_into(h_count, l.counts, sizeof(SgxSmall::unpack_count));
+    l.counts = st.count(c);
     rc = sgx_stage_run(c, st, [&](sgx_if* r) {
         l.y = reinterpret_cast<uint8_t*>(r->d);
         up_launch(bits, l);
     });
     if (rc != SGX_OK) return rc;
     if (code_counts)
-        for (int k = 0; k < 16; ++k) code_counts[k] = sgx_sum_slots(h_count + k, UP_COUNT_SLOTS, UP_COUNT_STRIDE);
+        for (int k = 0; k < 16; ++k) code_counts[k] = sgx_stage_count(c, k);
     return SGX_OK;
 }

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(1024) void wf_segment_kernel(const int8_t* __restri
         part = __builtin_amdgcn_sdot4((int)v.w, 0x01010101, part, false);
     });
     __syncthreads();
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_down(part, d, 64);
+    part = sgx_wave_sum(part);
     if ((tid & 63) == 0) atomicAdd(&s_sum, part);              // integers: any order gives the same sum
     __syncthreads();
     const int sum = s_sum;
@@ -165,11 +165,9 @@ __global__ __launch_bounds__(256) void wf_stats_kernel(const int8_t* __restrict_
                 }
             }
         }
-        for (int d = 32; d > 0; d >>= 1) {
-            s1 += __shfl_down(s1, d, 64);
-            s2 += __shfl_down(s2, d, 64);
-            s4 += __shfl_down(s4, d, 64);
-        }
+        s1 = sgx_wave_sum(s1);
+        s2 = sgx_wave_sum(s2);
+        s4 = sgx_wave_sum(s4);
         if ((tid & 63) == 0) {
             atomicAdd(&mom[j * 4 + 1], (unsigned long long)s1);  // (two's complement: the sum of the signed values)
             atomicAdd(&mom[j * 4 + 2], s2);

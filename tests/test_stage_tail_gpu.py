@@ -7,15 +7,21 @@ carry over into the next one.  What the stages compute is the business of their 
 Records are two tiles plus five bytes (elements, frames) of the stage, as its *_tile() reports it; the notch has the
 converter's tile, and the converter takes one byte more, because an I/Q record holds whole pairs.
 
-The decimator, the resampler and the combiner count their clipped outputs in ONE area of the context (csrc/sgx_fir_dot4.h:
-fir_run_counted), so the last test runs them one after the other on one context and holds every count and every byte
-against the stage's spec.  Run with -m gpu."""
+All eight counting entry points - requantize, condition, unpack, decimate, resample, combine, combine_blocks, excise_record
+- count in ONE area of the context (csrc/sgx_count.h, SgxStage::count), so the last test runs every one of them behind
+every other on one context and holds every count and every byte against the stage's spec.  Run with -m gpu."""
 import numpy as np
 import pytest
 
+import array_block_spec
 import array_spec
+import cond_spec
 import decim_spec
+import excise_cases
+import excise_spec
+import requant_spec
 import resamp_spec
+import unpack_spec
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -183,17 +189,124 @@ def clip_area_cases():
     return cases
 
 
+def as_bytes(x):
+    return np.frombuffer(np.ascontiguousarray(x).tobytes(), dtype=np.int8)
+
+
+def reads(call, *names):
+    """call(context, record) -> a record, as (context, record) -> (the record, its counters `names`)"""
+    def wrapped(c, r):
+        out = call(c, r)
+        return out, tuple(int(getattr(out, k)) for k in names)
+    return wrapped
+
+
+def counter_area_cases():
+    """(name, input bytes, call on a context and a record -> (record, its counters), (spec bytes, spec counters)) of all
+    eight counting entry points, which share ONE counter area (csrc/sgx_count.h): the three cases of clip_area_cases() as
+    they stand, and one case each of the requantiser (clipped), the conditioning stage (blanked, clipped), the unpacker at
+    2 and at 4 bits (4 and 16 code counts), the block combiner (clipped) and the excision (bins_cut, segments_cut, clipped)
+    on outputs of three tiles plus 17 bytes (one more for I/Q; the excision: three tiles of its plan at N = 64 and a
+    little of the next, excise_cases.tile_span).  Then one case per shape of the publish with more workgroups than the
+    256 slots of the area, so that a slot takes the atomics of two workgroups: 257 tiles plus 17 bytes of the requantiser
+    (one counter), the conditioning stage (two), the 4-bit unpacker (sixteen) and the excision (per wave).  Expected bytes
+    and counters come from the stage's spec module alone, and on those alone: every counter of every case is above zero
+    but the resampling's, which is zero; the excision's cases keep excise_spec.MARGIN as tests/excise_cases.py asks."""
+    n = pkg()._native
+    rng = np.random.default_rng(11)
+    cases = [(name, x, reads(call, "clipped"), (y, (count,))) for name, x, call, (y, count) in clip_area_cases()]
+
+    def requantize(tag, tiles):
+        x = rng.integers(-100, 101, tiles * n.requant_tile() + 17).astype("<i2")
+        y = requant_spec.quantise(as_bytes(x), np.int16, 3, 1)                 # |x| >= 85 lands on a rail
+        call = reads(lambda c, r: c.requantize(r, np.int16, mult=3, shift=1), "clipped")
+        return ("requantize" + tag, as_bytes(x), call, (y, (int(np.count_nonzero(np.abs(y.astype(np.int16)) == 127)),)))
+
+    def condition(tag, tiles):
+        x = rng.integers(-100, 101, tiles * n.cond_tile() + 17).astype("<i2")
+        plan = np.array([PLAN_ENTRY] * (-(-x.size // BLOCK)), dtype=cond_spec.PLAN_DTYPE)
+        y, blanked, clipped = cond_spec.condition(as_bytes(x), np.int16, 1, BLOCK, plan, 0)
+        call = reads(lambda c, r: c.condition(r, np.int16, 1, BLOCK, plan, 0), "blanked", "clipped")
+        return ("condition" + tag, as_bytes(x), call, (y, (blanked, clipped)))
+
+    def unpack(tag, bits, tiles):
+        # one field of every byte, so that any number of bytes is whole frames: an output per input byte
+        frame, first = 8 // bits, 1
+        b = rng.integers(0, 256, tiles * n.unpack_tile() + 17).astype(np.uint8)
+        table = unpack_spec.table(bits)
+        y = unpack_spec.unpack(b, bits, table, 0, frame, first, 1)
+        counts = unpack_spec.code_counts(b, bits, 0, frame, first, 1)
+        assert not counts[1 << bits:].any()
+        def call(c, r):
+            out = c.unpack(r, bits, table, frame=frame, first=first)
+            return out, tuple(int(v) for v in out.code_counts)
+        return ("unpack%d%s" % (bits, tag), as_bytes(b), call, (y, tuple(int(v) for v in counts[:1 << bits])))
+
+    def combine_blocks():
+        n_out = 3 * n.combine_tile() + 18                                      # two blocks of I/Q frames
+        x = rng.integers(-100, 101, 3 * n_out).astype(np.int8)
+        B = n.ARRAY_BLOCK_UNIT
+        h = rng.integers(-3000, 3001, (-(-(n_out // 2) // B), 3, 3, 2)).astype(np.int16)
+        y, count = array_block_spec.combine_blocks(x, h, B, 6, 2, 3)
+        return ("combine_blocks", x, reads(lambda c, r: c.combine_blocks(r, 2, 3, h, B, 6), "clipped"), (y, (count,)))
+
+    def excise(tag, tiles):
+        # a strong line under noise that saturates, as the "rails" cases of tests/excise_cases.py: with the line cut,
+        # samples on a rail move beyond it
+        m = excise_cases.tile_span(64, tiles)
+        x = excise_cases.to_int8(80.0 * np.cos(2.0 * np.pi * 0.2031 * np.arange(m)) + excise_cases.noise(rng, m, 60.0))
+        y, info = excise_spec.excise(x, 64, 8.0, 3, margins=True)
+        assert info["margin_compare"] >= excise_spec.MARGIN and info["margin_round"] >= excise_spec.MARGIN, info
+        def call(c, r):
+            out, got = c.excise_record(r, 64, 8.0, 3)
+            return out, (got["bins_cut"], got["segments_cut"], got["clipped"])
+        return ("excise" + tag, x, call, (y, (info["bins_cut"], info["segments_cut"], info["clipped"])))
+
+    cases += [requantize("", 3), condition("", 3), unpack("", 2, 3), unpack("", 4, 3), combine_blocks(), excise("", 3),
+              requantize("_257", 257), condition("_257", 257), unpack("_257", 4, 257), excise("_257", 257)]
+    sizes = {"requantize": 3 * n.requant_tile() + 17, "condition": 3 * n.cond_tile() + 17, "unpack2": 3 * n.unpack_tile() + 17,
+             "unpack4": 3 * n.unpack_tile() + 17, "combine_blocks": 3 * n.combine_tile() + 18,
+             "requantize_257": 257 * n.requant_tile() + 17, "condition_257": 257 * n.cond_tile() + 17,
+             "unpack4_257": 257 * n.unpack_tile() + 17}
+    for name, x, _, (y, counts) in cases:
+        assert y.size == sizes.get(name, y.size), (name, y.size)
+        assert all(v == 0 for v in counts) if name == "resample" else all(v > 0 for v in counts), (name, counts)
+    assert [len(counts) for _, _, _, (_, counts) in cases] == [1, 1, 1, 1, 2, 4, 16, 1, 3, 1, 2, 16, 3]
+    return cases
+
+
+def every_ordered_pair(n):
+    """A walk over 0 .. n - 1 on which every ordered pair (a, b), a == b included, occurs once as (a stop, the next stop):
+    an Euler circuit of the complete directed graph with loops, n^2 + 1 stops (Hierholzer)."""
+    left = [list(range(n)) for _ in range(n)]
+    stack, walk = [0], []
+    while stack:
+        if left[stack[-1]]:
+            stack.append(left[stack[-1]].pop())
+        else:
+            walk.append(stack.pop())
+    walk.reverse()
+    assert sorted(zip(walk, walk[1:])) == [(a, b) for a in range(n) for b in range(n)]
+    return walk
+
+
 def test_the_fir_stages_share_one_clip_area_and_each_count_is_its_own(ctx):
-    dec, res, com = clip_area_cases()
-    for name, x, call, (want, count) in (dec, res, com, res):
+    """Every stage that counts shares one counter area, so a call could read what the call before it left there.  On one
+    context ALL ordered pairs (first, second) of the thirteen cases of counter_area_cases() run, a case behind itself
+    included: the calls follow a walk on which every pair occurs once as neighbours, 170 calls, and every call's record
+    equals its spec in bytes and every one of its counters the spec's - among them each stage with one counter behind the
+    4-bit unpacker, which fills all 16 words of a slot, and behind the excision, which fills three."""
+    cases = counter_area_cases()
+    for i in every_ordered_pair(len(cases)):
+        name, x, call, (want, counts) = cases[i]
         rec = ctx.upload(x)
         try:
-            out = call(ctx, rec)
+            out, got = call(ctx, rec)
         finally:
             rec.free()
         try:
-            print(name, "clipped", out.clipped, "spec", count)
-            assert out.clipped == count, (name, out.clipped, count)
+            print(name, "counters", got, "spec", counts)
+            assert tuple(got) == tuple(counts), (name, got, counts)
             assert out.download().tobytes() == want.tobytes(), name
         finally:
             out.free()
