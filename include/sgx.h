@@ -519,6 +519,41 @@ int sgx_track_replay(sgx_ctx* c, const sgx_if* rec, int64_t rec_file_offset, con
                      int32_t n_taps, double* out);
 int sgx_replay_timing(sgx_ctx* c, float* kernel_ms, float* device_ms);
 
+/* ---- strong-signal cancellation: tracked channels subtracted from a record (no reference counterpart) ---------------
+ * A C/A code lies only about 24 dB under another one, so a strong satellite's cross-correlation peaks stand above a weak
+ * satellite's own peak however long the search integrates.  Once the strong channels are tracked, their blocks are on
+ * record (sgx_replay_state) and the prompt sums give each block's amplitude and phase: the signals are rebuilt and
+ * subtracted, and the new record is searched and tracked like any other.  For sample i < blk of block k < ms_done[c] of
+ * channel c, with the block's state (start, blk, rem_code, rem_carr, step, carr_freq) and its amplitude pair (aI, aQ):
+ *   arg_i = carr_freq 2.0 pi (i / fs) + rem_carr,  t_i = linspace(rem_code, blk step + rem_code, blk, endpoint=False)[i],
+ *   chip_i = code[(ceil(t_i) - 1) mod 1023],  s_c = chip_i (aI sin(arg_i) + aQ cos(arg_i))
+ * v[n] = x[n] - sum_c s_c[n] at file position n = start + i, channels in channel order; y[n] = clip(rint(v[n]), -127, 127),
+ * round half to even, where at least one block covers n, and y[n] = x[n] elsewhere (so -128 stays -128 there).  clipped:
+ * the covered samples whose rint(v) lay outside [-127, 127].  tests/cancel_spec.py restates all of it in numpy.
+ *
+ * sgx_cancel_design: the amplitude pairs amp[n_ch][ms][2] from the series and the state; exact host code, needs no GPU.
+ * p_j = 2 (I_P, Q_P)[j] / blk_j; (aI, aQ)_k is the mean, added in ascending j, of d p_j over the blocks j < ms_done[c] with
+ * |j - k| <= (smooth - 1) / 2, d = sign(pI_j pI_k + pQ_j pQ_k) with 0 counting as +1 (the data-bit sign of block j against
+ * block k).  smooth is odd, 1 .. 41; blocks k >= ms_done[c] and channels that are off hold 0.
+ *
+ * sgx_if_cancel: a resident int8 record (a streaming record is waited for, as sgx_track_replay) -> a NEW record of the same
+ * length (sgx_if_free); the input is not written.  It runs sgx_replay_state itself and hands its codes back unchanged.  Every
+ * output byte is written once by one lane and the channels are subtracted in channel order: two calls give the same bytes.
+ * SGX_E_ARG, before anything is launched or written, for a NULL pointer, n_ch outside 1 .. 32, a data_type other than
+ * SGX_DT_INT8, an amplitude that is not finite (all n_ch x ms pairs are looked at), an ms_done entry outside [0, ms], an empty
+ * record, a record on another device.
+ * sgx_cancel_host: the same work sample by sample with libm on the host, into the caller's y[n]; x is the record, the
+ * bytes from rec_file_offset on.  Needs no GPU.  sgx_cancel_timing: HIP-event time of the last sgx_if_cancel's kernel. */
+int sgx_cancel_design(const double* series, const sgx_replay_block* state, int32_t n_ch, int32_t ms, const int32_t* ms_done,
+                      int32_t smooth, double* amp);
+int sgx_if_cancel(sgx_ctx* c, const sgx_if* rec, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
+                  const int32_t* ms_done, const double* series, int32_t data_type, const double* amp, sgx_if** out,
+                  int64_t* clipped);
+int sgx_cancel_host(const sgx_settings* s, const int8_t* x, size_t n, int64_t rec_file_offset, const sgx_chan_init* ch,
+                    int32_t n_ch, int32_t ms, const int32_t* ms_done, const double* series, int32_t data_type,
+                    const double* amp, int8_t* y, int64_t* clipped);
+int sgx_cancel_timing(sgx_ctx* c, float* kernel_ms);
+
 /* ---- narrowband interference excision ahead of acquisition (no reference counterpart: initialize.py:330-417 only plots
  * the spectrum a continuous-wave line shows up in) ----------------------------------------------------------------------
  * Opt-in.  A resident int8 record goes through a zero-phase integer FIR and comes out as a NEW int8 record of the same

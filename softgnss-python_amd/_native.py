@@ -180,6 +180,12 @@ _PROTOS = {
     "sgx_replay_state": (C.c_int, [C.POINTER(Settings), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
     "sgx_track_replay": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P]),
     "sgx_replay_timing": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sgx_cancel_design": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "sgx_if_cancel": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.POINTER(_P),
+                                C.POINTER(C.c_int64)]),
+    "sgx_cancel_host": (C.c_int, [C.POINTER(Settings), _P, C.c_size_t, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P,
+                                  C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
+    "sgx_cancel_timing": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sgx_notch_design": (C.c_int, [C.POINTER(Settings), _P, _P, C.c_int32, C.c_double, C.c_double, C.c_int32, _P,
                                    C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32)]),
     "sgx_if_filter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_P)]),
@@ -526,6 +532,48 @@ def replay_state(settings, chans, series, ms_done=None, data_type=DT_INT8, rec_f
     check(lib().sgx_replay_state(C.byref(st), int(data_type), C.cast(_chan_array(chans), _P), n, ms,
                                  done_p, _ptr(a), int(rec_file_offset), int(rec_bytes), _ptr(out)))
     return out
+
+
+CANCEL_MAX_CHANNELS, CANCEL_MAX_SMOOTH = 32, 41
+
+
+def _amp3(amp, n, ms):
+    a = np.ascontiguousarray(amp, dtype=np.float64)
+    if a.shape != (n, ms, 2):
+        raise ValueError("expected a [%d, %d, 2] amplitude array, got shape %r" % (n, ms, a.shape))
+    return a
+
+
+def cancel_design(series, state, ms_done=None, smooth=1):
+    """float64[n_ch, ms, 2]: the amplitude pair (aI, aQ) of every block of tracked channels from their prompt sums
+    (sgx_cancel_design; needs no GPU).  series: float64[n_ch, 13, ms] of track(), state: what replay_state made of it,
+    smooth: the odd number of neighbouring blocks, 1 .. 41, a pair is averaged over (data-bit signs aligned)."""
+    st = np.ascontiguousarray(state, dtype=REPLAY_STATE_DTYPE)
+    n = st.shape[0]
+    a = _series3(series, n)
+    ms = a.shape[2]
+    if st.shape != (n, ms):
+        raise ValueError("the state has shape %r, the series %r" % (st.shape, a.shape))
+    done, done_p = _ms_done(ms_done, n)
+    out = np.zeros((n, ms, 2))
+    check(lib().sgx_cancel_design(_ptr(a), _ptr(st), n, ms, done_p, int(smooth), _ptr(out)))
+    return out
+
+
+def cancel_host(settings, x, chans, series, amp, ms_done=None, rec_file_offset=0, data_type=DT_INT8):
+    """(y int8, clipped) of sgx_cancel_host: the cancellation kernel's work sample by sample on the host; test
+    infrastructure, needs no GPU.  x: the record, the file's bytes from rec_file_offset on."""
+    a = np.ascontiguousarray(x, dtype=np.int8).ravel()
+    n = len(chans)
+    ser = _series3(series, n)
+    ms = ser.shape[2]
+    am = _amp3(amp, n, ms)
+    done, done_p = _ms_done(ms_done, n)
+    st = settings_struct(settings)
+    y, clipped = np.zeros(a.size, dtype=np.int8), C.c_int64(0)
+    check(lib().sgx_cancel_host(C.byref(st), _ptr(a), a.size, int(rec_file_offset), C.cast(_chan_array(chans), _P), n, ms,
+                                done_p, _ptr(ser), int(data_type), _ptr(am), _ptr(y), C.byref(clipped)))
+    return y, int(clipped.value)
 
 
 FILTER_MAX_TAPS = 4095
@@ -1239,6 +1287,23 @@ class Context(object):
     def excise_timing(self):
         """Kernel ms of the last excise_record on this context, from HIP events on its stream."""
         return self._timing("sgx_excise_timing", 1)[0]
+
+    def if_cancel(self, rec, chans, series, amp, ms_done=None, rec_file_offset=0, data_type=DT_INT8):
+        """A new int8 record of the same length: `rec` with the tracked channels subtracted (sgx_if_cancel).  chans: (prn,
+        acquiredFreq, codePhase) per channel as they were tracked, 1 .. 32 of them; series: float64[n_ch, 13, ms] of
+        track(); amp: float64[n_ch, ms, 2] of cancel_design; ms_done: int[n_ch] or None.  The record's attribute `clipped`
+        counts the outputs that lay outside [-127, 127] in front of the clip."""
+        n = len(chans)
+        ser = _series3(series, n)
+        ms = ser.shape[2]
+        am = _amp3(amp, n, ms)
+        done, done_p = _ms_done(ms_done, n)
+        return self._stage("sgx_if_cancel", (rec._h, int(rec_file_offset), C.cast(_chan_array(chans), _P), n, ms, done_p,
+                                             _ptr(ser), int(data_type), _ptr(am)), len(rec), counters=("clipped",))
+
+    def cancel_timing(self):
+        """Kernel ms of the last if_cancel on this context, from HIP events on its stream."""
+        return self._timing("sgx_cancel_timing", 1)[0]
 
     def iq_to_if(self, rec, taps, shift, q_first=False, offset_binary=False):
         """A new int8 record of the same length: `rec`, the raw bytes of an interleaved 8-bit I/Q file at complex rate fs_c,

@@ -2,7 +2,7 @@
 // the whole record - outputs on the rails, blanked frames, codes, cut bins - is folded per workgroup and added with integer
 // atomics into ONE area of the context, SgxSmall::stage_count, which the host sums (sgx_stage.h: SgxStage::count,
 // sgx_stage_count).  Every stage waits before it returns, so one call owns the area at a time.  Who counts what:
-//   sgx_count_publish   requantiser (1 counter), conditioning (2), unpacker (2^bits), decimator, resampler, combiners (1)
+//   sgx_count_publish   requantiser (1 counter), conditioning (2), unpacker (2^bits), decimator, resampler, combiners, cancellation (1)
 //   sgx_count_slot      excision (3 counters; it publishes per wave, between its own barriers)
 //   sgx_wave_sum / max  those, and every other integer fold over a wave in the stage files
 #pragma once

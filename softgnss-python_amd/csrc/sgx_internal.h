@@ -125,10 +125,11 @@ void ex_tables(int n_seg, cplx* tw, double* win);
 
 // The record front-end stages, one per entry point that runs through sgx_stage_run (sgx_stage.h): sgx_if_filter,
 // sgx_if_from_iq, sgx_requant_stats_of, sgx_if_requantize, sgx_cond_block_stats, sgx_if_condition, sgx_if_unpack, sgx_if_decimate,
-// sgx_if_resample, sgx_array_stats, sgx_if_combine, sgx_array_block_stats, sgx_if_combine_blocks, sgx_if_excise
+// sgx_if_resample, sgx_array_stats, sgx_if_combine, sgx_array_block_stats, sgx_if_combine_blocks, sgx_if_excise, sgx_if_cancel
 enum SgxStageSlot { SGX_STAGE_FILTER, SGX_STAGE_IQ, SGX_STAGE_REQUANT_STATS, SGX_STAGE_REQUANT, SGX_STAGE_COND_STATS,
                     SGX_STAGE_COND_APPLY, SGX_STAGE_UNPACK, SGX_STAGE_DECIM, SGX_STAGE_RESAMP, SGX_STAGE_ARRAY_STATS,
-                    SGX_STAGE_COMBINE, SGX_STAGE_ARRAY_BLOCK_STATS, SGX_STAGE_COMBINE_BLOCKS, SGX_STAGE_EXCISE, SGX_STAGE_SLOTS };
+                    SGX_STAGE_COMBINE, SGX_STAGE_ARRAY_BLOCK_STATS, SGX_STAGE_COMBINE_BLOCKS, SGX_STAGE_EXCISE, SGX_STAGE_CANCEL,
+                    SGX_STAGE_SLOTS };
 
 struct sgx_if {
     int8_t* d = nullptr;   // device pointer; allocation is padded by SGX_IF_PAD zero bytes
@@ -456,6 +457,8 @@ struct sgx_ctx {
     // (grow-only)
     SegPlan plan_excise;
     DevBuf<uint16_t> d_excise_cut;
+    // strong-signal cancellation (sgx_cancel.hip): the block table and the channels as the kernel reads them (grow-only)
+    DevBuf<char> d_cancel;
     // Everything above that the context owns goes here and nowhere else (sgx_host.cpp); safe on a partly built context
     ~sgx_ctx();
 };

@@ -1,11 +1,11 @@
 // The host side that the record front-end stages share: the notch (sgx_filter.hip), the I/Q converter (sgx_iq.hip), the
 // requantiser (sgx_requant.hip), the conditioning stage (sgx_cond.hip), the unpacker (sgx_unpack.hip), the decimator
-// (sgx_decim.hip), the resampler (sgx_resamp.hip), the multi-antenna combiner (sgx_array.hip) and the swept-interference
-// excision (sgx_excise.hip; what its kernel shares with the record monitor's is in sgx_seg_fft.h, not here).  Each of their
-// fourteen entry points keeps its own argument checks, in its own order and with its own messages, and its launch; what
-// comes around the launch is here once, and so is the host side of the one counter area that the eight counting entry
-// points share (SgxStage::count, sgx_stage_count; the device side is sgx_count.h)
-// ("The stage tail").
+// (sgx_decim.hip), the resampler (sgx_resamp.hip), the multi-antenna combiner (sgx_array.hip), the swept-interference
+// excision (sgx_excise.hip; what its kernel shares with the record monitor's is in sgx_seg_fft.h, not here) and the
+// strong-signal cancellation (sgx_cancel.hip).  Each of their fifteen entry points keeps its own argument checks, in its
+// own order and with its own messages, and its launch; what comes around the launch is here once, and so is the host side
+// of the one counter area that the nine counting entry points share (SgxStage::count, sgx_stage_count; the device side is
+// sgx_count.h) ("The stage tail").
 #pragma once
 #include "sgx_count.h"
 #include "sgx_internal.h"

@@ -5,6 +5,7 @@ by libsgx.so's exact host routines (include/sgx.h), not by Python arithmetic.
 """
 import ctypes as C
 import datetime
+import os
 
 import numpy as np
 
@@ -96,6 +97,14 @@ _ACQ_DEFAULTS = (
     ("acqBinStep", None),           # Doppler step in Hz; None: 500 / acqCoherentMs
 )
 
+# strong-signal cancellation behind tracking (TrackingResult.cancel; INTEGRATION.md, "Strong-signal cancellation"): the
+# channels tracked at a high C/N0 are subtracted from the record, and what they hid is searched for and tracked on the result
+_CANCEL_DEFAULTS = (
+    ("strongSignalCancellation", False),   # postProcessing() cancels, searches again and tracks what that finds
+    ("cancelCNoThreshold", 60.0),          # dB-Hz: a channel whose medianCNo reaches it is cancelled
+    ("cancelSmoothMs", 1),                 # blocks an amplitude pair is averaged over, odd, 1 .. 41
+)
+
 
 class Settings(frontend.FrontEnd):
     """Receiver configuration; attribute names and defaults of reference initialize.py:81-173.  The stages between a record
@@ -105,7 +114,7 @@ class Settings(frontend.FrontEnd):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + frontend.DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _CANCEL_DEFAULTS + frontend.DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()
@@ -227,7 +236,80 @@ class Settings(frontend.FrontEnd):
         print('   Tracking is over (elapsed time %s s)' % self.lastTrackingSeconds)
         if self.lockDetector and trackResults.has_results():
             trackResults.showTrackingQuality()
+        if self.strongSignalCancellation and trackResults.has_results():
+            trackResults = self._cancel_strong(results, acqResults, trackResults, track_source)
         return acqResults, trackResults
+
+    def _cancel_strong(self, results, acqResults, trackResults, track_source):
+        """strongSignalCancellation, behind tracking: every channel whose medianCNo reaches cancelCNoThreshold is cancelled
+        (TrackingResult.cancel), the PRNs that are not tracked are searched again on the cleaned record with this call's
+        acquisition settings, what that finds is tracked on the cleaned record in the free channels, and the rows join the
+        others (TrackingResult.join).  Sample positions are those of the record as it was.  Returns the tracking results
+        that go on to navigation: the joined ones, or trackResults where nothing was cancelled or nothing new found."""
+        from . import acquisition, tracking
+        from .record import DeviceFile, DeviceSignal
+        quality = trackResults.quality
+        rows = [j for j in range(len(quality)) if quality[j].medianCNo >= float(self.cancelCNoThreshold)]
+        if not rows:
+            print('   No channel reaches %.1f dB-Hz: nothing is cancelled' % float(self.cancelCNoThreshold))
+            return trackResults
+        nch, n = int(results.numberOfChannels), results.samplesPerCode
+        tracked = [int(p) for p in trackResults.results.PRN]
+        print('   Cancelling PRN %s (median C/N0 %s dB-Hz)...' % (
+            ", ".join("%d" % tracked[j] for j in rows), ", ".join("%.1f" % quality[j].medianCNo for j in rows)))
+        skip, own = int(results.skipNumberOfBytes), None
+        if not isinstance(track_source, DeviceFile):     # the record file: the bytes the search and both trackings read
+            start = (skip // 4096) * 4096
+            need = skip - start + max(results.acquisitionLength() + n, int(results.msToProcess) * (n + 2) + 2 * n)
+            name = getattr(track_source, 'name', None)
+            if isinstance(name, (str, bytes)) and os.path.isfile(name):
+                need = min(need, os.path.getsize(name) - start)
+            own = trackResults._window(track_source, start, need)
+            track_source = DeviceFile(own, start)
+        cleaned = None
+        try:
+            cleaned = trackResults.cancel(track_source, rows, smooth=int(self.cancelSmoothMs))
+            print('   %d channels cancelled in %.3f ms on the GPU, %d samples clipped' % (len(rows), cleaned.kernel_ms,
+                                                                                     cleaned.clipped))
+            free = nch - len(tracked)
+            left = [p for p in range(len(results.acqSatelliteList)) if p + 1 not in tracked]
+            # the search starts one code period behind skipNumberOfBytes: every cancelled channel's first block starts in
+            # front of that, so no sample of the window still holds a strong signal; a code phase found there holds one
+            # period earlier, where tracking starts (the loops pull in the fraction of a sample it may be off)
+            at = skip - cleaned.file_offset
+            if len(cleaned.record) - (at + n) >= results.acquisitionLength():
+                at += n
+            if free < 1 or not left or at < 0:
+                return trackResults
+            again = acquisition.AcquisitionResult(results)
+            again.acquire(DeviceSignal(cleaned.record, at, min(results.acquisitionLength(), len(cleaned.record) - at)),
+                          n_blocks=int(self.acqBlocks), noncoh=bool(self.acqNonCoherent), coherent_ms=int(self.acqCoherentMs),
+                          bin_step_hz=self.acqBinStep, prn_indices=left)
+            found = int(np.sum(again.carrFreq > 0))
+            if not found:
+                print('   The cleaned record shows no further satellite')
+                return trackResults
+            again.preRun()
+            table = again.channels
+            for i in range(min(free, found), nch):       # (the free channels only: the strongest of what was found)
+                table[i].PRN, table[i].acquiredFreq, table[i].codePhase, table[i].status = 0, 0.0, 0.0, '-'
+            print('   Found on the cleaned record: PRN %s' % ", ".join("%d" % p for p in table.PRN if p))
+            more = tracking.TrackingResult(again)
+            more.track(cleaned)
+            if not more.has_results():
+                return trackResults
+            for p in (int(q) - 1 for q in table.PRN if q):
+                for name in ("carrFreq", "codePhase", "peakMetric"):
+                    acqResults.results[name][p] = again.results[name][p]
+            joined = trackResults.join(more)
+            if self.lockDetector:
+                joined.showTrackingQuality()
+            return joined
+        finally:
+            if cleaned is not None:
+                cleaned.record.free()
+            if own is not None:
+                own.free()
 
     def _resident_processing(self, name):
         """postProcessing()'s acquire -> preRun -> track on a record that _prepared_record uploads once and prepares on the

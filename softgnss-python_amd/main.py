@@ -4,6 +4,7 @@
                                                   [--lock-detector] [--acq-coherent-ms T --acq-blocks M --acq-noncoh]
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]] [--dtype int8]
                                                   [--excise[=THRESHOLD] --excise-segment N]
+                                                  [--cancel-strong[=DBHZ] --cancel-smooth MS]
 %s
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
@@ -14,7 +15,11 @@ continuous-wave lines in the record's spectrum (8 dB above the local median, or 
 the GPU before acquisition and tracking, and prints the lines it removed.  --excise removes swept (chirp) interference in
 front of that: every segment of 256 samples (or --excise-segment N, a power of two in 64 .. 1024) loses the bins of its
 spectrum that stand 8 times (or --excise=THRESHOLD times) above the mean of its other bins; it prints the share of the
-time-frequency cells it cut and the samples it clipped.
+time-frequency cells it cut and the samples it clipped.  --cancel-strong works behind tracking: every channel tracked at a
+median C/N0 of 60 dB-Hz or more (or --cancel-strong=DBHZ) is rebuilt from its tracking results and subtracted from the record
+(one amplitude per block, or averaged over --cancel-smooth MS blocks, odd, 1 .. 41), the satellites that are not tracked are
+searched for again on the cleaned record and those found are tracked there in the free channels; they join the others for
+navigation.
 %s
 
 --monitor looks at the whole prepared record before anything else runs: per 100 ms (or --monitor=SLICE_MS) one Welch spectrum
@@ -108,6 +113,13 @@ def main(argv=None):
     ap.add_argument("--excise-segment", type=int, default=None, metavar="N",
                     help="with --excise: the segment length, a power of two in 64 .. 1024 (default: Settings.exciseSegment, "
                          "256)")
+    ap.add_argument("--cancel-strong", nargs="?", type=float, const=-1.0, default=None, metavar="DBHZ",
+                    help="after tracking, cancel every channel whose median C/N0 reaches DBHZ (default: "
+                         "Settings.cancelCNoThreshold, 60), search the cleaned record for the satellites that are not "
+                         "tracked and track what that finds in the free channels")
+    ap.add_argument("--cancel-smooth", type=int, default=None, metavar="MS",
+                    help="with --cancel-strong: average each block's amplitude over MS blocks, odd, 1 .. 41 (default: "
+                         "Settings.cancelSmoothMs, 1)")
     ap.add_argument("--monitor", nargs="?", type=float, const=-1.0, default=None, metavar="SLICE_MS",
                     help="monitor the whole record first: a spectrum and sample statistics per SLICE_MS ms (default: "
                          "Settings.monitorSliceMs, 100), a line printed per event and per slice that stands out")
@@ -134,6 +146,12 @@ def main(argv=None):
         ap.error("--excise takes the threshold, a factor of at least 1")
     if a.excise_segment is not None and not (64 <= a.excise_segment <= 1024 and a.excise_segment & (a.excise_segment - 1) == 0):
         ap.error("--excise-segment takes a power of two in 64 .. 1024")
+    if a.cancel_smooth is not None and a.cancel_strong is None:
+        ap.error("--cancel-smooth says how --cancel-strong forms its amplitudes: it needs --cancel-strong")
+    if a.cancel_strong is not None and not (a.cancel_strong == -1.0 or np.isfinite(a.cancel_strong)):
+        ap.error("--cancel-strong takes the C/N0 threshold in dB-Hz")
+    if a.cancel_smooth is not None and not (1 <= a.cancel_smooth <= 41 and a.cancel_smooth % 2 == 1):
+        ap.error("--cancel-smooth takes an odd number of blocks in 1 .. 41")
     if a.monitor_out is not None and a.monitor is None:
         ap.error("--monitor-out saves what --monitor sees: it needs --monitor")
     if a.monitor is not None and not (a.monitor == -1.0 or (np.isfinite(a.monitor) and a.monitor > 0)):
@@ -148,6 +166,9 @@ def main(argv=None):
                  sweptMitigation=True if a.excise is not None else None,
                  exciseThreshold=a.excise if a.excise is not None and a.excise >= 1.0 else None,
                  exciseSegment=a.excise_segment,
+                 strongSignalCancellation=True if a.cancel_strong is not None else None,
+                 cancelCNoThreshold=a.cancel_strong if a.cancel_strong is not None and a.cancel_strong != -1.0 else None,
+                 cancelSmoothMs=a.cancel_smooth,
                  monitorSliceMs=a.monitor if a.monitor is not None and a.monitor > 0 else None)
     for stage, names in zip(STAGES, dests):
         given = [val is not None and val is not False for val in (getattr(a, name) for name in names)]

@@ -57,6 +57,13 @@ class ReplayResult(object):
         print('')
 
 
+class _Acquired(object):
+    """A channel table and its settings: all of an acquisition that a TrackingResult made by join() looks at."""
+
+    def __init__(self, settings, channels):
+        self.settings, self.channels = settings, channels
+
+
 class TrackingResult(Result):
     def __init__(self, acqResult, device=None, verbose=False):
         """verbose: print the reference's progress lines (tracking.py:137-143: one per channel and 50 ms) - after the
@@ -191,6 +198,57 @@ class TrackingResult(Result):
             out = ctx.track_replay(rec, chans, series, taps, rec_file_offset=file_off, data_type=dtype_code)
             kernel_ms = ctx.replay_timing()[0]
         return ReplayResult(taps, prn, out, kernel_ms)
+
+    def cancel(self, fid, rows=None, smooth=1):
+        """Strong-signal cancellation (sgx_if_cancel): the signals of tracked channels rebuilt from their recorded blocks
+        and prompt sums and subtracted from the record, so that a search of the result finds what they hid.
+        fid: the int8 record track() read (open binary file or DeviceFile); rows: the rows of .results to cancel (None:
+        all of them, at most 32); smooth: the odd number of blocks, 1 .. 41, each amplitude pair is averaged over.
+        Returns a DeviceFile on the NEW record with the input's file_offset - DeviceSignal(result.record, ...) and track()
+        take it; its .clipped counts the outputs on the rails, .kernel_ms is the kernel's time.  Works after track() and
+        after .results was assigned from a cache."""
+        settings = self._settings
+        series, _, prn, chans = self._tracked()
+        pick = list(range(len(chans or ()))) if rows is None else [int(r) for r in rows]
+        if not pick or min(pick) < 0 or max(pick) >= len(chans or ()):
+            raise ValueError("cancel() takes rows of .results, 1 .. %d of them: got %r of %d"
+                             % (_native.CANCEL_MAX_CHANNELS, pick, len(chans or ())))
+        dtype_code, isz = self._data_type()
+        if dtype_code != _native.DT_INT8:
+            raise TypeError("cancel() rebuilds int8 records, not Settings.dataType %r" % (settings.dataType,))
+        chans = [chans[i] for i in pick]
+        series = np.ascontiguousarray(series[pick])
+        ctx = engine.get_context(settings, self._device)
+        first = int(settings.skipNumberOfBytes + min(c[2] for c in chans))
+        with self._record(fid, first, lambda: int(series[:, 0, :].max()) - first) as (rec, file_off):
+            state = _native.replay_state(settings, chans, series, rec_file_offset=file_off, rec_bytes=len(rec))
+            amp = _native.cancel_design(series, state, smooth=smooth)
+            out = ctx.if_cancel(rec, chans, series, amp, rec_file_offset=file_off)
+            kernel_ms = ctx.cancel_timing()
+        cleaned = DeviceFile(out, file_off)
+        cleaned.clipped, cleaned.kernel_ms, cleaned.PRN = int(out.clipped), kernel_ms, [c[0] for c in chans]
+        return cleaned
+
+    def join(self, other):
+        """A TrackingResult that holds this object's rows followed by `other`'s - channels found and tracked later, on a
+        cleaned record (Settings.strongSignalCancellation) - over one channel table of numberOfChannels rows: what
+        NavigationResult takes.  Both were tracked by track() for the same number of ms."""
+        if self.series is None or other.series is None or self.series.shape[2] != other.series.shape[2]:
+            raise ValueError("join() takes two results of track() over the same number of ms")
+        rows = [self._channels[i] for i in self._active] + [other._channels[i] for i in other._active]
+        nch = max(int(self._settings.numberOfChannels), len(rows))
+        table = np.rec.fromarrays([np.zeros(nch, dtype='int64'), np.zeros(nch), np.zeros(nch), ['-'] * nch],
+                                  names='PRN,acquiredFreq,codePhase,status')
+        for i, r in enumerate(rows):
+            table[i].PRN, table[i].acquiredFreq, table[i].codePhase = int(r.PRN), float(r.acquiredFreq), float(r.codePhase)
+            table[i].status = r.status
+        both = TrackingResult(_Acquired(self._settings, table), device=self._device, verbose=self._verbose)
+        both.kernel_ms = self.kernel_ms
+        both.series = np.concatenate([self.series, other.series])
+        both._active = list(range(len(rows)))
+        both._lazy = (both.series, both._active)
+        both._detect_locks()
+        return both
 
     def showTrackingQuality(self):
         """ASCII table of .quality, in the manner of AcquisitionResult.showChannelStatus."""
