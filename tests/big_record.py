@@ -18,6 +18,8 @@ Everything is written against the boundary B, so that the host test can hold the
 whole-record counter is  first + (reps - 2) middle + last  from the contract on two and on three blocks (see counters)."""
 import numpy as np
 
+import cancel_cases
+import cancel_spec
 import cond_spec
 import decim_spec
 import iq_spec
@@ -25,6 +27,7 @@ import notch_spec
 import requant_spec
 import resamp_spec
 import waterfall_spec
+from oracle import softgnss_oracle as orc
 
 B32 = 1 << 32
 P32 = 105 << 13
@@ -311,6 +314,69 @@ def small_cond_cases():
     tile it."""
     rec = Tiled(1 << 20, 105 << 10, extra=48 * 5)
     return {"condition_int8": (Cond(rec, np.int8, 1, 256), rec), "condition_int16": (Cond(rec, np.int16, 2, 256), rec)}
+
+
+# ---- the strong-signal cancellation ----------------------------------------------------------------------------------------
+
+class CancelPlan(object):
+    """Four hand-made channels (cancel_cases.handmade: blocks of 2046 samples at 2.046 Msps) on a tiled record of n = B + extra
+    bytes, B a multiple of the kernel's tile of 4096:
+      A  5 blocks that straddle B / 2
+      B  6 blocks that straddle B, block 2 starting exactly at B: a tile's first sample at a 33-bit position
+      C  4 blocks of which the last ends with the record's last sample
+      D  5 blocks that start in the first tile
+    with amplitudes of some tens of LSB on full-scale bytes, so that the bytes change and some clip.  A channel's window is
+    its blocks with MARGIN samples (more than a tile) either side, cut at the record's ends; the windows are disjoint, so the
+    record's clip count is the sum of theirs.  Two further windows that no block touches lie across B / 2 + Q and B - Q,
+    Q = min(2^20, B / 8): there the output is the input.  expect() is cancel_spec.cancel on the window's bytes with the
+    channel rebased to the window's first byte."""
+    MARGIN = 5000
+    BLOCKS = dict(A=5, B=6, C=4, D=5)
+
+    def __init__(self, rec, seed=0xCA9C):
+        self.rec = rec
+        B, n = rec.B, rec.n
+        assert B % 4096 == 0
+        rng = np.random.default_rng(seed)
+        self.s = orc.OracleSettings(samplingFreq=cancel_cases.LOW_FS, IF=cancel_cases.LOW_IF, numberOfChannels=4, msToProcess=6.0)
+        ms = 6
+        self.names, self.chans, rows, self.ms_done, self.windows = [], [], [], [], []
+        for i, name in enumerate("ABCD"):
+            done = self.BLOCKS[name]
+            prn, freq = 4 + 7 * i, cancel_cases.LOW_IF + float(rng.integers(-4000, 4001))
+            code = cancel_cases.CHIP_RATE + rng.uniform(-3.0, 3.0, ms)
+            carr = freq + rng.uniform(-20.0, 20.0, ms)
+            ends = cancel_cases.handmade(self.s, 0, freq, code, carr)[0].astype(np.int64)    # block ends of a channel from 0
+            start = {"A": B // 2 - int(ends[1]) - 777, "B": B - int(ends[1]), "C": n - int(ends[done - 1]), "D": 100}[name]
+            series = cancel_cases.handmade(self.s, start, freq, code, carr)
+            assert np.array_equal(series[0], ends + start)
+            self.names.append(name)
+            self.chans.append((prn, freq, float(start)))
+            rows.append(series)
+            self.ms_done.append(done)
+            self.windows.append((max(0, start - self.MARGIN), min(n, start + int(ends[done - 1]) + self.MARGIN)))
+        self.series = np.stack(rows)
+        self.ms_done = np.array(self.ms_done, dtype=np.int32)
+        self.amp = rng.uniform(-45.0, 45.0, (4, ms, 2))
+        q = min(1 << 20, B // 8)
+        self.quiet = [(B // 2 + q - 4096 - 3, B // 2 + q + 4096 + 5), (B - q - 4096 - 3, B - q + 4096 + 5)]
+        a, b, c, d = (dict(zip(self.names, self.chans))[k][2] for k in "ABCD")
+        end = lambda k: int(self.series[self.names.index(k), 0, self.BLOCKS[k] - 1])
+        assert a < B // 2 < end("A") and b < B < end("B") and B in self.series[1, 0, :].astype(np.int64) and end("C") == n
+        assert d < 4096
+        spans = sorted(self.windows + self.quiet)
+        assert all(x[1] <= y[0] for x, y in zip(spans, spans[1:])) and spans[0][0] == 0 and spans[-1][1] == n, spans
+
+    def expect(self, at, i, w0, w1):
+        """(y, v, clipped, covered) of the contract on window i: bytes [w0, w1) through `at`, channel i alone, rebased."""
+        prn, freq, start = self.chans[i]
+        series = np.array(self.series[i:i + 1])
+        series[:, 0] -= w0
+        return cancel_spec.cancel(self.s, at(w0, w1), 0, [(prn, freq, start - w0)], series, self.ms_done[i:i + 1],
+                                  self.amp[i:i + 1])
+
+    def contract(self, i):
+        return lambda at, w0, w1: self.expect(at, i, w0, w1)[0]
 
 
 # ---- the monitor --------------------------------------------------------------------------------------------------------

@@ -33,10 +33,11 @@ HALF_MARGIN = 1e-6       # a sample whose v lies this close to a half-integer is
 
 def states(s, record_bytes, rec_file_offset, chans, series, ms_done):
     """The block state of every channel (None for a channel that is off), the record being bytes [rec_file_offset,
-    rec_file_offset + record_bytes) of the file: replay_spec's recurrence on a file image that is never read."""
+    rec_file_offset + record_bytes) of the file: replay_spec's recurrence on the file's length alone - no byte is read, so
+    no image is made, and an offset beyond 2^33 costs nothing."""
     series = np.asarray(series)
     n_ch, _, ms = series.shape
-    image = np.zeros(int(rec_file_offset) + int(record_bytes), dtype=np.int8)
+    image = int(rec_file_offset) + int(record_bytes)
     out = []
     for c, (prn, f, cp) in enumerate(chans):
         if int(prn) == 0:

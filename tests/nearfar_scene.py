@@ -69,6 +69,53 @@ def oracle_cancelled(smooth=1):
     return (amp,) + spec.cancel(s, rec, 0, chans, series, None, amp)
 
 
+# The scene behind a record stage (the resident path of postProcessing): the file is the record with a DC offset, which the
+# conditioning stage - byte-exact against tests/cond_spec.py - removes; the prepared record is what acquisition, tracking and
+# the cancellation then read, positions being samples of it.  postProcessing() prepares the bytes it needs and no more:
+# msToProcess blocks of up to n + 2 samples and two code periods.
+DC_OFFSET = 5
+COND = dict(condBlockUs=100.0, condAgcBlocks=32.0, condBlankFactor=4.0, condGuardFrames=8, condTargetRms=12.0)   # the defaults
+
+
+@functools.lru_cache(maxsize=None)
+def offset_file():
+    """The record as a file whose front end adds DC_OFFSET LSB (int8, saturating)."""
+    rec = np.clip(record().astype(np.int16) + DC_OFFSET, -128, 127).astype(np.int8)
+    rec.setflags(write=False)
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
+def prepared_record():
+    """What Settings.conditionRecord makes of the bytes of offset_file() that postProcessing() reads, with the settings COND,
+    by the stage's numpy contract."""
+    import cond_spec
+    n = settings().samplesPerCode
+    raw = offset_file()[:MS_TRACKED * (n + 2) + 2 * n]
+    block = min(16384, max(256, 16 * int(np.rint(COND["condBlockUs"] * 1e-6 * FS / 16.0))))
+    blank_q4 = int(np.rint(16.0 * COND["condBlankFactor"] ** 2))
+    stats = cond_spec.block_stats(raw, np.int8, 1, block, blank_q4)
+    plan = cond_spec.plan(stats, 1, blank_q4, COND["condTargetRms"], COND["condAgcBlocks"])
+    y = cond_spec.condition(raw, np.int8, 1, block, plan, COND["condGuardFrames"])[0]
+    y.setflags(write=False)
+    return y
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_run_prepared():
+    """(raw search, chans, series, cleaned search) of the oracle on prepared_record(): the search, the strong channels
+    tracked for 40 ms, cancelled by the contract (one amplitude pair per block), and the search of the cleaned record."""
+    s, rec = settings(), prepared_record()
+    found = search(s, rec)
+    chans = [(p, found[p][2], found[p][1]) for p in STRONG]
+    ch = dict(PRN=np.array([c[0] for c in chans]), acquiredFreq=np.array([c[1] for c in chans]),
+              codePhase=np.array([c[2] for c in chans]), status=['T'] * len(chans))
+    series = orc.stack_series(orc.track(s, ch, rec, ms=MS_TRACKED))
+    amp = spec.design(series, spec.states(s, rec.size, 0, chans, series, None))
+    y = spec.cancel(s, rec, 0, chans, series, None, amp)[0]
+    return found, chans, series, search(s, y)
+
+
 def prompt_power_db(s, rec, chans, series):
     """Per channel, 10 log10 of the mean prompt power I_P^2 + Q_P^2 of the channel replayed on `rec`."""
     out = []

@@ -33,10 +33,16 @@ def replay(s, record, data_type, prn, acquired_freq, code_phase, absolute_sample
            correlate=True):
     """One channel.  record: the file from byte 0 (any array; its bytes are used); data_type: numpy dtype of the samples.
     Returns (I[K][ms], Q[K][ms], state) with state a dict of the STATE_FIELDS arrays [ms] (entries k >= ms_done are 0).
-    correlate=False: the state only."""
+    correlate=False: the state only; the record may then be given as its length in bytes, an int - no byte of it is read."""
     dt = np.dtype(data_type)
     isz = dt.itemsize
-    rec = np.ascontiguousarray(record).view(np.uint8).ravel()
+    if isinstance(record, (int, np.integer)):
+        if correlate:
+            raise ValueError("a record given as its length cannot be correlated")
+        rec, rec_size = None, int(record)
+    else:
+        rec = np.ascontiguousarray(record).view(np.uint8).ravel()
+        rec_size = rec.size
     fs = s.samplingFreq
     ms = len(absolute_sample)
     taps = [float(d) for d in taps]
@@ -55,7 +61,7 @@ def replay(s, record, data_type, prn, acquired_freq, code_phase, absolute_sample
         blk = int(np.ceil((s.codeLength - rem_code) / step))
         if pos + blk * isz != int(absolute_sample[k]):
             raise ValueError("block %d: rebuilt end %d, absoluteSample %d" % (k, pos + blk * isz, int(absolute_sample[k])))
-        if pos < 0 or pos + blk * isz > rec.size:
+        if pos < 0 or pos + blk * isz > rec_size:
             raise IndexError("block %d ends beyond the record" % k)
         st["blk"][k], st["start"][k], st["rem_code"][k], st["rem_carr"][k] = blk, pos, rem_code, rem_carr
         st["step"][k], st["carr_freq"][k] = step, kf

@@ -1,8 +1,10 @@
 """Records longer than 4 GiB on every path that reads one: the record handle, the generator, the record stages, the probe and
-the monitor, the acquisition entry points, the tracking kernels and the replay, each with record positions beyond 2^31 and
-2^32.  Every expectation is a window or an exact integer from tests/big_record.py, whose rule - a wrap must be visible - is
-run on the CPU before anything is compared with the device.  The cost is two 4.3 GB records in HBM (one made there, one
-uploaded once) and milliseconds of kernels; nothing on the host grows with the record.  Run with -m gpu.
+the monitor, the acquisition entry points, the tracking kernels, the replay and the strong-signal cancellation, each with
+record positions beyond 2^31 and 2^32.  Every expectation is a window or an exact integer from tests/big_record.py, whose
+rule - a wrap must be visible - is run on the CPU before anything is compared with the device.  The cost is two 4.3 GB
+records in HBM (one made there, one uploaded once), the stages' outputs of that size while their test runs (the
+cancellation's two calls: two of them) and milliseconds of kernels; nothing on the host grows with the record.  Run with
+-m gpu.
 
 Left out on purpose: the float32 sums of requant_stats (taken in double in a fixed order that the contract does not restate;
 its counts and max_abs are exact and are compared); the decimator, whose own file holds its 4 GiB case."""
@@ -248,6 +250,49 @@ def test_resample_4_3_input_beyond_the_boundary(env, tiled, cases, capsys):
     assert stage.out_len(rec.n) > 5.7e9
     _check_stage(capsys, "resample 4/3", stage, rec, lambda: ctx.resample(tiled[1], stage.h, stage.S, 4, 3),
                  m._native.resamp_tile() * 4 // 16, ("clipped",))
+
+
+# ---- the strong-signal cancellation ----------------------------------------------------------------------------------------
+
+def test_cancel_across_the_boundaries(env, tiled, capsys):
+    """One if_cancel over the whole tiled record at rec_file_offset 0 with the four hand-made channels of big.CancelPlan:
+    blocks across 2^31, across 2^32 - one of them starting exactly at 2^32 -, up to the record's last sample and in the
+    first tile.  Every channel's window equals its contract under the rule of cancel_cases.compare, the two windows that no
+    block touches (across 2^31 + 2^20 and 2^32 - 2^20) are the input, the clip count is the sum of the windows' (only
+    covered samples count: exact), the input is not written, and a second call gives the same bytes."""
+    m, s, _ = env
+    rec, dev = tiled
+    plan = big.CancelPlan(rec)
+    ctx = m.engine.get_context(plan.s, 0)
+    wants = []
+    for i, w in enumerate(plan.windows):
+        big.wrap_visible(rec.at, plan.contract(i), w)
+        wants.append(plan.expect(rec.at, i, *w))
+    quiet = [big.wrap_visible(rec.at, big.identity, w) for w in plan.quiet]
+    total = sum(e[2] for e in wants)
+    assert all(e[2] > 0 for e in wants)
+    out = ctx.if_cancel(dev, plan.chans, plan.series, plan.amp, ms_done=plan.ms_done)
+    try:
+        assert len(out) == rec.n
+        got = [out.download(w0, w1 - w0) for w0, w1 in plan.windows]
+        excluded = [big.cancel_cases.compare_to(e, "channel %s" % k, y) for e, k, y in zip(wants, plan.names, got)]
+        for (w0, w1), want in zip(plan.quiet, quiet):
+            assert out.download(w0, w1 - w0).tobytes() == want.tobytes(), (w0, w1)
+        assert out.clipped == total, (out.clipped, total)
+        for w0, w1 in plan.windows + plan.quiet:
+            assert dev.download(w0, w1 - w0).tobytes() == rec.at(w0, w1).tobytes(), (w0, w1)     # the input is not written
+        kernel_ms = ctx.cancel_timing()
+        again = ctx.if_cancel(dev, plan.chans, plan.series, plan.amp, ms_done=plan.ms_done)
+        try:
+            assert again.clipped == total
+            for (w0, w1), y in zip(plan.windows, got):
+                assert again.download(w0, w1 - w0).tobytes() == y.tobytes(), (w0, w1)
+        finally:
+            again.free()
+    finally:
+        out.free()
+    _report(capsys, "if_cancel over 2^32 + %d samples: %d windows under the rule (%d rounding decisions excluded), 2 untouched "
+            "windows byte for byte, %d clipped exact, kernel %.1f ms" % (big.EXTRA32, len(got), sum(excluded), total, kernel_ms))
 
 
 # ---- the probe and the monitor ------------------------------------------------------------------------------------------

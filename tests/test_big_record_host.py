@@ -1,7 +1,8 @@
 """The helpers of tests/big_record.py without a GPU: their arithmetic at a small boundary against the numpy contracts run by
 brute force on the whole small record, the wrap rule on every window of tests/test_big_record_gpu.py at B = 2^32 - and that
-the rule rejects a block of 2^20 bytes, which divides both boundaries -, the host generator across 2^31 and 2^32, and the
-oracle's indifference to where its window starts."""
+the rule rejects a block of 2^20 bytes, which divides both boundaries -, the host generator across 2^31 and 2^32, the
+oracle's indifference to where its window starts, and the cancellation's windows (big.CancelPlan) against its contract and
+its host twin on the whole small record."""
 import numpy as np
 import pytest
 
@@ -81,6 +82,47 @@ def test_the_monitor_s_whole_record_expectation_equals_the_contract():
         assert np.array_equal(got[k], want[k]), k
     # the same spectra summed phase by phase instead of segment by segment: rounding of 256 additions
     assert np.abs(got["pxx"] - want["pxx"]).max() < 1e-12 * want["pxx"].max()
+
+
+def test_the_cancellation_s_windows_equal_the_contract_and_the_host_twin_on_the_whole_record():
+    """big.CancelPlan at B = 2^20: every window obeys the rule, the windows of the contract on the WHOLE small record with all
+    four channels are the windows' own expectations (bytes, v and counts), the quiet windows and everything between the
+    windows are the input, and sgx_cancel_host on the whole record equals the windows under the rule of
+    cancel_cases.compare, its clip count the sum of theirs."""
+    n = pkg("_native")
+    B = 1 << 20
+    rec = big.Tiled(B, 105 << 10, extra=48 * 700 + 5)
+    plan = big.CancelPlan(rec)
+    x = rec.build()
+    assert rec.n % 16 != 0 and [plan.BLOCKS[k] for k in plan.names] == list(plan.ms_done) and plan.s.samplingFreq == 2.046e6
+    whole = big.cancel_spec.cancel(plan.s, x, 0, plan.chans, plan.series, plan.ms_done, plan.amp)
+    y, clipped = n.cancel_host(plan.s, x, plan.chans, plan.series, plan.amp, ms_done=plan.ms_done)
+    total, inside = 0, np.zeros(rec.n, dtype=bool)
+    for i, (w0, w1) in enumerate(plan.windows):
+        assert w1 - w0 >= plan.BLOCKS[plan.names[i]] * 2045 + (plan.MARGIN if i in (2, 3) else 2 * plan.MARGIN)
+        want = big.wrap_visible(rec.at, plan.contract(i), (w0, w1), B=B)
+        exp = plan.expect(rec.at, i, w0, w1)
+        assert want.tobytes() == exp[0].tobytes() == whole[0][w0:w1].tobytes() and np.any(want != x[w0:w1])
+        assert np.array_equal(exp[1], whole[1][w0:w1]) and np.array_equal(exp[3], whole[3][w0:w1])
+        assert 0 < exp[2] < exp[3].sum() and exp[3].sum() >= plan.BLOCKS[plan.names[i]] * 2045
+        big.cancel_cases.compare_to(exp, plan.names[i], y[w0:w1])
+        total += exp[2]
+        inside[w0:w1] = True
+    assert whole[2] == total == clipped and not whole[3][~inside].any()
+    assert np.array_equal(y[~inside], x[~inside])
+    for w0, w1 in plan.quiet:
+        assert not inside[w0:w1].any() and w1 - w0 > 2 * 4096
+        want = big.wrap_visible(rec.at, big.identity, (w0, w1), B=B)
+        assert y[w0:w1].tobytes() == want.tobytes() == whole[0][w0:w1].tobytes()
+    # the plan of the GPU test: the same placement at 2^32, block 2 of channel B on a tile's first sample past 2^32 - 1
+    full = big.CancelPlan(big.Tiled())
+    assert int(full.series[1, 0, 1]) == big.B32 and big.B32 % 4096 == 0 and int(full.series[2, 0, 3]) == big.B32 + big.EXTRA32
+    assert full.quiet[0][0] < big.B32 // 2 + (1 << 20) < full.quiet[0][1]
+    assert full.quiet[1][0] < big.B32 - (1 << 20) < full.quiet[1][1]
+    for i, w in enumerate(full.windows):
+        big.wrap_visible(full.rec.at, full.contract(i), w)
+    for w in full.quiet:
+        big.wrap_visible(full.rec.at, big.identity, w)
 
 
 # ---- the wrap rule ------------------------------------------------------------------------------------------------------

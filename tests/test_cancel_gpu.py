@@ -2,7 +2,9 @@
 Settings.strongSignalCancellation): the kernel against the numpy contract (tests/cancel_spec.py) and against the host twin on
 every case of tests/cancel_cases.py under the rule of cancel_cases.compare - equal bytes wherever v lies farther than 1e-6
 from a half-integer, clip counts exact -, and the near-far scene of tests/nearfar_scene.py through the Python layer with the
-GPU's own search and tracking.  Run with -m gpu."""
+GPU's own search and tracking - on a DeviceFile at offset 0 and at an offset that is no multiple of 16, through
+postProcessing() on a file at skipNumberOfBytes 0 and 5000 (the window of the file that Settings._cancel_strong uploads) and
+behind a record stage (the resident path: positions are samples of the prepared record).  Run with -m gpu."""
 import subprocess
 import sys
 
@@ -13,6 +15,7 @@ import cancel_cases as cases
 import cancel_spec as spec
 import nearfar_scene as nf
 from conftest import ROOT, pkg
+from test_gpu_parity import TRK_TOL, _trk_err
 
 pytestmark = pytest.mark.gpu
 
@@ -167,3 +170,99 @@ def test_command_line_cancel_strong(scene_run, tmp_path):
     tail = r.stdout[r.stdout.index("Found on the cleaned record"):]
     rows = [ln.split("|") for ln in tail.splitlines() if ln.startswith("|") and ln.count("|") == 6 and "PRN" not in ln]
     assert sorted(int(x[2]) for x in rows) == [1, 3, 7, 11], tail[-3000:]
+
+
+def test_cancel_on_a_device_file_at_an_odd_offset(scene_run):
+    """The record from byte 1003 of the file on (no multiple of 16, in front of the first code start) as
+    DeviceFile(window, 1003): searched over the same bytes [2 n, 13 n) of the file, tracked, cancelled.  The cleaned record
+    keeps the offset and equals the contract at that offset on the GPU's own series, as the scene test's does at offset 0."""
+    m, s, ctx, _, n, _, _ = scene_run
+    off = 1003
+    assert off % 16 != 0 and off < min(nf.CODE_STARTS)
+    host = nf.record()[off:]
+    rec = ctx.upload(host)
+    cleaned = None
+    try:
+        a = m.AcquisitionResult(s, device=0)
+        a.acquire(m.DeviceSignal(rec, 2 * n - off, 11 * n), prn_indices=[p - 1 for p in nf.SEARCHED])
+        a.preRun()
+        assert _detections(a) == [1, 3]
+        t = m.TrackingResult(a, device=0)
+        t.track(m.DeviceFile(rec, off))
+        assert list(t.results.PRN) == [1, 3] and t.series.shape == (2, 13, nf.MS_TRACKED)
+        cleaned = t.cancel(m.DeviceFile(rec, off))
+        assert cleaned.file_offset == off and len(cleaned.record) == len(rec) and cleaned.PRN == [1, 3]
+        chans = [(int(c.PRN), float(c.acquiredFreq), float(c.codePhase)) for c in a.channels if c.PRN != 0]
+        assert all(abs(c[2] - want) <= 1 for c, want in zip(chans, nf.CODE_STARTS))           # positions of the FILE
+        so = nf.settings()
+        amp = spec.design(t.series, spec.states(so, len(host), off, chans, t.series, None))
+        want, v, clipped, covered = spec.cancel(so, host, off, chans, t.series, None, amp)
+        y = cleaned.record.download()
+        differ = np.flatnonzero(y != want)
+        assert np.all(spec.decisions(v, covered)[differ]) and differ.size <= 1e-4 * y.size and cleaned.clipped == clipped
+        assert np.any(y != host) and np.array_equal(rec.download(), host)
+    finally:
+        if cleaned is not None:
+            cleaned.record.free()
+        rec.free()
+
+
+def _post_processing(m, path, **more):
+    """postProcessing() of a file with the settings of test_command_line_cancel_strong.  Returns (settings, acquisition
+    results, tracking results)."""
+    s = m.Settings()
+    s.fileName, s.samplingFreq, s.IF, s.msToProcess, s.numberOfChannels = path, nf.FS, nf.IF, float(nf.MS_TRACKED), 4
+    s.lockDetector, s.strongSignalCancellation, s.cancelCNoThreshold = True, True, 40.0
+    for k, val in more.items():
+        assert hasattr(s, k), k
+        setattr(s, k, val)
+    acq, trk, _ = s.postProcessing()
+    return s, acq, trk
+
+
+def test_post_processing_at_a_file_offset_equals_the_run_at_offset_zero(tmp_path, capsys):
+    """The near-far record behind 5000 arbitrary bytes, skipNumberOfBytes = 5000: Settings._cancel_strong uploads the
+    file from byte 4096 on and searches the cleaned record 904 + n samples into it.  Measured against the run on the plain
+    file: the same four satellites joined, the same acquisition results, absoluteSample 5000 further on, and the six
+    correlator series within the bar of tests/test_gpu_parity.py."""
+    m = pkg()
+    K = 5000
+    plain, padded = str(tmp_path / "nearfar.bin"), str(tmp_path / "padded.bin")
+    nf.record().tofile(plain)
+    with open(padded, "wb") as fh:
+        fh.write(np.random.default_rng(5).integers(-128, 128, K).astype(np.int8).tobytes())
+        fh.write(nf.record().tobytes())
+    s0, a0, t0 = _post_processing(m, plain)
+    s1, a1, t1 = _post_processing(m, padded, skipNumberOfBytes=K)
+    assert K // 4096 * 4096 == 4096 and K - 4096 == 904
+    for a, t in ((a0, t0), (a1, t1)):
+        assert sorted(int(p) for p in t.results.PRN) == [1, 3, 7, 11] and list(t.results.PRN[:2]) == [1, 3]
+        assert [int(p) + 1 for p in np.flatnonzero(np.asarray(a.results["carrFreq"]) > 0)] == [1, 3, 7, 11]
+    assert list(t1.results.PRN) == list(t0.results.PRN)
+    for k in ("codePhase", "carrFreq"):
+        assert np.array_equal(np.asarray(a1.results[k]), np.asarray(a0.results[k])), k
+    assert t0.series.shape == t1.series.shape == (4, 13, nf.MS_TRACKED)
+    assert np.array_equal(t1.series[:, 0] - K, t0.series[:, 0])
+    err = _trk_err(t1.series, t0.series)
+    with capsys.disabled():
+        print("\n[cancel] postProcessing at skipNumberOfBytes %d against 0: correlator series %.3g of RMS|P| (bar %.0e)"
+              % (K, err, TRK_TOL))
+    assert err < TRK_TOL
+
+
+def test_post_processing_behind_a_record_stage(tmp_path):
+    """The resident path: the scene's file with a DC offset through the conditioning stage (byte-exact against its contract,
+    tests/test_cond_gpu.py), strongSignalCancellation on.  _resident_processing hands Settings._cancel_strong a DeviceFile of
+    the PREPARED record.  What tests/test_cancel_host.py shows with the oracle on that record holds on the device: PRN 1 and
+    3 tracked and cancelled, PRN 7 and 11 found and tracked on the cleaned record, their code phases within one sample of
+    the oracle's."""
+    m = pkg()
+    path = str(tmp_path / "offset.bin")
+    nf.offset_file().tofile(path)
+    s, acq, trk = _post_processing(m, path, frontEndConditioning=True, **nf.COND)
+    raw, chans, series, clean = nf.oracle_run_prepared()
+    joined = [int(p) for p in trk.results.PRN]
+    assert joined[:2] == [1, 3] and sorted(joined) == [1, 3, 7, 11], joined
+    assert trk.series.shape == (4, 13, nf.MS_TRACKED) and s.lastConditioning["samples"] == nf.prepared_record().size
+    for p in nf.WEAK:
+        assert abs(float(acq.results["codePhase"][p - 1]) - clean[p][1]) <= 1, (p, acq.results["codePhase"][p - 1], clean[p][1])

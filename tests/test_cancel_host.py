@@ -58,6 +58,42 @@ def test_the_table_covers_what_it_says():
     assert np.count_nonzero(off["x"][covered] == -128) == 4 and not np.any(want[covered] == -128) and clipped >= 1
     assert cases.expected("clip")[2] > 1000
     assert np.array_equal(cases.expected("nearfar")[0], nf.oracle_cancelled()[1])
+    # the hand-made cases
+    lane = cases.LANE
+    for name, n_ch in (("ch32", 32), ("ch31", 31)):
+        c = cases.get(name)
+        cover = np.zeros(len(c["x"]), dtype=np.int32)
+        for st in c["states"]:
+            cover[st["start"][0]:st["start"][-1] + st["blk"][-1]] += 1
+        assert len(c["chans"]) == n_ch and [ch[0] for ch in c["chans"]] == list(range(1, n_ch + 1)), name
+        assert cover.max() == n_ch and c["series"].shape[2] == 4 and c["s"].samplingFreq == 2.046e6, name
+    assert cases.get("ch32")["series"][:31].tobytes() == cases.get("ch31")["series"].tobytes()
+    c = cases.get("short_blocks")
+    st = c["states"][0]
+    first, last = st["start"][1:], st["start"][1:] + st["blk"][1:] - 1
+    assert st["blk"][0] >= 2045 and 5 <= st["blk"][1:].min() and st["blk"][1:].max() <= 15
+    assert int(np.count_nonzero(first // lane == last // lane)) >= 20
+    assert first[0] < cases.TILE < last[-1] and st["rem_code"].max() > 100.0
+    other = c["states"][1]
+    assert other["start"][0] < first[0] and last[-1] < other["start"][2] + other["blk"][2] and c["ms_done"][1] == 3
+    c = cases.get("residues")
+    s0, s1 = c["states"]
+    assert set((s0["start"][1:] % lane).tolist()) == set(range(lane))        # 0: block k - 1 ends on a lane's last sample
+    assert set(s0["blk"].tolist()) == {2045, 2046, 2047}
+    inside = [set((st["start"][st["start"] % lane != 0] // lane).tolist()) for st in (s0, s1)]
+    assert inside[0] & inside[1]                                              # one lane, a boundary of either channel in it
+    ends = max(int(st["start"][-1] + st["blk"][-1]) for st in (s0, s1))
+    assert len(c["x"]) == ends - c["off"] and len(c["x"]) % lane != 0
+    c = cases.get("far_offset")
+    assert c["off"] > 2 ** 33 and len(c["x"]) == 3 * tile - 7
+    near = spec.states(c["s"], len(c["x"]), *c["near"], None)
+    for far, st in zip(c["states"], near):
+        assert np.all(far["start"] > 2 ** 33) and np.array_equal(far["start"] - 2 ** 33, st["start"])
+        for f in ("blk", "rem_code", "rem_carr", "step", "carr_freq"):
+            assert far[f].tobytes() == st[f].tobytes(), f
+    for name in ("ch32", "ch31", "short_blocks", "residues"):                 # amplitudes that are no integers
+        assert not np.any(cases.get(name)["amp"] == np.rint(cases.get(name)["amp"])), name
+        assert np.abs(cases.get(name)["x"].astype(np.int16)).max() <= 60, name
 
 
 @pytest.mark.parametrize("name", cases.NAMES)
@@ -162,6 +198,26 @@ def test_near_far_scene_with_oracle_search_and_tracking(capsys):
     assert abs(clean[7][1] - 4000) <= 1 and abs(clean[11][1] - 15000) <= 1
     assert clean[14][0] < s.acqThreshold and clean[19][0] < s.acqThreshold
     assert np.all(drop <= -25.0), drop
+
+
+def test_near_far_scene_behind_the_conditioning_stage_with_the_oracle(capsys):
+    """The claims of the resident path (tests/test_cancel_gpu.py) on the CPU: the scene's file carries a DC offset of 5 LSB,
+    the prepared record is the conditioning stage's numpy contract on it (the default settings: the offset removed, the rms
+    brought to 12 LSB); there the oracle's search detects PRN 1 and 3, and with both tracked and cancelled by the contract
+    its search of the cleaned record detects, of the PRNs that are not tracked, PRN 7 and 11 and no other."""
+    s = nf.settings()
+    prepared = nf.prepared_record()
+    assert abs(float(nf.offset_file().mean()) - nf.DC_OFFSET) < 0.5 and abs(float(prepared.mean())) < 0.05
+    assert abs(float(prepared.std()) - nf.COND["condTargetRms"]) < 0.5
+    assert prepared.size == nf.MS_TRACKED * (s.samplesPerCode + 2) + 2 * s.samplesPerCode      # what postProcessing() reads
+    raw, chans, series, clean = nf.oracle_run_prepared()
+    with capsys.disabled():
+        print("\n[cancel] behind the conditioning stage, peakMetric of PRN %s: raw %s, cleaned %s, code phases %s" % (
+            nf.SEARCHED, " ".join("%.2f" % raw[p][0] for p in nf.SEARCHED), " ".join("%.2f" % clean[p][0] for p in nf.SEARCHED),
+            [int(clean[p][1]) for p in nf.WEAK]))
+    assert nf.detected(raw, s) == [1, 3] and [c[0] for c in chans] == [1, 3]
+    assert [p for p in nf.detected(clean, s) if p not in nf.STRONG] == [7, 11]
+    assert abs(clean[7][1] - 4000) <= 1 and abs(clean[11][1] - 15000) <= 1
 
 
 def test_settings_and_command_line_surface():

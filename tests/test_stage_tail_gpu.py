@@ -7,14 +7,16 @@ carry over into the next one.  What the stages compute is the business of their 
 Records are two tiles plus five bytes (elements, frames) of the stage, as its *_tile() reports it; the notch has the
 converter's tile, and the converter takes one byte more, because an I/Q record holds whole pairs.
 
-All eight counting entry points - requantize, condition, unpack, decimate, resample, combine, combine_blocks, excise_record
-- count in ONE area of the context (csrc/sgx_count.h, SgxStage::count), so the last test runs every one of them behind
-every other on one context and holds every count and every byte against the stage's spec.  Run with -m gpu."""
+All nine counting entry points - requantize, condition, unpack, decimate, resample, combine, combine_blocks, excise_record,
+if_cancel - count in ONE area of the context (csrc/sgx_count.h, SgxStage::count), so the last test runs every one of them
+behind every other on one context and holds every count and every byte against the stage's spec.  Run with -m gpu."""
 import numpy as np
 import pytest
 
 import array_block_spec
 import array_spec
+import cancel_cases
+import cancel_spec
 import cond_spec
 import decim_spec
 import excise_cases
@@ -23,6 +25,7 @@ import requant_spec
 import resamp_spec
 import unpack_spec
 from conftest import pkg
+from oracle import softgnss_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
@@ -203,15 +206,19 @@ def reads(call, *names):
 
 def counter_area_cases():
     """(name, input bytes, call on a context and a record -> (record, its counters), (spec bytes, spec counters)) of all
-    eight counting entry points, which share ONE counter area (csrc/sgx_count.h): the three cases of clip_area_cases() as
+    nine counting entry points, which share ONE counter area (csrc/sgx_count.h): the three cases of clip_area_cases() as
     they stand, and one case each of the requantiser (clipped), the conditioning stage (blanked, clipped), the unpacker at
     2 and at 4 bits (4 and 16 code counts), the block combiner (clipped) and the excision (bins_cut, segments_cut, clipped)
     on outputs of three tiles plus 17 bytes (one more for I/Q; the excision: three tiles of its plan at N = 64 and a
     little of the next, excise_cases.tile_span).  Then one case per shape of the publish with more workgroups than the
     256 slots of the area, so that a slot takes the atomics of two workgroups: 257 tiles plus 17 bytes of the requantiser
-    (one counter), the conditioning stage (two), the 4-bit unpacker (sixteen) and the excision (per wave).  Expected bytes
+    (one counter), the conditioning stage (two), the 4-bit unpacker (sixteen) and the excision (per wave).  Last the
+    cancellation (clipped), whose blocks are those of hand-made channels at 2.046 Msps (cancel_cases.handmade) at ten times
+    a sensible amplitude: three tiles plus 17 bytes, and 257 tiles plus 17 bytes with one channel's blocks in tile 0 and
+    the other's in tile 256, both of which clip - two workgroups add into slot 0.  Expected bytes
     and counters come from the stage's spec module alone, and on those alone: every counter of every case is above zero
-    but the resampling's, which is zero; the excision's cases keep excise_spec.MARGIN as tests/excise_cases.py asks."""
+    but the resampling's, which is zero; the excision's cases keep excise_spec.MARGIN as tests/excise_cases.py asks; the
+    cancellation's cases have no rounding decision (cancel_spec.decisions), so their bytes are compared exactly too."""
     n = pkg()._native
     rng = np.random.default_rng(11)
     cases = [(name, x, reads(call, "clipped"), (y, (count,))) for name, x, call, (y, count) in clip_area_cases()]
@@ -262,17 +269,38 @@ def counter_area_cases():
             return out, (got["bins_cut"], got["segments_cut"], got["clipped"])
         return ("excise" + tag, x, call, (y, (info["bins_cut"], info["segments_cut"], info["clipped"])))
 
+    def cancel(tag, tiles, starts, seed):
+        tile = cancel_cases.TILE
+        rows = [(prn, dop, cp, cancel_cases.CHIP_RATE + np.array([1.5, -2.5])) for prn, dop, cp in zip((9, 23), (1800.0, -3300.0),
+                                                                                                     starts)]
+        c = cancel_cases.handmade_case(seed, rows, 2, 250.0, length=tiles * tile + 17)
+        assert bytes(n.settings_struct(c["s"])) == bytes(n.settings_struct(cancel_settings()))
+        y, v, clipped, covered = cancel_spec.cancel(c["s"], c["x"], 0, c["chans"], c["series"], None, c["amp"])
+        assert not cancel_spec.decisions(v, covered).any(), "cancel%s: a rounding decision - take another seed" % tag
+        over = np.flatnonzero(covered & (np.abs(np.rint(v)) > 127.0)) // tile
+        assert over.size == clipped and set(over.tolist()) >= set(s // tile for s in starts), (tag, set(over.tolist()))
+        call = reads(lambda ctx, r: ctx.if_cancel(r, c["chans"], c["series"], c["amp"]), "clipped")
+        return ("cancel" + tag, c["x"], call, (y, (clipped,)))
+
     cases += [requantize("", 3), condition("", 3), unpack("", 2, 3), unpack("", 4, 3), combine_blocks(), excise("", 3),
-              requantize("_257", 257), condition("_257", 257), unpack("_257", 4, 257), excise("_257", 257)]
+              requantize("_257", 257), condition("_257", 257), unpack("_257", 4, 257), excise("_257", 257),
+              cancel("", 3, (7, 4096 + 2100), 31), cancel("_257", 257, (1, 256 * 4096 + 3), 32)]
     sizes = {"requantize": 3 * n.requant_tile() + 17, "condition": 3 * n.cond_tile() + 17, "unpack2": 3 * n.unpack_tile() + 17,
              "unpack4": 3 * n.unpack_tile() + 17, "combine_blocks": 3 * n.combine_tile() + 18,
              "requantize_257": 257 * n.requant_tile() + 17, "condition_257": 257 * n.cond_tile() + 17,
-             "unpack4_257": 257 * n.unpack_tile() + 17}
+             "unpack4_257": 257 * n.unpack_tile() + 17, "cancel": 3 * cancel_cases.TILE + 17,
+             "cancel_257": 257 * cancel_cases.TILE + 17}
     for name, x, _, (y, counts) in cases:
         assert y.size == sizes.get(name, y.size), (name, y.size)
         assert all(v == 0 for v in counts) if name == "resample" else all(v > 0 for v in counts), (name, counts)
-    assert [len(counts) for _, _, _, (_, counts) in cases] == [1, 1, 1, 1, 2, 4, 16, 1, 3, 1, 2, 16, 3]
+    assert [len(counts) for _, _, _, (_, counts) in cases] == [1, 1, 1, 1, 2, 4, 16, 1, 3, 1, 2, 16, 3, 1, 1]
     return cases
+
+
+def cancel_settings():
+    """The settings of the context the walk runs on: the cancellation reads the sampling frequency, and at 2.046 Msps a block
+    is half a tile.  No other stage of the walk reads a setting."""
+    return orc.OracleSettings(samplingFreq=cancel_cases.LOW_FS, IF=cancel_cases.LOW_IF, numberOfChannels=2, msToProcess=2.0)
 
 
 def every_ordered_pair(n):
@@ -290,13 +318,15 @@ def every_ordered_pair(n):
     return walk
 
 
-def test_the_fir_stages_share_one_clip_area_and_each_count_is_its_own(ctx):
+def test_the_fir_stages_share_one_clip_area_and_each_count_is_its_own():
     """Every stage that counts shares one counter area, so a call could read what the call before it left there.  On one
-    context ALL ordered pairs (first, second) of the thirteen cases of counter_area_cases() run, a case behind itself
-    included: the calls follow a walk on which every pair occurs once as neighbours, 170 calls, and every call's record
+    context ALL ordered pairs (first, second) of the fifteen cases of counter_area_cases() run, a case behind itself
+    included: the calls follow a walk on which every pair occurs once as neighbours, 226 calls, and every call's record
     equals its spec in bytes and every one of its counters the spec's - among them each stage with one counter behind the
-    4-bit unpacker, which fills all 16 words of a slot, and behind the excision, which fills three."""
+    4-bit unpacker, which fills all 16 words of a slot, and behind the excision, which fills three.  The context has the
+    cancellation's sampling frequency (cancel_settings)."""
     cases = counter_area_cases()
+    ctx = pkg().engine.get_context(cancel_settings(), 0)
     for i in every_ordered_pair(len(cases)):
         name, x, call, (want, counts) = cases[i]
         rec = ctx.upload(x)
