@@ -41,6 +41,12 @@ extern "C" {
                                of the record); the caller runs sgx_acquire_end, preRun and sgx_track_ex instead (nothing
                                has been lost: the search's results are still pending).  A launch that has to be repeated
                                is repeated on the table the device made, inside the call */
+#define SGX_E_SILENT   -8   /* tracking: a channel went silent - the six sums of one block are exactly zero (a zero-filled
+                               stretch of the record), both discriminators are 0 / 0 and the next block has no length: the
+                               reference's ValueError "cannot convert float NaN to integer" (tracking.py:148-151).  out and
+                               ms_done are complete as for SGX_OK: the silent block is the channel's last row.  (Rates that are
+                               NaN behind a block whose sums are not zero - diverged loop filters - end the same way;
+                               the text says which.) */
 
 #define SGX_NUM_SERIES 13   /* per-ms tracking series, in this order (tracking.py:255-275):
                                absoluteSample codeFreq carrFreq I_P I_E I_L Q_E Q_P Q_L
@@ -261,6 +267,8 @@ int sgx_acquire_coherent_plan(const sgx_settings* s, const sgx_acq_params* p, in
  *                        waits once, for everything.  out = [n_ch][13][ms] (pinned memory from sgx_host_alloc), ms_done =
  *                        [n_ch]; the channel table as preRun made it comes back in prn / acquiredFreq / codePhase [n_ch]
  *                        (prn 0 = off; the first *n_active channels are on, in order of descending metric).  Returns
+ *                        SGX_E_SILENT as sgx_track: out, ms_done AND the table (prn, acquiredFreq, codePhase, n_active) are
+ *                        complete, the rows of out in the table's order.
  *                        SGX_E_DEFER when the queued sequence does not apply (see the code's comment; n_ch > 8) - then nothing has
  *                        been tracked and the eager calls do the work; SGX_E_INDEX / SGX_E_RANGE where the SEARCH failed
  *                        the way the reference's acquire() raises (no channel was tracked).
@@ -283,6 +291,9 @@ int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, int3
  * out is [n_ch][SGX_NUM_SERIES][ms] float64, pre-filled exactly like tracking.py:65-94 (0 or
  * +Inf) for entries never reached; ms_done[ch] = blocks completed (== ms unless the record ran
  * out, the reference's short-read exit tracking.py:159-163; channels with prn == 0 report 0).
+ * SGX_E_SILENT, whichever kernel ran: a channel stopped because block ms_done[ch] - 1 summed to exactly zero and left its
+ * rates NaN (the text names the lowest such channel and the block that could not start).  Decided on the host from the
+ * series; a launch that ended early for another reason keeps its own report.
  */
 int sgx_track(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
               const sgx_chan_init* ch, int32_t n_ch, int32_t ms,

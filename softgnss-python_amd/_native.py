@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SGX_LIB") or os.path.join(HERE, "lib", "libsgx.so")  
 
 SGX_OK = 0
 SGX_E_ARG, SGX_E_HIP, SGX_E_NOMEM, SGX_E_INDEX, SGX_E_RCCL, SGX_E_RANGE, SGX_E_DEFER = -1, -2, -3, -4, -5, -6, -7
+SGX_E_SILENT = -8
 NUM_SERIES = 13
 DT_INT8, DT_INT16, DT_UINT8, DT_FLOAT32 = 0, 1, 2, 3   # sgx_track_ex data_type (include/sgx.h)
 DT_FLOAT64, DT_UINT16, DT_INT32, DT_UINT32, DT_INT64, DT_UINT64, DT_FLOAT16 = 4, 5, 6, 7, 8, 9, 10
@@ -27,6 +28,18 @@ class SgxError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "libsgx error %d: %s" % (code, msg))
         self.code = code
+
+
+class SilentChannelError(ValueError):
+    """The reference's ValueError on a channel that went silent (SGX_E_SILENT: a block of exactly zero sums leaves the
+    rates NaN, and int(np.ceil(nan)) of the next block's length raises, tracking.py:148-151).  Where the call had
+    results to return they are attached: .series float64[n_ch, 13, ms] and .ms_done int32[n_ch], complete as after a
+    call that returned (the silent block is the channel's last row, the rows behind it hold the pre-fill)."""
+
+    def __init__(self, msg, series=None, ms_done=None):
+        ValueError.__init__(self, msg)
+        self.code = SGX_E_SILENT
+        self.series, self.ms_done = series, ms_done
 
 
 class Settings(C.Structure):
@@ -297,6 +310,8 @@ def check(code):
         msg = last_error()
         if code == SGX_E_INDEX:
             raise IndexError(msg)          # the reference raises IndexError here (acquisition.py:152-162)
+        if code == SGX_E_SILENT:
+            raise SilentChannelError(msg)  # the reference raises ValueError here (tracking.py:148-151)
         raise SgxError(code, msg)
 
 
@@ -1151,6 +1166,10 @@ class Context(object):
                                      int(data_type), _ptr(prn), _ptr(freq), _ptr(cph), C.byref(n_act))
         if rc == SGX_E_DEFER:
             return None
+        if rc == SGX_E_SILENT:     # (the table is complete too: the rows of .series are its first n_active channels)
+            e = SilentChannelError(last_error(), out, done)
+            e.table = (prn, freq, cph, n_act.value)
+            raise e
         check(rc)
         return out, done, prn, freq, cph, n_act.value
 
@@ -1497,6 +1516,7 @@ class Context(object):
 
     def track(self, rec, chans, ms, rec_file_offset=0, data_type=DT_INT8):
         """chans: sequence of (prn, acquiredFreq, codePhase). Returns (series[n_ch,13,ms], ms_done).
+        SilentChannelError (a ValueError, as in the reference) where a channel met a block of exactly zero sums.
         data_type DT_INT16: `rec` holds the BYTES of a little-endian int16 file (see sgx_track_ex in include/sgx.h)."""
         n = len(chans)
         arr = (ChanInit * n)()
@@ -1504,8 +1524,11 @@ class Context(object):
             arr[i] = ChanInit(float(f), float(cp), int(prn), 0)
         out = pinned_empty((n, NUM_SERIES, int(ms)))
         done = np.zeros(n, dtype=np.int32)
-        check(lib().sgx_track_ex(self._h, rec._h, int(rec_file_offset), C.cast(arr, _P), n, int(ms), _ptr(out),
-                                 _ptr(done), int(data_type)))
+        rc = lib().sgx_track_ex(self._h, rec._h, int(rec_file_offset), C.cast(arr, _P), n, int(ms), _ptr(out),
+                                _ptr(done), int(data_type))
+        if rc == SGX_E_SILENT:     # a channel went silent: the reference's ValueError, with what was tracked until then
+            raise SilentChannelError(last_error(), out, done)
+        check(rc)
         return out, done
 
 

@@ -13,6 +13,7 @@
 // HBM-resident scratch replaces the reference's per-PRN numpy temporaries.
 // A samplesPerCode with a prime factor above 31 has no transform of its own length here: its circular correlation runs
 // inside a longer one (acquire_passes, "padded length").
+#include <cmath>
 #include <math.h>
 #include <chrono>
 
@@ -431,6 +432,9 @@ struct AcqCall {
     long long N;
     double ts, tc;
     int spc;
+    // bit b: block b of the coarse search (window b of a coherent one) holds a sample that is not finite - an fp64 signal
+    // only; acq_peak_bin takes that block's rows as the reference's NaN maxima
+    unsigned long long bad_rows;
 };
 static AcqCall acq_call(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* prn0, int32_t n_prn, const AcqOut& out,
                         const AcqEnv& env) {
@@ -446,6 +450,7 @@ static AcqCall acq_call(sgx_ctx* c, SgxSig x, size_t n_samples, const int32_t* p
     a.ts = 1.0 / c->s.samplingFreq;
     a.tc = 1.0 / c->s.codeFreqBasis;
     a.spc = (int)llround(c->s.samplingFreq / c->s.codeFreqBasis);
+    a.bad_rows = 0ull;
     return a;
 }
 // The reference's Doppler grid (acquisition.py:68,99-101): bin k at IF - band / 2 + 500 k
@@ -493,6 +498,23 @@ struct AcqSource {
     const double* signal;
     size_t n_samples;
 };
+// Bit w: window w of the search - ms_per_row code periods each, `rows` of them (at most 64) - holds a sample that is not
+// finite.  A record's samples are integers; the caller's fp64 signal is looked at on the host, where it lies.  (64 bits hold
+// every search: n_blocks <= 64, acq_open_source, and ACQ_COH_MAX_WINDOWS = 64.)
+static unsigned long long acq_bad_rows(const AcqSource& src, long long N, int ms_per_row, int rows) {
+    if (src.r) return 0ull;
+    unsigned long long bad = 0ull;
+    const size_t len = (size_t)N * (size_t)ms_per_row;
+    for (int w = 0; w < rows && w < 64; ++w) {
+        const size_t lo = (size_t)w * len, hi = lo + len < src.n_samples ? lo + len : src.n_samples;
+        for (size_t i = lo; i < hi; ++i)
+            if (!std::isfinite(src.signal[i])) {
+                bad |= 1ull << w;
+                break;
+            }
+    }
+    return bad;
+}
 static int acq_source_sig(sgx_ctx* c, const AcqSource& src, SgxSig* x) {
     return src.r ? acq_record_sig(c, src.r, src.offset, src.n_samples, x) : acq_upload_f64(c, src.signal, src.n_samples, x);
 }
@@ -848,11 +870,11 @@ static int acq_peaks_publish(const AcqCall& a, const AcqCorr& k, unsigned long l
         pub.det = &dsm->det;
         acq_rowtop2_peak_kernel<<<k.rows_out_all, 64, 0, st>>>(k.t2b1, k.t2b2, k.t2i1, k.nres, k.rowmax, k.rowarg, dsm->arrived,
                                                                a.n_prn, k.out_per_prn, k.n_bins, k.n_blocks, k.noncoh, a.N, a.spc,
-                                                               &dsm->peak_out, dsm->second, pub);
+                                                               &dsm->peak_out, dsm->second, pub, a.bad_rows);
     } else {
         acq_rowmax_peak_kernel<<<k.rows_out_all, 64, 0, st>>>(k.pmax, k.parg, k.nblk, k.rowmax, k.rowarg, dsm->arrived, a.n_prn,
                                                               k.out_per_prn, k.n_bins, k.n_blocks, k.noncoh, a.N, a.spc,
-                                                              &dsm->peak_out, &dsm->second_args, dsm->row_map);
+                                                              &dsm->peak_out, &dsm->second_args, dsm->row_map, a.bad_rows);
         // the rows the second-peak search reads, transformed again
         Fft4Fuse fu;
         fu.mul_x = c->d_fwd;
@@ -1042,9 +1064,11 @@ static int acquire_fine(const AcqCall& a, const AcqDets& det, long long* d_sum, 
     hipEventRecord(c->ev[2], st);
     SGX_HIP(hipStreamSynchronize(st));
     for (int d = 0; d < n_det; ++d) {
-        double bv = -1.0;
-        long long bi = 0;
-        for (int b = 0; b < nblk; ++b) {
+        // (from the first partial, as the device-led fold of fine_rows_kernel: where every magnitude is NaN - a sample that
+        // is not finite behind the coarse blocks - the partials are (-1, first index searched), numpy's argmax of NaN)
+        double bv = h_pv[d * nblk];
+        long long bi = h_pi[d * nblk];
+        for (int b = 1; b < nblk; ++b) {
             const double v = h_pv[d * nblk + b];
             const long long i = h_pi[d * nblk + b];
             if (v > bv || (v == bv && i < bi)) {
@@ -1200,7 +1224,7 @@ static void acq_passes_peaks(const AcqCall& a, const AcqPasses& k, int np, PeakO
         AcqCand cand = {-1.0, -1, 0, 0};
         for (int b = 0; b < k.n_bins; ++b)
             cand = acq_peak_join(cand, acq_peak_bin(hsm->rowmax + pi * k.out_per_prn, hsm->rowarg + pi * k.out_per_prn, k.n_bins,
-                                                    k.n_blocks, k.noncoh != 0, b));
+                                                    k.n_blocks, k.noncoh != 0, b, a.bad_rows));
         po->peak[pi] = cand.v;
         po->cph[pi] = cand.a;
         po->fbi[pi] = cand.k;
@@ -1440,7 +1464,9 @@ static int acquire_source(sgx_ctx* c, const AcqSource& src, const int32_t* prn0,
     SgxSig x;
     const int rc = acq_open_source(c, src, prn0, n_prn, n_blocks, &x);
     if (rc != SGX_OK) return rc;
-    return acquire_any(acq_call(c, x, src.n_samples, prn0, n_prn, out, env), n_blocks, noncoh);
+    AcqCall a = acq_call(c, x, src.n_samples, prn0, n_prn, out, env);
+    a.bad_rows = acq_bad_rows(src, a.N, 1, n_blocks);
+    return acquire_any(a, n_blocks, noncoh);
 }
 extern "C" int sgx_acquire(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
                            int32_t n_prn, int32_t n_blocks, int32_t noncoh, double* carrFreq, double* codePhase,
@@ -1637,7 +1663,9 @@ static int acquire_coherent_source(sgx_ctx* c, const AcqSource& src, const int32
     if (legacy) return acquire_source(c, src, prn0, n_prn, g.M, g.noncoh, out, env);
     SgxSig x;
     if ((rc = acq_source_sig(c, src, &x)) != SGX_OK) return rc;
-    return acquire_coherent_any(acq_call(c, x, src.n_samples, prn0, n_prn, out, env), g);
+    AcqCall a = acq_call(c, x, src.n_samples, prn0, n_prn, out, env);
+    a.bad_rows = acq_bad_rows(src, a.N, g.T, g.M);
+    return acquire_coherent_any(a, g);
 }
 extern "C" int sgx_acquire_coherent(sgx_ctx* c, const sgx_if* r, size_t offset, size_t n_samples, const int32_t* prn0,
                                     int32_t n_prn, const sgx_acq_params* p, double* carrFreq, double* codePhase,

@@ -490,22 +490,32 @@ struct AcqCand {
 #define ACQ_LD(p) (*(p))
 #endif
 #define ACQ_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// (bad: bit b set - block b of the signal holds a sample that is not finite, so every power of the block is NaN in the
+// reference (numpy's max then is NaN, its argmax 0); the kernels' "v > best" reductions skip NaN, so the block's rows are
+// taken as (NaN, 0) here, where the reference's block rule meets them.  Only an fp64 signal can set a bit.)
 __host__ __device__ static inline AcqCand acq_peak_bin(const double* __restrict__ rowmax, const int* __restrict__ rowarg,
-                                                       int n_bins, int n_blocks, bool noncoh, int k) {
+                                                       int n_bins, int n_blocks, bool noncoh, int k,
+                                                       unsigned long long bad = 0ull) {
     int row = k, bsel = 0;
+    bool nan_row = noncoh && bad != 0ull;
     if (!noncoh) {
         int best = 0;   // acquisition.py:129-133 generalised left to right, later block wins ties
         for (int b = 1; b < n_blocks; ++b) {
             const double vb = ACQ_LD(rowmax + best * n_bins + k);
             const double vn = ACQ_LD(rowmax + b * n_bins + k);
-            if (!(vb > vn)) best = b;
+            if (!(vb > vn) || (((bad >> best) | (bad >> b)) & 1ull)) best = b;   // (a NaN maximum on either side: not larger)
         }
         row = best * n_bins + k;
         bsel = best;
+        nan_row = ((bad >> best) & 1ull) != 0ull;
     }
     AcqCand c;
     c.v = ACQ_LD(rowmax + row);
     c.a = ACQ_LD(rowarg + row);
+    if (nan_row) {
+        c.v = __builtin_nan("");
+        c.a = 0;
+    }
     c.k = k;
     c.b = bsel;
     return c;
@@ -608,12 +618,12 @@ __global__ __launch_bounds__(64) void acq_publish_kernel(const PeakOut* __restri
 // The peak of one PRN, a lane per Doppler bin (one lane per PRN scanning its rows was a chain of dependent loads: 12 us);
 // lane 0 holds the result.
 __device__ __forceinline__ AcqCand acq_peak_reduce(const double* __restrict__ pm, const int* __restrict__ pa, int lane,
-                                                   int n_bins, int n_blocks, int noncoh) {
+                                                   int n_bins, int n_blocks, int noncoh, unsigned long long bad) {
     AcqCand c;
     c.v = -1.0;
     c.k = -1;
     c.a = c.b = 0;
-    for (int k = lane; k < n_bins; k += 64) c = acq_peak_join(c, acq_peak_bin(pm, pa, n_bins, n_blocks, noncoh != 0, k));
+    for (int k = lane; k < n_bins; k += 64) c = acq_peak_join(c, acq_peak_bin(pm, pa, n_bins, n_blocks, noncoh != 0, k, bad));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         AcqCand o;
@@ -627,8 +637,8 @@ __device__ __forceinline__ AcqCand acq_peak_reduce(const double* __restrict__ pm
 }
 // ... and on every lane of the wave
 __device__ __forceinline__ AcqCand acq_peak_scan(const double* __restrict__ pm, const int* __restrict__ pa, int lane,
-                                                 int n_bins, int n_blocks, int noncoh) {
-    AcqCand c = acq_peak_reduce(pm, pa, lane, n_bins, n_blocks, noncoh);
+                                                 int n_bins, int n_blocks, int noncoh, unsigned long long bad) {
+    AcqCand c = acq_peak_reduce(pm, pa, lane, n_bins, n_blocks, noncoh, bad);
     c.v = __shfl(c.v, 0);
     c.k = __shfl(c.k, 0);
     c.a = __shfl(c.a, 0);
@@ -640,7 +650,7 @@ __device__ __forceinline__ AcqCand acq_peak_scan(const double* __restrict__ pm, 
 __device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, const int* __restrict__ rowarg, int pi,
                                              int lane, int n_prn, int out_per_prn, int n_bins, int n_blocks, int noncoh,
                                              long long N, int spc, PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
-                                             int2* __restrict__ row_map) {
+                                             int2* __restrict__ row_map, unsigned long long bad_rows) {
     if (pi >= n_prn) {
         if (lane == 0) {
             sa->row[pi] = -1;
@@ -649,7 +659,7 @@ __device__ __forceinline__ void acq_peak_one(const double* __restrict__ rowmax, 
         return;
     }
     const AcqCand c = acq_peak_reduce(rowmax + (long long)pi * out_per_prn, rowarg + (long long)pi * out_per_prn, lane, n_bins,
-                                      n_blocks, noncoh);
+                                      n_blocks, noncoh, bad_rows);
     if (lane != 0) return;
     int lo0, hi0, lo1, hi1;
     const int bad = acq_peak_ranges(c.a, N, spc, &lo0, &hi0, &lo1, &hi1);
@@ -698,13 +708,13 @@ __global__ __launch_bounds__(64) void acq_rowmax_peak_kernel(const double* __res
                                                              int* __restrict__ arrived, int n_prn, int out_per_prn,
                                                              int n_bins, int n_blocks, int noncoh, long long N, int spc,
                                                              PeakOut* __restrict__ po, SecondArgs* __restrict__ sa,
-                                                             int2* __restrict__ row_map) {
+                                                             int2* __restrict__ row_map, unsigned long long bad_rows) {
     const int row = blockIdx.x, lane = threadIdx.x;
     int pi;
     if (!acq_row_finish(pmax, parg, nblk, row, lane, rowmax, rowarg, arrived, out_per_prn, &pi)) return;
-    acq_peak_one(rowmax, rowarg, pi, lane, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map);
+    acq_peak_one(rowmax, rowarg, pi, lane, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map, bad_rows);
     if (pi == n_prn - 1 && n_prn + lane < 32)
-        acq_peak_one(rowmax, rowarg, n_prn + lane, 0, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map);
+        acq_peak_one(rowmax, rowarg, n_prn + lane, 0, n_prn, out_per_prn, n_bins, n_blocks, noncoh, N, spc, po, sa, row_map, bad_rows);
 }
 
 struct PublishArgs {
@@ -728,12 +738,12 @@ __global__ __launch_bounds__(64) void acq_rowtop2_peak_kernel(const double* __re
                                                               int* __restrict__ arrived, int n_prn, int out_per_prn,
                                                               int n_bins, int n_blocks, int noncoh, long long N, int spc,
                                                               PeakOut* __restrict__ po, double* __restrict__ second,
-                                                              PublishArgs pub) {
+                                                              PublishArgs pub, unsigned long long bad_rows) {
     const int row = blockIdx.x, lane = threadIdx.x;
     int pi;
     if (!acq_row_finish(b1, i1, nres, row, lane, rowmax, rowarg, arrived, out_per_prn, &pi)) return;
     const AcqCand c = acq_peak_scan(rowmax + (long long)pi * out_per_prn, rowarg + (long long)pi * out_per_prn, lane, n_bins,
-                                    n_blocks, noncoh);
+                                    n_blocks, noncoh, bad_rows);
     int lo0, hi0, lo1, hi1;
     const int bad = acq_peak_ranges(c.a, N, spc, &lo0, &hi0, &lo1, &hi1);
     double sec = 0.0;

@@ -269,6 +269,7 @@ struct TrkCall {
     TrkLaunch L;                 // the last launch ...
     hipError_t e;                // ... its status (hipSuccess before the first) ...
     int h_err;                   // ... and its error word: 0, or 1 + the channel that timed out
+    int range_ch1;               // 1 + the channel that reached a block beyond the launch's units (0: none); trk_diagnose
     void stamp(const char* what) const {
         if (E.trace) fprintf(stderr, "[sgx step trace] %-28s %8.1f us\n", what,
                              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
@@ -439,10 +440,11 @@ static int trk_repeat(TrkCall& T, int launch, const int words[2], bool& again) {
     h_err &= ~TRK_ERR_PLACE;
     if ((h_err & TRK_ERR_RANGE) == 0) h_err &= 0xFFFF;
     if (h_err & TRK_ERR_RANGE) {
-        sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
-                      "provides (the code NCO left its plausible range; dllNoiseBandwidth %g)",
-                      (words[1] ? words[1] : (h_err & 0xFFFF)) - 1, L.n_units, TRK_UNIT, T.c->s.dllNoiseBandwidth);
-        return SGX_E_RANGE;
+        // (every workgroup has retired: the series and ms_done are collected first, trk_diagnose then says what happened)
+        T.range_ch1 = words[1] ? words[1] : (h_err & 0xFFFF);
+        if (T.range_ch1 < 1) T.range_ch1 = 1;
+        h_err = 0;
+        return SGX_OK;
     }
     if (h_err == 0 || L.split == 1) return SGX_OK;
     // a member timed out (bounded spins) waiting for the others - something else occupies the CUs: one workgroup per channel
@@ -613,6 +615,51 @@ static int trk_finish(TrkCall& T) {
     return SGX_OK;
 }
 
+// Why a launch that completed ended a channel early, from what the kernels write anyway (nothing is added to a block chain).
+// A block whose six sums are exactly zero - a zero-filled stretch of the record - makes both discriminators 0 / 0: that
+// block is recorded with NaN rates, and no kernel starts the next one (a NaN step fails every kernel's test of the block
+// length: prep_code's stop, the latency kernels' (unsigned)(blk - 1) >= lim).  The reference dies there in
+// int(np.ceil(nan)) (tracking.py:148-151): one report for every kernel, SGX_E_SILENT.  A channel whose last row is finite
+// ran out of record (ms_done says so, SGX_OK) or reached a block beyond the launch's units (SGX_E_RANGE).
+// Why no kernel reads another block behind the NaN one, per kernel:
+//   trk3_kernel, trk2_kernel  the next block's length is (int)ceil(q) of a NaN quotient - 0 on the device, which the evaluator
+//       test of sgx_block_length holds (tests/test_trk_math_gpu.py) - so (unsigned)(blk - 1) >= lim posts stop 1 with the
+//       parameters; every role tests stop before it touches the block (the speculative pass of trk3 ran on block k's finite
+//       rates, and every load address is an integer position clamped to the allocation).  Their per-block chains are left as
+//       they are: unlike prep_code they have no test of the step itself.
+//   trk_kernel_tp, _multi, _any (per-sample), the float instances  prep_code posts stop = 1 for a step that is not > 0 (tested on
+//       the step, not on what (int) makes of NaN), and the loops test stop first, before a ramp or an address is formed.
+static int trk_diagnose(const TrkCall& T) {
+    const StepLook* slook = &T.c->h_look->step;   // (chained: preRun's table)
+    for (int i = 0; i < T.n_ch; ++i) {
+        if (T.chained ? slook->prn[i] == 0 : T.ch[i].prn == 0) continue;
+        const int dn = T.ms_done[i];
+        if (dn < 1 || dn >= T.ms) continue;
+        const double* row = T.out + (size_t)i * SGX_NUM_SERIES * (size_t)T.ms + (size_t)(dn - 1);
+        const double codeFreq = row[(size_t)T.ms];
+        if (codeFreq != codeFreq) {
+            bool zero = true;   // (the six sums of the block, series 3 .. 8)
+            for (int sidx = 3; sidx <= 8; ++sidx) zero = zero && row[(size_t)sidx * (size_t)T.ms] == 0.0;
+            if (zero)
+                sgx_set_error("ValueError: cannot convert float NaN to integer: channel %d went silent - the six sums of its "
+                              "block %d are exactly zero (a zero-filled stretch of the record), the loop filters' rates are "
+                              "NaN, and block %d has no length", i, dn - 1, dn);
+            else   // (NaN some other way - a loop filter that left the finite numbers: the reference dies at the same place)
+                sgx_set_error("ValueError: cannot convert float NaN to integer: channel %d - the loop filters' rates are NaN "
+                              "after block %d (its sums are not zero: the filters diverged), and block %d has no length",
+                              i, dn - 1, dn);
+            return SGX_E_SILENT;
+        }
+    }
+    if (T.range_ch1) {
+        sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
+                      "provides (the code NCO left its plausible range; dllNoiseBandwidth %g)",
+                      T.range_ch1 - 1, T.L.n_units, TRK_UNIT, T.c->s.dllNoiseBandwidth);
+        return SGX_E_RANGE;
+    }
+    return SGX_OK;
+}
+
 // sample_bytes: 1 (int8 record) or 2 (little-endian int16 record; the record handle holds the file's BYTES).  The
 // reference seeks skipNumberOfBytes + codePhase BYTES whatever the sample type and reports fid.tell(), also bytes
 // (tracking.py:107, 255); so a two-byte channel may start on an odd byte - its samples then straddle the file's - and
@@ -662,7 +709,8 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         rc = trk_launch_once(T, launch, reserved, again);
         if (rc != SGX_OK) return rc;
     }
-    return trk_finish(T);
+    rc = trk_finish(T);
+    return rc != SGX_OK ? rc : trk_diagnose(T);
 }
 
 int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
@@ -681,8 +729,9 @@ extern "C" int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_o
     if (data_type != SGX_DT_INT8 && data_type != SGX_DT_UINT8) return SGX_E_DEFER;
     const int rc = track_kind_impl(c, r, rec_file_offset, nullptr, n_ch, ms, out, ms_done, data_type,
                                    (long long)c->s.skipNumberOfBytes, 0.0, true);
-    if (rc != SGX_OK) return rc;
-    // (the stream has been synchronised: the page is complete)
+    if (rc != SGX_OK && rc != SGX_E_SILENT) return rc;
+    // (the stream has been synchronised: the page is complete - also for a silent channel, whose rows the caller reads with
+    // the table below)
     const StepLook* look = &c->h_look->step;
     if (look->n_ch != n_ch || look->flags != 0) return SGX_E_DEFER;   // a NaN metric, a failed search, a channel in front of
                                                                        // the record: nothing was tracked, the eager calls report it
@@ -692,7 +741,7 @@ extern "C" int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_o
         acquiredFreq[i] = look->acquiredFreq[i];
         codePhase[i] = look->codePhase[i];
     }
-    return SGX_OK;
+    return rc;
 }
 
 extern "C" int sgx_track(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch,

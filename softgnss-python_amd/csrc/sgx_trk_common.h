@@ -167,7 +167,8 @@ __device__ __forceinline__ void prep_code(const TrkConst& K, double codeFreq, do
     if (writer) {
         b.pos = pos;
         b.blk = blk;
-        b.stop = (blk <= 0 || pos + blk > (rec_len >= 0 ? rec_len : K.rec_len)) ? 1 : 0;
+        // (a step that is NaN, zero or negative has no block: said here, not left to what (int) makes of a NaN quotient)
+        b.stop = (!(step > 0.0) || blk <= 0 || pos + blk > (rec_len >= 0 ? rec_len : K.rec_len)) ? 1 : 0;
         b.startE = startE;
         b.stepE = stepE;
         b.startL = startL;

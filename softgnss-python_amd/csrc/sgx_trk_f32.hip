@@ -184,7 +184,7 @@ int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, cons
             hc[(size_t)i].codePhase = (double)((p0 - first) / 4 * sb);
         }
         rc = sgx_track_kind(c, &tmp, 0, hc.data(), n_ch, ms, out, ms_done, narrow8 ? SGX_DT_INT8 : SGX_DT_INT16, 0, 0.0);
-        if (rc == SGX_OK) {
+        if (rc == SGX_OK || rc == SGX_E_SILENT) {   // (a silent channel: out and ms_done are complete)
             // absoluteSample is fid.tell() in BYTES of the float file (tracking.py:255): integer-record bytes * 4 / sb
             // behind the window's first byte; the six correlator series carry the 2^k
             const double unscale = ldexp(1.0, -k);

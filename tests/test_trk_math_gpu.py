@@ -161,3 +161,21 @@ def test_block_length_of_a_degenerate_code_frequency_stops_the_kernels(ev):
         blk = ev("block_length", aa, cc, f, 1.0 / f)[0]
         inside = (blk >= 1) & (blk <= tm.LIM)
         assert not inside.any(), (fs, aa[inside], cc[inside], blk[inside])
+
+
+def test_a_degenerate_step_stops_prep_code(ev):
+    """the same for the kernels that go through prep_code (throughput, multi, per-sample, float, any-type): sgx_ceil_div of a
+    NaN, infinite, zero or negative step is no length 1 .. LIM, and prep_code posts stop = 1 for every such code frequency -
+    tested on the step itself, whatever the device's float -> int conversion makes of a NaN quotient"""
+    step = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, -1.023e6 / 38.192e6, -1e-300, 1e-300])
+    for a in (1023.0, 1022.99, np.nan):
+        blk = ev("ceil_div", np.full(step.size, a), step)[0]
+        assert not np.any((blk >= 1) & (blk <= tm.LIM)), (a, blk)
+    cf = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, -1.023e6, -1.0, -1e-300, -1e300, 1.023e6])
+    rem = np.array([0.0, 0.01])
+    for fs in tm.FS:
+        cc, rr = np.tile(cf, rem.size), np.repeat(rem, cf.size)
+        f, s = np.full(cc.size, fs), np.full(cc.size, 0.5)
+        stop = ev("prep_inv", cc, rr, f, s)[1]
+        sound = cc == 1.023e6                          # (the one code frequency of the list that has a block)
+        assert np.all(stop[~sound] == 1.0) and np.all(stop[sound] == 0.0), (fs, cc, rr, stop)

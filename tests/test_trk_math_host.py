@@ -76,3 +76,12 @@ def test_degenerate_values(built):
         f = np.full(cf.size, fs)
         blk = ev("block_length", np.full(cf.size, 1023.0), cf, f, 1.0 / f)[0]
         assert not np.any((blk >= 1) & (blk <= tm.LIM)), (fs, blk)
+
+
+def test_division_free_ceil_of_a_degenerate_step(built):
+    """sgx_ceil_div(a, step) with the step a NaN, infinite, zero or negative code frequency leaves (prep_code's block length
+    on a silent record): never a length a launch could run, 1 .. LIM"""
+    step = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, -1.023e6 / 38.192e6, -1e-300, 1e-300])
+    for a in (1023.0, 1022.99, np.nan):
+        blk = ev("ceil_div", np.full(step.size, a), step)[0]
+        assert not np.any((blk >= 1) & (blk <= tm.LIM)), (a, blk)
