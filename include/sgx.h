@@ -112,7 +112,7 @@ typedef struct sgx_timing {
     float synth_ms;          /* the generator kernel */
     float track_kernel;      /* which tracking kernel the last sgx_track ran: 2 latency-mode (sgx_trk2.hip), 3 throughput-mode
                                 (sgx_trk_tp.hip), 4 low-rate (sgx_trk_multi.hip), 5 speculative latency-mode (sgx_trk3.hip),
-                                6 per-sample, any sample type (sgx_trk_any.hip) */
+                                6 per-sample, any sample type (sgx_trk_any.hip); 7: sgx_track_coherent ran (sgx_trk_coh.hip) */
     float track_members;     /* workgroups per channel of that launch */
     float track_streamed;    /* 1: the kernel followed the watermark of a record that was still streaming in */
 } sgx_timing;
@@ -339,6 +339,46 @@ int sgx_track_ex(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
  *   members workgroups per channel (trk2_kernel with one workgroup per unit AND correlator arm: 3 x units) */
 int sgx_track_plan(const sgx_settings* s, int32_t data_type, int32_t n_ch, int32_t n_cus, int32_t float_in_range,
                    int32_t* kernel, int32_t* members);
+
+/* ---- Bit-aligned coherent tracking of weak signals (no reference counterpart; the contract in numpy is
+ * tests/coh_track_spec.py, the kernel csrc/sgx_trk_coh.hip) -------------------------------------------------------------
+ * Every block is sgx_track's block - its own length from remCodePhase and codeFreq, the reference's three ramps, a carrier
+ * that runs on through remCarrPhase, the six sums (tracking.py:148-219).  Only WHEN the loops are updated changes:
+ *   blocks k < k0    the reference's update after every block (tracking.py:223-251, PDI 0.001, the settings' loops).
+ *   bit sync         where bit_edge_in[ch] == -1, over the pull-in blocks k < pull_in_ms: with z = I_P + j Q_P, every
+ *                    hypothesis h in 0..19 adds z to a[h] from block h on and, at (k - h) % 20 == 19, adds |a[h]|^2 to
+ *                    E[h] and clears a[h]; behind block pull_in_ms - 1 the edge is the lowest h with the largest E[h].
+ *   k0               the smallest k >= pull_in_ms with (k - edge) % 20 == 0.  coherent_ms == 1: never.
+ *   hand-over        at the end of block k0 - 1 (if k0 < ms), behind its own update: oldCarrNco = the mean of carrNco over
+ *                    the last min(handover_ms, k0) blocks (added in ascending block order), oldCarrError = 0, carrFreq =
+ *                    carrFreqBasis + oldCarrNco; the same for the code loop (codeFreq = codeFreqBasis - oldCodeNco).
+ *   blocks k >= k0   groups of coherent_ms blocks: both NCO rates are held inside a group, the six sums of its blocks are
+ *                    added in block order, and behind its last block the reference's two discriminators are taken of the
+ *                    group sums and both filters run with PDI = coherent_ms x 0.001 and the coefficients of the
+ *                    parameters, in the reference's expressions.  A group that ms cuts short is never updated.
+ * out row k: absoluteSample and the six sums are block k's alone (bits, preambles, sgx_track_quality, sgx_replay_state and
+ * sgx_if_cancel read them as they read sgx_track's); codeFreq / carrFreq are the rates block k + 1 runs with (row k0 - 1:
+ * the handed-over ones); the four discriminator series hold the values of the latest update - they repeat inside a group.
+ * out (pre-fill, file positions) and ms_done as sgx_track; SGX_E_RANGE as there; SGX_E_SILENT where the six sums of an
+ * UPDATE (a block's before k0, a group's after) are exactly zero: that block is the channel's last row.
+ * bit_edge[ch]: the edge used or found (-1: the channel ended before it was found); coh_start[ch]: k0, or -1 where there
+ * is none (coherent_ms 1, no edge, a channel that is off); edge_energy[ch][20]: E (zeros where the edge was given).
+ * int8 records, resident before the launch (the call waits for the whole record; the kernel follows no watermark); one
+ * workgroup per channel at any sampling rate.  SGX_E_ARG before anything is launched: coherent_ms outside {1, 2, 4, 5, 10,
+ * 20}; pull_in_ms < 40, < 220 where an edge is to be found, or > ms; handover_ms outside 1..1000; an edge outside -1..19.
+ * sgx_get_timing: track_ms, track_kernel 7, track_members 1. */
+typedef struct sgx_coh_params {          /* 64 bytes */
+    double tau1_pll, tau2_pll;           /* the coherent loops: sgx_calc_loop_coef(cohPllBW, pllDampingRatio, 0.25) */
+    double tau1_dll, tau2_dll;           /* ... and sgx_calc_loop_coef(cohDllBW, dllDampingRatio, 1.0) */
+    int32_t coherent_ms;                 /* T: blocks per group */
+    int32_t pull_in_ms;                  /* P: blocks updated one by one in front of the first group */
+    int32_t handover_ms;                 /* H: blocks whose NCO values are averaged at the hand-over */
+    int32_t reserved;
+    double reserved2[2];
+} sgx_coh_params;
+int sgx_track_coherent(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
+                       int32_t ms, const sgx_coh_params* p, const int32_t* bit_edge_in, double* out, int32_t* ms_done,
+                       int32_t* bit_edge, int32_t* coh_start, double* edge_energy);
 
 /* How sgx_acquire cuts the correlation batch of a call into chunks over its (one or two) queues - the host's one rule
  * (csrc/sgx_acq.hip: acq_plan), without the SGX_ACQ_* overrides; no reference counterpart (acquisition.py:93-133 is one

@@ -84,6 +84,26 @@ def acq_params(coherent_ms=1, n_windows=2, noncoh=False, bin_step_hz=None):
     return AcqParams(int(coherent_ms), int(n_windows), 1 if noncoh else 0, 0, float(step if step is not None else 0.0))
 
 
+class CohParams(C.Structure):
+    """sgx_coh_params: the coherent loops and the schedule of sgx_track_coherent (64 bytes)."""
+    _fields_ = [("tau1_pll", C.c_double), ("tau2_pll", C.c_double), ("tau1_dll", C.c_double), ("tau2_dll", C.c_double),
+                ("coherent_ms", C.c_int32), ("pull_in_ms", C.c_int32), ("handover_ms", C.c_int32), ("reserved", C.c_int32),
+                ("reserved2", C.c_double * 2)]
+
+
+def coh_params(settings, coherent_ms=None, pull_in_ms=None, handover_ms=None):
+    """CohParams of a Settings-like object: trackCoherentMs, trackPullInMs, trackHandOverMs (or the arguments), and the
+    coherent loops' coefficients from cohPllNoiseBandwidth / cohDllNoiseBandwidth with the settings' damping ratios."""
+    t1p, t2p, t1d, t2d = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0)
+    check(lib().sgx_calc_loop_coef(float(getattr(settings, "cohPllNoiseBandwidth", 3.0)), float(settings.pllDampingRatio),
+                                   0.25, C.byref(t1p), C.byref(t2p)))
+    check(lib().sgx_calc_loop_coef(float(getattr(settings, "cohDllNoiseBandwidth", 1.0)), float(settings.dllDampingRatio),
+                                   1.0, C.byref(t1d), C.byref(t2d)))
+    pick = lambda given, name, default: int(getattr(settings, name, default) if given is None else given)
+    return CohParams(t1p.value, t2p.value, t1d.value, t2d.value, pick(coherent_ms, "trackCoherentMs", 1),
+                     pick(pull_in_ms, "trackPullInMs", 1000), pick(handover_ms, "trackHandOverMs", 100), 0)
+
+
 class LockParams(C.Structure):
     """sgx_lock_params: the C/N0 and lock-detector parameters of sgx_track_quality (32 bytes)."""
     _fields_ = [("T", C.c_double), ("cno_min", C.c_double), ("carr_lock_min", C.c_double), ("window", C.c_int32),
@@ -165,6 +185,7 @@ _PROTOS = {
     "sgx_track_chained": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
                                     C.POINTER(C.c_int32)]),
     "sgx_track": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    "sgx_track_coherent": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.POINTER(CohParams), _P, _P, _P, _P, _P, _P]),
     "sgx_track_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "sgx_track_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sgx_acquire_plan": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4),
@@ -1530,6 +1551,33 @@ class Context(object):
             raise SilentChannelError(last_error(), out, done)
         check(rc)
         return out, done
+
+    def track_coherent(self, rec, chans, ms, params, bit_edge=None, rec_file_offset=0, data_type=DT_INT8):
+        """sgx_track_coherent: bit-aligned coherent tracking of an int8 record.  chans: sequence of (prn, acquiredFreq,
+        codePhase); params: CohParams (coh_params); bit_edge: per channel -1 (find it, the default) or 0 .. 19.
+        Returns (series[n_ch,13,ms], ms_done, bit_edge, coh_start, edge_energy[n_ch,20]); SilentChannelError as track(),
+        the three further arrays attached to it as .bit_edge, .coh_start and .edge_energy."""
+        if int(data_type) != DT_INT8:
+            raise TypeError("coherent tracking reads int8 records: condition or requantise other sample types first "
+                            "(data_type %d)" % int(data_type))
+        n = len(chans)
+        arr = (ChanInit * n)()
+        for i, (prn, f, cp) in enumerate(chans):
+            arr[i] = ChanInit(float(f), float(cp), int(prn), 0)
+        edge_in = np.full(n, -1, dtype=np.int32) if bit_edge is None else np.ascontiguousarray(bit_edge, dtype=np.int32)
+        if edge_in.shape != (n,):
+            raise ValueError("bit_edge holds one value per channel")
+        out = pinned_empty((n, NUM_SERIES, int(ms)))
+        done, edge, start = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        energy = np.zeros((n, 20))
+        rc = lib().sgx_track_coherent(self._h, rec._h, int(rec_file_offset), C.cast(arr, _P), n, int(ms), C.byref(params),
+                                      _ptr(edge_in), _ptr(out), _ptr(done), _ptr(edge), _ptr(start), _ptr(energy))
+        if rc == SGX_E_SILENT:
+            e = SilentChannelError(last_error(), out, done)
+            e.bit_edge, e.coh_start, e.edge_energy = edge, start, energy
+            raise e
+        check(rc)
+        return out, done, edge, start, energy
 
 
 class Record(object):

@@ -97,6 +97,16 @@ _ACQ_DEFAULTS = (
     ("acqBinStep", None),           # Doppler step in Hz; None: 500 / acqCoherentMs
 )
 
+# bit-aligned coherent tracking of weak signals (TrackingResult.track; INTEGRATION.md, "Coherent tracking"): after a pull-in
+# with the reference's 1 ms loops the filters are updated once per trackCoherentMs blocks, aligned with the bit edge
+_COH_TRACK_DEFAULTS = (
+    ("trackCoherentMs", 1),         # ms per loop update behind the pull-in: 1 (the reference), 2, 4, 5, 10 or 20
+    ("trackPullInMs", 1000),        # blocks tracked with the reference's loops first; the bit edge is found over them
+    ("trackHandOverMs", 100),       # blocks whose NCO values are averaged where the coherent loops take over
+    ("cohPllNoiseBandwidth", 3.0),  # Hz, nominal (calcLoopCoef's k = 0.25 makes the loop about twice as wide)
+    ("cohDllNoiseBandwidth", 1.0),  # Hz
+)
+
 # strong-signal cancellation behind tracking (TrackingResult.cancel; INTEGRATION.md, "Strong-signal cancellation"): the
 # channels tracked at a high C/N0 are subtracted from the record, and what they hid is searched for and tracked on the result
 _CANCEL_DEFAULTS = (
@@ -114,7 +124,7 @@ class Settings(frontend.FrontEnd):
     startOffset = property(lambda self: 68.802, doc="initial travel-time guess, ms (read-only, initialize.py:172)")
 
     def __init__(self):
-        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _CANCEL_DEFAULTS + frontend.DEFAULTS:
+        for name, value in _DEFAULTS + _LOCK_DEFAULTS + _ACQ_DEFAULTS + _COH_TRACK_DEFAULTS + _CANCEL_DEFAULTS + frontend.DEFAULTS:
             setattr(self, name, value)
         self.acqSatelliteList = range(1, 33)      # PRN indices 0..31 are searched (acquisition.py:103)
         self.truePosition = TruePosition()

@@ -5,6 +5,7 @@
                                                   [--correlator-bank LO:HI:STEP] [--notch[=THRESHOLD_DB]] [--dtype int8]
                                                   [--excise[=THRESHOLD] --excise-segment N]
                                                   [--cancel-strong[=DBHZ] --cancel-smooth MS]
+                                                  [--track-coherent-ms T --track-pull-in-ms P --coh-pll-bw HZ --coh-dll-bw HZ]
 %s
 
 Prints the channel table, the tracking time (with --lock-detector: each channel's C/N0, carrier lock and the time it
@@ -19,7 +20,8 @@ time-frequency cells it cut and the samples it clipped.  --cancel-strong works b
 median C/N0 of 60 dB-Hz or more (or --cancel-strong=DBHZ) is rebuilt from its tracking results and subtracted from the record
 (one amplitude per block, or averaged over --cancel-smooth MS blocks, odd, 1 .. 41), the satellites that are not tracked are
 searched for again on the cleaned record and those found are tracked there in the free channels; they join the others for
-navigation.
+navigation.  --track-coherent-ms 20 keeps weak signals: after --track-pull-in-ms ms with the 1 ms loops (over which each
+channel's bit edge is found) both loops are updated once per 20 ms from sums aligned with the navigation bits.
 %s
 
 --monitor looks at the whole prepared record before anything else runs: per 100 ms (or --monitor=SLICE_MS) one Welch spectrum
@@ -100,6 +102,16 @@ def main(argv=None):
                     help="acquisition: ms summed coherently per window (weak signals: 10; Doppler step 500 / T Hz)")
     ap.add_argument("--acq-blocks", type=int, default=None, help="acquisition: number of windows (reference: 2)")
     ap.add_argument("--acq-noncoh", action="store_true", help="acquisition: sum the windows non-coherently")
+    ap.add_argument("--track-coherent-ms", type=int, default=None, metavar="T",
+                    help="tracking: behind the pull-in, update the loops once per T ms (2, 4, 5, 10 or 20), aligned with the "
+                         "navigation bit - keeps signals the 1 ms loops lose (below ~30 dB-Hz)")
+    ap.add_argument("--track-pull-in-ms", type=int, default=None, metavar="P",
+                    help="with --track-coherent-ms: ms tracked with the 1 ms loops first, over which the bit edge is found "
+                         "(default: Settings.trackPullInMs, 1000; at least 220)")
+    ap.add_argument("--coh-pll-bw", type=float, default=None, metavar="HZ",
+                    help="with --track-coherent-ms: nominal PLL noise bandwidth of the coherent loop (default 3)")
+    ap.add_argument("--coh-dll-bw", type=float, default=None, metavar="HZ",
+                    help="with --track-coherent-ms: DLL noise bandwidth of the coherent loop (default 1)")
     ap.add_argument("--correlator-bank", default=None, metavar="LO:HI:STEP",
                     help="after tracking, replay every channel at code offsets LO .. HI (chips, at most 64 taps) and "
                          "print the mean envelope per tap (a negative LO needs the = form: --correlator-bank=-1:1:0.25)")
@@ -152,6 +164,14 @@ def main(argv=None):
         ap.error("--cancel-strong takes the C/N0 threshold in dB-Hz")
     if a.cancel_smooth is not None and not (1 <= a.cancel_smooth <= 41 and a.cancel_smooth % 2 == 1):
         ap.error("--cancel-smooth takes an odd number of blocks in 1 .. 41")
+    if a.track_coherent_ms is not None and a.track_coherent_ms not in (1, 2, 4, 5, 10, 20):
+        ap.error("--track-coherent-ms takes 1, 2, 4, 5, 10 or 20")
+    if a.track_coherent_ms in (None, 1) and not (a.track_pull_in_ms is None and a.coh_pll_bw is None and a.coh_dll_bw is None):
+        ap.error("--track-pull-in-ms, --coh-pll-bw and --coh-dll-bw describe the coherent loops: they need --track-coherent-ms")
+    if a.track_pull_in_ms is not None and a.track_pull_in_ms < 220:
+        ap.error("--track-pull-in-ms takes at least 220 ms (the bit edge is found over them)")
+    if (a.coh_pll_bw is not None and not a.coh_pll_bw > 0) or (a.coh_dll_bw is not None and not a.coh_dll_bw > 0):
+        ap.error("--coh-pll-bw and --coh-dll-bw take a bandwidth in Hz, above 0")
     if a.monitor_out is not None and a.monitor is None:
         ap.error("--monitor-out saves what --monitor sees: it needs --monitor")
     if a.monitor is not None and not (a.monitor == -1.0 or (np.isfinite(a.monitor) and a.monitor > 0)):
@@ -168,7 +188,8 @@ def main(argv=None):
                  exciseSegment=a.excise_segment,
                  strongSignalCancellation=True if a.cancel_strong is not None else None,
                  cancelCNoThreshold=a.cancel_strong if a.cancel_strong is not None and a.cancel_strong != -1.0 else None,
-                 cancelSmoothMs=a.cancel_smooth,
+                 cancelSmoothMs=a.cancel_smooth, trackCoherentMs=a.track_coherent_ms, trackPullInMs=a.track_pull_in_ms,
+                 cohPllNoiseBandwidth=a.coh_pll_bw, cohDllNoiseBandwidth=a.coh_dll_bw,
                  monitorSliceMs=a.monitor if a.monitor is not None and a.monitor > 0 else None)
     for stage, names in zip(STAGES, dests):
         given = [val is not None and val is not False for val in (getattr(a, name) for name in names)]

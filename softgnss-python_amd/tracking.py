@@ -88,6 +88,7 @@ class TrackingResult(Result):
         self._lost_rows = ()        # rows of .results the lock detector declared lost inside track() (status '-')
         self._active = []           # channel numbers of the rows of .series
         self._assigned = False      # .results was assigned (the reference's cache path): .quality reads it, not .series
+        self.bitEdge = self.coherentStart = self.edgeEnergy = None   # coherent tracking only (Settings.trackCoherentMs > 1)
 
     def has_results(self):
         """False after the reference's short-read exit (tracking.py:159-163 leaves the results unset) and before track()."""
@@ -357,6 +358,9 @@ class TrackingResult(Result):
         ms = int(settings.msToProcess)            # float in the reference (Q9)
         nch = int(settings.numberOfChannels)
         self._reset()
+        coherent = int(getattr(settings, "trackCoherentMs", 1))
+        if coherent > 1:
+            return self._track_coherent(fid, ctx, nch, ms)
         if self._channels is None and self._try_chained(fid, ctx, nch, ms):
             return
         channel = self._table()   # (where the queued sequence did not apply: the search is looked at, preRun runs here)
@@ -376,6 +380,35 @@ class TrackingResult(Result):
             series, done = ctx.track(rec, chans, ms, rec_file_offset=file_off, data_type=dtype_code)
             self.kernel_ms = ctx.timing()["track_ms"]
         self._finish(fid, series, active, done, ms)
+
+    def _track_coherent(self, fid, ctx, nch, ms):
+        """Settings.trackCoherentMs > 1: the record as track() loads it, every channel through sgx_track_coherent (the
+        bit edges found during the pull-in), .series / .results as ever - the six sums, absoluteSample and the rates are
+        per block - plus .bitEdge, .coherentStart (int32 per row) and .edgeEnergy (float64[n, 20])."""
+        settings = self._settings
+        dtype_code, isz = self._data_type()
+        if dtype_code != _native.DT_INT8:
+            raise TypeError("coherent tracking (trackCoherentMs %d) reads int8 records, not Settings.dataType %r: the "
+                            "conditioning and requantising stages make one" % (int(settings.trackCoherentMs), settings.dataType))
+        channel = self._table()
+        active = [i for i in range(nch) if channel[i].PRN != 0]
+        if not active:
+            return self._finish(fid, None, active, None, ms)
+        chans = [(int(channel[i].PRN), float(channel[i].acquiredFreq), float(channel[i].codePhase)) for i in active]
+        first = int(settings.skipNumberOfBytes + min(c[2] for c in chans))
+        last = int(settings.skipNumberOfBytes + max(c[2] for c in chans))
+
+        def need():
+            n = settings.samplesPerCode
+            return last - first + ms * (n + 2) + n
+        params = _native.coh_params(settings)
+        with self._record(fid, first, need) as (rec, file_off):
+            rec.wait()          # (a record still streaming in: the kernel follows no watermark)
+            series, done, edge, start, energy = ctx.track_coherent(rec, chans, ms, params, rec_file_offset=file_off)
+            self.kernel_ms = ctx.timing()["track_ms"]
+        self._finish(fid, series, active, done, ms)
+        if self.series is not None:
+            self.bitEdge, self.coherentStart, self.edgeEnergy = edge, start, energy
 
     def _try_chained(self, fid, ctx, nch, ms):
         """The record is resident, and the acquisition's search and its preRun are still queued on this context: preRun
