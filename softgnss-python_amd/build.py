@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libsgx.so")
 SOURCES = ["sgx_host.cpp", "sgx_core.cpp", "sgx_record.cpp", "sgx_comm.cpp", "sgx_synth.hip", "sgx_fft.hip", "sgx_acq.hip", "sgx_trk.hip", "sgx_trk_f32.hip", "sgx_trk_tp.hip", "sgx_trk2.hip", "sgx_trk3.hip", "sgx_trk_multi.hip", "sgx_trk_any.hip", "sgx_trk_coh.hip", "sgx_trk_math_dev.hip", "sgx_nav.hip", "sgx_navhost.cpp", "sgx_quality.hip", "sgx_replay.hip", "sgx_filter.hip", "sgx_notch.cpp", "sgx_iq.hip", "sgx_requant.hip", "sgx_cond.hip", "sgx_cond.cpp", "sgx_unpack.hip", "sgx_decim.hip", "sgx_decim.cpp", "sgx_resamp.hip", "sgx_resamp.cpp", "sgx_array.hip", "sgx_array.cpp", "sgx_waterfall.hip", "sgx_excise.hip", "sgx_cancel.hip", "sgx_cancel.cpp", "sgx_geo.cpp"]
-HEADERS = [os.path.join(CSRC, "sgx_trk_persample.h"), os.path.join(CSRC, "sgx_trk_math.h"), os.path.join(CSRC, "sgx_trk_math_eval.h"), os.path.join(CSRC, "sgx_trk_common.h"), os.path.join(CSRC, "sgx_trk2_parts.h"), os.path.join(CSRC, "sgx_fir_dot4.h"), os.path.join(CSRC, "sgx_stage.h"), os.path.join(CSRC, "sgx_count.h"), os.path.join(CSRC, "sgx_seg_fft.h"), os.path.join(CSRC, "sgx_waterfall_core.h"), os.path.join(CSRC, "sgx_excise_core.h"), os.path.join(CSRC, "sgx_cancel_core.h"), os.path.join(CSRC, "sgx_acq_kernels.h"), os.path.join(CSRC, "sgx_internal.h"), os.path.join(CSRC, "sgx_check.h"), os.path.join(ROOT, "include", "sgx.h")]
+HEADERS = [os.path.join(CSRC, "sgx_trk_persample.h"), os.path.join(CSRC, "sgx_trk_block.h"), os.path.join(CSRC, "sgx_trk_math.h"), os.path.join(CSRC, "sgx_trk_math_eval.h"), os.path.join(CSRC, "sgx_trk_common.h"), os.path.join(CSRC, "sgx_trk2_parts.h"), os.path.join(CSRC, "sgx_fir_dot4.h"), os.path.join(CSRC, "sgx_stage.h"), os.path.join(CSRC, "sgx_count.h"), os.path.join(CSRC, "sgx_seg_fft.h"), os.path.join(CSRC, "sgx_waterfall_core.h"), os.path.join(CSRC, "sgx_excise_core.h"), os.path.join(CSRC, "sgx_cancel_core.h"), os.path.join(CSRC, "sgx_acq_kernels.h"), os.path.join(CSRC, "sgx_internal.h"), os.path.join(CSRC, "sgx_check.h"), os.path.join(ROOT, "include", "sgx.h")]
 # -ffp-contract=off: chip-boundary index math must round exactly like the reference's numpy
 # expressions; fused multiply-adds are written explicitly where wanted.
 EXTRA = os.environ.get("SGX_EXTRA_FLAGS", "").split()   # e.g. -DTRK_FINEPROF for the diagnosis build

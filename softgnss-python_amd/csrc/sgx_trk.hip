@@ -20,6 +20,9 @@ __global__ __launch_bounds__(256) void trk_fill_kernel(double* __restrict__ out,
     const bool zero = (series == 0) || (series >= 3 && series <= 8);
     out[i] = zero ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
 }
+void sgx_trk_fill(double* d_out, int ms, size_t elems, hipStream_t st) {
+    trk_fill_kernel<<<(unsigned)((elems + 255) / 256), 256, 0, st>>>(d_out, ms, (long long)elems);
+}
 
 // What a tracking launch leaves for the host: the result page's TrkLook (sgx_internal.h), then the word the host spins on
 __global__ __launch_bounds__(SGX_TRK_LOOK_CH) void trk_finish_kernel(const int* __restrict__ d_err, const int* __restrict__ d_done,
@@ -120,6 +123,82 @@ static TrkEnv trk_env() {
     return E;
 }
 
+// ---- The stages every per-channel tracking call runs (sgx_trk_common.h declares them: sgx_track_coherent, sgx_trk_coh.hip, is
+// the other caller).  Fewer than ~15.4 samples per chip: a 16-sample group can hold several chip switches of a ramp
+int sgx_trk_multi(const sgx_settings& S) {
+    return (15.0 * 1.001 * S.codeFreqBasis / S.samplingFreq >= 1.0) ? 1 : 0;
+}
+
+// Units needed by the longest possible block, worst alignment.  A block is samplesPerCode +- 1 samples long while the
+// code NCO stays near its basis; the allowance of 64 samples corresponds to a code-rate error of 0.17 % (1.7 kHz at
+// 1.023 MHz), three orders of magnitude beyond what the DLL's filter can command.
+int sgx_trk_units(long long n_code) {
+    return (int)((n_code + 64 + 15 + 15) / 16 + TRK_THREADS - 1) / TRK_THREADS;
+}
+int sgx_trk_units_check(long long n_code, int n_units) {
+    if (n_units <= 16) return SGX_OK;
+    sgx_set_error("samplesPerCode %lld needs %d units, the tracking kernel holds 16", n_code, n_units);
+    return SGX_E_ARG;
+}
+
+// tracking.py:13-64: the constants every kernel reads, for a record of rec_len bytes of `kind` samples that starts at byte
+// file_off of its file (each launch sets split, n_units and mark; fast_xcd and fscale are the caller's)
+void sgx_trk_const(TrkConst& K, const sgx_settings& S, long long n_code, long long rec_len, int kind, long long file_off, int ms,
+                   int n_ch, int multi) {
+    memset(&K, 0, sizeof(K));
+    K.fs = S.samplingFreq;
+    K.code_basis = S.codeFreqBasis;
+    K.code_len = (double)S.codeLength;
+    K.spacing = S.dllCorrelatorSpacing;
+    double t1c, t2c, t1p, t2p;
+    sgx_calc_loop_coef(S.dllNoiseBandwidth, S.dllDampingRatio, 1.0, &t1c, &t2c);     // tracking.py:45
+    sgx_calc_loop_coef(S.pllNoiseBandwidth, S.pllDampingRatio, 0.25, &t1p, &t2p);    // tracking.py:52
+    K.k_code_a = t2c / t1c;
+    K.k_code_b = 0.001 / t1c;
+    K.k_carr_a = t2p / t1p;
+    K.k_carr_b = 0.001 / t1p;
+    const long double two_pi = 2.0L * (long double)M_PI;   // the reference's 2*np.pi (a double)
+    const long double inv = 1.0L / (two_pi * (long double)S.samplingFreq);
+    K.inv_2pifs_hi = (double)inv;
+    K.inv_2pifs_lo = (double)(inv - (long double)K.inv_2pifs_hi);
+    K.inv_2pi = (double)(1.0L / two_pi);
+    K.rec_len = rec_len;                                 // bytes; wider samples: the kernel divides (per-channel shift)
+    K.rec_alloc = rec_len + SGX_IF_PAD - (sgx_dt_bytes(kind) - 1);   // bytes, less the largest per-channel shift
+    K.multi = multi;
+    K.uns = kind == SGX_DT_UINT8 ? 1 : 0;
+    K.kind = kind;
+    K.file_off = file_off;
+    K.ms = ms;
+    K.n_ch = n_ch;
+    K.nb_base = (int)n_code - 3;
+    for (int k = 0; k < 8; ++k) K.inv_nb[k] = 1.0 / (double)(K.nb_base + k);
+    K.inv_fs = 1.0 / S.samplingFreq;
+    K.inv_pi = 1.0 / M_PI;
+    K.fscale = 1.0;
+}
+
+// The channel table the kernels read, from channels that start skip_bytes + codePhase bytes into the file
+int sgx_trk_channels(std::vector<TrkChan>& hc, const sgx_chan_init* ch, int n_ch, long long skip_bytes, long long file_off,
+                     int sample_bytes) {
+    hc.resize((size_t)n_ch);
+    for (int i = 0; i < n_ch; ++i) {
+        TrkChan& h = hc[(size_t)i];
+        h.acquiredFreq = ch[i].acquiredFreq;
+        h.prn = ch[i].prn;
+        SGX_CHECK_ARG(ch[i].prn >= 0 && ch[i].prn <= 32);
+        const long long p0 = skip_bytes + (long long)ch[i].codePhase - file_off;
+        if (ch[i].prn != 0 && p0 < 0) {
+            sgx_set_error("channel %d starts at file byte %lld, before the record (offset %lld)", i,
+                          skip_bytes + (long long)ch[i].codePhase, file_off);
+            return SGX_E_RANGE;
+        }
+        // wider samples: the channel's own sample grid starts at byte p0 % sample_bytes of the record
+        h.pos0 = p0 / sample_bytes;
+        h.pad = (int)(p0 % sample_bytes);
+    }
+    return SGX_OK;
+}
+
 // ---- WHICH KERNEL, HOW MANY MEMBERS: the one rule (include/sgx.h: sgx_track_plan; tests/test_cabi_and_host.py holds the table)
 //
 //   sample type                      channels   samples / chip      spacing   -> kernel                        members per channel
@@ -144,15 +223,12 @@ struct TrkPlan {
 static TrkPlan trk_plan(const sgx_settings& S, int kind, int n_ch, long long n_code, int cus_total, bool floaty,
                         int split_env = 0, int arms_env = 0, bool v3_off = false) {
     TrkPlan P;
-    P.multi = (15.0 * 1.001 * S.codeFreqBasis / S.samplingFreq >= 1.0) ? 1 : 0;
+    P.multi = sgx_trk_multi(S);
     if (P.multi) floaty = false;
     const bool typed = kind == SGX_DT_INT8 || kind == SGX_DT_UINT8 || kind == SGX_DT_INT16 || floaty;
     const bool use_any = !typed || (P.multi && kind != SGX_DT_INT8);
     const int ch8 = P.ch8 = ((n_ch + 7) / 8) * 8;
-    // units needed by the longest possible block, worst alignment.  A block is samplesPerCode +- 1 samples long while the
-    // code NCO stays near its basis; the allowance of 64 samples corresponds to a code-rate error of 0.17 % (1.7 kHz at
-    // 1.023 MHz), three orders of magnitude beyond what the DLL's filter can command.
-    P.n_units = (int)((n_code + 64 + 15 + 15) / 16 + TRK_THREADS - 1) / TRK_THREADS;
+    P.n_units = sgx_trk_units(n_code);
     int split = cus_total / ch8;
     if (split > P.n_units) split = P.n_units;
     if ((P.multi || use_any) && split > TRK_MAX_SPLIT) split = TRK_MAX_SPLIT;
@@ -269,69 +345,12 @@ struct TrkCall {
     TrkLaunch L;                 // the last launch ...
     hipError_t e;                // ... its status (hipSuccess before the first) ...
     int h_err;                   // ... and its error word: 0, or 1 + the channel that timed out
-    int range_ch1;               // 1 + the channel that reached a block beyond the launch's units (0: none); trk_diagnose
+    int range_ch1;               // 1 + the channel that reached a block beyond the launch's units (0: none); sgx_trk_diagnose
     void stamp(const char* what) const {
         if (E.trace) fprintf(stderr, "[sgx step trace] %-28s %8.1f us\n", what,
                              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     }
 };
-
-// tracking.py:13-64: the constants every kernel reads (each launch sets split, n_units and mark)
-static void trk_const(TrkCall& T) {
-    const sgx_settings& S = T.c->s;
-    TrkConst& K = T.K;
-    K.fs = S.samplingFreq;
-    K.code_basis = S.codeFreqBasis;
-    K.code_len = (double)S.codeLength;
-    K.spacing = S.dllCorrelatorSpacing;
-    double t1c, t2c, t1p, t2p;
-    sgx_calc_loop_coef(S.dllNoiseBandwidth, S.dllDampingRatio, 1.0, &t1c, &t2c);     // tracking.py:45
-    sgx_calc_loop_coef(S.pllNoiseBandwidth, S.pllDampingRatio, 0.25, &t1p, &t2p);    // tracking.py:52
-    K.k_code_a = t2c / t1c;
-    K.k_code_b = 0.001 / t1c;
-    K.k_carr_a = t2p / t1p;
-    K.k_carr_b = 0.001 / t1p;
-    const long double two_pi = 2.0L * (long double)M_PI;   // the reference's 2*np.pi (a double)
-    const long double inv = 1.0L / (two_pi * (long double)S.samplingFreq);
-    K.inv_2pifs_hi = (double)inv;
-    K.inv_2pifs_lo = (double)(inv - (long double)K.inv_2pifs_hi);
-    K.inv_2pi = (double)(1.0L / two_pi);
-    K.rec_len = (long long)T.r->n;                       // bytes; two-byte samples: the kernel divides (per-channel shift)
-    K.rec_alloc = (long long)T.r->n + SGX_IF_PAD - (T.sample_bytes - 1);   // bytes, less the largest per-channel shift
-    K.multi = T.P.multi;
-    K.uns = T.kind == SGX_DT_UINT8 ? 1 : 0;
-    K.kind = T.kind;
-    K.file_off = T.rec_file_offset;
-    K.ms = T.ms;
-    K.n_ch = T.n_ch;
-    K.fast_xcd = T.E.fast_xcd ? 1 : 0;
-    K.nb_base = (int)T.c->n_code - 3;
-    for (int k = 0; k < 8; ++k) K.inv_nb[k] = 1.0 / (double)(K.nb_base + k);
-    K.inv_fs = 1.0 / S.samplingFreq;
-    K.inv_pi = 1.0 / M_PI;
-}
-
-// The channel table the kernels read (chained: made on the device by preRun instead)
-static int trk_channels(TrkCall& T) {
-    const sgx_chan_init* ch = T.ch;
-    T.hc.resize((size_t)T.n_ch);
-    for (int i = 0; i < T.n_ch && !T.chained; ++i) {
-        TrkChan& h = T.hc[(size_t)i];
-        h.acquiredFreq = ch[i].acquiredFreq;
-        h.prn = ch[i].prn;
-        SGX_CHECK_ARG(ch[i].prn >= 0 && ch[i].prn <= 32);
-        const long long p0 = T.skip_bytes + (long long)ch[i].codePhase - T.rec_file_offset;
-        if (ch[i].prn != 0 && p0 < 0) {
-            sgx_set_error("channel %d starts at file byte %lld, before the record (offset %lld)", i,
-                          T.skip_bytes + (long long)ch[i].codePhase, (long long)T.rec_file_offset);
-            return SGX_E_RANGE;
-        }
-        // two-byte samples: the channel's own sample grid starts at byte (p0 & 1) of the record
-        h.pos0 = p0 / T.sample_bytes;
-        h.pad = (int)(p0 % T.sample_bytes);
-    }
-    return SGX_OK;
-}
 
 // If the caller's result buffer is pinned host memory (sgx_host_alloc; the Python binding's is), the kernel's record
 // stores - 104 bytes per channel per millisecond, issued by an otherwise idle wave - go straight to it over PCIe: no device
@@ -440,7 +459,7 @@ static int trk_repeat(TrkCall& T, int launch, const int words[2], bool& again) {
     h_err &= ~TRK_ERR_PLACE;
     if ((h_err & TRK_ERR_RANGE) == 0) h_err &= 0xFFFF;
     if (h_err & TRK_ERR_RANGE) {
-        // (every workgroup has retired: the series and ms_done are collected first, trk_diagnose then says what happened)
+        // (every workgroup has retired: the series and ms_done are collected first, sgx_trk_diagnose then says what happened)
         T.range_ch1 = words[1] ? words[1] : (h_err & 0xFFFF);
         if (T.range_ch1 < 1) T.range_ch1 = 1;
         h_err = 0;
@@ -501,7 +520,7 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
     T.stamp("channel table queued");
     SGX_HIP(hipMemsetAsync(T.d_done, 0, T.sz_clear, st));   // done, every polled word, err
     T.stamp("memset queued");
-    if (!T.direct) trk_fill_kernel<<<(unsigned)((T.elems + 255) / 256), 256, 0, st>>>(T.d_out, T.ms, (long long)T.elems);
+    if (!T.direct) sgx_trk_fill(T.d_out, T.ms, T.elems, st);
     const TrkLaunch& L = T.L = trk_launch_step(T.P, T.rep, [&](int want) { return sgx_cu_reserve(c->device, T.cus_total, want); });
     reserved.n = L.cus;
     T.K.split = L.split;
@@ -629,21 +648,25 @@ static int trk_finish(TrkCall& T) {
 //       they are: unlike prep_code they have no test of the step itself.
 //   trk_kernel_tp, _multi, _any (per-sample), the float instances  prep_code posts stop = 1 for a step that is not > 0 (tested on
 //       the step, not on what (int) makes of NaN), and the loops test stop first, before a ramp or an address is formed.
-static int trk_diagnose(const TrkCall& T) {
-    const StepLook* slook = &T.c->h_look->step;   // (chained: preRun's table)
-    for (int i = 0; i < T.n_ch; ++i) {
-        if (T.chained ? slook->prn[i] == 0 : T.ch[i].prn == 0) continue;
-        const int dn = T.ms_done[i];
-        if (dn < 1 || dn >= T.ms) continue;
-        const double* row = T.out + (size_t)i * SGX_NUM_SERIES * (size_t)T.ms + (size_t)(dn - 1);
-        const double codeFreq = row[(size_t)T.ms];
+// ch, or (chained: ch is null) look_prn, preRun's table: which channels are off.  zero_sums: what was exactly zero when the
+// rates became NaN, in front of the block's number - "its block", or the coherent call's "the update behind its block" (the
+// sums of a group of blocks; all zero, the group's last block is).  range_ch1: 1 + the channel that reached a block beyond
+// the launch's n_units (0: none).
+int sgx_trk_diagnose(const sgx_chan_init* ch, const int32_t* look_prn, int n_ch, int ms, const double* out, const int32_t* ms_done,
+                     const char* zero_sums, int range_ch1, int n_units, double dll_bw) {
+    for (int i = 0; i < n_ch; ++i) {
+        if (ch ? ch[i].prn == 0 : look_prn[i] == 0) continue;
+        const int dn = ms_done[i];
+        if (dn < 1 || dn >= ms) continue;
+        const double* row = out + (size_t)i * SGX_NUM_SERIES * (size_t)ms + (size_t)(dn - 1);
+        const double codeFreq = row[(size_t)ms];
         if (codeFreq != codeFreq) {
             bool zero = true;   // (the six sums of the block, series 3 .. 8)
-            for (int sidx = 3; sidx <= 8; ++sidx) zero = zero && row[(size_t)sidx * (size_t)T.ms] == 0.0;
+            for (int sidx = 3; sidx <= 8; ++sidx) zero = zero && row[(size_t)sidx * (size_t)ms] == 0.0;
             if (zero)
-                sgx_set_error("ValueError: cannot convert float NaN to integer: channel %d went silent - the six sums of its "
-                              "block %d are exactly zero (a zero-filled stretch of the record), the loop filters' rates are "
-                              "NaN, and block %d has no length", i, dn - 1, dn);
+                sgx_set_error("ValueError: cannot convert float NaN to integer: channel %d went silent - the six sums of %s "
+                              "%d are exactly zero (a zero-filled stretch of the record), the loop filters' rates are "
+                              "NaN, and block %d has no length", i, zero_sums, dn - 1, dn);
             else   // (NaN some other way - a loop filter that left the finite numbers: the reference dies at the same place)
                 sgx_set_error("ValueError: cannot convert float NaN to integer: channel %d - the loop filters' rates are NaN "
                               "after block %d (its sums are not zero: the filters diverged), and block %d has no length",
@@ -651,10 +674,10 @@ static int trk_diagnose(const TrkCall& T) {
             return SGX_E_SILENT;
         }
     }
-    if (T.range_ch1) {
+    if (range_ch1) {
         sgx_set_error("tracking: channel %d reached a block longer than the %d units of %d samples the kernel "
                       "provides (the code NCO left its plausible range; dllNoiseBandwidth %g)",
-                      T.range_ch1 - 1, T.L.n_units, TRK_UNIT, T.c->s.dllNoiseBandwidth);
+                      range_ch1 - 1, n_units, TRK_UNIT, dll_bw);
         return SGX_E_RANGE;
     }
     return SGX_OK;
@@ -692,13 +715,12 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     SGX_HIP(hipDeviceGetAttribute(&T.cus_total, hipDeviceAttributeMultiprocessorCount, c->device));
     // THE RULE (trk_plan above), with the diagnostic overrides of this process's environment
     T.P = trk_plan(c->s, kind, n_ch, (long long)c->n_code, T.cus_total, floaty, T.E.split, T.E.arms, T.E.v3_off);
-    trk_const(T);
+    sgx_trk_const(T.K, c->s, (long long)c->n_code, (long long)r->n, kind, T.rec_file_offset, ms, n_ch, T.P.multi);
+    T.K.fast_xcd = T.E.fast_xcd ? 1 : 0;
     T.K.fscale = (floaty && !T.P.multi) ? fscale : 1.0;   // (a float record on the typed kernel: scaled back at the end)
-    if (T.P.n_units > 16) {
-        sgx_set_error("samplesPerCode %lld needs %d units, the tracking kernel holds 16", (long long)c->n_code, T.P.n_units);
-        return SGX_E_ARG;
-    }
-    int rc = trk_channels(T);
+    int rc = sgx_trk_units_check((long long)c->n_code, T.P.n_units);
+    // (chained: the channel table is made on the device by preRun instead)
+    if (rc == SGX_OK && !chained) rc = sgx_trk_channels(T.hc, ch, n_ch, skip_bytes, T.rec_file_offset, sample_bytes);
     if (rc == SGX_OK) rc = trk_buffers(T);
     if (rc != SGX_OK) return rc;
     if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
@@ -710,7 +732,8 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         if (rc != SGX_OK) return rc;
     }
     rc = trk_finish(T);
-    return rc != SGX_OK ? rc : trk_diagnose(T);
+    if (rc != SGX_OK) return rc;
+    return sgx_trk_diagnose(ch, c->h_look->step.prn, n_ch, ms, out, ms_done, "its block", T.range_ch1, T.L.n_units, c->s.dllNoiseBandwidth);
 }
 
 int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,

@@ -1,5 +1,21 @@
-// Device helpers shared by the tracking kernels (sgx_trk.hip, sgx_trk2.hip, sgx_trk_tp.hip).  Everything here follows the reference's fp64 operation order where an integer
-// rounding follows; both files are built with -ffp-contract=off.
+// What the tracking host (sgx_trk.hip) and the files of the tracking kernels share: the constants and the layout the host
+// fills and sizes, the launchers and the host's call stages, and device helpers.  Who uses which helper:
+//   TrkConst, the error words      every kernel and the host
+//   div_rn, ramp_at, ramp_setup, sincos_turns, dpp_add, load_group
+//                                  the latency-mode kernels (sgx_trk2.hip, sgx_trk3.hip, sgx_trk2_parts.h) and the block pieces
+//                                  of the per-channel kernels (sgx_trk_block.h); ramp_at also trk_kernel_tp
+//   PROBE, xcc_id, granule_store   the kernels whose workgroups cooperate on a channel: the latency-mode kernels and the
+//                                  per-sample body (sgx_trk_persample.h: trk_kernel_multi, trk_kernel_any)
+//   wait_mark                      the latency-mode kernels, which follow a streaming record
+//   TrkBlock, TrkState, prep_code  the per-channel kernels, which keep the loop state in LDS: trk_kernel_tp (sgx_trk_tp.hip), the
+//                                  per-sample body and trk_kernel_coh (sgx_trk_coh.hip)
+//   prep_carr, half_wave_sum       the per-sample body and trk_kernel_coh (both map a block in groups of 16 samples with the
+//                                  pieces of sgx_trk_block.h); row_sum: the per-sample body and trk_kernel_tp
+//   any_sample, any_group          the per-sample body (trk_kernel_any)
+//   first_above, TpCarr, tp_tables, cmul2, U4a / U2a               trk_kernel_tp alone: one lane per prompt chip
+// The device functions of sgx_trk_math_dev.hip evaluate prep_code, ramp_setup, div_rn and sincos_turns for the tests.
+// Everything here follows the reference's fp64 operation order where an integer rounding follows (SURVEY.md section 9
+// T1-T5); every file of the library is built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -89,6 +105,21 @@ void sgx_trk_multi_launch(int n_blocks, hipStream_t st, const int8_t* rec, const
 // sgx_trk_any.hip: the same body with every sample fetched where it lies, for any sample type (K.kind)
 void sgx_trk_any_launch(int n_blocks, hipStream_t st, const int8_t* rec, const int8_t* codes, const TrkChan* chans,
                         double* out, int* done, const TrkConst& K, long long* prof, unsigned long long* xch, int* err);
+
+// sgx_trk.hip: the stages of a tracking call that take only what they need, so that sgx_track_coherent (sgx_trk_coh.hip, with
+// its own kernel and launch) runs them too: the sampling-rate rule behind TrkConst::multi; the units of a block and the error
+// beyond 16; TrkConst for a record; the channel table with its refusals; the series' initial values on the device; and, after
+// the launch, why a channel ended early (SGX_E_SILENT, SGX_E_RANGE or SGX_OK)
+int sgx_trk_multi(const sgx_settings& S);
+int sgx_trk_units(long long n_code);
+int sgx_trk_units_check(long long n_code, int n_units);
+void sgx_trk_const(TrkConst& K, const sgx_settings& S, long long n_code, long long rec_len, int kind, long long file_off, int ms,
+                   int n_ch, int multi);
+int sgx_trk_channels(std::vector<TrkChan>& hc, const sgx_chan_init* ch, int n_ch, long long skip_bytes, long long file_off,
+                     int sample_bytes);
+void sgx_trk_fill(double* d_out, int ms, size_t elems, hipStream_t st);
+int sgx_trk_diagnose(const sgx_chan_init* ch, const int32_t* look_prn, int n_ch, int ms, const double* out, const int32_t* ms_done,
+                     const char* zero_sums, int range_ch1, int n_units, double dll_bw);
 
 // Per-block parameters: code part written by wave 1, carrier part by wave 0, read by everybody.
 struct TrkBlock {
@@ -380,7 +411,7 @@ __device__ __forceinline__ uint4 load_group(const int8_t* __restrict__ rec, long
     return *reinterpret_cast<const uint4*>(rec + addr);
 }
 
-// ---- chip-lane maps (sgx_trk_tp.hip: one lane per prompt chip; sgx_trk_chip.hip: one lane per half chip) ----
+// ---- the chip-lane map of trk_kernel_tp (sgx_trk_tp.hip: one lane per prompt chip) ----
 #define TP_RUN 20   // samples per run handled by the unrolled path
 
 // first sample i with T(i) = fl(fl(i*step)+start) > thr (exact reference arithmetic; see ramp_setup)

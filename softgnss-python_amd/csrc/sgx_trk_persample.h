@@ -3,8 +3,11 @@
 //   sgx_trk_multi.hip  <false> int8 records at low sampling rates (fewer than ~15.4 samples per chip), 16-byte groups;
 //   sgx_trk_any.hip    <true>  any sample type numpy reads (K.kind), each sample fetched where it lies: float32 /
 //                      float64 records of arbitrary values, the wider integers, and int16 / uint8 at low rates.
+// The pieces that work on one workgroup's view of a block - code table, maps, fold, filters, record - are those of
+// sgx_trk_block.h, shared with the coherent kernel; what is this body's own is the members of a channel: placement check,
+// granule exchange, abort, and the profile and its probes.
 #pragma once
-#include "sgx_trk_common.h"
+#include "sgx_trk_block.h"
 
 // (static: an instance's LDS variables then have internal linkage, like those a kernel declares itself)
 template <bool ANY>
@@ -82,24 +85,8 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         fast = (s_tot[0][0] != 0.0) && (K.fast_xcd != 0);
         __syncthreads();
     }
-    for (int i = tid; i < 1028; i += TRK_THREADS) {
-        int j = i - 1;
-        if (j < 0) j = 1022;
-        if (j >= 1023) j -= 1023;
-        if (j >= 1023) j -= 1023;
-        s_code_hi[i] = (codes[(cc.prn - 1) * 1023 + j] > 0) ? 0x3FF00000u : 0xBFF00000u;
-    }
-    if (tid == 0) {   // tracking.py:114-130
-        s_st.codeFreq = K.code_basis;
-        s_st.remCode = 0.0;
-        s_st.oldCodeNco = s_st.oldCodeErr = 0.0;
-        s_st.pos = cc.pos0;
-        s_st.carrFreq = cc.acquiredFreq;
-        s_st.carrBasis = cc.acquiredFreq;
-        s_st.remCarr = 0.0;
-        s_st.w = (cc.acquiredFreq * 2.0) * M_PI;
-        s_st.oldCarrNco = s_st.oldCarrErr = 0.0;
-    }
+    trk_code_table(s_code_hi, codes, cc.prn, tid, TRK_THREADS);
+    if (tid == 0) trk_state_start(s_st, K, cc);
     __syncthreads();
     if (wave == 0) prep_carr(K, s_st.w, s_st.remCarr, (int)(cc.pos0 & 15), s_blk, lane);
     if (wave == 1) prep_code(K, s_st.codeFreq, s_st.remCode, s_st.pos, s_st, s_blk, lane == 0, rec_len);
@@ -110,7 +97,6 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
     uint4 cur = make_uint4(0u, 0u, 0u, 0u);                                    // (16-byte groups: the int8 instance only)
     if constexpr (!ANY) cur = load_group(rec, (s_blk.pos & ~15ll) + lane_off, limit);
     double* __restrict__ o = out + (long long)ch * SGX_NUM_SERIES * K.ms;
-    const double two_pi = 2 * M_PI;
     int done = 0;
     for (int it = 0; it < K.ms; ++it) {
         const long long tk0 = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -129,10 +115,7 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
             if (tid == 0) atomicExch(err, TRK_ERR_RANGE | (1 + ch));
             break;
         }
-        const double startE = s_blk.startE, stepE = s_blk.stepE;
-        const double startP = s_blk.startP, stepP = s_blk.stepP;
-        const double startL = s_blk.startL, stepL = s_blk.stepL;
-        const double inv_step = s_blk.inv_step;
+        const TrkRamps R = trk_ramps(s_blk);
         double2 B[16];
 #pragma unroll
         for (int b = 0; b < 16; ++b) B[b] = s_blk.B[b];
@@ -141,7 +124,7 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         const long long abase_next = (pos + blk) & ~15ll;
         const int head = (int)(pos - abase);              // bytes of the first group before the block
         const int n_groups = (head + blk + 15) >> 4;
-        double aIE = 0.0, aQE = 0.0, aIP = 0.0, aQP = 0.0, aIL = 0.0, aQL = 0.0;
+        TrkSums sum = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         // carrier phasor of the lane's group inside a unit: W1[tid & 15] * W2[tid >> 4]
         double lc, ls;
         {
@@ -162,131 +145,32 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
             if (g < n_groups) {
                 const int i0 = g * 16 - head;             // sample index of byte 0 of this group
                 unsigned wd[4] = {cur.x, cur.y, cur.z, cur.w};
-                if (!ANY && (i0 < 0 || i0 + 16 > blk)) {
-                    // zero the bytes outside [0, blk): they then add nothing to the sums
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        int lo = -(i0 + 4 * d);
-                        lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-                        int hi = i0 + 4 * d + 4 - blk;
-                        hi = hi < 0 ? 0 : (hi > 4 ? 4 : hi);
-                        unsigned m = (lo >= 4) ? 0u : (0xFFFFFFFFu << (8 * lo));
-                        m &= (hi >= 4) ? 0u : (0xFFFFFFFFu >> (8 * hi));
-                        wd[d] &= m;
-                    }
-                }
+                if constexpr (!ANY) trk_mask_group(wd, i0, blk);
                 // group-start phasor G = (lane part) * W3[u]
                 const double2 w3 = s_blk.W3[u];
                 const double gc = __builtin_fma(lc, w3.x, -(ls * w3.y));
                 const double gs = __builtin_fma(lc, w3.y, ls * w3.x);
                 if (ANY && !K.multi) {
-                    // A group meets at most one switch of a ramp (16 samples span less than a chip): the three ramps' index
-                    // and switch sample at the group's first sample by the exact reference arithmetic (ramp_setup), then
-                    // the group as a sum over all its samples plus a sum over those behind the switch - when the ramps that
-                    // switch inside the group do so at ONE sample (always, at >= 16 samples per half chip and
-                    // dllCorrelatorSpacing 1/2); the samples one by one with the switches as compares otherwise.
+                    // (trk_kernel_any above ~15.4 samples per chip; the carrier table from its register copy)
                     double xd[16];
                     any_group(recc + (pos + i0) * any_sb, K.kind, i0, blk, xd);
-                    const int ilo = i0 < 0 ? 0 : i0;
-                    int kE, swE, kP, swP, kL, swL;
-                    ramp_setup(startE, stepE, inv_step, ilo, kE, swE);
-                    ramp_setup(startP, stepP, inv_step, ilo, kP, swP);
-                    ramp_setup(startL, stepL, inv_step, ilo, kL, swL);
-                    const double cE1 = __hiloint2double((int)s_code_hi[kE], 0), cE2 = __hiloint2double((int)s_code_hi[kE + 1], 0);
-                    const double cP1 = __hiloint2double((int)s_code_hi[kP], 0), cP2 = __hiloint2double((int)s_code_hi[kP + 1], 0);
-                    const double cL1 = __hiloint2double((int)s_code_hi[kL], 0), cL2 = __hiloint2double((int)s_code_hi[kL + 1], 0);
-                    const int iend = i0 + 16;
-                    int swmin = swE < swP ? swE : swP;
-                    swmin = swL < swmin ? swL : swmin;
-                    const bool eS = (swE == swmin), pS = (swP == swmin), lS = (swL == swmin);
-                    const bool odd = (swE < iend && !eS) || (swP < iend && !pS) || (swL < iend && !lS);
-                    if (__any(odd)) {
-#pragma unroll
-                        for (int b = 0; b < 16; ++b) {
-                            const int i = i0 + b;
-                            const double c = __builtin_fma(gc, B[b].x, -(gs * B[b].y));
-                            const double sn = __builtin_fma(gs, B[b].x, gc * B[b].y);
-                            const double xs = sn * xd[b], xc = c * xd[b];
-                            const double cE = i >= swE ? cE2 : cE1;
-                            const double cP = i >= swP ? cP2 : cP1;
-                            const double cL = i >= swL ? cL2 : cL1;
-                            aIE = __builtin_fma(cE, xs, aIE);
-                            aQE = __builtin_fma(cE, xc, aQE);
-                            aIP = __builtin_fma(cP, xs, aIP);
-                            aQP = __builtin_fma(cP, xc, aQP);
-                            aIL = __builtin_fma(cL, xs, aIL);
-                            aQL = __builtin_fma(cL, xc, aQL);
-                        }
-                    } else {
-                        const int bsw = swmin - i0;           // samples b >= bsw come after the switch
-                        double Ac = 0.0, As = 0.0, Tc = 0.0, Ts = 0.0;
-#pragma unroll
-                        for (int b = 0; b < 16; ++b) {
-                            Ac = __builtin_fma(xd[b], B[b].x, Ac);
-                            As = __builtin_fma(xd[b], B[b].y, As);
-                            const double xt = (b >= bsw) ? xd[b] : 0.0;
-                            Tc = __builtin_fma(xt, B[b].x, Tc);
-                            Ts = __builtin_fma(xt, B[b].y, Ts);
-                        }
-                        // rotate by the group phasor: cos part -> Q, sin part -> I (tracking.py:205-207)
-                        const double allQ = __builtin_fma(gc, Ac, -(gs * As));
-                        const double allI = __builtin_fma(gs, Ac, gc * As);
-                        const double tlQ = __builtin_fma(gc, Tc, -(gs * Ts));
-                        const double tlI = __builtin_fma(gs, Tc, gc * Ts);
-                        const double dE = eS ? (cE2 - cE1) : 0.0;
-                        const double dP = pS ? (cP2 - cP1) : 0.0;
-                        const double dL = lS ? (cL2 - cL1) : 0.0;
-                        aIE = __builtin_fma(dE, tlI, __builtin_fma(cE1, allI, aIE));
-                        aQE = __builtin_fma(dE, tlQ, __builtin_fma(cE1, allQ, aQE));
-                        aIP = __builtin_fma(dP, tlI, __builtin_fma(cP1, allI, aIP));
-                        aQP = __builtin_fma(dP, tlQ, __builtin_fma(cP1, allQ, aQP));
-                        aIL = __builtin_fma(dL, tlI, __builtin_fma(cL1, allI, aIL));
-                        aQL = __builtin_fma(dL, tlQ, __builtin_fma(cL1, allQ, aQL));
-                    }
+                    trk_map_one_switch<16>(sum, xd, B, s_code_hi, R, i0, gc, gs);
                 } else {
-                    // Low sampling rates (under ~15 samples per chip): a group can hold several chip switches of a
-                    // ramp, so the replicas are indexed sample by sample exactly as the reference does,
-                    // code[ceil(linspace(...))] (tracking.py:166-188).  Its own kernel (sgx_trk_multi.hip): correctness over speed.
-#pragma unroll 1
-                    for (int b = 0; b < 16; ++b) {
-                        const int i = i0 + b;
-                        if (i < 0 || i >= blk) continue;
-                        const double xd = ANY ? any_sample(recc + (pos + i) * any_sb, K.kind)
-                                              : (double)(int)(signed char)((wd[b >> 2] >> (8 * (b & 3))) & 0xFF);
-                        const double2 Bb = s_blk.B[b];
-                        const double c = __builtin_fma(gc, Bb.x, -(gs * Bb.y));
-                        const double sn = __builtin_fma(gs, Bb.x, gc * Bb.y);
-                        const double xs = sn * xd, xc = c * xd;
-                        const double cE = __hiloint2double((int)s_code_hi[(int)ceil(ramp_at(i, stepE, startE))], 0);
-                        const double cP = __hiloint2double((int)s_code_hi[(int)ceil(ramp_at(i, stepP, startP))], 0);
-                        const double cL = __hiloint2double((int)s_code_hi[(int)ceil(ramp_at(i, stepL, startL))], 0);
-                        aIE = __builtin_fma(cE, xs, aIE);
-                        aQE = __builtin_fma(cE, xc, aQE);
-                        aIP = __builtin_fma(cP, xs, aIP);
-                        aQP = __builtin_fma(cP, xc, aQP);
-                        aIL = __builtin_fma(cL, xs, aIL);
-                        aQL = __builtin_fma(cL, xc, aQL);
-                    }
+                    // (low sampling rates: trk_kernel_multi always, its own kernel for them, and trk_kernel_any below the bound)
+                    trk_map_by_sample(sum, s_blk.B, s_code_hi, R, i0, blk, gc, gs, [&](int b, int i) {
+                        return ANY ? any_sample(recc + (pos + i) * any_sb, K.kind) : trk_byte(wd, b);
+                    });
                 }
             }
             cur = nxt;
             PROBE(4);   // group finalisation
         }
         const long long tk1 = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        s_red[0][tid] = aIE;
-        s_red[1][tid] = aQE;
-        s_red[2][tid] = aIP;
-        s_red[3][tid] = aQP;
-        s_red[4][tid] = aIL;
-        s_red[5][tid] = aQL;
+        sum.publish(s_red, tid);
         // carrier phase at the end of this block (T5) does not need the sums: the otherwise idle wave 3
         // computes it.  remCarrPhase = trigarg[blk] % (2 pi), trigarg = w*(blk/fs) + rem; exact remainder by FMA
         if (wave == 3) {
-            const double arg_end = s_st.w * ((double)blk / K.fs) + s_st.remCarr;
-            const double kq = floor(arg_end * K.inv_2pi);
-            double rc = __builtin_fma(-kq, two_pi, arg_end);
-            if (rc < 0.0) rc += two_pi;
-            if (rc >= two_pi) rc -= two_pi;
+            const double rc = trk_end_phase(K, s_st.w, s_st.remCarr, blk);
             if (lane == 0) s_rc = rc;
         }
         PROBE(5);   // partials to LDS, end-of-block carrier phase
@@ -294,12 +178,9 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         PROBE(6);   // barrier 1 (waits for the slowest wave)
         const long long tk2 = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
         if (wave < 3) {
-            // wave w folds values 2w (lanes 0..31) and 2w+1 (lanes 32..63): 8 partials per lane, then DPP
+            // wave w folds values 2w (lanes 0..31) and 2w+1 (lanes 32..63)
             const int v = 2 * wave + (lane >> 5), l = lane & 31;
-            double acc = s_red[v][l];
-#pragma unroll
-            for (int k = 1; k < TRK_THREADS / 32; ++k) acc += s_red[v][l + 32 * k];
-            acc = half_wave_sum(acc, lane);
+            const double acc = trk_fold(s_red, wave, lane);
             PROBE(7);   // local fold
             if (P == 1) {
                 if (l == 0) s_tot[it & 1][v] = acc;
@@ -374,15 +255,12 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         }
         PROBE(10);  // barrier 2 (single-member mode only)
         const long long tk3 = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        const long long m = K.ms;
         const bool more = (it + 1 < K.ms);
         if (wave == 0) {
             // T7 PLL (tracking.py:223-235); carrier parameters of the next block
-            const double I_P = tA, Q_P = tB;
-            const double oldNco = s_st.oldCarrNco, oldErr = s_st.oldCarrErr, basis = s_st.carrBasis;
-            const double carrError = div_rn(atan(Q_P / I_P) / 2.0, M_PI, K.inv_pi);   // atan(Q/I) / 2 / pi
-            const double carrNco = oldNco + K.k_carr_a * (carrError - oldErr) + carrError * K.k_carr_b;
-            const double carrFreq = basis + carrNco;
+            double carrError;
+            const double carrNco = trk_pll_update(tA, tB, s_st.oldCarrNco, s_st.oldCarrErr, K.k_carr_a, K.k_carr_b, K.inv_pi, carrError);
+            const double carrFreq = s_st.carrBasis + carrNco;
             const double w_new = (carrFreq * 2.0) * M_PI;
             const double rc = s_rc;
             if (more) prep_carr(K, w_new, rc, (int)((pos + blk) & 15), s_blk, lane);
@@ -400,14 +278,10 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
             }
         } else if (wave == 1) {
             // T8 DLL (tracking.py:238-251), then block size and ramps of the next block (T1, T3, T4)
-            const double I_E = tA, Q_E = tB, I_L = tC, Q_L = tD;
-            const double oldNco = s_st.oldCodeNco, oldErr = s_st.oldCodeErr;
             const long long pos_after = s_st.pos;
             const double rem_next = s_st.remCode;
-            const double eE = sqrt(I_E * I_E + Q_E * Q_E);
-            const double eL = sqrt(I_L * I_L + Q_L * Q_L);
-            const double codeError = (eE - eL) / (eE + eL);
-            const double codeNco = oldNco + K.k_code_a * (codeError - oldErr) + codeError * K.k_code_b;
+            double codeError;
+            const double codeNco = trk_dll_update(tA, tB, tC, tD, s_st.oldCodeNco, s_st.oldCodeErr, K.k_code_a, K.k_code_b, codeError);
             const double codeFreq = K.code_basis - codeNco;
             if (lane == 0) {
                 s_st.oldCodeNco = codeNco;
@@ -426,15 +300,7 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         else if (wave == 2 && member == 0) {
             // record (T9) of the PREVIOUS block: its six sums and scalar series were staged in LDS by the
             // filter waves and are visible since the last barrier - off the critical path
-            if (it > 0 && lane < 6) {
-                const int series = (lane == 0) ? 4 : (lane == 1) ? 6 : (lane == 2) ? 3 : (lane == 3) ? 7 : (lane == 4) ? 5 : 8;
-                o[series * m + (it - 1)] = s_tot[(it - 1) & 1][lane];
-            }
-            if (it > 0 && lane >= 8 && lane < 16 && lane != 11) {
-                const int k = lane - 8;
-                const int series = (k == 0) ? 2 : (k == 1) ? 11 : (k == 2) ? 12 : (k == 4) ? 0 : (k == 5) ? 1 : (k == 6) ? 9 : 10;
-                o[series * m + (it - 1)] = s_out[(it - 1) & 1][k];
-            }
+            if (it > 0) trk_store_row(o, K.ms, it - 1, s_tot[(it - 1) & 1], s_out[(it - 1) & 1], lane);
         }
         done = it + 1;
         PROBE(11);  // loop filter (this wave's side) + next block's parameters
@@ -454,15 +320,7 @@ static __device__ __forceinline__ void trk_persample_body(const int8_t* __restri
         prof[ch * 64 + 2] = pf_red;
         prof[ch * 64 + 3] = pf_flt;
     }
-    if (wave == 2 && member == 0 && done > 0 && lane < 6) {
-        const int series = (lane == 0) ? 4 : (lane == 1) ? 6 : (lane == 2) ? 3 : (lane == 3) ? 7 : (lane == 4) ? 5 : 8;
-        o[series * (long long)K.ms + (done - 1)] = s_tot[(done - 1) & 1][lane];
-    }
-    if (wave == 2 && member == 0 && done > 0 && lane >= 8 && lane < 16 && lane != 11) {
-        const int k = lane - 8;
-        const int series = (k == 0) ? 2 : (k == 1) ? 11 : (k == 2) ? 12 : (k == 4) ? 0 : (k == 5) ? 1 : (k == 6) ? 9 : 10;
-        o[series * (long long)K.ms + (done - 1)] = s_out[(done - 1) & 1][k];
-    }
+    if (wave == 2 && member == 0 && done > 0) trk_store_row(o, K.ms, done - 1, s_tot[(done - 1) & 1], s_out[(done - 1) & 1], lane);
 #ifdef TRK_FINEPROF
     if (tid == 0 && prof && member == 0 && ch == 0) {
         for (int k = 0; k < 13; ++k) printf("[fineprof] probe %2d: %8.1f cycles/block\n", k, (double)fp[k] / K.ms);

@@ -25,7 +25,7 @@
 //   per pair of dwords de-interleave a run into a low and a high plane, four samples per dword like an int8 run, so the
 //   same forty weight dwords serve).  sum_k x_k B_k = [256 sum h B] + sum x' B + 128 sum_{k < len} B_k; the last term from a
 //   per-block table of prefix sums of the integer weights (exact).  int16: twice the dot products of int8.
-#include "sgx_trk_common.h"
+#include "sgx_trk_block.h"   // (the code table and the loop state's start; the map, fold and record here are this kernel's own)
 #include "sgx_trk_math.h"
 
 // Threads per workgroup (one channel) and workgroups per CU the register budget is cut for.  Measured on 2048 channels
@@ -326,24 +326,8 @@ __global__ __launch_bounds__(TP_THREADS, TP_OCC) void trk_kernel_tp(const int8_t
     const int8_t* __restrict__ const rec = rec0 + cc.pad;
     const long long rec_samples = (K.rec_len - cc.pad) / SB;
     const long long alloc_bytes = K.rec_alloc - cc.pad;
-    for (int i = tid; i < 1028; i += TP_THREADS) {
-        int j = i - 1;
-        if (j < 0) j = 1022;
-        if (j >= 1023) j -= 1023;
-        if (j >= 1023) j -= 1023;
-        s_code_hi[i] = (codes[(cc.prn - 1) * 1023 + j] > 0) ? 0x3FF00000u : 0xBFF00000u;
-    }
-    if (tid == 0) {   // tracking.py:114-130
-        s_st.codeFreq = K.code_basis;
-        s_st.remCode = 0.0;
-        s_st.oldCodeNco = s_st.oldCodeErr = 0.0;
-        s_st.pos = cc.pos0;
-        s_st.carrFreq = cc.acquiredFreq;
-        s_st.carrBasis = cc.acquiredFreq;
-        s_st.remCarr = 0.0;
-        s_st.w = (cc.acquiredFreq * 2.0) * M_PI;
-        s_st.oldCarrNco = s_st.oldCarrErr = 0.0;
-    }
+    trk_code_table(s_code_hi, codes, cc.prn, tid, TP_THREADS);
+    if (tid == 0) trk_state_start(s_st, K, cc);
     __syncthreads();
     if (wave == 0) {
         tp_tables(K, s_st.w, s_st.remCarr, s_car, lane, 0);

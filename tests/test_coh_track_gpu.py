@@ -78,8 +78,12 @@ def _trio(ms, fs=cases.FS_LOW, IF=cases.IF_LOW):
 
 
 @pytest.mark.parametrize("fs,IF", [(cases.FS_LOW, cases.IF_LOW), (16.368e6, 4.1304e6)])
-def test_all_1ms_anchor(fs, IF):
-    """The pull-in as long as the run: the spec, and sgx_track's series on the same channels."""
+def test_all_1ms_anchor(fs, IF, monkeypatch):
+    """The pull-in as long as the run: the spec, and sgx_track's series on the same channels - within TOL of the kernels
+    sgx_track picks by itself, and BIT FOR BIT those of the per-sample body with one member per channel, which runs the
+    block pieces the coherent kernel runs (csrc/sgx_trk_block.h): trk_kernel_multi at 4 samples per chip (both take the
+    sample-by-sample map), trk_kernel_any on the same values as an int32 record at 16 samples per chip (both take the
+    one-switch map; positions are bytes there)."""
     m = pkg()
     ms = 300
     s, rec, chans, edges = _trio(ms, fs, IF)
@@ -95,6 +99,23 @@ def test_all_1ms_anchor(fs, IF):
         dev.free()
     assert np.array_equal(done, got[1]) and np.array_equal(plain[:, 0], got[0][:, 0])
     assert _trk_err(got[0], plain, done) < TOL
+    monkeypatch.setenv("SGX_TRK_SPLIT", "1")       # (read at each call: one workgroup per channel)
+    low = fs == cases.FS_LOW
+    dev = ctx.upload(rec) if low else ctx.upload_bytes(rec.astype('<i4'))
+    try:
+        if low:
+            one, done = ctx.track(dev, chans, ms)
+        else:
+            one, done = ctx.track(dev, [(prn, f, 4 * cp) for prn, f, cp in chans], ms, data_type=m._native.DT_INT32)
+            assert np.all(one[:, 0] % 4 == 0)
+            one = one.copy()
+            one[:, 0] /= 4                         # absoluteSample: bytes of the int32 record -> samples
+    finally:
+        dev.free()
+    t = ctx.timing()
+    assert t["track_kernel"] == (4 if low else 6) and t["track_members"] == 1
+    assert np.array_equal(done, got[1])
+    assert np.array_equal(one, got[0], equal_nan=True)
 
 
 @pytest.mark.parametrize("T", [2, 4, 5, 10, 20])
