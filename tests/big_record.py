@@ -462,6 +462,21 @@ def low_rate_window():
     return typed_start(1, LOW_SPC), typed_start(1, LOW_SPC) + (TRACK_MS + 13) * LOW_SPC
 
 
+# The coherent run on the low-rate window (sgx_track_coherent; tests/coh_track_spec.py): groups of 4 blocks behind a pull-in of
+# 40, given edges.  A channel starts within the acquisition's 11 periods of the window's start, TRACK_BEFORE periods before
+# byte 2^32: the boundary falls in the pull-in, and every group (k0 = 43, 51) reads at 33-bit positions.
+LOW_COHERENT = dict(T=4, P=40, H=100, edges=(3, 11))
+
+
+def low_rate_coherent_window():
+    """The bytes the coherent phase of that run reads at the least: from the latest start of its first group (a channel that
+    begins 11 periods into the window, blocks of at most LOW_SPC + 1 samples) to the end of a channel's 80 blocks that
+    begins at the window's start (blocks of at least LOW_SPC - 1)."""
+    w0, _ = low_rate_window()
+    k0 = max(LOW_COHERENT["P"] + (e - LOW_COHERENT["P"]) % 20 for e in LOW_COHERENT["edges"])
+    return w0 + 11 * LOW_SPC + k0 * (LOW_SPC + 1), w0 + TRACK_MS * (LOW_SPC - 1)
+
+
 def scene_windows():
     """Every window of scene8 that the GPU test reads, by the name of what reads it."""
     out = dict(("synth-%d" % i, w) for i, w in enumerate(SYNTH_WINDOWS))

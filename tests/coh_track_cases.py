@@ -1,6 +1,6 @@
 """Scenes shared by the coherent-tracking tests (plain numpy): one or more C/A satellites with random data bits on a
 known bit edge, Gaussian noise, int8.  tests/test_coh_track_cases.py shows on the CPU that they are well-conditioned;
-tests/test_coh_track_gpu.py runs the kernel on them.
+tests/test_coh_track_gpu.py runs the kernel on them, tests/test_coh_track_limits_gpu.py on the cases at the end of this file.
 
 Sample n holds  sum_sat A(n) d(n) c(n) sin(2 pi (IF + doppler) n / fs + phase) + noise:  the code starts at sample
 `start` and runs at codeFreqBasis (1 + doppler / 1575.42e6); bit b covers the code periods edge + 20 b ... edge + 20 b + 19
@@ -117,3 +117,112 @@ def edge_margin(energy):
     """E_max / E_second of one channel's 20 bit-synchronisation energies."""
     e = np.sort(np.asarray(energy, dtype=np.float64))
     return e[-1] / e[-2]
+
+
+# ---- the limits: tests/test_coh_track_limits_gpu.py runs the kernel on what follows, tests/test_coh_track_cases.py shows on
+# the CPU, with the contract alone, that a slip in each case would lie outside the GPU test's bar --------------------------
+
+# 1. RATES.  scene_trio(110, fs, IF), ms = 110, T = 20, P = 40, H = 100, the trio's own edges: a coherent phase at rates that
+# are neither 4.092 nor 38.192 Msps.  (fs, IF, units of 4096 samples the launch holds, the sample-by-sample map?):
+#   5.456 Msps   5.33 samples per chip - no whole number of them (full_scale.LOW_RATE)
+#   15.345 Msps  15 per chip: the last whole rate on the sample-by-sample map, four units
+#   16.368 Msps  16 per chip: the one-switch map, where E, P and L switch 8 samples apart - its sample-by-sample route
+#   61.38 Msps   60 per chip: 16 units, the most the kernel holds
+RATE_SCENES = ((5.456e6, 1.364e6, 2, True), (15.345e6, 3.9e6, 4, True), (16.368e6, 4.1304e6, 5, False), (61.38e6, 15.3e6, 16, False))
+RATE_RUN = dict(ms=110, T=20, P=40, H=100)
+
+
+def trk_units(n_code):
+    """csrc/sgx_trk.hip, sgx_trk_units: the units of 256 groups of 16 samples that hold the longest block, worst alignment."""
+    return -(-((n_code + 94) // 16) // 256)
+
+
+def trk_by_sample(fs):
+    """csrc/sgx_trk.hip, sgx_trk_multi: under ~15.4 samples per chip a group of 16 can hold several switches of a ramp."""
+    return 15.0 * 1.001 * 1.023e6 / fs >= 1.0
+
+
+# 2. A RECORD AT AN OFFSET.  The record a call is given starts at byte `off` of the file and the channels keep their file
+# positions.  A channel that starts in front of `off` is moved behind it by whole code periods (4092 samples: the code phase
+# holds), and its bit edge with it - block k of the moved channel is code period k + periods of the satellite.
+OFFSETS = dict(window=3 * 4096, odd=3 * 4096 + 5, large=2 ** 33 + 4096, classes=8192)
+OFFSET_RUN = dict(ms=110, T=10, P=40, H=100)
+OFFSET_SYNC = dict(ms=SYNC_MS, T=20, P=300, H=100)        # 2(e), TrackingResult.track: the edges are found
+
+
+def moved_behind(chans, edges, off, spc=4092):
+    """-> (channels, edges) with every active channel in front of file byte `off` moved behind it by whole code periods."""
+    out_c, out_e = [], []
+    for (prn, f, cp), e in zip(chans, edges):
+        k = max(0, -(-(off - int(cp)) // spc)) if prn else 0
+        out_c.append((prn, f, cp + spc * k))
+        out_e.append((e - k) % 20 if prn else e)
+    return out_c, out_e
+
+
+# 4. MANY CHANNELS.  300 rows: 294 active ones with pairwise different carriers and edges, six that are off - at the table's
+# start, around the 64 rows up to which the call's int arrays fill one 256-byte slot, and further in.  ms = 60, T = 4, H = 7.
+MANY = 300
+MANY_OFF = (0, 63, 64, 65, 128, 298)
+MANY_RUN = dict(ms=60, T=4, P=40, H=7)
+
+
+def many_channels(chans, edges, n=MANY):
+    """-> (n channels, n edges): row i is satellite i % 3, (i // 3) / 4 - 10 Hz beside it, its edge moved on by i."""
+    rows = [(0, 0.0, 0.0) if i in MANY_OFF else (chans[i % 3][0], chans[i % 3][1] + (i // 3) * 0.25 - 10.0, chans[i % 3][2])
+            for i in range(n)]
+    return rows, [(edges[i % 3] + i) % 20 for i in range(n)]
+
+
+# 5. FULL SCALE.  tests/full_scale.py's records of 104 ms at its low rate and at the default front end: one whose every byte
+# is -128 or 127, one noiseless at amplitude 127.  One channel, 2 Hz beside the carrier; ms = 100, T = 20, edge 3.
+FULL_SCALE_RATES = ((5456000.0, 1364000.0), (38.192e6, 9.548e6))
+FULL_SCALE_RUN = dict(ms=100, T=20, P=40, H=100)
+FULL_SCALE_EDGE = 3
+
+
+def full_scale_case(m, fs, IF, kind):
+    """kind 'clipped' | 'clean' -> (oracle settings, int8 record, [channel])."""
+    import full_scale as fsc
+    ps = m.Settings()
+    ps.samplingFreq, ps.IF = fs, IF
+    rec = fsc.clipped_record(m, ps, "int8", 104) if kind == "clipped" else fsc.clean_record(m, ps, 127, 104).astype(np.int8)
+    prn, f, start = fsc.clean_channel(ps)
+    return settings(fs, IF), rec, [(prn, f + 2.0, float(start))]
+
+
+# 6. T = 1 through the entry point: the 400 ms trio, P = 300, the edges found; k0 = -1 and the reference's series throughout.
+# (P = 220 would not do: 1.03 on the edge-19 channel, as above.)
+T1_RUN = dict(ms=300, T=1, P=300, H=100)
+
+# 7. A CHANNEL THAT ENDS WHILE ITS EDGE IS SOUGHT (T = 20, P = 220, ms = 300, every edge -1): zeros from block 100 of channel 0
+# on, and a record cut 100 samples into its block 150.  The edge stays -1, k0 -1, the energies are those of the whole
+# 20-block sums so far.
+ENDS_RUN = dict(ms=300, T=20, P=220, H=100)
+
+
+def ends_early(rec, chans, how):
+    at = int(chans[0][2])
+    if how == "silence":
+        out = rec.copy()
+        out[at + 100 * 4092:] = 0
+        return out
+    return rec[:at + 150 * 4092 + 100]
+
+
+# 8. A BLOCK BEYOND THE UNITS (tests/test_gpu_parity.py's range test): synth.Scene.default() of 80 periods at 38.192 Msps,
+# two channels off any signal; ten units of 4096 samples.  dllNoiseBandwidth 2000 still fits, 6000 does not.
+RANGE_CHANNELS = [(7, 9.548e6, 1234.0), (1, 9.5478e6, 12345.0)]
+RANGE_RUN = dict(ms=60, T=4, P=40, H=100)
+RANGE_ROOM = 10 * 4096 - 15
+
+# 9. OTHER LOOPS.  ms = 150, T = 10: a quarter-chip spacing, and other 1 ms loops; both with coherent loops of 8 and 0.5 Hz.
+LOOPS_RUN = dict(ms=150, T=10, P=40, H=100)
+LOOPS_COH = dict(cohPllNoiseBandwidth=8.0, cohDllNoiseBandwidth=0.5)
+LOOPS = (dict(dllCorrelatorSpacing=0.25),
+         dict(pllDampingRatio=0.9, dllDampingRatio=0.5, pllNoiseBandwidth=18.0, dllNoiseBandwidth=3.0))
+LOOPS_DEFAULT_RUN = dict(ms=120, T=10, P=40, H=100)        # the quarter chip at 38.192 Msps: 9.3 samples, edges [3, 11]
+
+# 10. BESIDE CANCELLATION: the trio of 400 ms in a DeviceFile at file offset 4096, channel 0 moved; ms = 110, T = 20.
+CANCEL_OFF = 4096
+CANCEL_RUN = dict(ms=110, T=20, P=40, H=100)

@@ -15,11 +15,13 @@ import numpy as np
 import pytest
 
 import big_record as big
+import coh_track_spec as coh_spec
 import coherent_acq_spec
 import replay_spec
 import waterfall_spec
 from conftest import pkg
 from oracle import softgnss_oracle as orc
+from test_coh_track_gpu import _same as _same_as_the_contract
 
 pytestmark = pytest.mark.gpu
 
@@ -632,9 +634,23 @@ def test_track_low_rate_int8_record_made_on_the_device(capsys):
         want[:, 0] += w0
         got, done = ctx.track(dev, [(p, f, w0 + cp) for p, f, cp in rel], big.TRACK_MS)
         assert ctx.timing()["track_kernel"] == 4
+        # the coherent kernel on the same device record and the same downloaded window (big.LOW_COHERENT: the boundary falls
+        # in the pull-in, every group lies at 33-bit positions); the scene has no data bits, so any edge is a true one
+        coh = big.LOW_COHERENT
+        c0, c1 = big.low_rate_coherent_window()
+        big.wrap_visible(big.scene_reader(m.synth.generate, sc), big.identity, (c0, c0 + big.PROBE_RULE))
+        want_coh = coh_spec.track(so, rel, host, big.TRACK_MS, coh["T"], coh["P"], coh["H"], list(coh["edges"]))
+        assert list(want_coh["ms_done"]) == [big.TRACK_MS] * 2 and list(want_coh["k0"]) == [43, 51]
+        assert np.all(want_coh["series"][:, 0, 0] + w0 < big.B32) and np.all(want_coh["series"][:, 0, coh["P"] - 1] + w0 > big.B32)
+        want_coh["series"][:, 0] += w0
+        got_coh = ctx.track_coherent(dev, [(p, f, w0 + cp) for p, f, cp in rel], big.TRACK_MS,
+                                     m._native.coh_params(s, coh["T"], coh["P"], coh["H"]), bit_edge=list(coh["edges"]))
+        assert ctx.timing()["track_kernel"] == 7
     finally:
         dev.free()
     _same_as_the_oracle(capsys, "trk_kernel_multi at 4.092 Msps across 2^32", got, done, want)
+    with capsys.disabled():
+        _same_as_the_contract(got_coh, want_coh)
 
 
 def test_track_low_rate_uint8_sparse_record(capsys):

@@ -175,6 +175,12 @@ def test_scene_and_sparse_windows_obey_the_rule():
     w0, w1 = big.low_rate_window()
     assert 0 < w0 < big.B32 < w1 <= big.LOW_N
     big.wrap_visible(low, big.identity, (w0, w0 + big.PROBE_RULE))
+    # the coherent run on that window: the boundary lies in its pull-in, and what its groups read - all of it beyond 2^32 -
+    # obeys the rule as well
+    c0, c1 = big.low_rate_coherent_window()
+    assert w0 + big.LOW_COHERENT["P"] * (big.LOW_SPC - 1) > big.B32 > w0 + 11 * big.LOW_SPC and big.B32 < c0 < c1 <= w1
+    assert c0 + big.PROBE_RULE <= c1
+    big.wrap_visible(low, big.identity, (c0, c0 + big.PROBE_RULE))
     # the typed sparse records: the payload starts 20 code periods (of its sample width) before byte 2^32
     for isz, spc in ((2, big.SPC), (4, big.SPC), (1, big.LOW_SPC)):
         start, nbytes = big.typed_start(isz, spc), (big.TRACK_MS + 13) * spc * isz
