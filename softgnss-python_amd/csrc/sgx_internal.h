@@ -213,17 +213,15 @@ private:
 };
 // Tracking (sgx_trk.hip).  kind: SGX_DT_*.  int8 / uint8 / int16 run the typed kernels (sgx_trk2 / sgx_trk3 / sgx_trk_tp);
 // every other type - and int16 / uint8 at sampling rates below 16 x the chip rate - the per-sample kernel of sgx_trk_any.hip.
-// skip_bytes: Settings.skipNumberOfBytes, or what stands in for it (sgx_trk_f32.hip tracks a narrowed copy of a window).
-// fscale > 0 (float32 / float64 only): every sample the channels can reach is finite and at most 128 / fscale in magnitude
-// (sgx_trk_f32.hip has scanned the window; fscale is a power of two) - the record then runs the latency-mode kernel, which
-// scales the samples by it on conversion; the correlator series are scaled back.  0: the per-sample kernel.
+// The one entry of every eager tracking call.  It describes what the call runs on (TrkSource, sgx_trk_common.h: the bytes, the
+// sample kind, every channel's start, the undo) and runs that description; the chained call makes its own, without a host table.
 int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                   int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale);
-// float32 records by exact narrowing to int8 / int16 (sgx_trk_f32.hip)
-int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
-                      double* out, int32_t* ms_done);
-int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
-                      double* out, int32_t* ms_done);
+                   int32_t ms, double* out, int32_t* ms_done, int kind);
+// The float front (sgx_trk_f32.hip), sgx_track_kind's way for float32 / float64: one scan of the window the channels can reach
+// picks the route - the per-sample kernel, the latency-mode kernel on samples scaled by a power of two, or (float32) an exact
+// int8 / int16 copy of the window with the map back to the caller's file - and the description says which.
+int sgx_track_float(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
+                    double* out, int32_t* ms_done, int kind);
 
 // ---- acquisition (sgx_acq.hip): the limits and the small structs its kernels hand to each other and to the host ----
 #define ACQ_MAX_BINS 128          // Doppler bins of the 1-ms search

@@ -74,30 +74,28 @@ __global__ __launch_bounds__(256) void if_mag_kernel(const int8_t* __restrict__ 
 
 // -> the bound (cached in the handle), or -1 when the record is not fully resident yet / on an error
 // (resident: every copy has completed - host_mark reaches the end a moment before the loader thread sets load_done)
-static long long if_mag_bound(sgx_ctx* c, const sgx_if* r) {
-    long long known = r->mag_max.load();
-    if (known >= 0) return known;
-    if (r->loader && !r->load_done.load() && r->host_mark.load() < r->n) return -1;
+// (a buffer of the call's own, S.rec null, is resident and has no handle to cache the bound in)
+static long long if_mag_bound(sgx_ctx* c, const TrkSource& S) {
+    const sgx_if* r = S.rec;
+    if (r) {
+        long long known = r->mag_max.load();
+        if (known >= 0) return known;
+        if (r->loader && !r->load_done.load() && r->host_mark.load() < r->n) return -1;
+    }
     int* d_max = &c->d_small->trk_mag;
     if (hipMemsetAsync(d_max, 0, sizeof(int), c->stream) != hipSuccess) return -1;
-    const long long n_blocks128 = ((long long)r->n + 127) / 128;
+    const long long n_blocks128 = (S.n + 127) / 128;
     const unsigned grid = (unsigned)((n_blocks128 + 255) / 256);
-    if_mag_kernel<<<grid ? grid : 1u, 256, 0, c->stream>>>(r->d, (long long)r->n + SGX_IF_PAD - 128, d_max);
+    if_mag_kernel<<<grid ? grid : 1u, 256, 0, c->stream>>>(S.d, S.n + SGX_IF_PAD - 128, d_max);
     int h = 0;
     if (hipMemcpyAsync(&h, d_max, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-    const_cast<sgx_if*>(r)->mag_max.store((long long)h);
+    if (r) const_cast<sgx_if*>(r)->mag_max.store((long long)h);
     return (long long)h;
 }
 
-// The environment a tracking call reads, once at its entry: diagnosis switches and test hooks (sgx_track_plan ignores them)
-struct TrkEnv {
-    bool trace, float_typed, v3_off, v3_generic, fast_xcd, profile, stream, withhold, stall, scatter;
-    int split, arms, lds_pad;
-    char timeout;
-};
-
-static TrkEnv trk_env() {
+// (struct TrkEnv: sgx_trk_common.h - the float front reads its two switches from it)
+TrkEnv sgx_trk_env() {
     auto first = [](const char* name) -> char {   // (0 when unset)
         const char* v = getenv(name);
         return v ? v[0] : 0;
@@ -108,6 +106,7 @@ static TrkEnv trk_env() {
     TrkEnv E;
     E.trace = first("SGX_STEP_TRACE") == '1';              // host-side time stamps of the call on stderr, us since its entry
     E.float_typed = first("SGX_TRK_FLOAT_TYPED") != '0';   // '0': float records always on the per-sample kernel
+    E.f32_narrow = first("SGX_TRK_F32_NARROW") != '0';     // '0': no narrowing - every float32 record as floats
     E.split = (split && atoi(split) >= 1) ? atoi(split) : 0;
     E.arms = arms ? (arms[0] == '3' ? 3 : 1) : 0;
     E.v3_off = first("SGX_TRK_V3") == '0';
@@ -197,6 +196,15 @@ int sgx_trk_channels(std::vector<TrkChan>& hc, const sgx_chan_init* ch, int n_ch
         h.pad = (int)(p0 % sample_bytes);
     }
     return SGX_OK;
+}
+
+int sgx_trk_source(TrkSource& S, const sgx_settings& st, const sgx_if* r, long long file_off, const sgx_chan_init* ch, int n_ch, int kind) {
+    S.d = r->d;
+    S.n = (long long)r->n;
+    S.rec = r;
+    S.kind = kind;
+    S.file_off = file_off;
+    return ch ? sgx_trk_channels(S.hc, ch, n_ch, (long long)st.skipNumberOfBytes, file_off, sgx_dt_bytes(kind)) : SGX_OK;
 }
 
 // ---- WHICH KERNEL, HOW MANY MEMBERS: the one rule (include/sgx.h: sgx_track_plan; tests/test_cabi_and_host.py holds the table)
@@ -318,10 +326,9 @@ extern "C" int sgx_track_plan(const sgx_settings* s, int32_t data_type, int32_t 
 // One tracking call: its arguments, and what the stages below make of them
 struct TrkCall {
     sgx_ctx* c;
-    const sgx_if* r;
+    const TrkSource& S;          // what it runs on, and how its results are undone (sgx_trk_common.h)
     const sgx_chan_init* ch;     // null when chained
-    int n_ch, ms, kind, sample_bytes;
-    long long skip_bytes, rec_file_offset;
+    int n_ch, ms;
     double* out;
     int32_t* ms_done;
     bool chained;
@@ -330,7 +337,6 @@ struct TrkCall {
     int cus_total;
     TrkPlan P;
     TrkConst K;
-    std::vector<TrkChan> hc;     // the channel table (not when chained)
     size_t elems;                // n_ch x SGX_NUM_SERIES x ms
     double* d_out;               // the series: the caller's pinned buffer itself (direct), or the context's staging buffer
     bool direct;
@@ -488,18 +494,19 @@ struct CuGuard {
 // the profile, the kernel between ev[3] and ev[4], its result words; -> what trk_repeat makes of them
 static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& again) {
     sgx_ctx* c = T.c;
-    const sgx_if* r = T.r;
+    const TrkSource& S = T.S;
+    const sgx_if* r = S.rec;
     hipStream_t st = c->stream;
     // a record that is still streaming in is followed by the latency-mode kernel (its record wave watches the
     // device watermark); the other kernels, and a launch repeated on the resident record, first wait for all of it
-    const bool streaming = r->loader && !r->load_done.load() && launch == 0 && T.E.stream && (T.P.kernel == 2 || T.P.kernel == 5);
-    if (T.P.kernel == 5 && T.kind == SGX_DT_INT8 && !T.rep.one_member && !T.rep.v3_off && !streaming) {
+    const bool streaming = r && r->loader && !r->load_done.load() && launch == 0 && T.E.stream && (T.P.kernel == 2 || T.P.kernel == 5);
+    if (T.P.kernel == 5 && S.kind == SGX_DT_INT8 && !T.rep.one_member && !T.rep.v3_off && !streaming) {
         // THE SCALE GUARD of every speculative launch that does not stream (sgx_trk3.hip says why 2^17; a streaming launch
         // has its record wave's): a bound computed once per record, before the kernel is chosen and its CUs reserved,
         // whatever the record was when the call began - still loading (SGX_TRK_STREAM=0, a stalled stream) or resident
-        const int rq = sgx_if_require(r, r->n);
+        const int rq = r ? sgx_if_require(r, r->n) : SGX_OK;
         if (rq != SGX_OK) return rq;
-        const long long mag = if_mag_bound(c, r);
+        const long long mag = if_mag_bound(c, S);
         if (mag < 0) {
             sgx_set_error("tracking: the magnitude scan of the record failed");
             return SGX_E_HIP;
@@ -511,10 +518,10 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
         }
     }
     if (!T.chained) {
-        SGX_HIP(hipMemcpyAsync(T.d_ch, T.hc.data(), sizeof(TrkChan) * (size_t)T.n_ch, hipMemcpyHostToDevice, st));
+        SGX_HIP(hipMemcpyAsync(T.d_ch, S.hc.data(), sizeof(TrkChan) * (size_t)T.n_ch, hipMemcpyHostToDevice, st));
     } else if (launch == 0) {
         // preRun on the device: the table lands in d_ch (a repeated launch finds it there)
-        const int rp = sgx_prerun_enqueue(c, T.d_ch, T.n_ch, T.skip_bytes, T.rec_file_offset, T.sample_bytes);
+        const int rp = sgx_prerun_enqueue(c, T.d_ch, T.n_ch, (long long)c->s.skipNumberOfBytes, S.file_off, sgx_dt_bytes(S.kind));
         if (rp != SGX_OK) return rp;
     }
     T.stamp("channel table queued");
@@ -525,7 +532,7 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
     reserved.n = L.cus;
     T.K.split = L.split;
     T.K.n_units = L.n_units;
-    if (!streaming) {
+    if (r && !streaming) {
         const int rq = sgx_if_require(r, r->n);
         if (rq != SGX_OK) return rq;
     }
@@ -539,16 +546,16 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
     const int8_t* codes = c->d_codes;
     switch (L.kernel) {
     case 2:   // (one workgroup per CU only matters while members wait for each other)
-        sgx_trk2_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.sample_bytes,
+        sgx_trk2_launch(nb, st, S.d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, sgx_dt_bytes(S.kind),
                         L.arms, L.split > 1 ? T.E.lds_pad : 0);
         break;
-    case 3: sgx_trk_tp_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
-    case 4: sgx_trk_multi_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    case 3: sgx_trk_tp_launch(nb, st, S.d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    case 4: sgx_trk_multi_launch(nb, st, S.d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
     case 5:
-        sgx_trk3_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.E.lds_pad,
+        sgx_trk3_launch(nb, st, S.d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err, T.E.lds_pad,
                         T.E.v3_generic || T.rep.scattered, T.E.scatter);
         break;
-    case 6: sgx_trk_any_launch(nb, st, r->d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
+    case 6: sgx_trk_any_launch(nb, st, S.d, codes, T.d_ch, T.d_out, T.d_done, T.K, T.d_prof, T.d_xch, T.d_err); break;
     }
     hipEventRecord(c->ev[4], st);
     T.stamp("kernel queued");
@@ -564,7 +571,7 @@ static int trk_launch_once(TrkCall& T, int launch, CuGuard& reserved, bool& agai
 }
 
 // After the last launch: ms_done (and the series out of the staging buffer), the profile, the entries no channel reached,
-// the errors, the kernel time, the float scale undone
+// the errors, the kernel time, the description's undo
 static int trk_finish(TrkCall& T) {
     sgx_ctx* c = T.c;
     const int n_ch = T.n_ch, ms = T.ms;
@@ -616,20 +623,23 @@ static int trk_finish(TrkCall& T) {
         sgx_set_error("tracking kernel: channel %d reported a timeout with split %d", T.h_err - 1, T.K.split);
         return SGX_E_HIP;
     }
-    if (T.r->loader && T.r->load_rc.load() != SGX_OK) return sgx_if_require(T.r, T.r->n);   // the loader failed while the kernel ran
+    const sgx_if* r = T.S.rec;
+    if (r && r->loader && r->load_rc.load() != SGX_OK) return sgx_if_require(r, r->n);   // the loader failed while the kernel ran
     hipEventElapsedTime(&c->timing.track_ms, c->ev[3], c->ev[4]);
     T.stamp("done");
-    if (T.K.fscale != 1.0) {
-        // the kernel tracked fscale x the record: the six correlator series carry the factor (a power of two: exact),
-        // everything the discriminators made of them (ratios) does not
-        const double un = 1.0 / T.K.fscale;
-        for (int i = 0; i < n_ch && !T.chained; ++i) {
-            if (T.ch[i].prn == 0) continue;
-            double* o = T.out + (size_t)i * SGX_NUM_SERIES * (size_t)ms;
-            const int dn = T.ms_done[i] < ms ? T.ms_done[i] : ms;
-            for (int sidx = 3; sidx <= 8; ++sidx)
-                for (int t = 0; t < dn; ++t) o[(size_t)sidx * ms + t] *= un;
-        }
+    // THE UNDO.  The kernel tracked a power of two times the caller's samples (scaled on conversion, or narrowed to integers):
+    // the six correlator series carry the factor (exact), everything the discriminators made of them (ratios) does not.  It
+    // reported absoluteSample, fid.tell() in the reference (tracking.py:255), in bytes of what it read: those of a narrowed
+    // window map back to bytes of the caller's file.  Only rows that were written: a silent channel's are, an off channel has none.
+    const TrkSource& S = T.S;
+    const bool moved = S.pos_a != 1.0 || S.pos_b != 0.0;
+    for (int i = 0; i < n_ch && !T.chained && (moved || S.sums != 1.0); ++i) {
+        if (T.ch[i].prn == 0) continue;
+        double* o = T.out + (size_t)i * SGX_NUM_SERIES * (size_t)ms;
+        const int dn = T.ms_done[i] < ms ? T.ms_done[i] : ms;
+        for (int t = 0; t < dn && moved; ++t) o[t] = o[t] * S.pos_a + S.pos_b;
+        for (int sidx = 3; sidx <= 8 && S.sums != 1.0; ++sidx)
+            for (int t = 0; t < dn; ++t) o[(size_t)sidx * ms + t] *= S.sums;
     }
     return SGX_OK;
 }
@@ -687,15 +697,13 @@ int sgx_trk_diagnose(const sgx_chan_init* ch, const int32_t* look_prn, int n_ch,
 // reference seeks skipNumberOfBytes + codePhase BYTES whatever the sample type and reports fid.tell(), also bytes
 // (tracking.py:107, 255); so a two-byte channel may start on an odd byte - its samples then straddle the file's - and
 // the kernel follows it there (per-channel byte shift of the record pointer, unaligned 16-byte loads).
-// kind, skip_bytes, fscale: sgx_internal.h (sgx_track_kind).
+// What the call runs on - the record as it lies, or what the float front made of it - and how its results are undone: S
+// (TrkSource, sgx_trk_common.h).
 // chained (round 6, sgx_track_chained): `ch` is null - the channel table is made ON THE DEVICE by the preRun kernel queued
 // in front of the first launch (sgx_prerun_enqueue, sgx_acq.hip) from the acquisition that is pending on this context.
-static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                           int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale,
-                           bool chained) {
-    SGX_CHECK_ARG(c && r && (ch || chained) && out && ms_done);
-    const int sample_bytes = sgx_dt_bytes(kind);
-    SGX_CHECK_ARG(sample_bytes >= 1);
+int sgx_track_source(sgx_ctx* c, const TrkSource& S, const TrkEnv& E, const sgx_chan_init* ch, int n_ch, int ms, double* out,
+                     int32_t* ms_done) {
+    const bool chained = !ch;
     SGX_CHECK_ARG(n_ch >= 1 && n_ch <= 65535 && ms >= 1);
     if (!(c->s.dllCorrelatorSpacing > 0.0 && c->s.dllCorrelatorSpacing < 1.0)) {
         // beyond one chip the reference's replica index ceil(t) leaves its 1025-entry code table (or wraps)
@@ -703,27 +711,17 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
         return SGX_E_ARG;
     }
     SGX_HIP(hipSetDevice(c->device));
-    TrkCall T{c, r, ch, n_ch, ms, kind, sample_bytes, skip_bytes, (long long)rec_file_offset, out, ms_done, chained,
-              trk_env(), std::chrono::steady_clock::now()};
-    // (a float record the typed kernel can take: in range, no channel starting inside a sample, not switched off)
-    bool floaty = (kind == SGX_DT_FLOAT32 || kind == SGX_DT_FLOAT64) && fscale > 0.0 && T.E.float_typed;
-    for (int i = 0; i < n_ch && floaty && !chained; ++i) {
-        // (a channel that starts inside a sample reads other values than the ones that were scanned)
-        const long long p0 = skip_bytes + (long long)ch[i].codePhase - rec_file_offset;
-        if (ch[i].prn != 0 && p0 >= 0 && p0 % sample_bytes != 0) floaty = false;
-    }
+    TrkCall T{c, S, ch, n_ch, ms, out, ms_done, chained, E, std::chrono::steady_clock::now()};
     SGX_HIP(hipDeviceGetAttribute(&T.cus_total, hipDeviceAttributeMultiprocessorCount, c->device));
     // THE RULE (trk_plan above), with the diagnostic overrides of this process's environment
-    T.P = trk_plan(c->s, kind, n_ch, (long long)c->n_code, T.cus_total, floaty, T.E.split, T.E.arms, T.E.v3_off);
-    sgx_trk_const(T.K, c->s, (long long)c->n_code, (long long)r->n, kind, T.rec_file_offset, ms, n_ch, T.P.multi);
-    T.K.fast_xcd = T.E.fast_xcd ? 1 : 0;
-    T.K.fscale = (floaty && !T.P.multi) ? fscale : 1.0;   // (a float record on the typed kernel: scaled back at the end)
+    T.P = trk_plan(c->s, S.kind, n_ch, (long long)c->n_code, T.cus_total, S.float_typed, E.split, E.arms, E.v3_off);
+    sgx_trk_const(T.K, c->s, (long long)c->n_code, S.n, S.kind, S.file_off, ms, n_ch, T.P.multi);
+    T.K.fast_xcd = E.fast_xcd ? 1 : 0;
+    T.K.fscale = S.fscale;
     int rc = sgx_trk_units_check((long long)c->n_code, T.P.n_units);
-    // (chained: the channel table is made on the device by preRun instead)
-    if (rc == SGX_OK && !chained) rc = sgx_trk_channels(T.hc, ch, n_ch, skip_bytes, T.rec_file_offset, sample_bytes);
     if (rc == SGX_OK) rc = trk_buffers(T);
     if (rc != SGX_OK) return rc;
-    if (chained && r->loader && !r->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
+    if (chained && S.rec->loader && !S.rec->load_done.load()) return SGX_E_DEFER;   // (a record that is still streaming in)
     CuGuard reserved{c->device, 0};
     bool again = true;
     // at most five launches: a repeat has a cause in T.rep (trk_repeat), said on stderr
@@ -736,9 +734,15 @@ static int track_kind_impl(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset,
     return sgx_trk_diagnose(ch, c->h_look->step.prn, n_ch, ms, out, ms_done, "its block", T.range_ch1, T.L.n_units, c->s.dllNoiseBandwidth);
 }
 
+// A record of `kind` samples tracked as it lies; float32 / float64 records enter through the float front, which may describe
+// them otherwise (sgx_trk_f32.hip)
 int sgx_track_kind(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                   int32_t ms, double* out, int32_t* ms_done, int kind, long long skip_bytes, double fscale) {
-    return track_kind_impl(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, kind, skip_bytes, fscale, false);
+                   int32_t ms, double* out, int32_t* ms_done, int kind) {
+    SGX_CHECK_ARG(c && r && ch && out && ms_done && n_ch >= 1 && ms >= 1 && sgx_dt_bytes(kind) >= 1);
+    if (kind == SGX_DT_FLOAT32 || kind == SGX_DT_FLOAT64) return sgx_track_float(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, kind);
+    TrkSource S;
+    const int rc = sgx_trk_source(S, c->s, r, (long long)rec_file_offset, ch, n_ch, kind);
+    return rc == SGX_OK ? sgx_track_source(c, S, sgx_trk_env(), ch, n_ch, ms, out, ms_done) : rc;
 }
 
 // include/sgx.h: preRun on the device behind the pending acquisition, the tracking kernel behind it, ONE wait.
@@ -750,8 +754,9 @@ extern "C" int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_o
     // rounded up to 8 - with at most 8 configured channels that is the same launch whatever preRun finds)
     if (c->acq_pending.mode != 1 || n_ch < 1 || n_ch > 8) return SGX_E_DEFER;
     if (data_type != SGX_DT_INT8 && data_type != SGX_DT_UINT8) return SGX_E_DEFER;
-    const int rc = track_kind_impl(c, r, rec_file_offset, nullptr, n_ch, ms, out, ms_done, data_type,
-                                   (long long)c->s.skipNumberOfBytes, 0.0, true);
+    TrkSource S;   // (no host table: preRun makes it on the device; tracked as it lies, nothing to undo)
+    (void)sgx_trk_source(S, c->s, r, (long long)rec_file_offset, nullptr, n_ch, data_type);
+    const int rc = sgx_track_source(c, S, sgx_trk_env(), nullptr, n_ch, ms, out, ms_done);
     if (rc != SGX_OK && rc != SGX_E_SILENT) return rc;
     // (the stream has been synchronised: the page is complete - also for a silent channel, whose rows the caller reads with
     // the table below)
@@ -769,18 +774,14 @@ extern "C" int sgx_track_chained(sgx_ctx* c, const sgx_if* r, int64_t rec_file_o
 
 extern "C" int sgx_track(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch,
                          int32_t n_ch, int32_t ms, double* out, int32_t* ms_done) {
-    SGX_CHECK_ARG(c);
-    return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, SGX_DT_INT8, (long long)c->s.skipNumberOfBytes, 0.0);
+    return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, SGX_DT_INT8);
 }
 
 extern "C" int sgx_track_ex(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch,
                             int32_t n_ch, int32_t ms, double* out, int32_t* ms_done, int32_t data_type) {
-    SGX_CHECK_ARG(c);
-    if (data_type == SGX_DT_FLOAT32) return sgx_track_float32(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done);
-    if (data_type == SGX_DT_FLOAT64) return sgx_track_float64(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done);
     if (sgx_dt_bytes(data_type) == 0) {
         sgx_set_error("sgx_track_ex: data_type %d is not one of SGX_DT_* (include/sgx.h)", (int)data_type);
         return SGX_E_ARG;
     }
-    return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, data_type, (long long)c->s.skipNumberOfBytes, 0.0);
+    return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, data_type);
 }

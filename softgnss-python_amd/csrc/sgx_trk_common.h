@@ -121,6 +121,37 @@ void sgx_trk_fill(double* d_out, int ms, size_t elems, hipStream_t st);
 int sgx_trk_diagnose(const sgx_chan_init* ch, const int32_t* look_prn, int n_ch, int ms, const double* out, const int32_t* ms_done,
                      const char* zero_sums, int range_ch1, int n_units, double dll_bw);
 
+// The environment a tracking call reads, once at its entry: diagnosis switches and test hooks (sgx_track_plan ignores them)
+struct TrkEnv {
+    bool trace, float_typed, f32_narrow, v3_off, v3_generic, fast_xcd, profile, stream, withhold, stall, scatter;
+    int split, arms, lds_pad;
+    char timeout;
+};
+TrkEnv sgx_trk_env();
+
+// WHAT A TRACKING CALL RUNS ON: which kernel input, read where, undone how.  sgx_trk_source describes a caller's record as it
+// is; the float front (sgx_trk_f32.hip) rewrites that description after one scan of the window; sgx_track_source runs it.
+struct TrkSource {
+    const int8_t* d;           // the device bytes the kernels read, SGX_IF_PAD zero bytes behind them ...
+    long long n;               // ... and their length
+    const sgx_if* rec;         // the caller's record where d is its memory: it may still stream in (loader, watermark), and it
+                               // caches the speculative kernel's magnitude bound; null: a resident buffer of the call's own
+    int kind;                  // SGX_DT_* of the samples the kernel sees
+    long long file_off;        // the file byte the kernels take d[0] for (TrkConst::file_off)
+    std::vector<TrkChan> hc;   // per channel: its start relative to d (sgx_trk_channels); empty when chained (made on the device)
+    bool float_typed = false;  // float samples that take the latency-mode kernel: the window was scanned - finite, in range, no
+                               // channel inside a sample - and the kernel scales every sample by ...
+    double fscale = 1.0;       // ... this power of two on conversion (TrkConst::fscale; 1: none)
+    // THE UNDO (trk_finish), the identity for every record that is tracked as it lies:
+    double sums = 1.0;                 // the power of two series 3 .. 8 (the six correlator sums) are multiplied by
+    double pos_a = 1.0, pos_b = 0.0;   // absoluteSample = pos_a x (what the kernel reported) + pos_b: bytes of the caller's file
+};
+// a record whose channels start skipNumberOfBytes + codePhase bytes into the file it is byte file_off of (ch null: chained)
+int sgx_trk_source(TrkSource& S, const sgx_settings& st, const sgx_if* r, long long file_off, const sgx_chan_init* ch, int n_ch, int kind);
+// the call: plan, launches, collection, undo, diagnosis (ch null: chained - the channel table is made on the device)
+int sgx_track_source(sgx_ctx* c, const TrkSource& S, const TrkEnv& E, const sgx_chan_init* ch, int n_ch, int ms, double* out,
+                     int32_t* ms_done);
+
 // Per-block parameters: code part written by wave 1, carrier part by wave 0, read by everybody.
 struct TrkBlock {
     long long pos;

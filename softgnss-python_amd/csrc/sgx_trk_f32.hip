@@ -1,66 +1,66 @@
-// Tracking of float32 records (Settings.dataType 'float32'; reference tracking.py:154 reads np.fromfile(fid, dataType,
-// blksize) and computes in float64).  The fast way is EXACT NARROWING: when every sample of the window is m 2^-k for one k
-// (of either sign) and integers m that fit 8 or 16 bits - floats written from ADC samples (k = 0) or normalised by a power
-// of two (int16 / 32768: k = 15) are - the integers are tracked by the int8 / int16 kernels; a power of two commutes with
-// every rounding of the reference's arithmetic, so the correlator series are the integer record's times 2^-k exactly and
-// everything the discriminators make of them (ratios) is untouched.  A record of arbitrary floats has no such k, and a
-// channel may start inside a sample of the file (the reference seeks skipNumberOfBytes + codePhase BYTES, tracking.py:107):
-// both go to the per-sample kernel of sgx_trk_any.hip, which reads every float where it lies.
-#include "sgx_internal.h"
+// The float front of tracking (Settings.dataType 'float32' / 'float64'; reference tracking.py:154 reads np.fromfile(fid,
+// dataType, blksize) and computes in float64): one scan of the window the channels can reach, one route, and the description
+// of what the call then runs on (TrkSource, sgx_trk_common.h).  The fast way for float32 is EXACT NARROWING: when every sample
+// of the window is m 2^-k for one k (of either sign) and integers m that fit 8 or 16 bits - floats written from ADC samples
+// (k = 0) or normalised by a power of two (int16 / 32768: k = 15) are - the integers are tracked by the int8 / int16 kernels;
+// a power of two commutes with every rounding of the reference's arithmetic, so the correlator series are the integer
+// record's times 2^-k exactly and everything the discriminators make of them (ratios) is untouched.  A record of arbitrary
+// floats has no such k: in range it takes the latency-mode kernel, which scales every sample by a power of two on conversion.
+// A channel may start inside a sample of the file (the reference seeks skipNumberOfBytes + codePhase BYTES, tracking.py:107):
+// that, and whatever the other routes cannot hold, goes to the per-sample kernel of sgx_trk_any.hip, which reads every float
+// where it lies.
+#include "sgx_trk_common.h"
 
+#include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <vector>
+#include <type_traits>
 
-// the power of two that brings a record whose largest |sample| is mx to at most 128 (what the typed kernels' fixed point
-// is cut for); 1 for an all-zero record
-// The typed kernel's granules are a fixed point cut for samples of comparable size (2^-28 of the largest): a record whose
-// largest sample towers 2^12 times above the mean |x| (an outlier, a burst) would lose the small ones' last digits against
-// the reference's float64 sums - such a record takes the per-sample kernel (0 is returned).
-static double scale_for(double mx, double sum_abs, long long n) {
-    if (!(mx > 0.0)) return 1.0;
-    if (n > 0 && mx > 4096.0 * (sum_abs / (double)n)) return 0.0;
-    int ex = 0;
-    (void)frexp(mx, &ex);          // mx = m 2^ex, 1/2 <= m < 1
-    // (records near the ends of the float64 range: the scale, its reciprocal or the reference's own I^2 + Q^2 would
-    // leave the range - the per-sample kernel follows the reference there, overflow and all)
-    if (7 - ex > 900 || 7 - ex < -900) return 0.0;
-    return ldexp(1.0, 7 - ex);
-}
+// What the scan leaves.  sum_abs is for a threshold only: the order of its additions is not fixed.
+struct FScan {
+    unsigned long long mx;   // the bits of the largest finite |x| (the bits of non-negative floats order like integers)
+    unsigned lo;             // float32: smallest exponent of a sample's lowest set bit + 1024 (F_NO_BIT: no nonzero sample)
+    unsigned bad;            // a sample that is not finite was seen
+    double sum_abs;          // the sum of |x| over the finite samples
+};
+#define F_NO_BIT 0x7FFFFFFFu
 
-// [0]: largest |x| (float bits), [1]: smallest exponent of a sample's lowest set bit + 1024 (0x7FFFFFFF: no nonzero sample),
-// [2]: a sample that is not finite was seen; sum_abs: the sum of |x| over the finite samples (for a threshold only: the
-// order of its additions is not fixed)
-__global__ __launch_bounds__(256) void f32_scan_kernel(const float* __restrict__ x, long long n, unsigned* __restrict__ st,
-                                                       double* __restrict__ sum_abs) {
-    unsigned mx = 0u, lo = 0x7FFFFFFFu, bad = 0u;
+template <typename F>
+__global__ __launch_bounds__(256) void f_scan_kernel(const F* __restrict__ x, long long n, FScan* __restrict__ st) {
+    constexpr bool f32 = sizeof(F) == 4;
+    typedef typename std::conditional<f32, unsigned, unsigned long long>::type U;
+    constexpr int MANT = f32 ? 23 : 52;
+    constexpr U E_ALL = f32 ? 255 : 2047;
+    unsigned long long mx = 0ull;
+    unsigned lo = F_NO_BIT, bad = 0u;
     double sa = 0.0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned u = __float_as_uint(x[i]) & 0x7FFFFFFFu;
-        const unsigned e = u >> 23, m = u & 0x7FFFFFu;
-        if (e == 255u) bad = 1u;
-        if (u != 0u && e != 255u) {
+        const U u = __builtin_bit_cast(U, x[i]) & ~(U(1) << (8 * sizeof(F) - 1));
+        const U e = u >> MANT;
+        if (e == E_ALL) bad = 1u;
+        if (u == 0 || e == E_ALL) continue;
+        mx = u > mx ? u : mx;
+        sa += (double)__builtin_bit_cast(F, u);
+        if constexpr (f32) {
             // value = (m | implicit) 2^(e - 150) (a subnormal: m 2^-149): the exponent of its lowest set bit
-            const unsigned full = e ? (m | 0x800000u) : m;
+            const unsigned m = u & 0x7FFFFFu, full = e ? (m | 0x800000u) : m;
             const int lb = (int)(e ? e : 1u) - 150 + (__ffs((int)full) - 1);
             const unsigned key = (unsigned)(lb + 1024);
             lo = key < lo ? key : lo;
-            mx = u > mx ? u : mx;
-            sa += (double)__uint_as_float(u);
         }
     }
     for (int off = 32; off > 0; off >>= 1) {
-        const unsigned omx = __shfl_down(mx, off), olo = __shfl_down(lo, off), ob = __shfl_down(bad, off);
+        const unsigned long long omx = __shfl_down(mx, off);
+        const unsigned olo = __shfl_down(lo, off), ob = __shfl_down(bad, off);
         mx = omx > mx ? omx : mx;
         lo = olo < lo ? olo : lo;
         bad |= ob;
         sa += __shfl_down(sa, off);
     }
     if ((threadIdx.x & 63) == 0) {
-        atomicMax(&st[0], mx);
-        atomicMin(&st[1], lo);
-        if (bad) atomicOr(&st[2], 1u);
-        if (sum_abs) atomicAdd(sum_abs, sa);
+        atomicMax(&st->mx, mx);
+        atomicMin(&st->lo, lo);
+        if (bad) atomicOr(&st->bad, 1u);
+        atomicAdd(&st->sum_abs, sa);
     }
 }
 
@@ -72,209 +72,134 @@ __global__ __launch_bounds__(256) void f32_narrow_kernel(const float* __restrict
         y[i] = (T)(int)(x[i] * s);
 }
 
-int sgx_track_float32(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                      int32_t ms, double* out, int32_t* ms_done) {
-    SGX_CHECK_ARG(c && r && ch && out && ms_done);
-    SGX_CHECK_ARG(n_ch >= 1 && ms >= 1);
-    const sgx_settings& S = c->s;
-    const long long skip = (long long)S.skipNumberOfBytes;
-    // the per-sample kernel (fs = 0), or the latency-mode kernel on samples scaled by the power of two fs
-    auto generic = [&](double fs = 0.0) {
-        return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, SGX_DT_FLOAT32, skip, fs);
-    };
-    const char* ne = getenv("SGX_TRK_F32_NARROW");       // '0': no narrowing - every float32 record as floats
-    const bool no_narrow = ne && ne[0] == '0';
-    long long first = -1, last = -1;
-    for (int i = 0; i < n_ch; ++i) {
-        if (ch[i].prn == 0) continue;
-        const long long p0 = skip + (long long)ch[i].codePhase - rec_file_offset;
-        if (p0 < 0) {
-            sgx_set_error("channel %d starts at file byte %lld, before the record (offset %lld)", i,
-                          skip + (long long)ch[i].codePhase, (long long)rec_file_offset);
-            return SGX_E_RANGE;
-        }
-        // a channel that starts inside a sample of the file reads the bit patterns of bytes of two samples (the reference
-        // does): nothing to narrow
-        if (p0 % 4 != 0) return generic();
-        first = (first < 0 || p0 < first) ? p0 : first;
-        last = p0 > last ? p0 : last;
+// THE WINDOW the channels can reach, in samples of sb bytes from the description's first byte: [first, end), with the same
+// allowance per block as the kernels' units (64 samples, sgx_trk.hip), cut to the record's whole samples.  false: nothing to
+// scan - no channel is on, no whole sample (the kernel reports the short read), or a channel starts inside a sample of the
+// file: it reads the bit patterns of bytes of two samples (the reference does), other values than a scan would see.
+static bool f_window(const TrkSource& S, int sb, long long ms, long long n_code, long long& first, long long& end) {
+    long long last = -1;
+    first = -1;
+    for (const TrkChan& h : S.hc) {
+        if (h.prn == 0) continue;
+        if (h.pad != 0) return false;
+        first = (first < 0 || h.pos0 < first) ? h.pos0 : first;
+        last = h.pos0 > last ? h.pos0 : last;
     }
-    if (first < 0) return generic();   // nothing to track
-    // the window the channels can reach: the same allowance per block as the kernels' units (64 samples, sgx_trk.hip)
-    const long long n_code = c->n_code;
-    long long end = last + ((long long)ms * (n_code + 64) + n_code) * 4;
-    if (end > (long long)r->n) end = (long long)r->n;
-    end &= ~3ll;
-    const long long n_samp = (end - first) / 4;
-    if (n_samp <= 0) return generic();  // (no whole sample: the kernel reports the short read)
-    {
-        const int rq = sgx_if_require(r, (size_t)end);   // (a streaming record: the scan needs every sample)
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    DevBuf<unsigned> d_st;   // [3 words | pad | sum of |x|]
-    int rc = d_st.ensure(4 * sizeof(unsigned) + sizeof(double));
+    end = std::min(last + ms * (n_code + 64) + n_code, S.n / sb);
+    return first >= 0 && end > first;
+}
+
+// The scan of n samples at x, launched and read back
+static int f_scan(sgx_ctx* c, const int8_t* x, long long n, int kind, FScan& h) {
+    DevBuf<FScan> d_st;
+    const int rc = d_st.ensure(sizeof(FScan));
     if (rc != SGX_OK) return rc;
-    const unsigned h_init[6] = {0u, 0x7FFFFFFFu, 0u, 0u, 0u, 0u};
-    unsigned h_st[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    const float* x = reinterpret_cast<const float*>(r->d + first);
-    hipError_t e = hipMemcpyAsync(d_st, h_init, sizeof(h_init), hipMemcpyHostToDevice, c->stream);
+    h = FScan{0ull, F_NO_BIT, 0u, 0.0};
+    hipError_t e = hipMemcpyAsync(d_st, &h, sizeof(h), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        const int grid = (int)((n_samp + 255) / 256 < 4096 ? (n_samp + 255) / 256 : 4096);
-        f32_scan_kernel<<<grid, 256, 0, c->stream>>>(x, n_samp, d_st, reinterpret_cast<double*>(d_st + 4));
-        e = hipMemcpyAsync(h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
+        const int grid = (int)std::min((n + 255) / 256, 4096ll);
+        if (kind == SGX_DT_FLOAT32) f_scan_kernel<float><<<grid, 256, 0, c->stream>>>(reinterpret_cast<const float*>(x), n, d_st);
+        else f_scan_kernel<double><<<grid, 256, 0, c->stream>>>(reinterpret_cast<const double*>(x), n, d_st);
+        e = hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        sgx_set_error("float32 record scan: %s", hipGetErrorString(e));
-        return SGX_E_HIP;
-    }
-    if (h_st[2]) return generic();      // NaN or infinite samples: numpy's arithmetic carries them, so does the kernel
-    int k = 0;
-    double peak = 0.0;
-    if (h_st[1] != 0x7FFFFFFFu) {
-        const int lb = (int)h_st[1] - 1024;     // every sample is a multiple of 2^lb
-        k = -lb;                                // (negative for records of multiples of 2^j, j > 0)
-        float mxf;
-        memcpy(&mxf, &h_st[0], sizeof(mxf));
-        peak = ldexp((double)mxf, k);
-    }
-    {
-        float mxf;
-        memcpy(&mxf, &h_st[0], sizeof(mxf));
-        if (no_narrow || k > 120 || k < -120 || peak > 32767.0)   // arbitrary floats: the latency-mode kernel reads them as they are
-        {
-            double sum_abs;
-            memcpy(&sum_abs, &h_st[4], sizeof(sum_abs));
-            return generic(scale_for((double)mxf, sum_abs, n_samp));
-        }
-    }
-    const bool narrow8 = peak <= 127.0;
+    if (e == hipSuccess) return SGX_OK;
+    sgx_set_error("float%d record scan: %s", 8 * sgx_dt_bytes(kind), hipGetErrorString(e));
+    return SGX_E_HIP;
+}
+
+// THE ROUTE of a scanned window of n samples: which kernel, on what
+struct FRoute {
+    enum Way { PER_SAMPLE, TYPED, NARROW8, NARROW16 } way;
+    double fscale;   // TYPED: the power of two the kernel scales the samples by
+    int k;           // NARROW8 / NARROW16: the integers are the samples times 2^k
+};
+static FRoute f_route(const FScan& s, long long n, int kind, const TrkEnv& E, bool multi) {
+    const FRoute per_sample{FRoute::PER_SAMPLE, 1.0, 0};
+    // NaN or infinite samples: numpy's arithmetic carries them, so does the per-sample kernel
+    if (s.bad) return per_sample;
+    const bool f32 = kind == SGX_DT_FLOAT32;
+    const double mx = f32 ? (double)__builtin_bit_cast(float, (unsigned)s.mx) : __builtin_bit_cast(double, s.mx);
+    // float32: every sample is a multiple of 2^lb, so an integer times 2^-k, k = -lb (negative for records of multiples of
+    // 2^j, j > 0), the largest of them `peak`; integers that fit 16 bits are narrowed, to int8 where they fit 8
+    // (SGX_TRK_F32_NARROW=0: never; an all-zero window: k = 0, int8)
+    const int k = s.lo != F_NO_BIT ? 1024 - (int)s.lo : 0;
+    const double peak = s.lo != F_NO_BIT ? ldexp(mx, k) : 0.0;
+    if (f32 && E.f32_narrow && k <= 120 && k >= -120 && peak <= 32767.0)
+        return FRoute{peak <= 127.0 ? FRoute::NARROW8 : FRoute::NARROW16, 1.0, k};
+    // arbitrary floats: the latency-mode kernel reads them as they are (SGX_TRK_FLOAT_TYPED=0: never; nor at fewer than ~15.4
+    // samples per chip, where no typed kernel runs: trk_plan) and scales them on conversion by the power of two that
+    // brings the largest |sample| to at most 128 (what the typed kernels' fixed point is cut for); 1 for an all-zero window
+    if (!E.float_typed || multi) return per_sample;
+    if (!(mx > 0.0)) return FRoute{FRoute::TYPED, 1.0, 0};
+    // The typed kernel's granules are a fixed point cut for samples of comparable size (2^-28 of the largest): a window whose
+    // largest sample towers 2^12 times above the mean |x| (an outlier, a burst) would lose the small ones' last digits against
+    // the reference's float64 sums - such a record takes the per-sample kernel.
+    if (mx > 4096.0 * (s.sum_abs / (double)n)) return per_sample;
+    int ex = 0;
+    (void)frexp(mx, &ex);          // mx = m 2^ex, 1/2 <= m < 1
+    // (records near the ends of the float64 range: the scale, its reciprocal or the reference's own I^2 + Q^2 would
+    // leave the range - the per-sample kernel follows the reference there, overflow and all)
+    if (7 - ex > 900 || 7 - ex < -900) return per_sample;
+    return FRoute{FRoute::TYPED, ldexp(1.0, 7 - ex), 0};
+}
+
+// The float32 window [first, first + n) as 8- or 16-bit integers (x 2^k) in `buf`: S becomes the description of that copy -
+// its first sample at byte 0, every channel where it started in the window - with the way back: the kernel's positions are
+// bytes of the copy, sb per 4 of the file behind the window's first byte, and the six correlator series carry the 2^k.
+static int f_narrow(sgx_ctx* c, TrkSource& S, long long first, long long n, int k, bool narrow8, DevBuf<int8_t>& buf) {
     const int sb = narrow8 ? 1 : 2;
-    // the integer record: the window only, its first sample at record byte 0
-    sgx_if tmp;
-    tmp.device = c->device;
-    tmp.n = (size_t)n_samp * (size_t)sb;
-    DevBuf<int8_t> narrowed;   // (owns the record's memory: tmp is a handle for sgx_track_kind only)
-    rc = narrowed.ensure(tmp.n + SGX_IF_PAD);
+    const size_t bytes = (size_t)n * (size_t)sb;
+    const int rc = buf.ensure(bytes + SGX_IF_PAD);
     if (rc != SGX_OK) return rc;
-    tmp.d = narrowed;
-    {
-        const int grid = (int)((n_samp + 255) / 256 < 8192 ? (n_samp + 255) / 256 : 8192);
-        if (narrow8) f32_narrow_kernel<int8_t><<<grid, 256, 0, c->stream>>>(x, n_samp, k, tmp.d);
-        else f32_narrow_kernel<short><<<grid, 256, 0, c->stream>>>(x, n_samp, k, reinterpret_cast<short*>(tmp.d));
-        e = hipMemsetAsync(tmp.d + tmp.n, 0, SGX_IF_PAD, c->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            sgx_set_error("float32 record narrowing: %s", hipGetErrorString(e));
-            rc = SGX_E_HIP;
-        }
-    }
-    if (rc == SGX_OK) {
-        // Byte p of the float file is byte (p - F) sb / 4 of the integer record, F = the window's first file byte.  The
-        // integer kernels place a channel at skipNumberOfBytes + codePhase - rec_file_offset, so the channels are handed
-        // over with skipNumberOfBytes folded into codePhase... which is a double and may not be changed; instead the
-        // record offset is chosen so that channel i lands on sample (p0_i - first) / 4: that needs one offset per
-        // channel, so the channels are tracked with codePhase' = (p0_i - first) / 4 * sb and skip' = offset' = 0.
-        std::vector<sgx_chan_init> hc((size_t)n_ch);
-        for (int i = 0; i < n_ch; ++i) {
-            hc[(size_t)i] = ch[i];
-            if (ch[i].prn == 0) continue;
-            const long long p0 = skip + (long long)ch[i].codePhase - rec_file_offset;
-            hc[(size_t)i].codePhase = (double)((p0 - first) / 4 * sb);
-        }
-        rc = sgx_track_kind(c, &tmp, 0, hc.data(), n_ch, ms, out, ms_done, narrow8 ? SGX_DT_INT8 : SGX_DT_INT16, 0, 0.0);
-        if (rc == SGX_OK || rc == SGX_E_SILENT) {   // (a silent channel: out and ms_done are complete)
-            // absoluteSample is fid.tell() in BYTES of the float file (tracking.py:255): integer-record bytes * 4 / sb
-            // behind the window's first byte; the six correlator series carry the 2^k
-            const double unscale = ldexp(1.0, -k);
-            const double file0 = (double)(rec_file_offset + first);
-            for (int i = 0; i < n_ch; ++i) {
-                double* o = out + (size_t)i * SGX_NUM_SERIES * (size_t)ms;
-                if (ch[i].prn == 0) continue;
-                const int done = ms_done[i] < ms ? ms_done[i] : ms;
-                for (int t = 0; t < done; ++t) o[t] = o[t] * (4.0 / sb) + file0;
-                for (int s = 3; s <= 8; ++s)
-                    for (int t = 0; t < done; ++t) o[(size_t)s * ms + t] *= unscale;
-            }
-        }
-    }
-    return rc;
-}
-
-// ---- float64 records: the same latency-mode kernel on samples scaled by a power of two, after one scan of the window -------
-// [0]: largest |x| (the bits of a non-negative double order like integers), [1]: a sample that is not finite was seen,
-// [2]: the sum of |x| over the finite samples (a double; for a threshold only)
-__global__ __launch_bounds__(256) void f64_scan_kernel(const double* __restrict__ x, long long n, unsigned long long* __restrict__ st) {
-    unsigned long long mx = 0ull, bad = 0ull;
-    double sa = 0.0;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long u = (unsigned long long)__double_as_longlong(x[i]) & 0x7FFFFFFFFFFFFFFFull;
-        if ((u >> 52) == 0x7FFull) bad = 1ull;
-        else {
-            mx = u > mx ? u : mx;
-            sa += __longlong_as_double((long long)u);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long omx = __shfl_down(mx, off), ob = __shfl_down(bad, off);
-        mx = omx > mx ? omx : mx;
-        bad |= ob;
-        sa += __shfl_down(sa, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(&st[0], mx);
-        if (bad) atomicOr(&st[1], 1ull);
-        atomicAdd(reinterpret_cast<double*>(&st[2]), sa);
-    }
-}
-
-int sgx_track_float64(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch,
-                      int32_t ms, double* out, int32_t* ms_done) {
-    SGX_CHECK_ARG(c && r && ch && out && ms_done);
-    SGX_CHECK_ARG(n_ch >= 1 && ms >= 1);
-    const long long skip = (long long)c->s.skipNumberOfBytes;
-    auto generic = [&](double fs) {
-        return sgx_track_kind(c, r, rec_file_offset, ch, n_ch, ms, out, ms_done, SGX_DT_FLOAT64, skip, fs);
-    };
-    long long first = -1, last = -1;
-    for (int i = 0; i < n_ch; ++i) {
-        if (ch[i].prn == 0) continue;
-        const long long p0 = skip + (long long)ch[i].codePhase - rec_file_offset;
-        if (p0 < 0 || p0 % 8 != 0) return generic(0.0);   // (before the record: reported there; inside a sample: per-sample kernel)
-        first = (first < 0 || p0 < first) ? p0 : first;
-        last = p0 > last ? p0 : last;
-    }
-    if (first < 0) return generic(0.0);
-    const long long n_code = c->n_code;
-    long long end = last + ((long long)ms * (n_code + 64) + n_code) * 8;
-    if (end > (long long)r->n) end = (long long)r->n;
-    end &= ~7ll;
-    const long long n_samp = (end - first) / 8;
-    if (n_samp <= 0) return generic(0.0);
-    {
-        const int rq = sgx_if_require(r, (size_t)end);
-        if (rq != SGX_OK) return rq;
-    }
-    SGX_HIP(hipSetDevice(c->device));
-    DevBuf<unsigned long long> d_st;
-    const int rc = d_st.ensure(3 * sizeof(unsigned long long));
-    if (rc != SGX_OK) return rc;
-    unsigned long long h_st[3] = {0ull, 0ull, 0ull};
-    hipError_t e = hipMemsetAsync(d_st, 0, sizeof(h_st), c->stream);
-    if (e == hipSuccess) {
-        const int grid = (int)((n_samp + 255) / 256 < 4096 ? (n_samp + 255) / 256 : 4096);
-        f64_scan_kernel<<<grid, 256, 0, c->stream>>>(reinterpret_cast<const double*>(r->d + first), n_samp, d_st);
-        e = hipMemcpyAsync(h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    const float* x = reinterpret_cast<const float*>(S.d) + first;
+    const int grid = (int)std::min((n + 255) / 256, 8192ll);
+    if (narrow8) f32_narrow_kernel<int8_t><<<grid, 256, 0, c->stream>>>(x, n, k, buf.get());
+    else f32_narrow_kernel<short><<<grid, 256, 0, c->stream>>>(x, n, k, reinterpret_cast<short*>(buf.get()));
+    hipError_t e = hipMemsetAsync(buf.get() + bytes, 0, SGX_IF_PAD, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) {
-        sgx_set_error("float64 record scan: %s", hipGetErrorString(e));
+        sgx_set_error("float32 record narrowing: %s", hipGetErrorString(e));
         return SGX_E_HIP;
     }
-    if (h_st[1]) return generic(0.0);        // NaN or infinite samples: numpy's arithmetic carries them, so does the per-sample kernel
-    double mx, sum_abs;
-    memcpy(&mx, &h_st[0], sizeof(mx));
-    memcpy(&sum_abs, &h_st[2], sizeof(sum_abs));
-    return generic(scale_for(mx, sum_abs, n_samp));
+    S.pos_a = 4.0 / sb;
+    S.pos_b = (double)(S.file_off + first * 4);
+    S.sums = ldexp(1.0, -k);
+    S.d = buf.get();
+    S.n = (long long)bytes;
+    S.rec = nullptr;
+    S.kind = narrow8 ? SGX_DT_INT8 : SGX_DT_INT16;
+    S.file_off = 0;
+    for (TrkChan& h : S.hc)
+        if (h.prn != 0) h.pos0 -= first;
+    return SGX_OK;
+}
+
+int sgx_track_float(sgx_ctx* c, const sgx_if* r, int64_t rec_file_offset, const sgx_chan_init* ch, int32_t n_ch, int32_t ms,
+                    double* out, int32_t* ms_done, int kind) {
+    const int sb = sgx_dt_bytes(kind);
+    const TrkEnv E = sgx_trk_env();
+    TrkSource S;   // (as it lies: the per-sample kernel)
+    int rc = sgx_trk_source(S, c->s, r, (long long)rec_file_offset, ch, n_ch, kind);
+    if (rc != SGX_OK) return rc;
+    DevBuf<int8_t> narrowed;   // (the memory of a narrowed window, for the length of the call)
+    long long first, end;
+    if (f_window(S, sb, ms, (long long)c->n_code, first, end)) {
+        rc = sgx_if_require(r, (size_t)(end * sb));   // (a streaming record: the scan needs every sample)
+        if (rc != SGX_OK) return rc;
+        SGX_HIP(hipSetDevice(c->device));
+        FScan scan;
+        rc = f_scan(c, S.d + first * sb, end - first, kind, scan);
+        if (rc != SGX_OK) return rc;
+        const FRoute R = f_route(scan, end - first, kind, E, sgx_trk_multi(c->s) != 0);
+        if (R.way == FRoute::TYPED) {
+            S.float_typed = true;
+            S.fscale = R.fscale;
+            S.sums = 1.0 / R.fscale;
+        } else if (R.way != FRoute::PER_SAMPLE) {
+            rc = f_narrow(c, S, first, end - first, R.k, R.way == FRoute::NARROW8, narrowed);
+            if (rc != SGX_OK) return rc;
+        }
+    }
+    return sgx_track_source(c, S, E, ch, n_ch, ms, out, ms_done);
 }

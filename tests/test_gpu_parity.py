@@ -1681,6 +1681,62 @@ def test_track_float32_record_by_exact_narrowing(tmp_path):
     assert ctx.timing()["track_kernel"] in (2, 5)          # (the typed kernels ran)
 
 
+def test_track_float32_narrowed_window_behind_a_record_offset():
+    """Exact narrowing away from the easy case: the record handle holds the float file from byte 4096 on, the channels are
+    listed from the last start byte to the first (the narrowed window starts at the LAST one's), and the second of the four
+    is off.  Positions are bytes of the whole file exactly as the oracle's; the run is the int8 record's own, positions
+    x 4 + skipNumberOfBytes; the off channel keeps the initial values of every series."""
+    m = pkg()
+    ms, skip, off = 10, 8192, 4096
+    s = m.Settings()
+    s.dataType, s.numberOfChannels, s.msToProcess, s.skipNumberOfBytes = 'float32', 4, float(ms), skip
+    n = s.samplesPerCode
+    rec8 = m.synth.generate(m.synth.Scene.default(), m.synth.record_length(n, ms))
+    a8 = orc.acquire(orc.OracleSettings(), rec8[:11 * n])
+    ch = orc.pre_run(orc.OracleSettings(numberOfChannels=3), a8)
+    order = np.argsort(-np.asarray(ch["codePhase"], dtype=np.int64), kind="stable")
+    prn, freq = np.asarray(ch["PRN"])[order], np.asarray(ch["acquiredFreq"], dtype=np.float64)[order]
+    cp = np.asarray(ch["codePhase"], dtype=np.int64)[order] - 1          # sample of rec8 each channel starts on
+    raw = np.concatenate([np.zeros(skip // 4, "<f4"), rec8.astype("<f4")])
+    so = orc.OracleSettings(numberOfChannels=3, msToProcess=float(ms), dataType='float32', skipNumberOfBytes=skip)
+    want = orc.stack_series(orc.track(so, dict(PRN=prn, acquiredFreq=freq, codePhase=(cp * 4).astype(np.float64),
+                                               status=['T'] * 3), raw))
+    on = [0, 2, 3]
+
+    def chans(phase):
+        rows = [(int(prn[i]), float(freq[i]), float(phase[i])) for i in range(3)]
+        return [rows[0], (0, 0.0, 0.0), rows[1], rows[2]]
+
+    ctx = m.engine.get_context(s, 0)
+    got, done = ctx.track(ctx.upload_bytes(raw.view(np.int8)[off:]), chans(cp * 4), ms, rec_file_offset=off,
+                          data_type=m._native.DT_FLOAT32)
+    assert ctx.timing()["track_kernel"] in (2, 5)          # (narrowed: the typed integer kernels ran)
+    assert done.tolist() == [ms, 0, ms, ms]
+    assert np.array_equal(got[on, 0], want[:, 0]) and _trk_err(got[on], want) < TRK_TOL
+    s8 = m.Settings()
+    s8.numberOfChannels, s8.msToProcess = 4, float(ms)
+    ctx8 = m.engine.get_context(s8, 0)
+    got8, done8 = ctx8.track(ctx8.upload(rec8), chans(cp), ms, data_type=m._native.DT_INT8)
+    assert done8.tolist() == [ms, 0, ms, ms]
+    assert np.array_equal(got[1], got8[1])                 # the off channel: zeros and +Inf as the int8 call leaves them
+    assert np.array_equal(got[on, 0], got8[on, 0] * 4 + skip)
+
+
+def test_a_channel_before_the_record_is_refused_alike_for_every_sample_type():
+    """A channel whose start byte lies in front of the record's first byte: SGX_E_RANGE with the same words whatever the
+    sample type, and before anything is launched (the kernel time of the last call stays what it was)."""
+    m = pkg()
+    s = m.Settings()
+    ctx = m.engine.get_context(s, 0)
+    rec = ctx.upload_bytes(np.zeros(65536, np.int8))
+    for dt in (m._native.DT_INT8, m._native.DT_INT16, m._native.DT_FLOAT32, m._native.DT_FLOAT64):
+        before = ctx.timing()["track_ms"]
+        with pytest.raises(m._native.SgxError, match=r"channel 0 starts at file byte \d+, before the record") as e:
+            ctx.track(rec, [(1, 0.0, 96.0)], 10, rec_file_offset=4096, data_type=dt)
+        assert e.value.code == m._native.SGX_E_RANGE, dt
+        assert ctx.timing()["track_ms"] == before, dt
+
+
 def test_track_any_sample_type_against_the_oracle(tmp_path):
     """Settings.dataType is whatever numpy dtype the settings name (tracking.py:154): records of arbitrary float32 and
     float64 values on the latency-mode kernel (scaled by a power of two on conversion, sgx_trk2.hip) and - float16, the
